@@ -9,10 +9,15 @@ genes with M_g ~ Uniform{20..80}; genes shard across ranks with no data-path col
 only collectives are one broadcast of the null model and one gather of the per-gene result records per step.
 
 Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the engine's stream around the
-sufficient-statistics kernel; `cpu_baseline` times the CPU oracle (literal SKAT-O + folded SKAT + CMC + Zeggini,
-reference release flags -O2 -msse2) on a sample of genes of the same workload — 1 thread alone, then one process
-per core — and `parity` compares the oracle's numbers for those genes with the GPU records of the timed run
-(the second half of the BASELINE metric: p-value max-abs-diff).
+sufficient-statistics kernel.  A plain run sets up, warms up, times `--steps` steps and prints the line; everything
+else it can measure runs only with `--full`, after the timed region: `cpu_baseline` times the CPU oracle (literal
+SKAT-O + folded SKAT + CMC + Zeggini, reference release flags -O2 -msse2) on a sample of genes of the same workload —
+1 thread alone, then one process per core — and `parity` compares the oracle's numbers for those genes with the GPU
+records of the timed run (the second half of the BASELINE metric: p-value max-abs-diff); `from_host`,
+`resident_bed`, `from_host_cpp` and `drop_in` are the secondary rates of the other hand-offs.
+
+`--dump-outputs DIR` writes the per-gene records of the last timed step (rank 0's genes), one float64 array per
+record field, as DIR/<field>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts N ranks itself (torch.distributed.run as a child
 process, before this process touches the GPU).
@@ -427,6 +432,24 @@ def resident_bed_rate(eng, blocks, Ms, N, rows_resident=8192, genes=6144, per_ca
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(path, records):
+    """--dump-outputs: every field of the GeneResult records the caller of rvt_run_blocks_async received for the last timed
+    step, one float64 array per field in gene order (DIR/<field>.npy; `gene_id` names the rows).  Above 64 MB in all,
+    a fixed seeded sample of the genes, kept in gene order."""
+    os.makedirs(path, exist_ok=True)
+    recs = np.frombuffer(records, dtype=np.dtype(rvtests_amd.GeneResult))
+    names = [f[0] for f in rvtests_amd.GeneResult._fields_]
+    rows = np.arange(len(recs))
+    max_rows = DUMP_BYTES_MAX // (8 * len(names))
+    if len(rows) > max_rows:
+        rows = np.sort(np.random.default_rng(20260002).choice(len(rows), max_rows, replace=False))
+    for name in names:
+        np.save(os.path.join(path, name + ".npy"), recs[name][rows].astype(np.float64))
+
+
 def spawn_ranks(n):
     """`--gpus n` without a launcher: start n ranks as a child torch.distributed.run BEFORE this process touches the
     GPU, pass its output through and return its exit code."""
@@ -464,9 +487,14 @@ def main():
     ap.add_argument("--dosage-float", action="store_true",
                     help="with --dosage: float-precision dosages as an 8-bit BGEN file gives them (multiples of 2^-31), no lattice "
                          "stated; the engine is told so (rvt_set_dosage_float) and tries the float-digit int8 kernel for M <= 64")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the secondary figures: from-host and resident .bed rates, the "
+                         "CPU baselines with the in-run parity against the oracle, the C++ caller and the drop-in runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the per-gene records of the last timed step as DIR/<field>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity")
     ap.add_argument("--no-literal-baseline", action="store_true", help="skip the literal N x N SKAT timing (~20 s of CPU)")
-    ap.add_argument("--no-from-host", action="store_true", help="skip the from-host (PCIe-inclusive) secondary rates")
+    ap.add_argument("--no-from-host", action="store_true", help="with --full: skip the from-host (PCIe-inclusive) secondary rates")
     ap.add_argument("--cpu-genes", type=int, default=24,
                     help="genes of the batch run through the CPU oracle after the timed region (baseline + parity)")
     ap.add_argument("--tests", type=int, default=rvtests_amd.TEST_ALL)
@@ -613,10 +641,13 @@ def main():
         dist.all_gather(allm, mine)
         per_rank = [[float(t[0]), float(t[1])] for t in allm]
 
+    secondary = args.full and world == 1          # the figures after the timed region (one GPU, --full)
     if rank == 0:
         total_genes = world * args.genes * args.steps
         value = total_genes / elapsed
         out0 = batches[(args.steps - 1) % NSLOT]["out"] if args.steps else batch["out"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out0)
         T = args.tests
         # (genes whose requested kernel tests all came back with a p-value; the flags of the line below name what was asked)
         ok = sum(1 for r in out0 if (r.skat_ok or not T & rvtests_amd.TEST_SKAT) and (r.skato_ok or not T & rvtests_amd.TEST_SKATO))
@@ -706,12 +737,12 @@ def main():
             "davies_terms_per_gene": float(np.mean([r.davies_terms for r in out0])),
             "warmup_ms_per_step": warm_ms,
         }
-        if world == 1 and not args.no_from_host and not binary:
+        if secondary and not args.no_from_host and not binary:
             try:
                 line["from_host"] = from_host_rates(eng, blocks, Ms, afs, N)
             except Exception as e:                        # (secondary figures must never cost the line)
                 line["from_host"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_from_host and not binary and not args.dosage and args.tests == rvtests_amd.TEST_ALL:
+        if secondary and not args.no_from_host and not binary and not args.dosage and args.tests == rvtests_amd.TEST_ALL:
             try:
                 line["resident_bed"] = resident_bed_rate(eng, blocks, Ms, N)
             except Exception as e:
@@ -723,7 +754,7 @@ def main():
             line["c2_gather_ms_per_step_by_rank"] = [1e3 * r[1] for r in per_rank]
             line["gathered_records_last_step"] = last_gather["n"]
             line["gathered_ids_in_order"] = last_gather["ordered"]
-        if world == 1 and not args.no_cpu_baseline and args.cpu_genes > 0:
+        if secondary and not args.no_cpu_baseline and args.cpu_genes > 0:
             # ---- CPU baseline + parity on a sample of the batch's genes (after the timed region) ------------------
             try:
                 ncpu = len(os.sched_getaffinity(0))
@@ -789,7 +820,7 @@ def main():
                 line["parity"] = parity_summary(recs, out0)
                 line["pvalue_max_abs_diff"] = line["parity"]["pvalue_max_abs_diff"]
                 line["q_max_rel_diff"] = line["parity"]["q_max_rel_diff"]
-        if world == 1 and not args.no_from_host and not binary:
+        if secondary and not args.no_from_host and not binary:
             # the same hand-off from a C++ caller (tools/host_feed_bench: one thread, rvt_submit_gene_* per gene — what the
             # drop-in adapters do), as a child process AFTER this process has closed its engine: two contexts on one device
             # oversubscribe its hardware queues (every context creates its streams with queues of their own) — the

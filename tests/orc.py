@@ -13,6 +13,30 @@ c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int)
 
 
+REF_GOLDEN = os.path.join(ROOT, "tests", "golden", "ref_live.npz")
+_ref_golden = None
+
+
+def ref_outputs(key, live, available):
+    """The compiled reference fragment's outputs for one test, a dict of arrays: `live()` where the fragment is built
+    (`available`), checked against the committed vector of the same calls; elsewhere that vector itself
+    (tests/golden/ref_live.npz, written by tests/golden/make_ref_live_golden.py from the same `live` functions)."""
+    global _ref_golden
+    if _ref_golden is None:
+        with np.load(REF_GOLDEN, allow_pickle=False) as z:
+            _ref_golden = {k: z[k] for k in z.files}
+    want = {k.split("/", 1)[1]: v for k, v in _ref_golden.items() if k.split("/", 1)[0] == key}
+    assert want, "no committed vector '%s' in %s" % (key, REF_GOLDEN)
+    if not available:
+        return want
+    got = {k: np.asarray(v) for k, v in live().items()}
+    assert sorted(got) == sorted(want), (key, sorted(got), sorted(want))
+    for k, v in got.items():
+        assert v.shape == want[k].shape and np.array_equal(v, want[k], equal_nan=v.dtype.kind == "f"), \
+            "%s/%s: the committed vector no longer matches the live reference" % (key, k)
+    return got
+
+
 def _dp(a):
     return a.ctypes.data_as(c_double_p)
 

@@ -5,7 +5,6 @@ import json
 import os
 
 import numpy as np
-import pytest
 
 import hc
 import orc
@@ -48,32 +47,55 @@ def test_davies_bit_exact_and_liu_close():
     assert nd > 400
 
 
-def test_negative_q_is_one_or_fault():
-    """The invariant behind the device's Q < 0 shortcut, checked on the live reference when it is available."""
-    if orc.ref() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here); covered by the committed fixture")
+def _negative_q_cases():
     rng = np.random.default_rng(5)
     for _ in range(3000):
         r = int(rng.integers(2, 90))
         lam = np.sort(rng.gamma(rng.choice([0.3, 1, 5]), 1.0, size=r) * 10 ** rng.uniform(-8, 8))[::-1].copy()
         c = -lam.sum() * 10 ** rng.uniform(-16, 6)
-        assert orc.davies(lam, c, "ref") in (1.0, -1.0)
+        yield lam, c
 
 
-def test_oracle_matches_live_reference():
-    if orc.ref() is None:
-        pytest.skip("oracle/_ref not built")
+def _ref_negative_q():
+    return {"davies": [orc.davies(lam, c, "ref") for lam, c in _negative_q_cases()]}
+
+
+def test_negative_q_is_one_or_fault():
+    """The invariant behind the device's Q < 0 shortcut, on the live reference where it is built, else on its committed
+    outputs (tests/golden/ref_live.npz); the oracle's restatement gives the same values."""
+    want = orc.ref_outputs("negative_q", _ref_negative_q, orc.ref() is not None)["davies"]
+    assert len(want) == 3000
+    for (lam, c), w in zip(_negative_q_cases(), want):
+        assert w in (1.0, -1.0)
+        assert orc.davies(lam, c) == w
+
+
+def _live_reference_cases():
     rng = np.random.default_rng(9)
     for _ in range(1500):
         r = int(rng.integers(2, 80))
         lam = np.sort(rng.gamma(0.5, 1.0, size=r) * rng.choice([1, 1e-3, 10]))[::-1].copy()
         Q = lam.sum() * rng.choice([0.01, 0.1, 0.5, 1, 2, 5, 10, 50]) * rng.uniform(0.5, 1.5)
-        assert orc.davies(lam, Q) == orc.davies(lam, Q, "ref")
-        a, b = orc.liu(lam, Q), orc.liu(lam, Q, "ref")
+        yield lam, Q
+
+
+def _ref_live_reference():
+    qf = [orc.qf(lam, Q, "ref") for lam, Q in _live_reference_cases()]
+    return {"davies": [orc.davies(lam, Q, "ref") for lam, Q in _live_reference_cases()],
+            "liu": [orc.liu(lam, Q, "ref") for lam, Q in _live_reference_cases()],
+            "qf_value": [q[0] for q in qf], "qf_fault": [q[1] for q in qf], "qf_trace": [q[2] for q in qf]}
+
+
+def test_oracle_matches_live_reference():
+    """The oracle's Davies / Liu / qf() against the reference's (live where built, else its committed outputs)."""
+    ref = orc.ref_outputs("live_reference", _ref_live_reference, orc.ref() is not None)
+    assert len(ref["davies"]) == 1500
+    for i, (lam, Q) in enumerate(_live_reference_cases()):
+        assert orc.davies(lam, Q) == ref["davies"][i]
+        a, b = orc.liu(lam, Q), ref["liu"][i]
         assert abs(a - b) <= 1e-11 * abs(b) + 2e-15
         v1, f1, t1 = orc.qf(lam, Q)
-        v2, f2, t2 = orc.qf(lam, Q, "ref")
-        assert v1 == v2 and f1 == f2 and np.array_equal(t1, t2)
+        assert v1 == ref["qf_value"][i] and f1 == ref["qf_fault"][i] and np.array_equal(t1, ref["qf_trace"][i])
 
 
 def test_product_form_davies_matches_term_by_term():
@@ -127,52 +149,62 @@ def _counter_columns(rng, N, M):
     return np.asfortranarray(G)
 
 
-def test_counter_af_against_the_compiled_reference_counter():
-    """orc_counter_af (the weights of every kernel test, quirk #4) vs src/GenotypeCounter.h as compiled."""
-    R = orc.ref_counter()
-    if R is None:
-        pytest.skip("oracle/_ref/libref_counter.so not built (no /root/reference here)")
+def _counter_cases():
     rng = np.random.default_rng(11)
     for N, M in ((1, 3), (7, 5), (500, 12), (4001, 9)):
         G = _counter_columns(rng, max(N, 2), max(M, 5))[:N, :M].copy(order="F") if N >= 2 else np.asfortranarray(
             rng.choice([0.0, 1.0, 2.0, -9.0], size=(N, M)))
+        yield N, M, G
+
+
+def _ref_counter_outputs(cols):
+    R = orc.ref_counter()
+    outs = []
+    for col in cols:
+        out = np.zeros(8)
+        col = np.ascontiguousarray(col, dtype=np.float64)
+        R.ref_counter(orc._dp(col), len(col), orc._dp(out))
+        outs.append(out)
+    return np.array(outs)
+
+
+def _ref_counter_af():
+    return {"out": _ref_counter_outputs([G[:, j] for N, M, G in _counter_cases() for j in range(M)])}
+
+
+def test_counter_af_against_the_compiled_reference_counter():
+    """orc_counter_af (the weights of every kernel test, quirk #4) vs src/GenotypeCounter.h as compiled (live where built,
+    else its committed outputs)."""
+    outs = iter(orc.ref_outputs("counter_af", _ref_counter_af, orc.ref_counter() is not None)["out"])
+    for N, M, G in _counter_cases():
         af = orc.counter_af(G)
         for j in range(M):
-            out = np.zeros(8)
+            out = next(outs)
             col = np.ascontiguousarray(G[:, j])
-            R.ref_counter(orc._dp(col), N, orc._dp(out))
             assert af[j] == out[0], (N, j, af[j], out[0])       # same additions in the same order: bit-identical
             ok = (col >= 0) & (col <= 2.0)
             assert out[7] == N - ok.sum() and out[4] + out[5] + out[6] == ok.sum()
             assert 0.0 <= out[3] <= 1.0
+    assert next(outs, None) is None
+
+
+def _ref_hwe():
+    return {"out": _ref_counter_outputs([np.full(10, -9.0), np.array([1.0] * 42 + [0.0] * 49 + [2.0] * 9),
+                                         np.array([1.0] * 2 + [0.0] * 69 + [2.0] * 29)])}
 
 
 def test_hwe_exact_test_known_values():
-    """SNPHWE through GenotypeCounter::getHWE: the all-missing convention and a textbook table."""
-    R = orc.ref_counter()
-    if R is None:
-        pytest.skip("oracle/_ref/libref_counter.so not built")
-    out = np.zeros(8)
-    col = np.full(10, -9.0)
-    R.ref_counter(orc._dp(col), 10, orc._dp(out))
+    """SNPHWE through GenotypeCounter::getHWE: the all-missing convention and a textbook table (live where built, else
+    the committed outputs)."""
+    outs = orc.ref_outputs("hwe", _ref_hwe, orc.ref_counter() is not None)["out"]
+    out = outs[0]                                   # ten missing calls
     assert out[3] == 0.0 and out[0] == 0.0 and out[2] == 0.0
     # 57 het / 14 hom-alt / 50 hom-ref ... in HWE proportions the p-value is large; a het deficit gives a small one
-    col = np.array([1.0] * 42 + [0.0] * 49 + [2.0] * 9)
-    R.ref_counter(orc._dp(col), len(col), orc._dp(out))
-    assert out[3] > 0.9
-    col = np.array([1.0] * 2 + [0.0] * 69 + [2.0] * 29)
-    R.ref_counter(orc._dp(col), len(col), orc._dp(out))
-    assert out[3] < 1e-15
+    assert outs[1][3] > 0.9
+    assert outs[2][3] < 1e-15
 
 
-def test_metacov_window_walk_on_the_reference_ring_pool():
-    """MetaCovTest keeps its window in RingMemoryPool chunks that are allocated per kept variant and released in queue
-    order (src/Model.h:3956-3990, quirk #20).  Drive the same walk over the REAL pool — chunk payload = the variant's
-    index, so a stale or moved chunk shows — and require the (head, marker) pairs it visits to be exactly the finite
-    entries of orc_metacov's band, through several doublings of the pool."""
-    R = orc.ref_counter()
-    if R is None:
-        pytest.skip("oracle/_ref/libref_counter.so not built")
+def _ring_walk_inputs():
     rng = np.random.default_rng(3)
     N, V, d = 60, 300, 2
     G = rng.choice([0.0, 1.0, 2.0], size=(N, V), p=[0.7, 0.25, 0.05])
@@ -186,6 +218,13 @@ def test_metacov_window_walk_on_the_reference_ring_pool():
     window = 700                                   # > 64 kept variants in a window: the pool has to grow (64 -> 128 -> ...)
     rc, kept, cov, row_end, xz, zz = orc.metacov(G, chrom, pos, X, y, 0, window)
     assert rc == 0
+    return V, chrom, pos, window, kept, cov, row_end
+
+
+def _ref_ring_walk():
+    """The window walk over the REAL pool: the (head, marker) pairs it visits and how often the pool grew."""
+    R = orc.ref_counter()
+    V, chrom, pos, window, kept, cov, row_end = _ring_walk_inputs()
     pool = R.ref_ring_new(4, 2)                    # small start: growth while head > tail is exercised (case 2 / 4)
     queue, pairs, grew = [], set(), 0
     try:
@@ -210,7 +249,19 @@ def test_metacov_window_walk_on_the_reference_ring_pool():
         assert R.ref_ring_size(pool) == 0
     finally:
         R.ref_ring_delete(pool)
-    assert grew >= 4
+    return {"pairs": np.array(sorted(pairs), dtype=np.int32).reshape(-1, 2), "grew": np.array([grew])}
+
+
+def test_metacov_window_walk_on_the_reference_ring_pool():
+    """MetaCovTest keeps its window in RingMemoryPool chunks that are allocated per kept variant and released in queue
+    order (src/Model.h:3956-3990, quirk #20).  Drive the same walk over the REAL pool — chunk payload = the variant's
+    index, so a stale or moved chunk shows — and require the (head, marker) pairs it visits to be exactly the finite
+    entries of orc_metacov's band, through several doublings of the pool (live where the pool is built, else the walk's
+    committed record)."""
+    walk = orc.ref_outputs("ring_walk", _ref_ring_walk, orc.ref_counter() is not None)
+    V, chrom, pos, window, kept, cov, row_end = _ring_walk_inputs()
+    pairs = {(int(h), int(j)) for h, j in walk["pairs"]}
+    assert walk["grew"][0] >= 4
     want = {(h, j) for h in range(V) for j in range(h, V) if np.isfinite(cov[h, j])}
     assert pairs == want and len(want) > 5000
     assert all((row_end[h] == max(j for (hh, j) in want if hh == h)) for h in range(V) if kept[h])
@@ -241,11 +292,13 @@ def test_search_memo_changes_nothing_and_stays_small():
 
 # ---- the reference's Permutation stop rule, ModelParser and floatToString compiled where they lie (oracle/_ref/libref_host.so) ----
 def _ref_host():
+    """The compiled host pieces of the reference, or None where they are not built (the tests then read their committed
+    outputs)."""
     import ctypes as C
     import os
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libref_host.so")
     if not os.path.exists(path):
-        pytest.skip("oracle/_ref/libref_host.so not built (needs the reference tree: make -C oracle ref)")
+        return None
     L = C.CDLL(path)
     L.ref_permutation_run.restype = C.c_double
     L.ref_permutation_run.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
@@ -262,18 +315,8 @@ def _ref_host():
     return L
 
 
-def test_permutation_stop_rule_matches_the_compiled_reference():
-    """The oracle's adaptive stop rule (orc_perm_stop_run = the PermStop that orc_skat_permute runs, which the engine's counters
-    are compared with in tests/test_gpu_perm.py) against the reference's own Permutation class (src/Permutation.h:48-158) on
-    the same sequences of statistics: permutations used, counters and p-value identical — early stops, ties with the observed
-    value, nPerm exhausted, alpha = 0 and an empty list included."""
-    import ctypes as C
-    R = _ref_host()
-    O = orc.lib()
-    O.orc_perm_stop_run.restype = C.c_double
-    O.orc_perm_stop_run.argtypes = R.ref_permutation_run.argtypes
+def _permutation_cases():
     rng = np.random.default_rng(20)
-    n_early = 0
     for trial in range(400):
         nperm = int(rng.choice([0, 1, 10, 100, 1000, 10000]))
         alpha = float(rng.choice([0.0, 0.001, 0.05, 0.5, 1.0]))
@@ -281,13 +324,38 @@ def test_permutation_stop_rule_matches_the_compiled_reference():
         n = int(rng.integers(0, nperm + 5))
         stats = rng.normal(size=max(n, 1)) + rng.choice([-1.0, 0.0, 1.5])
         stats[rng.random(max(n, 1)) < 0.05] = obs                 # ties
-        sp = stats.ctypes.data_as(C.POINTER(C.c_double))
-        a, b = (C.c_int * 3)(), (C.c_int * 3)()
-        pr = R.ref_permutation_run(nperm, alpha, obs, sp, n, a)
-        po = O.orc_perm_stop_run(nperm, alpha, obs, sp, n, b)
-        assert list(a) == list(b) and pr == po, (trial, nperm, alpha, list(a), list(b))
+        yield nperm, alpha, obs, stats, n
+
+
+def _ref_permutation():
+    import ctypes as C
+    R = _ref_host()
+    counts, pvalues = [], []
+    for nperm, alpha, obs, stats, n in _permutation_cases():
+        a = (C.c_int * 3)()
+        pvalues.append(R.ref_permutation_run(nperm, alpha, obs, stats.ctypes.data_as(C.POINTER(C.c_double)), n, a))
+        counts.append(list(a))
+    return {"counts": np.array(counts, dtype=np.int32), "pvalue": pvalues}
+
+
+def test_permutation_stop_rule_matches_the_compiled_reference():
+    """The oracle's adaptive stop rule (orc_perm_stop_run = the PermStop that orc_skat_permute runs, which the engine's counters
+    are compared with in tests/test_gpu_perm.py) against the reference's own Permutation class (src/Permutation.h:48-158) on
+    the same sequences of statistics: permutations used, counters and p-value identical — early stops, ties with the observed
+    value, nPerm exhausted, alpha = 0 and an empty list included (live where built, else its committed outputs)."""
+    import ctypes as C
+    ref = orc.ref_outputs("permutation", _ref_permutation, _ref_host() is not None)
+    O = orc.lib()
+    O.orc_perm_stop_run.restype = C.c_double
+    O.orc_perm_stop_run.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
+    n_early = 0
+    for trial, (nperm, alpha, obs, stats, n) in enumerate(_permutation_cases()):
+        b = (C.c_int * 3)()
+        po = O.orc_perm_stop_run(nperm, alpha, obs, stats.ctypes.data_as(C.POINTER(C.c_double)), n, b)
+        a, pr = list(ref["counts"][trial]), ref["pvalue"][trial]
+        assert a == list(b) and pr == po, (trial, nperm, alpha, a, list(b))
         n_early += a[0] < min(n, nperm)
-    assert n_early > 50                                            # the rule did stop early in many trials
+    assert trial == 399 and n_early > 50                           # the rule did stop early in many trials
 
 
 def _driver(args, stdin=None):
@@ -302,64 +370,107 @@ def _driver(args, stdin=None):
     return p.stdout.splitlines()
 
 
-def test_model_parser_matches_the_compiled_reference():
-    """The adapters' ModelParser (csrc/host/ModelFitterGpu.cpp) against the reference's compiled src/ModelParser.cpp: return code,
-    model name, number of parameters, hasTag / value and the assign() conversions (int through a double: "1e4" is 10 000;
-    case folding; ':' and ',' separators; flags without a value; empty pieces; a missing ']')."""
+PARSER_SPECS = ["skat", "Skat[nPerm=1e4:alpha=0.05,beta1=1:beta2=25]", "SKATO", "cmc[]", "kbac[nPerm=10000,alpha=0.001]",
+                "famSkat[Beta1=0.5]", "cov[windowSize=1000000:gwama]", "score[]", "skat[nperm=5", "vt[a=1::b=2]", "x[=3]",
+                "x[a==3,b=]", "analytic[k=1.9,K=2.7]", "Skat[nPerm=-3.7]", "skat[nperm=abc]", "m[,]", "m[a]", "M[A=Hello:b=WORLD]",
+                "[a=1]", "x]"]
+PARSER_TAGS = ["nperm", "nPerm", "alpha", "beta1", "BETA2", "windowsize", "gwama", "a", "b", "k", "", "nosuch"]
+
+
+def _ref_parser():
+    """Per spec: return code, model name, number of parameters; per tag of an accepted spec: hasTag, value ("<null>" for
+    none), and the double / int / bool conversions with the defaults -7.5 / -7 / 0."""
     import ctypes as C
     R = _ref_host()
-    specs = ["skat", "Skat[nPerm=1e4:alpha=0.05,beta1=1:beta2=25]", "SKATO", "cmc[]", "kbac[nPerm=10000,alpha=0.001]",
-             "famSkat[Beta1=0.5]", "cov[windowSize=1000000:gwama]", "score[]", "skat[nperm=5", "vt[a=1::b=2]", "x[=3]", "x[a==3,b=]",
-             "analytic[k=1.9,K=2.7]", "Skat[nPerm=-3.7]", "skat[nperm=abc]", "m[,]", "m[a]", "M[A=Hello:b=WORLD]", "[a=1]", "x]"]
-    tags = ["nperm", "nPerm", "alpha", "beta1", "BETA2", "windowsize", "gwama", "a", "b", "k", "", "nosuch"]
-    for spec in specs:
+    rc, names, npars, has, vals, dv, iv, bv = [], [], [], [], [], [], [], []
+    for spec in PARSER_SPECS:
         name = C.create_string_buffer(256)
         npar = C.c_int()
-        rc = R.ref_parser_parse(spec.encode(), name, 256, C.byref(npar))
-        got = _driver(["--parse", spec] + tags)
+        rc.append(R.ref_parser_parse(spec.encode(), name, 256, C.byref(npar)))
+        names.append(name.value.decode())
+        npars.append(npar.value)
+        row = [[], [], [], [], []]
+        for tag in PARSER_TAGS:
+            if rc[-1] != 0:                                       # (a rejected spec: nothing is asked of it)
+                for r, v in zip(row, (0, "", 0.0, 0, 0)):
+                    r.append(v)
+                continue
+            buf = C.create_string_buffer(256)
+            row[0].append(R.ref_parser_has(tag.encode()))
+            row[1].append(buf.value.decode() if R.ref_parser_value(tag.encode(), buf, 256) else "<null>")
+            row[2].append(R.ref_parser_double(tag.encode(), -7.5))
+            row[3].append(R.ref_parser_int(tag.encode(), -7))
+            row[4].append(R.ref_parser_bool(tag.encode(), 0))
+        for dst, r in zip((has, vals, dv, iv, bv), row):
+            dst.append(r)
+    return {"rc": rc, "name": np.array(names, dtype=str), "npar": npars, "has": has, "value": np.array(vals, dtype=str),
+            "double": dv, "int": iv, "bool": bv}
+
+
+def test_model_parser_matches_the_compiled_reference():
+    """The adapters' ModelParser (csrc/host/ModelFitterGpu.cpp) against the reference's compiled src/ModelParser.cpp (live where
+    built, else its committed outputs): return code, model name, number of parameters, hasTag / value and the assign()
+    conversions (int through a double: "1e4" is 10 000; case folding; ':' and ',' separators; flags without a value; empty
+    pieces; a missing ']')."""
+    ref = orc.ref_outputs("parser", _ref_parser, _ref_host() is not None)
+    for i, spec in enumerate(PARSER_SPECS):
+        got = _driver(["--parse", spec] + PARSER_TAGS)
+        rc = int(ref["rc"][i])
         assert int(got[0]) == rc, spec
         if rc != 0:
             continue                                              # (a rejected spec: the models are not created)
-        assert got[1] == name.value.decode() and int(got[2]) == npar.value, (spec, got[:3], name.value, npar.value)
-        for tag, line in zip(tags, got[3:]):
+        assert got[1] == ref["name"][i] and int(got[2]) == ref["npar"][i], (spec, got[:3], ref["name"][i], ref["npar"][i])
+        for k, (tag, line) in enumerate(zip(PARSER_TAGS, got[3:])):
             has, val, dv, iv, bv = line.split("\t")
-            assert int(has) == R.ref_parser_has(tag.encode()), (spec, tag)
-            buf = C.create_string_buffer(256)
-            if R.ref_parser_value(tag.encode(), buf, 256):
-                assert val == buf.value.decode(), (spec, tag)
-            else:
-                assert val == "<null>"
-            assert float(dv) == R.ref_parser_double(tag.encode(), -7.5), (spec, tag)
-            assert int(iv) == R.ref_parser_int(tag.encode(), -7), (spec, tag)
-            assert int(bv) == R.ref_parser_bool(tag.encode(), 0), (spec, tag)
+            assert int(has) == ref["has"][i][k], (spec, tag)
+            assert val == ref["value"][i][k], (spec, tag)
+            assert float(dv) == ref["double"][i][k], (spec, tag)
+            assert int(iv) == ref["int"][i][k], (spec, tag)
+            assert int(bv) == ref["bool"][i][k], (spec, tag)
 
 
-def test_float_to_string_matches_the_compiled_reference():
-    """floatToString (base/TypeConversion.h:97-105: a stringstream at precision 6, what Result prints the CMC / Zeggini / covZZ
-    numbers with) compiled from the reference against the adapters' floatToString and against C's "%g" (formatG, what the SKAT /
-    MetaCov rows use): the three agree on every finite value tried, as doubles and through float."""
-    import ctypes as C
-    R = _ref_host()
+def _format_values():
+    """The values floatToString is asked about: as doubles, and (those a float can hold) through float."""
     rng = np.random.default_rng(3)
     xs = [0.0, -0.0, 1.0, -1.0, 0.5, 1e-5, 9.99999e-5, 1e-4, 0.000123456789, 123456.0, 1234567.0, 999999.5, 1e6, 1e15, 1e16, 1e-300,
           5e-324, 1.7976931348623157e308, 0.1, 2.5e-7, 100.0, 1e5, 99999.95, 0.05, 3.14159265358979, 2.0 / 3.0]
     xs += list(10.0 ** rng.uniform(-320, 308, 3000) * rng.choice([-1.0, 1.0], 3000))
     xs += list(rng.normal(size=2000)) + list(np.round(rng.normal(size=500) * 1000, 2))
-    for f32 in (False, True):
-        if f32:
-            vals = [float(np.float32(x)) for x in xs if abs(x) < 3e38]
-            lines = _driver(["--format"], "".join("f:%r\n" % v for v in vals))
-        else:
-            vals = [float(x) for x in xs]
-            lines = _driver(["--format"], "".join("%r\n" % v for v in vals))
-        assert len(lines) == len(vals)
-        buf = C.create_string_buffer(128)
-        for v, line in zip(vals, lines):
+    return [float(x) for x in xs], [float(np.float32(x)) for x in xs if abs(x) < 3e38]
+
+
+def _ref_format():
+    import ctypes as C
+    R = _ref_host()
+    f64, f32 = _format_values()
+    buf = C.create_string_buffer(128)
+    out = {}
+    for key, vals, fn in (("f64", f64, R.ref_float_to_string), ("f32", f32, lambda v, b, n: R.ref_float_to_string_f32(C.c_float(v), b, n))):
+        strs = []
+        for v in vals:
+            fn(v, buf, 128)
+            strs.append(buf.value.decode())
+        out[key] = np.array(strs, dtype=str)
+    return out
+
+
+def test_float_to_string_matches_the_compiled_reference():
+    """floatToString (base/TypeConversion.h:97-105: a stringstream at precision 6, what Result prints the CMC / Zeggini / covZZ
+    numbers with) compiled from the reference (live where built, else its committed outputs) against the adapters'
+    floatToString and against C's "%g" (formatG, what the SKAT / MetaCov rows use): the three agree on every finite value
+    tried, as doubles and through float."""
+    ref = orc.ref_outputs("float_to_string", _ref_format, _ref_host() is not None)
+    f64, f32 = _format_values()
+    for key, vals in (("f64", f64), ("f32", f32)):
+        fmt = "f:%r\n" if key == "f32" else "%r\n"
+        lines = _driver(["--format"], "".join(fmt % v for v in vals))
+        assert len(lines) == len(vals) == len(ref[key])
+        for v, line, want in zip(vals, lines, ref[key]):
             fts, g = line.split("\t")
-            if f32:
-                R.ref_float_to_string_f32(C.c_float(v), buf, 128)
-            else:
-                R.ref_float_to_string(v, buf, 128)
-            ref = buf.value.decode()
-            assert fts == ref, (v, fts, ref)
-            assert g == "%g" % v == ref, (v, g, ref)               # (the stream at precision 6 prints what %g prints)
+            assert fts == want, (v, fts, want)
+            assert g == "%g" % v == want, (v, g, want)             # (the stream at precision 6 prints what %g prints)
+
+
+# the reference's outputs per test, as tests/golden/make_ref_live_golden.py records them
+REF_LIVE = {"negative_q": _ref_negative_q, "live_reference": _ref_live_reference, "counter_af": _ref_counter_af, "hwe": _ref_hwe,
+            "ring_walk": _ref_ring_walk, "permutation": _ref_permutation, "parser": _ref_parser, "float_to_string": _ref_format}

@@ -84,22 +84,36 @@ def test_male_hemizygous_rules_match_golden_and_reference():
     assert d.tolist() == [0.5, 0.5, 1.5]
 
 
-def test_oracle_matches_compiled_reference_exhaustively():
+INT_SUBFIELDS = [(b"0/1:17:40", 1), (b"0/1:17:40", 2), (b"0/1:17", 2), (b"0/1:.:3", 1), (b"0/1: 7x", 1), (b"0/1:-4", 1)]
+
+
+def _ref_exhaustive():
+    """The reference's genotype codes of every column up to five bytes (index 0 / 1 / 2), of vcfgen.GT_POOL (index 0),
+    and the integer subfields the GD / GQ filters read."""
     R = orc.ref_vcf()
-    if R is None:
-        pytest.skip("reference tree not present: the golden vector covers this machine")
+    return {"codes": np.array([[R.ref_vcf_column_genotype(col, len(col), idx) for idx in (0, 1, 2)]
+                               for col in enumerate_columns(5)], dtype=np.int8),
+            "pool": np.array([R.ref_vcf_column_genotype(col, len(col), 0) for col in vcfgen.GT_POOL], dtype=np.int8),
+            "ints": [R.ref_vcf_column_int(col, len(col), idx) for col, idx in INT_SUBFIELDS]}
+
+
+REF_LIVE = {"vcf_exhaustive": _ref_exhaustive}
+
+
+def test_oracle_matches_compiled_reference_exhaustively():
+    """Every column up to five bytes against the reference's parsers (live where built, else their committed outputs)."""
+    ref = orc.ref_outputs("vcf_exhaustive", _ref_exhaustive, orc.ref_vcf() is not None)
     n = 0
-    for col in enumerate_columns(5):
+    for col, want in zip(enumerate_columns(5), ref["codes"]):
         for idx in (0, 1, 2):
-            assert orc.vcf_column_genotype(col, idx) == R.ref_vcf_column_genotype(col, len(col), idx), (col, idx)
+            assert orc.vcf_column_genotype(col, idx) == want[idx], (col, idx)
             n += 1
-    assert n > 150000
-    for col in vcfgen.GT_POOL:                       # bytes >= 0x80 compare as negative chars on the host
-        assert orc.vcf_column_genotype(col, 0) == R.ref_vcf_column_genotype(col, len(col), 0), col
+    assert n == 3 * len(ref["codes"]) and n > 150000
+    assert len(ref["pool"]) == len(vcfgen.GT_POOL)
+    for col, want in zip(vcfgen.GT_POOL, ref["pool"]):     # bytes >= 0x80 compare as negative chars on the host
+        assert orc.vcf_column_genotype(col, 0) == want, col
     # the integer subfields the GD / GQ filters read (atoi of the NUL-terminated subfield; "." when absent)
-    for col, idx, want in [(b"0/1:17:40", 1, 17), (b"0/1:17:40", 2, 40), (b"0/1:17", 2, 0), (b"0/1:.:3", 1, 0),
-                           (b"0/1: 7x", 1, 7), (b"0/1:-4", 1, -4)]:
-        assert R.ref_vcf_column_int(col, len(col), idx) == want
+    assert list(ref["ints"]) == [17, 40, 0, 0, 7, -4]
 
 
 def test_filters_and_record_walk():

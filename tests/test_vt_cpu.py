@@ -31,7 +31,17 @@ def test_phiinv_round_trip():
         assert abs(0.5 * erfc(-x / sqrt(2)) - p) <= 1e-14 * max(p, 1e-300) + 1e-16
 
 
-@pytest.mark.parametrize("K,T", [(2, 1.0), (3, 2.2), (8, 2.5), (25, 3.0), (60, 2.0), (60, 4.0)])
+def _ref_mvn_band(R, T):
+    return {"inform_p_err": [orc.ref_mvn_band(R, T, seed) for seed in (1, 7)]}
+
+
+BAND_CASES = [(2, 1.0), (3, 2.2), (8, 2.5), (25, 3.0), (60, 2.0), (60, 4.0)]
+# the reference's outputs per case, as tests/golden/make_ref_live_golden.py records them
+REF_LIVE = {"mvn_band_%d" % i: (lambda K=K, T=T: _ref_mvn_band(_nested_cor(np.random.default_rng(100 + K), K), T))
+            for i, (K, T) in enumerate(BAND_CASES)}
+
+
+@pytest.mark.parametrize("K,T", BAND_CASES)
 def test_band_probability_three_ways(K, T):
     rng = np.random.default_rng(100 + K)
     R = _nested_cor(rng, K)
@@ -39,10 +49,11 @@ def test_band_probability_three_ways(K, T):
     p_orc, e_orc = orc.mvn_band(R, T, points=2048)
     assert abs(p_dev - p_orc) <= e_dev + e_orc + 1e-5      # two independent deterministic rules
     assert e_dev < (5e-4 if K <= 25 else 2e-3)
-    if orc.ref_mvt() is None:
-        pytest.skip("reference MVTDST not built on this machine")
-    for seed in (1, 7):
-        inform, p_ref, e_ref = orc.ref_mvn_band(R, T, seed)
+    # the reference's MVTDST on the same band (live where built, else its committed outputs)
+    key = "mvn_band_%d" % BAND_CASES.index((K, T))
+    ref = orc.ref_outputs(key, REF_LIVE[key], orc.ref_mvt() is not None)["inform_p_err"]
+    assert len(ref) == 2
+    for inform, p_ref, e_ref in ref:
         # inform = 1: the reference's own error estimate exceeds abseps = 1e-3 — MvtNorm::compute_Band then returns -1
         # and AnalyticVT prints NA (high-dimensional cases with a moderate threshold)
         assert inform in (0, 1) and (inform == 1) == (e_ref > 1e-3)

@@ -8,7 +8,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench_line.json"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o k -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-from-host > "$OUT/kt.log" 2>&1
 cp "$OUT"/kt/k_kernel_stats.csv "$OUT/kernel_stats.csv" 2>/dev/null || find "$OUT/kt" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;

@@ -51,7 +51,7 @@ python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-from-host --missin
 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-from-host --samples 50000 --m-lo 30 --m-hi 30 --genes 1024 --tests 1 > "$OUT/bench_config1.json" 2>/dev/null
 python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-from-host --samples 50000 --m-lo 30 --m-hi 30 --genes 1024 --tests 1 > "$OUT/bench_config1_100steps.json" 2>/dev/null
 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-from-host --trait binary --samples 200000 > "$OUT/bench_config3_binary.json" 2>/dev/null
-python3 bench.py --steps 20 --warmup 5 --no-from-host --dosage > "$OUT/bench_dosage.json" 2>/dev/null
+python3 bench.py --full --steps 20 --warmup 5 --no-from-host --dosage > "$OUT/bench_dosage.json" 2>/dev/null
 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-from-host --dosage --dosage-lattice 0 > "$OUT/bench_dosage_fp64.json" 2>/dev/null
 stats dosage python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-from-host --dosage
 ls -la "$OUT"

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 B="--trait binary --samples 200000"
-python3 bench.py $B --steps 40 --warmup 8 > "$OUT/bench_config3.json" 2> "$OUT/bench.err"
+python3 bench.py $B --full --steps 40 --warmup 8 > "$OUT/bench_config3.json" 2> "$OUT/bench.err"
 tail -c 300 "$OUT/bench_config3.json"
 python3 bench.py $B --steps 40 --warmup 8 --missing-frac 0 --no-cpu-baseline --no-from-host > "$OUT/bench_config3_missing_none.json" 2>> "$OUT/bench.err"
 python3 bench.py $B --steps 40 --warmup 8 --missing-frac 1.0 --no-cpu-baseline --no-from-host > "$OUT/bench_config3_missing_all.json" 2>> "$OUT/bench.err"

@@ -7,7 +7,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_r4
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 tail -c 300 "$OUT/bench_line.json"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o k -- python3 bench.py --no-cpu-baseline --no-from-host > "$OUT/kt.log" 2>&1
 find "$OUT/kt" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;

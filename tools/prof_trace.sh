@@ -8,7 +8,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/trace_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o k -- python3 bench.py --steps 10 --warmup 5 --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o k -- python3 bench.py --full --steps 10 --warmup 5 --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 find "$OUT/kt" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;
 TR=$(find "$OUT/kt" -name '*kernel_trace.csv' | head -1)
 python3 tools/timeline.py "$TR" --last-ms 200 --rows 120 > "$OUT/timeline.txt" 2>&1
