@@ -376,6 +376,23 @@ int rvt_cov_band_last_path(rvt_ctx* ctx);
  * Genotypes are taken as stored (imputed, NOT flipped), as MetaScoreTest does. */
 int rvt_score_block(rvt_ctx* ctx, const double* dG, int V, int* ok, double* ustat, double* vstat, double* effect,
                     double* effect_se, double* pvalue);
+/* SingleVariantWaldTest (src/Model.h:99-180): the full regression of y on A = [1, g_h, X_1 .. X_{d-1}] for each of the V
+ * imputed columns g_h of a device block (inputs and units as rvt_score_block; hard-call, mean-imputed and dosage columns).
+ *   quantitative: LinearRegression::FitLinearModel (regression/LinearRegression.cpp:20-84) in closed form from the score
+ *                 partials: SS = g'g - t'C^-1 t (C = X'X, t = X'g), beta_g = g'res / SS, beta_X = beta0 - C^-1 t beta_g,
+ *                 sigma1^2 = (RSS0 - (g'res)^2 / SS) / N (the MLE), covB = sigma1^2 (A'A)^-1; rounds = 0
+ *   binary:       LogisticRegression::FitLogisticModel(A, y, 100) (regression/LogisticRegression.cpp:279-336) replayed per
+ *                 variant on the device (wald_logistic.hip.h): beta = 0, Newton / IRLS, deviance on the p of the round with
+ *                 non-finite terms dropped (safeSum), converged when rounds > 1 and |deviance change| < 1e-3, failed on a
+ *                 deviance that is not FP_NORMAL or after 100 rounds, covB = D^-1 of the last executed round.  A D that is
+ *                 not positive definite is a failed fit (the reference's Eigen LLT does not report it).
+ * beta / se / pvalue: V x d, row-major; row h holds the reference's columns 1 .. d of A — g first, then the covariates (the
+ * intercept is not reported); se = sqrt(covB_kk), pvalue = chisq_Q(beta^2 / covB_kk, 1) (GetAsyPvalue).
+ * ok[h]: 1 fitted, 0 monomorphic (isMonomorphicMarker; nothing fitted), -1 failed fit.  rounds[h] (may be NULL): IRLS rounds
+ * executed (0 for a quantitative trait and a monomorphic site).  Values of rows with ok[h] != 1 are 0 / 0 / 1.
+ * Needs the null model of rvt_fit_null (beta0 and, for a binary trait, y come from it): RVT_E_STATE otherwise, also after a
+ * plain rvt_set_null.  Synchronous. */
+int rvt_wald_block(rvt_ctx* ctx, const double* dG, int V, int* ok, double* beta, double* se, double* pvalue, int* rounds);
 /* What MetaScoreTest::PrintNullModel prints (src/Model.h:3526-3542, 3737-3752): the estimates beta (d; NaN when the
  * model was installed by rvt_set_null, whose caller fitted it), the diagonal of their covariance (LinearRegression
  * covB = (X'X)^-1 sigma2, regression/LinearRegression.cpp:62-66; LogisticRegression covB = (X'WX)^-1,

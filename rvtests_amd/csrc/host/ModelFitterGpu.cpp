@@ -904,6 +904,167 @@ int MetaScoreTest::flush() {
   return scored || lastError.empty() ? 0 : -1;
 }
 
+// ---- SingleVariantWaldTest / SingleVariantScoreTest (src/Model.h:98-180, 259-377), unrelated samples ---------------------
+std::string GeneData::columnLabel() const {
+  if (!genotypeLabel.empty() || !site) return genotypeLabel;
+  return site->get("CHROM") + ":" + site->get("POS");
+}
+
+SingleVariantBlockTest::SingleVariantBlockTest() {
+  if (const char* e = getenv("RVT_SINGLE_BLOCK")) capacity = std::max(1, std::min(65536, atoi(e)));
+}
+SingleVariantBlockTest::~SingleVariantBlockTest() {
+  if (ctx && block) rvt_block_free(ctx, block);
+}
+int SingleVariantBlockTest::fit(GeneData* dc) {
+  if ((int)rows.size() >= capacity && used > 0 && flush()) return -1;
+  if (used >= capacity) {  // flush() could not run: no writeOutput() has named the output sink yet
+    lastError = getModelName() + ": the device block is full and no output was requested for its sites";
+    return -1;
+  }
+  rows.emplace_back();
+  Row& row = rows.back();
+  // X = [1, g, cov] is built (and its labels with it) before the monomorphic check (src/Model.h:117-129)
+  row.labels.push_back(dc->columnLabel());
+  for (int k = 0; k < dc->ncov; ++k) row.labels.push_back(k < (int)covLabel.size() ? covLabel[k] : std::string());
+  row.af = dc->M == 1 && dc->markerFrequency.size() == 1 ? dc->markerFrequency[0] : dc->counter.af;  // getMarkerFrequency(dc, 0)
+  if (dc->M != 1 || dc->N == 0) return -1;  // genotype.cols != 1
+  if (nSample >= 0 && nSample != dc->N) {
+    lastError = "Sample size changed";
+    return -1;
+  }
+  if (nSample >= 0 && (dc->phenotypeUpdated || dc->covariateUpdated) && used > 0) {
+    // rows tested so far belong to the previous null model: finish them before it is replaced
+    Row keep = row;
+    rows.pop_back();
+    if (flush()) return -1;
+    rows.push_back(keep);
+  }
+  ctx = GpuBroker::instance().contextWithNull(*dc, isBinaryOutcome(), &lastError);
+  if (!ctx) return -1;
+  if (nSample < 0) {
+    nSample = dc->N;
+    nCovariate = dc->ncov + 1;
+    if (rvt_block_alloc(ctx, capacity, &block)) {
+      lastError = rvt_last_error(ctx);
+      return -1;
+    }
+  }
+  // the caller overwrites the genotype buffer for the next site: copy the column into the device block now; whether the site
+  // is monomorphic is decided on the device when the block is processed
+  if (rvt_block_upload_columns(ctx, block, used, 1, dc->genotype)) {
+    lastError = rvt_last_error(ctx);
+    return -1;
+  }
+  rows.back().column = used++;
+  return 0;
+}
+void SingleVariantBlockTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
+  fout = fp;
+  if (rows.empty() || rows.back().written) rows.emplace_back();  // writeOutput without a fit()
+  rows.back().siteTab = siteInfo.valueTab();
+  rows.back().written = true;
+}
+void SingleVariantBlockTest::writeFootnote(TextSink* fp) {
+  fout = fp;
+  flush();
+}
+int SingleVariantBlockTest::flush() {
+  if (!fout) return 0;
+  ok.assign(std::max(used, 1), 0);
+  const bool ran = used > 0 && runBlock();
+  if (!ran) std::fill(ok.begin(), ok.end(), 0);
+  for (const Row& r : rows) {
+    if (!r.written) continue;  // main calls writeOutput after every fit(); a row never written is never printed
+    fout->write(formatSingleRow(r));
+  }
+  rows.clear();
+  used = 0;
+  return ran || lastError.empty() ? 0 : -1;
+}
+
+SingleVariantWaldTest::SingleVariantWaldTest() { modelName = "SingleWald"; }
+SingleVariantWaldTest::~SingleVariantWaldTest() {
+  if (fout) flush();
+}
+void SingleVariantWaldTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab() + "Test\tBeta\tSE\tPvalue\n");
+}
+bool SingleVariantWaldTest::runBlock() {
+  const size_t n = (size_t)used * (size_t)nCovariate;
+  beta.assign(n, 0.0);
+  se.assign(n, 0.0);
+  pv.assign(n, 0.0);
+  if (rvt_wald_block(ctx, block, used, ok.data(), beta.data(), se.data(), pv.data(), nullptr)) {
+    lastError = rvt_last_error(ctx);
+    return false;
+  }
+  return true;
+}
+std::string SingleVariantWaldTest::formatSingleRow(const Row& r) {
+  std::string out;
+  const int k = r.column;
+  const bool fitted = k >= 0 && ok[k] == 1;
+  for (size_t i = 0; i < r.labels.size(); ++i) {  // columns 1 .. of X (the intercept is skipped)
+    if (hideCovar && i > 0) continue;
+    if (fitted) {  // (Result::updateValue; never cleared in between)
+      const size_t o = (size_t)k * nCovariate + i;
+      lastBeta = floatToString(beta[o]);
+      lastSE = floatToString(se[o]);
+      lastP = floatToString(pv[o]);
+    }
+    out += r.siteTab + r.labels[i] + "\t" + lastBeta + "\t" + lastSE + "\t" + lastP + "\n";
+  }
+  return out;
+}
+
+SingleVariantScoreTest::SingleVariantScoreTest() { modelName = "SingleScore"; }
+SingleVariantScoreTest::~SingleVariantScoreTest() {
+  if (fout) flush();
+}
+void SingleVariantScoreTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab() + "AF\tU\tV\tSTAT\tDIRECTION\tEFFECT\tSE\tPVALUE\n");
+}
+bool SingleVariantScoreTest::runBlock() {
+  const size_t n = (size_t)used;
+  u.assign(n, 0.0);
+  v.assign(n, 0.0);
+  eff.assign(n, 0.0);
+  se.assign(n, 0.0);
+  pv.assign(n, 0.0);
+  std::vector<double> beta0(nCovariate), covb(nCovariate);
+  if (rvt_score_block(ctx, block, used, ok.data(), u.data(), v.data(), eff.data(), se.data(), pv.data()) ||
+      rvt_null_summary(ctx, beta0.data(), covb.data(), &sigma2)) {
+    lastError = rvt_last_error(ctx);
+    return false;
+  }
+  return true;
+}
+std::string SingleVariantScoreTest::formatSingleRow(const Row& r) {
+  const int k = r.column;
+  std::string na = "NA";
+  std::string U = na, V = na, STAT = na, DIR = na, EFF = na, SE = na, P = na;
+  if (k >= 0 && ok[k]) {
+    // rvt_score_block returns MetaScore's units: U_STAT = U / sigma2, V_STAT = SS / sigma2 (quantitative; the binary ones are
+    // LogisticRegressionScoreTest's own)
+    const bool bin = isBinaryOutcome();
+    const double s2 = bin ? 1.0 : sigma2;
+    const double uu = u[k] * s2, vv = bin ? v[k] : v[k] * s2 * s2;
+    const double ss = bin ? v[k] : v[k] * s2;  // SS
+    U = floatToString(uu);
+    V = floatToString(vv);
+    STAT = floatToString(bin ? uu * (1.0 / vv) * uu : uu * ((1.0 / ss) / s2) * uu);
+    if (uu != 0.0) DIR = uu > 0 ? "+" : "-";
+    if (vv > 0.0) {
+      EFF = floatToString(bin ? uu / vv : eff[k]);
+      SE = floatToString(bin ? 1.0 / std::sqrt(vv) : s2 / std::sqrt(vv));  // GetSEBeta (LinearRegressionScoreTest.cpp:365)
+    }
+    P = floatToString(pv[k]);
+  }
+  return r.siteTab + floatToString(r.af) + "\t" + U + "\t" + V + "\t" + STAT + "\t" + DIR + "\t" + EFF +
+         "\t" + SE + "\t" + P + "\n";
+}
+
 // ---- MetaCovTest ---------------------------------------------------------------------------------------------------------
 MetaCovTest::MetaCovTest(int windowSize_) : windowSize(windowSize_) {
   modelName = "MetaCov";
@@ -1228,6 +1389,15 @@ int ModelManager::create(const std::string& type, const std::string& modelList) 
         parser.assign("windowSize", &windowSize, 1000000);  // src/ModelManager.cpp:227-233
         model.push_back(new MetaCovTest(windowSize));
       } else {
+        lastError = "Unknown model name: " + modelName + " .";
+        return -1;
+      }
+    } else if (modelType == "single") {
+      if (modelName == "wald")  // src/ModelManager.cpp:54-98 (exact / firth / the family tests are not provided)
+        model.push_back(new SingleVariantWaldTest());
+      else if (modelName == "score")
+        model.push_back(new SingleVariantScoreTest());
+      else {
         lastError = "Unknown model name: " + modelName + " .";
         return -1;
       }

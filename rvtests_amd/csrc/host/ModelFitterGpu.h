@@ -58,6 +58,9 @@ struct GeneData {
   bool phenotypeUpdated = false, covariateUpdated = false;  // dc->isPhenotypeUpdated() / isCovariateUpdated()
   int64_t serial = 0;                 // increases with every dc.consolidate() (new gene)
   const SiteInfo* site = nullptr;     // dc->getResult(): CHROM / POS of the current site (single-variant models)
+  // the genotype column's label (genotype.GetColumnLabel(0), the "Test" column of SingleWald); empty: CHROM:POS of `site`
+  std::string genotypeLabel;
+  std::string columnLabel() const;
   // dc->hasKinship(), getKinshipUForAuto() / getKinshipSForAuto() (src/DataConsolidator.h:236-258): EigenMatrix holds
   // Eigen::MatrixXf, i.e. float, column-major N x N and N x 1
   const float* kinshipU = nullptr;
@@ -438,11 +441,81 @@ class MetaScoreTest : public ModelFitter {
   TextSink* fout = nullptr;
 };
 
+// `--single wald,score` for unrelated samples.  fit() is called once per variant (genotype.cols == 1) and copies the column
+// into a device block; a full block (or writeFootnote / the destructor) runs ONE device call over all of them and writes their
+// rows in file order, as MetaScoreTest does.  The null model is the device fit of rvt_fit_null.
+class SingleVariantBlockTest : public ModelFitter {
+ public:
+  ~SingleVariantBlockTest() override;
+  int fit(GeneData* dc) override;
+  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeFootnote(TextSink* fp) override;
+  std::vector<std::string> covLabel;  // covariate column labels (cov.GetColumnLabel(k)): set by the caller
+
+ protected:
+  struct Row {
+    std::string siteTab;
+    std::vector<std::string> labels;  // X.GetColumnLabel(1 ..): the genotype, then the covariates
+    double af = -1.0;
+    int column = -1;       // column in the device block; -1: not tested (fit() failed before the test)
+    bool written = false;  // writeOutput was called for this site
+  };
+  SingleVariantBlockTest();
+  // Rows still pending are written by the destructors of the concrete classes (flush() calls the virtual members below,
+  // which a base destructor could no longer reach); this one only frees the device block.
+  // the device call over the first `used` columns; false when it failed (its rows then print NA)
+  virtual bool runBlock() = 0;
+  virtual std::string formatSingleRow(const Row& r) = 0;
+  int flush();
+  int capacity = 1024;  // RVT_SINGLE_BLOCK
+  int64_t nSample = -1;
+  int nCovariate = 0;   // columns of the null X, intercept included
+  int used = 0;
+  rvt_ctx* ctx = nullptr;
+  double* block = nullptr;
+  std::vector<Row> rows;
+  std::vector<int> ok;
+  TextSink* fout = nullptr;
+};
+
+// SingleVariantWaldTest (src/Model.h:98-180): "Test Beta SE Pvalue", one row per column of X after the intercept (only the
+// genotype's with hideCovar = FLAG_hideCovar).  Like the reference's writeOutput this never clears its Result: a failed or
+// monomorphic site prints the Beta / SE / Pvalue the previous row left (NA before the first fitted row).
+class SingleVariantWaldTest final : public SingleVariantBlockTest {
+ public:
+  SingleVariantWaldTest();
+  ~SingleVariantWaldTest() override;
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  bool hideCovar = false;
+
+ private:
+  bool runBlock() override;
+  std::string formatSingleRow(const Row& r) override;
+  std::vector<double> beta, se, pv;
+  std::string lastBeta = "NA", lastSE = "NA", lastP = "NA";
+};
+
+// SingleVariantScoreTest (src/Model.h:259-377): "AF U V STAT DIRECTION EFFECT SE PVALUE" in LinearRegressionScoreTest's units
+// (U = g'res, V = SS sigma2, EFFECT = U / SS, SE = GetSEBeta) or LogisticRegressionScoreTest's (U, V, EFFECT = U / V,
+// SE = 1 / sqrt(V)), from rvt_score_block.
+class SingleVariantScoreTest final : public SingleVariantBlockTest {
+ public:
+  SingleVariantScoreTest();
+  ~SingleVariantScoreTest() override;
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+
+ private:
+  bool runBlock() override;
+  std::string formatSingleRow(const Row& r) override;
+  std::vector<double> u, v, eff, se, pv;
+  double sigma2 = 1.0;
+};
+
 // ---- ModelManager::create -----------------------------------------------------------------------------------------
 class ModelManager {
  public:
   ~ModelManager();
-  // type: "burden" | "kernel" | "meta"; modelList: "cmc,zeggini", "skat[nPerm=0:beta1=1],skato" or "cov[windowSize=500000]"
+  // type: "burden" | "kernel" | "vt" | "meta" | "single"; modelList: "cmc,zeggini", "skat[nPerm=0:beta1=1],skato" or "cov[windowSize=500000]"
   int create(const std::string& type, const std::string& modelList);
   const std::vector<ModelFitter*>& getModel() const { return model; }
   void setBinaryOutcome();

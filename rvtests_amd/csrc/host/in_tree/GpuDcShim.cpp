@@ -8,6 +8,10 @@
 #include "DataConsolidator.h"
 #include "GenotypeCounter.h"
 
+namespace parameter {
+extern bool FLAG_hideCovar;  // DECLARE_BOOL_PARAMETER(hideCovar), src/Model.h:55
+}
+
 namespace rvt_intree {
 
 // kinship decomposition as floats (EigenMatrix = Eigen::MatrixXf, regression/EigenMatrix.h:9-12): the one accessor that
@@ -52,6 +56,7 @@ void fillGeneData(DataConsolidator* dc, bool familyModel, const void* who, rvt_h
     gd->kinshipU = eigenMatrixData(dc->getKinshipUForAuto());
     gd->kinshipS = eigenMatrixData(dc->getKinshipSForAuto());
   }
+  if (G.cols == 1) gd->genotypeLabel = G.GetColumnLabel(0);  // (empty: the adapters use CHROM:POS)
   if (G.cols == 1) {  // single-variant models print the raw-genotype counters (src/Model.h:3211-3230)
     GenotypeCounter all, cases, ctrls;
     dc->countRawGenotype(0, &all);
@@ -61,6 +66,14 @@ void fillGeneData(DataConsolidator* dc, bool familyModel, const void* who, rvt_h
     dc->countRawGenotypeFromControl(0, &ctrls);
     gd->ctrlCounter = countsOf(ctrls);
   }
+}
+
+void configureSingle(rvt_host::SingleVariantBlockTest* m, DataConsolidator* dc) {
+  const Matrix& Z = dc->getCovariate();
+  m->covLabel.resize(Z.cols);
+  for (int k = 0; k < Z.cols; ++k) m->covLabel[k] = Z.GetColumnLabel(k);
+  if (rvt_host::SingleVariantWaldTest* w = dynamic_cast<rvt_host::SingleVariantWaldTest*>(m))
+    w->hideCovar = parameter::FLAG_hideCovar;  // --hide-covar (src/Main.cpp:419)
 }
 
 }  // namespace rvt_intree

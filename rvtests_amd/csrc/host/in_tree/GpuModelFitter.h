@@ -33,6 +33,12 @@ namespace rvt_intree {
 // Fills what the GPU models read from the caller (src/DataConsolidator.h getters).  Defined in GpuDcShim.cpp.
 void fillGeneData(DataConsolidator* dc, bool familyModel, const void* who, rvt_host::GeneData* gd);
 
+// The single-variant models: covariate column labels (cov.GetColumnLabel, the "Test" column of SingleWald) and
+// FLAG_hideCovar.  Defined in GpuDcShim.cpp; the other models take nothing.
+void configureSingle(rvt_host::SingleVariantBlockTest* m, DataConsolidator* dc);
+inline void configure(rvt_host::ModelFitter*, DataConsolidator*) {}
+inline void configure(rvt_host::SingleVariantBlockTest* m, DataConsolidator* dc) { configureSingle(m, dc); }
+
 class FileWriterSink : public rvt_host::TextSink {
  public:
   explicit FileWriterSink(FileWriter* f) : fp(f) {}
@@ -67,6 +73,7 @@ class GpuModel : public ::ModelFitter {
       impl.setQuantitativeOutcome();
     rvt_host::GeneData gd;
     fillGeneData(dc, familyAware, this, &gd);
+    configure(&impl, dc);
     gd.site = &lastSite;
     return impl.fit(&gd);
   }
@@ -121,6 +128,8 @@ typedef GpuModel<rvt_host::FamBurdenTest> FamBurdenTest;
 typedef GpuModel<rvt_host::MetaCovTest> MetaCovTest;      // new MetaCovTest(windowSize)            :238-247
 typedef GpuModel<rvt_host::MetaScoreTest> MetaScoreTest;  // new MetaScoreTest()
 typedef GpuModel<rvt_host::KbacTest> KBACTest;            // new KBACTest(nPerm, alpha)
+typedef GpuModel<rvt_host::SingleVariantWaldTest> SingleVariantWaldTest;    // new SingleVariantWaldTest()   :54-98
+typedef GpuModel<rvt_host::SingleVariantScoreTest> SingleVariantScoreTest;  // new SingleVariantScoreTest()
 // new AnalyticVT(AnalyticVT::UNRELATED) / new AnalyticVT(AnalyticVT::RELATED)   ModelManager.cpp:158-161
 class AnalyticVT : public GpuModel<rvt_host::AnalyticVTTest> {
  public:

@@ -28,6 +28,8 @@ int rvt_binding_check(DataConsolidator* dc, FileWriter* fp, const Result& siteIn
   parser.parse("cov[windowSize=500000]");
   parser.assign("windowSize", &windowSize, 1000000);
   model.push_back(new rvt_intree::MetaCovTest(windowSize));
+  model.push_back(new rvt_intree::SingleVariantWaldTest());  // src/ModelManager.cpp:54-98 (single)
+  model.push_back(new rvt_intree::SingleVariantScoreTest());
   model.push_back(new rvt_intree::MetaScoreTest());
   model.push_back(new rvt_intree::AnalyticVT(rvt_intree::AnalyticVT::UNRELATED));  // src/ModelManager.cpp:158-159
   model.push_back(new rvt_intree::KBACTest(nPerm, alpha));

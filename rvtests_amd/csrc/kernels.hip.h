@@ -1014,13 +1014,11 @@ static __global__ __launch_bounds__(256) void vt_direct_kernel(int m, int Mp, do
 // needed, so each slice streams once at the narrow-class rate); gene_id carries the slice's first column.
 // out: ustat | vstat | effect | se | pval (vt entries each); ok[h] = 1 when the site is polymorphic and SS > 0.
 #if !defined(RVT_K_SPLIT) || defined(RVT_K_ENGINE)
-static __global__ __launch_bounds__(64) void score_finish_kernel(const GeneDesc* __restrict__ genes,
-                                                          const NullConsts* __restrict__ ncp, int vt,
-                                                          double* __restrict__ out, int* __restrict__ ok) {
-  const GeneDesc gd = genes[blockIdx.x];
-  const int V = gd.M, h = threadIdx.x;
-  if (h >= V) return;
-  const long long col = gd.gene_id + h;
+// the column statistics of column h of a slice from its per-wave partials: polymorphic flag, g'g (shh), X'g (t, d entries)
+// and g'rr (u) — shared by the score and the linear Wald finishers
+static __device__ __forceinline__ int slice_column_sums(const GeneDesc& gd, int h, int d, double* shh_out, double* t,
+                                                        double* u_out) {
+  const int V = gd.M;
   double mn = INFINITY, mx = -INFINITY, cm = 0.0;
   unsigned long long orb = 0ull;
   // a hard-call slice that was handed back (gene_flags_hc_kernel) holds the general kernel's statistics
@@ -1040,10 +1038,7 @@ static __global__ __launch_bounds__(64) void score_finish_kernel(const GeneDesc*
     mn = fmin(mn, mu);
     mx = fmax(mx, mu);
   }
-  const int polymorphic = (mn == mx) ? 0 : 1;
-  const int d = ncp->d, binary = ncp->binary;
-  const double sigma2 = ncp->sigma2;
-  double shh = 0.0, u = 0.0, t[RVT_MAX_COV];
+  double shh = 0.0, u = 0.0;
   for (int k = 0; k < d; ++k) t[k] = 0.0;
   for (int p = 0; p < gd.n_wparts; ++p) {
     const double* row = gd.parts + (long long)p * gd.Mp * gd.Cp + (long long)h * gd.Cp;
@@ -1053,6 +1048,22 @@ static __global__ __launch_bounds__(64) void score_finish_kernel(const GeneDesc*
   }
   // the diagonal of the hard-call Gram tile is sum (H + 4m)^2 = sum H^2 + 16 cm, and H = 0 where masked
   if (cm > 0.0) shh = (shh - 16.0 * cm) + (mu * mu) * cm;
+  *shh_out = shh;
+  *u_out = u;
+  return (mn == mx) ? 0 : 1;
+}
+
+static __global__ __launch_bounds__(64) void score_finish_kernel(const GeneDesc* __restrict__ genes,
+                                                          const NullConsts* __restrict__ ncp, int vt,
+                                                          double* __restrict__ out, int* __restrict__ ok) {
+  const GeneDesc gd = genes[blockIdx.x];
+  const int V = gd.M, h = threadIdx.x;
+  if (h >= V) return;
+  const long long col = gd.gene_id + h;
+  const int d = ncp->d, binary = ncp->binary;
+  const double sigma2 = ncp->sigma2;
+  double shh, u, t[RVT_MAX_COV];
+  const int polymorphic = slice_column_sums(gd, h, d, &shh, t, &u);
   double q = 0.0;
   for (int k = 0; k < d; ++k) {
     double s = 0.0;
@@ -1084,6 +1095,64 @@ static __global__ __launch_bounds__(64) void score_finish_kernel(const GeneDesc*
   out[2LL * vt + col] = eff;
   out[3LL * vt + col] = se;
   out[4LL * vt + col] = pv;
+  ok[col] = fit;
+}
+#endif  // RVT_K_ENGINE
+
+// ---- SingleVariantWaldTest, quantitative trait (src/Model.h:99-180 over LinearRegression::FitLinearModel,
+// regression/LinearRegression.cpp:20-84 on A = [1, g, cov]): the full fit is a closed form of the score partials.
+// C = X'X (Cinv in NullConsts), t = X'g, s = g'g, u = g'res, RSS0 = sum res^2 of the null fit, beta0 its estimates:
+//   SS = s - t'C^-1 t,  beta_g = u / SS,  beta_X = beta0 - C^-1 t beta_g,  sigma1^2 = (RSS0 - u^2 / SS) / N (the MLE)
+//   var(beta_g) = sigma1^2 / SS,  var(beta_X,k) = sigma1^2 [C^-1 + C^-1 t t'C^-1 / SS]_kk,  p = chisq_Q(beta^2 / var, 1)
+// out: beta | se | pval, each vt x d (row of column `col`: g, then X_1 .. X_{d-1}; the intercept is not reported).
+// ok[col] = 1 fitted, 0 monomorphic, -1 SS <= 0 (A'A singular).
+struct WaldConsts {
+  double beta0[RVT_MAX_COV];
+};
+#if !defined(RVT_K_SPLIT) || defined(RVT_K_ENGINE)
+static __global__ __launch_bounds__(64) void wald_linear_finish_kernel(const GeneDesc* __restrict__ genes,
+                                                                const NullConsts* __restrict__ ncp, WaldConsts wc,
+                                                                int vt, double* __restrict__ out, int* __restrict__ ok) {
+  const GeneDesc gd = genes[blockIdx.x];
+  const int V = gd.M, h = threadIdx.x;
+  if (h >= V) return;
+  const long long col = gd.gene_id + h;
+  const int d = ncp->d;
+  double s, u, t[RVT_MAX_COV], w[RVT_MAX_COV];
+  const int polymorphic = slice_column_sums(gd, h, d, &s, t, &u);
+  double q = 0.0;
+  for (int k = 0; k < d; ++k) {
+    double a = 0.0;
+    for (int l = 0; l < d; ++l) a += ncp->Cinv[k * d + l] * t[l];
+    w[k] = a;
+    q += t[k] * a;
+  }
+  const double SS = s - q;
+  const int fit = !polymorphic ? 0 : (SS > 0.0 ? 1 : -1);
+  double* ob = out + col * d;
+  double* os = out + (long long)vt * d + col * d;
+  double* op = out + 2LL * vt * d + col * d;
+  if (fit == 1) {
+    const double bg = u / SS;
+    const double s1 = (ncp->rss - u * bg) / (double)ncp->N;
+    const double vg = s1 / SS;
+    ob[0] = bg;
+    os[0] = sqrt(vg);
+    op[0] = chisq_Q(bg * bg / vg, 1.0);
+    for (int k = 1; k < d; ++k) {
+      const double b = wc.beta0[k] - w[k] * bg;
+      const double v = s1 * (ncp->Cinv[k * d + k] + w[k] * w[k] / SS);
+      ob[k] = b;
+      os[k] = sqrt(v);
+      op[k] = chisq_Q(b * b / v, 1.0);
+    }
+  } else {
+    for (int k = 0; k < d; ++k) {
+      ob[k] = 0.0;
+      os[k] = 0.0;
+      op[k] = 1.0;
+    }
+  }
   ok[col] = fit;
 }
 #endif  // RVT_K_ENGINE

@@ -200,6 +200,8 @@ static void free_null(rvt_ctx* c) {
   c->d_dq = c->d_xq = nullptr;
   c->d_xscale = nullptr;
   c->hcx_ok = false;
+  if (c->d_null_y) hipFree(c->d_null_y);
+  c->d_null_y = nullptr;
   c->have_null = false;
 }
 
@@ -264,6 +266,7 @@ void rvt_destroy(rvt_ctx* c) {
     hipStreamDestroy(sl.stream);
   }
   if (c->d_nc) hipFree(c->d_nc);
+  if (c->d_wald_ws) hipFree(c->d_wald_ws);
   for (double* p : {c->d_S, c->d_u1, c->d_uxy, c->d_lmm_part, c->d_fX, c->d_frr, c->d_fv, c->d_fzeros,
                     c->d_fbeta, c->d_Gp, c->d_Gt, c->d_cX, c->d_cv, c->d_cr})
     if (p) hipFree(p);
@@ -1384,7 +1387,7 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
   if (cov && cov->score) {  // one gene per 16-column slice of the block: per-variant records only
     size_t vt = 0;
     for (int g = 0; g < n; ++g) vt += (size_t)Ms[g];
-    off_cov_bur = add(sizeof(double) * vt * 5);
+    off_cov_bur = add(sizeof(double) * vt * (cov->wald ? std::max(5, 3 * d) : 5));
     off_cov_ok = add(sizeof(int) * vt);
   } else if (cov) {
     const size_t V = (size_t)Ms[0];
@@ -1569,6 +1572,20 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
     for (int g = 0; g < n; ++g) vt += (size_t)Ms[g];
     double* d_bur = reinterpret_cast<double*>(base + off_cov_bur);
     int* d_ok = reinterpret_cast<int*>(base + off_cov_ok);
+    if (cov->wald) {  // rvt_wald_block, quantitative trait: the linear fits of the same columns
+      WaldConsts wc;
+      for (int k = 0; k < RVT_MAX_COV; ++k) wc.beta0[k] = cov->wald_beta0[k];
+      hipLaunchKernelGGL(wald_linear_finish_kernel, dim3((unsigned)n), dim3(64), 0, st, d_desc, c->d_nc, wc, (int)vt, d_bur,
+                         d_ok);
+      HIP_TRY(c, hipGetLastError());
+      const size_t vd8 = sizeof(double) * vt * (size_t)d;
+      HIP_TRY(c, hipMemcpyAsync(cov->wbeta, d_bur, vd8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(cov->wse, d_bur + vt * (size_t)d, vd8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(cov->wpval, d_bur + 2 * vt * (size_t)d, vd8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(cov->ok, d_ok, sizeof(int) * vt, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, sync_stream(st));
+      return RVT_OK;
+    }
     hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)n), dim3(64), 0, st, d_desc, c->d_nc, (int)vt, d_bur, d_ok);
     HIP_TRY(c, hipGetLastError());
     const size_t vb8 = sizeof(double) * vt;
@@ -2103,6 +2120,12 @@ int rvt_fit_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
   if (rcs == RVT_OK) {  // kept for rvt_null_summary (rvt_set_null alone leaves the estimates unknown)
     for (int a = 0; a < d; ++a) c->null_beta[a] = beta[a];
     c->have_null_beta = true;
+    if (binary) {  // the per-variant logistic fits of rvt_wald_block start from y (zero-padded to the block's ld)
+      const size_t vb = sizeof(double) * (size_t)c->null_ld;
+      HIP_TRY(c, hipMalloc((void**)&c->d_null_y, vb));
+      HIP_TRY(c, hipMemset(c->d_null_y, 0, vb));
+      HIP_TRY(c, hipMemcpy(c->d_null_y, y, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
+    }
   }
   return rcs;
 }

@@ -368,6 +368,10 @@ struct rvt_ctx {
   bool hc_enabled = true;     // RVT_HARDCALL=0 forces the general kernel (experiments)
   double null_beta[RVT_MAX_COV] = {};  // estimates of the model rvt_fit_null fitted
   bool have_null_beta = false;
+  double* d_null_y = nullptr;  // rvt_fit_null with a binary trait: y (ld doubles, zero-padded) for the per-variant Wald fits
+  // rvt_wald_block's work space (wald_logistic.hip.h): one grow-only allocation, never touched inside the round loop
+  char* d_wald_ws = nullptr;
+  size_t wald_ws_cap = 0;
   // streaming interface
   struct Pending {
     int64_t id;
@@ -758,5 +762,10 @@ struct CovOut {  // rvt_cov_block: host destinations
   bool uncentred = false;  // family mode: FastLMM::disableCenterGenotype (MetaFamBinary)
   double *effect = nullptr, *se = nullptr;
   int* ok = nullptr;
+  // rvt_wald_block, quantitative trait (score mode as well): the linear Wald fit of every column from the same partials
+  // (wald_linear_finish_kernel); beta / se / pval are V x d (row of column h: g, then the covariates), ok as ok[h] of the ABI
+  bool wald = false;
+  double wald_beta0[RVT_MAX_COV] = {};
+  double *wbeta = nullptr, *wse = nullptr, *wpval = nullptr;
 };
 

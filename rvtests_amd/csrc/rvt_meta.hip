@@ -6,6 +6,7 @@
 #include "rvt_engine_int.h"
 #include "gemm_f64.hip.h"
 #include "band_rows.hip.h"
+#include "wald_logistic.hip.h"
 
 // row slices of MetaCov's column pass (cov_hc_prep_kernel): a function of N alone, so that a column's sums are the same numbers
 // whether it is treated inside a block or alone behind its upload (rvt_block_upload_columns)
@@ -121,11 +122,9 @@ int rvt_kbac_blocks(rvt_ctx* c, int n, const double* const* dG, const int* M, co
 }
 
 // ---- MetaScore: single-variant score statistics of a block of variants (unrelated samples) -----------------
-int rvt_score_block(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat, double* vstat, double* effect,
-                    double* effect_se, double* pvalue) {
-  if (!c || !dG || V < 1 || !ok || !ustat || !vstat || !effect || !effect_se || !pvalue)
-    return fail(c, RVT_E_INVALID, "bad arguments");
-  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+// The block as slices through run_batch and the score finisher; with proto.wald the linear Wald finisher instead (outputs
+// d per column).  proto holds the host destinations of column 0.
+static int score_slices(rvt_ctx* c, const double* dG, int V, const CovOut& proto) {
   int rc = rvt_sync(c);  // processed synchronously
   if (rc) return rc;
   // Which slices START on the hard-call kernel: all of them unless the per-column flags of rvt_block_upload_columns say a
@@ -144,6 +143,7 @@ int rvt_score_block(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat,
   if (const char* e = getenv("RVT_SCORE_SLICE")) kSlice = std::max(1, std::min(64, atoi(e)));
   constexpr int kChunk = 256;  // slices per launch
   const int64_t ld = c->null_ld;
+  const size_t d = (size_t)c->nc.d;
   std::vector<double> af((size_t)kSlice * kChunk, 0.01);
   std::vector<rvt_gene_result> rs(kChunk);
   std::vector<unsigned char> shc(kChunk);
@@ -163,17 +163,135 @@ int rvt_score_block(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat,
       }
       shc[g] = hc ? 1 : 0;
     }
-    CovOut co;
+    CovOut co = proto;
     co.score = true;
     co.slice_hc = any_hc ? shc.data() : nullptr;
-    co.ok = ok + c0;
-    co.ustat = ustat + c0;
-    co.vstat = vstat + c0;
-    co.effect = effect + c0;
-    co.se = effect_se + c0;
-    co.pval = pvalue + c0;
+    co.ok = proto.ok + c0;
+    if (proto.wald) {
+      co.wbeta = proto.wbeta + (size_t)c0 * d;
+      co.wse = proto.wse + (size_t)c0 * d;
+      co.wpval = proto.wpval + (size_t)c0 * d;
+    } else {
+      co.ustat = proto.ustat + c0;
+      co.vstat = proto.vstat + c0;
+      co.effect = proto.effect + c0;
+      co.se = proto.se + c0;
+      co.pval = proto.pval + c0;
+    }
     rc = run_batch(c, n, ptr.data(), Ms.data(), af.data(), ids.data(), 0u, nullptr, rs.data(), nullptr, &co);
     if (rc) return rc;
+  }
+  return RVT_OK;
+}
+
+int rvt_score_block(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat, double* vstat, double* effect,
+                    double* effect_se, double* pvalue) {
+  if (!c || !dG || V < 1 || !ok || !ustat || !vstat || !effect || !effect_se || !pvalue)
+    return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  CovOut co;
+  co.ok = ok;
+  co.ustat = ustat;
+  co.vstat = vstat;
+  co.effect = effect;
+  co.se = effect_se;
+  co.pval = pvalue;
+  return score_slices(c, dG, V, co);
+}
+
+// ---- SingleVariantWaldTest: the full regression of every column of a block on [1, g, cov] ----------------------------
+int rvt_wald_block(rvt_ctx* c, const double* dG, int V, int* ok, double* beta, double* se, double* pvalue, int* rounds) {
+  using namespace rvt_wald;
+  if (!c || !dG || V < 1 || !ok || !beta || !se || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null || !c->have_null_beta) return fail(c, RVT_E_STATE, "no null model fitted by rvt_fit_null");
+  const NullConsts& nc = c->nc;
+  const int d = nc.d;
+  if (!nc.binary) {  // closed form of the score partials (wald_linear_finish_kernel)
+    CovOut co;
+    co.wald = true;
+    for (int k = 0; k < d; ++k) co.wald_beta0[k] = c->null_beta[k];
+    co.ok = ok;
+    co.wbeta = beta;
+    co.wse = se;
+    co.wpval = pvalue;
+    int rc = score_slices(c, dG, V, co);
+    if (rc == RVT_OK && rounds) std::fill(rounds, rounds + V, 0);
+    return rc;
+  }
+  if (!c->d_null_y) return fail(c, RVT_E_STATE, "no binary null model fitted by rvt_fit_null");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const int64_t N = nc.N, ld = c->null_ld;
+  const int P = d + 1, E = wald_entries(P);
+  const int n_chunks = (int)((N + kWaldChunk - 1) / kWaldChunk);
+  constexpr int kBatch = 4096;  // variants per launch chunk
+  const int Vb = std::min(V, kBatch);
+  // work space: beta | last deviance | beta, se, p out | chunk partials | iteration | two lists | ok | rounds | two counters
+  size_t off = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t o_beta = carve(sizeof(double) * (size_t)Vb * kWaldMaxP), o_last = carve(sizeof(double) * (size_t)Vb);
+  const size_t o_ob = carve(sizeof(double) * (size_t)Vb * d), o_os = carve(sizeof(double) * (size_t)Vb * d),
+               o_op = carve(sizeof(double) * (size_t)Vb * d);
+  const size_t o_part = carve(sizeof(double) * (size_t)Vb * n_chunks * E);
+  const size_t o_iter = carve(sizeof(int) * (size_t)Vb), o_l0 = carve(sizeof(int) * (size_t)Vb),
+               o_l1 = carve(sizeof(int) * (size_t)Vb), o_ok = carve(sizeof(int) * (size_t)Vb),
+               o_rounds = carve(sizeof(int) * (size_t)Vb), o_cnt = carve(sizeof(int) * 2);
+  if (c->wald_ws_cap < off) {
+    if (c->d_wald_ws) hipFree(c->d_wald_ws);
+    c->d_wald_ws = nullptr;
+    c->wald_ws_cap = 0;
+    HIP_TRY(c, hipMalloc((void**)&c->d_wald_ws, off));
+    c->wald_ws_cap = off;
+    if (const char* e = getenv("RVT_POISON")) HIP_TRY(c, hipMemset(c->d_wald_ws, atoi(e) & 0xff, off));
+  }
+  char* ws = c->d_wald_ws;
+  double* d_beta = reinterpret_cast<double*>(ws + o_beta);
+  double* d_last = reinterpret_cast<double*>(ws + o_last);
+  double* d_ob = reinterpret_cast<double*>(ws + o_ob);
+  double* d_os = reinterpret_cast<double*>(ws + o_os);
+  double* d_op = reinterpret_cast<double*>(ws + o_op);
+  double* d_part = reinterpret_cast<double*>(ws + o_part);
+  int* d_iter = reinterpret_cast<int*>(ws + o_iter);
+  int* d_list[2] = {reinterpret_cast<int*>(ws + o_l0), reinterpret_cast<int*>(ws + o_l1)};
+  int* d_ok = reinterpret_cast<int*>(ws + o_ok);
+  int* d_rounds = reinterpret_cast<int*>(ws + o_rounds);
+  int* d_cnt = reinterpret_cast<int*>(ws + o_cnt);
+  for (int c0 = 0; c0 < V; c0 += kBatch) {
+    const int nb = std::min(kBatch, V - c0);
+    HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(int) * 2, st));
+    hipLaunchKernelGGL(wald_logistic_init_kernel, dim3((unsigned)nb), dim3(256), 0, st, dG, (long long)ld, c0, (long long)N, d,
+                       d_beta, d_last, d_iter, d_list[0], d_cnt, d_ok, d_rounds, d_ob, d_os, d_op);
+    HIP_TRY(c, hipGetLastError());
+    int n_active = 0, cur = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_active, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    for (int round = 0; n_active > 0 && round < kWaldRounds; ++round) {
+      const int nxt = 1 - cur;
+      hipLaunchKernelGGL(wald_logistic_round_kernel, dim3((unsigned)((n_active + kWaldSlice - 1) / kWaldSlice), (unsigned)n_chunks),
+                         dim3(256), wald_round_lds_bytes(d), st, dG, (long long)ld, c0, c->d_X, c->d_null_y, (long long)N, d, d_list[cur], n_active,
+                         d_beta, n_chunks, d_part);
+      HIP_TRY(c, hipMemsetAsync(d_cnt + nxt, 0, sizeof(int), st));
+      hipLaunchKernelGGL(wald_logistic_step_kernel, dim3((unsigned)((n_active + 63) / 64)), dim3(64), 0, st, d_list[cur], n_active, d,
+                         n_chunks, d_part, d_beta, d_last, d_iter, d_list[nxt], d_cnt + nxt, d_ok, d_rounds, d_ob, d_os, d_op);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipMemcpyAsync(&n_active, d_cnt + nxt, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, sync_stream(st));
+      cur = nxt;
+    }
+    if (n_active > 0) return fail(c, RVT_E_HIP, "logistic Wald fits did not end in %d rounds", kWaldRounds);
+    const size_t vd = sizeof(double) * (size_t)nb * d;
+    HIP_TRY(c, hipMemcpyAsync(ok + c0, d_ok, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, st));
+    if (rounds) HIP_TRY(c, hipMemcpyAsync(rounds + c0, d_rounds, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(beta + (size_t)c0 * d, d_ob, vd, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(se + (size_t)c0 * d, d_os, vd, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(pvalue + (size_t)c0 * d, d_op, vd, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
   }
   return RVT_OK;
 }

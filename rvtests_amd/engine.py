@@ -238,6 +238,8 @@ def load_library():
     L.rvt_cov_block_fam.argtypes = [vp, vp, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]
     L.rvt_score_block.restype = C.c_int
     L.rvt_score_block.argtypes = [vp, vp, C.c_int, c_int_p] + [c_double_p] * 5
+    L.rvt_wald_block.restype = C.c_int
+    L.rvt_wald_block.argtypes = [vp, vp, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
     L.rvt_null_summary.restype = C.c_int
     L.rvt_null_summary.argtypes = [vp, c_double_p, c_double_p, c_double_p]
     L.rvt_score_block_fam.restype = C.c_int
@@ -895,6 +897,18 @@ class Engine:
         self._check(self.L.rvt_score_block(self.ctx, C.c_void_p(int(ptr)), int(V), ok.ctypes.data_as(c_int_p),
                                            *[_dp(a) for a in arr]))
         return dict(ok=ok, U=arr[0], V=arr[1], effect=arr[2], se=arr[3], p=arr[4])
+
+    def wald_block(self, ptr, V):
+        """SingleVariantWaldTest of the V columns of a device block on [1, g, cov] (after fit_null): dict of ok (1 fitted,
+        0 monomorphic, -1 failed), rounds, and beta / se / p as V x d arrays (column 0: g, then the covariates)."""
+        V = int(V)
+        d = int(self.d) if self.d else 0
+        ok = np.zeros(V, dtype=np.int32)
+        rounds = np.zeros(V, dtype=np.int32)
+        arr = [np.zeros((V, max(d, 1))) for _ in range(3)]
+        self._check(self.L.rvt_wald_block(self.ctx, C.c_void_p(int(ptr)), V, ok.ctypes.data_as(c_int_p),
+                                          *[_dp(a) for a in arr], rounds.ctypes.data_as(c_int_p)))
+        return dict(ok=ok, rounds=rounds, beta=arr[0], se=arr[1], p=arr[2])
 
     def score_block_fam(self, ptr, V, binary=0):
         """MetaFamQtl (binary=1: MetaFamBinary) statistics of the V raw columns of a device block (after set_kinship +
