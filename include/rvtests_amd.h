@@ -151,6 +151,16 @@ typedef struct rvt_fam_null {
   int brent_evals;          /* goal-function evaluations of the Brent refinement     */
 } rvt_fam_null;
 
+/* GrammarGamma null model (regression/GrammarGamma.cpp:29-121) */
+typedef struct rvt_grammar_null {
+  double delta;    /* sigma2_e / sigma2_g: Brent's minimum, or the best grid point at a boundary     */
+  double sigma2_g; /* SSR / N of the LAST likelihood evaluation                                      */
+  double gamma;    /* sum lambda / (lambda + delta) / sigma2_g / (N - 1)                               */
+  double ySigmaY;  /* resid' ty                                                                      */
+  int max_index;   /* best point of the 101-point delta grid                                         */
+  int brent_evals; /* goal-function evaluations of the Brent refinement                              */
+} rvt_grammar_null;
+
 /* accumulated device time per kernel family, measured with HIP events on the engine's stream */
 typedef struct rvt_timing {
   double ms_suffstat;   /* gene_suffstat_hc + gene_suffstat_mfma launches      */
@@ -415,6 +425,28 @@ int rvt_score_block_fam(rvt_ctx* ctx, const double* dG, int V, int binary, int* 
 /* Diagonal of FastLMM::GetNullCovB (regression/FastLMM.cpp:473-483) for MetaFamQtl::PrintNullModel; beta, SigmaG2 =
  * sigma2_g and SigmaE2 = sigma2_g * delta come from rvt_fit_fam_null's rvt_fam_null. */
 int rvt_fam_null_summary(rvt_ctx* ctx, double* covb_diag);
+/* SingleVariantFamilyLRT (src/Model.h:620-712): FastLMM::TestCovariate in its LRT branch (regression/FastLMM.cpp:150-212, model
+ * MLE) and FastLMM::GetAF (:362-400) of every raw column of a device block, after rvt_set_kinship + rvt_fit_fam_null; blocks
+ * wider than RVT_MAX_VARIANTS are walked in pieces.  Per column: the GLS of U'y on [U'X | U'g] at the null's delta,
+ * altSigma2 = altSSR / N, alt_loglik = -1/2 (N log 2 pi + sum log(|lambda| + delta) + N + N log altSigma2), null_loglik the
+ * same with the sigma2_g of the null fit, pvalue = chisq_Q(2 (alt - null), 1).  ok[h] = 1 fitted, 0 monomorphic, -1 when g
+ * lies in the span of X (ug'W ug - b'A^-1 b <= 1e-12 ug'W ug; the reference's LDLT goes on there). */
+int rvt_lrt_block_fam(rvt_ctx* ctx, const double* dG, int V, int* ok, double* af, double* null_loglik, double* alt_loglik,
+                      double* pvalue);
+/* GrammarGamma::FitNullModel (regression/GrammarGamma.cpp:29-121, with getBetaSigma2 / getLogLikelihood of :159-197) after
+ * rvt_set_kinship: raw lambda = S, beta(delta) weighted with (lambda + delta), SSR with 1 / (lambda + delta), objective
+ * -1/2 (N log 2 pi + sum log|lambda + delta| + N + N log SSR), the 101-point grid and the GSL-Brent replay of
+ * rvt_fit_fam_null; gamma, ty = U (lambda + delta)^-1 U' resid / sigma2_g with the OLS residual of y on X, ySigmaY.
+ * X: N x d column-major incl. intercept (d <= RVT_MAX_COV), y: N.  At a boundary maximum delta is the grid point (the
+ * reference keeps its previous, on the first fit uninitialised, value). */
+int rvt_fit_grammar_null(rvt_ctx* ctx, int64_t N, int d, const double* X, const double* y, rvt_grammar_null* out);
+/* SingleVariantFamilyGrammarGamma (src/Model.h:714-805): GrammarGamma::TestCovariate (regression/GrammarGamma.cpp:122-152)
+ * of every raw column of a device block, after rvt_fit_grammar_null and an rvt_fit_fam_null on the same samples (which
+ * defines the block layout).  g centred by its mean: beta = g'ty / g'g / gamma, beta_var = ySigmaY / g'g / gamma,
+ * pvalue = chisq_Q((g'ty)^2 / g'g / gamma, 1); af = mean / 2 (af_kinship = 0) or GetAF's AF_KINSHIP form
+ * 1/2 sum (lambda + delta) u1 ug / sum (lambda + delta) u1^2 (:199-213).  ok[h] = 0 for a monomorphic column. */
+int rvt_grammar_block(rvt_ctx* ctx, const double* dG, int V, int af_kinship, int* ok, double* af, double* beta,
+                      double* beta_var, double* pvalue);
 /* Copy columns between two device blocks (growing the adapter's ring).  What the engine keeps per uploaded column (below)
  * travels with them when both blocks came from rvt_block_alloc. */
 int rvt_block_copy_columns(rvt_ctx* ctx, double* dst, int dst_col, const double* src, int src_col, int ncols);

@@ -940,7 +940,7 @@ int SingleVariantBlockTest::fit(GeneData* dc) {
     if (flush()) return -1;
     rows.push_back(keep);
   }
-  ctx = GpuBroker::instance().contextWithNull(*dc, isBinaryOutcome(), &lastError);
+  ctx = acquireContext(dc);
   if (!ctx) return -1;
   if (nSample < 0) {
     nSample = dc->N;
@@ -958,6 +958,9 @@ int SingleVariantBlockTest::fit(GeneData* dc) {
   }
   rows.back().column = used++;
   return 0;
+}
+rvt_ctx* SingleVariantBlockTest::acquireContext(GeneData* dc) {
+  return GpuBroker::instance().contextWithNull(*dc, isBinaryOutcome(), &lastError);
 }
 void SingleVariantBlockTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   fout = fp;
@@ -1063,6 +1066,95 @@ std::string SingleVariantScoreTest::formatSingleRow(const Row& r) {
   }
   return r.siteTab + floatToString(r.af) + "\t" + U + "\t" + V + "\t" + STAT + "\t" + DIR + "\t" + EFF +
          "\t" + SE + "\t" + P + "\n";
+}
+
+// ---- SingleVariantFamilyScore / LRT / GrammarGamma (src/Model.h:525-805), related samples ------------------------------------
+SingleVariantFamilyTest::SingleVariantFamilyTest(const char* name, const char* header_, const char* what_)
+    : header(header_), what(what_) {
+  modelName = name;
+}
+void SingleVariantFamilyTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab() + header + "\n");
+}
+rvt_ctx* SingleVariantFamilyTest::acquireContext(GeneData* dc) {
+  if (isBinaryOutcome()) {  // warnOnce (src/Model.h:544-549, 640-645, 734-739)
+    lastError = "Single variant " + what + " does not support binary outcomes. Results will be all NAs.";
+    return nullptr;
+  }
+  if (!dc->kinshipU || !dc->kinshipS) {  // as FamSkatTest
+    lastError = "Single variant " + what + " cannot find kinship. Results will be all NAs.";
+    return nullptr;
+  }
+  return GpuBroker::instance().contextWithFamNull(*dc, &lastError);
+}
+std::string SingleVariantFamilyTest::formatSingleRow(const Row& r) {
+  const int k = r.column;
+  if (k >= 0 && ok[k] == 1)  // (Result::updateValue; never cleared in between)
+    for (int q = 0; q < 4; ++q) last[q] = floatToString(col[q][k]);
+  return r.siteTab + last[0] + "\t" + last[1] + "\t" + last[2] + "\t" + last[3] + "\n";
+}
+
+SingleVariantFamilyScore::SingleVariantFamilyScore()
+    : SingleVariantFamilyTest("FamScore", "AF\tU.Stat\tV.Stat\tPvalue", "score test (related individual)") {}
+SingleVariantFamilyScore::~SingleVariantFamilyScore() {
+  if (fout) flush();
+}
+bool SingleVariantFamilyScore::runBlock() {
+  for (auto& v : col) v.assign((size_t)used, 0.0);
+  if (rvt_score_block_fam(ctx, block, used, 0, ok.data(), col[1].data(), col[2].data(), col[0].data(), col[3].data())) {
+    lastError = rvt_last_error(ctx);
+    return false;
+  }
+  return true;
+}
+
+SingleVariantFamilyLRT::SingleVariantFamilyLRT()
+    : SingleVariantFamilyTest("FamLRT", "AF\tNullLogLik\tAltLogLik\tPvalue", "likelihood ratio test (related individuals)") {}
+SingleVariantFamilyLRT::~SingleVariantFamilyLRT() {
+  if (fout) flush();
+}
+bool SingleVariantFamilyLRT::runBlock() {
+  for (auto& v : col) v.assign((size_t)used, 0.0);
+  if (rvt_lrt_block_fam(ctx, block, used, ok.data(), col[0].data(), col[1].data(), col[2].data(), col[3].data())) {
+    lastError = rvt_last_error(ctx);
+    return false;
+  }
+  return true;
+}
+
+SingleVariantFamilyGrammarGamma::SingleVariantFamilyGrammarGamma(bool afKinship_)
+    : SingleVariantFamilyTest("FamGrammarGamma", "AF\tBeta\tBetaVar\tPvalue", "garmma-gamma test (related individuals)"),
+      afKinship(afKinship_) {}
+SingleVariantFamilyGrammarGamma::~SingleVariantFamilyGrammarGamma() {
+  if (fout) flush();
+}
+rvt_ctx* SingleVariantFamilyGrammarGamma::acquireContext(GeneData* dc) {
+  rvt_ctx* cx = SingleVariantFamilyTest::acquireContext(dc);
+  if (!cx) return nullptr;
+  if (!haveNull || nullKinship != dc->kinshipU || dc->phenotypeUpdated || dc->covariateUpdated) {
+    const int d = 1 + dc->ncov;  // copyCovariateAndIntercept (src/ModelUtil.h:102-130)
+    std::vector<double> X((size_t)dc->N * d);
+    for (int64_t i = 0; i < dc->N; ++i) X[i] = 1.0;
+    if (dc->ncov) std::memcpy(X.data() + dc->N, dc->covariate, sizeof(double) * (size_t)dc->N * dc->ncov);
+    rvt_grammar_null gn;
+    haveNull = false;
+    if (rvt_fit_grammar_null(cx, dc->N, d, X.data(), dc->phenotype, &gn)) {
+      lastError = rvt_last_error(cx);
+      return nullptr;
+    }
+    haveNull = true;
+    nullKinship = dc->kinshipU;
+  }
+  return cx;
+}
+bool SingleVariantFamilyGrammarGamma::runBlock() {
+  for (auto& v : col) v.assign((size_t)used, 0.0);
+  if (rvt_grammar_block(ctx, block, used, afKinship ? 1 : 0, ok.data(), col[0].data(), col[1].data(), col[2].data(),
+                        col[3].data())) {
+    lastError = rvt_last_error(ctx);
+    return false;
+  }
+  return true;
 }
 
 // ---- MetaCovTest ---------------------------------------------------------------------------------------------------------
@@ -1393,11 +1485,27 @@ int ModelManager::create(const std::string& type, const std::string& modelList) 
         return -1;
       }
     } else if (modelType == "single") {
-      if (modelName == "wald")  // src/ModelManager.cpp:54-98 (exact / firth / the family tests are not provided)
+      // src/ModelManager.cpp:54-98 (exact, dominantexact, firth and the multiple-trait tests are not provided)
+      if (modelName == "wald")
         model.push_back(new SingleVariantWaldTest());
       else if (modelName == "score")
         model.push_back(new SingleVariantScoreTest());
-      else {
+      else if (modelName == "famscore")
+        model.push_back(new SingleVariantFamilyScore());
+      else if (modelName == "famlrt")
+        model.push_back(new SingleVariantFamilyLRT());
+      else if (modelName == "famgrammargamma") {  // src/ModelManager.cpp:68-84
+        const char* v = parser.value("af");
+        const std::string afMethod = v ? v : "mean";
+        if (afMethod == "kinship")
+          model.push_back(new SingleVariantFamilyGrammarGamma(true));
+        else if (afMethod == "mean")
+          model.push_back(new SingleVariantFamilyGrammarGamma(false));
+        else {
+          lastError = "FamGrammarGamma cannot recoginized specified kinship calculation method [ " + afMethod + " ], exit...";
+          return -1;
+        }
+      } else {
         lastError = "Unknown model name: " + modelName + " .";
         return -1;
       }

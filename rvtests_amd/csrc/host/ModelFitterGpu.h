@@ -466,6 +466,9 @@ class SingleVariantBlockTest : public ModelFitter {
   // the device call over the first `used` columns; false when it failed (its rows then print NA)
   virtual bool runBlock() = 0;
   virtual std::string formatSingleRow(const Row& r) = 0;
+  // the context with this model's null installed (default: rvt_fit_null's); nullptr with lastError set when the site
+  // cannot be tested
+  virtual rvt_ctx* acquireContext(GeneData* dc);
   int flush();
   int capacity = 1024;  // RVT_SINGLE_BLOCK
   int64_t nSample = -1;
@@ -509,6 +512,56 @@ class SingleVariantScoreTest final : public SingleVariantBlockTest {
   std::string formatSingleRow(const Row& r) override;
   std::vector<double> u, v, eff, se, pv;
   double sigma2 = 1.0;
+};
+
+// The single-variant tests for related samples (src/Model.h:525-805): FamScore "AF U.Stat V.Stat Pvalue" (rvt_score_block_fam),
+// FamLRT "AF NullLogLik AltLogLik Pvalue" (rvt_lrt_block_fam) and FamGrammarGamma "AF Beta BetaVar Pvalue"
+// (rvt_grammar_block).  The kinship is GeneData::kinshipU / kinshipS through the broker's install; a binary trait or a missing
+// kinship fails every fit().  Like the reference's writeOutput these never clear their Result: a failed or monomorphic site
+// prints the values the previous row left (NA before the first fitted row).
+class SingleVariantFamilyTest : public SingleVariantBlockTest {
+ public:
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+
+ protected:
+  SingleVariantFamilyTest(const char* name, const char* header, const char* what);
+  rvt_ctx* acquireContext(GeneData* dc) override;
+  std::string formatSingleRow(const Row& r) override;
+  std::vector<double> col[4];  // the four printed values per column of the block
+  std::string last[4] = {"NA", "NA", "NA", "NA"};
+  std::string header;
+  std::string what;  // the model's words in the reference's warnings
+};
+
+class SingleVariantFamilyScore final : public SingleVariantFamilyTest {
+ public:
+  SingleVariantFamilyScore();
+  ~SingleVariantFamilyScore() override;
+
+ private:
+  bool runBlock() override;
+};
+
+class SingleVariantFamilyLRT final : public SingleVariantFamilyTest {
+ public:
+  SingleVariantFamilyLRT();
+  ~SingleVariantFamilyLRT() override;
+
+ private:
+  bool runBlock() override;
+};
+
+class SingleVariantFamilyGrammarGamma final : public SingleVariantFamilyTest {
+ public:
+  explicit SingleVariantFamilyGrammarGamma(bool afKinship);
+  ~SingleVariantFamilyGrammarGamma() override;
+
+ private:
+  rvt_ctx* acquireContext(GeneData* dc) override;
+  bool runBlock() override;
+  bool afKinship = false;
+  bool haveNull = false;
+  const float* nullKinship = nullptr;  // the decomposition the GrammarGamma null was fitted on
 };
 
 // ---- ModelManager::create -----------------------------------------------------------------------------------------

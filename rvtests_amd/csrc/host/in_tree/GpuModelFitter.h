@@ -130,6 +130,20 @@ typedef GpuModel<rvt_host::MetaScoreTest> MetaScoreTest;  // new MetaScoreTest()
 typedef GpuModel<rvt_host::KbacTest> KBACTest;            // new KBACTest(nPerm, alpha)
 typedef GpuModel<rvt_host::SingleVariantWaldTest> SingleVariantWaldTest;    // new SingleVariantWaldTest()   :54-98
 typedef GpuModel<rvt_host::SingleVariantScoreTest> SingleVariantScoreTest;  // new SingleVariantScoreTest()
+// the single-variant tests for related samples (src/ModelManager.cpp:63-84); familyModel = true as their constructors set it
+class SingleVariantFamilyScore : public GpuModel<rvt_host::SingleVariantFamilyScore> {
+ public:
+  SingleVariantFamilyScore() { related(); }
+};
+class SingleVariantFamilyLRT : public GpuModel<rvt_host::SingleVariantFamilyLRT> {
+ public:
+  SingleVariantFamilyLRT() { related(); }
+};
+// new SingleVariantFamilyGrammarGamma(GrammarGamma::AF_KINSHIP | AF_MEAN): regression/GrammarGamma.h:9-12 numbers them 0, 1
+class SingleVariantFamilyGrammarGamma : public GpuModel<rvt_host::SingleVariantFamilyGrammarGamma> {
+ public:
+  explicit SingleVariantFamilyGrammarGamma(int afMethod) : GpuModel(afMethod == 0) { related(); }
+};
 // new AnalyticVT(AnalyticVT::UNRELATED) / new AnalyticVT(AnalyticVT::RELATED)   ModelManager.cpp:158-161
 class AnalyticVT : public GpuModel<rvt_host::AnalyticVTTest> {
  public:

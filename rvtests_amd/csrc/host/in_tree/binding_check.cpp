@@ -7,6 +7,7 @@
 #include "GpuModelFitter.h"
 
 #include "DataConsolidator.h"
+#include "regression/GrammarGamma.h"
 
 int rvt_binding_check(DataConsolidator* dc, FileWriter* fp, const Result& siteInfo) {
   std::vector< ::ModelFitter*> model;
@@ -30,6 +31,9 @@ int rvt_binding_check(DataConsolidator* dc, FileWriter* fp, const Result& siteIn
   model.push_back(new rvt_intree::MetaCovTest(windowSize));
   model.push_back(new rvt_intree::SingleVariantWaldTest());  // src/ModelManager.cpp:54-98 (single)
   model.push_back(new rvt_intree::SingleVariantScoreTest());
+  model.push_back(new rvt_intree::SingleVariantFamilyScore());
+  model.push_back(new rvt_intree::SingleVariantFamilyLRT());
+  model.push_back(new rvt_intree::SingleVariantFamilyGrammarGamma(GrammarGamma::AF_MEAN));
   model.push_back(new rvt_intree::MetaScoreTest());
   model.push_back(new rvt_intree::AnalyticVT(rvt_intree::AnalyticVT::UNRELATED));  // src/ModelManager.cpp:158-159
   model.push_back(new rvt_intree::KBACTest(nPerm, alpha));

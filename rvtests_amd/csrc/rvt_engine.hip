@@ -267,6 +267,8 @@ void rvt_destroy(rvt_ctx* c) {
   }
   if (c->d_nc) hipFree(c->d_nc);
   if (c->d_wald_ws) hipFree(c->d_wald_ws);
+  if (c->d_lrt_ws) hipFree(c->d_lrt_ws);
+  if (c->d_gg_ws) hipFree(c->d_gg_ws);
   for (double* p : {c->d_S, c->d_u1, c->d_uxy, c->d_lmm_part, c->d_fX, c->d_frr, c->d_fv, c->d_fzeros,
                     c->d_fbeta, c->d_Gp, c->d_Gt, c->d_cX, c->d_cv, c->d_cr})
     if (p) hipFree(p);
@@ -304,6 +306,8 @@ void rvt_destroy(rvt_ctx* c) {
   if (c->d_bgen_seg) hipFree(c->d_bgen_seg);
   if (c->d_Uq) hipFree(c->d_Uq);
   if (c->d_uq_range) hipFree(c->d_uq_range);
+  for (void* q : {(void*)c->d_csr_ptr, (void*)c->d_csr_cols, (void*)c->d_csr_vals})
+    if (q) hipFree(q);
   for (void* q : {(void*)c->d_csc_ptr, (void*)c->d_csc_rows, (void*)c->d_csc_vals})
     if (q) hipFree(q);
   if (c->d_rotB) hipFree(c->d_rotB);

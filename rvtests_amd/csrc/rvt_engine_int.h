@@ -117,6 +117,10 @@ struct rvt_ctx {
   // sparse form of U (<= 64 non-zeros per eigenvector on average: families in any sample order), column-compressed;
   // used by the rotation when the K-chunk ranges (d_uq_range) do not apply; null otherwise
   long long* d_csc_ptr = nullptr;
+  // row-compressed copy of the same sparse U (U v for rvt_fit_grammar_null), made from d_csc_* on first use
+  long long* d_csr_ptr = nullptr;
+  int* d_csr_cols = nullptr;
+  double* d_csr_vals = nullptr;
   int* d_csc_rows = nullptr;
   double* d_csc_vals = nullptr;
   int2* d_uq_range = nullptr;  // per 256-row panel of the planes: K chunks [x, y) that hold its non-zeros; null = dense U
@@ -372,6 +376,20 @@ struct rvt_ctx {
   // rvt_wald_block's work space (wald_logistic.hip.h): one grow-only allocation, never touched inside the round loop
   char* d_wald_ws = nullptr;
   size_t wald_ws_cap = 0;
+  // single-variant tests for related samples (fam_single.hip.h): grow-only work spaces of rvt_lrt_block_fam and of
+  // rvt_fit_grammar_null / rvt_grammar_block, their null constants, and the generation of the FastLMM null they belong to
+  uint64_t fam_gen = 0;        // counts rvt_fit_fam_null
+  double fam_sigma2 = 0.0;     // sigma2_g of the fitted FastLMM null
+  char* d_lrt_ws = nullptr;
+  size_t lrt_ws_cap = 0;
+  uint64_t lrt_gen = 0;        // fam_gen the famLRT constants were formed for (0: none)
+  double lrt_ssr0 = 0.0, lrt_slog = 0.0;
+  char* d_gg_ws = nullptr;
+  size_t gg_ws_cap = 0;
+  bool have_grammar = false;
+  int64_t gg_N = 0;
+  int gg_d = 0;
+  double gg_delta = 0.0, gg_gamma = 0.0, gg_ysy = 0.0, gg_sumty = 0.0, gg_afden = 0.0;
   // streaming interface
   struct Pending {
     int64_t id;

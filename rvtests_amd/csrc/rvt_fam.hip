@@ -6,6 +6,7 @@
 #define RVT_K_FAM
 #include "rvt_engine_int.h"
 #include "tridiag_kernels.hip.h"
+#include "fam_single.hip.h"
 
 extern "C" {
 
@@ -41,12 +42,13 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
   c->d_Uq = nullptr;
   if (c->d_uq_range) hipFree(c->d_uq_range);
   c->d_uq_range = nullptr;
-  for (void** q : {(void**)&c->d_csc_ptr, (void**)&c->d_csc_rows, (void**)&c->d_csc_vals}) {
+  for (void** q : {(void**)&c->d_csc_ptr, (void**)&c->d_csc_rows, (void**)&c->d_csc_vals, (void**)&c->d_csr_ptr,
+                   (void**)&c->d_csr_cols, (void**)&c->d_csr_vals}) {
     if (*q) hipFree(*q);
     *q = nullptr;
   }
   c->uq_visit = 1.0;
-  c->have_kin = c->have_fam = false;
+  c->have_kin = c->have_fam = c->have_grammar = false;
   HIP_TRY(c, hipMalloc((void**)&c->d_S, sizeof(double) * N));
   HIP_TRY(c, hipMalloc((void**)&c->d_u1, sizeof(double) * N));
   // U -> fixed-point digit planes (rot_gemm.hip.h).  Eigenvectors have |u| <= 1; entries up to 2 are representable.
@@ -1100,6 +1102,7 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
     *p = nullptr;
   }
   c->have_fam = false;
+  ++c->fam_gen;
   c->famcov_b2 = 1.0;
   const int dx = d + 1;
   double* d_xy = nullptr;  // N x (d+1): X | y
@@ -1194,6 +1197,7 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
   out->delta = delta;
   out->sigma2_g = sigma2;
   c->fam_delta = delta;
+  c->fam_sigma2 = sigma2;
   std::memset(out->beta, 0, sizeof(out->beta));
   for (int a = 0; a < d; ++a) out->beta[a] = beta[a];
   out->max_index = maxIndex;
@@ -1853,6 +1857,445 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
     r.famskat_p = rec[k].famskat_p;
     r.skat_nlambda = rec[k].skat_nlambda;
     r.davies_terms = rec[k].davies_terms;
+  }
+  return RVT_OK;
+}
+
+// ---- single-variant tests for related samples: famLRT and famGrammarGamma (fam_single.hip.h) ------------------------------
+namespace {
+using namespace rvt_fs;
+
+size_t fs_align(size_t b) { return (b + 255) / 256 * 256; }
+
+// grow-only work space (allocated outside every loop; RVT_POISON fills a new one as the Wald work space is filled)
+int fs_grow(rvt_ctx* c, char** p, size_t* cap, size_t want) {
+  if (*cap >= want) return RVT_OK;
+  if (*p) hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  HIP_TRY(c, hipMalloc((void**)p, want));
+  *cap = want;
+  if (const char* e = getenv("RVT_POISON")) HIP_TRY(c, hipMemset(*p, atoi(e) & 0xff, want));
+  return RVT_OK;
+}
+
+// the kLmmBlocks partial records of a reduction, summed in block order
+int fs_records(rvt_ctx* c, const double* d_part, int rec, hipStream_t st, std::vector<double>* sums) {
+  std::vector<double> part((size_t)kLmmBlocks * rec);
+  HIP_TRY(c, hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  sums->assign(rec, 0.0);
+  for (int q = 0; q < rec; ++q) {
+    double s = 0.0;
+    for (int b = 0; b < kLmmBlocks; ++b) s += part[(size_t)b * rec + q];
+    (*sums)[q] = s;
+  }
+  return RVT_OK;
+}
+
+// d_out = U d_v (N doubles each, eigenpairs in the installed order).  The digit planes with the family panels of the
+// rotation (apply_u_kernel), or, for a sparse U whose supports are scattered, a gather over its row-compressed copy
+// (apply_u_sparse_kernel; the copy is made once per installed kinship).
+int fs_apply_u(rvt_ctx* c, const double* d_v, double* d_out, double* d_part, int64_t ldp, hipStream_t st) {
+  const int64_t N = c->kin_N;
+  if (c->d_Uq) {
+    const long long npanels = (long long)(c->uq_rows_pad / kRotBM);
+    const int slices = (int)std::max<long long>(1, std::min<long long>(kApplySlices, npanels));
+    hipLaunchKernelGGL(apply_u_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)slices), dim3(kFsThreads), 0, st, c->d_Uq,
+                       (long long)c->uq_plane, kRotPlanesU, (long long)c->uq_ldk, c->d_uq_range, kRotBM, kRotKC,
+                       (long long)N, npanels, d_v, d_part, (long long)ldp);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(apply_u_reduce_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_part, (long long)ldp,
+                       slices, (long long)N, c->uq_sexp, d_out);
+    HIP_TRY(c, hipGetLastError());
+    return RVT_OK;
+  }
+  if (!c->d_csc_ptr) return fail(c, RVT_E_STATE, "no kinship eigenvectors installed");
+  if (!c->d_csr_ptr) {  // once per installed kinship: the column-compressed U transposed (rows in order, columns ascending)
+    std::vector<long long> ptr((size_t)N + 1);
+    HIP_TRY(c, hipMemcpyAsync(ptr.data(), c->d_csc_ptr, sizeof(long long) * ptr.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    const size_t nnz = (size_t)ptr[N];
+    std::vector<int> rows(nnz), cols(nnz);
+    std::vector<double> vals(nnz), tvals(nnz);
+    HIP_TRY(c, hipMemcpyAsync(rows.data(), c->d_csc_rows, sizeof(int) * nnz, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(vals.data(), c->d_csc_vals, sizeof(double) * nnz, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    std::vector<long long> rp((size_t)N + 1, 0), fill;
+    for (size_t e = 0; e < nnz; ++e) ++rp[(size_t)rows[e] + 1];
+    for (int64_t i = 0; i < N; ++i) rp[i + 1] += rp[i];
+    fill.assign(rp.begin(), rp.end() - 1);
+    for (int64_t k = 0; k < N; ++k)
+      for (long long e = ptr[k]; e < ptr[k + 1]; ++e) {
+        const long long o = fill[rows[e]]++;
+        cols[o] = (int)k;
+        tvals[o] = vals[e];
+      }
+    HIP_TRY(c, hipMalloc((void**)&c->d_csr_ptr, sizeof(long long) * ((size_t)N + 1)));
+    HIP_TRY(c, hipMalloc((void**)&c->d_csr_cols, sizeof(int) * std::max<size_t>(nnz, 1)));
+    HIP_TRY(c, hipMalloc((void**)&c->d_csr_vals, sizeof(double) * std::max<size_t>(nnz, 1)));
+    HIP_TRY(c, hipMemcpyAsync(c->d_csr_ptr, rp.data(), sizeof(long long) * rp.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_csr_cols, cols.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_csr_vals, tvals.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, sync_stream(st));
+  }
+  hipLaunchKernelGGL(apply_u_sparse_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_csr_ptr, c->d_csr_cols,
+                     c->d_csr_vals, (long long)N, d_v, d_out);
+  HIP_TRY(c, hipGetLastError());
+  return RVT_OK;
+}
+
+extern "C++" {
+template <int DMAX, int VT>
+void fs_launch_lrt(hipStream_t st, int n, const double* Gt, long long ld, long long N, const double* ux, const double* vec,
+                   long long vld, const double* Ainv, const int* poly, const LrtConsts& k, int* ok, double* af, double* nll,
+                   double* all, double* pv) {
+  hipLaunchKernelGGL((fam_lrt_kernel<DMAX, VT>), dim3((unsigned)((n + VT - 1) / VT)), dim3(kFsThreads), 0, st, Gt, ld, N, n,
+                     ux, vec, vld, Ainv, poly, k, ok, af, nll, all, pv);
+}
+}  // extern "C++"
+}  // namespace
+
+int rvt_lrt_block_fam(rvt_ctx* c, const double* dG, int V, int* ok, double* af, double* null_loglik, double* alt_loglik,
+                      double* pvalue) {
+  if (!c || !dG || V < 1 || !ok || !af || !null_loglik || !alt_loglik || !pvalue)
+    return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_fam) return fail(c, RVT_E_STATE, "rvt_set_kinship + rvt_fit_fam_null first");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
+  const int d = c->fam_nc.d - 1;
+  const int MV = RVT_MAX_VARIANTS;
+  size_t off = 0;
+  auto carve = [&](size_t b) {
+    const size_t o = off;
+    off += fs_align(b);
+    return o;
+  };
+  const size_t o_vec = carve(sizeof(double) * 3 * (size_t)ld), o_abs = carve(sizeof(double) * (size_t)ld),
+               o_ainv = carve(sizeof(double) * RVT_MAX_COV * RVT_MAX_COV), o_beta = carve(sizeof(double) * RVT_MAX_COV),
+               o_part = carve(sizeof(double) * (size_t)kLmmBlocks * lmm_rec_len(RVT_MAX_COV)),
+               o_cs = carve(sizeof(double) * MV), o_poly = carve(sizeof(int) * MV), o_ok = carve(sizeof(int) * MV),
+               o_af = carve(sizeof(double) * MV), o_nll = carve(sizeof(double) * MV), o_all = carve(sizeof(double) * MV),
+               o_pv = carve(sizeof(double) * MV);
+  if (c->lrt_ws_cap < off) {
+    c->lrt_gen = 0;  // the constants live in the work space
+    rc = fs_grow(c, &c->d_lrt_ws, &c->lrt_ws_cap, off);
+    if (rc) return rc;
+  }
+  char* ws = c->d_lrt_ws;
+  double* d_vec = reinterpret_cast<double*>(ws + o_vec);
+  double* d_abs = reinterpret_cast<double*>(ws + o_abs);
+  double* d_ainv = reinterpret_cast<double*>(ws + o_ainv);
+  double* d_beta = reinterpret_cast<double*>(ws + o_beta);
+  double* d_part = reinterpret_cast<double*>(ws + o_part);
+  double* d_cs = reinterpret_cast<double*>(ws + o_cs);
+  int* d_poly = reinterpret_cast<int*>(ws + o_poly);
+  int* d_ok = reinterpret_cast<int*>(ws + o_ok);
+  double* d_af = reinterpret_cast<double*>(ws + o_af);
+  double* d_nll = reinterpret_cast<double*>(ws + o_nll);
+  double* d_all = reinterpret_cast<double*>(ws + o_all);
+  double* d_pv = reinterpret_cast<double*>(ws + o_pv);
+  const double delta = c->fam_delta;
+  if (c->lrt_gen != c->fam_gen) {  // constants of the null fit, once per null (FastLMM.cpp:150-180 at the null's delta)
+    std::vector<double> absS((size_t)N);
+    for (int64_t i = 0; i < N; ++i) absS[i] = std::fabs(c->h_S[i]);
+    HIP_TRY(c, hipMemcpyAsync(d_abs, absS.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(lmm_sums_kernel, dim3(kLmmBlocks), dim3(256), sizeof(double) * 256, st, c->d_uxy, d_abs,
+                       (long long)N, d, delta, 1, d_part);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<double> sums;
+    rc = fs_records(c, d_part, lmm_rec_len(d), st, &sums);
+    if (rc) return rc;
+    double Ai[RVT_MAX_COV * RVT_MAX_COV] = {}, beta[RVT_MAX_COV] = {};
+    if (!invert_spd(sums.data(), d, Ai)) return fail(c, RVT_E_INVALID, "ux' W ux is singular");
+    for (int a = 0; a < d; ++a)
+      for (int k = 0; k < d; ++k) beta[a] += Ai[a * d + k] * sums[d * d + k];
+    c->lrt_slog = sums[d * d + d + 1];
+    HIP_TRY(c, hipMemcpyAsync(d_ainv, Ai, sizeof(Ai), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_beta, beta, sizeof(beta), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(fam_lrt_null_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_uxy, d_abs, c->d_u1,
+                       (long long)N, d, delta, d_beta, d_vec, (long long)ld);
+    hipLaunchKernelGGL(grammar_sums_kernel, dim3(kLmmBlocks), dim3(kFsThreads), 0, st, c->d_uxy, d_abs, (long long)N, d,
+                       delta, 1, d_beta, d_part);
+    HIP_TRY(c, hipGetLastError());
+    rc = fs_records(c, d_part, 1, st, &sums);
+    if (rc) return rc;
+    c->lrt_ssr0 = sums[0];
+    c->lrt_gen = c->fam_gen;
+  }
+  LrtConsts k;
+  k.n = (double)N;
+  k.ssr0 = c->lrt_ssr0;
+  k.sigma2 = c->fam_sigma2;
+  k.slog = c->lrt_slog;
+  k.afden = c->fam_nc.rss;  // u1' |S|^-1 u1 (rvt_fit_fam_null)
+  k.d = d;
+  for (int c0 = 0; c0 < V; c0 += MV) {
+    const int n = std::min(MV, V - c0);
+    const double* g = dG + (size_t)c0 * ld;
+    rc = ensure_fam_cols(c, (size_t)n, ld);
+    if (rc) return rc;
+    hipLaunchKernelGGL(raw_colstat_kernel, dim3((unsigned)n), dim3(256), 0, st, g, (long long)N, (long long)ld, d_cs, d_poly);
+    HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * n, st));
+    rc = rotate_columns(c, g, ld, n, c->d_Gt, ld, st);
+    if (rc) return rc;
+    if (d <= 4)
+      fs_launch_lrt<4, 4>(st, n, c->d_Gt, ld, N, c->d_uxy, d_vec, ld, d_ainv, d_poly, k, d_ok, d_af, d_nll, d_all, d_pv);
+    else if (d <= 8)
+      fs_launch_lrt<8, 2>(st, n, c->d_Gt, ld, N, c->d_uxy, d_vec, ld, d_ainv, d_poly, k, d_ok, d_af, d_nll, d_all, d_pv);
+    else
+      fs_launch_lrt<RVT_MAX_COV, 1>(st, n, c->d_Gt, ld, N, c->d_uxy, d_vec, ld, d_ainv, d_poly, k, d_ok, d_af, d_nll, d_all,
+                                    d_pv);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(ok + c0, d_ok, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(af + c0, d_af, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(null_loglik + c0, d_nll, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(alt_loglik + c0, d_all, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(pvalue + c0, d_pv, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+  }
+  return RVT_OK;
+}
+
+namespace {
+struct GgLayout {
+  size_t o_ty, o_wu1, o_xy, o_uxy, o_r, o_ur, o_upart, o_part, o_beta, o_ok, o_af, o_b, o_bv, o_pv, total;
+};
+GgLayout gg_layout(int64_t ld, int64_t N, int d) {
+  GgLayout L;
+  size_t off = 0;
+  auto carve = [&](size_t b) {
+    const size_t o = off;
+    off += fs_align(b);
+    return o;
+  };
+  const int MV = RVT_MAX_VARIANTS;
+  L.o_ty = carve(sizeof(double) * (size_t)ld);
+  L.o_wu1 = carve(sizeof(double) * (size_t)ld);
+  L.o_xy = carve(sizeof(double) * (size_t)N * (d + 1));
+  L.o_uxy = carve(sizeof(double) * (size_t)N * (d + 1));
+  L.o_r = carve(sizeof(double) * (size_t)ld);
+  L.o_ur = carve(sizeof(double) * (size_t)ld);
+  L.o_upart = carve(sizeof(double) * (size_t)kApplySlices * ld);
+  L.o_part = carve(sizeof(double) * (size_t)kLmmBlocks * (d * d + d + 1));
+  L.o_beta = carve(sizeof(double) * RVT_MAX_COV);
+  L.o_ok = carve(sizeof(int) * MV);
+  L.o_af = carve(sizeof(double) * MV);
+  L.o_b = carve(sizeof(double) * MV);
+  L.o_bv = carve(sizeof(double) * MV);
+  L.o_pv = carve(sizeof(double) * MV);
+  L.total = off;
+  return L;
+}
+}  // namespace
+
+int rvt_fit_grammar_null(rvt_ctx* c, int64_t N, int d, const double* X, const double* y, rvt_grammar_null* out) {
+  if (!c || !X || !y || !out || d < 1 || d > RVT_MAX_COV || N < 2) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_kin || c->kin_N != N) return fail(c, RVT_E_STATE, "rvt_set_kinship with the same N first");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  c->have_grammar = false;
+  const int64_t ld = rvt_padded_ld(N);
+  const GgLayout L = gg_layout(ld, N, d);
+  rc = fs_grow(c, &c->d_gg_ws, &c->gg_ws_cap, L.total);
+  if (rc) return rc;
+  char* ws = c->d_gg_ws;
+  double* d_ty = reinterpret_cast<double*>(ws + L.o_ty);
+  double* d_wu1 = reinterpret_cast<double*>(ws + L.o_wu1);
+  double* d_xy = reinterpret_cast<double*>(ws + L.o_xy);
+  double* d_uxy = reinterpret_cast<double*>(ws + L.o_uxy);
+  double* d_r = reinterpret_cast<double*>(ws + L.o_r);
+  double* d_ur = reinterpret_cast<double*>(ws + L.o_ur);
+  double* d_upart = reinterpret_cast<double*>(ws + L.o_upart);
+  double* d_part = reinterpret_cast<double*>(ws + L.o_part);
+  double* d_beta = reinterpret_cast<double*>(ws + L.o_beta);
+  // ux = U'X, uy = U'y (GrammarGamma.cpp:38-40)
+  HIP_TRY(c, hipMemcpyAsync(d_xy, X, sizeof(double) * (size_t)N * d, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_xy + (size_t)N * d, y, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, st));
+  rc = rotate_columns(c, d_xy, N, d + 1, d_uxy, N, st);
+  if (rc) return rc;
+  double minS = c->h_S[0];
+  for (int64_t i = 1; i < N; ++i) minS = std::min(minS, c->h_S[i]);
+  const double n = (double)N;
+  double sigma2_g = NAN;
+  bool hip_failed = false;
+  std::vector<double> sums;
+  // getBetaSigma2 + getLogLikelihood (GrammarGamma.cpp:159-197): beta by the least squares weighted with (lambda + delta),
+  // SSR with 1 / (lambda + delta), raw lambda; the objective takes log SSR (not log sigma2)
+  auto evaluate = [&](double delta) -> double {
+    if (minS + delta < 0.0) {  // sqrt(lambda + delta) of a negative number: NaN throughout
+      sigma2_g = NAN;
+      return NAN;
+    }
+    const int rec = d * d + d + 1;
+    hipLaunchKernelGGL(grammar_sums_kernel, dim3(kLmmBlocks), dim3(kFsThreads), 0, st, d_uxy, c->d_S, (long long)N, d, delta,
+                       0, d_beta, d_part);
+    if (hipGetLastError() != hipSuccess || fs_records(c, d_part, rec, st, &sums)) {
+      hip_failed = true;
+      return NAN;
+    }
+    const double slog = sums[d * d + d];
+    double Ai[RVT_MAX_COV * RVT_MAX_COV], beta[RVT_MAX_COV] = {};
+    if (!invert_spd(sums.data(), d, Ai)) {
+      sigma2_g = NAN;
+      return NAN;
+    }
+    for (int a = 0; a < d; ++a)
+      for (int k = 0; k < d; ++k) beta[a] += Ai[a * d + k] * sums[d * d + k];
+    if (hipMemcpyAsync(d_beta, beta, sizeof(double) * d, hipMemcpyHostToDevice, st) != hipSuccess) hip_failed = true;
+    hipLaunchKernelGGL(grammar_sums_kernel, dim3(kLmmBlocks), dim3(kFsThreads), 0, st, d_uxy, c->d_S, (long long)N, d, delta,
+                       1, d_beta, d_part);
+    if (hipGetLastError() != hipSuccess || fs_records(c, d_part, 1, st, &sums)) {
+      hip_failed = true;
+      return NAN;
+    }
+    const double ssr = sums[0];
+    sigma2_g = ssr / n;
+    return -0.5 * (n * std::log(2.0 * kRefPi) + slog + n + n * std::log(ssr));
+  };
+  int maxIndex = -1;
+  double maxLL = 0.0;
+  for (int i = 0; i <= 100; ++i) {
+    const double ll = evaluate(std::exp(-10. + i * 0.2));
+    if (std::isnan(ll)) continue;
+    if (maxIndex < 0 || ll > maxLL) {
+      maxIndex = i;
+      maxLL = ll;
+    }
+  }
+  if (hip_failed) return fail(c, RVT_E_HIP, "device evaluation of the GrammarGamma likelihood failed");
+  if (maxIndex < 0) return fail(c, RVT_E_INVALID, "GrammarGamma: the likelihood is NaN at every grid point");
+  // at a boundary maximum the reference leaves delta as it was (uninitialised on the first fit): here the grid point
+  double delta = std::exp(-10. + maxIndex * 0.2);
+  int evals = 0;
+  if (maxIndex > 0 && maxIndex < 100) {
+    const double lb = std::exp(-10. + (maxIndex - 1) * 0.2), ub = std::exp(-10. + (maxIndex + 1) * 0.2);
+    const double start = delta;
+    double xmin = start;
+    auto goal = [&](double x) {
+      ++evals;
+      return -evaluate(x);
+    };
+    delta = brent_like_gsl(goal, start, lb, ub, &xmin) ? start : xmin;
+    if (hip_failed) return fail(c, RVT_E_HIP, "device evaluation of the GrammarGamma likelihood failed");
+  }  // sigma2_g stays that of the LAST evaluation (the last Brent call, or grid point 100)
+  // gamma (GrammarGamma.cpp:100-102)
+  double glam = 0.0;
+  for (int64_t i = 0; i < N; ++i) glam += c->h_S[i] / (c->h_S[i] + delta);
+  const double gamma = glam / sigma2_g / (n - 1.0);
+  // resid = y - X (X'X)^-1 X'y in the original space (GrammarGamma.cpp:113-120)
+  std::vector<double> resid((size_t)N);
+  {
+    double XtX[RVT_MAX_COV * RVT_MAX_COV], XtXi[RVT_MAX_COV * RVT_MAX_COV], Xty[RVT_MAX_COV] = {}, b[RVT_MAX_COV] = {};
+    for (int a = 0; a < d; ++a) {
+      for (int k = a; k < d; ++k) {
+        double s = 0.0;
+        for (int64_t i = 0; i < N; ++i) s += X[(size_t)a * N + i] * X[(size_t)k * N + i];
+        XtX[a * d + k] = XtX[k * d + a] = s;
+      }
+      for (int64_t i = 0; i < N; ++i) Xty[a] += X[(size_t)a * N + i] * y[i];
+    }
+    if (!invert_spd(XtX, d, XtXi)) return fail(c, RVT_E_INVALID, "X'X is singular");
+    for (int a = 0; a < d; ++a)
+      for (int k = 0; k < d; ++k) b[a] += XtXi[a * d + k] * Xty[k];
+    for (int64_t i = 0; i < N; ++i) {
+      double p = 0.0;
+      for (int a = 0; a < d; ++a) p += X[(size_t)a * N + i] * b[a];
+      resid[i] = y[i] - p;
+    }
+  }
+  // ty = U (lambda + delta)^-1 U' resid / sigma2_g (GrammarGamma.cpp:122-128); wu1 = (lambda + delta) u1 for af=kinship
+  HIP_TRY(c, hipMemcpyAsync(d_r, resid.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, st));
+  rc = rotate_columns(c, d_r, ld, 1, d_ur, ld, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(grammar_scale_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_S, c->d_u1, (long long)N,
+                     delta, 1.0 / sigma2_g, d_ur, d_wu1);
+  HIP_TRY(c, hipGetLastError());
+  rc = fs_apply_u(c, d_ur, d_ty, d_upart, ld, st);
+  if (rc) return rc;
+  std::vector<double> ty((size_t)N);
+  HIP_TRY(c, hipMemcpyAsync(ty.data(), d_ty, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  double ysy = 0.0, sumty = 0.0, afden = 0.0;
+  for (int64_t i = 0; i < N; ++i) {
+    ysy += resid[i] * ty[i];
+    sumty += ty[i];
+    afden += (c->h_S[i] + delta) * c->h_u1[i] * c->h_u1[i];
+  }
+  c->gg_N = N;
+  c->gg_d = d;
+  c->gg_delta = delta;
+  c->gg_gamma = gamma;
+  c->gg_ysy = ysy;
+  c->gg_sumty = sumty;
+  c->gg_afden = afden;
+  c->have_grammar = true;
+  out->delta = delta;
+  out->sigma2_g = sigma2_g;
+  out->gamma = gamma;
+  out->ySigmaY = ysy;
+  out->max_index = maxIndex;
+  out->brent_evals = evals;
+  return RVT_OK;
+}
+
+int rvt_grammar_block(rvt_ctx* c, const double* dG, int V, int af_kinship, int* ok, double* af, double* beta,
+                      double* beta_var, double* pvalue) {
+  if (!c || !dG || V < 1 || !ok || !af || !beta || !beta_var || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_grammar) return fail(c, RVT_E_STATE, "rvt_set_kinship + rvt_fit_grammar_null first");
+  if (!c->have_fam || c->fam_nc.N != c->gg_N)
+    return fail(c, RVT_E_STATE, "rvt_fit_fam_null with the same samples first (it defines the block layout)");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const int64_t N = c->gg_N, ld = c->fam_nc.ld;
+  const GgLayout L = gg_layout(rvt_padded_ld(N), N, c->gg_d);
+  char* ws = c->d_gg_ws;
+  const double* d_ty = reinterpret_cast<const double*>(ws + L.o_ty);
+  const double* d_wu1 = reinterpret_cast<const double*>(ws + L.o_wu1);
+  int* d_ok = reinterpret_cast<int*>(ws + L.o_ok);
+  double* d_af = reinterpret_cast<double*>(ws + L.o_af);
+  double* d_b = reinterpret_cast<double*>(ws + L.o_b);
+  double* d_bv = reinterpret_cast<double*>(ws + L.o_bv);
+  double* d_pv = reinterpret_cast<double*>(ws + L.o_pv);
+  const int MV = RVT_MAX_VARIANTS;
+  GgConsts k;
+  k.n = (double)N;
+  k.gamma = c->gg_gamma;
+  k.ysy = c->gg_ysy;
+  k.sumty = c->gg_sumty;
+  k.afden = c->gg_afden;
+  for (int c0 = 0; c0 < V; c0 += MV) {
+    const int n = std::min(MV, V - c0);
+    const double* g = dG + (size_t)c0 * ld;
+    const double* gt = nullptr;
+    if (af_kinship) {  // U'g for the kinship-weighted frequency (GrammarGamma.cpp:129-134, 199-213)
+      rc = ensure_fam_cols(c, (size_t)n, ld);
+      if (rc) return rc;
+      HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * n, st));
+      rc = rotate_columns(c, g, ld, n, c->d_Gt, ld, st);
+      if (rc) return rc;
+      gt = c->d_Gt;
+    }
+    if (af_kinship)
+      hipLaunchKernelGGL(grammar_stream_kernel<true>, dim3((unsigned)n), dim3(kFsThreads), 0, st, g, (long long)ld, (long long)N,
+                         n, d_ty, gt, d_wu1, k, d_ok, d_af, d_b, d_bv, d_pv);
+    else
+      hipLaunchKernelGGL(grammar_stream_kernel<false>, dim3((unsigned)n), dim3(kFsThreads), 0, st, g, (long long)ld, (long long)N,
+                         n, d_ty, nullptr, nullptr, k, d_ok, d_af, d_b, d_bv, d_pv);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(ok + c0, d_ok, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(af + c0, d_af, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(beta + c0, d_b, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(beta_var + c0, d_bv, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(pvalue + c0, d_pv, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
   }
   return RVT_OK;
 }

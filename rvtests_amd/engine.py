@@ -62,6 +62,11 @@ class FamNull(C.Structure):
                 ("brent_evals", C.c_int)]
 
 
+class GrammarNull(C.Structure):
+    _fields_ = [("delta", C.c_double), ("sigma2_g", C.c_double), ("gamma", C.c_double), ("ySigmaY", C.c_double),
+                ("max_index", C.c_int), ("brent_evals", C.c_int)]
+
+
 class Timing(C.Structure):
     _fields_ = [("ms_suffstat", C.c_double), ("ms_burden", C.c_double), ("ms_stats", C.c_double),
                 ("ms_pvalue", C.c_double), ("n_suffstat_launches", C.c_int64), ("n_burden_launches", C.c_int64),
@@ -246,6 +251,12 @@ def load_library():
     L.rvt_score_block_fam.argtypes = [vp, vp, C.c_int, C.c_int, c_int_p] + [c_double_p] * 4
     L.rvt_fam_null_summary.restype = C.c_int
     L.rvt_fam_null_summary.argtypes = [vp, c_double_p]
+    L.rvt_lrt_block_fam.restype = C.c_int
+    L.rvt_lrt_block_fam.argtypes = [vp, vp, C.c_int, c_int_p] + [c_double_p] * 4
+    L.rvt_fit_grammar_null.restype = C.c_int
+    L.rvt_fit_grammar_null.argtypes = [vp, C.c_int64, C.c_int, c_double_p, c_double_p, C.POINTER(GrammarNull)]
+    L.rvt_grammar_block.restype = C.c_int
+    L.rvt_grammar_block.argtypes = [vp, vp, C.c_int, C.c_int, c_int_p] + [c_double_p] * 4
     L.rvt_cov_block.restype = C.c_int
     L.rvt_cov_block.argtypes = [vp, vp, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]
     L.rvt_block_upload_columns.restype = C.c_int
@@ -919,6 +930,35 @@ class Engine:
                                                ok.ctypes.data_as(c_int_p),
                                                *[_dp(a) for a in arr]))
         return dict(ok=ok, U=arr[0], V=arr[1], af=arr[2], p=arr[3])
+
+    def lrt_block_fam(self, ptr, V):
+        """SingleVariantFamilyLRT of the V raw columns of a device block (after set_kinship + fit_fam_null): dict of ok (1
+        fitted, 0 monomorphic, -1 g in the span of X), af, null / alt log-likelihoods and p."""
+        V = int(V)
+        ok = np.zeros(V, dtype=np.int32)
+        arr = [np.zeros(V) for _ in range(4)]
+        self._check(self.L.rvt_lrt_block_fam(self.ctx, C.c_void_p(int(ptr)), V, ok.ctypes.data_as(c_int_p),
+                                             *[_dp(a) for a in arr]))
+        return dict(ok=ok, af=arr[0], null_ll=arr[1], alt_ll=arr[2], p=arr[3])
+
+    def fit_grammar_null(self, X, y):
+        """GrammarGamma::FitNullModel on the installed kinship (rvt_fit_grammar_null)."""
+        X = np.asfortranarray(X, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        N, d = X.shape
+        out = GrammarNull()
+        self._check(self.L.rvt_fit_grammar_null(self.ctx, N, d, _dp(X), _dp(y), C.byref(out)))
+        return out
+
+    def grammar_block(self, ptr, V, af_kinship=0):
+        """SingleVariantFamilyGrammarGamma of the V raw columns of a device block (after fit_grammar_null and fit_fam_null
+        on the same samples): dict of ok (1 tested, 0 monomorphic), af, beta, beta_var and p."""
+        V = int(V)
+        ok = np.zeros(V, dtype=np.int32)
+        arr = [np.zeros(V) for _ in range(4)]
+        self._check(self.L.rvt_grammar_block(self.ctx, C.c_void_p(int(ptr)), V, int(af_kinship),
+                                             ok.ctypes.data_as(c_int_p), *[_dp(a) for a in arr]))
+        return dict(ok=ok, af=arr[0], beta=arr[1], beta_var=arr[2], p=arr[3])
 
     def fam_null_summary(self, d):
         covb = np.zeros(d)
