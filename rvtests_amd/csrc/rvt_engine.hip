@@ -155,10 +155,11 @@ int rvt_init(rvt_ctx** out, int device_id) {
     hipEventCreateWithFlags(&c->ev_k2[i], hipEventDisableTiming);
     hipEventCreateWithFlags(&c->ev_k2b[i], hipEventDisableTiming);
   }
-  if (hipMalloc((void**)&c->d_nc, sizeof(NullConsts)) != hipSuccess) {
+  if (c->nc_buf.alloc(sizeof(NullConsts)) != hipSuccess) {
     delete c;
     return RVT_E_HIP;
   }
+  c->d_nc = c->nc_buf;
   {  // let the eigen kernel keep matrices up to ~120 x 120 doubles in LDS
     const int want = 128 * 1024;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(gene_tridiag_kernel),
@@ -177,32 +178,31 @@ int rvt_init(rvt_ctx** out, int device_id) {
 }
 
 static void free_null(rvt_ctx* c) {
-  for (double** p : {&c->d_nulltile, &c->d_res, &c->d_v}) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-  }
-  c->d_X = c->d_rr = c->d_zeros = nullptr;  // inside d_nulltile
-  if (c->d_hcp_xq) hipFree(c->d_hcp_xq);
-  if (c->d_hcp_scale) hipFree(c->d_hcp_scale);
-  c->d_hcp_xq = nullptr;
-  c->d_hcp_scale = nullptr;
+  c->d_nulltile.reset();
+  c->res_buf.reset();
+  c->v_buf.reset();
+  c->d_X = c->d_res = c->d_rr = c->d_v = c->d_zeros = nullptr;
+  c->d_hcp_xq.reset();
+  c->d_hcp_scale.reset();
   c->hcp_planes_state = 0;
-  if (c->d_nulltile_w) hipFree(c->d_nulltile_w);
-  if (c->d_vq) hipFree(c->d_vq);
-  if (c->d_dq) hipFree(c->d_dq);
-  if (c->d_xq) hipFree(c->d_xq);
-  if (c->d_xscale) hipFree(c->d_xscale);
-  if (c->d_fxq) hipFree(c->d_fxq);
-  c->d_fxq = nullptr;
+  c->d_nulltile_w.reset();
+  c->d_vq.reset();
+  c->d_dq.reset();
+  c->d_xq.reset();
+  c->d_xscale.reset();
+  c->d_fxq.reset();
   c->fdx_ok = false;
-  c->d_nulltile_w = nullptr;
-  c->d_vq = nullptr;
-  c->d_dq = c->d_xq = nullptr;
-  c->d_xscale = nullptr;
   c->hcx_ok = false;
-  if (c->d_null_y) hipFree(c->d_null_y);
-  c->d_null_y = nullptr;
+  c->d_null_y.reset();
   c->have_null = false;
+}
+
+// a block whose content is new: its column flags and cache go (its column count and whether its cache could be allocated stay)
+static void clear_col_kind(rvt_ctx::ColKind& ck) {
+  rvt_ctx::ColKind fresh;
+  fresh.cols = ck.cols;
+  fresh.cache_failed = ck.cache_failed;
+  ck = std::move(fresh);
 }
 
 void rvt_destroy(rvt_ctx* c) {
@@ -240,8 +240,6 @@ void rvt_destroy(rvt_ctx* c) {
     sync_stream(c->io_stream);
     hipStreamDestroy(c->io_stream);
   }
-  for (char* p : c->stage.chunk) hipHostFree(p);
-  if (c->h_small) hipHostFree(c->h_small);
   for (hipEvent_t e : c->small_ev)
     if (e) hipEventDestroy(e);
   for (hipEvent_t e : c->stage_ev)
@@ -254,34 +252,8 @@ void rvt_destroy(rvt_ctx* c) {
   }
   drain_events(c);
   for (auto e : c->event_pool) hipEventDestroy(e);
-  free_null(c);
-  for (auto& p : c->queue)
-    if (p.dG) hipFree(p.dG);
-  for (auto& bp : c->block_pool) hipFree(bp.second);
-  for (auto& bp : c->pk_pool) hipFree(bp.second);
-  c->pk_pool.clear();
-  for (auto& sl : c->slots) {
-    if (sl.arena.base) hipFree(sl.arena.base);
-    if (sl.h_stage) hipHostFree(sl.h_stage);
-    hipStreamDestroy(sl.stream);
-  }
-  if (c->d_nc) hipFree(c->d_nc);
-  if (c->d_wald_ws) hipFree(c->d_wald_ws);
-  if (c->d_lrt_ws) hipFree(c->d_lrt_ws);
-  if (c->d_gg_ws) hipFree(c->d_gg_ws);
-  for (double* p : {c->d_S, c->d_u1, c->d_uxy, c->d_lmm_part, c->d_fX, c->d_frr, c->d_fv, c->d_fzeros,
-                    c->d_fbeta, c->d_Gp, c->d_Gt, c->d_cX, c->d_cv, c->d_cr})
-    if (p) hipFree(p);
-  if (c->d_famcov_nc) hipFree(c->d_famcov_nc);
-  for (void* p : {(void*)c->d_perm_idx, (void*)c->d_perm_states, (void*)c->d_perm_R, (void*)c->d_perm_C,
-                  (void*)c->d_perm_Q, (void*)c->d_perm_cur, (void*)c->d_pc_part, (void*)c->d_pc_Q})
-    if (p) hipFree(p);
-  if (c->d_consol_af) hipFree(c->d_consol_af);
-  if (c->d_consol_parts) hipFree(c->d_consol_parts);
-  if (c->h_af_ring) hipHostFree(c->h_af_ring);
-  if (c->d_consol_i8) hipFree(c->d_consol_i8);
+  for (auto& sl : c->slots) hipStreamDestroy(sl.stream);
   for (int k = 0; k < rvt_ctx::kPack; ++k) {
-    if (c->d_pack[k]) hipFree(c->d_pack[k]);
     if (c->ev_pack_copied[k]) hipEventDestroy(c->ev_pack_copied[k]);
     if (c->ev_pack_free[k]) hipEventDestroy(c->ev_pack_free[k]);
   }
@@ -289,46 +261,22 @@ void rvt_destroy(rvt_ctx* c) {
     sync_stream(c->copy_stream);
     hipStreamDestroy(c->copy_stream);
   }
-  for (auto& kv : c->col_kind) kv.second.release();
-  if (c->d_cc_part) hipFree(c->d_cc_part);
   for (int k = 0; k < rvt_ctx::kTextBufs; ++k) {
-    if (c->text_buf[k]) hipFree(c->text_buf[k]);
     if (c->ev_text_free[k]) hipEventDestroy(c->ev_text_free[k]);
     if (c->ev_text_copied[k]) hipEventDestroy(c->ev_text_copied[k]);
   }
-  if (c->d_vcf_rec) hipFree(c->d_vcf_rec);
-  if (c->d_vcf_seg) hipFree(c->d_vcf_seg);
-  if (c->d_vcf_rows) hipFree(c->d_vcf_rows);
-  if (c->h_io_err) hipHostFree(c->h_io_err);
-  if (c->d_vcf_sex) hipFree(c->d_vcf_sex);
-  if (c->d_fam_list) hipFree(c->d_fam_list);
-  if (c->d_bgen_rec) hipFree(c->d_bgen_rec);
-  if (c->d_bgen_seg) hipFree(c->d_bgen_seg);
-  if (c->d_Uq) hipFree(c->d_Uq);
-  if (c->d_uq_range) hipFree(c->d_uq_range);
-  for (void* q : {(void*)c->d_csr_ptr, (void*)c->d_csr_cols, (void*)c->d_csr_vals})
-    if (q) hipFree(q);
-  for (void* q : {(void*)c->d_csc_ptr, (void*)c->d_csc_rows, (void*)c->d_csc_vals})
-    if (q) hipFree(q);
-  if (c->d_rotB) hipFree(c->d_rotB);
-  if (c->d_rotA) hipFree(c->d_rotA);
-  if (c->d_rot_part) hipFree(c->d_rot_part);
-  if (c->d_cov_work) hipFree(c->d_cov_work);
-  if (c->d_colpack) hipFree(c->d_colpack);
-  if (c->d_mu_nan) hipFree(c->d_mu_nan);
-  if (c->d_bedbatch) hipFree(c->d_bedbatch);
-  for (int i = 0; i < 2; ++i) {
-    if (c->colq.h[i]) hipHostFree(c->colq.h[i]);
+  for (int i = 0; i < 2; ++i)
     if (c->colq.ev[i]) hipEventDestroy(c->colq.ev[i]);
-  }
   for (int i = 0; i < 2; ++i) {
     if (c->ev_band_fin[i]) hipEventDestroy(c->ev_band_fin[i]);
     if (c->ev_band_copied[i]) hipEventDestroy(c->ev_band_copied[i]);
   }
-  if (c->d_rot_scale) hipFree(c->d_rot_scale);
-  if (c->d_rot_sexp) hipFree(c->d_rot_sexp);
-  if (c->d_kind) hipFree(c->d_kind);
-  if (c->d_fam_nc) hipFree(c->d_fam_nc);
+  // device memory: the blocks of the streaming interface (raw: the caller's blocks share their pools), then every buffer
+  // the context owns (its members' destructors)
+  for (auto& p : c->queue)
+    if (p.dG) hipFree(p.dG);
+  for (auto& bp : c->block_pool) hipFree(bp.second);
+  for (auto& bp : c->pk_pool) hipFree(bp.second);
   delete c;
 }
 
@@ -386,12 +334,14 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
   // device copies, padded with zeros
   const size_t vb = sizeof(double) * (size_t)ld;
   // [X | rr | zeros] in one allocation: the hard-call kernel reads its null-model tile through one buffer descriptor
-  HIP_TRY(c, hipMalloc((void**)&c->d_nulltile, vb * (d + 2)));
+  HIP_TRY(c, c->d_nulltile.alloc(vb * (d + 2)));
   c->d_X = c->d_nulltile;
   c->d_rr = c->d_nulltile + (size_t)ld * d;
   c->d_zeros = c->d_nulltile + (size_t)ld * (d + 1);
-  HIP_TRY(c, hipMalloc((void**)&c->d_res, vb));
-  HIP_TRY(c, hipMalloc((void**)&c->d_v, vb));
+  HIP_TRY(c, c->res_buf.alloc(vb));
+  c->d_res = c->res_buf;
+  HIP_TRY(c, c->v_buf.alloc(vb));
+  c->d_v = c->v_buf;
   HIP_TRY(c, hipMemset(c->d_nulltile, 0, vb * (d + 2)));
   HIP_TRY(c, hipMemset(c->d_res, 0, vb));
   HIP_TRY(c, hipMemset(c->d_v, 0, vb));
@@ -432,8 +382,8 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
         tile[(size_t)d * ld + i] = res[i];
         tile[(size_t)(d + 1) * ld + i] = v[i];
       }
-      HIP_TRY(c, hipMalloc((void**)&c->d_nulltile_w, sizeof(double) * tile.size()));
-      HIP_TRY(c, hipMalloc((void**)&c->d_vq, vq.size()));
+      HIP_TRY(c, c->d_nulltile_w.alloc(sizeof(double) * tile.size()));
+      HIP_TRY(c, c->d_vq.alloc(vq.size()));
       HIP_TRY(c, hipMemcpy(c->d_nulltile_w, tile.data(), sizeof(double) * tile.size(), hipMemcpyHostToDevice));
       HIP_TRY(c, hipMemcpy(c->d_vq, vq.data(), vq.size(), hipMemcpyHostToDevice));
       // The workgroup-cooperative kernel (suffstat_hcx.hip.h) multiplies the null tile on the int8 matrix cores too: every
@@ -498,9 +448,9 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
               xq[(((size_t)(g * kHcwPlanes + p) * 4 + q) * ncx + k) * 16 + T * 4 + l] = (unsigned char)dg[p];
           }
         }
-        HIP_TRY(c, hipMalloc((void**)&c->d_dq, dq.size()));
-        HIP_TRY(c, hipMalloc((void**)&c->d_xq, xq.size()));
-        HIP_TRY(c, hipMalloc((void**)&c->d_xscale, sizeof(scale)));
+        HIP_TRY(c, c->d_dq.alloc(dq.size()));
+        HIP_TRY(c, c->d_xq.alloc(xq.size()));
+        HIP_TRY(c, c->d_xscale.alloc(sizeof(scale)));
         HIP_TRY(c, hipMemcpy(c->d_dq, dq.data(), dq.size(), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(c->d_xq, xq.data(), xq.size(), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(c->d_xscale, scale, sizeof(scale), hipMemcpyHostToDevice));
@@ -560,7 +510,7 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
         }
         put(i, d + 1, 1ll);
       }
-      HIP_TRY(c, hipMalloc((void**)&c->d_fxq, fx.size()));
+      HIP_TRY(c, c->d_fxq.alloc(fx.size()));
       HIP_TRY(c, hipMemcpy(c->d_fxq, fx.data(), fx.size(), hipMemcpyHostToDevice));
       c->fdx_tile.xq = c->d_fxq;
       for (int k = 0; k < 16; ++k) c->fdx_tile.scale[k] = scale[k];
@@ -587,7 +537,7 @@ int rvt_block_alloc(rvt_ctx* c, int M, double** out) {
   HIP_TRY(c, sync_stream(c->io_stream));
   {  // (flags are allocated by the first column upload; a zeroed block holds hard calls only)
     rvt_ctx::ColKind& ck = c->col_kind[*out];
-    ck.release();  // (an earlier block at the same address that was freed behind our back)
+    clear_col_kind(ck);  // (an earlier block at the same address that was freed behind our back)
     ck.cols = M;
   }
   return RVT_OK;
@@ -612,7 +562,7 @@ int rvt_block_classify(rvt_ctx* c, const double* dG, int M, int* is_hard_call) {
   if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first (defines N)");
   hipSetDevice(c->device);
   const int64_t N = c->have_null ? c->nc.N : c->fam_nc.N, ld = c->have_null ? c->null_ld : c->fam_nc.ld;
-  if (!c->d_kind) HIP_TRY(c, hipMalloc((void**)&c->d_kind, sizeof(int)));
+  HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int)));
   int rc = enqueue_classify(c, dG, M, N, ld, c->io_stream, c->d_kind);
   if (rc) return rc;
   int flag = 0;
@@ -669,10 +619,7 @@ int rvt_block_free(rvt_ctx* c, double* dG) {
   (void)sync_stream(c->io_stream);
   {
     auto it = c->col_kind.find(dG);
-    if (it != c->col_kind.end()) {
-      it->second.release();
-      c->col_kind.erase(it);
-    }
+    if (it != c->col_kind.end()) c->col_kind.erase(it);
   }
   if (dG) HIP_TRY(c, hipFree(dG));
   return RVT_OK;
@@ -683,9 +630,8 @@ int rvt_block_free(rvt_ctx* c, double* dG) {
 int stage_ready(rvt_ctx* c) {
   if (!c->stage.chunk.empty()) return RVT_OK;
   for (int k = 0; k < rvt_ctx::kStageChunks; ++k) {
-    char* p = nullptr;
-    HIP_TRY(c, hipHostMalloc((void**)&p, rvt_ctx::kStageBytes, hipHostMallocDefault));
-    c->stage.chunk.push_back(p);
+    HIP_TRY(c, c->stage_buf[k].alloc(rvt_ctx::kStageBytes));
+    c->stage.chunk.push_back(c->stage_buf[k]);
     HIP_TRY(c, hipEventCreateWithFlags(&c->stage_ev[k], hipEventDisableTiming));
   }
   c->stage.chunk_bytes = rvt_ctx::kStageBytes;
@@ -847,8 +793,8 @@ int rvt_host_diagnose(rvt_ctx* c, rvt_host_diag* o) {
     dst[i] = 1;
   }
   o->buffer_numa_node = numa_node_of(src.data());
-  char* pin = nullptr;
-  void* dev = nullptr;
+  PinBuf<char> pin;
+  DevBuf<void> dev;
   auto best = [&](const std::function<void()>& fn) {
     double t = 1e30;
     for (int r = 0; r < 3; ++r) {
@@ -859,7 +805,7 @@ int rvt_host_diagnose(rvt_ctx* c, rvt_host_diag* o) {
     return (double)B / t / 1e9;
   };
   o->memcpy_one_thread = best([&] { std::memcpy(dst.data(), src.data(), B); });
-  if (hipHostMalloc((void**)&pin, B, hipHostMallocDefault) == hipSuccess && hipMalloc(&dev, B) == hipSuccess) {
+  if (pin.alloc(B) == hipSuccess && dev.alloc(B) == hipSuccess) {
     std::memset(pin, 0, B);
     o->pinned_numa_node = numa_node_of(pin);
     o->stage_pool = best([&] { CopyPool::instance().copy(pin, src.data(), B); });
@@ -875,8 +821,6 @@ int rvt_host_diagnose(rvt_ctx* c, rvt_host_diag* o) {
     (void)hipGetLastError();
     o->pinned_numa_node = -1;
   }
-  if (pin) hipHostFree(pin);
-  if (dev) hipFree(dev);
   return RVT_OK;
 }
 
@@ -934,7 +878,7 @@ int small_h2d(rvt_ctx* c, void* dst, const void* src, size_t bytes) {
     return RVT_OK;
   }
   if (!c->h_small) {
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_small, rvt_ctx::kSmallSlots * rvt_ctx::kSmallBytes, hipHostMallocDefault));
+    HIP_TRY(c, c->h_small.alloc(rvt_ctx::kSmallSlots * rvt_ctx::kSmallBytes));
     for (auto& e : c->small_ev) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
   const int k = c->small_next;
@@ -999,11 +943,7 @@ int upload_block_data(rvt_ctx* c, double* dG, int M, const double* G) {
   }
   {  // per-column flags of an earlier column-wise fill no longer describe the block
     auto it = c->col_kind.find(dG);
-    if (it != c->col_kind.end()) {
-      const int cols = it->second.cols;
-      it->second.release();
-      it->second.cols = cols;
-    }
+    if (it != c->col_kind.end()) clear_col_kind(it->second);
   }
   const size_t N = (size_t)(c->have_null ? c->nc.N : c->fam_nc.N);
   const size_t bld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
@@ -1204,8 +1144,8 @@ static int ensure_hcp_planes(rvt_ctx* c) {
       }
     }
   }
-  HIP_TRY(c, hipMalloc((void**)&c->d_hcp_xq, xq.size()));
-  HIP_TRY(c, hipMalloc((void**)&c->d_hcp_scale, sizeof(scale)));
+  HIP_TRY(c, c->d_hcp_xq.alloc(xq.size()));
+  HIP_TRY(c, c->d_hcp_scale.alloc(sizeof(scale)));
   HIP_TRY(c, hipMemcpy(c->d_hcp_xq, xq.data(), xq.size(), hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(c->d_hcp_scale, scale, sizeof(scale), hipMemcpyHostToDevice));
   c->hcp_planes_state = 1;
@@ -1408,12 +1348,12 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
   }
   int rc = ensure_arena(c, sl, total + 4096);
   if (rc) return rc;
-  char* base = sl.arena.base;
+  char* base = sl.arena;
   // ---- host staging: descriptors + af ------------------------------------------------------------------
   const size_t stage_bytes = sizeof(GeneDesc) * n + sizeof(double) * af_total + sizeof(rvt_gene_result) * n + 64;
   rc = ensure_stage(c, sl, stage_bytes);
   if (rc) return rc;
-  GeneDesc* h_desc = reinterpret_cast<GeneDesc*>(sl.h_stage);
+  GeneDesc* h_desc = reinterpret_cast<GeneDesc*>(sl.h_stage.get());
   double* h_af = reinterpret_cast<double*>(sl.h_stage + sizeof(GeneDesc) * n);
   size_t afpos = 0;
   for (int g = 0; g < n; ++g) {
@@ -2033,21 +1973,14 @@ int rvt_fit_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
   if (rc) return rc;
   hipStream_t st = c->stream;
   const bool binary = trait == RVT_TRAIT_BINARY;
-  double *d_xy = nullptr, *d_part = nullptr, *d_beta = nullptr, *d_a = nullptr, *d_b = nullptr, *d_zero = nullptr;
-  struct Guard {
-    double **a, **b, **c2, **d2, **e, **f;
-    ~Guard() {
-      for (double** p : {a, b, c2, d2, e, f})
-        if (*p) hipFree(*p);
-    }
-  } guard{&d_xy, &d_part, &d_beta, &d_a, &d_b, &d_zero};
+  DevBuf<double> d_xy, d_part, d_beta, d_a, d_b, d_zero;
   const int rec = lmm_rec_len(d);
-  HIP_TRY(c, hipMalloc((void**)&d_xy, sizeof(double) * (size_t)N * (d + 1)));  // X | y
-  HIP_TRY(c, hipMalloc((void**)&d_part, sizeof(double) * (size_t)kLmmBlocks * rec));
-  HIP_TRY(c, hipMalloc((void**)&d_beta, sizeof(double) * RVT_MAX_COV));
-  HIP_TRY(c, hipMalloc((void**)&d_a, sizeof(double) * (size_t)N));
-  HIP_TRY(c, hipMalloc((void**)&d_b, sizeof(double) * (size_t)N));
-  HIP_TRY(c, hipMalloc((void**)&d_zero, sizeof(double) * (size_t)N));
+  HIP_TRY(c, d_xy.alloc(sizeof(double) * (size_t)N * (d + 1)));  // X | y
+  HIP_TRY(c, d_part.alloc(sizeof(double) * (size_t)kLmmBlocks * rec));
+  HIP_TRY(c, d_beta.alloc(sizeof(double) * RVT_MAX_COV));
+  HIP_TRY(c, d_a.alloc(sizeof(double) * (size_t)N));
+  HIP_TRY(c, d_b.alloc(sizeof(double) * (size_t)N));
+  HIP_TRY(c, d_zero.alloc(sizeof(double) * (size_t)N));
   HIP_TRY(c, hipMemcpyAsync(d_xy, X, sizeof(double) * (size_t)N * d, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_xy + (size_t)N * d, y, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemsetAsync(d_zero, 0, sizeof(double) * (size_t)N, st));
@@ -2126,7 +2059,7 @@ int rvt_fit_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
     c->have_null_beta = true;
     if (binary) {  // the per-variant logistic fits of rvt_wald_block start from y (zero-padded to the block's ld)
       const size_t vb = sizeof(double) * (size_t)c->null_ld;
-      HIP_TRY(c, hipMalloc((void**)&c->d_null_y, vb));
+      HIP_TRY(c, c->d_null_y.alloc(vb));
       HIP_TRY(c, hipMemset(c->d_null_y, 0, vb));
       HIP_TRY(c, hipMemcpy(c->d_null_y, y, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
     }

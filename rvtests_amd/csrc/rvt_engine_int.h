@@ -62,15 +62,69 @@ namespace {
 
 constexpr int kMaxMT = 6;  // widest single-pass tile configuration instantiated below
 
-struct Arena {  // grow-only bump allocator over one device allocation
-  char* base = nullptr;
-  size_t cap = 0, off = 0;
-  void reset() { off = 0; }
-  void* take(size_t bytes, size_t align = 256) {
-    off = (off + align - 1) / align * align;
-    void* p = base + off;
-    off += bytes;
-    return p;
+// Wait for a stream by polling.  A blocking hipStreamSynchronize() relies on a completion interrupt; on a fresh box
+// one such wake-up was seen to go missing (the kernels had long finished while the host slept for seconds), so the
+// engine never blocks in the runtime: it spins briefly, then sleeps in 20 us slices between hipStreamQuery calls.
+hipError_t sync_stream(hipStream_t st) {
+  hipError_t e;
+  int spins = 0;
+  while ((e = hipStreamQuery(st)) == hipErrorNotReady) {
+    if (++spins > 64) {
+      struct timespec ts = {0, 20000};
+      nanosleep(&ts, nullptr);
+    }
+  }
+  return e;
+}
+
+// Owner of one device allocation (Pinned: one pinned host allocation) of T; `cap` is its size in BYTES.  Freed by reset()
+// and by the destructor, so the context's members and per-call temporaries need no teardown of their own.  It converts to
+// T* where a raw pointer is expected (kernel arguments, copies, pointer arithmetic).
+template <class T, bool Pinned = false>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p), std::swap(cap, o.cap); return *this; }
+  ~DevBuf() { reset(); }
+  T* get() const { return p; }
+  operator T*() const { return p; }
+  hipError_t reset() {
+    const hipError_t e = !p ? hipSuccess : Pinned ? hipHostFree((void*)p) : hipFree((void*)p);
+    p = nullptr, cap = 0;
+    return e;
+  }
+  // Grow-only: when fewer than `need` bytes are held, the old block is freed (after `sync` has drained, when given: its last
+  // reader may still be queued there) and `want` bytes are allocated — uninitialised, or filled with the RVT_POISON byte
+  // when `poison` is set (tests: no result may depend on what a fresh allocation happens to hold).
+  hipError_t grow(size_t need, size_t want, hipStream_t sync = nullptr, bool poison = false, unsigned flags = 0) {
+    if (cap >= need) return hipSuccess;
+    hipError_t e = (p && sync) ? sync_stream(sync) : hipSuccess;
+    if (e == hipSuccess) e = reset();
+    if (e != hipSuccess) return e;
+    void* q = nullptr;
+    e = Pinned ? hipHostMalloc(&q, want, flags) : hipMalloc(&q, want);
+    if (e != hipSuccess) return e;
+    p = static_cast<T*>(q), cap = want;
+    if (const char* v = poison ? getenv("RVT_POISON") : nullptr) e = hipMemset(q, atoi(v) & 0xff, want);
+    return e;
+  }
+  hipError_t alloc(size_t bytes, unsigned flags = 0) {  // a fresh block of `bytes`
+    reset();
+    return grow(bytes, bytes, nullptr, false, flags);
+  }
+};
+template <class T>
+using PinBuf = DevBuf<T, true>;
+
+// 256-byte-aligned offsets of the sub-buffers of one work-space allocation, in one pass: `total` is the bytes to allocate
+struct Layout {
+  size_t total = 0;
+  size_t take(size_t bytes) {
+    const size_t o = total;
+    total += (bytes + 255) / 256 * 256;
+    return o;
   }
 };
 
@@ -86,9 +140,8 @@ struct ProfEvent {
 // batch i+1 (sufficient statistics) on a second HIP stream.
 struct Slot {
   hipStream_t stream = nullptr;
-  Arena arena;
-  char* h_stage = nullptr;
-  size_t h_stage_cap = 0;
+  DevBuf<char> arena;   // the batch's work space (grow-only)
+  PinBuf<char> h_stage;
   rvt_gene_result* pending_out = nullptr;
   bool* pending_done = nullptr;  // set when the batch's records have been handed over (streaming interface)
   rvt_gene_result* h_results = nullptr;
@@ -113,92 +166,83 @@ struct rvt_ctx {
   int64_t kin_N = 0;
   // eigenvectors of the kinship as kRotPlanesU signed base-128 digit planes (rot_gemm.hip.h): plane p at
   // d_Uq + p * uq_plane, row k (= column k of U) at k * uq_ldk; scaled by 2^uq_sexp
-  signed char* d_Uq = nullptr;
+  DevBuf<signed char> d_Uq;
   // sparse form of U (<= 64 non-zeros per eigenvector on average: families in any sample order), column-compressed;
   // used by the rotation when the K-chunk ranges (d_uq_range) do not apply; null otherwise
-  long long* d_csc_ptr = nullptr;
+  DevBuf<long long> d_csc_ptr;
   // row-compressed copy of the same sparse U (U v for rvt_fit_grammar_null), made from d_csc_* on first use
-  long long* d_csr_ptr = nullptr;
-  int* d_csr_cols = nullptr;
-  double* d_csr_vals = nullptr;
-  int* d_csc_rows = nullptr;
-  double* d_csc_vals = nullptr;
-  int2* d_uq_range = nullptr;  // per 256-row panel of the planes: K chunks [x, y) that hold its non-zeros; null = dense U
+  DevBuf<long long> d_csr_ptr;
+  DevBuf<int> d_csr_cols;
+  DevBuf<double> d_csr_vals;
+  DevBuf<int> d_csc_rows;
+  DevBuf<double> d_csc_vals;
+  DevBuf<int2> d_uq_range;  // per 256-row panel of the planes: K chunks [x, y) that hold its non-zeros; null = dense U
   double uq_visit = 1.0;       // fraction of the K chunks the rotation visits (1 = dense)
   size_t uq_plane = 0;
   int64_t uq_ldk = 0, uq_rows_pad = 0;
   int uq_sexp = 0;
-  signed char* d_rotB = nullptr;  // digit planes of the columns being rotated (B side of an integer-plane product)
-  size_t rotB_cap = 0;
-  signed char* d_rotA = nullptr;  // A side of gemm_tn_planes
-  size_t rotA_cap = 0;
-  double* d_rot_scale = nullptr;  // per-column scale (RVT_ROT_MAXCOLS doubles) | column maxima
-  int* d_rot_sexp = nullptr;
-  double* d_S = nullptr;   // N raw eigenvalues
-  double* d_u1 = nullptr;  // U'1
+  DevBuf<signed char> d_rotB;  // digit planes of the columns being rotated (B side of an integer-plane product)
+  DevBuf<signed char> d_rotA;  // A side of gemm_tn_planes
+  DevBuf<double> d_rot_scale;  // per-column scale (RVT_ROT_MAXCOLS doubles) | column maxima
+  DevBuf<int> d_rot_sexp;
+  DevBuf<double> d_S;   // N raw eigenvalues
+  DevBuf<double> d_u1;  // U'1
   std::vector<double> h_S, h_u1;
-  double* d_uxy = nullptr;  // N x (d+1): U'X | U'y
-  double* d_lmm_part = nullptr;
+  DevBuf<double> d_uxy;  // N x (d+1): U'X | U'y
+  DevBuf<double> d_lmm_part;
   NullConsts fam_nc;
-  NullConsts* d_fam_nc = nullptr;
-  double *d_fX = nullptr, *d_frr = nullptr, *d_fv = nullptr, *d_fzeros = nullptr, *d_fbeta = nullptr;
+  DevBuf<NullConsts> d_fam_nc;
+  DevBuf<double> d_fX, d_frr, d_fv, d_fzeros, d_fbeta;
   // family MetaCov null set + constants
   NullConsts famcov_nc;
-  NullConsts* d_famcov_nc = nullptr;
-  double *d_cX = nullptr, *d_cv = nullptr;
+  DevBuf<NullConsts> d_famcov_nc;
+  DevBuf<double> d_cX, d_cv;
   double fam_delta = 0.0;   // delta of the fitted FastLMM null (rvt_fam_null_summary)
   double famcov_b2 = 1.0;  // MetaCovFamBinary: b^2
   double famcov_k1r = 0.0; // u1' D uResid
-  double* d_cr = nullptr;  // uResid (the rr column of the family-covariance null set)
+  DevBuf<double> d_cr;  // uResid (the rr column of the family-covariance null set)
   double famcov_c11 = 0.0, famcov_c1x[RVT_MAX_COV], famcov_zz[RVT_MAX_COV * RVT_MAX_COV],
          famcov_zzinv[RVT_MAX_COV * RVT_MAX_COV];
-  double* d_Gp = nullptr;  // flipped / filtered genotypes of a FamSKAT batch (ld x T)
-  double* d_Gt = nullptr;  // ... rotated by U'
-  char* d_bedbatch = nullptr;   // rvt_submit_genes kind 7: row / gene references and partial counts of one call
-  size_t bedbatch_cap = 0;
+  DevBuf<double> d_Gp;  // flipped / filtered genotypes of a FamSKAT batch (ld x T)
+  DevBuf<double> d_Gt;  // ... rotated by U'
+  DevBuf<char> d_bedbatch;   // rvt_submit_genes kind 7: row / gene references and partial counts of one call
   bool no_i8_pack = false;      // submit_common: this int8 gene holds a value above 2 — send its bytes
   // gene_tnull_hcp: eight digit planes of [X | rr] in operand order + the columns' scales (quantitative null models)
-  unsigned char* d_hcp_xq = nullptr;
-  double* d_hcp_scale = nullptr;
+  DevBuf<unsigned char> d_hcp_xq;
+  DevBuf<double> d_hcp_scale;
   int hcp_planes_state = 0;     // 0 not built for this null model, 1 ready, -1 the model's columns cannot be carried
   int submit_group = 32;   // genes per asynchronous sub-batch of the streaming interface (RVT_SUBMIT_GROUP, rvt_set_submit_group)
-  size_t fam_cols_cap = 0;
   int64_t fam_cols_ld = 0;  // (the leading dimension d_Gp / d_Gt were sized for)
   // raw / packed genotype submission
-  double* d_consol_af = nullptr;  // af (RVT_MAX_VARIANTS) | fill values (RVT_MAX_VARIANTS)
-  size_t consol_af_cap = 0;
-  ConsolPart* d_consol_parts = nullptr;
-  size_t consol_parts_cap = 0;
+  DevBuf<double> d_consol_af;  // af (RVT_MAX_VARIANTS) | fill values (RVT_MAX_VARIANTS)
+  DevBuf<ConsolPart> d_consol_parts;
   // allele frequencies of raw / packed submissions whose caller did not ask for them: written into a ring slot and
   // copied back asynchronously; resolved (one stream wait) when the gene's group is launched
   static constexpr int kAfSlots = 128;
-  double* h_af_ring = nullptr;  // kAfSlots x RVT_MAX_VARIANTS, pinned and device-mapped: the kernels write it directly
+  PinBuf<double> h_af_ring;  // kAfSlots x RVT_MAX_VARIANTS, pinned and device-mapped: the kernels write it directly
   unsigned long long af_seq = 0;
   int af_unresolved = 0;
-  void* d_consol_i8 = nullptr;
-  size_t consol_i8_cap = 0;
+  DevBuf<void> d_consol_i8;
   // packed hand-offs from the host (int8 / 2-bit): a ring of landing buffers and a copy stream of their own, so that the DMA of
   // gene g + 1 runs while the consolidation kernels of gene g read another buffer (one stream serialised them: 3.3 k
   // 2-bit genes/s where the link carries 8 k)
   static constexpr int kPack = 16;  // landing buffers: a consolidation delayed by a batch launch does not stop the copies
-  void* d_pack[kPack] = {};
-  size_t pack_cap[kPack] = {};
+  DevBuf<void> d_pack[kPack];
   hipEvent_t ev_pack_copied[kPack] = {}, ev_pack_free[kPack] = {};
   int pack_next = 0;
   hipStream_t copy_stream = nullptr;
   hipStream_t h2d_stream = nullptr;  // where staged_h2d enqueues: io_stream, or copy_stream for the packed hand-offs
-  double* d_rot_part = nullptr;  // split-K partial results of the integer GEMM
+  DevBuf<double> d_rot_part;  // split-K partial results of the integer GEMM
   int band_last_path = -1;       // which product the last rvt_cov_band took (rvt_cov_band_last_path)
-  double* d_mu_nan = nullptr;    // packed_columns_pass: the other values of up to kColQueue columns (NaN = none)
-  char* d_colpack = nullptr;     // rvt_block_upload_columns: the columns as 2-bit rows + their other values, before they are expanded
-  size_t colpack_cap = 0;
+  DevBuf<double> d_mu_nan;    // packed_columns_pass: the other values of up to kColQueue columns (NaN = none)
+  DevBuf<char> d_colpack;     // rvt_block_upload_columns: the columns as 2-bit rows + their other values, before they are expanded
   // single columns uploaded one call at a time (MetaCovTest / MetaScoreTest: one site per fit()) are packed into pinned memory
   // and QUEUED: the DMA, the expansion and the column pass run once per kColQueue consecutive columns (flush_col_queue) — the
   // per-call device work (eight HIP calls, ~70 us) was what held the adapter at 9 k sites/s.  Everything that reads a block
   // flushes first (rvt_sync, the column operations).
   static constexpr int kColQueue = 32;
   struct ColQueue {
-    unsigned char* h[2] = {nullptr, nullptr};  // pinned, kColQueue rows of `pitch` bytes each
+    PinBuf<unsigned char> h[2];  // kColQueue rows of `pitch` bytes each
     hipEvent_t ev[2] = {nullptr, nullptr};     // recorded behind the DMA that read h[k]
     bool used[2] = {false, false};
     size_t pitch = 0;
@@ -207,10 +251,8 @@ struct rvt_ctx {
     double mu[kColQueue];
     int hard[kColQueue];
   } colq;
-  char* d_cov_work = nullptr;    // work space of the MetaCov rectangles (S, T, the band, column statistics): grow-only
+  DevBuf<char> d_cov_work;    // work space of the MetaCov rectangles (S, T, the band, column statistics): grow-only
   hipEvent_t ev_band_fin[2] = {}, ev_band_copied[2] = {};  // rvt_cov_band: a pass's rows are copied out while the next pass multiplies
-  size_t cov_work_cap = 0;
-  size_t rot_part_cap = 0;
   // per-column content flags of blocks filled column by column (rvt_block_upload_columns): nonzero = hard calls only
   // Round 5: ... and, for a ring that MetaCov will read (unweighted model), what the column pass of the hard-call band would
   // compute for the column anyway — the int8 copy, the column sum, the polymorphic flag and its row of T = G'X — made by the
@@ -218,67 +260,49 @@ struct rvt_ctx {
   // flush starts at the integer product.  `valid[j]`: column j's entries were made under null model number `gen`.
   struct ColKind {
     int cols = 0;
-    int* d_flags = nullptr;
-    signed char* d_i8 = nullptr;  // [cols rounded up + a tile of slack][ldk]
-    unsigned char* d_i4 = nullptr;  // [cols][ldk4]: the same hard calls as E2M1 codes, two per byte (band_gemm.hip.h, FP4)
-    unsigned char* d_m4 = nullptr;  // [cols][ldk4]: round 6 — the mask of a column's ONE other value (the imputed mean), same codes
-    double* d_mu = nullptr;         // [cols]: that other value (0 for a column without one)
+    DevBuf<int> d_flags;
+    DevBuf<signed char> d_i8;    // [cols rounded up + a tile of slack][ldk]
+    DevBuf<unsigned char> d_i4;  // [cols][ldk4]: the same hard calls as E2M1 codes, two per byte (band_gemm.hip.h, FP4)
+    DevBuf<unsigned char> d_m4;  // [cols][ldk4]: round 6 — the mask of a column's ONE other value (the imputed mean), same codes
+    DevBuf<double> d_mu;         // [cols]: that other value (0 for a column without one)
     int64_t ldk4 = 0;
     bool cache_failed = false;  // the cache could not be allocated once: not retried for this block
-    double* d_cs = nullptr;       // [cols] column sums
-    int* d_poly = nullptr;        // [cols]
-    double* d_T = nullptr;        // [cols][RVT_MAX_COV]
+    DevBuf<double> d_cs;    // [cols] column sums
+    DevBuf<int> d_poly;     // [cols]
+    DevBuf<double> d_T;     // [cols][RVT_MAX_COV]
     int64_t ldk = 0;
     uint64_t gen = 0;
     std::vector<unsigned char> valid;  // per column: 0 nothing known / not usable, 1 hard calls only, 2 hard calls + one other value
-    void release() {
-      for (void* q : {(void*)d_flags, (void*)d_i8, (void*)d_i4, (void*)d_m4, (void*)d_mu, (void*)d_cs, (void*)d_poly, (void*)d_T})
-        if (q) hipFree(q);
-      d_flags = nullptr;
-      d_i8 = nullptr;
-      d_i4 = nullptr;
-      d_m4 = nullptr;
-      d_mu = nullptr;
-      d_cs = nullptr;
-      d_poly = nullptr;
-      d_T = nullptr;
-      valid.clear();
-    }
   };
   int handed_back_recently = 0;   // > 0: a hard-call gene was handed back within the last 16 batches (launch_suffstat's list grid)
   uint64_t null_gen = 0;          // counts rvt_set_null / rvt_fit_null: a column cache made under another model is not used
-  double* d_cc_part = nullptr;    // slice partials of the one-column pass (64 slices x (RVT_MAX_COV + 3))
+  DevBuf<double> d_cc_part;    // slice partials of the one-column pass (64 slices x (RVT_MAX_COV + 3))
   std::unordered_map<const double*, ColKind> col_kind;
   // VCF text front end (vcf_kernels.hip.h)
-  char* d_vcf_text = nullptr;   // the text / block buffer of the gene being submitted: text_buf[text_cur]
+  char* d_vcf_text = nullptr;   // the text / block buffer of the gene being submitted: aliases text_buf[text_cur]
   static constexpr int kTextBufs = 3;  // ring: the copies of gene g + 1 run while the decode kernels of gene g read theirs
-  char* text_buf[kTextBufs] = {};
-  size_t text_buf_cap[kTextBufs] = {};
+  DevBuf<char> text_buf[kTextBufs];
   hipEvent_t ev_text_copied[kTextBufs] = {}, ev_text_free[kTextBufs] = {};
   int text_next = 0, text_cur = 0;
-  size_t vcf_text_cap = 0;
-  VcfRecord* d_vcf_rec = nullptr;
-  int* d_vcf_seg = nullptr;
-  size_t vcf_seg_cap = 0;
-  int* d_vcf_rows = nullptr;   // output row of every sample column of the file (-1: not analysed)
+  DevBuf<VcfRecord> d_vcf_rec;
+  DevBuf<int> d_vcf_seg;
+  DevBuf<int> d_vcf_rows;   // output row of every sample column of the file (-1: not analysed)
   int vcf_n_file = 0;
   int64_t vcf_n_rows = 0;      // rows the map addresses (must equal the null model's N)
   VcfFilters vcf_flt{0, 0, 0, 0};
   std::vector<int> vcf_alt;    // rvt_vcf_set_alt_alleles: alternative-allele index per record of the NEXT VCF call
   bool vcf_dosage = false;     // rvt_vcf_set_dosage: the index handed over is a dosage tag's, values through atof
   // BGEN probability blocks (bgen_kernels.hip.h); the blocks are staged in d_vcf_text
-  char* d_fam_list = nullptr;  // rvt_run_fam_tests: column pointers + flags of a batch (grow-only)
-  size_t fam_list_cap = 0;
-  signed char* d_vcf_sex = nullptr;  // PLINK sex code per file sample (rvt_vcf_set_sex); hemizygous records only
+  DevBuf<char> d_fam_list;  // rvt_run_fam_tests: column pointers + flags of a batch (grow-only)
+  DevBuf<signed char> d_vcf_sex;  // PLINK sex code per file sample (rvt_vcf_set_sex); hemizygous records only
   std::vector<int> vcf_hemi;         // per record of the NEXT decode call (rvt_vcf_set_hemi)
-  BgenRecord* d_bgen_rec = nullptr;
-  long long* d_bgen_seg = nullptr;
-  size_t bgen_seg_cap = 0;
+  DevBuf<BgenRecord> d_bgen_rec;
+  DevBuf<long long> d_bgen_seg;
   // pinned, device-visible input-error words of the VCF / BGEN decoders: record index + 1 of a record with a wrong column
   // count (negative: a dosage the device cannot round exactly) resp. variant index + 1 of a block shorter than its ploidy
   // bytes demand.  One word per allele-frequency ring slot (the streaming submissions: read when the gene's frequencies
   // are resolved, so the error lands on the gene that caused it) + word kAfSlots for the synchronous calls.
-  int* h_io_err = nullptr;
+  PinBuf<int> h_io_err;
   // ---- SKAT permutations: the emulated glibc rand() stream (TYPE_3), oldest word first ----
   // Permutation mode: exact (the DEFAULT of a single context: `--kernel skat[nPerm=..]` reproduces the reference's
   // ActualPerm / NumGreater / NumEqual / PermPvalue) = the reference's own rand() stream replayed (one sequential stream in
@@ -288,16 +312,14 @@ struct rvt_ctx {
   // deals genes over more than one member (rvt_group_init).
   bool perm_exact = true;
   uint64_t perm_seed = 1;
-  double* d_pc_part = nullptr;  // counter mode: partial products [slice][shuffle][variant]
-  size_t pc_part_cap = 0;
-  double* d_pc_Q = nullptr;
+  DevBuf<double> d_pc_part;  // counter mode: partial products [slice][shuffle][variant]
+  DevBuf<double> d_pc_Q;
   uint32_t rand_state[31];
   int64_t jump_N = -1;                 // J = A^(jump_N - 1) is cached for this sample count
   std::vector<uint32_t> jump;          // 31 x 31, row-major
-  uint32_t* d_perm_idx = nullptr;      // N x B
-  uint32_t* d_perm_states = nullptr;   // B x 31
-  double *d_perm_R = nullptr, *d_perm_C = nullptr, *d_perm_Q = nullptr, *d_perm_cur = nullptr;
-  size_t perm_cap_NB = 0, perm_cap_BM = 0, perm_cap_N = 0;
+  DevBuf<uint32_t> d_perm_idx;      // N x B
+  DevBuf<uint32_t> d_perm_states;   // B x 31
+  DevBuf<double> d_perm_R, d_perm_C, d_perm_Q, d_perm_cur;
   int perm_cap_B = 0;
   hipEvent_t ev_in[kSlotsAll] = {}, ev_k2[kSlotsAll] = {}, ev_k2b[kSlotsAll] = {};
   // The p-value kernel on CUs of its own (RVT_PV_CUS, see rvt_init): two streams restricted to the first pv_cus mask bits,
@@ -312,11 +334,12 @@ struct rvt_ctx {
   static constexpr int kStageChunks = 4;
   static constexpr size_t kStageBytes = (size_t)32 << 20;
   StageRing stage;
+  PinBuf<char> stage_buf[kStageChunks];  // the memory of stage.chunk
   hipEvent_t stage_ev[kStageChunks] = {};
   bool stage_on = true;
   static constexpr int kSmallSlots = 8;
   static constexpr size_t kSmallBytes = (size_t)128 << 10;
-  char* h_small = nullptr;      // pinned: kSmallSlots x kSmallBytes (record tables of the VCF / BGEN decoders)
+  PinBuf<char> h_small;      // kSmallSlots x kSmallBytes (record tables of the VCF / BGEN decoders)
   hipEvent_t small_ev[kSmallSlots] = {};
   int small_next = 0;
   // RVT_TRACE_SUBMIT=1: host seconds spent in the phases of the streaming submissions, printed by rvt_destroy
@@ -329,21 +352,25 @@ struct rvt_ctx {
   // null model
   bool have_null = false;
   NullConsts nc;
+  // the null set the kernels read: raw pointers into the buffers below, which the family paths point at a family set for
+  // the length of a call (famcov_run, Swap)
   NullConsts* d_nc = nullptr;
   double *d_X = nullptr, *d_res = nullptr, *d_rr = nullptr, *d_v = nullptr, *d_zeros = nullptr;
-  double* d_nulltile = nullptr;  // ONE allocation [X_0 .. X_{d-1} | rr | zeros]: d_X, d_rr and d_zeros point into it
+  DevBuf<NullConsts> nc_buf;
+  DevBuf<double> d_nulltile;  // ONE allocation [X_0 .. X_{d-1} | rr | zeros]: d_X, d_rr and d_zeros point into it
+  DevBuf<double> res_buf, v_buf;
   // binary trait: the weighted hard-call kernel's tile [vX_0 .. vX_{d-1} | res | v | zeros] and the digit planes of v
-  double* d_nulltile_w = nullptr;
-  unsigned char* d_vq = nullptr;
+  DevBuf<double> d_nulltile_w;
+  DevBuf<unsigned char> d_vq;
   // ... and the integer operands of the workgroup-cooperative kernel (suffstat_hcx.hip.h): the digits of v and of the null
   // tile in operand order, the power-of-two scale of every null column (host copy in hcx_tile, device copy for gene_assemble)
-  unsigned char *d_dq = nullptr, *d_xq = nullptr;
-  double* d_xscale = nullptr;
+  DevBuf<unsigned char> d_dq, d_xq;
+  DevBuf<double> d_xscale;
   NullTileX hcx_tile;
   bool hcx_ok = false;
   // ... and of the float-digit dosage kernel (suffstat_fdx.hip.h; quantitative trait): five base-256 digit planes of [X | res | 1]
   bool reg_defer = false;  // inside rvt_submit_genes: the wait for the DMAs out of registered caller memory comes once, at the end
-  unsigned char* d_fxq = nullptr;
+  DevBuf<unsigned char> d_fxq;
   NullTileF fdx_tile;
   bool fdx_ok = false;
   bool dosage_float = false;  // rvt_set_dosage_float: blocks of unknown content hold float-precision dosages
@@ -368,24 +395,21 @@ struct rvt_ctx {
   hipStream_t reg_stream = nullptr;  // the stream ev_reg was last recorded on
   bool reg_pending = false;
   int lattice_den = 0;        // rvt_set_dosage_lattice: dosage doubles are multiples of 1 / lattice_den (0: not stated)
-  int* d_kind = nullptr;      // device flag of rvt_block_classify (a stateless query)
+  DevBuf<int> d_kind;      // device flag of rvt_block_classify (a stateless query)
   bool hc_enabled = true;     // RVT_HARDCALL=0 forces the general kernel (experiments)
   double null_beta[RVT_MAX_COV] = {};  // estimates of the model rvt_fit_null fitted
   bool have_null_beta = false;
-  double* d_null_y = nullptr;  // rvt_fit_null with a binary trait: y (ld doubles, zero-padded) for the per-variant Wald fits
+  DevBuf<double> d_null_y;  // rvt_fit_null with a binary trait: y (ld doubles, zero-padded) for the per-variant Wald fits
   // rvt_wald_block's work space (wald_logistic.hip.h): one grow-only allocation, never touched inside the round loop
-  char* d_wald_ws = nullptr;
-  size_t wald_ws_cap = 0;
+  DevBuf<char> d_wald_ws;
   // single-variant tests for related samples (fam_single.hip.h): grow-only work spaces of rvt_lrt_block_fam and of
   // rvt_fit_grammar_null / rvt_grammar_block, their null constants, and the generation of the FastLMM null they belong to
   uint64_t fam_gen = 0;        // counts rvt_fit_fam_null
   double fam_sigma2 = 0.0;     // sigma2_g of the fitted FastLMM null
-  char* d_lrt_ws = nullptr;
-  size_t lrt_ws_cap = 0;
+  DevBuf<char> d_lrt_ws;
   uint64_t lrt_gen = 0;        // fam_gen the famLRT constants were formed for (0: none)
   double lrt_ssr0 = 0.0, lrt_slog = 0.0;
-  char* d_gg_ws = nullptr;
-  size_t gg_ws_cap = 0;
+  DevBuf<char> d_gg_ws;
   bool have_grammar = false;
   int64_t gg_N = 0;
   int gg_d = 0;
@@ -449,47 +473,13 @@ int fail(rvt_ctx* c, int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(ctx, RVT_E_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
-// Wait for a stream by polling.  A blocking hipStreamSynchronize() relies on a completion interrupt; on a fresh box
-// one such wake-up was seen to go missing (the kernels had long finished while the host slept for seconds), so the
-// engine never blocks in the runtime: it spins briefly, then sleeps in 20 us slices between hipStreamQuery calls.
-hipError_t sync_stream(hipStream_t st) {
-  hipError_t e;
-  int spins = 0;
-  while ((e = hipStreamQuery(st)) == hipErrorNotReady) {
-    if (++spins > 64) {
-      struct timespec ts = {0, 20000};
-      nanosleep(&ts, nullptr);
-    }
-  }
-  return e;
-}
-
+// a slot's work space and pinned staging: grow-only, the old block freed once the slot's last batch has finished with it
 int ensure_arena(rvt_ctx* c, Slot& sl, size_t bytes) {
-  if (sl.arena.cap >= bytes) return RVT_OK;
-  if (sl.arena.base) {
-    HIP_TRY(c, sync_stream(sl.stream));
-    HIP_TRY(c, hipFree(sl.arena.base));
-    sl.arena.base = nullptr;
-    sl.arena.cap = 0;
-  }
-  const size_t want = bytes + bytes / 4;
-  HIP_TRY(c, hipMalloc((void**)&sl.arena.base, want));
-  sl.arena.cap = want;
-  // tests: fill the workspace with a byte pattern — no result may depend on what a fresh allocation happens to hold
-  if (const char* e = getenv("RVT_POISON")) HIP_TRY(c, hipMemset(sl.arena.base, atoi(e) & 0xff, want));
+  HIP_TRY(c, sl.arena.grow(bytes, bytes + bytes / 4, sl.stream, true));
   return RVT_OK;
 }
-
 int ensure_stage(rvt_ctx* c, Slot& sl, size_t bytes) {
-  if (sl.h_stage_cap >= bytes) return RVT_OK;
-  if (sl.h_stage) {
-    HIP_TRY(c, sync_stream(sl.stream));
-    HIP_TRY(c, hipHostFree(sl.h_stage));
-    sl.h_stage = nullptr;
-  }
-  const size_t want = bytes * 2;
-  HIP_TRY(c, hipHostMalloc((void**)&sl.h_stage, want, hipHostMallocDefault));
-  sl.h_stage_cap = want;
+  HIP_TRY(c, sl.h_stage.grow(bytes, bytes * 2, sl.stream));
   return RVT_OK;
 }
 

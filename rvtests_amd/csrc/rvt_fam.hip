@@ -8,21 +8,25 @@
 #include "tridiag_kernels.hip.h"
 #include "fam_single.hip.h"
 
+static void free_csc(rvt_ctx* c) {  // the column-compressed form of U
+  c->d_csc_ptr.reset();
+  c->d_csc_rows.reset();
+  c->d_csc_vals.reset();
+}
+
 extern "C" {
 
 int ensure_fam_cols(rvt_ctx* c, size_t T, int64_t ld) {
   // (the capacity is columns OF THIS LEADING DIMENSION: a context whose null model was replaced by one with more samples
   //  otherwise kept buffers of the old column length — a memory fault in the permutation stage, found in round 6)
-  if (T <= c->fam_cols_cap && ld <= c->fam_cols_ld) return RVT_OK;
-  if (c->d_Gp) hipFree(c->d_Gp);
-  if (c->d_Gt) hipFree(c->d_Gt);
-  c->d_Gp = c->d_Gt = nullptr;
-  const size_t want = std::max(T + T / 4, c->fam_cols_cap);
-  c->fam_cols_cap = 0;
+  const size_t cols = c->fam_cols_ld ? c->d_Gp.cap / (sizeof(double) * (size_t)c->fam_cols_ld) : 0;  // columns held
+  if (T <= cols && ld <= c->fam_cols_ld) return RVT_OK;
+  c->d_Gp.reset();
+  c->d_Gt.reset();
+  const size_t want = std::max(T + T / 4, cols);
   c->fam_cols_ld = 0;
-  HIP_TRY(c, hipMalloc((void**)&c->d_Gp, sizeof(double) * (size_t)ld * want));
-  HIP_TRY(c, hipMalloc((void**)&c->d_Gt, sizeof(double) * (size_t)ld * want));
-  c->fam_cols_cap = want;
+  HIP_TRY(c, c->d_Gp.alloc(sizeof(double) * (size_t)ld * want));
+  HIP_TRY(c, c->d_Gt.alloc(sizeof(double) * (size_t)ld * want));
   c->fam_cols_ld = ld;
   return RVT_OK;
 }
@@ -34,61 +38,42 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
   hipSetDevice(c->device);
   int rc = rvt_sync(c);
   if (rc) return rc;
-  for (double** p : {&c->d_S, &c->d_u1}) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-  }
-  if (c->d_Uq) hipFree(c->d_Uq);
-  c->d_Uq = nullptr;
-  if (c->d_uq_range) hipFree(c->d_uq_range);
-  c->d_uq_range = nullptr;
-  for (void** q : {(void**)&c->d_csc_ptr, (void**)&c->d_csc_rows, (void**)&c->d_csc_vals, (void**)&c->d_csr_ptr,
-                   (void**)&c->d_csr_cols, (void**)&c->d_csr_vals}) {
-    if (*q) hipFree(*q);
-    *q = nullptr;
-  }
+  c->d_S.reset();
+  c->d_u1.reset();
+  c->d_Uq.reset();
+  c->d_uq_range.reset();
+  free_csc(c);
+  c->d_csr_ptr.reset();
+  c->d_csr_cols.reset();
+  c->d_csr_vals.reset();
   c->uq_visit = 1.0;
   c->have_kin = c->have_fam = c->have_grammar = false;
-  HIP_TRY(c, hipMalloc((void**)&c->d_S, sizeof(double) * N));
-  HIP_TRY(c, hipMalloc((void**)&c->d_u1, sizeof(double) * N));
+  HIP_TRY(c, c->d_S.alloc(sizeof(double) * N));
+  HIP_TRY(c, c->d_u1.alloc(sizeof(double) * N));
   // U -> fixed-point digit planes (rot_gemm.hip.h).  Eigenvectors have |u| <= 1; entries up to 2 are representable.
   c->uq_ldk = (N + 127) / 128 * 128;
   c->uq_rows_pad = (N + kRotBM - 1) / kRotBM * kRotBM;
   c->uq_plane = (size_t)c->uq_rows_pad * (size_t)c->uq_ldk;
   c->uq_sexp = 7 * kRotPlanesU - 3;
-  HIP_TRY(c, hipMalloc((void**)&c->d_Uq, c->uq_plane * kRotPlanesU));
+  HIP_TRY(c, c->d_Uq.alloc(c->uq_plane * kRotPlanesU));
   HIP_TRY(c, hipMemsetAsync(c->d_Uq, 0, c->uq_plane * kRotPlanesU, c->stream));
   const long long csc_cap = 64ll * N;  // non-zeros the sparse form may hold
   std::vector<long long> csc_ptr((size_t)N + 1, 0);
   bool csc_ok = !getenv("RVT_KINSHIP_DENSE");
-  int* d_cnt = nullptr;
-  int* d_span = nullptr;  // first / last non-zero row of every column of U
-  struct SpanGuard {
-    int** p;
-    ~SpanGuard() {
-      if (*p) hipFree(*p);
-    }
-  } span_guard{&d_span};
+  DevBuf<int> d_span;  // first / last non-zero row of every column of U
   {  // whole columns at a time through a bounded staging buffer (the caller's U can be tens of GB): digits + column sums
     const int64_t cols_per = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)256 << 20) / N));
-    float* d_tmp = nullptr;
-    double* d_tmp64 = nullptr;
-    int* d_flag = nullptr;
-    struct TmpGuard {  // (every early return below leaves through HIP_TRY)
-      void** p[4];
-      ~TmpGuard() {
-        for (void** q : p)
-          if (*q) hipFree(*q);
-      }
-    } tmp_guard{{(void**)&d_tmp, (void**)&d_tmp64, (void**)&d_flag, (void**)&d_cnt}};
-    HIP_TRY(c, hipMalloc((void**)&d_span, sizeof(int) * 2 * (size_t)N));
-    HIP_TRY(c, hipMalloc((void**)&d_cnt, sizeof(int) * (size_t)cols_per));
-    HIP_TRY(c, hipMalloc((void**)&c->d_csc_ptr, sizeof(long long) * (size_t)(N + 1)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_csc_rows, sizeof(int) * (size_t)csc_cap));
-    HIP_TRY(c, hipMalloc((void**)&c->d_csc_vals, sizeof(double) * (size_t)csc_cap));
-    HIP_TRY(c, hipMalloc((void**)&d_tmp, sizeof(float) * (size_t)cols_per * N));
-    HIP_TRY(c, hipMalloc((void**)&d_tmp64, sizeof(double) * (size_t)cols_per * N));
-    HIP_TRY(c, hipMalloc((void**)&d_flag, sizeof(int)));
+    DevBuf<int> d_cnt, d_flag;
+    DevBuf<double> d_tmp64;
+    DevBuf<float> d_tmp;
+    HIP_TRY(c, d_span.alloc(sizeof(int) * 2 * (size_t)N));
+    HIP_TRY(c, d_cnt.alloc(sizeof(int) * (size_t)cols_per));
+    HIP_TRY(c, c->d_csc_ptr.alloc(sizeof(long long) * (size_t)(N + 1)));
+    HIP_TRY(c, c->d_csc_rows.alloc(sizeof(int) * (size_t)csc_cap));
+    HIP_TRY(c, c->d_csc_vals.alloc(sizeof(double) * (size_t)csc_cap));
+    HIP_TRY(c, d_tmp.alloc(sizeof(float) * (size_t)cols_per * N));
+    HIP_TRY(c, d_tmp64.alloc(sizeof(double) * (size_t)cols_per * N));
+    HIP_TRY(c, d_flag.alloc(sizeof(int)));
     HIP_TRY(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
     for (int64_t k0 = 0; k0 < N; k0 += cols_per) {
       const int64_t nc = std::min(cols_per, N - k0);
@@ -123,11 +108,7 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
     }
     int bad = 0;
     HIP_TRY(c, hipMemcpy(&bad, d_flag, sizeof(int), hipMemcpyDeviceToHost));
-    if (!csc_ok)
-      for (void** q : {(void**)&c->d_csc_ptr, (void**)&c->d_csc_rows, (void**)&c->d_csc_vals}) {
-        if (*q) hipFree(*q);
-        *q = nullptr;
-      }
+    if (!csc_ok) free_csc(c);
     if (bad) return fail(c, RVT_E_INVALID, "kinship eigenvectors have entries >= 2 in magnitude (not unit vectors)");
   }
   c->h_S.resize(N);
@@ -142,8 +123,7 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
     // visits only those (rot_gemm.hip.h: a_krange).  Exact — the skipped chunks are exact zeros.
     std::vector<int> span(2 * (size_t)N);
     HIP_TRY(c, hipMemcpy(span.data(), d_span, sizeof(int) * 2 * (size_t)N, hipMemcpyDeviceToHost));
-    hipFree(d_span);
-    d_span = nullptr;
+    d_span.reset();
     const int* lo = span.data();
     const int* hi = span.data() + N;
     std::vector<int> order((size_t)N);
@@ -166,10 +146,10 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
       bool identity = true;
       for (int64_t k = 0; k < N && identity; ++k) identity = order[k] == (int)k;
       if (!identity) {  // re-order the rows of every plane (one plane-sized scratch buffer) and S, U'1 with them
-        signed char* d_scratch = nullptr;
-        int* d_order = nullptr;
-        HIP_TRY(c, hipMalloc((void**)&d_scratch, c->uq_plane));
-        HIP_TRY(c, hipMalloc((void**)&d_order, sizeof(int) * (size_t)N));
+        DevBuf<signed char> d_scratch;
+        DevBuf<int> d_order;
+        HIP_TRY(c, d_scratch.alloc(c->uq_plane));
+        HIP_TRY(c, d_order.alloc(sizeof(int) * (size_t)N));
         HIP_TRY(c, hipMemcpy(d_order, order.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice));
         for (int p = 0; p < kRotPlanesU; ++p) {
           signed char* plane = c->d_Uq + (size_t)p * c->uq_plane;
@@ -178,8 +158,8 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
                              (long long)c->uq_ldk, plane);
         }
         HIP_TRY(c, sync_stream(c->stream));
-        hipFree(d_scratch);
-        hipFree(d_order);
+        d_scratch.reset();
+        d_order.reset();
         std::vector<double> s2((size_t)N), u2((size_t)N);
         for (int64_t r = 0; r < N; ++r) {
           s2[r] = c->h_S[order[r]];
@@ -189,20 +169,16 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
         c->h_u1.swap(u2);
         HIP_TRY(c, hipMemcpy(c->d_u1, c->h_u1.data(), sizeof(double) * N, hipMemcpyHostToDevice));
       }
-      HIP_TRY(c, hipMalloc((void**)&c->d_uq_range, sizeof(int2) * (size_t)nrp));
+      HIP_TRY(c, c->d_uq_range.alloc(sizeof(int2) * (size_t)nrp));
       HIP_TRY(c, hipMemcpy(c->d_uq_range, range.data(), sizeof(int2) * (size_t)nrp, hipMemcpyHostToDevice));
       c->uq_visit = frac;
-      for (void** q : {(void**)&c->d_csc_ptr, (void**)&c->d_csc_rows, (void**)&c->d_csc_vals}) {  // not needed then
-        if (*q) hipFree(*q);
-        *q = nullptr;
-      }
+      free_csc(c);  // not needed then
     } else if (c->d_csc_ptr) {
       // sparse eigenvectors whose supports are scattered over the samples (families interleaved in the sample order):
       // the rotation gathers (rot_sparse_kernel); eigenpairs stay in the caller's order.  The digit planes (6 N^2 bytes)
       // are never read in this mode: give them back.
       c->uq_visit = (double)csc_ptr[N] / ((double)N * (double)N);
-      hipFree(c->d_Uq);
-      c->d_Uq = nullptr;
+      c->d_Uq.reset();
     }
   }
   HIP_TRY(c, hipMemcpy(c->d_S, c->h_S.data(), sizeof(double) * N, hipMemcpyHostToDevice));
@@ -280,20 +256,16 @@ static int decompose_by_family(rvt_ctx* c, int64_t N, const float* K,
   }
   hipStream_t st = c->stream;
   struct Bufs {
-    double *A = nullptr, *R = nullptr, *lam = nullptr;
-    unsigned long long* maxcos = nullptr;
-    float* dU = nullptr;
-    int* meta = nullptr;
-    ~Bufs() {
-      for (void* p : {(void*)A, (void*)R, (void*)lam, (void*)maxcos, (void*)dU, (void*)meta})
-        if (p) hipFree(p);
-    }
+    DevBuf<double> A, R, lam;
+    DevBuf<unsigned long long> maxcos;
+    DevBuf<float> dU;
+    DevBuf<int> meta;
   } b;
   const size_t tile_bytes = sizeof(double) * (size_t)kJacP * kJacP;
-  HIP_TRY(c, hipMalloc((void**)&b.A, tile_bytes * nt));
-  HIP_TRY(c, hipMalloc((void**)&b.R, tile_bytes * nt));
-  HIP_TRY(c, hipMalloc((void**)&b.lam, sizeof(double) * kJacP * nt));
-  HIP_TRY(c, hipMalloc((void**)&b.maxcos, sizeof(unsigned long long)));
+  HIP_TRY(c, b.A.alloc(tile_bytes * nt));
+  HIP_TRY(c, b.R.alloc(tile_bytes * nt));
+  HIP_TRY(c, b.lam.alloc(sizeof(double) * kJacP * nt));
+  HIP_TRY(c, b.maxcos.alloc(sizeof(unsigned long long)));
   HIP_TRY(c, hipMemsetAsync(b.maxcos, 0, sizeof(unsigned long long), st));
   HIP_TRY(c, hipMemcpyAsync(b.A, A.data(), tile_bytes * nt, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(jac_small_eig_kernel, dim3((unsigned)nt), dim3(256), 0, st, b.A, 1, 1e-14, b.R, b.maxcos, 1, b.lam);
@@ -342,9 +314,9 @@ static int decompose_by_family(rvt_ctx* c, int64_t N, const float* K,
   for (size_t t = 0; t < nt; ++t)
     for (int r = 0; r < tlen[t]; ++r) meta[3 * (size_t)N + t * kJacP + r] = trow[t][r];
   if (U_out || install) {
-    HIP_TRY(c, hipMalloc((void**)&b.dU, sizeof(float) * (size_t)N * (size_t)N));
+    HIP_TRY(c, b.dU.alloc(sizeof(float) * (size_t)N * (size_t)N));
     HIP_TRY(c, hipMemsetAsync(b.dU, 0, sizeof(float) * (size_t)N * (size_t)N, st));
-    HIP_TRY(c, hipMalloc((void**)&b.meta, sizeof(int) * meta.size()));
+    HIP_TRY(c, b.meta.alloc(sizeof(int) * meta.size()));
     HIP_TRY(c, hipMemcpyAsync(b.meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(jac_scatter_blocks_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, b.R, b.meta,
                        b.meta + N, b.meta + 2 * N, b.meta + 3 * N, (long long)N, b.dU);
@@ -374,35 +346,22 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
   *done = false;
   // an allocation the device cannot serve (fragmentation, another context, the K-slice buffers of gemm_tn_f64) is not an error of
   // the call: the matrix goes to the Jacobi iteration (*done stays false), as the size check below promises
-#define TD_ALLOC(call)                                                                                                \
-  do {                                                                                                                \
-    if ((call) != hipSuccess) {                                                                                       \
-      (void)hipGetLastError();                                                                                        \
-      if (c->d_rot_part) {                                                                                            \
-        hipFree(c->d_rot_part);                                                                                       \
-        c->d_rot_part = nullptr;                                                                                      \
-        c->rot_part_cap = 0;                                                                                          \
-      }                                                                                                               \
-      if (trace) fprintf(stderr, "[rvt] tridiag: device allocation failed: left to the Jacobi iteration\n");          \
-      return RVT_OK;                                                                                                  \
-    }                                                                                                                 \
-  } while (0)
   hipStream_t st = c->stream;
   const bool trace = getenv("RVT_TRIDIAG_TRACE") != nullptr;
+  auto alloc_failed = [&]() {
+    (void)hipGetLastError();
+    c->d_rot_part.reset();
+    if (trace) fprintf(stderr, "[rvt] tridiag: device allocation failed: left to the Jacobi iteration\n");
+    return RVT_OK;
+  };
   const double t_start = now_s();
   const int n = (int)N;
   const int64_t ld = (N + 63) / 64 * 64;
   struct Bufs {
-    float* dK = nullptr;
-    float* dU = nullptr;
-    double *A = nullptr, *B1 = nullptr, *B2 = nullptr, *B3 = nullptr, *B4 = nullptr, *W = nullptr, *vec = nullptr, *cz = nullptr,
-           *yy = nullptr, *P = nullptr;
-    unsigned long long* worst = nullptr;
-    ~Bufs() {
-      for (void* p : {(void*)dK, (void*)dU, (void*)A, (void*)B1, (void*)B2, (void*)B3, (void*)B4, (void*)W, (void*)vec, (void*)cz,
-                      (void*)yy, (void*)P, (void*)worst})
-        if (p) hipFree(p);
-    }
+    DevBuf<float> dK;
+    DevBuf<float> dU;
+    DevBuf<double> A, B1, B2, B3, B4, W, vec, cz, yy, P;
+    DevBuf<unsigned long long> worst;
   } b;
   const size_t mat = sizeof(double) * (size_t)ld * (size_t)N;
   {
@@ -419,15 +378,15 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
       return RVT_OK;
     }
   }
-  TD_ALLOC(hipMalloc((void**)&b.dK, sizeof(float) * (size_t)N * (size_t)N));
-  TD_ALLOC(hipMalloc((void**)&b.A, mat));
-  TD_ALLOC(hipMalloc((void**)&b.W, sizeof(double) * (size_t)ld * kTdNb));
+  if (b.dK.alloc(sizeof(float) * (size_t)N * (size_t)N) != hipSuccess) return alloc_failed();
+  if (b.A.alloc(mat) != hipSuccess) return alloc_failed();
+  if (b.W.alloc(sizeof(double) * (size_t)ld * kTdNb) != hipSuccess) return alloc_failed();
   // vec: d | e | tau | y | t12 (2 kTdNb) | partial dots | scaled d | scaled e^2 | lambda
   const int64_t vs = std::max<int64_t>(ld, 1024);  // (y doubles as the panel's Gram matrix later)
   const int comb_blocks = (int)((N + 63) / 64);                   // workgroups of td_w_comb_kernel = partial dots per column
   const int64_t n_part = std::max<int64_t>(1024, comb_blocks);
   const size_t nv = 7 * (size_t)vs + 2 * kTdNb + (size_t)n_part;
-  TD_ALLOC(hipMalloc((void**)&b.vec, sizeof(double) * nv));
+  if (b.vec.alloc(sizeof(double) * nv) != hipSuccess) return alloc_failed();
   HIP_TRY(c, hipMemsetAsync(b.vec, 0, sizeof(double) * nv, st));
   HIP_TRY(c, hipMemsetAsync(b.W, 0, sizeof(double) * (size_t)ld * kTdNb, st));
   double *d_d = b.vec, *d_e = d_d + vs, *d_tau = d_e + vs, *d_y = d_tau + vs, *d_t12 = d_y + vs, *d_part = d_t12 + 2 * kTdNb, *d_ss = d_y,
@@ -436,7 +395,7 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
   hipLaunchKernelGGL(td_init_kernel, dim3(4096), dim3(256), 0, st, b.dK, (long long)N, (long long)ld, b.A);
   // 1. K = Q T Q'
   const int nblk = (int)((N + kSyT - 1) / kSyT);  // 64-row blocks of the matrix; P: the (nblk + 1) x ld partial products of a column step
-  TD_ALLOC(hipMalloc((void**)&b.P, sizeof(double) * (size_t)(nblk + 1) * (size_t)ld));
+  if (b.P.alloc(sizeof(double) * (size_t)(nblk + 1) * (size_t)ld) != hipSuccess) return alloc_failed();
   for (int j0 = 0; j0 < n; j0 += kTdNb) {
     const int j1 = std::min(n, j0 + kTdNb);
     for (int j = j0; j < j1; ++j) {
@@ -465,8 +424,7 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
   HIP_TRY(c, hipMemcpyAsync(hd.data(), d_d, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(he.data(), d_e, sizeof(double) * (size_t)(N - 1), hipMemcpyDeviceToHost, st));
   HIP_TRY(c, sync_stream(st));
-  hipFree(b.dK);
-  b.dK = nullptr;
+  b.dK.reset();
   const double t_tri = now_s();
   // 2. eigenvalues of T (scaled as coop_tridiag_eigvals scales: Gershgorin span into [1/2, 1), squares floored)
   double lo = hd[0], hi = hd[0];
@@ -510,7 +468,7 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
   // boundary stores (the closing check below holds the result to 1e-7 whatever this predicts)
   if (!(min_gap > 4e-9 * span0)) return RVT_OK;
   // 3. eigenvectors of T, a batch of columns at a time (the factors of a batch: three [row][eigenvector] arrays + the vectors)
-  TD_ALLOC(hipMalloc((void**)&b.B2, mat));
+  if (b.B2.alloc(mat) != hipSuccess) return alloc_failed();
   HIP_TRY(c, hipMemsetAsync(b.B2, 0, mat, st));
   {
     size_t free_b = 0, total_b = 0;
@@ -519,7 +477,7 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
     if (const char* e = getenv("RVT_TRIDIAG_BATCH")) nkb = std::max(64, atoi(e) / 64 * 64);  // (tests: several batches on a small matrix)
     nkb = std::max<int64_t>(64, std::min<int64_t>(nkb, ld));
     const size_t arr = sizeof(double) * (size_t)ld * (size_t)nkb;
-    TD_ALLOC(hipMalloc((void**)&b.B1, 4 * arr));
+    if (b.B1.alloc(4 * arr) != hipSuccess) return alloc_failed();
     double *zt = b.B1, *ud = zt + (size_t)ld * nkb, *uu = ud + (size_t)ld * nkb, *uw = uu + (size_t)ld * nkb;
     for (int64_t k0 = 0; k0 < N; k0 += nkb) {
       const int nk = (int)std::min<int64_t>(nkb, N - k0);
@@ -530,8 +488,7 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, sync_stream(st));
-    hipFree(b.B1);
-    b.B1 = nullptr;
+    b.B1.reset();
   }
   double* Z = b.B2;
   HIP_TRY(c, hipGetLastError());
@@ -539,8 +496,8 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
   const double t_vec = now_s();
   // 4. U = Q Z, the reflectors kTdNbb at a time in reverse order: G = V'V and V'Z (K = N), the back substitution with
   //    T^-1 = triu(G, 1) + diag(1 / tau), and Z -= V Y' (K = kTdNbb) — all three products on the matrix cores
-  TD_ALLOC(hipMalloc((void**)&b.cz, sizeof(double) * (size_t)ld * kTdNbb));
-  TD_ALLOC(hipMalloc((void**)&b.yy, sizeof(double) * (size_t)ld * kTdNbb * 2 + sizeof(double) * kTdNbb * kTdNbb));
+  if (b.cz.alloc(sizeof(double) * (size_t)ld * kTdNbb) != hipSuccess) return alloc_failed();
+  if (b.yy.alloc(sizeof(double) * (size_t)ld * kTdNbb * 2 + sizeof(double) * kTdNbb * kTdNbb) != hipSuccess) return alloc_failed();
   double *d_yt = b.yy, *d_vt = b.yy + (size_t)ld * kTdNbb, *d_gram = d_vt + (size_t)ld * kTdNbb;
   HIP_TRY(c, hipMemsetAsync(d_gram, 0, sizeof(double) * kTdNbb * kTdNbb, st));
   for (int j0 = ((n - 1) / kTdNbb) * kTdNbb; j0 >= 0; j0 -= kTdNbb) {
@@ -561,21 +518,17 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
   HIP_TRY(c, sync_stream(st));
   const double t_back = now_s();
   // 5. the closing check: max |K u - lambda u|, max |U'U - I|, in column batches (the product's K slices need room)
-  TD_ALLOC(hipMalloc((void**)&b.worst, 2 * sizeof(unsigned long long)));
+  if (b.worst.alloc(2 * sizeof(unsigned long long)) != hipSuccess) return alloc_failed();
   HIP_TRY(c, hipMemsetAsync(b.worst, 0, 2 * sizeof(unsigned long long), st));
   // (the reflectors are not needed any more: A takes the fp64 copy of K; the float upload is freed behind the conversion)
-  for (double** q : {&b.cz, &b.yy, &b.W, &b.P}) {
-    if (*q) hipFree(*q);
-    *q = nullptr;
-  }
-  TD_ALLOC(hipMalloc((void**)&b.dK, sizeof(float) * (size_t)N * (size_t)N));
+  for (DevBuf<double>* q : {&b.cz, &b.yy, &b.W, &b.P}) q->reset();
+  if (b.dK.alloc(sizeof(float) * (size_t)N * (size_t)N) != hipSuccess) return alloc_failed();
   HIP_TRY(c, hipMemcpyAsync(b.dK, K, sizeof(float) * (size_t)N * (size_t)N, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(td_init_kernel, dim3(4096), dim3(256), 0, st, b.dK, (long long)N, (long long)ld, b.A);
   HIP_TRY(c, sync_stream(st));
-  hipFree(b.dK);
-  b.dK = nullptr;
+  b.dK.reset();
   constexpr int kBatch = 1024;
-  TD_ALLOC(hipMalloc((void**)&b.B3, sizeof(double) * (size_t)ld * kBatch));
+  if (b.B3.alloc(sizeof(double) * (size_t)ld * kBatch) != hipSuccess) return alloc_failed();
   for (int k0 = 0; k0 < n; k0 += kBatch) {
     const int nk = std::min(kBatch, n - k0);
     int rc = gemm_tn_f64(c, b.A, ld, n, Z + (size_t)k0 * ld, ld, nk, nullptr, 0, 0, nullptr, ld, b.B3, ld, false, st);
@@ -597,28 +550,18 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
     fprintf(stderr, "[rvt] tridiag: vectors %.3f s, back-transformation %.3f s, check %.3f s: residual %.3g (scale %.3g), |U'U - I| %.3g\n",
             t_vec - t_eig, t_back - t_vec, t_chk - t_back, resid, span0, orth);
   if (!(resid <= 1e-9 * mu) || !(orth <= 1e-7)) {  // (mu = 4 x a bound on the spectral radius; Jacobi's own bar)
-    if (c->d_rot_part) {  // (the products' K slices: the Jacobi iteration that takes over needs the room)
-      hipFree(c->d_rot_part);
-      c->d_rot_part = nullptr;
-      c->rot_part_cap = 0;
-    }
+    c->d_rot_part.reset();  // (the products' K slices: the Jacobi iteration that takes over needs the room)
     return RVT_OK;
   }
   std::vector<float> S((size_t)N);
   for (int64_t j = 0; j < N; ++j) S[j] = (float)lam[j];
-  hipFree(b.A);
-  b.A = nullptr;
-  TD_ALLOC(hipMalloc((void**)&b.dU, sizeof(float) * (size_t)N * (size_t)N));
+  b.A.reset();
+  if (b.dU.alloc(sizeof(float) * (size_t)N * (size_t)N) != hipSuccess) return alloc_failed();
   hipLaunchKernelGGL(td_to_float_kernel, dim3(4096), dim3(256), 0, st, Z, (long long)ld, (long long)N, b.dU);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, sync_stream(st));
-  hipFree(b.B2);  // (Z: the installation below needs room for the digit planes of U)
-  b.B2 = nullptr;
-  if (c->d_rot_part) {  // (the K slices of the check's products: GBs at this size)
-    hipFree(c->d_rot_part);
-    c->d_rot_part = nullptr;
-    c->rot_part_cap = 0;
-  }
+  b.B2.reset();  // (Z: the installation below needs room for the digit planes of U)
+  c->d_rot_part.reset();  // (the K slices of the check's products: GBs at this size)
   if (U_out) HIP_TRY(c, hipMemcpy(U_out, b.dU, sizeof(float) * (size_t)N * (size_t)N, hipMemcpyDeviceToHost));
   if (S_out) std::memcpy(S_out, S.data(), sizeof(float) * (size_t)N);
   if (info) {
@@ -632,7 +575,6 @@ static int decompose_dense_tridiag(rvt_ctx* c, int64_t N, const float* K, double
   if (install) return rvt_set_kinship(c, N, b.dU, S.data());
   return RVT_OK;
 }
-#undef TD_ALLOC
 
 // ---- KinshipHolder::decompose on the device (jacobi_kernels.hip.h) ---------------------------------------------------------
 int rvt_kinship_decompose(rvt_ctx* c, int64_t N, const float* K, float* U_out, float* S_out, int install,
@@ -710,25 +652,21 @@ int rvt_kinship_decompose(rvt_ctx* c, int64_t N, const float* K, float* U_out, f
     if (rc || done) return rc;
   }
   struct Bufs {
-    float* dK = nullptr;
-    double *W = nullptr, *V = nullptr, *part = nullptr, *R = nullptr, *lam = nullptr;
-    unsigned long long* maxcos = nullptr;
-    float* dU = nullptr;
-    int* dsrc = nullptr;
-    ~Bufs() {
-      for (void* p : {(void*)dK, (void*)W, (void*)V, (void*)part, (void*)R, (void*)lam, (void*)maxcos, (void*)dU, (void*)dsrc})
-        if (p) hipFree(p);
-    }
+    DevBuf<float> dK;
+    DevBuf<double> W, V, part, R, lam;
+    DevBuf<unsigned long long> maxcos;
+    DevBuf<float> dU;
+    DevBuf<int> dsrc;
   } b;
   const size_t nn = (size_t)np * (size_t)np;
-  HIP_TRY(c, hipMalloc((void**)&b.V, sizeof(double) * nn));
+  HIP_TRY(c, b.V.alloc(sizeof(double) * nn));
   // row splits of the Gram pass / row slabs of the update: enough waves to fill the chip when there are few pairs
   const int splits = (int)std::max<int64_t>(1, std::min<int64_t>(np / 64, (1024 + pairs - 1) / pairs / 4));
   const int nparts = splits * 4, slabs = splits;
-  HIP_TRY(c, hipMalloc((void**)&b.part, sizeof(double) * (size_t)pairs * nparts * kJacP * kJacP));
-  HIP_TRY(c, hipMalloc((void**)&b.R, sizeof(double) * (size_t)pairs * kJacP * kJacP));
-  HIP_TRY(c, hipMalloc((void**)&b.lam, sizeof(double) * 2 * (size_t)np));
-  HIP_TRY(c, hipMalloc((void**)&b.maxcos, sizeof(unsigned long long)));
+  HIP_TRY(c, b.part.alloc(sizeof(double) * (size_t)pairs * nparts * kJacP * kJacP));
+  HIP_TRY(c, b.R.alloc(sizeof(double) * (size_t)pairs * kJacP * kJacP));
+  HIP_TRY(c, b.lam.alloc(sizeof(double) * 2 * (size_t)np));
+  HIP_TRY(c, b.maxcos.alloc(sizeof(unsigned long long)));
   const double tol = 1e-10;
   const int max_sweeps = 40;
   const int sort_mode = getenv("RVT_JACOBI_NOSORT") ? 0 : 1;
@@ -736,14 +674,13 @@ int rvt_kinship_decompose(rvt_ctx* c, int64_t N, const float* K, float* U_out, f
   double last = 0.0, shift = 0.0, worst_resid = 0.0;
   std::vector<double> lam((size_t)np), resid((size_t)np);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    if (!b.W) HIP_TRY(c, hipMalloc((void**)&b.W, sizeof(double) * nn));
-    HIP_TRY(c, hipMalloc((void**)&b.dK, sizeof(float) * (size_t)N * (size_t)N));
+    HIP_TRY(c, b.W.grow(sizeof(double) * nn, sizeof(double) * nn));
+    HIP_TRY(c, b.dK.alloc(sizeof(float) * (size_t)N * (size_t)N));
     HIP_TRY(c, hipMemcpyAsync(b.dK, K, sizeof(float) * (size_t)N * (size_t)N, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(jac_init_kernel, dim3(4096), dim3(256), 0, st, b.dK, (long long)N, (long long)np, mu + shift, shift,
                        b.W, b.V);
     HIP_TRY(c, sync_stream(st));
-    hipFree(b.dK);
-    b.dK = nullptr;
+    b.dK.reset();
     for (sweeps = 0; sweeps < max_sweeps;) {
       HIP_TRY(c, hipMemsetAsync(b.maxcos, 0, sizeof(unsigned long long), st));
       for (int r = 0; r < nb - 1; ++r) {
@@ -776,8 +713,7 @@ int rvt_kinship_decompose(rvt_ctx* c, int64_t N, const float* K, float* U_out, f
     shift = 0.26 * mu;  // mu = 4 x (bound on the spectral radius): K + shift I is positive definite
   }
   for (int64_t j = 0; j < np; ++j) lam[j] -= shift;
-  hipFree(b.W);  // (80 GB at N = 100 000: not needed any more)
-  b.W = nullptr;
+  b.W.reset();  // (80 GB at N = 100 000: not needed any more)
   std::vector<int> src;
   src.reserve((size_t)N);
   for (int64_t j = 0; j < np; ++j)
@@ -786,14 +722,13 @@ int rvt_kinship_decompose(rvt_ctx* c, int64_t N, const float* K, float* U_out, f
   std::stable_sort(src.begin(), src.end(), [&](int x, int y) { return lam[x] < lam[y]; });  // ascending, as Eigen returns them
   std::vector<float> S((size_t)N);
   for (int64_t j = 0; j < N; ++j) S[j] = (float)lam[src[j]];
-  HIP_TRY(c, hipMalloc((void**)&b.dsrc, sizeof(int) * (size_t)N));
+  HIP_TRY(c, b.dsrc.alloc(sizeof(int) * (size_t)N));
   HIP_TRY(c, hipMemcpyAsync(b.dsrc, src.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, hipMalloc((void**)&b.dU, sizeof(float) * (size_t)N * (size_t)N));
+  HIP_TRY(c, b.dU.alloc(sizeof(float) * (size_t)N * (size_t)N));
   hipLaunchKernelGGL(jac_gather_kernel, dim3((unsigned)N), dim3(256), 0, st, b.V, (long long)np, (long long)N, b.dsrc, b.dU);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, sync_stream(st));
-  hipFree(b.V);
-  b.V = nullptr;
+  b.V.reset();
   if (U_out) HIP_TRY(c, hipMemcpy(U_out, b.dU, sizeof(float) * (size_t)N * (size_t)N, hipMemcpyDeviceToHost));
   if (S_out) std::memcpy(S_out, S.data(), sizeof(float) * (size_t)N);
   if (info) {
@@ -820,8 +755,8 @@ struct QuantCols {       // digit planes of a set of columns, in a context-owned
 
 int ensure_rot_scratch(rvt_ctx* c) {
   if (!c->d_rot_scale) {
-    HIP_TRY(c, hipMalloc((void**)&c->d_rot_scale, sizeof(double) * 4 * kRotMaxCols));  // col | max | row | spare
-    HIP_TRY(c, hipMalloc((void**)&c->d_rot_sexp, sizeof(int) * kRotMaxCols));
+    HIP_TRY(c, c->d_rot_scale.alloc(sizeof(double) * 4 * kRotMaxCols));  // col | max | row | spare
+    HIP_TRY(c, c->d_rot_sexp.alloc(sizeof(int) * kRotMaxCols));
   }
   return RVT_OK;
 }
@@ -829,7 +764,7 @@ int ensure_rot_scratch(rvt_ctx* c) {
 // Quantise ncols <= kRotMaxCols columns of n_rows doubles (column-major, leading dimension ld_src) into planes laid out
 // [plane][column (padded to `pad`)][ldk].  One plane when every column holds integers in [-127, 127], else kRotPlanesG.
 int quantize_columns(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld_src, int ncols, int pad, int64_t ldk,
-                     signed char** buf, size_t* cap, hipStream_t st, QuantCols* out, bool known_hard_calls = false) {
+                     DevBuf<signed char>& buf, hipStream_t st, QuantCols* out, bool known_hard_calls = false) {
   int rc = ensure_rot_scratch(c);
   if (rc) return rc;
   double* d_max = c->d_rot_scale + kRotMaxCols;
@@ -853,14 +788,8 @@ int quantize_columns(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld
   const int64_t cols_pad = ((int64_t)ncols + pad - 1) / pad * pad;
   out->plane_stride = (size_t)cols_pad * (size_t)ldk;
   const size_t need = out->plane_stride * PG;
-  if (*cap < need) {
-    if (*buf) hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(c, hipMalloc((void**)buf, need + need / 4));
-    *cap = need + need / 4;
-  }
-  out->d = *buf;
+  HIP_TRY(c, buf.grow(need, need + need / 4));
+  out->d = buf;
   HIP_TRY(c, hipMemsetAsync(out->d, 0, need, st));
   HIP_TRY(c, hipMemcpyAsync(c->d_rot_sexp, out->sexp.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(rot_quantize_f64_kernel, dim3(2048), dim3(256), 0, st, d_src, (long long)n_rows, (long long)ncols,
@@ -911,13 +840,7 @@ int planes_gemm(rvt_ctx* c, const signed char* A, size_t a_stride, int PA, int n
   if (slices > 1) {
     c_slice = (long long)ldc * nB;
     const size_t need = sizeof(double) * (size_t)c_slice * (size_t)slices;
-    if (c->rot_part_cap < need) {
-      if (c->d_rot_part) hipFree(c->d_rot_part);
-      c->d_rot_part = nullptr;
-      c->rot_part_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_rot_part, need));
-      c->rot_part_cap = need;
-    }
+    HIP_TRY(c, c->d_rot_part.grow(need, need));
     d_part = c->d_rot_part;
   }
   if (a_krange && !row_exp) {
@@ -982,7 +905,7 @@ int rotate_columns(rvt_ctx* c, const double* d_src, int64_t ld_src, int ncols, d
   for (int c0 = 0; c0 < ncols; c0 += kRotMaxCols) {  // long lists in pieces
     const int nc = std::min(kRotMaxCols, ncols - c0);
     QuantCols qb;
-    int rc = quantize_columns(c, d_src + (size_t)c0 * ld_src, N, ld_src, nc, kRotBN, c->uq_ldk, &c->d_rotB, &c->rotB_cap, st,
+    int rc = quantize_columns(c, d_src + (size_t)c0 * ld_src, N, ld_src, nc, kRotBN, c->uq_ldk, c->d_rotB, st,
                               &qb);
     if (rc) return rc;
     rc = planes_gemm(c, c->d_Uq, c->uq_plane, kRotPlanesU, (int)N, nullptr, c->uq_sexp, qb.d, qb.plane_stride, qb.planes,
@@ -999,9 +922,9 @@ int gemm_tn_planes(rvt_ctx* c, const double* dA, int64_t ldA, int nA, const doub
   if (nA > kRotMaxCols || nB > kRotMaxCols) return fail(c, RVT_E_TOO_LARGE, "integer-plane product: too many columns");
   const int64_t ldk = (n_rows + 127) / 128 * 128;
   QuantCols qa, qb;
-  int rc = quantize_columns(c, dA, n_rows, ldA, nA, kRotBM, ldk, &c->d_rotA, &c->rotA_cap, st, &qa);
+  int rc = quantize_columns(c, dA, n_rows, ldA, nA, kRotBM, ldk, c->d_rotA, st, &qa);
   if (rc) return rc;
-  rc = quantize_columns(c, dB, n_rows, ldB, nB, kRotBN, ldk, &c->d_rotB, &c->rotB_cap, st, &qb);
+  rc = quantize_columns(c, dB, n_rows, ldB, nB, kRotBN, ldk, c->d_rotB, st, &qb);
   if (rc) return rc;
   return planes_gemm(c, qa.d, qa.plane_stride, qa.planes, nA, qa.sexp.data(), 0, qb.d, qb.plane_stride, qb.planes, nB,
                      qb.sexp.data(), n_rows, ldk, C, ldc, st);
@@ -1097,36 +1020,30 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
   if (rc) return rc;
   hipStream_t st = c->stream;
   const int64_t ld = rvt_padded_ld(N);
-  for (double** p : {&c->d_uxy, &c->d_lmm_part, &c->d_fX, &c->d_frr, &c->d_fv, &c->d_fzeros, &c->d_fbeta}) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-  }
+  for (DevBuf<double>* p : {&c->d_uxy, &c->d_lmm_part, &c->d_fX, &c->d_frr, &c->d_fv, &c->d_fzeros, &c->d_fbeta}) p->reset();
   c->have_fam = false;
   ++c->fam_gen;
   c->famcov_b2 = 1.0;
   const int dx = d + 1;
-  double* d_xy = nullptr;  // N x (d+1): X | y
-  HIP_TRY(c, hipMalloc((void**)&d_xy, sizeof(double) * (size_t)N * dx));
-  HIP_TRY(c, hipMalloc((void**)&c->d_uxy, sizeof(double) * (size_t)N * dx));
+  DevBuf<double> d_xy;  // N x (d+1): X | y
+  HIP_TRY(c, d_xy.alloc(sizeof(double) * (size_t)N * dx));
+  HIP_TRY(c, c->d_uxy.alloc(sizeof(double) * (size_t)N * dx));
   HIP_TRY(c, hipMemcpy(d_xy, X, sizeof(double) * (size_t)N * d, hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(d_xy + (size_t)N * d, y, sizeof(double) * (size_t)N, hipMemcpyHostToDevice));
   {  // ux = U'X, uy = U'y  (FastLMM.cpp:55-57)
     int rcr = rotate_columns(c, d_xy, N, dx, c->d_uxy, N, st);
-    if (rcr) {
-      hipFree(d_xy);
-      return rcr;
-    }
+    if (rcr) return rcr;
     HIP_TRY(c, sync_stream(st));
   }
-  hipFree(d_xy);
+  d_xy.reset();
   // |lambda| for the likelihood (FastLMM.cpp:50); the raw S stays in d_S for FamSkat's Sigma
   std::vector<double> absS(N);
   for (int64_t i = 0; i < N; ++i) absS[i] = std::fabs(c->h_S[i]);
-  double* d_abs = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d_abs, sizeof(double) * N));
+  DevBuf<double> d_abs;
+  HIP_TRY(c, d_abs.alloc(sizeof(double) * N));
   HIP_TRY(c, hipMemcpy(d_abs, absS.data(), sizeof(double) * N, hipMemcpyHostToDevice));
   const int rec = lmm_rec_len(d);
-  HIP_TRY(c, hipMalloc((void**)&c->d_lmm_part, sizeof(double) * (size_t)kLmmBlocks * rec));
+  HIP_TRY(c, c->d_lmm_part.alloc(sizeof(double) * (size_t)kLmmBlocks * rec));
   std::vector<double> part((size_t)kLmmBlocks * rec), sums(rec);
   std::vector<double> beta(d, 0.0);
   double sigma2 = 0.0;
@@ -1190,10 +1107,7 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
     };
     delta = brent_like_gsl(goal, start, lb, ub, &xmin) ? start : xmin;
   }  // else: on the boundary delta (and beta, sigma2) stay at the LAST grid point, as in the reference
-  if (hip_failed) {
-    hipFree(d_abs);
-    return fail(c, RVT_E_HIP, "device evaluation of the FastLMM likelihood failed");
-  }
+  if (hip_failed) return fail(c, RVT_E_HIP, "device evaluation of the FastLMM likelihood failed");
   out->delta = delta;
   out->sigma2_g = sigma2;
   c->fam_delta = delta;
@@ -1214,10 +1128,7 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
     device_sums(c->d_S, delta, 0);
     double C[RVT_MAX_COV * RVT_MAX_COV], Ci[RVT_MAX_COV * RVT_MAX_COV];
     for (int a = 0; a < d * d; ++a) C[a] = sums[a] / sigma2;
-    if (hip_failed || !invert_spd(C, d, Ci)) {
-      hipFree(d_abs);
-      return fail(c, RVT_E_INVALID, "X' Sigma^-1 X is singular");
-    }
+    if (hip_failed || !invert_spd(C, d, Ci)) return fail(c, RVT_E_INVALID, "X' Sigma^-1 X is singular");
     for (int a = 0; a < dx; ++a)
       for (int b = 0; b < dx; ++b) {
         const bool in = a < d && b < d;
@@ -1225,18 +1136,18 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
         fn.Cinv[a * dx + b] = in ? Ci[a * d + b] : (a == b ? 1.0 : 0.0);
       }
   }
-  hipFree(d_abs);
+  d_abs.reset();
   {  // denom of FastGetAF: u1' |S|^-1 u1 (FastLMM.cpp:414-420), kept in the otherwise unused rss slot
     double den = 0.0;
     for (int64_t i = 0; i < N; ++i) den += c->h_u1[i] / std::fabs(c->h_S[i]) * c->h_u1[i];
     fn.rss = den;
   }
   const size_t vb = sizeof(double) * (size_t)ld;
-  HIP_TRY(c, hipMalloc((void**)&c->d_fX, vb * dx));
-  HIP_TRY(c, hipMalloc((void**)&c->d_frr, vb));
-  HIP_TRY(c, hipMalloc((void**)&c->d_fv, vb));
-  HIP_TRY(c, hipMalloc((void**)&c->d_fzeros, vb));
-  HIP_TRY(c, hipMalloc((void**)&c->d_fbeta, sizeof(double) * RVT_MAX_COV));
+  HIP_TRY(c, c->d_fX.alloc(vb * dx));
+  HIP_TRY(c, c->d_frr.alloc(vb));
+  HIP_TRY(c, c->d_fv.alloc(vb));
+  HIP_TRY(c, c->d_fzeros.alloc(vb));
+  HIP_TRY(c, c->d_fbeta.alloc(sizeof(double) * RVT_MAX_COV));
   HIP_TRY(c, hipMemsetAsync(c->d_fX, 0, vb * dx, st));
   HIP_TRY(c, hipMemsetAsync(c->d_frr, 0, vb, st));
   HIP_TRY(c, hipMemsetAsync(c->d_fv, 0, vb, st));
@@ -1244,24 +1155,24 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
   HIP_TRY(c, hipMemcpyAsync(c->d_fbeta, out->beta, sizeof(double) * RVT_MAX_COV, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(fam_build_null_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_uxy, c->d_S,
                      c->d_u1, (long long)N, (long long)ld, d, sigma2, delta, c->d_fbeta, c->d_fX, c->d_frr, c->d_fv);
-  if (!c->d_fam_nc) HIP_TRY(c, hipMalloc((void**)&c->d_fam_nc, sizeof(NullConsts)));
+  HIP_TRY(c, c->d_fam_nc.grow(sizeof(NullConsts), sizeof(NullConsts)));
   HIP_TRY(c, hipMemcpyAsync(c->d_fam_nc, &fn, sizeof(NullConsts), hipMemcpyHostToDevice, st));
   // ---- the family MetaCov's constants and null set (MetaCovFamQtl over FastLMM::GetCov*, FastLMM.cpp:510-625) ----
   {
     // [U'X | u1] with weights 1/|lambda + delta|: A = ux'W ux, b = ux'W u1, yy = u1'W u1
-    double* d_xu = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d_xu, sizeof(double) * (size_t)N * dx));
+    DevBuf<double> d_xu;
+    HIP_TRY(c, d_xu.alloc(sizeof(double) * (size_t)N * dx));
     HIP_TRY(c, hipMemcpyAsync(d_xu, c->d_uxy, sizeof(double) * (size_t)N * d, hipMemcpyDeviceToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_xu + (size_t)N * d, c->d_u1, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
-    double* d_abs2 = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d_abs2, sizeof(double) * N));
+    DevBuf<double> d_abs2;
+    HIP_TRY(c, d_abs2.alloc(sizeof(double) * N));
     HIP_TRY(c, hipMemcpyAsync(d_abs2, absS.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(lmm_sums_kernel, dim3(kLmmBlocks), dim3(256), sizeof(double) * 256, st, d_xu, d_abs2,
                        (long long)N, d, delta, 1, c->d_lmm_part);
     HIP_TRY(c, hipMemcpyAsync(part.data(), c->d_lmm_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, sync_stream(st));
-    hipFree(d_xu);
-    hipFree(d_abs2);
+    d_xu.reset();
+    d_abs2.reset();
     for (int q = 0; q < rec; ++q) {
       double s2 = 0.0;
       for (int b = 0; b < kLmmBlocks; ++b) s2 += part[(size_t)b * rec + q];
@@ -1272,13 +1183,13 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
     c->famcov_c11 = sums[d * d + d] / sigma2;
     if (!invert_spd(c->famcov_zz, d, c->famcov_zzinv)) return fail(c, RVT_E_INVALID, "covZZ is singular");
     {  // k1r = u1' D uResid = (u1'W uy - (ux'W u1)' beta) / sigma2 : one more reduction over [u1 | uy]
-      double* d_uy2 = nullptr;
-      HIP_TRY(c, hipMalloc((void**)&d_uy2, sizeof(double) * (size_t)N * 2));
+      DevBuf<double> d_uy2;
+      HIP_TRY(c, d_uy2.alloc(sizeof(double) * (size_t)N * 2));
       HIP_TRY(c, hipMemcpyAsync(d_uy2, c->d_u1, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
       HIP_TRY(c, hipMemcpyAsync(d_uy2 + (size_t)N, c->d_uxy + (size_t)N * d, sizeof(double) * (size_t)N,
                                 hipMemcpyDeviceToDevice, st));
-      double* d_abs3 = nullptr;
-      HIP_TRY(c, hipMalloc((void**)&d_abs3, sizeof(double) * N));
+      DevBuf<double> d_abs3;
+      HIP_TRY(c, d_abs3.alloc(sizeof(double) * N));
       HIP_TRY(c, hipMemcpyAsync(d_abs3, absS.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(lmm_sums_kernel, dim3(kLmmBlocks), dim3(256), sizeof(double) * 256, st, d_uy2, d_abs3,
                          (long long)N, 1, delta, 1, c->d_lmm_part);
@@ -1286,22 +1197,19 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
       std::vector<double> p1((size_t)kLmmBlocks * rec1);
       HIP_TRY(c, hipMemcpyAsync(p1.data(), c->d_lmm_part, sizeof(double) * p1.size(), hipMemcpyDeviceToHost, st));
       HIP_TRY(c, sync_stream(st));
-      hipFree(d_uy2);
-      hipFree(d_abs3);
+      d_uy2.reset();
+      d_abs3.reset();
       double u1Wy = 0.0;
       for (int b = 0; b < kLmmBlocks; ++b) u1Wy += p1[(size_t)b * rec1 + 1];  // b[0] = u1' W uy
       double k = u1Wy;
       for (int a = 0; a < d; ++a) k -= sums[d * d + a] * beta[a];
       c->famcov_k1r = k / sigma2;
     }
-    for (double** pp : {&c->d_cX, &c->d_cv, &c->d_cr}) {
-      if (*pp) hipFree(*pp);
-      *pp = nullptr;
-    }
+    for (DevBuf<double>* pp : {&c->d_cX, &c->d_cv, &c->d_cr}) pp->reset();
     const int dc = d + 2;  // U'X | u1 | allele-frequency column
-    HIP_TRY(c, hipMalloc((void**)&c->d_cX, vb * dc));
-    HIP_TRY(c, hipMalloc((void**)&c->d_cv, vb));
-    HIP_TRY(c, hipMalloc((void**)&c->d_cr, vb));
+    HIP_TRY(c, c->d_cX.alloc(vb * dc));
+    HIP_TRY(c, c->d_cv.alloc(vb));
+    HIP_TRY(c, c->d_cr.alloc(vb));
     HIP_TRY(c, hipMemsetAsync(c->d_cX, 0, vb * dc, st));
     HIP_TRY(c, hipMemsetAsync(c->d_cv, 0, vb, st));
     HIP_TRY(c, hipMemsetAsync(c->d_cr, 0, vb, st));
@@ -1316,7 +1224,7 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
     cn.binary = 1;
     cn.sigma2 = 1.0;
     for (int a = 0; a < dc; ++a) cn.C[a * dc + a] = cn.Cinv[a * dc + a] = 1.0;  // unused by the covariance kernels
-    if (!c->d_famcov_nc) HIP_TRY(c, hipMalloc((void**)&c->d_famcov_nc, sizeof(NullConsts)));
+    HIP_TRY(c, c->d_famcov_nc.grow(sizeof(NullConsts), sizeof(NullConsts)));
     HIP_TRY(c, hipMemcpyAsync(c->d_famcov_nc, &cn, sizeof(NullConsts), hipMemcpyHostToDevice, st));
   }
   HIP_TRY(c, sync_stream(st));
@@ -1381,17 +1289,10 @@ static int fam_block_run(rvt_ctx* c, const double* dG, int V, CovOut* cop) {
   const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
   rc = ensure_fam_cols(c, (size_t)V, ld);
   if (rc) return rc;
-  double* d_cs = nullptr;
-  int* d_poly = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d_cs, sizeof(double) * (size_t)V));
-  HIP_TRY(c, hipMalloc((void**)&d_poly, sizeof(int) * (size_t)V));
-  struct Guard {
-    void *a, *b;
-    ~Guard() {
-      hipFree(a);
-      hipFree(b);
-    }
-  } guard{(void*)d_cs, (void*)d_poly};
+  DevBuf<double> d_cs;
+  DevBuf<int> d_poly;
+  HIP_TRY(c, d_cs.alloc(sizeof(double) * (size_t)V));
+  HIP_TRY(c, d_poly.alloc(sizeof(int) * (size_t)V));
   hipLaunchKernelGGL(raw_colstat_kernel, dim3((unsigned)V), dim3(256), 0, st, dG, (long long)N, (long long)ld, d_cs,
                      d_poly);
   HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * V, st));
@@ -1447,19 +1348,12 @@ int rvt_fam_analytic_vt(rvt_ctx* c, int n, const double* const* dG, const int* M
     // flip / polymorphic decisions on the raw columns (DataConsolidator.cpp:46-69,94-116)
     std::vector<const double*> cols(M);
     for (int j = 0; j < M; ++j) cols[j] = dG[g] + (size_t)j * ld;
-    const double** d_cols = nullptr;
-    int* d_flags = nullptr;
-    double* d_buf = nullptr;
-    rvt_gene_result* d_res = nullptr;
-    struct Guard {
-      std::vector<void**> p;
-      ~Guard() {
-        for (void** q : p)
-          if (*q) hipFree(*q);
-      }
-    } guard{{(void**)&d_cols, (void**)&d_flags, (void**)&d_buf, (void**)&d_res}};
-    HIP_TRY(c, hipMalloc((void**)&d_cols, sizeof(double*) * (size_t)M));
-    HIP_TRY(c, hipMalloc((void**)&d_flags, sizeof(int) * (size_t)M));
+    DevBuf<const double*> d_cols;
+    DevBuf<int> d_flags;
+    DevBuf<double> d_buf;
+    DevBuf<rvt_gene_result> d_res;
+    HIP_TRY(c, d_cols.alloc(sizeof(double*) * (size_t)M));
+    HIP_TRY(c, d_flags.alloc(sizeof(int) * (size_t)M));
     HIP_TRY(c, hipMemcpyAsync(d_cols, cols.data(), sizeof(double*) * M, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(fam_colstat_kernel, dim3((unsigned)M), dim3(256), 0, st, d_cols, (long long)N, d_flags);
     std::vector<int> flags(M);
@@ -1498,8 +1392,8 @@ int rvt_fam_analytic_vt(rvt_ctx* c, int n, const double* const* dG, const int* M
         host[2 * (size_t)m + (size_t)b * m + a] = sa * sb * v;
       }
     }
-    HIP_TRY(c, hipMalloc((void**)&d_buf, sizeof(double) * nbuf));
-    HIP_TRY(c, hipMalloc((void**)&d_res, sizeof(rvt_gene_result)));
+    HIP_TRY(c, d_buf.alloc(sizeof(double) * nbuf));
+    HIP_TRY(c, d_res.alloc(sizeof(rvt_gene_result)));
     HIP_TRY(c, hipMemcpyAsync(d_buf, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_res, &r, sizeof(r), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(vt_direct_kernel, dim3(1), dim3(256), 0, st, m, Mp, d_buf, d_res);
@@ -1509,15 +1403,15 @@ int rvt_fam_analytic_vt(rvt_ctx* c, int n, const double* const* dG, const int* M
       gdv.Mp = Mp;
       gdv.vt_mem = d_buf + 2 * (size_t)m + (size_t)m * m;
       gdv.result = d_res;
-      GeneDesc* d_gdv = nullptr;
-      HIP_TRY(c, hipMalloc((void**)&d_gdv, sizeof(GeneDesc)));
+      DevBuf<GeneDesc> d_gdv;
+      HIP_TRY(c, d_gdv.alloc(sizeof(GeneDesc)));
       hipError_t e = hipMemcpyAsync(d_gdv, &gdv, sizeof(gdv), hipMemcpyHostToDevice, st);
       for (int stage = 0; stage < 2 && e == hipSuccess; ++stage) {
         k_vt_integrate(dim3(1, kMvnShifts), st, d_gdv, stage);
         k_vt_finish(dim3(1), st, d_gdv, 1, stage);
       }
       if (e == hipSuccess) e = sync_stream(st);
-      hipFree(d_gdv);
+      d_gdv.reset();
       HIP_TRY(c, e);
     }
     HIP_TRY(c, hipGetLastError());
@@ -1638,15 +1532,9 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
   // column pointer / flag lists of the batch: one grow-only allocation of the context (no hipMalloc / hipFree per batch)
   {
     const size_t need = (sizeof(double*) + sizeof(int)) * tot * 2 + 64;
-    if (c->fam_list_cap < need) {
-      if (c->d_fam_list) hipFree(c->d_fam_list);
-      c->d_fam_list = nullptr;
-      c->fam_list_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_fam_list, need + need / 2));
-      c->fam_list_cap = need + need / 2;
-    }
+    HIP_TRY(c, c->d_fam_list.grow(need, need + need / 2));
   }
-  const double** d_cols = reinterpret_cast<const double**>(c->d_fam_list);
+  const double** d_cols = reinterpret_cast<const double**>(c->d_fam_list.get());
   int* d_flags = reinterpret_cast<int*>(c->d_fam_list + sizeof(double*) * tot * 2);
   HIP_TRY(c, hipMemcpyAsync(d_cols, cols.data(), sizeof(double*) * tot, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(fam_colstat_kernel, dim3((unsigned)tot), dim3(256), 0, st, d_cols, (long long)N, d_flags);
@@ -1707,22 +1595,15 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
     }
     HIP_TRY(c, hipGetLastError());
   }
-  int* d_koff = nullptr;
-  double* d_bcs = nullptr;
-  int* d_bpoly = nullptr;
-  struct Guard2 {
-    void **a, **b, **c2;
-    ~Guard2() {
-      for (void** p : {a, b, c2})
-        if (*p) hipFree(*p);
-    }
-  } guard2{(void**)&d_koff, (void**)&d_bcs, (void**)&d_bpoly};
+  DevBuf<int> d_koff;
+  DevBuf<double> d_bcs;
+  DevBuf<int> d_bpoly;
   if (burden) {
     // cmcCollapse / zegginiCollapse of the flipped, filtered blocks into columns T .. T + 2 nk - 1, then their raw
     // sums (the score test centres the collapsed genotype, FastLMM.cpp:218-220)
-    HIP_TRY(c, hipMalloc((void**)&d_koff, sizeof(int) * 2 * nk));
-    HIP_TRY(c, hipMalloc((void**)&d_bcs, sizeof(double) * TB));
-    HIP_TRY(c, hipMalloc((void**)&d_bpoly, sizeof(int) * TB));
+    HIP_TRY(c, d_koff.alloc(sizeof(int) * 2 * nk));
+    HIP_TRY(c, d_bcs.alloc(sizeof(double) * TB));
+    HIP_TRY(c, d_bpoly.alloc(sizeof(int) * TB));
     HIP_TRY(c, hipMemcpyAsync(d_koff, koff.data(), sizeof(int) * nk, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_koff + nk, km.data(), sizeof(int) * nk, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemsetAsync(c->d_Gp + (size_t)T * ld, 0, sizeof(double) * (size_t)ld * TB, st));
@@ -1737,13 +1618,7 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
       const int ncp = (int)std::min<size_t>(kRotMaxCols, T - c0);
       const int64_t cols_pad = ((int64_t)ncp + kRotBN - 1) / kRotBN * kRotBN;
       const size_t need = (size_t)cols_pad * (size_t)ldk;
-      if (c->rotB_cap < need) {
-        if (c->d_rotB) hipFree(c->d_rotB);
-        c->d_rotB = nullptr;
-        c->rotB_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->d_rotB, need + need / 4));
-        c->rotB_cap = need + need / 4;
-      }
+      HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
       HIP_TRY(c, hipMemsetAsync(c->d_rotB, 0, need, st));
       hipLaunchKernelGGL(fam_flip_quant_kernel, dim3(64, (unsigned)ncp), dim3(256), 0, st, d_cols + tot + c0,
                          d_flags + tot + c0, (long long)N, (long long)ldk, c->d_rotB);
@@ -1865,20 +1740,6 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
 namespace {
 using namespace rvt_fs;
 
-size_t fs_align(size_t b) { return (b + 255) / 256 * 256; }
-
-// grow-only work space (allocated outside every loop; RVT_POISON fills a new one as the Wald work space is filled)
-int fs_grow(rvt_ctx* c, char** p, size_t* cap, size_t want) {
-  if (*cap >= want) return RVT_OK;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(c, hipMalloc((void**)p, want));
-  *cap = want;
-  if (const char* e = getenv("RVT_POISON")) HIP_TRY(c, hipMemset(*p, atoi(e) & 0xff, want));
-  return RVT_OK;
-}
-
 // the kLmmBlocks partial records of a reduction, summed in block order
 int fs_records(rvt_ctx* c, const double* d_part, int rec, hipStream_t st, std::vector<double>* sums) {
   std::vector<double> part((size_t)kLmmBlocks * rec);
@@ -1931,9 +1792,9 @@ int fs_apply_u(rvt_ctx* c, const double* d_v, double* d_out, double* d_part, int
         cols[o] = (int)k;
         tvals[o] = vals[e];
       }
-    HIP_TRY(c, hipMalloc((void**)&c->d_csr_ptr, sizeof(long long) * ((size_t)N + 1)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_csr_cols, sizeof(int) * std::max<size_t>(nnz, 1)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_csr_vals, sizeof(double) * std::max<size_t>(nnz, 1)));
+    HIP_TRY(c, c->d_csr_ptr.alloc(sizeof(long long) * ((size_t)N + 1)));
+    HIP_TRY(c, c->d_csr_cols.alloc(sizeof(int) * std::max<size_t>(nnz, 1)));
+    HIP_TRY(c, c->d_csr_vals.alloc(sizeof(double) * std::max<size_t>(nnz, 1)));
     HIP_TRY(c, hipMemcpyAsync(c->d_csr_ptr, rp.data(), sizeof(long long) * rp.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->d_csr_cols, cols.data(), sizeof(int) * nnz, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(c->d_csr_vals, tvals.data(), sizeof(double) * nnz, hipMemcpyHostToDevice, st));
@@ -1968,23 +1829,15 @@ int rvt_lrt_block_fam(rvt_ctx* c, const double* dG, int V, int* ok, double* af, 
   const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
   const int d = c->fam_nc.d - 1;
   const int MV = RVT_MAX_VARIANTS;
-  size_t off = 0;
-  auto carve = [&](size_t b) {
-    const size_t o = off;
-    off += fs_align(b);
-    return o;
-  };
-  const size_t o_vec = carve(sizeof(double) * 3 * (size_t)ld), o_abs = carve(sizeof(double) * (size_t)ld),
-               o_ainv = carve(sizeof(double) * RVT_MAX_COV * RVT_MAX_COV), o_beta = carve(sizeof(double) * RVT_MAX_COV),
-               o_part = carve(sizeof(double) * (size_t)kLmmBlocks * lmm_rec_len(RVT_MAX_COV)),
-               o_cs = carve(sizeof(double) * MV), o_poly = carve(sizeof(int) * MV), o_ok = carve(sizeof(int) * MV),
-               o_af = carve(sizeof(double) * MV), o_nll = carve(sizeof(double) * MV), o_all = carve(sizeof(double) * MV),
-               o_pv = carve(sizeof(double) * MV);
-  if (c->lrt_ws_cap < off) {
-    c->lrt_gen = 0;  // the constants live in the work space
-    rc = fs_grow(c, &c->d_lrt_ws, &c->lrt_ws_cap, off);
-    if (rc) return rc;
-  }
+  Layout L;
+  const size_t o_vec = L.take(sizeof(double) * 3 * (size_t)ld), o_abs = L.take(sizeof(double) * (size_t)ld),
+               o_ainv = L.take(sizeof(double) * RVT_MAX_COV * RVT_MAX_COV), o_beta = L.take(sizeof(double) * RVT_MAX_COV),
+               o_part = L.take(sizeof(double) * (size_t)kLmmBlocks * lmm_rec_len(RVT_MAX_COV)),
+               o_cs = L.take(sizeof(double) * MV), o_poly = L.take(sizeof(int) * MV), o_ok = L.take(sizeof(int) * MV),
+               o_af = L.take(sizeof(double) * MV), o_nll = L.take(sizeof(double) * MV), o_all = L.take(sizeof(double) * MV),
+               o_pv = L.take(sizeof(double) * MV);
+  if (c->d_lrt_ws.cap < L.total) c->lrt_gen = 0;  // the constants live in the work space
+  HIP_TRY(c, c->d_lrt_ws.grow(L.total, L.total, nullptr, true));  // (grow-only, outside every loop; RVT_POISON fills it)
   char* ws = c->d_lrt_ws;
   double* d_vec = reinterpret_cast<double*>(ws + o_vec);
   double* d_abs = reinterpret_cast<double*>(ws + o_abs);
@@ -2066,28 +1919,23 @@ struct GgLayout {
 };
 GgLayout gg_layout(int64_t ld, int64_t N, int d) {
   GgLayout L;
-  size_t off = 0;
-  auto carve = [&](size_t b) {
-    const size_t o = off;
-    off += fs_align(b);
-    return o;
-  };
+  Layout lay;
   const int MV = RVT_MAX_VARIANTS;
-  L.o_ty = carve(sizeof(double) * (size_t)ld);
-  L.o_wu1 = carve(sizeof(double) * (size_t)ld);
-  L.o_xy = carve(sizeof(double) * (size_t)N * (d + 1));
-  L.o_uxy = carve(sizeof(double) * (size_t)N * (d + 1));
-  L.o_r = carve(sizeof(double) * (size_t)ld);
-  L.o_ur = carve(sizeof(double) * (size_t)ld);
-  L.o_upart = carve(sizeof(double) * (size_t)kApplySlices * ld);
-  L.o_part = carve(sizeof(double) * (size_t)kLmmBlocks * (d * d + d + 1));
-  L.o_beta = carve(sizeof(double) * RVT_MAX_COV);
-  L.o_ok = carve(sizeof(int) * MV);
-  L.o_af = carve(sizeof(double) * MV);
-  L.o_b = carve(sizeof(double) * MV);
-  L.o_bv = carve(sizeof(double) * MV);
-  L.o_pv = carve(sizeof(double) * MV);
-  L.total = off;
+  L.o_ty = lay.take(sizeof(double) * (size_t)ld);
+  L.o_wu1 = lay.take(sizeof(double) * (size_t)ld);
+  L.o_xy = lay.take(sizeof(double) * (size_t)N * (d + 1));
+  L.o_uxy = lay.take(sizeof(double) * (size_t)N * (d + 1));
+  L.o_r = lay.take(sizeof(double) * (size_t)ld);
+  L.o_ur = lay.take(sizeof(double) * (size_t)ld);
+  L.o_upart = lay.take(sizeof(double) * (size_t)kApplySlices * ld);
+  L.o_part = lay.take(sizeof(double) * (size_t)kLmmBlocks * (d * d + d + 1));
+  L.o_beta = lay.take(sizeof(double) * RVT_MAX_COV);
+  L.o_ok = lay.take(sizeof(int) * MV);
+  L.o_af = lay.take(sizeof(double) * MV);
+  L.o_b = lay.take(sizeof(double) * MV);
+  L.o_bv = lay.take(sizeof(double) * MV);
+  L.o_pv = lay.take(sizeof(double) * MV);
+  L.total = lay.total;
   return L;
 }
 }  // namespace
@@ -2102,8 +1950,7 @@ int rvt_fit_grammar_null(rvt_ctx* c, int64_t N, int d, const double* X, const do
   c->have_grammar = false;
   const int64_t ld = rvt_padded_ld(N);
   const GgLayout L = gg_layout(ld, N, d);
-  rc = fs_grow(c, &c->d_gg_ws, &c->gg_ws_cap, L.total);
-  if (rc) return rc;
+  HIP_TRY(c, c->d_gg_ws.grow(L.total, L.total, nullptr, true));
   char* ws = c->d_gg_ws;
   double* d_ty = reinterpret_cast<double*>(ws + L.o_ty);
   double* d_wu1 = reinterpret_cast<double*>(ws + L.o_wu1);

@@ -41,13 +41,7 @@ int gemm_tn_f64(rvt_ctx* c, const double* A, int64_t lda, int M, const double* B
   if (slices > 1) {
     c_slice = ldc * Ntot;
     const size_t need = sizeof(double) * (size_t)c_slice * (size_t)slices;
-    if (c->rot_part_cap < need) {
-      if (c->d_rot_part) hipFree(c->d_rot_part);
-      c->d_rot_part = nullptr;
-      c->rot_part_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_rot_part, need));
-      c->rot_part_cap = need;
-    }
+    HIP_TRY(c, c->d_rot_part.grow(need, need));
     d_out = c->d_rot_part;
   }
   const int64_t groups = (slices + 7) / 8;
@@ -229,27 +223,15 @@ int rvt_wald_block(rvt_ctx* c, const double* dG, int V, int* ok, double* beta, d
   constexpr int kBatch = 4096;  // variants per launch chunk
   const int Vb = std::min(V, kBatch);
   // work space: beta | last deviance | beta, se, p out | chunk partials | iteration | two lists | ok | rounds | two counters
-  size_t off = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t o_beta = carve(sizeof(double) * (size_t)Vb * kWaldMaxP), o_last = carve(sizeof(double) * (size_t)Vb);
-  const size_t o_ob = carve(sizeof(double) * (size_t)Vb * d), o_os = carve(sizeof(double) * (size_t)Vb * d),
-               o_op = carve(sizeof(double) * (size_t)Vb * d);
-  const size_t o_part = carve(sizeof(double) * (size_t)Vb * n_chunks * E);
-  const size_t o_iter = carve(sizeof(int) * (size_t)Vb), o_l0 = carve(sizeof(int) * (size_t)Vb),
-               o_l1 = carve(sizeof(int) * (size_t)Vb), o_ok = carve(sizeof(int) * (size_t)Vb),
-               o_rounds = carve(sizeof(int) * (size_t)Vb), o_cnt = carve(sizeof(int) * 2);
-  if (c->wald_ws_cap < off) {
-    if (c->d_wald_ws) hipFree(c->d_wald_ws);
-    c->d_wald_ws = nullptr;
-    c->wald_ws_cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_wald_ws, off));
-    c->wald_ws_cap = off;
-    if (const char* e = getenv("RVT_POISON")) HIP_TRY(c, hipMemset(c->d_wald_ws, atoi(e) & 0xff, off));
-  }
+  Layout L;
+  const size_t o_beta = L.take(sizeof(double) * (size_t)Vb * kWaldMaxP), o_last = L.take(sizeof(double) * (size_t)Vb);
+  const size_t o_ob = L.take(sizeof(double) * (size_t)Vb * d), o_os = L.take(sizeof(double) * (size_t)Vb * d),
+               o_op = L.take(sizeof(double) * (size_t)Vb * d);
+  const size_t o_part = L.take(sizeof(double) * (size_t)Vb * n_chunks * E);
+  const size_t o_iter = L.take(sizeof(int) * (size_t)Vb), o_l0 = L.take(sizeof(int) * (size_t)Vb),
+               o_l1 = L.take(sizeof(int) * (size_t)Vb), o_ok = L.take(sizeof(int) * (size_t)Vb),
+               o_rounds = L.take(sizeof(int) * (size_t)Vb), o_cnt = L.take(sizeof(int) * 2);
+  HIP_TRY(c, c->d_wald_ws.grow(L.total, L.total, nullptr, true));
   char* ws = c->d_wald_ws;
   double* d_beta = reinterpret_cast<double*>(ws + o_beta);
   double* d_last = reinterpret_cast<double*>(ws + o_last);
@@ -383,13 +365,7 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
                  bT = up(sizeof(double) * (size_t)W * d), bV = up(sizeof(double) * (size_t)W), bP = up(sizeof(int) * (size_t)W);
     const size_t bM = up(sizeof(double) * (size_t)64 * W * (RVT_MAX_COV + 3));   // slice partials of the column pass (<= 64 slices)
     const size_t need = bS + bC + 2 * bT + bV + bP + bM;
-    if (c->cov_work_cap < need) {
-      if (c->d_cov_work) hipFree(c->d_cov_work);
-      c->d_cov_work = nullptr;
-      c->cov_work_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_cov_work, need + need / 4));
-      c->cov_work_cap = need + need / 4;
-    }
+    HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4));
     char* q = c->d_cov_work;
     d_S = reinterpret_cast<double*>(q);      // H x (W + d): T sits behind S when heads = window
     q += bS;
@@ -463,13 +439,7 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
     const int64_t ldk = (N + 127) / 128 * 128;
     const int64_t cols_pad = ((int64_t)W + kRotBM - 1) / kRotBM * kRotBM;
     const size_t need = (size_t)cols_pad * (size_t)ldk;
-    if (c->rotB_cap < need) {
-      if (c->d_rotB) hipFree(c->d_rotB);
-      c->d_rotB = nullptr;
-      c->rotB_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_rotB, need + need / 4));
-      c->rotB_cap = need + need / 4;
-    }
+    HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
     // the product reads cols_pad columns of ldk bytes: the column pass writes the W columns' rows up to N rounded to 4 — only
     // the pad rows behind them and the pad columns have to be zeroed (the whole 0.5 GB copy cost 0.1 ms of a 2.3 ms block)
     {
@@ -478,7 +448,7 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
         HIP_TRY(c, hipMemset2DAsync(c->d_rotB + n4, (size_t)ldk, 0, (size_t)(ldk - n4), (size_t)W, st));
       if (cols_pad > W) HIP_TRY(c, hipMemsetAsync(c->d_rotB + (size_t)W * ldk, 0, (size_t)(cols_pad - W) * (size_t)ldk, st));
     }
-    if (!c->d_kind) HIP_TRY(c, hipMalloc((void**)&c->d_kind, sizeof(int)));
+    HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int)));
     d_bad = c->d_kind;
     HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(int), st));
     {
@@ -634,13 +604,7 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
     const size_t bB = 2 * up(sizeof(float) * (size_t)Hp * ((size_t)halo + 1));
     const size_t bS = fast ? 0 : up(sizeof(double) * (size_t)Hp * Wp);
     const size_t need = 2 * bT + 2 * bV + bP + bM + bB + bS;
-    if (c->cov_work_cap < need) {
-      if (c->d_cov_work) hipFree(c->d_cov_work);
-      c->d_cov_work = nullptr;
-      c->cov_work_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_cov_work, need + need / 4));
-      c->cov_work_cap = need + need / 4;
-    }
+    HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4));
     char* q = c->d_cov_work;
     d_T = reinterpret_cast<double*>(q);
     q += bT;
@@ -674,29 +638,23 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
     hipLaunchKernelGGL(band_cache_gather_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, ckc->d_cs, ckc->d_poly,
                        ckc->d_T, ringk, col0, W, d, RVT_MAX_COV, d_cs, d_poly, d_T, masked ? ckc->d_mu : (const double*)nullptr,
                        masked ? d_mu_l : (double*)nullptr);
-    R8 = fp4 ? reinterpret_cast<const int8_t*>(ckc->d_i4) : reinterpret_cast<const int8_t*>(ckc->d_i8);
+    R8 = fp4 ? reinterpret_cast<const int8_t*>(ckc->d_i4.get()) : reinterpret_cast<const int8_t*>(ckc->d_i8.get());
     r8_ring = ringk;
     r8_col0 = col0;
   } else if (fast) {
     // no cache: ONE pass over the window's columns gives the statistics, T = G'X and a linear copy of the window's hard calls
     const size_t need = ((size_t)W + kBandBT) * (size_t)ldk;
-    if (c->rotB_cap < need) {
-      if (c->d_rotB) hipFree(c->d_rotB);
-      c->d_rotB = nullptr;
-      c->rotB_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_rotB, need + need / 4));
-      c->rotB_cap = need + need / 4;
-    }
+    HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
     const int64_t n4 = (N + 3) / 4 * 4, nw = fp4 ? n4 / 2 : n4;   // bytes of a column the pass writes; the pad behind them: zero
     if (ldk > nw) HIP_TRY(c, hipMemset2DAsync(c->d_rotB + nw, (size_t)ldk, 0, (size_t)(ldk - nw), (size_t)W, st));
-    if (!c->d_kind) HIP_TRY(c, hipMalloc((void**)&c->d_kind, sizeof(int)));
+    HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int)));
     d_bad = c->d_kind;
     HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(int), st));
     launch_cov_prep(st, d, true, dim3((unsigned)wgs, (unsigned)slices), Gbase, N, ld, W, c->d_X, fp4 ? nullptr : c->d_rotB, ldk8, d_tmp,
-                    d_bad, nullptr, nullptr, ringk, pcol0, fp4 ? reinterpret_cast<unsigned char*>(c->d_rotB) : nullptr, ldk4);
+                    d_bad, nullptr, nullptr, ringk, pcol0, fp4 ? reinterpret_cast<unsigned char*>(c->d_rotB.get()) : nullptr, ldk4);
     hipLaunchKernelGGL(cov_hc_finish_kernel, dim3((unsigned)((W * (dmax + 3) + 255) / 256)), dim3(256), 0, st, d_tmp, slices,
                        W, d, dmax, d_cs, d_poly, d_T);
-    R8 = reinterpret_cast<const int8_t*>(c->d_rotB);
+    R8 = reinterpret_cast<const int8_t*>(c->d_rotB.get());
   } else {
     launch_cov_prep(st, d, false, dim3((unsigned)wgs, (unsigned)slices), Gbase, N, ld, W, c->d_X, nullptr, 0, d_tmp, nullptr,
                     nc.binary ? c->d_v : nullptr, nullptr, ringk, pcol0, nullptr, 0);
@@ -731,21 +689,15 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
       nsl = (kbytes + kslice - 1) / kslice;
       const long long set_stride = (long long)n_tiles * (long long)nsl * kBandBT * kBandBT;
       const size_t need = sizeof(int) * (size_t)set_stride * (size_t)n_sets;
-      if (c->rot_part_cap < need) {
-        if (c->d_rot_part) hipFree(c->d_rot_part);
-        c->d_rot_part = nullptr;
-        c->rot_part_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->d_rot_part, need));
-        c->rot_part_cap = need;
-      }
-      int* d_part = reinterpret_cast<int*>(c->d_rot_part);
+      HIP_TRY(c, c->d_rot_part.grow(need, need));
+      int* d_part = reinterpret_cast<int*>(c->d_rot_part.get());
       int pc = r8_col0 + h0;
       if (r8_ring > 0 && pc >= r8_ring) pc -= r8_ring;
       const int pr = (r8_ring > 0 && pc + wsub > r8_ring) ? r8_ring : 0;
       const unsigned grid = (unsigned)(8 * (int64_t)n_tiles * ((nsl + 7) / 8));
       if (masked) {
-        const int8_t* Hs = reinterpret_cast<const int8_t*>(ckc->d_i4);
-        const int8_t* Ms = reinterpret_cast<const int8_t*>(ckc->d_m4);
+        const int8_t* Hs = reinterpret_cast<const int8_t*>(ckc->d_i4.get());
+        const int8_t* Ms = reinterpret_cast<const int8_t*>(ckc->d_m4.get());
         const int8_t* sideA[4] = {Hs, Hs, Ms, Ms};
         const int8_t* sideB[4] = {Hs, Ms, Hs, Ms};
         for (int k = 0; k < 4; ++k)
@@ -836,26 +788,18 @@ static int cov_rect_fam_impl(rvt_ctx* c, const double* dG, int ring, int col0, i
     segs[1] = Seg{0, W - segs[0].n, segs[0].n};
     nseg = 2;
   }
-  double *d_S = nullptr, *d_T = nullptr, *d_cs = nullptr, *d_xz = nullptr, *d_cov = nullptr, *d_w = nullptr, *d_t1 = nullptr;
-  float* d_band = nullptr;
-  int* d_poly = nullptr;
-  struct Guard {
-    std::vector<void**> p;
-    ~Guard() {
-      for (void** q : p)
-        if (*q) hipFree(*q);
-    }
-  } guard{{(void**)&d_S, (void**)&d_T, (void**)&d_cs, (void**)&d_xz, (void**)&d_cov, (void**)&d_w, (void**)&d_t1,
-           (void**)&d_poly, (void**)&d_band}};
-  HIP_TRY(c, hipMalloc((void**)&d_S, sizeof(double) * (size_t)H * W));
-  if (halo < 0) HIP_TRY(c, hipMalloc((void**)&d_cov, sizeof(double) * (size_t)H * W));
-  else HIP_TRY(c, hipMalloc((void**)&d_band, sizeof(float) * (size_t)H * ((size_t)halo + 1)));
-  HIP_TRY(c, hipMalloc((void**)&d_T, sizeof(double) * (size_t)W * (du + 1)));
-  HIP_TRY(c, hipMalloc((void**)&d_xz, sizeof(double) * (size_t)W * du));
-  HIP_TRY(c, hipMalloc((void**)&d_t1, sizeof(double) * (size_t)W));
-  HIP_TRY(c, hipMalloc((void**)&d_cs, sizeof(double) * (size_t)W));
-  HIP_TRY(c, hipMalloc((void**)&d_poly, sizeof(int) * (size_t)W));
-  HIP_TRY(c, hipMalloc((void**)&d_w, sizeof(double) * (size_t)ld * (size_t)(du + 1 + H)));
+  DevBuf<double> d_S, d_T, d_cs, d_xz, d_cov, d_w, d_t1;
+  DevBuf<float> d_band;
+  DevBuf<int> d_poly;
+  HIP_TRY(c, d_S.alloc(sizeof(double) * (size_t)H * W));
+  if (halo < 0) HIP_TRY(c, d_cov.alloc(sizeof(double) * (size_t)H * W));
+  else HIP_TRY(c, d_band.alloc(sizeof(float) * (size_t)H * ((size_t)halo + 1)));
+  HIP_TRY(c, d_T.alloc(sizeof(double) * (size_t)W * (du + 1)));
+  HIP_TRY(c, d_xz.alloc(sizeof(double) * (size_t)W * du));
+  HIP_TRY(c, d_t1.alloc(sizeof(double) * (size_t)W));
+  HIP_TRY(c, d_cs.alloc(sizeof(double) * (size_t)W));
+  HIP_TRY(c, d_poly.alloc(sizeof(int) * (size_t)W));
+  HIP_TRY(c, d_w.alloc(sizeof(double) * (size_t)ld * (size_t)(du + 1 + H)));
   HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * W, st));
   for (int k = 0; k < nseg; ++k) {
     const double* GW = dG + (size_t)segs[k].phys * ld;
@@ -936,26 +880,24 @@ int rvt_cov_band_fam(rvt_ctx* c, const double* dG, int ring_cols, int col0, int 
 // the column cache of a block (int8 copy, E2M1 copy, sums, flags, rows of T): an optimisation — a failed allocation leaves the
 // block without one (every column invalid; the covariance calls then run their own column pass), it does not fail the call
 static void free_col_cache(rvt_ctx::ColKind& ck) {
-  for (void* q : {(void*)ck.d_i8, (void*)ck.d_i4, (void*)ck.d_m4, (void*)ck.d_mu, (void*)ck.d_cs, (void*)ck.d_poly, (void*)ck.d_T})
-    if (q) hipFree(q);
-  ck.d_i8 = nullptr;
-  ck.d_i4 = nullptr;
-  ck.d_m4 = nullptr;
-  ck.d_mu = nullptr;
-  ck.d_cs = nullptr;
-  ck.d_poly = nullptr;
-  ck.d_T = nullptr;
+  ck.d_i8.reset();
+  ck.d_i4.reset();
+  ck.d_m4.reset();
+  ck.d_mu.reset();
+  ck.d_cs.reset();
+  ck.d_poly.reset();
+  ck.d_T.reset();
   std::fill(ck.valid.begin(), ck.valid.end(), 0);
 }
 static bool alloc_col_cache(rvt_ctx* c, rvt_ctx::ColKind& ck, int64_t ldk, int64_t ldk4, uint64_t gen, hipStream_t st) {
   const size_t cap = ((size_t)ck.cols + 255) / 256 * 256 + 256;  // (the products read whole tiles of columns)
-  bool ok = hipMalloc((void**)&ck.d_i8, cap * (size_t)ldk) == hipSuccess &&
-            hipMalloc((void**)&ck.d_i4, cap * (size_t)ldk4) == hipSuccess &&
-            hipMalloc((void**)&ck.d_m4, cap * (size_t)ldk4) == hipSuccess &&
-            hipMalloc((void**)&ck.d_mu, sizeof(double) * (size_t)ck.cols) == hipSuccess &&
-            hipMalloc((void**)&ck.d_cs, sizeof(double) * (size_t)ck.cols) == hipSuccess &&
-            hipMalloc((void**)&ck.d_poly, sizeof(int) * (size_t)ck.cols) == hipSuccess &&
-            hipMalloc((void**)&ck.d_T, sizeof(double) * (size_t)ck.cols * RVT_MAX_COV) == hipSuccess;
+  bool ok = ck.d_i8.alloc(cap * (size_t)ldk) == hipSuccess &&
+            ck.d_i4.alloc(cap * (size_t)ldk4) == hipSuccess &&
+            ck.d_m4.alloc(cap * (size_t)ldk4) == hipSuccess &&
+            ck.d_mu.alloc(sizeof(double) * (size_t)ck.cols) == hipSuccess &&
+            ck.d_cs.alloc(sizeof(double) * (size_t)ck.cols) == hipSuccess &&
+            ck.d_poly.alloc(sizeof(int) * (size_t)ck.cols) == hipSuccess &&
+            ck.d_T.alloc(sizeof(double) * (size_t)ck.cols * RVT_MAX_COV) == hipSuccess;
   ok = ok && hipMemsetAsync(ck.d_i8, 0, cap * (size_t)ldk, st) == hipSuccess &&
        hipMemsetAsync(ck.d_i4, 0, cap * (size_t)ldk4, st) == hipSuccess &&
        hipMemsetAsync(ck.d_m4, 0, cap * (size_t)ldk4, st) == hipSuccess &&
@@ -1045,7 +987,7 @@ int rvt_block_copy_columns(rvt_ctx* c, double* dst, int dst_col, const double* s
     if (dst_col + ncols <= t.cols) {
       if (s && s->d_flags && src_col + ncols <= s->cols) {
         if (!t.d_flags) {
-          HIP_TRY(c, hipMalloc((void**)&t.d_flags, sizeof(int) * (size_t)t.cols));
+          HIP_TRY(c, t.d_flags.alloc(sizeof(int) * (size_t)t.cols));
           HIP_TRY(c, hipMemsetAsync(t.d_flags, 0x01, sizeof(int) * (size_t)t.cols, c->io_stream));
         }
         HIP_TRY(c, hipMemcpyAsync(t.d_flags + dst_col, s->d_flags + src_col, sizeof(int) * (size_t)ncols, hipMemcpyDeviceToDevice,
@@ -1074,7 +1016,7 @@ static int packed_columns_pass(rvt_ctx* c, double* dG, int col0, int n, const do
   if (it == c->col_kind.end() || !c->hc_enabled || col0 + n > it->second.cols) return RVT_OK;
   rvt_ctx::ColKind& ck = it->second;
   if (!ck.d_flags) {
-    HIP_TRY(c, hipMalloc((void**)&ck.d_flags, sizeof(int) * (size_t)ck.cols));
+    HIP_TRY(c, ck.d_flags.alloc(sizeof(int) * (size_t)ck.cols));
     HIP_TRY(c, hipMemsetAsync(ck.d_flags, 0x01, sizeof(int) * (size_t)ck.cols, st));
   }
   // the content of a packed column is KNOWN: hard calls only unless it has an other value
@@ -1089,12 +1031,12 @@ static int packed_columns_pass(rvt_ctx* c, double* dG, int col0, int n, const do
     cache = ck.d_i8 != nullptr;
     if (cache) {
       const size_t part_doubles = (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
-      if (!c->d_cc_part) HIP_TRY(c, hipMalloc((void**)&c->d_cc_part, sizeof(double) * part_doubles));
+      HIP_TRY(c, c->d_cc_part.grow(sizeof(double) * part_doubles, sizeof(double) * part_doubles));
       const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, (int64_t)N / 4096 + 1));
       // (the columns' other values, NaN where a column has none: the pass splits g = h + mu m by them)
       double mu_nan[rvt_ctx::kColQueue];
       for (int k = 0; k < n; ++k) mu_nan[k] = hard[k] ? (double)NAN : mu[k];
-      if (!c->d_mu_nan) HIP_TRY(c, hipMalloc((void**)&c->d_mu_nan, sizeof(double) * (size_t)rvt_ctx::kColQueue));
+      HIP_TRY(c, c->d_mu_nan.grow(sizeof(double) * (size_t)rvt_ctx::kColQueue, sizeof(double) * (size_t)rvt_ctx::kColQueue));
       double* d_mu_nan = c->d_mu_nan;
       rc = small_h2d(c, d_mu_nan, mu_nan, sizeof(double) * (size_t)n);
       if (rc) return rc;
@@ -1127,14 +1069,7 @@ int flush_col_queue(rvt_ctx* c) {
   const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
   const size_t pitch = q.pitch;
   const size_t need = pitch * (size_t)rvt_ctx::kColQueue + 2 * sizeof(double) * (size_t)rvt_ctx::kColQueue;
-  if (c->colpack_cap < need) {
-    HIP_TRY(c, sync_stream(c->io_stream));
-    if (c->d_colpack) hipFree(c->d_colpack);
-    c->d_colpack = nullptr;
-    c->colpack_cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_colpack, need + need / 2));
-    c->colpack_cap = need + need / 2;
-  }
+  HIP_TRY(c, c->d_colpack.grow(need, need + need / 2, c->io_stream));
   hipStream_t st = c->io_stream;
   double* dG = q.dG;
   const int col0 = q.col0;
@@ -1147,7 +1082,7 @@ int flush_col_queue(rvt_ctx* c) {
   int rc = small_h2d(c, d_mu, q.mu, sizeof(double) * (size_t)n);
   if (rc) return rc;
   hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)n), dim3(256), 0, st,
-                     reinterpret_cast<const unsigned char*>(c->d_colpack), (long long)pitch, d_mu, (long long)N, (long long)ld,
+                     reinterpret_cast<const unsigned char*>(c->d_colpack.get()), (long long)pitch, d_mu, (long long)N, (long long)ld,
                      dG + (size_t)col0 * ld);
   HIP_TRY(c, hipGetLastError());
   return packed_columns_pass(c, dG, col0, n, q.mu, q.hard);
@@ -1171,14 +1106,13 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
     if (q.pitch != pitch) {  // (another N: new pinned rows)
       HIP_TRY(c, sync_stream(c->io_stream));
       for (int i = 0; i < 2; ++i) {
-        if (q.h[i]) hipHostFree(q.h[i]);
-        q.h[i] = nullptr;
+        q.h[i].reset();
         q.used[i] = false;
       }
       q.pitch = pitch;
     }
     for (int i = 0; i < 2; ++i)
-      if (!q.h[i]) HIP_TRY(c, hipHostMalloc((void**)&q.h[i], pitch * (size_t)rvt_ctx::kColQueue, hipHostMallocDefault));
+      HIP_TRY(c, q.h[i].grow(pitch * (size_t)rvt_ctx::kColQueue, pitch * (size_t)rvt_ctx::kColQueue));
     if (q.n == 0) {
       if (q.used[q.cur]) {  // the DMA that last read these rows has finished?
         while (hipEventQuery(q.ev[q.cur]) == hipErrorNotReady) {
@@ -1191,7 +1125,7 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
       q.col0 = col0;
     }
     PackedColumn pc;
-    if (StageRing::pack_columns_to(reinterpret_cast<char*>(q.h[q.cur]) + pitch * (size_t)q.n, pitch, G, N, N, 1,
+    if (StageRing::pack_columns_to(reinterpret_cast<char*>(q.h[q.cur].get()) + pitch * (size_t)q.n, pitch, G, N, N, 1,
                                    CopyPool::column_instance(), &pc)) {
       // whatever the engine knew about the overwritten column is void from here on
       auto itq = c->col_kind.find(dG);
@@ -1221,13 +1155,7 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
     if (rc) return rc;
     const size_t pitch = ((N + 3) / 4 + 15) / 16 * 16;
     const size_t need = pitch * (size_t)ncols + sizeof(double) * (size_t)ncols;
-    if (c->colpack_cap < need) {
-      if (c->d_colpack) hipFree(c->d_colpack);
-      c->d_colpack = nullptr;
-      c->colpack_cap = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_colpack, need + need / 2));
-      c->colpack_cap = need + need / 2;
-    }
+    HIP_TRY(c, c->d_colpack.grow(need, need + need / 2));
     if (pitch <= c->stage.chunk_bytes) {
       std::vector<PackedColumn> pc((size_t)ncols);
       const int prc = c->stage.pack_f64(c->d_colpack, pitch, G, N, N, (size_t)ncols, CopyPool::pack_instance(), pc.data());
@@ -1239,7 +1167,7 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
         rc = small_h2d(c, d_mu, mu.data(), sizeof(double) * (size_t)ncols);
         if (rc) return rc;
         hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)ncols), dim3(256), 0, c->io_stream,
-                           reinterpret_cast<const unsigned char*>(c->d_colpack), (long long)pitch, d_mu, (long long)N, (long long)ld,
+                           reinterpret_cast<const unsigned char*>(c->d_colpack.get()), (long long)pitch, d_mu, (long long)N, (long long)ld,
                            dG + (size_t)col0 * ld);
         HIP_TRY(c, hipGetLastError());
         packed = true;
@@ -1278,7 +1206,7 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
   if (it != c->col_kind.end() && c->hc_enabled && col0 + ncols <= it->second.cols) {
     rvt_ctx::ColKind& ck = it->second;
     if (!ck.d_flags) {
-      HIP_TRY(c, hipMalloc((void**)&ck.d_flags, sizeof(int) * (size_t)ck.cols));
+      HIP_TRY(c, ck.d_flags.alloc(sizeof(int) * (size_t)ck.cols));
       HIP_TRY(c, hipMemsetAsync(ck.d_flags, 0x01, sizeof(int) * (size_t)ck.cols, c->io_stream));
     }
     bool cache = c->have_null && !c->nc.binary && !getenv("RVT_METACOV_NO_CACHE");
@@ -1288,8 +1216,8 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
       if (ck.d_i8 && (ck.ldk != ldk || ck.gen != c->null_gen || !ck.d_i4)) free_col_cache(ck);  // another model: nothing of the old cache is used
       if (!ck.d_i8 && !ck.cache_failed && !alloc_col_cache(c, ck, ldk, ldk4, c->null_gen, c->io_stream)) ck.cache_failed = true;
       cache = ck.d_i8 != nullptr;
-      if (cache && !c->d_cc_part)
-        HIP_TRY(c, hipMalloc((void**)&c->d_cc_part, sizeof(double) * (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3)));
+      const size_t part_bytes = sizeof(double) * (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
+      if (cache) HIP_TRY(c, c->d_cc_part.grow(part_bytes, part_bytes));
     }
     for (int k = 0; k < ncols; ++k) {
       const int col = col0 + k;

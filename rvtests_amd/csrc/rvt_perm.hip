@@ -43,6 +43,13 @@ void mat31_apply(const uint32_t* J, const uint32_t* x, uint32_t* y) {
   std::memcpy(y, t, sizeof(t));
 }
 
+// the chunk buffers of both permutation stages, freed together before either grows them (perm_cap_B: the shuffles they hold)
+static void free_perm(rvt_ctx* c) {
+  for (DevBuf<uint32_t>* b : {&c->d_perm_idx, &c->d_perm_states}) b->reset();
+  for (DevBuf<double>* b : {&c->d_perm_R, &c->d_perm_C, &c->d_perm_Q, &c->d_perm_cur}) b->reset();
+  c->perm_cap_B = 0;
+}
+
 // The permutation test of one gene whose analytic SKAT result (obs = skat_Q) and weights are already on the device.
 //   dG: the gene's block (unflipped), g0: its descriptor of the batch that just finished (weights in its scratch)
 int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rvt_params& prm, rvt_gene_result* r) {
@@ -52,17 +59,10 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
   // flipped, polymorphic genotype block (K_sqrt = diag(w^1/2) G', Skat.cpp:42-47)
   std::vector<const double*> cols(M);
   for (int j = 0; j < M; ++j) cols[j] = dG + (size_t)j * ld;
-  const double** d_cols = nullptr;
-  int* d_flags = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d_cols, sizeof(double*) * (size_t)M * 2));
-  HIP_TRY(c, hipMalloc((void**)&d_flags, sizeof(int) * (size_t)M * 2));
-  struct Guard {
-    void *a, *b;
-    ~Guard() {
-      hipFree(a);
-      hipFree(b);
-    }
-  } guard{(void*)d_cols, (void*)d_flags};
+  DevBuf<const double*> d_cols;
+  DevBuf<int> d_flags;
+  HIP_TRY(c, d_cols.alloc(sizeof(double*) * (size_t)M * 2));
+  HIP_TRY(c, d_flags.alloc(sizeof(int) * (size_t)M * 2));
   HIP_TRY(c, hipMemcpyAsync(d_cols, cols.data(), sizeof(double*) * M, hipMemcpyHostToDevice, st));
   k_fam_colstat(dim3((unsigned)M), st, d_cols, (long long)N, d_flags);
   std::vector<int> flags(M);
@@ -88,7 +88,7 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
     constexpr int kChunk = 2048;
     const int Mp = (m + 15) / 16 * 16;
     const long long ngroups = (N + 15) / 16;
-    if (!c->d_pc_Q) HIP_TRY(c, hipMalloc((void**)&c->d_pc_Q, sizeof(double) * kChunk));
+    HIP_TRY(c, c->d_pc_Q.grow(sizeof(double) * kChunk, sizeof(double) * kChunk));
     const double obs = r->skat_Q;
     // Permutation::init — `threshold` is an INT member of the reference's class (src/Permutation.h:153): the product is truncated
     // (nPerm = 100, alpha = 0.001 -> 0: the test stops before its first shuffle and reports p = 1; found by running the
@@ -108,13 +108,7 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
       const int gps = (int)((ngroups + slices - 1) / slices);
       slices = (int)((ngroups + gps - 1) / gps);
       const size_t need = (size_t)slices * nb * Mp;
-      if (c->pc_part_cap < need) {
-        if (c->d_pc_part) hipFree(c->d_pc_part);
-        c->d_pc_part = nullptr;
-        c->pc_part_cap = 0;
-        HIP_TRY(c, hipMalloc((void**)&c->d_pc_part, sizeof(double) * (need + need / 4)));
-        c->pc_part_cap = need + need / 4;
-      }
+      HIP_TRY(c, c->d_pc_part.grow(sizeof(double) * need, sizeof(double) * (need + need / 4)));
       hipLaunchKernelGGL(perm_counter_partial_kernel, dim3((unsigned)slices, (unsigned)n_bt), dim3(64), 0, st, c->d_Gp,
                          (long long)ld, (long long)N, m, c->d_res, (unsigned long long)c->perm_seed,
                          (unsigned long long)r->gene_id, (unsigned)actual, nb, gps, Mp, c->d_pc_part);
@@ -143,26 +137,17 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
   }
   // chunk buffers
   const int B = std::max(1, std::min(nPerm, (int)std::min<int64_t>(2048, ((int64_t)6 << 30) / (8 * N))));
-  if ((size_t)N * B > c->perm_cap_NB || B > c->perm_cap_B || (size_t)B * m > c->perm_cap_BM || (size_t)N > c->perm_cap_N) {
-    for (void** p : {(void**)&c->d_perm_idx, (void**)&c->d_perm_states, (void**)&c->d_perm_R, (void**)&c->d_perm_C,
-                     (void**)&c->d_perm_Q, (void**)&c->d_perm_cur}) {
-      if (*p) hipFree(*p);
-      *p = nullptr;
-    }
-    c->perm_cap_NB = c->perm_cap_BM = 0;
-    c->perm_cap_B = 0;
-    c->perm_cap_N = 0;
+  if (sizeof(uint32_t) * N * B > c->d_perm_idx.cap || B > c->perm_cap_B || sizeof(double) * B * m > c->d_perm_C.cap ||
+      sizeof(double) * N * 2 > c->d_perm_cur.cap) {  // (d_perm_cur holds 2 N doubles whatever B is: fewer shuffles of more samples must not keep it)
+    free_perm(c);
     const size_t bm = (size_t)B * std::max(m, RVT_MAX_VARIANTS / 4);
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_idx, sizeof(uint32_t) * (size_t)N * B));
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_states, sizeof(uint32_t) * 31 * (size_t)B));
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_R, sizeof(double) * (size_t)N * B));
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_C, sizeof(double) * bm));
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_Q, sizeof(double) * (size_t)B));
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_cur, sizeof(double) * (size_t)N * 2));
-    c->perm_cap_NB = (size_t)N * B;
+    HIP_TRY(c, c->d_perm_idx.alloc(sizeof(uint32_t) * (size_t)N * B));
+    HIP_TRY(c, c->d_perm_states.alloc(sizeof(uint32_t) * 31 * (size_t)B));
+    HIP_TRY(c, c->d_perm_R.alloc(sizeof(double) * (size_t)N * B));
+    HIP_TRY(c, c->d_perm_C.alloc(sizeof(double) * bm));
+    HIP_TRY(c, c->d_perm_Q.alloc(sizeof(double) * (size_t)B));
+    HIP_TRY(c, c->d_perm_cur.alloc(sizeof(double) * (size_t)N * 2));
     c->perm_cap_B = B;
-    c->perm_cap_BM = bm;
-    c->perm_cap_N = (size_t)N;  // (d_perm_cur holds 2 N doubles whatever B is: fewer shuffles of more samples must not keep it)
   }
   if (c->jump_N != N) {
     c->jump.resize(31 * 31);
@@ -248,20 +233,13 @@ int kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std:
   // ---- flipped, polymorphic block (dc->getFlippedToMinorPolymorphicGenotype()) ---------------------------------------
   std::vector<const double*> cols(M);
   for (int j = 0; j < M; ++j) cols[j] = dG + (size_t)j * ld;
-  const double** d_cols = nullptr;
-  int* d_flags = nullptr;
-  double* d_id = nullptr;
-  int* d_carrier = nullptr;
-  unsigned char *d_y = nullptr, *d_sub = nullptr;
-  struct Guard {
-    std::vector<void**> p;
-    ~Guard() {
-      for (void** q : p)
-        if (*q) hipFree(*q);
-    }
-  } guard{{(void**)&d_cols, (void**)&d_flags, (void**)&d_id, (void**)&d_carrier, (void**)&d_y, (void**)&d_sub}};
-  HIP_TRY(c, hipMalloc((void**)&d_cols, sizeof(double*) * (size_t)M * 2));
-  HIP_TRY(c, hipMalloc((void**)&d_flags, sizeof(int) * (size_t)M * 3));
+  DevBuf<const double*> d_cols;
+  DevBuf<int> d_flags;
+  DevBuf<double> d_id;
+  DevBuf<int> d_carrier;
+  DevBuf<unsigned char> d_y, d_sub;
+  HIP_TRY(c, d_cols.alloc(sizeof(double*) * (size_t)M * 2));
+  HIP_TRY(c, d_flags.alloc(sizeof(int) * (size_t)M * 3));
   HIP_TRY(c, hipMemcpyAsync(d_cols, cols.data(), sizeof(double*) * M, hipMemcpyHostToDevice, st));
   k_fam_colstat(dim3((unsigned)M), st, d_cols, (long long)N, d_flags);
   std::vector<int> flags(M);
@@ -295,7 +273,7 @@ int kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std:
     std::vector<double> p3((size_t)n_used + 1);
     for (int k = 0; k <= n_used; ++k) p3[k] = std::pow(3.0, 1.0 * k);  // the host's pow, as the reference evaluates it
     double* d_p3 = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d_id, sizeof(double) * ((size_t)N + p3.size())));
+    HIP_TRY(c, d_id.alloc(sizeof(double) * ((size_t)N + p3.size())));
     d_p3 = d_id + N;
     HIP_TRY(c, hipMemcpyAsync(d_p3, p3.data(), sizeof(double) * p3.size(), hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_flags + 2 * M, use.data(), sizeof(int) * n_used, hipMemcpyHostToDevice, st));
@@ -355,18 +333,10 @@ int kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std:
   const unsigned adaptive = alpha >= 1.0 ? 0u : 5000u;
   const int total = nPerm + 1;  // the loop shuffles once more after the last statistic (kbac.cpp:185,323-324)
   const int B = std::max(1, std::min(total, (int)std::min<int64_t>(2048, ((int64_t)6 << 30) / (4 * N))));
-  if ((size_t)N * B > c->perm_cap_NB || B > c->perm_cap_B) {
-    for (void** p : {(void**)&c->d_perm_idx, (void**)&c->d_perm_states, (void**)&c->d_perm_R, (void**)&c->d_perm_C,
-                     (void**)&c->d_perm_Q, (void**)&c->d_perm_cur}) {
-      if (*p) hipFree(*p);
-      *p = nullptr;
-    }
-    c->perm_cap_NB = c->perm_cap_BM = 0;
-    c->perm_cap_B = 0;
-    c->perm_cap_N = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_idx, sizeof(uint32_t) * (size_t)N * B));
-    HIP_TRY(c, hipMalloc((void**)&c->d_perm_states, sizeof(uint32_t) * 31 * (size_t)B));
-    c->perm_cap_NB = (size_t)N * B;
+  if (sizeof(uint32_t) * N * B > c->d_perm_idx.cap || B > c->perm_cap_B) {
+    free_perm(c);
+    HIP_TRY(c, c->d_perm_idx.alloc(sizeof(uint32_t) * (size_t)N * B));
+    HIP_TRY(c, c->d_perm_states.alloc(sizeof(uint32_t) * 31 * (size_t)B));
     c->perm_cap_B = B;
   }
   if (c->jump_N != N) {
@@ -374,9 +344,9 @@ int kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std:
     jump_matrix((uint64_t)(N - 1), c->jump.data());  // one shuffle draws N-1 numbers
     c->jump_N = N;
   }
-  HIP_TRY(c, hipMalloc((void**)&d_y, (size_t)N * 2));
-  HIP_TRY(c, hipMalloc((void**)&d_sub, (size_t)B * nc_));
-  HIP_TRY(c, hipMalloc((void**)&d_carrier, sizeof(int) * (size_t)nc_));
+  HIP_TRY(c, d_y.alloc((size_t)N * 2));
+  HIP_TRY(c, d_sub.alloc((size_t)B * nc_));
+  HIP_TRY(c, d_carrier.alloc(sizeof(int) * (size_t)nc_));
   HIP_TRY(c, hipMemcpyAsync(d_carrier, carrier.data(), sizeof(int) * (size_t)nc_, hipMemcpyHostToDevice, st));
   unsigned char *cur = d_y, *nxt = d_y + N;
   HIP_TRY(c, hipMemcpyAsync(cur, y.data(), (size_t)N, hipMemcpyHostToDevice, st));

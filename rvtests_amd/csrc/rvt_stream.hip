@@ -129,9 +129,11 @@ int launch_pending(rvt_ctx* c, size_t upto, bool only_full) {
 }  // namespace
 
 namespace {
+constexpr size_t kAfRingBytes = sizeof(double) * rvt_ctx::kAfSlots * RVT_MAX_VARIANTS;  // h_af_ring
+
 int io_err_ready(rvt_ctx* c) {
   if (c->h_io_err) return RVT_OK;
-  HIP_TRY(c, hipHostMalloc((void**)&c->h_io_err, sizeof(int) * (rvt_ctx::kAfSlots + 1), hipHostMallocMapped));
+  HIP_TRY(c, c->h_io_err.alloc(sizeof(int) * (rvt_ctx::kAfSlots + 1), hipHostMallocMapped));
   std::memset(c->h_io_err, 0, sizeof(int) * (rvt_ctx::kAfSlots + 1));
   return RVT_OK;
 }
@@ -157,13 +159,7 @@ static int text_acquire(rvt_ctx* c, size_t total) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->ev_text_free[k], hipEventDisableTiming));
     HIP_TRY(c, hipEventCreateWithFlags(&c->ev_text_copied[k], hipEventDisableTiming));
   }
-  if (c->text_buf_cap[k] < total) {
-    if (c->text_buf[k]) hipFree(c->text_buf[k]);
-    c->text_buf[k] = nullptr;
-    c->text_buf_cap[k] = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->text_buf[k], total + total / 4));
-    c->text_buf_cap[k] = total + total / 4;
-  }
+  HIP_TRY(c, c->text_buf[k].grow(total, total + total / 4));
   HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_text_free[k], 0));
   c->d_vcf_text = c->text_buf[k];
   c->text_cur = k;
@@ -231,16 +227,9 @@ int vcf_decode_gene(rvt_ctx* c, const VcfGene* vg, int M, int64_t N, hipStream_t
     max_len = std::max<int64_t>(max_len, vg->len[j]);
   }
   if (int rca = text_acquire(c, total)) return rca;
-  if (!c->d_vcf_rec) HIP_TRY(c, hipMalloc((void**)&c->d_vcf_rec, sizeof(VcfRecord) * RVT_MAX_VARIANTS));
+  HIP_TRY(c, c->d_vcf_rec.grow(sizeof(VcfRecord) * RVT_MAX_VARIANTS, sizeof(VcfRecord) * RVT_MAX_VARIANTS));
   const int max_seg = (int)std::max<int64_t>(1, (max_len + kVcfSegBytes - 1) / kVcfSegBytes);
-  if (c->vcf_seg_cap < (size_t)max_seg * M) {
-    if (c->d_vcf_seg) hipFree(c->d_vcf_seg);
-    c->d_vcf_seg = nullptr;
-    c->vcf_seg_cap = 0;
-    const size_t want = (size_t)max_seg * std::max(M, 64);
-    HIP_TRY(c, hipMalloc((void**)&c->d_vcf_seg, sizeof(int) * want));
-    c->vcf_seg_cap = want;
-  }
+  HIP_TRY(c, c->d_vcf_seg.grow(sizeof(int) * max_seg * M, sizeof(int) * max_seg * std::max(M, 64)));
   {
     int rce = io_err_ready(c);
     if (rce) return rce;
@@ -269,7 +258,7 @@ int vcf_decode_gene(rvt_ctx* c, const VcfGene* vg, int M, int64_t N, hipStream_t
                        c->d_vcf_seg, c->d_vcf_rows, c->d_vcf_sex, c->vcf_n_file, (long long)dosage_ld, c->vcf_flt, dosage_out,
                        d_err);
   } else {
-    signed char* out = (signed char*)c->d_consol_i8;
+    signed char* out = (signed char*)c->d_consol_i8.get();
     HIP_TRY(c, hipMemsetAsync(out, 0xF7, (size_t)N * M, st));  // -9: rows the sample map never addresses stay missing
     hipLaunchKernelGGL(vcf_decode_kernel, grid, dim3(256), 0, st, c->d_vcf_text, c->d_vcf_rec, max_seg, c->d_vcf_seg,
                        c->d_vcf_rows, c->d_vcf_sex, c->vcf_n_file, (long long)N, c->vcf_flt, out);
@@ -385,16 +374,9 @@ int bgen_decode_gene(rvt_ctx* c, const BgenGene* bg, int M, int64_t N, hipStream
   total += 16;
   if (int rca = text_acquire(c, total)) return rca;
   c->vcf_alt.clear();  // (one call only)
-  if (!c->d_bgen_rec) HIP_TRY(c, hipMalloc((void**)&c->d_bgen_rec, sizeof(BgenRecord) * RVT_MAX_VARIANTS));
+  HIP_TRY(c, c->d_bgen_rec.grow(sizeof(BgenRecord) * RVT_MAX_VARIANTS, sizeof(BgenRecord) * RVT_MAX_VARIANTS));
   const int max_seg = (int)((n_file + kBgenSeg - 1) / kBgenSeg);
-  if (c->bgen_seg_cap < (size_t)max_seg * M) {
-    if (c->d_bgen_seg) hipFree(c->d_bgen_seg);
-    c->d_bgen_seg = nullptr;
-    c->bgen_seg_cap = 0;
-    const size_t want = (size_t)max_seg * std::max(M, 64);
-    HIP_TRY(c, hipMalloc((void**)&c->d_bgen_seg, sizeof(long long) * want));
-    c->bgen_seg_cap = want;
-  }
+  HIP_TRY(c, c->d_bgen_seg.grow(sizeof(long long) * max_seg * M, sizeof(long long) * max_seg * std::max(M, 64)));
   {
     int rce = io_err_ready(c);
     if (rce) return rce;
@@ -525,22 +507,10 @@ int try_submit_packed_f64(rvt_ctx* c, int64_t gene_id, int M, const double* G, c
   auto give_back = [&]() { c->pk_pool.emplace_back(p.bytes, p.dG); };
   hipStream_t st = c->io_stream;
   hipError_t e = hipSuccess;
-  if (c->consol_af_cap < (size_t)M) {
-    if (c->d_consol_af) hipFree(c->d_consol_af);
-    c->d_consol_af = nullptr;
-    c->consol_af_cap = 0;
-    e = hipMalloc((void**)&c->d_consol_af, sizeof(double) * 2 * RVT_MAX_VARIANTS);
-    if (e == hipSuccess) c->consol_af_cap = RVT_MAX_VARIANTS;
-  }
+  e = c->d_consol_af.grow(sizeof(double) * 2 * M, sizeof(double) * 2 * RVT_MAX_VARIANTS);
   const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
-  if (e == hipSuccess && c->consol_parts_cap < (size_t)M * nparts) {
-    if (c->d_consol_parts) hipFree(c->d_consol_parts);
-    c->d_consol_parts = nullptr;
-    c->consol_parts_cap = 0;
-    const size_t want = (size_t)std::max(M, 128) * nparts;
-    e = hipMalloc((void**)&c->d_consol_parts, sizeof(ConsolPart) * want);
-    if (e == hipSuccess) c->consol_parts_cap = want;
-  }
+  if (e == hipSuccess)
+    e = c->d_consol_parts.grow(sizeof(ConsolPart) * M * nparts, sizeof(ConsolPart) * std::max(M, 128) * nparts);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     give_back();
@@ -671,34 +641,19 @@ int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, int mode, c
     // own: the set-up stream is also slot 0's batch stream, and waiting on it would wait for a whole batch.
     hipStream_t st = c->io_stream;
     const size_t afb = sizeof(double) * (size_t)M;
-    if (c->consol_af_cap < (size_t)M) {
-      if (c->d_consol_af) hipFree(c->d_consol_af);
-      c->d_consol_af = nullptr;
-      c->consol_af_cap = 0;
-      if (hipMalloc((void**)&c->d_consol_af, sizeof(double) * 2 * RVT_MAX_VARIANTS) != hipSuccess) {
-        give_back();
-        return fail(c, RVT_E_HIP, "hipMalloc failed");
-      }
-      c->consol_af_cap = RVT_MAX_VARIANTS;
+    if (c->d_consol_af.grow(sizeof(double) * 2 * M, sizeof(double) * 2 * RVT_MAX_VARIANTS) != hipSuccess) {
+      give_back();
+      return fail(c, RVT_E_HIP, "hipMalloc failed");
     }
-    hipError_t e = hipSuccess;
     const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
-    if (c->consol_parts_cap < (size_t)M * nparts) {
-      if (c->d_consol_parts) hipFree(c->d_consol_parts);
-      c->d_consol_parts = nullptr;
-      c->consol_parts_cap = 0;
-      const size_t want = (size_t)std::max(M, 128) * nparts;
-      e = hipMalloc((void**)&c->d_consol_parts, sizeof(ConsolPart) * want);
-      if (e == hipSuccess) c->consol_parts_cap = want;
-    }
+    hipError_t e = c->d_consol_parts.grow(sizeof(ConsolPart) * M * nparts, sizeof(ConsolPart) * std::max(M, 128) * nparts);
     double* d_fill = c->d_consol_af + RVT_MAX_VARIANTS;
     const dim3 cgrid((unsigned)nparts, (unsigned)M);
     // where this gene's allele frequencies (and, for VCF text / BGEN blocks, its input-error word) come back: through a
     // ring slot when nobody waits for them, through the synchronous word otherwise
     int ring_slot = -1;
     if (!af_out && e == hipSuccess) {
-      if (!c->h_af_ring)
-        e = hipHostMalloc((void**)&c->h_af_ring, sizeof(double) * rvt_ctx::kAfSlots * RVT_MAX_VARIANTS, hipHostMallocMapped);
+      e = c->h_af_ring.grow(kAfRingBytes, kAfRingBytes, nullptr, false, hipHostMallocMapped);
       if (e == hipSuccess && c->af_unresolved >= rvt_ctx::kAfSlots && resolve_af(c)) e = hipErrorUnknown;
       if (e == hipSuccess) ring_slot = (int)(c->af_seq++ % rvt_ctx::kAfSlots);
     }
@@ -802,13 +757,7 @@ int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, int mode, c
       const void* d_packed = nullptr;  // where the packed genotypes of this gene are on the device
       int pk = -1;
       if (mode == 4) {
-        if (c->consol_i8_cap < bytes8) {
-          if (c->d_consol_i8) hipFree(c->d_consol_i8);
-          c->d_consol_i8 = nullptr;
-          c->consol_i8_cap = 0;
-          e = hipMalloc((void**)&c->d_consol_i8, bytes8 + bytes8 / 4);
-          if (e == hipSuccess) c->consol_i8_cap = bytes8 + bytes8 / 4;
-        }
+        e = c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4);
         if (e == hipSuccess && vcf_decode_gene(c, (const VcfGene*)G, M, N, st, err_slot) != RVT_OK) e = hipErrorUnknown;
         d_packed = c->d_consol_i8;
       } else {
@@ -816,13 +765,7 @@ int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, int mode, c
         // the gene that used it last have run); the kernels of THIS gene wait for the copy by event
         pk = c->pack_next;
         c->pack_next = (pk + 1) % rvt_ctx::kPack;
-        if (c->pack_cap[pk] < bytes8) {
-          if (c->d_pack[pk]) hipFree(c->d_pack[pk]);
-          c->d_pack[pk] = nullptr;
-          c->pack_cap[pk] = 0;
-          e = hipMalloc((void**)&c->d_pack[pk], bytes8 + bytes8 / 4);
-          if (e == hipSuccess) c->pack_cap[pk] = bytes8 + bytes8 / 4;
-        }
+        e = c->d_pack[pk].grow(bytes8, bytes8 + bytes8 / 4);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_pack_free[pk], 0);
         if (e == hipSuccess && mode == 7) {  // (device-resident rows: into the same landing buffer, whatever their alignment)
           e = hipMemcpyAsync(c->d_pack[pk], G, bytes8, hipMemcpyDeviceToDevice, c->copy_stream);
@@ -1026,8 +969,7 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
   const int64_t N = c->nc.N;
   const size_t cb = (size_t)((N + 3) / 4), pk_pitch = (cb + 15) / 16 * 16;
   const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
-  if (!c->h_af_ring)
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_af_ring, sizeof(double) * rvt_ctx::kAfSlots * RVT_MAX_VARIANTS, hipHostMallocMapped));
+  HIP_TRY(c, c->h_af_ring.grow(kAfRingBytes, kAfRingBytes, nullptr, false, hipHostMallocMapped));
   if (c->af_unresolved + n > rvt_ctx::kAfSlots) {
     int rc = resolve_af(c);
     if (rc) return rc;
@@ -1037,14 +979,7 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
   // device work space of the call: row and gene references, the rows' partial counts
   const size_t b_rows = (sizeof(BedRowRef) * (size_t)R + 255) / 256 * 256, b_genes = (sizeof(BedGeneRef) * (size_t)n + 255) / 256 * 256;
   const size_t need = b_rows + b_genes + sizeof(ConsolPart) * (size_t)R * nparts;
-  if (c->bedbatch_cap < need) {
-    HIP_TRY(c, sync_stream(st));
-    if (c->d_bedbatch) hipFree(c->d_bedbatch);
-    c->d_bedbatch = nullptr;
-    c->bedbatch_cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_bedbatch, need + need / 2));
-    c->bedbatch_cap = need + need / 2;
-  }
+  HIP_TRY(c, c->d_bedbatch.grow(need, need + need / 2, st));
   std::vector<BedRowRef> rows((size_t)R);
   std::vector<BedGeneRef> genes((size_t)n);
   std::vector<rvt_ctx::Pending> pend((size_t)n);
@@ -1148,14 +1083,7 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
   const size_t b_rows = (sizeof(BedRowRef) * (size_t)Rmax + 255) / 256 * 256, b_genes = (sizeof(BedGeneRef) * (size_t)kChunk + 255) / 256 * 256;
   const size_t b_parts = (sizeof(ConsolPart) * (size_t)Rmax * nparts + 255) / 256 * 256, b_af = sizeof(double) * (size_t)Rmax;
   const size_t need = b_rows + b_genes + b_parts + b_af + sizeof(long long) * 4 * (size_t)Rmax;
-  if (c->bedbatch_cap < need) {
-    HIP_TRY(c, sync_stream(st));
-    if (c->d_bedbatch) hipFree(c->d_bedbatch);
-    c->d_bedbatch = nullptr;
-    c->bedbatch_cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_bedbatch, need + need / 2));
-    c->bedbatch_cap = need + need / 2;
-  }
+  HIP_TRY(c, c->d_bedbatch.grow(need, need + need / 2, st));
   char* w = c->d_bedbatch;
   BedRowRef* d_rref = reinterpret_cast<BedRowRef*>(w);
   BedGeneRef* d_gref = reinterpret_cast<BedGeneRef*>(w + b_rows);
@@ -1362,11 +1290,9 @@ int rvt_vcf_set_samples(rvt_ctx* c, int n_file_samples, const int32_t* row_of_sa
     if (!seen[r]) return fail(c, RVT_E_INVALID, "sample map: row %lld is never addressed", (long long)r);
   int rc = rvt_sync(c);
   if (rc) return rc;
-  if (c->d_vcf_rows) hipFree(c->d_vcf_rows);
-  c->d_vcf_rows = nullptr;
-  if (c->d_vcf_sex) hipFree(c->d_vcf_sex);  // (belongs to the previous file)
-  c->d_vcf_sex = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&c->d_vcf_rows, sizeof(int) * (size_t)n_file_samples));
+  c->d_vcf_rows.reset();
+  c->d_vcf_sex.reset();  // (belongs to the previous file)
+  HIP_TRY(c, c->d_vcf_rows.alloc(sizeof(int) * (size_t)n_file_samples));
   HIP_TRY(c, hipMemcpy(c->d_vcf_rows, row_of_sample, sizeof(int) * (size_t)n_file_samples, hipMemcpyHostToDevice));
   c->vcf_n_file = n_file_samples;
   c->vcf_n_rows = rows;
@@ -1388,9 +1314,7 @@ int rvt_vcf_set_sex(rvt_ctx* c, int n_file_samples, const int8_t* sex) {
   hipSetDevice(c->device);
   int rc = rvt_sync(c);
   if (rc) return rc;
-  if (c->d_vcf_sex) hipFree(c->d_vcf_sex);
-  c->d_vcf_sex = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&c->d_vcf_sex, (size_t)n_file_samples));
+  HIP_TRY(c, c->d_vcf_sex.alloc((size_t)n_file_samples));
   HIP_TRY(c, hipMemcpy(c->d_vcf_sex, sex, (size_t)n_file_samples, hipMemcpyHostToDevice));
   return RVT_OK;
 }
@@ -1439,13 +1363,7 @@ int rvt_vcf_decode(rvt_ctx* c, int M, const char* const* sample_text, const int6
   const size_t bytes8 = (size_t)N * M;
   hipStream_t st = c->io_stream;
   HIP_TRY(c, sync_stream(st));
-  if (c->consol_i8_cap < bytes8) {
-    if (c->d_consol_i8) hipFree(c->d_consol_i8);
-    c->d_consol_i8 = nullptr;
-    c->consol_i8_cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&c->d_consol_i8, bytes8 + bytes8 / 4));
-    c->consol_i8_cap = bytes8 + bytes8 / 4;
-  }
+  HIP_TRY(c, c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4));
   VcfGene vg{sample_text, text_len, gt_index, gd_index, gq_index};
   int rc = io_err_ready(c);
   if (rc) return rc;
@@ -1493,8 +1411,8 @@ int rvt_bgen_decode(rvt_ctx* c, int M, const unsigned char* const* block, const 
   hipSetDevice(c->device);
   hipStream_t st = c->io_stream;
   HIP_TRY(c, sync_stream(st));
-  double* d_out = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d_out, sizeof(double) * (size_t)n_rows * M));
+  DevBuf<double> d_out;
+  HIP_TRY(c, d_out.alloc(sizeof(double) * (size_t)n_rows * M));
   BgenGene bg{block, block_len, layout};
   rc = io_err_ready(c);
   if (!rc) {
@@ -1504,7 +1422,7 @@ int rvt_bgen_decode(rvt_ctx* c, int M, const unsigned char* const* block, const 
   hipError_t e = hipSuccess;
   if (!rc) e = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)n_rows * M, hipMemcpyDeviceToHost, st);
   if (!rc && e == hipSuccess) e = sync_stream(st);
-  hipFree(d_out);
+  d_out.reset();
   if (rc) return rc;
   if (e != hipSuccess) return fail(c, RVT_E_HIP, "BGEN decode failed: %s", hipGetErrorString(e));
   if (const int k = c->h_io_err[rvt_ctx::kAfSlots]) {
@@ -1601,8 +1519,8 @@ int rvt_vcf_decode_dosage(rvt_ctx* c, int M, const char* const* sample_text, con
   const int64_t N = c->vcf_n_rows;
   hipStream_t st = c->io_stream;
   HIP_TRY(c, sync_stream(st));
-  double* d_out = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d_out, sizeof(double) * (size_t)N * M));
+  DevBuf<double> d_out;
+  HIP_TRY(c, d_out.alloc(sizeof(double) * (size_t)N * M));
   VcfGene vg{sample_text, text_len, tag_index, gd_index, gq_index};
   int rc = io_err_ready(c);
   if (!rc) {
@@ -1611,7 +1529,7 @@ int rvt_vcf_decode_dosage(rvt_ctx* c, int M, const char* const* sample_text, con
   }
   hipError_t e = rc ? hipSuccess : hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)N * M, hipMemcpyDeviceToHost, st);
   if (!rc && e == hipSuccess) e = sync_stream(st);
-  hipFree(d_out);
+  d_out.reset();
   if (rc) return rc;
   HIP_TRY(c, e);
   if (const int k = c->h_io_err[rvt_ctx::kAfSlots]) {
