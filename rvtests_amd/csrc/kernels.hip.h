@@ -236,15 +236,15 @@ static __global__ __launch_bounds__(64) void gene_flags_hc_kernel(const GeneDesc
       mn = fmin(mn, mu);
       mx = fmax(mx, mu);
     }
-    // (lattice dosages, hc == 2: s is the integer sum of K = den x the column sum — compared exactly)
-    const bool flip = in && !(s <= ((gd.hc == 2 || gd.hc == 4) ? (double)N * gd.lat_den : (double)N));
+    // (lattice dosages, kPathLattice: s is the integer sum of K = den x the column sum — compared exactly)
+    const bool flip = in && !(s <= (path_integer_gram(gd.hc) ? (double)N * gd.lat_den : (double)N));
     const bool poly = in && !(mn == mx);
     const bool pred = in && (j >> 4) < 8 && ((gd.pflip[(j >> 4) & 7] >> (j & 15)) & 1);
     const bool counted_mono = in && !poly && (pred ? mn != 2.0 : mn != 0.0);
     // the in-pass collapse never counts a masked entry: wrong when (int)g' > 0 for the imputed value
     const bool masked_counts = masked && poly && (flip ? mu <= 1.0 : mu >= 1.0);
-    // (hc == 3, packed rows: the kernel had the exact flips, polymorphic flags and imputed values — nothing to verify)
-    if (gd.hc != 3) bad |= (flip != pred) || counted_mono || masked_counts;
+    // (kPathPacked, packed rows: the kernel had the exact flips, polymorphic flags and imputed values — nothing to verify)
+    if (gd.hc != kPathPacked) bad |= (flip != pred) || counted_mono || masked_counts;
     const unsigned long long bf = __ballot(flip), bp = __ballot(poly);
     if (tid < 4) {
       const int b = (base >> 4) + tid;
@@ -366,7 +366,7 @@ static __global__ __launch_bounds__(256) void gene_reduce_parts_kernel(const Gen
   if (blockIdx.x * kReducePiece >= total) return;
   GeneScratch ws = gene_scratch_carve(gd.scratch, Mp, Cp);
   const bool handed_back = gd.hc && gd.flags[2 * gd.MT + 1];
-  const double lat_den = ((gd.hc == 2 || gd.hc == 4) && !handed_back) ? gd.lat_den : 0.0;
+  const double lat_den = (path_integer_gram(gd.hc) && !handed_back) ? gd.lat_den : 0.0;
   const double lat2 = lat_den > 0.0 ? lat_den * lat_den : 0.0;
   const size_t stride = (size_t)Mp * Cp;
   const int P = gd.n_wparts;
@@ -406,8 +406,7 @@ static __global__ __launch_bounds__(256) void gene_reduce_parts_kernel(const Gen
 #if !defined(RVT_K_SPLIT) || defined(RVT_K_ENGINE)
 static __global__ __launch_bounds__(1024) void gene_assemble_kernel(const GeneDesc* __restrict__ genes,
                                                             const NullConsts* __restrict__ ncp, rvt_params prm,
-                                                            unsigned tests, int n_bparts, const double* xscale,
-                                                            int parts_reduced = 0) {
+                                                            unsigned tests, int n_bparts, const double* xscale) {
   __shared__ double red[64];
   __shared__ NullConsts nc;
   const GeneDesc gd = genes[blockIdx.x];
@@ -415,14 +414,15 @@ static __global__ __launch_bounds__(1024) void gene_assemble_kernel(const GeneDe
   __syncthreads();
   Coop co{(int)threadIdx.x, (int)blockDim.x, red};
   GeneScratch ws = gene_scratch_carve(gd.scratch, gd.Mp, gd.Cp);
-  const HcMasked hcm{gd.pq, gd.wflags, hc_pq_words(gd.MT), (gd.hc == 2 || gd.hc == 4) ? gd.lat_den : 0.0, gd.pqw, xscale};
+  const HcMasked hcm{gd.pq, gd.wflags, hc_pq_words(gd.MT), path_integer_gram(gd.hc) ? gd.lat_den : 0.0, gd.pqw, xscale};
   // a hard-call gene that was handed back holds the general kernel's statistics (three rows per wave-part, G'DG itself)
   const bool handed_back = gd.hc && gd.flags[2 * gd.MT + 1];
-  const bool masks = gd.hc != 0 && !handed_back;  // (pq is null for the weighted and the lattice kernel: no masked tiles)
+  const bool masks = gd.hc != kPathGeneral && !handed_back;  // (pq is null for the weighted and the lattice kernel: no masked tiles)
   gene_assemble(co, nc, gd.M, gd.Mp, gd.Cp, gd.parts, gd.n_wparts, gd.colstat,
                 (tests & (RVT_TEST_CMC | RVT_TEST_ZEGGINI)) ? gd.bparts : nullptr, gd.n_bparts > 0 ? gd.n_bparts : n_bparts,
                 gd.af, prm, tests, ws,
-                gd.stats, gd.dbg_flip, gd.dbg_kept, masks ? &hcm : nullptr, handed_back ? kStatusHandedBack : 0u, parts_reduced != 0);
+                gd.stats, gd.dbg_flip, gd.dbg_kept, masks ? &hcm : nullptr, handed_back ? kStatusHandedBack : 0u,
+                true);  // (the wave-part images are summed already: gene_reduce_parts_kernel)
 }
 #endif  // RVT_K_ENGINE
 

@@ -77,7 +77,7 @@ int rvt_init(rvt_ctx** out, int device_id) {
         for (int b = 0; b < tk; ++b) m2[b / 32] |= 1u << (b % 32);
       }
     }
-    for (int i = 0; masked && i < kSlotsAll; ++i)
+    for (int i = 0; masked && i < kSlots; ++i)
       masked = hipExtStreamCreateWithCUMask(&c->slots[i].stream, words, m2.data()) == hipSuccess;
     if (!masked) {
       (void)hipGetLastError();
@@ -85,7 +85,7 @@ int rvt_init(rvt_ctx** out, int device_id) {
       c->k2_stream = nullptr;
       if (c->k2b_stream) hipStreamDestroy(c->k2b_stream);
       c->k2b_stream = nullptr;
-      for (int i = 0; i < kSlotsAll; ++i) {
+      for (int i = 0; i < kSlots; ++i) {
         if (c->slots[i].stream) hipStreamDestroy(c->slots[i].stream);
         c->slots[i].stream = nullptr;
       }
@@ -111,7 +111,7 @@ int rvt_init(rvt_ctx** out, int device_id) {
       if (hipExtStreamCreateWithCUMask(&c->pv_stream[0], words, mp.data()) == hipSuccess &&
           hipExtStreamCreateWithCUMask(&c->pv_stream[1], words, mp.data()) == hipSuccess) {
         c->pv_cus = pv;
-        for (int i = 0; i < kSlotsAll; ++i) {
+        for (int i = 0; i < kSlots; ++i) {
           hipEventCreateWithFlags(&c->ev_pv_in[i], hipEventDisableTiming);
           hipEventCreateWithFlags(&c->ev_pv_out[i], hipEventDisableTiming);
         }
@@ -125,7 +125,7 @@ int rvt_init(rvt_ctx** out, int device_id) {
     }
   }
   if (!masked) {
-    for (int i = 0; i < kSlotsAll; ++i)
+    for (int i = 0; i < kSlots; ++i)
       if (hipStreamCreateWithFlags(&c->slots[i].stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return RVT_E_HIP;
@@ -150,7 +150,7 @@ int rvt_init(rvt_ctx** out, int device_id) {
     hipEventCreateWithFlags(&c->ev_pack_copied[k], hipEventDisableTiming);
     hipEventCreateWithFlags(&c->ev_pack_free[k], hipEventDisableTiming);
   }
-  for (int i = 0; i < kSlotsAll; ++i) {
+  for (int i = 0; i < kSlots; ++i) {
     hipEventCreateWithFlags(&c->ev_in[i], hipEventDisableTiming);
     hipEventCreateWithFlags(&c->ev_k2[i], hipEventDisableTiming);
     hipEventCreateWithFlags(&c->ev_k2b[i], hipEventDisableTiming);
@@ -228,7 +228,7 @@ void rvt_destroy(rvt_ctx* c) {
       sync_stream(c->pv_stream[k]);
       hipStreamDestroy(c->pv_stream[k]);
     }
-  for (int i = 0; i < kSlotsAll; ++i) {
+  for (int i = 0; i < kSlots; ++i) {
     if (c->ev_pv_in[i]) hipEventDestroy(c->ev_pv_in[i]);
     if (c->ev_pv_out[i]) hipEventDestroy(c->ev_pv_out[i]);
   }
@@ -245,7 +245,7 @@ void rvt_destroy(rvt_ctx* c) {
   for (hipEvent_t e : c->stage_ev)
     if (e) hipEventDestroy(e);
   if (c->ev_io) hipEventDestroy(c->ev_io);
-  for (int i = 0; i < kSlotsAll; ++i) {
+  for (int i = 0; i < kSlots; ++i) {
     if (c->ev_in[i]) hipEventDestroy(c->ev_in[i]);
     if (c->ev_k2[i]) hipEventDestroy(c->ev_k2[i]);
     if (c->ev_k2b[i]) hipEventDestroy(c->ev_k2b[i]);
@@ -1038,42 +1038,46 @@ int cov_constants(rvt_ctx* c, bool fam, CovConsts* ccp, std::vector<double>* zzp
 // Arena layout of one gene of a batch (shared by run_batch and rvt_reserve).
 struct GeneOff {
   size_t parts, colstat, masks, flags, bparts, scratch, lambda, qags, stats, vt, dbg_flip, dbg_kept, pq, wflags;
+  size_t pqw;  // from BatchOff::pqw (layout_arena)
 };
-// hc: 1 = hard-call path (no mask planes, burden records per wave-part), 0 = general path, -1 = either (rvt_reserve)
-static void layout_gene(int M, int d, int n_wparts, int64_t nsteps, int n_bparts, bool dbg, int hc, size_t* total,
+// Which sub-buffers a gene's work space holds.  Not a KernelPath: every integer kernel lays its gene out the same way.
+enum class GeneArena {
+  General,  // mask planes, three column-statistics rows, burden records per burden part
+  Integer,  // no mask planes, kHcColstatRows rows, burden records per wave-part
+  Either,   // room for both (rvt_reserve: the path is not known yet)
+};
+static void layout_gene(int M, int d, int n_wparts, int64_t nsteps, int n_bparts, bool dbg, GeneArena ga, Layout& L,
                         GeneOff* o, bool vt = false) {
-  auto add = [&](size_t bytes) {
-    *total = (*total + 255) / 256 * 256;
-    const size_t at = *total;
-    *total += bytes;
-    return at;
-  };
+  const bool general = ga == GeneArena::General, integer = ga == GeneArena::Integer;
   const int MT = (M + 15) / 16, CT = (M + d + 1 + 15) / 16, Mp = 16 * MT, Cp = 16 * CT;
-  o->parts = add(sizeof(double) * (size_t)n_wparts * Mp * Cp);
-  o->colstat = add(sizeof(double) * (size_t)n_wparts * (hc == 0 ? 3 : kHcColstatRows) * Mp);
-  o->masks = (hc == 1) ? 0 : add(sizeof(unsigned long long) * (size_t)2 * nsteps * MT * 4);
+  o->parts = L.take(sizeof(double) * (size_t)n_wparts * Mp * Cp);
+  o->colstat = L.take(sizeof(double) * (size_t)n_wparts * (general ? 3 : kHcColstatRows) * Mp);
+  o->masks = integer ? 0 : L.take(sizeof(unsigned long long) * (size_t)2 * nsteps * MT * 4);
   o->pq = o->wflags = 0;
-  if (hc != 0 && MT <= kHcMaxMT) {  // packed counters of the masked tiles + flags, per wave-part (suffstat_hc.hip.h)
-    o->pq = add(sizeof(unsigned) * (size_t)n_wparts * hc_pq_words(MT));
-    o->wflags = add(sizeof(unsigned) * (size_t)n_wparts);
+  if (!general && MT <= kHcMaxMT) {  // packed counters of the masked tiles + flags, per wave-part (suffstat_hc.hip.h)
+    o->pq = L.take(sizeof(unsigned) * (size_t)n_wparts * hc_pq_words(MT));
+    o->wflags = L.take(sizeof(unsigned) * (size_t)n_wparts);
   }
-  o->flags = add(sizeof(unsigned short) * (2 * MT + 2));
-  const int nb = (hc == 1) ? n_wparts : (hc == 0 ? n_bparts : std::max(n_bparts, n_wparts));
-  o->bparts = add(sizeof(double) * (size_t)nb * 2 * (3 + d));
-  o->scratch = add(sizeof(double) * (gene_scratch_doubles(Mp, Cp) + 8));
-  o->lambda = add(sizeof(double) * 2 * M);
-  o->qags = add(qags_workspace_bytes(kSkatoLimit));
-  o->stats = add(sizeof(GeneStats));
-  o->vt = vt ? add(sizeof(double) * (gene_vt_doubles(Mp) + Mp)) : 0;
+  o->flags = L.take(sizeof(unsigned short) * (2 * MT + 2));
+  const int nb = integer ? n_wparts : (general ? n_bparts : std::max(n_bparts, n_wparts));
+  o->bparts = L.take(sizeof(double) * (size_t)nb * 2 * (3 + d));
+  o->scratch = L.take(sizeof(double) * (gene_scratch_doubles(Mp, Cp) + 8));
+  o->lambda = L.take(sizeof(double) * 2 * M);
+  o->qags = L.take(qags_workspace_bytes(kSkatoLimit));
+  o->stats = L.take(sizeof(GeneStats));
+  o->vt = vt ? L.take(sizeof(double) * (gene_vt_doubles(Mp) + Mp)) : 0;
   o->dbg_flip = o->dbg_kept = 0;
   if (dbg) {
-    o->dbg_flip = add(sizeof(int) * M);
-    o->dbg_kept = add(sizeof(int) * M);
+    o->dbg_flip = L.take(sizeof(int) * M);
+    o->dbg_kept = L.take(sizeof(int) * M);
   }
 }
 
-// kind (optional, per gene): what the engine's own decoder wrote into the block — 1 hard calls (+ imputed means),
-// 0 dosages, -1 unknown.
+// where the sub-buffers that a batch's genes share land in the arena (layout_arena)
+struct BatchOff {
+  size_t af, desc, res, pqw, pqw_bytes, lists, cov, cov_xz, cov_cs, cov_poly, cov_bur, cov_ok, dbg_cmc, dbg_zeg;
+};
+
 // RVT_TRACE_BATCH=1: host time of run_batch's phases to stderr (diagnosis of a host-bound launch path)
 struct BatchTrace {
   bool on;
@@ -1152,14 +1156,161 @@ static int ensure_hcp_planes(rvt_ctx* c) {
   return RVT_OK;
 }
 
-int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const double* af,
-              const int64_t* ids, uint32_t tests, const rvt_params* prm, rvt_gene_result* out,
-              DebugOut* dbg, CovOut* cov, const signed char* kind) {
+// What a batch as a whole may use — the null model, the call and the switches, before any gene is looked at.
+struct BatchCaps {
+  bool nd_is_default;  // the kernels read the context's own null tile (no family set swapped in)
+  bool score_hc;       // MetaScore slices whose content the caller states per slice (CovOut::slice_hc)
+  bool hcw;            // binary trait: the weighted hard-call kernel's digit planes exist
+  bool hc_possible;    // the integer kernels may be used at all
+  bool hcx;            // binary trait: hard-call genes take the workgroup-cooperative kernel (plan_batch: if one starts on it)
+  bool lat_possible;   // the lattice kernel may be used
+  bool fdx_model;      // the float-digit kernel may be used (wave-part length aside)
+  bool predict_hc;     // blocks of unknown content start on the hard-call kernel (rvt_set_content_hint)
+  int hc_max_mt;       // widest tile class of the batch's hard-call kernel
+};
+static_assert(kHcxMaxMT == kHcwMaxMT, "the cooperative kernel takes every class the weighted hard-call kernel takes");
+
+static BatchCaps batch_caps(const rvt_ctx* c, uint32_t tests, const DebugOut* dbg, const CovOut* cov) {
+  const NullConsts& nc = c->nc;
+  const int d = nc.d;
+  const int64_t ld = nc.ld;
+  const bool dbg_cmc = dbg && dbg->cmc, fam = (tests & RVT_TEST_FAMSKAT) != 0;
+  BatchCaps cp;
+  cp.nd_is_default = c->d_nulltile && c->d_X == c->d_nulltile && c->d_rr == c->d_nulltile + (size_t)ld * d &&
+                     c->d_zeros == c->d_nulltile + (size_t)ld * (d + 1);
+  cp.score_hc = cov && cov->score && cov->slice_hc;
+  // (a binary trait takes the weighted hard-call kernel when its digit planes exist: gene tests and MetaScore slices)
+  cp.hcw = nc.binary && c->d_nulltile_w != nullptr && c->d_vq != nullptr && (!cov || cp.score_hc);
+  cp.hc_possible = c->hc_enabled && (!nc.binary || cp.hcw) && (!cov || cp.score_hc) && !dbg_cmc && d <= kHcMaxD && !fam &&
+                   c->d_nulltile != nullptr && cp.nd_is_default;
+  // binary trait, gene tests: the hard-call genes of the batch take the workgroup-cooperative integer kernel when the null
+  // model's operands exist (rvt_set_null); MetaScore slices and debug runs keep the one-wave kernel
+  cp.hcx = cp.hc_possible && c->hcx_ok && !cov;
+  // dosages on a decimal lattice (rvt_set_dosage_lattice): the caller's doubles when the hint says dosages, and what the
+  // VCF dosage decoder wrote — gene_suffstat_lat, which tests every value like the hard-call kernel does
+  cp.lat_possible = cp.hc_possible && !nc.binary && !cov && c->lattice_den > 0;
+  // float-precision dosages (quantitative trait) — gene_suffstat_fdx, which tests every value as well.  Round 5: OPT-IN —
+  // only when the caller asked for it with rvt_set_dosage_float(1).  It computes G'G of float-precision dosages as an exact
+  // integer (bit-reproducible whatever the split of the samples), but it does not pay in speed (0.44 of HBM live against the
+  // fp64 kernel's 0.42: +3 %, DESIGN 7), and BGEN genes with a missing call paid a failed pass on it — so BGEN genes no
+  // longer start on it by themselves.
+  cp.fdx_model = cp.hc_possible && !nc.binary && !cov && c->fdx_ok && c->lattice_den == 0 && c->dosage_float;
+  cp.predict_hc = c->content_hint != 0;
+  cp.hc_max_mt = cp.hcw ? kHcwMaxMT : kHcMaxMT;
+  return cp;
+}
+
+// The kernel gene g (M columns, block content kb) starts on.  THE per-gene rule: the batch-level questions of plan_batch
+// ("does a gene of the batch start on kernel X") are loops over it — they once were predicates of their own and drifted
+// apart.  steps_per: the wave-part length from choose_split, which the float-digit kernel bounds; while the
+// split is not chosen yet, kSplitPending gives the candidate answer (that bound aside).
+constexpr int kSplitPending = 0;
+static int gene_path(const rvt_ctx* c, const BatchCaps& cp, const CovOut* cov, int g, int M, KindBits kb, int steps_per) {
+  const int MT = (M + 15) / 16, k = kb.kind;
+  const bool packed = k == kKindPacked;
+  // an integer kernel: a single-pass tile class, and an fp64 block that one buffer descriptor of M x ld x 8 < 2^31 bytes
+  // covers (packed rows are not doubles — four samples a byte — and have a descriptor of their own: no such bound)
+  if (!cp.hc_possible || MT > cp.hc_max_mt || !(packed || (uint64_t)M * (uint64_t)c->nc.ld * 8ull < (1ull << 31)))
+    return kPathGeneral;
+  if (cp.score_hc)  // (packed: a slice of a resident .bed matrix, rvt_score_bed_dev)
+    return packed ? kPathPacked : (cov->slice_hc[g] ? kPathHardCall : kPathGeneral);
+  if (packed) return kPathPacked;  // the block holds PLINK 2-bit rows (rvt_submit_gene_bed)
+  const bool unknown = k == kKindUnknown;
+  // M <= 64; the batch's wave-parts are cut for it (choose_split)
+  if (cp.fdx_model && steps_per <= kFdxMaxSteps && MT <= kFdxEngineMT && (k == kKindDosage || (unknown && !cp.predict_hc)))
+    return kPathFloatDigit;
+  if (cp.lat_possible && MT <= kLatMaxMT && (k == kKindDecimal || (unknown && !cp.predict_hc))) return kPathLattice;
+  return (k == kKindHardCall || (unknown && cp.predict_hc)) ? kPathHardCall : kPathGeneral;
+}
+
+// One batch on its way through run_batch: what its phases hand each other.
+struct Batch {
   BatchTrace bt;
-  if (!c || n < 0 || (n > 0 && (!dG || !Ms || !af || !out))) return fail(c, RVT_E_INVALID, "bad batch arguments");
-  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
-  if (n == 0) return RVT_OK;
-  hipSetDevice(c->device);
+  // the call
+  int n = 0;
+  const double* const* dG = nullptr;
+  const int* Ms = nullptr;
+  const double* af = nullptr;
+  const int64_t* ids = nullptr;
+  uint32_t tests = 0;
+  rvt_params params;
+  DebugOut* dbg = nullptr;
+  CovOut* cov = nullptr;
+  const signed char* kind = nullptr;
+  // the slot (acquire_slot)
+  Slot* sl = nullptr;
+  int slot_idx = 0;
+  hipStream_t st = nullptr;
+  // the plan (plan_batch)
+  BatchCaps caps{};
+  bool fdx_batch = false;  // a gene starts on the float-digit kernel
+  int n_wparts = 0, steps_per = 0, n_bparts = 0;
+  // descriptors in the caller's order and the arena (describe_genes)
+  std::vector<GeneDesc> desc;
+  std::vector<GeneOff> offs;
+  BatchOff off;
+  size_t af_total = 0;
+  int maxM = 0, n_hc = 0, n_gen = 0;  // descriptors [0, n_gen) take the general kernels, [n_gen, n) the integer kernels
+  char* base = nullptr;
+  // sorted descriptors, host and device (upload_genes)
+  GeneDesc *h_desc = nullptr, *d_desc = nullptr;
+  NullDev nd;
+};
+
+// The arena of one batch: every gene's sub-buffers (b.offs), then what the batch shares (b.off).  Returns the bytes.
+// worst_case (rvt_reserve: no descriptors yet): every gene gets room for either path.
+static size_t layout_arena(const rvt_ctx* c, Batch& b, bool worst_case) {
+  const int d = c->nc.d;
+  const int64_t N = c->nc.N, nsteps = c->nc.ld >> 4;
+  Layout L;
+  size_t af_total = 0;
+  int n_hc = 0;
+  b.offs.resize(b.n);
+  b.off = BatchOff{};
+  for (int g = 0; g < b.n; ++g) {
+    GeneOff& o = b.offs[g];
+    const GeneArena ga = worst_case ? GeneArena::Either : (b.desc[g].hc ? GeneArena::Integer : GeneArena::General);
+    layout_gene(b.Ms[g], d, b.n_wparts, nsteps, b.n_bparts, b.dbg != nullptr, ga, L, &o, (b.tests & RVT_TEST_ANALYTICVT) != 0);
+    af_total += (size_t)b.Ms[g];
+    if (ga != GeneArena::General) ++n_hc;
+    // masked-entry tables of the genes on the cooperative weighted kernel (64-bit integers, zeroed before the launch)
+    o.pqw = b.off.pqw_bytes;
+    if (b.caps.hcx && (worst_case || b.desc[g].hc == kPathHardCall))
+      b.off.pqw_bytes += sizeof(unsigned long long) * hcx_pq_entries(16 * ((b.Ms[g] + 15) / 16));
+  }
+  BatchOff& bo = b.off;
+  bo.af = L.take(sizeof(double) * af_total);
+  bo.desc = L.take(sizeof(GeneDesc) * b.n);
+  bo.res = L.take(sizeof(rvt_gene_result) * b.n);
+  if (bo.pqw_bytes) bo.pqw = L.take(bo.pqw_bytes);
+  // device work lists of the hard-call genes (gene_flags_hc_kernel): [0] handed back, [1] burden sums to redo, then
+  // the two index lists
+  bo.lists = L.take(sizeof(int) * (4 + 2 * (size_t)std::max(n_hc, 1)));
+  if (b.cov && b.cov->score) {  // one gene per 16-column slice of the block: per-variant records only
+    bo.cov_bur = L.take(sizeof(double) * af_total * (b.cov->wald ? std::max(5, 3 * d) : 5));
+    bo.cov_ok = L.take(sizeof(int) * af_total);
+  } else if (b.cov) {
+    const size_t V = (size_t)b.Ms[0];
+    bo.cov = L.take(sizeof(double) * V * V);
+    bo.cov_xz = L.take(sizeof(double) * V * (size_t)d);
+    bo.cov_cs = L.take(sizeof(double) * V);
+    bo.cov_poly = L.take(sizeof(int) * V);
+    bo.cov_bur = L.take(sizeof(double) * V * 4);
+  }
+  if (b.dbg && b.dbg->cmc) {
+    bo.dbg_cmc = L.take(sizeof(double) * N);
+    bo.dbg_zeg = L.take(sizeof(double) * N);
+  }
+  return L.total;
+}
+
+// pinned staging of a batch: descriptors | allele frequencies | records
+static size_t batch_stage_bytes(int n, size_t af_total) {
+  return sizeof(GeneDesc) * n + sizeof(double) * af_total + sizeof(rvt_gene_result) * n + 64;
+}
+
+// flush the column queue, take the slot that was launched longest ago and drain it
+static int acquire_slot(rvt_ctx* c, Batch& b) {
   if (c->colq.n > 0) {  // (columns queued by rvt_block_upload_columns may belong to a block of this batch)
     int rcq = flush_col_queue(c);
     if (rcq) return rcq;
@@ -1169,299 +1320,219 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
   Slot* slp = &c->slots[0];
   for (int i = 1; i < kSlots; ++i)
     if (c->slots[i].seq < slp->seq) slp = &c->slots[i];
-  if (dbg) {  // inspection calls run alone
+  if (b.dbg) {  // inspection calls run alone
     int rc = rvt_sync(c);
     if (rc) return rc;
     slp = &c->slots[0];
   }
-  Slot& sl = *slp;
-  {
-    int rc = finish_slot(c, sl);
-    if (rc) return rc;
-  }
-  bt.mark(0);
-  sl.seq = ++c->launch_seq;
-  hipStream_t st = sl.stream;
+  int rc = finish_slot(c, *slp);
+  if (rc) return rc;
+  b.bt.mark(0);
+  b.sl = slp;
+  b.slot_idx = (int)(slp - &c->slots[0]);
+  b.st = slp->stream;
+  slp->seq = ++c->launch_seq;
   if (c->io_wait_pending) {
-    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_io, 0));
+    HIP_TRY(c, hipStreamWaitEvent(b.st, c->ev_io, 0));
     c->io_wait_pending = false;
   }
-  rvt_params params;
-  if (prm)
-    params = *prm;
-  else
-    params = rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05};
-  const NullConsts& nc = c->nc;
-  const int d = nc.d;
-  const int64_t ld = nc.ld, N = nc.N, nsteps = ld >> 4;
-  const int n_bparts = (int)((N + kBurdenSPB - 1) / kBurdenSPB);
-  // binary trait, gene tests: the hard-call genes of the batch take the workgroup-cooperative integer kernel when the null
-  // model's operands exist (rvt_set_null); MetaScore slices and debug runs keep the one-wave kernel
-  bool hcx = nc.binary && c->hcx_ok && c->hc_enabled && !cov && !(dbg && dbg->cmc) && !(tests & RVT_TEST_FAMSKAT);
-  if (hcx) {  // ... and only if a gene of the batch will start on it (the split of the sample axis follows the kernel: a batch
-              // of dosage blocks must be cut exactly as with the hard-call path off — the same records bit for bit)
-    bool any = false;
-    for (int g = 0; g < n && !any; ++g) {
-      const int k = kind ? (kind[g] < 0 ? -1 : (kind[g] & 0xf)) : -1;
-      any = (Ms[g] + 15) / 16 <= kHcxMaxMT && (k == 1 || (k < 0 && c->content_hint != 0));
-    }
-    hcx = any;
-  }
-  const bool nd_is_default = c->d_nulltile && c->d_X == c->d_nulltile && c->d_rr == c->d_nulltile + (size_t)ld * d &&
-                             c->d_zeros == c->d_nulltile + (size_t)ld * (d + 1);
-  const bool score_hc = cov && cov->score && cov->slice_hc;
-  // (a binary trait takes the weighted hard-call kernel when its digit planes exist: gene tests and MetaScore slices)
-  const bool hcw = nc.binary && c->d_nulltile_w != nullptr && c->d_vq != nullptr && (!cov || score_hc);
-  const bool hc_possible = c->hc_enabled && (!nc.binary || hcw) && (!cov || score_hc) &&
-                           !(dbg && dbg->cmc) && d <= kHcMaxD && !(tests & RVT_TEST_FAMSKAT) &&
-                           c->d_nulltile != nullptr && nd_is_default;
-  // the per-gene condition of the float-digit dosage kernel (quantitative trait; wave-part length aside).  Round 5: OPT-IN —
-  // only when the caller asked for it with rvt_set_dosage_float(1).  It computes G'G of float-precision dosages as an exact
-  // integer (bit-reproducible whatever the split of the samples), but it does not pay in speed (0.44 of HBM live against the
-  // fp64 kernel's 0.42: +3 %, DESIGN 7), and BGEN genes with a missing call paid a failed pass on it — so BGEN genes no
-  // longer start on it by themselves.  ONE predicate for
-  // the batch-level prediction below and the per-gene decision further down (they had drifted apart)
-  const bool fdx_model = hc_possible && !nc.binary && !cov && c->fdx_ok && c->lattice_den == 0;
-  auto fdx_gene = [&](int g) {
-    const int k = kind ? (kind[g] < 0 ? -1 : (kind[g] & 0xf)) : -1;
-    return fdx_model && (Ms[g] + 15) / 16 <= kFdxEngineMT && (uint64_t)Ms[g] * (uint64_t)ld * 8ull < (1ull << 31) &&
-           c->dosage_float && (k == 0 || (k < 0 && c->content_hint == 0));
-  };
-  // does a gene of the batch start on it?  (its wave-parts are shorter, and the batch is not split over two streams)
-  bool fdx_batch = false;
-  for (int g = 0; g < n && !fdx_batch; ++g) fdx_batch = fdx_gene(g);
-  int n_wparts, steps_per;
-  choose_split(ld, n, nc.binary != 0, &n_wparts, &steps_per, hcx, fdx_batch);
-  // ---- sizes ---------------------------------------------------------------------------------------
-  std::vector<GeneDesc> desc(n);
-  size_t total = 0, af_total = 0;
-  auto add = [&](size_t bytes) {
-    total = (total + 255) / 256 * 256;
-    const size_t o = total;
-    total += bytes;
-    return o;
-  };
-  std::vector<GeneOff> offs(n);
-  int maxM = 0, n_hc = 0;
-  const int hc_max_mt = hcw ? kHcwMaxMT : kHcMaxMT;
-  const bool predict_hc = c->content_hint != 0;  // blocks of unknown content (rvt_set_content_hint)
-  // dosages on a decimal lattice (rvt_set_dosage_lattice): the caller's doubles when the hint says dosages, and what the
-  // VCF dosage decoder wrote — gene_suffstat_lat (hc = 2), which tests every value like the hard-call kernel does
-  const bool lat_possible = hc_possible && !nc.binary && !cov && c->lattice_den > 0;
-  // float-precision dosages (what the BGEN decoder wrote: kind 0; blocks of unknown content when rvt_set_dosage_float says
-  // so): gene_suffstat_fdx (hc = 4), which tests every value as well.  M <= 64; the batch's wave-parts are cut for it.
-  const bool fdx_possible = fdx_model && steps_per <= kFdxMaxSteps;
+  return RVT_OK;
+}
 
+// which kernels the batch may use, and — from the kernels its genes start on — how the sample axis is cut
+static void plan_batch(const rvt_ctx* c, Batch& b) {
+  b.caps = batch_caps(c, b.tests, b.dbg, b.cov);
+  auto any_starts_on = [&](int path) {
+    for (int g = 0; g < b.n; ++g)
+      if (gene_path(c, b.caps, b.cov, g, b.Ms[g], decode_kind(b.kind, g), kSplitPending) == path) return true;
+    return false;
+  };
+  // the cooperative kernel only if a gene of the batch will start on it (the split of the sample axis follows the kernel: a
+  // batch of dosage blocks must be cut exactly as with the hard-call path off — the same records bit for bit)
+  b.caps.hcx = b.caps.hcx && any_starts_on(kPathHardCall);
+  // does a gene of the batch start on the float-digit kernel?  (its wave-parts are shorter, and the batch is not split over
+  // two streams)
+  b.fdx_batch = any_starts_on(kPathFloatDigit);
+  b.n_bparts = (int)((c->nc.N + kBurdenSPB - 1) / kBurdenSPB);
+  choose_split(c->nc.ld, b.n, c->nc.binary != 0, &b.n_wparts, &b.steps_per, b.caps.hcx, b.fdx_batch);
+}
+
+// the genes' descriptors (pointers aside) in the caller's order, the arena's layout and the arena itself
+static int describe_genes(rvt_ctx* c, Batch& b) {
+  const NullConsts& nc = c->nc;
+  const int d = nc.d, n = b.n;
+  b.desc.resize(n);
   for (int g = 0; g < n; ++g) {
-    const int M = Ms[g];
+    const int M = b.Ms[g];
     if (M < 1) return fail(c, RVT_E_INVALID, "gene %d has M=%d", g, M);
     if (M > RVT_MAX_VARIANTS) return fail(c, RVT_E_TOO_LARGE, "gene %d: M=%d exceeds RVT_MAX_VARIANTS", g, M);
-    maxM = std::max(maxM, M);
-    GeneDesc& gd = desc[g];
+    b.maxM = std::max(b.maxM, M);
+    GeneDesc& gd = b.desc[g];
     std::memset(&gd, 0, sizeof(gd));
-    gd.G = dG[g];
+    gd.G = b.dG[g];
     gd.M = M;
     gd.MT = (M + 15) / 16;
     gd.CT = (M + d + 1 + 15) / 16;
     gd.Mp = 16 * gd.MT;
     gd.Cp = 16 * gd.CT;
-    gd.n_wparts = n_wparts;
-    gd.steps_per_wpart = steps_per;
-    gd.gene_id = ids ? ids[g] : g;
-    // hard-call path: unweighted null model, block known to hold only 0.0 / 1.0 / 2.0, a single-pass tile class
-    gd.hc = 0;
-    const bool kind_packed = kind && kind[g] >= 0 && (kind[g] & 0xf) == 3;  // (bit 4 of a packed kind: T from digit planes)
-    gd.hcp_planes = 0;
-    if (hc_possible && gd.MT <= hc_max_mt && (kind_packed || (uint64_t)M * (uint64_t)ld * 8ull < (1ull << 31))) {
-      if (score_hc) {
-        gd.hc = cov->slice_hc[g] ? 1 : 0;
-        if (kind_packed) {  // a slice of a resident .bed matrix (rvt_score_bed_dev): packed rows, gene_suffstat_hcp
-          gd.hc = 3;
-          gd.pk_pitch = (int)(((size_t)((N + 3) / 4) + 15) / 16 * 16);
-          gd.hcp_planes = (kind[g] & 0x10) ? 1 : 0;
-        }
-      } else {
-        const int k = kind ? (kind[g] < 0 ? -1 : (kind[g] & 0xf)) : -1;
-        gd.hc = (k == 1 || (k < 0 && predict_hc)) ? 1 : 0;
-        if (k == 3) {  // the block holds PLINK 2-bit rows (rvt_submit_gene_bed): gene_suffstat_hcp
-          gd.hc = 3;
-          gd.hcp_planes = (kind[g] & 0x10) ? 1 : 0;
-          gd.pk_pitch = (int)(((size_t)((N + 3) / 4) + 15) / 16 * 16);
-        }
-        if (lat_possible && gd.MT <= kLatMaxMT && (k == 2 || (k < 0 && !predict_hc))) {
-          gd.hc = 2;
-          gd.lat_den = (double)c->lattice_den;
-        }
-        if (fdx_possible && fdx_gene(g)) {
-          gd.hc = 4;
-          gd.lat_den = 0x1p37;
-        }
-      }
-    }
-    if (kind_packed && gd.hc != 3)
+    gd.n_wparts = b.n_wparts;
+    gd.steps_per_wpart = b.steps_per;
+    gd.gene_id = b.ids ? b.ids[g] : g;
+    const KindBits kb = decode_kind(b.kind, g);
+    gd.hc = gene_path(c, b.caps, b.cov, g, M, kb, b.steps_per);
+    if (gd.hc == kPathPacked) {
+      gd.pk_pitch = (int)hcp_row_pitch(nc.N);
+      gd.hcp_planes = kb.planes ? 1 : 0;
+    } else if (kb.kind == kKindPacked) {
       return fail(c, RVT_E_STATE, "gene %d was submitted as packed rows but the batch cannot take the packed kernel", g);
-    gd.n_bparts = gd.hc ? n_wparts : n_bparts;
-    if (gd.hc) {
-      n_hc++;
-      for (int j = 0; j < M; ++j)  // predicted flips: column sum > N  <=>  allele frequency > 1/2 (verified on the device)
-        if (af[af_total + j] > 0.5) gd.pflip[j >> 4] |= (unsigned short)(1u << (j & 15));
     }
-    layout_gene(M, d, n_wparts, nsteps, n_bparts, dbg != nullptr, gd.hc ? 1 : 0, &total, &offs[g],
-                (tests & RVT_TEST_ANALYTICVT) != 0);
-    af_total += M;
+    if (gd.hc == kPathLattice) gd.lat_den = (double)c->lattice_den;
+    if (gd.hc == kPathFloatDigit) gd.lat_den = 0x1p37;
+    gd.n_bparts = gd.hc ? b.n_wparts : b.n_bparts;
+    if (gd.hc) {
+      b.n_hc++;
+      for (int j = 0; j < M; ++j)  // predicted flips: column sum > N  <=>  allele frequency > 1/2 (verified on the device)
+        if (b.af[b.af_total + j] > 0.5) gd.pflip[j >> 4] |= (unsigned short)(1u << (j & 15));
+    }
+    b.af_total += M;
   }
-  bt.mark(1);
-  const size_t off_af = add(sizeof(double) * af_total);
-  const size_t off_desc = add(sizeof(GeneDesc) * n);
-  const size_t off_res = add(sizeof(rvt_gene_result) * n);
-  // masked-entry tables of the genes on the cooperative weighted kernel (64-bit integers, zeroed before the launch)
-  size_t pqw_bytes = 0;
-  std::vector<size_t> pqw_at(hcx ? n : 0);
-  if (hcx)
-    for (int g = 0; g < n; ++g)
-      if (desc[g].hc == 1) {
-        pqw_at[g] = pqw_bytes;
-        pqw_bytes += sizeof(unsigned long long) * hcx_pq_entries(desc[g].Mp);
-      }
-  const size_t off_pqw = pqw_bytes ? add(pqw_bytes) : 0;
-  // device work lists of the hard-call genes (gene_flags_hc_kernel): [0] handed back, [1] burden sums to redo, then
-  // the two index lists
-  const size_t off_lists = add(sizeof(int) * (4 + 2 * (size_t)std::max(n_hc, 1)));
-  size_t off_cov = 0, off_cov_xz = 0, off_cov_cs = 0, off_cov_poly = 0, off_cov_bur = 0, off_cov_ok = 0;
-  if (cov && cov->score) {  // one gene per 16-column slice of the block: per-variant records only
-    size_t vt = 0;
-    for (int g = 0; g < n; ++g) vt += (size_t)Ms[g];
-    off_cov_bur = add(sizeof(double) * vt * (cov->wald ? std::max(5, 3 * d) : 5));
-    off_cov_ok = add(sizeof(int) * vt);
-  } else if (cov) {
-    const size_t V = (size_t)Ms[0];
-    off_cov = add(sizeof(double) * V * V);
-    off_cov_xz = add(sizeof(double) * V * (size_t)d);
-    off_cov_cs = add(sizeof(double) * V);
-    off_cov_poly = add(sizeof(int) * V);
-    off_cov_bur = add(sizeof(double) * V * 4);
-  }
-  size_t off_dbg_cmc = 0, off_dbg_zeg = 0;
-  if (dbg && dbg->cmc) {
-    off_dbg_cmc = add(sizeof(double) * N);
-    off_dbg_zeg = add(sizeof(double) * N);
-  }
-  int rc = ensure_arena(c, sl, total + 4096);
+  b.n_gen = n - b.n_hc;
+  const size_t total = layout_arena(c, b, false);
+  b.bt.mark(1);
+  int rc = ensure_arena(c, *b.sl, total + 4096);
   if (rc) return rc;
-  char* base = sl.arena;
+  b.base = b.sl->arena;
+  return RVT_OK;
+}
+
+// genes whose tile configuration has no unrolled body (more than 6 row tiles, or — with many covariates — more than
+// one extra column tile) go to the panelled kernel
+static bool needs_panel(const GeneDesc& g) { return !g.hc && (g.MT > kMaxMT || g.CT > g.MT + 1); }
+
+// the descriptors' pointers into the arena; then the descriptors, sorted for the launches, and the allele frequencies go to
+// the device
+static int upload_genes(rvt_ctx* c, Batch& b) {
+  const int n = b.n;
+  Slot& sl = *b.sl;
+  char* base = b.base;
+  const BatchOff& bo = b.off;
   // ---- host staging: descriptors + af ------------------------------------------------------------------
-  const size_t stage_bytes = sizeof(GeneDesc) * n + sizeof(double) * af_total + sizeof(rvt_gene_result) * n + 64;
-  rc = ensure_stage(c, sl, stage_bytes);
+  int rc = ensure_stage(c, sl, batch_stage_bytes(n, b.af_total));
   if (rc) return rc;
-  GeneDesc* h_desc = reinterpret_cast<GeneDesc*>(sl.h_stage.get());
+  b.h_desc = reinterpret_cast<GeneDesc*>(sl.h_stage.get());
   double* h_af = reinterpret_cast<double*>(sl.h_stage + sizeof(GeneDesc) * n);
   size_t afpos = 0;
   for (int g = 0; g < n; ++g) {
-    GeneDesc& gd = desc[g];
-    const GeneOff& o = offs[g];
+    GeneDesc& gd = b.desc[g];
+    const GeneOff& o = b.offs[g];
+    const bool coop = b.caps.hcx && gd.hc == kPathHardCall;
     gd.parts = reinterpret_cast<double*>(base + o.parts);
     gd.colstat = reinterpret_cast<double*>(base + o.colstat);
     gd.masks = gd.hc ? nullptr : reinterpret_cast<unsigned long long*>(base + o.masks);
-    gd.pq = ((gd.hc == 1 || gd.hc == 3) && !hcw && o.pq) ? reinterpret_cast<unsigned*>(base + o.pq) : nullptr;
-    gd.pqw = (hcx && gd.hc == 1) ? reinterpret_cast<unsigned long long*>(base + off_pqw + pqw_at[g]) : nullptr;
+    gd.pq = ((gd.hc == kPathHardCall || gd.hc == kPathPacked) && !b.caps.hcw && o.pq) ? reinterpret_cast<unsigned*>(base + o.pq)
+                                                                                        : nullptr;
+    gd.pqw = coop ? reinterpret_cast<unsigned long long*>(base + bo.pqw + o.pqw) : nullptr;
     gd.wflags = (gd.hc && o.wflags) ? reinterpret_cast<unsigned*>(base + o.wflags) : nullptr;
     gd.flags = reinterpret_cast<unsigned short*>(base + o.flags);
     gd.bparts = reinterpret_cast<double*>(base + o.bparts);
     gd.scratch = reinterpret_cast<double*>(base + o.scratch);
     gd.lambda = reinterpret_cast<double*>(base + o.lambda);
     gd.qags_mem = base + o.qags;
-    gd.af = reinterpret_cast<const double*>(base + off_af) + afpos;
+    gd.af = reinterpret_cast<const double*>(base + bo.af) + afpos;
     gd.stats = reinterpret_cast<GeneStats*>(base + o.stats);
-    gd.vt_mem = (tests & RVT_TEST_ANALYTICVT) ? reinterpret_cast<double*>(base + o.vt) : nullptr;
-    gd.result = reinterpret_cast<rvt_gene_result*>(base + off_res) + g;
-    if (dbg) {
+    gd.vt_mem = (b.tests & RVT_TEST_ANALYTICVT) ? reinterpret_cast<double*>(base + o.vt) : nullptr;
+    gd.result = reinterpret_cast<rvt_gene_result*>(base + bo.res) + g;
+    if (b.dbg) {
       gd.dbg_flip = reinterpret_cast<int*>(base + o.dbg_flip);
       gd.dbg_kept = reinterpret_cast<int*>(base + o.dbg_kept);
-      if (dbg->cmc && g == 0) {
-        gd.dbg_cmc = reinterpret_cast<double*>(base + off_dbg_cmc);
-        gd.dbg_zeg = reinterpret_cast<double*>(base + off_dbg_zeg);
+      if (b.dbg->cmc && g == 0) {
+        gd.dbg_cmc = reinterpret_cast<double*>(base + bo.dbg_cmc);
+        gd.dbg_zeg = reinterpret_cast<double*>(base + bo.dbg_zeg);
       }
     }
     afpos += gd.M;
   }
-  bt.mark(2);
-  std::memcpy(h_af, af, sizeof(double) * af_total);
-  HIP_TRY(c, hipMemcpyAsync(base + off_af, h_af, sizeof(double) * af_total, hipMemcpyHostToDevice, st));
-  // widest genes first: their workgroups run longest, so they should not be the tail of the launch
+  b.bt.mark(2);
+  std::memcpy(h_af, b.af, sizeof(double) * b.af_total);
+  HIP_TRY(c, hipMemcpyAsync(base + bo.af, h_af, sizeof(double) * b.af_total, hipMemcpyHostToDevice, b.st));
+  // order: general-path genes first (panelled ones in front), then the integer kernels' genes by path; widest first inside
+  // each: their workgroups run longest, so they should not be the tail of the launch
   std::vector<int> order(n);
   for (int g = 0; g < n; ++g) order[g] = g;
-  // genes whose tile configuration has no unrolled body (more than 6 row tiles, or — with many covariates — more than
-  // one extra column tile) go to the panelled kernel; they come first
-  // order: general-path genes first (panelled ones in front), then the hard-call genes; widest first inside each
-  auto needs_panel = [&](const GeneDesc& g) { return !g.hc && (g.MT > kMaxMT || g.CT > g.MT + 1); };
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-    if (desc[a].hc != desc[b].hc) return desc[a].hc < desc[b].hc;
-    const bool pa = needs_panel(desc[a]), pb = needs_panel(desc[b]);
-    if (pa != pb) return pa;
-    return desc[a].M > desc[b].M;
+  const std::vector<GeneDesc>& desc = b.desc;
+  std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+    if (desc[x].hc != desc[y].hc) return desc[x].hc < desc[y].hc;
+    const bool px = needs_panel(desc[x]), py = needs_panel(desc[y]);
+    if (px != py) return px;
+    return desc[x].M > desc[y].M;
   });
-  const int n_gen = n - n_hc;  // descriptors [0, n_gen) take the general kernels, [n_gen, n) the hard-call kernels
+  GeneDesc* h_desc = b.h_desc;
   for (int k = 0; k < n; ++k) h_desc[k] = desc[order[k]];
   {  // order of the p-value workgroups: workgroup b takes h_desc[h_desc[b].pv_gene] — indices into the SORTED array, by
      // falling M (stable): the longest work first
     std::vector<int>& ord = c->pv_order;
     ord.resize(n);
     for (int k = 0; k < n; ++k) ord[k] = k;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return h_desc[a].M > h_desc[b].M; });
-    for (int b = 0; b < n; ++b) h_desc[b].pv_gene = ord[b];
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return h_desc[x].M > h_desc[y].M; });
+    for (int k = 0; k < n; ++k) h_desc[k].pv_gene = ord[k];
   }
-  GeneDesc* d_desc = reinterpret_cast<GeneDesc*>(base + off_desc);
-  HIP_TRY(c, hipMemcpyAsync(d_desc, h_desc, sizeof(GeneDesc) * n, hipMemcpyHostToDevice, st));
-  NullDev nd{c->d_X, c->d_res, c->d_rr, c->d_v, c->d_zeros};
-  // ---- K2: one launch for the whole batch ------------------------------------------------------------------
-  // Stage 1 (bandwidth / MFMA bound) runs on the shared K2 stream so that two batches never split the chip
-  // between two sufficient-statistics launches; stage 2 (latency bound, few waves) continues on the slot's
-  // stream and overlaps the NEXT batch's stage 1.
-  bt.mark(3);
-  const int slot_idx = (int)(slp - &c->slots[0]);
-  HIP_TRY(c, hipEventRecord(c->ev_in[slot_idx], st));
-  HIP_TRY(c, hipStreamWaitEvent(c->k2_stream, c->ev_in[slot_idx], 0));
-  // general-path genes of a mixed batch (a few genes with imputed values among hard-call ones) go to the second
-  // sufficient-statistics stream and run beside the hard-call launches
-  // (not beside the float-digit kernel: its whole-CU workgroups find no free CU while one-wave workgroups flood the chip)
-  const bool split = n_gen > 0 && n_hc > 0 && !fdx_batch;
-  hipStream_t gst = split ? c->k2b_stream : c->k2_stream;
-  if (split) HIP_TRY(c, hipStreamWaitEvent(gst, c->ev_in[slot_idx], 0));
+  b.d_desc = reinterpret_cast<GeneDesc*>(base + bo.desc);
+  HIP_TRY(c, hipMemcpyAsync(b.d_desc, h_desc, sizeof(GeneDesc) * n, hipMemcpyHostToDevice, b.st));
+  b.nd = NullDev{c->d_X, c->d_res, c->d_rr, c->d_v, c->d_zeros};
+  b.bt.mark(3);
+  return RVT_OK;
+}
+
+// descriptors [0, n_gen) on stream gst: the panelled kernel, then one launch per register-budget group
+static void launch_general_genes(rvt_ctx* c, const Batch& b, hipStream_t gst) {
+  const NullConsts& nc = c->nc;
+  const GeneDesc* h_desc = b.h_desc;
   int k0 = 0;
-  while (k0 < n_gen && needs_panel(h_desc[k0])) ++k0;  // these need the panelled kernel
+  while (k0 < b.n_gen && needs_panel(h_desc[k0])) ++k0;  // these need the panelled kernel
   if (k0 > 0) {
     Scope sc(c, 0, gst);
     const int nPR = (h_desc[0].MT + 3) / 4, nPC = (h_desc[0].CT + 3) / 4;
     int npanels = 0;
     for (int pr = 0; pr < nPR; ++pr) npanels += nPC - pr;
-    dim3 grid(n_wparts, k0, npanels), block(64);
+    dim3 grid(b.n_wparts, k0, npanels), block(64);
     if (nc.binary)
-      k2_launch_panel_w1(grid, gst, d_desc, nd, (long long)N, (long long)ld, d);
+      k2_launch_panel_w1(grid, gst, b.d_desc, b.nd, (long long)nc.N, (long long)nc.ld, nc.d);
     else
-      k2_launch_panel_w0(grid, gst, d_desc, nd, (long long)N, (long long)ld, d);
+      k2_launch_panel_w0(grid, gst, b.d_desc, b.nd, (long long)nc.N, (long long)nc.ld, nc.d);
   }
-  for (int k = k0; k < n_gen;) {  // descriptors are sorted by width, so every register-budget group is one contiguous run
+  for (int k = k0; k < b.n_gen;) {  // descriptors are sorted by width, so every register-budget group is one contiguous run
     const int grp = suffstat_group(h_desc[k].MT, h_desc[k].CT, nc.binary != 0);
     int e = k;
-    while (e < n_gen && suffstat_group(h_desc[e].MT, h_desc[e].CT, nc.binary != 0) == grp) ++e;
-    launch_suffstat(c, gst, grp, d_desc + k, e - k, n_wparts, nd);
+    while (e < b.n_gen && suffstat_group(h_desc[e].MT, h_desc[e].CT, nc.binary != 0) == grp) ++e;
+    launch_suffstat(c, gst, grp, b.d_desc + k, e - k, b.n_wparts, b.nd);
     k = e;
   }
-  if (pqw_bytes) HIP_TRY(c, hipMemsetAsync(base + off_pqw, 0, pqw_bytes, c->k2_stream));
-  for (int k = n_gen; k < n;) {  // hard-call genes: one launch per tile class (contiguous runs, widest class first)
+}
+
+// descriptors [n_gen, n) on the shared streaming stream: one launch per path and tile class (contiguous runs, widest class
+// first)
+static int launch_integer_genes(rvt_ctx* c, const Batch& b) {
+  const NullConsts& nc = c->nc;
+  const long long N = nc.N, ld = nc.ld;
+  const int d = nc.d, n = b.n;
+  const GeneDesc *h_desc = b.h_desc, *d_desc = b.d_desc;
+  const bool hcx = b.caps.hcx;
+  static const int planes_sw = getenv("RVT_HCP_PLANES") ? atoi(getenv("RVT_HCP_PLANES")) : 1;  // 0 never, 2 every packed gene
+  for (int k = b.n_gen; k < n;) {
     int e = k;
+    const int path = h_desc[k].hc, MT = h_desc[k].MT;
     // (gene_suffstat_hcx_any / gene_suffstat_fdx_any: every class at once)
-    const bool one_launch = (hcx && c->hcx_fused && h_desc[k].hc == 1) || (h_desc[k].hc == 4 && c->hcx_fused);
-    while (e < n && (one_launch || h_desc[e].MT == h_desc[k].MT) && h_desc[e].hc == h_desc[k].hc &&
-           h_desc[e].hcp_planes == h_desc[k].hcp_planes)
+    const bool one_launch = c->hcx_fused && ((hcx && path == kPathHardCall) || path == kPathFloatDigit);
+    while (e < n && (one_launch || h_desc[e].MT == MT) && h_desc[e].hc == path && h_desc[e].hcp_planes == h_desc[k].hcp_planes)
       ++e;
     hipStream_t hst = c->k2_stream;
     Scope sc(c, 4, hst);
-    if (h_desc[k].hc == 3) {
+    const dim3 grid(b.n_wparts, e - k);
+    const NullTile tile{c->d_nulltile, d + 2};
+    if (path == kPathPacked) {
       // (resident genes: G'[X | rr] from the digit planes of THIS null tile — rvt_set_null drops them with the model; a wave-part
       //  beyond the int32 range of a pair sum, or a model whose columns the planes cannot carry, keeps the fp64 product)
-      static const int planes_sw = getenv("RVT_HCP_PLANES") ? atoi(getenv("RVT_HCP_PLANES")) : 1;  // 0 never, 2 every packed gene
-      bool planes = nd_is_default && (h_desc[k].hcp_planes || planes_sw == 2) && planes_sw != 0 &&
+      bool planes = b.caps.nd_is_default && (h_desc[k].hcp_planes || planes_sw == 2) && planes_sw != 0 &&
                     (long long)h_desc[k].steps_per_wpart * 16 <= kHcpPlaneMaxSamples;
       if (planes) {
         const int rcp = ensure_hcp_planes(c);
@@ -1469,26 +1540,42 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
         planes = c->hcp_planes_state == 1;
       }
       const HcpPlanes pl{c->d_hcp_xq, c->d_hcp_scale, d + 1};
-      k2_launch_hcp(h_desc[k].MT, dim3(n_wparts, e - k), hst, d_desc + k, NullTile{c->d_nulltile, d + 2}, (long long)N,
-                    (long long)ld, d, planes ? &pl : nullptr,
-                    planes && cov && cov->score && h_desc[k].MT <= 2 && !getenv("RVT_SCORE_BED_FULL"));
-    }
-    else if (h_desc[k].hc == 4)
-      k2_launch_fdx(one_launch ? 0 : h_desc[k].MT, dim3(n_wparts, e - k), hst, d_desc + k, c->fdx_tile, (long long)N, (long long)ld, d);
-    else if (h_desc[k].hc == 2)
-      k2_launch_lat(h_desc[k].MT, dim3(n_wparts, e - k), hst, d_desc + k, NullTile{c->d_nulltile, d + 2},
-                    (double)c->lattice_den, (long long)N, (long long)ld, d);
+      k2_launch_hcp(MT, grid, hst, d_desc + k, tile, N, ld, d, planes ? &pl : nullptr,
+                    planes && b.cov && b.cov->score && MT <= 2 && !getenv("RVT_SCORE_BED_FULL"));
+    } else if (path == kPathFloatDigit)
+      k2_launch_fdx(one_launch ? 0 : MT, grid, hst, d_desc + k, c->fdx_tile, N, ld, d);
+    else if (path == kPathLattice)
+      k2_launch_lat(MT, grid, hst, d_desc + k, tile, (double)c->lattice_den, N, ld, d);
     else if (hcx)
-      k2_launch_hcx(one_launch ? 0 : h_desc[k].MT, dim3(n_wparts, e - k), hst, d_desc + k, c->hcx_tile, (long long)N,
-                    (long long)ld, d);
-    else if (hcw)
-      k2_launch_hcw(h_desc[k].MT, dim3(n_wparts, e - k), hst, d_desc + k, NullTileW{c->d_nulltile_w, d + 3, c->d_vq},
-                    (long long)N, (long long)ld, d);
+      k2_launch_hcx(one_launch ? 0 : MT, grid, hst, d_desc + k, c->hcx_tile, N, ld, d);
+    else if (b.caps.hcw)
+      k2_launch_hcw(MT, grid, hst, d_desc + k, NullTileW{c->d_nulltile_w, d + 3, c->d_vq}, N, ld, d);
     else
-      k2_launch_hc(h_desc[k].MT, dim3(n_wparts, e - k), hst, d_desc + k, NullTile{c->d_nulltile, d + 2}, (long long)N,
-                   (long long)ld, d);
+      k2_launch_hc(MT, grid, hst, d_desc + k, tile, N, ld, d);
     k = e;
   }
+  return RVT_OK;
+}
+
+// ---- K2: the sufficient statistics of the whole batch ------------------------------------------------------
+// Stage 1 (bandwidth / MFMA bound) runs on the shared K2 stream so that two batches never split the chip
+// between two sufficient-statistics launches; stage 2 (latency bound, few waves) continues on the slot's
+// stream and overlaps the NEXT batch's stage 1.
+static int launch_suffstats(rvt_ctx* c, Batch& b) {
+  const int n = b.n, n_gen = b.n_gen, n_hc = b.n_hc, slot_idx = b.slot_idx;
+  hipStream_t st = b.st;
+  HIP_TRY(c, hipEventRecord(c->ev_in[slot_idx], st));
+  HIP_TRY(c, hipStreamWaitEvent(c->k2_stream, c->ev_in[slot_idx], 0));
+  // general-path genes of a mixed batch (a few genes with imputed values among hard-call ones) go to the second
+  // sufficient-statistics stream and run beside the hard-call launches
+  // (not beside the float-digit kernel: its whole-CU workgroups find no free CU while one-wave workgroups flood the chip)
+  const bool split = n_gen > 0 && n_hc > 0 && !b.fdx_batch;
+  hipStream_t gst = split ? c->k2b_stream : c->k2_stream;
+  if (split) HIP_TRY(c, hipStreamWaitEvent(gst, c->ev_in[slot_idx], 0));
+  launch_general_genes(c, b, gst);
+  if (b.off.pqw_bytes) HIP_TRY(c, hipMemsetAsync(b.base + b.off.pqw, 0, b.off.pqw_bytes, c->k2_stream));
+  int rc = launch_integer_genes(c, b);
+  if (rc) return rc;
   if (split) {
     HIP_TRY(c, hipEventRecord(c->ev_k2b[slot_idx], gst));
     HIP_TRY(c, hipStreamWaitEvent(st, c->ev_k2b[slot_idx], 0));
@@ -1501,144 +1588,151 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
     // back are computed by the general kernel right here, on the batch's own stream (the shared streaming stream goes
     // straight on to the next batch) — one launch per register-budget group over the device work list the flags kernel
     // writes; its workgroups leave at once when the list is empty.
-    int* d_lists = reinterpret_cast<int*>(base + off_lists);
+    int* d_lists = reinterpret_cast<int*>(b.base + b.off.lists);
     HIP_TRY(c, hipMemsetAsync(d_lists, 0, 4 * sizeof(int), st));
-    hipLaunchKernelGGL(gene_flags_hc_kernel, dim3(n_hc), dim3(64), 0, st, d_desc + n_gen, (long long)N, d_lists,
-                       n_hc);
+    hipLaunchKernelGGL(gene_flags_hc_kernel, dim3(n_hc), dim3(64), 0, st, b.d_desc + n_gen, (long long)c->nc.N, d_lists, n_hc);
     bool grp_present[3] = {false, false, false};
-    for (int k = n_gen; k < n; ++k) grp_present[suffstat_group(h_desc[k].MT, h_desc[k].CT, nc.binary != 0)] = true;
+    for (int k = n_gen; k < n; ++k) grp_present[suffstat_group(b.h_desc[k].MT, b.h_desc[k].CT, c->nc.binary != 0)] = true;
     for (int grp = 0; grp < 3; ++grp)
-      if (grp_present[grp]) launch_suffstat(c, st, grp, d_desc + n_gen, n_hc, n_wparts, nd, d_lists);
+      if (grp_present[grp]) launch_suffstat(c, st, grp, b.d_desc + n_gen, n_hc, b.n_wparts, b.nd, d_lists);
   }
-  bt.mark(4);
-  if (cov && cov->score) {  // MetaScore: per-variant statistics of every slice, returned synchronously
-    size_t vt = 0;
-    for (int g = 0; g < n; ++g) vt += (size_t)Ms[g];
-    double* d_bur = reinterpret_cast<double*>(base + off_cov_bur);
-    int* d_ok = reinterpret_cast<int*>(base + off_cov_ok);
-    if (cov->wald) {  // rvt_wald_block, quantitative trait: the linear fits of the same columns
-      WaldConsts wc;
-      for (int k = 0; k < RVT_MAX_COV; ++k) wc.beta0[k] = cov->wald_beta0[k];
-      hipLaunchKernelGGL(wald_linear_finish_kernel, dim3((unsigned)n), dim3(64), 0, st, d_desc, c->d_nc, wc, (int)vt, d_bur,
-                         d_ok);
-      HIP_TRY(c, hipGetLastError());
-      const size_t vd8 = sizeof(double) * vt * (size_t)d;
-      HIP_TRY(c, hipMemcpyAsync(cov->wbeta, d_bur, vd8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(cov->wse, d_bur + vt * (size_t)d, vd8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(cov->wpval, d_bur + 2 * vt * (size_t)d, vd8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(cov->ok, d_ok, sizeof(int) * vt, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, sync_stream(st));
-      return RVT_OK;
-    }
-    hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)n), dim3(64), 0, st, d_desc, c->d_nc, (int)vt, d_bur, d_ok);
-    HIP_TRY(c, hipGetLastError());
-    const size_t vb8 = sizeof(double) * vt;
-    HIP_TRY(c, hipMemcpyAsync(cov->ustat, d_bur, vb8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(cov->vstat, d_bur + vt, vb8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(cov->effect, d_bur + 2 * vt, vb8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(cov->se, d_bur + 3 * vt, vb8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(cov->pval, d_bur + 4 * vt, vb8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(cov->ok, d_ok, sizeof(int) * vt, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, sync_stream(st));
-    return RVT_OK;
+  b.bt.mark(4);
+  return RVT_OK;
+}
+
+// MetaScore (and, with cov->wald, rvt_wald_block's linear fits of the same columns): per-variant statistics of every slice,
+// returned synchronously
+static int score_tail(rvt_ctx* c, Batch& b) {
+  const CovOut* cov = b.cov;
+  hipStream_t st = b.st;
+  const size_t vt = b.af_total;  // the columns of all slices
+  double* d_bur = reinterpret_cast<double*>(b.base + b.off.cov_bur);
+  int* d_ok = reinterpret_cast<int*>(b.base + b.off.cov_ok);
+  if (cov->wald) {  // quantitative trait
+    WaldConsts wc;
+    for (int k = 0; k < RVT_MAX_COV; ++k) wc.beta0[k] = cov->wald_beta0[k];
+    hipLaunchKernelGGL(wald_linear_finish_kernel, dim3((unsigned)b.n), dim3(64), 0, st, b.d_desc, c->d_nc, wc, (int)vt, d_bur,
+                       d_ok);
+  } else {
+    hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)b.n), dim3(64), 0, st, b.d_desc, c->d_nc, (int)vt, d_bur, d_ok);
   }
-  if (cov) {  // MetaCov: finish the covariance algebra of this one block and return its band synchronously
-    const int V = Ms[0];
-    CovConsts cc;
-    std::vector<double> zz;
+  HIP_TRY(c, hipGetLastError());
+  // d_bur: the records' fields one after the other, `per` doubles each
+  double* const wald_out[] = {cov->wbeta, cov->wse, cov->wpval};
+  double* const score_out[] = {cov->ustat, cov->vstat, cov->effect, cov->se, cov->pval};
+  double* const* outs = cov->wald ? wald_out : score_out;
+  const int n_out = cov->wald ? 3 : 5;
+  const size_t per = cov->wald ? vt * (size_t)c->nc.d : vt;
+  for (int k = 0; k < n_out; ++k)
+    HIP_TRY(c, hipMemcpyAsync(outs[k], d_bur + k * per, sizeof(double) * per, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(cov->ok, d_ok, sizeof(int) * vt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  return RVT_OK;
+}
+
+// MetaCov: finish the covariance algebra of this one block and return its band synchronously
+static int cov_tail(rvt_ctx* c, Batch& b) {
+  const CovOut* cov = b.cov;
+  hipStream_t st = b.st;
+  char* base = b.base;
+  const int V = b.Ms[0];
+  CovConsts cc;
+  std::vector<double> zz;
+  {
+    int rcc = cov_constants(c, cov->fam, &cc, &zz);
+    if (rcc) return rcc;
+    if (cov->fam && cov->uncentred) cc.inv_n = 0.0;  // every centring term carries the column mean s / N
+  }
+  double* d_xz = reinterpret_cast<double*>(base + b.off.cov_xz);
+  double* d_cs = reinterpret_cast<double*>(base + b.off.cov_cs);
+  int* d_poly = reinterpret_cast<int*>(base + b.off.cov_poly);
+  double* d_cov = reinterpret_cast<double*>(base + b.off.cov);
+  if (cov->fam) {
+    HIP_TRY(c, hipMemcpyAsync(d_cs, cov->d_raw_colsum, sizeof(double) * (size_t)V, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_poly, cov->d_raw_poly, sizeof(int) * (size_t)V, hipMemcpyDeviceToDevice, st));
+  }
+  double* d_bur = reinterpret_cast<double*>(base + b.off.cov_bur);  // ustat | vstat | af | pval
+  const bool bur = cov->fam && cov->ustat;
+  hipLaunchKernelGGL(cov_prepare_kernel, dim3(1), dim3(256), 0, st, b.d_desc, cc, d_xz, d_cs, d_poly,
+                     bur ? d_bur : (double*)nullptr, bur ? d_bur + 2 * (size_t)V : (double*)nullptr);
+  hipLaunchKernelGGL(cov_rows_kernel, dim3(V), dim3(256), 0, st, b.d_desc, cc, d_xz, d_cs, d_cov);
+  if (bur)
+    hipLaunchKernelGGL(fam_burden_finish_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_cov, V, d_bur,
+                       d_bur + (size_t)V, d_bur + 3 * (size_t)V);
+  HIP_TRY(c, hipGetLastError());
+  const int dz = cc.d;
+  if (cov->cov) HIP_TRY(c, hipMemcpyAsync(cov->cov, d_cov, sizeof(double) * (size_t)V * V, hipMemcpyDeviceToHost, st));
+  if (cov->xz) HIP_TRY(c, hipMemcpyAsync(cov->xz, d_xz, sizeof(double) * (size_t)V * dz, hipMemcpyDeviceToHost, st));
+  if (cov->poly) HIP_TRY(c, hipMemcpyAsync(cov->poly, d_poly, sizeof(int) * (size_t)V, hipMemcpyDeviceToHost, st));
+  if (bur) {
+    double* const outs[] = {cov->ustat, cov->vstat, cov->af, cov->pval};
+    for (int k = 0; k < 4; ++k)
+      HIP_TRY(c, hipMemcpyAsync(outs[k], d_bur + k * (size_t)V, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, sync_stream(st));
+  if (cov->zz) std::memcpy(cov->zz, zz.data(), sizeof(double) * (size_t)dz * dz);
+  return RVT_OK;
+}
+
+// the burden collapse (CMC / Zeggini, debug runs)
+// on the batch's own stream: the collapse overlaps the next batch's sufficient-statistics launches, which
+// leave about half of the HBM bandwidth unused
+static void launch_burden(rvt_ctx* c, const Batch& b) {
+  const NullConsts& nc = c->nc;
+  const long long N = nc.N, ld = nc.ld;
+  const int d = nc.d, n_gen = b.n_gen, n_hc = b.n_hc;
+  hipStream_t bs = b.st;
+  GeneDesc* d_desc = b.d_desc;
+  if (n_gen > 0) {
     {
-      int rcc = cov_constants(c, cov->fam, &cc, &zz);
-      if (rcc) return rcc;
-      if (cov->fam && cov->uncentred) cc.inv_n = 0.0;  // every centring term carries the column mean s / N
-    }
-    double* d_xz = reinterpret_cast<double*>(base + off_cov_xz);
-    double* d_cs = reinterpret_cast<double*>(base + off_cov_cs);
-    int* d_poly = reinterpret_cast<int*>(base + off_cov_poly);
-    double* d_cov = reinterpret_cast<double*>(base + off_cov);
-    if (cov->fam) {
-      HIP_TRY(c, hipMemcpyAsync(d_cs, cov->d_raw_colsum, sizeof(double) * (size_t)V, hipMemcpyDeviceToDevice, st));
-      HIP_TRY(c, hipMemcpyAsync(d_poly, cov->d_raw_poly, sizeof(int) * (size_t)V, hipMemcpyDeviceToDevice, st));
-    }
-    double* d_bur = reinterpret_cast<double*>(base + off_cov_bur);  // ustat | vstat | af | pval
-    const bool bur = cov->fam && cov->ustat;
-    hipLaunchKernelGGL(cov_prepare_kernel, dim3(1), dim3(256), 0, st, d_desc, cc, d_xz, d_cs, d_poly,
-                       bur ? d_bur : (double*)nullptr, bur ? d_bur + 2 * (size_t)V : (double*)nullptr);
-    hipLaunchKernelGGL(cov_rows_kernel, dim3(V), dim3(256), 0, st, d_desc, cc, d_xz, d_cs, d_cov);
-    if (bur)
-      hipLaunchKernelGGL(fam_burden_finish_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_cov, V, d_bur,
-                         d_bur + (size_t)V, d_bur + 3 * (size_t)V);
-    HIP_TRY(c, hipGetLastError());
-    const int dz = cc.d;
-    if (cov->cov)
-      HIP_TRY(c, hipMemcpyAsync(cov->cov, d_cov, sizeof(double) * (size_t)V * V, hipMemcpyDeviceToHost, st));
-    if (cov->xz)
-      HIP_TRY(c, hipMemcpyAsync(cov->xz, d_xz, sizeof(double) * (size_t)V * dz, hipMemcpyDeviceToHost, st));
-    if (cov->poly)
-      HIP_TRY(c, hipMemcpyAsync(cov->poly, d_poly, sizeof(int) * (size_t)V, hipMemcpyDeviceToHost, st));
-    if (bur) {
-      const size_t vb8 = sizeof(double) * (size_t)V;
-      HIP_TRY(c, hipMemcpyAsync(cov->ustat, d_bur, vb8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(cov->vstat, d_bur + (size_t)V, vb8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(cov->af, d_bur + 2 * (size_t)V, vb8, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(cov->pval, d_bur + 3 * (size_t)V, vb8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(c, sync_stream(st));
-    if (cov->zz) std::memcpy(cov->zz, zz.data(), sizeof(double) * (size_t)dz * dz);
-    return RVT_OK;
-  }
-  const bool burden = (tests & (RVT_TEST_CMC | RVT_TEST_ZEGGINI)) != 0;
-  if (burden || dbg) {
-    // on the batch's own stream: the collapse overlaps the next batch's sufficient-statistics launches, which
-    // leave about half of the HBM bandwidth unused
-    hipStream_t bs = st;
-    if (n_gen > 0) {
-      {
-        Scope sc(c, 1, bs);
-        hipLaunchKernelGGL(gene_flags_kernel, dim3(n_gen), dim3(64), 0, bs, d_desc, (long long)N);
-      }
-      // gene groups of <= 64 keep one workgroup's loop short while X/res/v stay in registers; all groups in one launch
-      const int gpg = 64, ngroups = (n_gen + gpg - 1) / gpg;
       Scope sc(c, 1, bs);
-      if (d <= 4)
-        hipLaunchKernelGGL((burden_collapse_kernel<4>), dim3(n_bparts, ngroups), dim3(256), 0, bs, d_desc, n_gen, gpg,
-                           nd, (long long)N, (long long)ld, d, nc.binary, tests);
-      else
-        hipLaunchKernelGGL((burden_collapse_kernel<RVT_MAX_COV>), dim3(n_bparts, ngroups), dim3(256), 0, bs, d_desc,
-                           n_gen, gpg, nd, (long long)N, (long long)ld, d, nc.binary, tests);
+      hipLaunchKernelGGL(gene_flags_kernel, dim3(n_gen), dim3(64), 0, bs, d_desc, N);
     }
-    if (n_hc > 0) {
-      // hard-call genes carry their burden sums already; where gene_flags_hc_kernel found the in-pass collapse wrong
-      // (flip prediction, a counted monomorphic column, an imputed value that counts) or handed the gene back, the sums
-      // are redone from the block (a handed-back gene first gets its flags from the general kernel's statistics)
-      Scope sc(c, 1, bs);
-      const int* d_lists = reinterpret_cast<const int*>(base + off_lists);
-      hipLaunchKernelGGL(gene_flags_kernel, dim3(n_hc), dim3(64), 0, bs, d_desc + n_gen, (long long)N);
-      if (d <= 4)
-        hipLaunchKernelGGL((burden_fallback_kernel<4>), dim3(kFallbackGrid), dim3(256), 0, bs, d_desc + n_gen, d_lists,
-                           n_hc, n_wparts, nd, (long long)N, (long long)ld, d, nc.binary);
-      else
-        hipLaunchKernelGGL((burden_fallback_kernel<kHcMaxD>), dim3(kFallbackGrid), dim3(256), 0, bs, d_desc + n_gen,
-                           d_lists, n_hc, n_wparts, nd, (long long)N, (long long)ld, d, nc.binary);
-    }
+    // gene groups of <= 64 keep one workgroup's loop short while X/res/v stay in registers; all groups in one launch
+    const int gpg = 64, ngroups = (n_gen + gpg - 1) / gpg;
+    Scope sc(c, 1, bs);
+    if (d <= 4)
+      hipLaunchKernelGGL((burden_collapse_kernel<4>), dim3(b.n_bparts, ngroups), dim3(256), 0, bs, d_desc, n_gen, gpg, b.nd, N,
+                         ld, d, nc.binary, b.tests);
+    else
+      hipLaunchKernelGGL((burden_collapse_kernel<RVT_MAX_COV>), dim3(b.n_bparts, ngroups), dim3(256), 0, bs, d_desc, n_gen,
+                         gpg, b.nd, N, ld, d, nc.binary, b.tests);
   }
-  const unsigned tests_eff = burden ? tests : (tests & ~(RVT_TEST_CMC | RVT_TEST_ZEGGINI));
+  if (n_hc > 0) {
+    // hard-call genes carry their burden sums already; where gene_flags_hc_kernel found the in-pass collapse wrong
+    // (flip prediction, a counted monomorphic column, an imputed value that counts) or handed the gene back, the sums
+    // are redone from the block (a handed-back gene first gets its flags from the general kernel's statistics)
+    Scope sc(c, 1, bs);
+    const int* d_lists = reinterpret_cast<const int*>(b.base + b.off.lists);
+    hipLaunchKernelGGL(gene_flags_kernel, dim3(n_hc), dim3(64), 0, bs, d_desc + n_gen, N);
+    if (d <= 4)
+      hipLaunchKernelGGL((burden_fallback_kernel<4>), dim3(kFallbackGrid), dim3(256), 0, bs, d_desc + n_gen, d_lists, n_hc,
+                         b.n_wparts, b.nd, N, ld, d, nc.binary);
+    else
+      hipLaunchKernelGGL((burden_fallback_kernel<kHcMaxD>), dim3(kFallbackGrid), dim3(256), 0, bs, d_desc + n_gen, d_lists,
+                         n_hc, b.n_wparts, b.nd, N, ld, d, nc.binary);
+  }
+}
+
+// the genes' statistics from the wave-part images: the assembly, and the variable-threshold test behind it
+static void launch_assembly(rvt_ctx* c, const Batch& b, unsigned tests_eff) {
+  const int n = b.n, d = c->nc.d;
+  hipStream_t st = b.st;
+  GeneDesc* d_desc = b.d_desc;
   {
     Scope sc(c, 2, st);
-    if (tests & RVT_TEST_FAMSKAT)
+    if (b.tests & RVT_TEST_FAMSKAT)
       hipLaunchKernelGGL(fam_assemble_kernel, dim3(n), dim3(1024), 0, st, d_desc, c->d_nc);
     else {
-      // the sum of the wave-part images on a grid of its own (RVT_AS_REDUCE=0: inside the assembly kernel, as until round 5)
-      static const bool reduce_apart = !(getenv("RVT_AS_REDUCE") && atoi(getenv("RVT_AS_REDUCE")) == 0);
-      if (reduce_apart) {
-        const int maxMpA = (maxM + 15) / 16 * 16, maxCpA = (maxM + d + 1 + 15) / 16 * 16;
-        hipLaunchKernelGGL(gene_reduce_parts_kernel, dim3((unsigned)((maxMpA * maxCpA + kReducePiece - 1) / kReducePiece), (unsigned)n),
-                           dim3(256), 0, st, d_desc);
-      }
-      hipLaunchKernelGGL(gene_assemble_kernel, dim3(n), dim3(c->as_threads), 0, st, d_desc, c->d_nc, params, tests_eff,
-                         n_bparts, (const double*)c->d_xscale, reduce_apart ? 1 : 0);
+      // the sum of the wave-part images on a grid of its own
+      const int maxMpA = (b.maxM + 15) / 16 * 16, maxCpA = (b.maxM + d + 1 + 15) / 16 * 16;
+      hipLaunchKernelGGL(gene_reduce_parts_kernel, dim3((unsigned)((maxMpA * maxCpA + kReducePiece - 1) / kReducePiece), (unsigned)n),
+                         dim3(256), 0, st, d_desc);
+      hipLaunchKernelGGL(gene_assemble_kernel, dim3(n), dim3(c->as_threads), 0, st, d_desc, c->d_nc, b.params, tests_eff,
+                         b.n_bparts, (const double*)c->d_xscale);
     }
   }
-  if ((tests & RVT_TEST_ANALYTICVT) && !(tests & RVT_TEST_FAMSKAT)) {
+  if ((b.tests & RVT_TEST_ANALYTICVT) && !(b.tests & RVT_TEST_FAMSKAT)) {
     Scope sc(c, 2, st);
     hipLaunchKernelGGL(gene_vt_kernel, dim3(n), dim3(256), 0, st, d_desc, c->d_nc);
     for (int stage = 0; stage < 2; ++stage) {  // the band probability: a short first stage, a long one where it is needed
@@ -1646,85 +1740,138 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
       hipLaunchKernelGGL(vt_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_desc, n, stage);
     }
   }
-  const unsigned tests_eig = (tests & RVT_TEST_FAMSKAT) ? (unsigned)RVT_TEST_SKAT : tests_eff;
-  if (tests & (RVT_TEST_SKAT | RVT_TEST_SKATO | RVT_TEST_FAMSKAT)) {
-    const int maxMp = (maxM + 15) / 16 * 16;
-    {
-      Scope sc(c, 2, st);
-      size_t want = sizeof(double) * ((size_t)4 * maxMp + (size_t)maxM * maxM);
-      if (want > c->eigen_lds_max) want = sizeof(double) * (size_t)4 * maxMp;  // matrices stay in global scratch
-      hipLaunchKernelGGL(gene_tridiag_kernel, dim3(kNTridiag, n), dim3(256), want, st, d_desc, c->d_nc, tests_eig,
-                         (int)(want / sizeof(double)));
-    }
-    {
-      Scope sc(c, 2, st);
-      // (one workgroup per gene over all 13 problems; RVT_SPECTRUM_PER_PROBLEM=1 or a gene too wide for the LDS: a workgroup
-      //  per problem, as until round 4)
-      static const bool per_problem = getenv("RVT_SPECTRUM_PER_PROBLEM") != nullptr;
-      const size_t lds_all = sizeof(double) * ((size_t)39 * maxMp + 64);
-      if (per_problem || lds_all > ((size_t)60 << 10))
-        hipLaunchKernelGGL(gene_spectrum_kernel, dim3(kNEigen, n), dim3(128), sizeof(double) * (size_t)4 * maxMp, st,
-                           d_desc, c->d_nc, tests_eig);
-      else
-        hipLaunchKernelGGL(gene_spectrum_all_kernel, dim3(n), dim3(128), lds_all, st, d_desc, c->d_nc, tests_eig);
-    }
+}
+
+// the spectra of the SKAT family's matrices
+static void launch_eigen(rvt_ctx* c, const Batch& b, unsigned tests_eig) {
+  const int n = b.n, maxM = b.maxM, maxMp = (maxM + 15) / 16 * 16;
+  hipStream_t st = b.st;
+  GeneDesc* d_desc = b.d_desc;
+  {
+    Scope sc(c, 2, st);
+    size_t want = sizeof(double) * ((size_t)4 * maxMp + (size_t)maxM * maxM);
+    if (want > c->eigen_lds_max) want = sizeof(double) * (size_t)4 * maxMp;  // matrices stay in global scratch
+    hipLaunchKernelGGL(gene_tridiag_kernel, dim3(kNTridiag, n), dim3(256), want, st, d_desc, c->d_nc, tests_eig,
+                       (int)(want / sizeof(double)));
   }
   {
-    // (on CUs of its own when RVT_PV_CUS is in force and the batch is big enough to matter: see rvt_init)
-    const bool pv_apart = c->pv_cus > 0 && n >= 64 && (tests & RVT_TEST_SKATO);
-    hipStream_t pst = st;
-    if (pv_apart) {
-      pst = c->pv_stream[c->pv_turn++ & 1];
-      HIP_TRY(c, hipEventRecord(c->ev_pv_in[slot_idx], st));
-      HIP_TRY(c, hipStreamWaitEvent(pst, c->ev_pv_in[slot_idx], 0));
-    }
-    {
-      Scope sc(c, 3, pst);
-      // (four coefficient arrays of an even length, the 42 integrand values, the staging of wave_davies_pvalue)
-      const size_t smem = sizeof(double) * 4 * ((maxM + 1) & ~1) + sizeof(double) * 42 +
-                          sizeof(double) * (3 * 64 + 2 * kTermCap) + sizeof(int) * (64 + 64 + 66) + 32;
-      if (tests & RVT_TEST_EXACT_DAVIES)  // Davies' coefficient sums term by term (verification) / in product form
-        hipLaunchKernelGGL((gene_pvalue_kernel<false>), dim3(n), dim3(64), smem, pst, d_desc, tests);
-      else
-        hipLaunchKernelGGL((gene_pvalue_kernel<true>), dim3(n), dim3(64), smem, pst, d_desc, tests);
-    }
-    if (pv_apart) {
-      HIP_TRY(c, hipEventRecord(c->ev_pv_out[slot_idx], pst));
-      HIP_TRY(c, hipStreamWaitEvent(st, c->ev_pv_out[slot_idx], 0));
-    }
+    Scope sc(c, 2, st);
+    // (one workgroup per gene over all 13 problems; RVT_SPECTRUM_PER_PROBLEM=1 or a gene too wide for the LDS: a workgroup
+    //  per problem, as until round 4)
+    static const bool per_problem = getenv("RVT_SPECTRUM_PER_PROBLEM") != nullptr;
+    const size_t lds_all = sizeof(double) * ((size_t)39 * maxMp + 64);
+    if (per_problem || lds_all > ((size_t)60 << 10))
+      hipLaunchKernelGGL(gene_spectrum_kernel, dim3(kNEigen, n), dim3(128), sizeof(double) * (size_t)4 * maxMp, st, d_desc,
+                         c->d_nc, tests_eig);
+    else
+      hipLaunchKernelGGL(gene_spectrum_all_kernel, dim3(n), dim3(128), lds_all, st, d_desc, c->d_nc, tests_eig);
   }
+}
+
+// the p-values
+// (on CUs of its own when RVT_PV_CUS is in force and the batch is big enough to matter: see rvt_init)
+static int launch_pvalue(rvt_ctx* c, const Batch& b) {
+  const int n = b.n, slot_idx = b.slot_idx;
+  hipStream_t st = b.st;
+  const bool pv_apart = c->pv_cus > 0 && n >= 64 && (b.tests & RVT_TEST_SKATO);
+  hipStream_t pst = st;
+  if (pv_apart) {
+    pst = c->pv_stream[c->pv_turn++ & 1];
+    HIP_TRY(c, hipEventRecord(c->ev_pv_in[slot_idx], st));
+    HIP_TRY(c, hipStreamWaitEvent(pst, c->ev_pv_in[slot_idx], 0));
+  }
+  {
+    Scope sc(c, 3, pst);
+    // (four coefficient arrays of an even length, the 42 integrand values, the staging of wave_davies_pvalue)
+    const size_t smem = sizeof(double) * 4 * ((b.maxM + 1) & ~1) + sizeof(double) * 42 +
+                        sizeof(double) * (3 * 64 + 2 * kTermCap) + sizeof(int) * (64 + 64 + 66) + 32;
+    if (b.tests & RVT_TEST_EXACT_DAVIES)  // Davies' coefficient sums term by term (verification) / in product form
+      hipLaunchKernelGGL((gene_pvalue_kernel<false>), dim3(n), dim3(64), smem, pst, b.d_desc, b.tests);
+    else
+      hipLaunchKernelGGL((gene_pvalue_kernel<true>), dim3(n), dim3(64), smem, pst, b.d_desc, b.tests);
+  }
+  if (pv_apart) {
+    HIP_TRY(c, hipEventRecord(c->ev_pv_out[slot_idx], pst));
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_pv_out[slot_idx], 0));
+  }
+  return RVT_OK;
+}
+
+// the gene tests: burden, assembly, spectra, p-values; the records start their way back and the slot remembers where to
+static int gene_tests_tail(rvt_ctx* c, Batch& b, rvt_gene_result* out) {
+  const int n = b.n;
+  const uint32_t tests = b.tests;
+  Slot& sl = *b.sl;
+  const bool burden = (tests & (RVT_TEST_CMC | RVT_TEST_ZEGGINI)) != 0;
+  if (burden || b.dbg) launch_burden(c, b);
+  const unsigned tests_eff = burden ? tests : (tests & ~(RVT_TEST_CMC | RVT_TEST_ZEGGINI));
+  launch_assembly(c, b, tests_eff);
+  if (tests & (RVT_TEST_SKAT | RVT_TEST_SKATO | RVT_TEST_FAMSKAT))
+    launch_eigen(c, b, (tests & RVT_TEST_FAMSKAT) ? (unsigned)RVT_TEST_SKAT : tests_eff);
+  int rc = launch_pvalue(c, b);
+  if (rc) return rc;
   HIP_TRY(c, hipGetLastError());
   rvt_gene_result* h_res = reinterpret_cast<rvt_gene_result*>(sl.h_stage + sizeof(GeneDesc) * n +
-                                                               (sizeof(double) * af_total + 63) / 64 * 64);
-  HIP_TRY(c, hipMemcpyAsync(h_res, base + off_res, sizeof(rvt_gene_result) * n, hipMemcpyDeviceToHost, st));
-  bt.mark(5);
-  bt.print(n);
+                                                               (sizeof(double) * b.af_total + 63) / 64 * 64);
+  HIP_TRY(c, hipMemcpyAsync(h_res, b.base + b.off.res, sizeof(rvt_gene_result) * n, hipMemcpyDeviceToHost, b.st));
+  b.bt.mark(5);
+  b.bt.print(n);
   sl.pending_out = out;
   sl.pending_done = c->next_done_flag;
   c->next_done_flag = nullptr;
   sl.h_results = h_res;
   sl.pending_n = n;
+  return RVT_OK;
+}
+
+// profiling counters; an inspection call waits and takes gene 0's debug data out
+static int account_and_inspect(rvt_ctx* c, const Batch& b) {
+  const int n = b.n, d = c->nc.d;
+  const double N = (double)c->nc.N;
   if (c->profiling) {
     c->timing.genes += n;
-    c->timing.genes_hard_call += n_hc;
+    c->timing.genes_hard_call += b.n_hc;
     for (int g = 0; g < n; ++g) {
-      if (desc[g].hc == 3)
-        c->timing.alg_bytes_hc += (double)desc[g].pk_pitch * Ms[g] + 8.0 * (double)N * (d + 2);
-      else if (desc[g].hc) c->timing.alg_bytes_hc += 8.0 * (double)N * Ms[g] + 8.0 * (double)N * (d + 2);  // (SURVEY 8d's d + 2, also for the weighted kernels)
-      c->timing.alg_bytes += 8.0 * (double)N * Ms[g] + 8.0 * (double)N * (d + 2);
-      c->timing.alg_flops += 2.0 * (double)N * Ms[g] * (Ms[g] + d + 1);
+      const double M = b.Ms[g], null_bytes = 8.0 * N * (d + 2);  // (SURVEY 8d's d + 2, also for the weighted kernels)
+      if (b.desc[g].hc == kPathPacked)
+        c->timing.alg_bytes_hc += (double)b.desc[g].pk_pitch * M + null_bytes;
+      else if (b.desc[g].hc)
+        c->timing.alg_bytes_hc += 8.0 * N * M + null_bytes;
+      c->timing.alg_bytes += 8.0 * N * M + null_bytes;
+      c->timing.alg_flops += 2.0 * N * M * (M + d + 1);
     }
   }
-  if (dbg) {
-    HIP_TRY(c, sync_stream(st));
-    const GeneDesc& g0 = desc[0];
+  if (const DebugOut* dbg = b.dbg) {
+    HIP_TRY(c, sync_stream(b.st));
+    const GeneDesc& g0 = b.desc[0];
     if (dbg->flip) HIP_TRY(c, hipMemcpy(dbg->flip, g0.dbg_flip, sizeof(int) * g0.M, hipMemcpyDeviceToHost));
     if (dbg->kept) HIP_TRY(c, hipMemcpy(dbg->kept, g0.dbg_kept, sizeof(int) * g0.M, hipMemcpyDeviceToHost));
-    if (dbg->cmc) HIP_TRY(c, hipMemcpy(dbg->cmc, g0.dbg_cmc, sizeof(double) * N, hipMemcpyDeviceToHost));
-    if (dbg->zeg) HIP_TRY(c, hipMemcpy(dbg->zeg, g0.dbg_zeg, sizeof(double) * N, hipMemcpyDeviceToHost));
+    if (dbg->cmc) HIP_TRY(c, hipMemcpy(dbg->cmc, g0.dbg_cmc, sizeof(double) * c->nc.N, hipMemcpyDeviceToHost));
+    if (dbg->zeg) HIP_TRY(c, hipMemcpy(dbg->zeg, g0.dbg_zeg, sizeof(double) * c->nc.N, hipMemcpyDeviceToHost));
     if (dbg->desc0) *dbg->desc0 = g0;
   }
   return RVT_OK;
+}
+
+int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const double* af,
+              const int64_t* ids, uint32_t tests, const rvt_params* prm, rvt_gene_result* out,
+              DebugOut* dbg, CovOut* cov, const signed char* kind) {
+  Batch b;
+  if (!c || n < 0 || (n > 0 && (!dG || !Ms || !af || !out))) return fail(c, RVT_E_INVALID, "bad batch arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  if (n == 0) return RVT_OK;
+  hipSetDevice(c->device);
+  b.n = n, b.dG = dG, b.Ms = Ms, b.af = af, b.ids = ids, b.tests = tests, b.dbg = dbg, b.cov = cov, b.kind = kind;
+  b.params = prm ? *prm : rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05};
+  int rc = acquire_slot(c, b);
+  if (rc) return rc;
+  plan_batch(c, b);
+  if ((rc = describe_genes(c, b)) != RVT_OK) return rc;
+  if ((rc = upload_genes(c, b)) != RVT_OK) return rc;
+  if ((rc = launch_suffstats(c, b)) != RVT_OK) return rc;
+  if (cov) return cov->score ? score_tail(c, b) : cov_tail(c, b);
+  if ((rc = gene_tests_tail(c, b, out)) != RVT_OK) return rc;
+  return account_and_inspect(c, b);
 }
 
 int rvt_sync(rvt_ctx* c) {
@@ -1760,9 +1907,7 @@ int rvt_reserve(rvt_ctx* c, int n, const int* Ms) {
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   hipSetDevice(c->device);
   const NullConsts& nc = c->nc;
-  const int d = nc.d;
-  const int64_t nsteps = nc.ld >> 4;
-  const int n_bparts = (int)((nc.N + kBurdenSPB - 1) / kBurdenSPB);
+  // the worst-case plan of a batch of these genes: the most wave-parts any of its splits gives, every gene on either path
   const bool hcx = nc.binary && c->hcx_ok && c->hc_enabled;
   int n_wparts, steps_per, n_wparts1, steps_per1;
   choose_split(nc.ld, n, nc.binary != 0, &n_wparts, &steps_per, hcx);
@@ -1772,21 +1917,19 @@ int rvt_reserve(rvt_ctx* c, int n, const int* Ms) {
     choose_split(nc.ld, n, false, &n_wparts1, &steps_per1, false, true);
     n_wparts = std::max(n_wparts, n_wparts1);
   }
-  size_t total = 0, af_total = 0;
-  GeneOff o;
+  size_t af_total = 0;
   for (int g = 0; g < n; ++g) {
     if (Ms[g] < 1 || Ms[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_INVALID, "gene %d has M=%d", g, Ms[g]);
-    layout_gene(Ms[g], d, n_wparts, nsteps, n_bparts, false, -1, &total, &o);
     af_total += (size_t)Ms[g];
-    if (hcx) total += 256 + sizeof(unsigned long long) * hcx_pq_entries(16 * ((Ms[g] + 15) / 16));
   }
-  total += sizeof(double) * af_total + sizeof(GeneDesc) * n + sizeof(rvt_gene_result) * n + 4 * 256;
-  const size_t stage_bytes = sizeof(GeneDesc) * n + sizeof(double) * af_total + sizeof(rvt_gene_result) * n + 64;
+  Batch b;
+  b.n = n, b.Ms = Ms, b.n_wparts = n_wparts, b.n_bparts = (int)((nc.N + kBurdenSPB - 1) / kBurdenSPB), b.caps.hcx = hcx;
+  const size_t total = layout_arena(c, b, true);
   for (int i = 0; i < kSlots; ++i) {  // (the re-run slot grows on demand)
     Slot& sl = c->slots[i];
     int rc = ensure_arena(c, sl, total + 4096);
     if (rc) return rc;
-    rc = ensure_stage(c, sl, stage_bytes);
+    rc = ensure_stage(c, sl, batch_stage_bytes(n, af_total));
     if (rc) return rc;
   }
   return RVT_OK;
@@ -1858,7 +2001,7 @@ int rvt_debug_suffstat(rvt_ctx* c, const double* dG, int M, double* S, double* T
   if (g0.hc) {  // handed back by the hard-call kernel: the general kernel's statistics are what the buffers hold
     unsigned short fl = 0;
     HIP_TRY(c, hipMemcpy(&fl, g0.flags + 2 * g0.MT + 1, sizeof(fl), hipMemcpyDeviceToHost));
-    if (fl) g0.hc = 0;
+    if (fl) g0.hc = kPathGeneral;
   }
   const int rows = g0.hc ? kHcColstatRows : 3;
   std::vector<double> parts((size_t)g0.n_wparts * psz), cs((size_t)g0.n_wparts * rows * g0.Mp);
@@ -1935,7 +2078,7 @@ int rvt_debug_suffstat(rvt_ctx* c, const double* dG, int M, double* S, double* T
       const double hh = s - 4.0 * (pij + pji) - 16.0 * q;
       s = hh + mu[j] * pij + mu[i] * pji + (mu[i] * mu[j]) * q;
     }
-    if (j < M && (g0.hc == 2 || g0.hc == 4)) s /= g0.lat_den * g0.lat_den;  // lattice dosages: the integer K'K, divided once (gene_assemble)
+    if (j < M && path_integer_gram(g0.hc)) s /= g0.lat_den * g0.lat_den;  // lattice dosages: the integer K'K, divided once (gene_assemble)
     return s;
   };
   for (int i = 0; i < M; ++i) {
@@ -1956,7 +2099,7 @@ int rvt_debug_suffstat(rvt_ctx* c, const double* dG, int M, double* S, double* T
       mn = std::min(mn, mu[i]);
       mx = std::max(mx, mu[i]);
     }
-    if (g0.hc == 2 || g0.hc == 4) s /= g0.lat_den;
+    if (path_integer_gram(g0.hc)) s /= g0.lat_den;
     if (colsum) colsum[i] = s;
     if (cmin) cmin[i] = mn;
     if (cmax) cmax[i] = mx;

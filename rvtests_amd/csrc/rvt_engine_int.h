@@ -149,11 +149,31 @@ struct Slot {
   unsigned long long seq = 0;  // launch order
 };
 constexpr int kSlots = RVT_MAX_INFLIGHT;
-constexpr int kSlotsAll = kSlots;
+
+// What the engine's own decoder wrote into a gene's block: Pending::kind, and — as one byte per gene — run_batch's `kind`.
+enum BlockKind : int {
+  kKindUnknown = -1,  // fp64 from the caller: the content hint decides (rvt_set_content_hint)
+  kKindDosage = 0,    // dosages (BGEN)
+  kKindHardCall = 1,  // hard calls (+ imputed means)
+  kKindDecimal = 2,   // decimal dosages (VCF text)
+  kKindPacked = 3,    // the block holds PLINK 2-bit rows, not doubles
+};
+constexpr int kKindPlanesFlag = 0x10;  // beside kKindPacked: T = G'[X | rr] from the null tile's digit planes (resident .bed genes)
+struct KindBits {
+  int kind;     // a BlockKind
+  bool planes;
+};
+inline signed char encode_kind(int kind, bool planes) {
+  return (signed char)(kind == kKindPacked && planes ? (kind | kKindPlanesFlag) : kind);
+}
+inline KindBits decode_kind(const signed char* kind, int g) {
+  if (!kind || kind[g] < 0) return {kKindUnknown, false};
+  return {kind[g] & 0xf, (kind[g] & kKindPlanesFlag) != 0};
+}
 
 struct rvt_ctx {
   int device = 0;
-  Slot slots[kSlotsAll];
+  Slot slots[kSlots];
   unsigned long long launch_seq = 0;
   hipStream_t stream = nullptr;  // == slots[0].stream (set-up work, rvt_stream())
   hipStream_t io_stream = nullptr;  // host copies + consolidation of the streaming interface: never behind a batch
@@ -321,11 +341,11 @@ struct rvt_ctx {
   DevBuf<uint32_t> d_perm_states;   // B x 31
   DevBuf<double> d_perm_R, d_perm_C, d_perm_Q, d_perm_cur;
   int perm_cap_B = 0;
-  hipEvent_t ev_in[kSlotsAll] = {}, ev_k2[kSlotsAll] = {}, ev_k2b[kSlotsAll] = {};
+  hipEvent_t ev_in[kSlots] = {}, ev_k2[kSlots] = {}, ev_k2b[kSlots] = {};
   // The p-value kernel on CUs of its own (RVT_PV_CUS, see rvt_init): two streams restricted to the first pv_cus mask bits,
   // used by alternate batches; the batch's stream hands over by event and takes the records back by event.
   hipStream_t pv_stream[2] = {nullptr, nullptr};
-  hipEvent_t ev_pv_in[kSlotsAll] = {}, ev_pv_out[kSlotsAll] = {};
+  hipEvent_t ev_pv_in[kSlots] = {}, ev_pv_out[kSlots] = {};
   int pv_cus = 0;
   unsigned pv_turn = 0;
   std::vector<int> pv_order;  // scratch of run_batch: the batch's genes by falling M (GeneDesc::pv_gene)
@@ -429,8 +449,7 @@ struct rvt_ctx {
     int io_error = 0;     // != 0: the gene's VCF text / BGEN blocks were malformed (h_io_err): its record is void
     int decoded = 0;      // 1: VCF text, 2: BGEN blocks (the submission has an input-error word in its ring slot)
     bool planes = false;  // kind 3 only: G'[X | rr] on the int8 matrix cores from the null tile's digit planes (resident .bed genes)
-    int kind = -1;        // what the engine's decoder wrote: 1 hard calls (+ imputed means), 0 dosages (BGEN), 2 decimal
-                          // dosages (VCF text), 3 the block holds PLINK 2-bit rows (not doubles), -1 unknown
+    int kind = kKindUnknown;  // what the engine's decoder wrote (a BlockKind)
   };
   std::deque<Pending> queue;
   std::vector<std::pair<size_t, double*>> block_pool;  // free device blocks of the streaming interface (bytes, ptr)
@@ -694,8 +713,7 @@ RVT_INTERNAL int staged_h2d_2d(rvt_ctx* c, void* dst, size_t dpitch, const void*
 RVT_INTERNAL int upload_block_data(rvt_ctx* c, double* dG, int M, const double* G);
 struct DebugOut;
 struct CovOut;
-// kind (optional, per gene): what the engine's own decoder wrote into the block — 1 hard calls (+ imputed means), 0 dosages,
-// 2 decimal dosages, 3 packed 2-bit rows, -1 unknown
+// kind (optional, per gene): what the engine's own decoder wrote into the block — a BlockKind byte (encode_kind, above)
 RVT_INTERNAL int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const double* af, const int64_t* ids,
                            uint32_t tests, const rvt_params* prm, rvt_gene_result* out, DebugOut* dbg, CovOut* cov = nullptr,
                            const signed char* kind = nullptr);
@@ -750,7 +768,6 @@ struct DebugOut {
   int* kept = nullptr;
   double* cmc = nullptr;
   double* zeg = nullptr;
-  double** parts_out = nullptr;  // device pointers of gene 0's partials etc.
   GeneDesc* desc0 = nullptr;
 };
 

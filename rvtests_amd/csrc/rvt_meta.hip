@@ -1098,7 +1098,7 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
   // device work runs once per 32 consecutive columns (flush_col_queue)
   if (ncols == 1 && c->hc_enabled && !getenv("RVT_UPLOAD_FP64") && !getenv("RVT_UPLOAD_NO_QUEUE") && N >= 4096) {
     rvt_ctx::ColQueue& q = c->colq;
-    const size_t pitch = ((N + 3) / 4 + 15) / 16 * 16;
+    const size_t pitch = hcp_row_pitch(N);
     if (q.n > 0 && (q.dG != dG || col0 != q.col0 + q.n || q.n == rvt_ctx::kColQueue || q.pitch != pitch)) {
       int rc = flush_col_queue(c);
       if (rc) return rc;
@@ -1153,7 +1153,7 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
   if (c->hc_enabled && !getenv("RVT_UPLOAD_FP64") && N >= 4096) {
     int rc = stage_ready(c);
     if (rc) return rc;
-    const size_t pitch = ((N + 3) / 4 + 15) / 16 * 16;
+    const size_t pitch = hcp_row_pitch(N);
     const size_t need = pitch * (size_t)ncols + sizeof(double) * (size_t)ncols;
     HIP_TRY(c, c->d_colpack.grow(need, need + need / 2));
     if (pitch <= c->stage.chunk_bytes) {

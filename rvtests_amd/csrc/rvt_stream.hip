@@ -54,7 +54,7 @@ int launch_group(rvt_ctx* c, size_t first, int n) {
     Ms.push_back(p.M);
     ids.push_back(p.id);
     af.insert(af.end(), p.af.begin(), p.af.end());
-    kinds.push_back((signed char)(p.kind == 3 && p.planes ? (3 | 0x10) : p.kind));
+    kinds.push_back(encode_kind(p.kind, p.planes));
   }
   c->launched.emplace_back();
   rvt_ctx::Launched& L = c->launched.back();
@@ -478,7 +478,7 @@ int try_submit_packed_f64(rvt_ctx* c, int64_t gene_id, int M, const double* G, c
   //  registered fp64 block always took the DMA.  It still does when the block cannot be packed: dosages, RVT_PACK_FP64=0.)
   const int64_t N = c->nc.N;
   if (N < 4096) return 0;  // small blocks: nothing to gain
-  const size_t pk_pitch = ((size_t)((N + 3) / 4) + 15) / 16 * 16;
+  const size_t pk_pitch = hcp_row_pitch(N);
   if (stage_ready(c) != RVT_OK || pk_pitch > c->stage.chunk_bytes) return 0;
   const size_t need = (size_t)kHcpHeaderBytes + pk_pitch * M + 16;
   rvt_ctx::Pending p;
@@ -558,7 +558,7 @@ int try_submit_packed_f64(rvt_ctx* c, int64_t gene_id, int M, const double* G, c
     *rc_out = fail(c, RVT_E_HIP, "packed fp64 gene: %s", hipGetErrorString(e));
     return 1;
   }
-  p.kind = 3;
+  p.kind = kKindPacked;
   p.decoded = 0;
   p.af.assign(af, af + M);
   p.tests = tests;
@@ -598,7 +598,7 @@ int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, int mode, c
   const bool i8_packs = mode == 2 && !c->no_i8_pack && c->stage_on && c->nc.N >= 4096 &&
                         !(getenv("RVT_PACK_I8") && atoi(getenv("RVT_PACK_I8")) == 0);
   const bool packed = (mode == 3 || mode == 7 || i8_packs) && packed_eligible(c, M, tests, prm);
-  const size_t pk_pitch = ((size_t)((c->nc.N + 3) / 4) + 15) / 16 * 16;
+  const size_t pk_pitch = hcp_row_pitch(c->nc.N);
   const size_t need = packed ? (size_t)kHcpHeaderBytes + pk_pitch * M + 16 : sizeof(double) * (size_t)c->null_ld * M;
   bool fresh_packed = false;
   int best = -1;
@@ -626,7 +626,10 @@ int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, int mode, c
   const int64_t N = c->nc.N, ld = c->null_ld;
   // what this entry point writes into the block: hard calls with imputed means (packed / text genotypes), dosages
   // (dosage text, BGEN), or whatever the caller's doubles are
-  p.kind = packed ? 3 : ((mode == 2 || mode == 3 || mode == 4 || mode == 7) ? 1 : (mode == 5 ? 2 : (mode == 6 ? 0 : -1)));
+  p.kind = packed ? kKindPacked
+                  : ((mode == 2 || mode == 3 || mode == 4 || mode == 7)
+                         ? kKindHardCall
+                         : (mode == 5 ? kKindDecimal : (mode == 6 ? kKindDosage : kKindUnknown)));
   p.planes = packed && mode == 7;
   p.decoded = (mode == 4 || mode == 5) ? 1 : (mode == 6 ? 2 : 0);
   if (mode == 0) {
@@ -967,7 +970,7 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
   TraceScope ts_all(c, &c->tr_block);
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
-  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = (cb + 15) / 16 * 16;
+  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
   const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
   HIP_TRY(c, c->h_af_ring.grow(kAfRingBytes, kAfRingBytes, nullptr, false, hipHostMallocMapped));
   if (c->af_unresolved + n > rvt_ctx::kAfSlots) {
@@ -1023,7 +1026,7 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
     genes[(size_t)g] = BedGeneRef{r0, M, reinterpret_cast<HcpHeader*>(p.dG), mapped + (size_t)slot * RVT_MAX_VARIANTS, nullptr};
     p.af_slot = slot;
     p.af.resize((size_t)M);
-    p.kind = 3;
+    p.kind = kKindPacked;
     p.planes = true;  // (resident rows: nothing waits for a link, the sufficient-statistics kernel is the bound)
     p.decoded = 0;
     p.tests = tests;
@@ -1075,7 +1078,7 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
   if (rc) return rc;
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
-  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = (cb + 15) / 16 * 16;
+  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
   const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
   const size_t gene_bytes = (size_t)kHcpHeaderBytes + pk_pitch * kSlice + 16;
   // work space: row / gene references, partial counts (as submit_bed_dev_batch), a frequency sink, the counts
@@ -1136,7 +1139,7 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
     ptr.clear();
     Ms.clear();
     ids.clear();
-    kinds.assign((size_t)n, (signed char)(3 | 0x10));
+    kinds.assign((size_t)n, encode_kind(kKindPacked, true));
     shc.assign((size_t)n, 1);
     for (int g = 0; g < n; ++g) {
       const int M = std::min(kSlice, cols - g * kSlice);
@@ -1565,7 +1568,7 @@ static void pop_collected(rvt_ctx* c, int n, rvt_gene_result* out) {
       snprintf(who, sizeof(who), " of gene %lld", (long long)c->queue[g].id);
       io_err_message(c, c->queue[g].io_error, c->queue[g].decoded == 2, who);
     }
-    (c->queue[g].kind == 3 ? c->pk_pool : c->block_pool).emplace_back(c->queue[g].bytes, c->queue[g].dG);
+    (c->queue[g].kind == kKindPacked ? c->pk_pool : c->block_pool).emplace_back(c->queue[g].bytes, c->queue[g].dG);
   }
   c->queue.erase(c->queue.begin(), c->queue.begin() + n);
   for (auto& L : c->launched) L.first -= (size_t)n;

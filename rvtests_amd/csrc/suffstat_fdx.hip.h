@@ -29,7 +29,7 @@
 // (r, c), c = MT standing for the null tile, dealt out in row-major order; the last wave, which gets the fewest, also owns
 // the burden tile), two operand buffers in LDS, one barrier per iteration of 128 samples.  The operands are five times those
 // of the hard-call kernel (5 bytes per genotype), which is why an iteration is 128 samples, not 256: 104 KB of LDS for
-// M in 65..80.  Outputs as gene_suffstat_lat writes them (GeneDesc::hc == 2 with lat_den = 2^37): the integer K'K in the
+// M in 65..80.  Outputs as gene_suffstat_lat writes them (GeneDesc::hc as kPathLattice, with lat_den = 2^37): the integer K'K in the
 // G'G block, true values in the [X | res] columns, the integer column sums; gene_assemble divides once.
 #pragma once
 #include "suffstat_hcx.hip.h"

@@ -13,6 +13,18 @@ namespace rvt {
 
 struct GeneStats;
 
+// Which sufficient-statistics kernel a gene STARTS on (GeneDesc::hc).  The values are read by the device and order a batch's
+// descriptors (general genes first), so they stay what they are.
+enum KernelPath : int {
+  kPathGeneral = 0,     // gene_suffstat_mfma / _panel: the fp64 kernel, any content
+  kPathHardCall = 1,    // gene_suffstat_hc / _hcw / _hcx: hard calls (+ one imputed value per column)
+  kPathLattice = 2,     // gene_suffstat_lat: dosages on a decimal lattice
+  kPathPacked = 3,      // gene_suffstat_hcp: PLINK 2-bit rows
+  kPathFloatDigit = 4,  // gene_suffstat_fdx: float-precision dosages (as kPathLattice, with lat_den = 2^37)
+};
+// the paths whose `parts` / `colstat` hold the INTEGERS K'K and sum K, divided by GeneDesc::lat_den once (gene_assemble)
+__host__ __device__ inline bool path_integer_gram(int hc) { return hc == kPathLattice || hc == kPathFloatDigit; }
+
 typedef double d4_t __attribute__((ext_vector_type(4)));
 typedef double d2_t __attribute__((ext_vector_type(2)));
 // pointers read from descriptors in memory are generic; loads through them would be flat_load (which also ties
@@ -47,16 +59,14 @@ struct GeneDesc {
   // hard-call path (suffstat_hc.hip.h)
   unsigned short pflip[8];  // predicted flip bits (af > 0.5) per 16-variant block, first 6 blocks
   int n_bparts;             // burden partial records of this gene (wave-parts on the hard-call path)
-  int hcp_planes;           // hc == 3: G'[X | rr] from the digit planes of the null tile (gene_tnull_hcp; resident .bed genes)
-  int hc;                   // 4: gene_suffstat_fdx (float-precision dosages: as 2, with lat_den = 2^37),
-                            // 1: gene_suffstat_hc / _hcw (hard calls), 2: gene_suffstat_lat (lattice dosages), 3: gene_suffstat_hcp
-                            // (PLINK 2-bit rows), 0: general kernel
+  int hcp_planes;           // kPathPacked: G'[X | rr] from the digit planes of the null tile (gene_tnull_hcp; resident .bed genes)
+  int hc;                   // a KernelPath: the kernel the gene starts on (non-zero: one of the integer kernels)
   double* vt_mem;           // AnalyticVT workspace (gene_vt_doubles(Mp)), null unless the test is requested
   unsigned* pq;             // hard-call path: n_wparts x hc_pq_words(MT) packed 16-bit counters of the masked tiles
   unsigned* wflags;         // hard-call path: per wave-part, bit 0 = masked entries met (pq written), bit 1 = bad entry
-  int pk_pitch;             // hc == 3 (gene_suffstat_hcp): G points to a packed block — header, then M rows of 2-bit codes,
+  int pk_pitch;             // kPathPacked (gene_suffstat_hcp): G points to a packed block — header, then M rows of 2-bit codes,
                             // pk_pitch bytes apart
-  double lat_den;           // hc == 2: the lattice denominator — the G'G tiles and column sums of `parts` / `colstat` are
+  double lat_den;           // path_integer_gram(hc): the lattice denominator — the G'G tiles and column sums of `parts` / `colstat` are
                             // the INTEGERS K'K and sum K (exact through the reduction), divided once in gene_assemble
   unsigned long long* pqw;  // weighted hard-call path (suffstat_hcx.hip.h): the gene's masked-entry tables P = H'Vm (Mp x Mp) and
                             // Q = m'Vm (Mp x Mp, upper triangle) as 64-bit integers in units of 2^-42, zeroed by the host
