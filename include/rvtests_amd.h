@@ -602,6 +602,36 @@ typedef struct rvt_kbac_result {
 int rvt_kbac_blocks(rvt_ctx* ctx, int n, const double* const* dG, const int* M, const double* af, const double* y,
                     int nperm, double alpha, rvt_kbac_result* out);
 
+/* ---- Price's variable-threshold test (--vt price[nPerm=10000,alpha=0.05]; VariableThresholdPrice src/Model.h:1745-1882 over
+ * makeVariableThreshodlGenotype / zegginiCollapse src/Model.cpp:132-148,301-382, permute / centerVector / getRowVariance
+ * src/LinearAlgebra.h:8-21,43-49,183-191 and Permutation src/Permutation.h:48-158) --------------------------------------------
+ * Quantitative AND binary traits; covariates are ignored (the reference only warns).  The flipped, polymorphic columns are
+ * grouped by ceil(1e6 af) / 1e6, ascending and cumulative; the collapsed genotype at threshold t counts per sample the
+ * carried variants ((int)g > 0: a mean-imputed value below 1 is no carrier) of the groups up to t;
+ * z_t = sum_i b_t(i) (y_i - mean y) / sd_t with sd_t^2 = sum (b - mean b)^2 / N (undivided where sd_t = 0), zmax = max |z_t|
+ * (first maximiser: opt_freq), and the phenotype is shuffled until NumGreater + NumEqual >= (int)(2 nperm alpha) or nperm
+ * shuffles are done.  Exact mode (default) replays the reference's cumulative Fisher-Yates shuffles on the emulated rand()
+ * stream (rvt_rand_seed; N - 1 draws per shuffle, genes in call order; a gene without polymorphic column draws nothing);
+ * rvt_set_perm_exact(ctx, 0) keys the shuffles by (seed, a hash of the gene's M and af, shuffle) instead: the same result
+ * in any gene order on any context.  The device holds the blocks (as for rvt_run_blocks), a null model must be set (it
+ * defines N); y = the phenotype, af = the concatenated frequencies of every gene's columns, af[j] being paired with column j
+ * of the flipped, polymorphic block as the reference's groupFrequency pairs them.  A gene with one frequency group only is
+ * computed like any other (the reference's assert(rows > 1) is compiled out of its release build).  For a 0 / 1 phenotype
+ * sum b y is formed from exact integers (cases among the carriers), so equal configurations tie exactly.
+ * The rvt_group_* layer does not carry this test. */
+typedef struct rvt_vtprice_result {
+  int fit_ok;                /* 0: no polymorphic column (the other fields as after Permutation::reset; opt_freq = zmax = -1) */
+  int n_poly;                /* columns after flip-to-minor + monomorphic removal */
+  int n_threshold;           /* distinct frequency groups = thresholds */
+  int64_t n_carrier_entries; /* (sample, variant) pairs with (int)g > 0 */
+  double opt_freq;           /* threshold of the first maximiser */
+  double zmax;               /* observed max |z_t| (the permutation test's Stat) */
+  int num_perm, actual_perm, num_greater, num_equal;
+  double perm_pvalue;        /* (NumGreater + NumEqual / 2) / ActualPerm, 1 when no shuffle ran */
+} rvt_vtprice_result;
+int rvt_vtprice_blocks(rvt_ctx* ctx, int n, const double* const* dG, const int* M, const double* af, const double* y,
+                       int nperm, double alpha, rvt_vtprice_result* out);
+
 /* ---- raw / packed genotypes at the boundary (SURVEY §8f "next" #1) --------------------------------------------------
  * Like rvt_submit_gene, but the block is what the genotype extractor produced, BEFORE DataConsolidator::consolidate:
  * missing genotypes are negative (-9, libVcf/VCFConstant.h:4).  The device then does what consolidate() does to the

@@ -9,8 +9,8 @@ CPU fallback: if the HIP library is missing or there is no GPU, construction fai
 """
 from .engine import (Engine, Group, GeneResult, Params, Timing, RvtError, build_library, library_path, load_library,
                      TEST_SKAT, TEST_SKATO, TEST_CMC, TEST_ZEGGINI, TEST_ALL, TEST_ANALYTICVT, TRAIT_QUANTITATIVE,
-                     TRAIT_BINARY, MAX_INFLIGHT, KbacResult, DecomposeInfo)
+                     TRAIT_BINARY, MAX_INFLIGHT, KbacResult, DecomposeInfo, VtPriceResult)
 
 __all__ = ["Engine", "Group", "GeneResult", "Params", "Timing", "RvtError", "build_library", "library_path", "load_library",
            "TEST_SKAT", "TEST_SKATO", "TEST_CMC", "TEST_ZEGGINI", "TEST_ALL", "TEST_ANALYTICVT", "TRAIT_QUANTITATIVE",
-           "TRAIT_BINARY", "MAX_INFLIGHT", "KbacResult", "DecomposeInfo"]
+           "TRAIT_BINARY", "MAX_INFLIGHT", "KbacResult", "DecomposeInfo", "VtPriceResult"]

@@ -629,6 +629,57 @@ void KbacTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   }
 }
 
+// ---- VariableThresholdPrice ---------------------------------------------------------------------------------------------------
+VariableThresholdPrice::VariableThresholdPrice(int nPerm_, double alpha_) : nPerm(nPerm_), alpha(alpha_) {
+  modelName = "VariableThresholdPrice";
+}
+void VariableThresholdPrice::reset() {  // src/Model.h:1820-1824 over Permutation::reset (src/Permutation.h:99-105)
+  fitOK = false;
+  obs = 0.0;
+  actualPerm = numX = numEqual = 0;
+}
+int VariableThresholdPrice::fit(GeneData* dc) {
+  fitOK = false;
+  rvt_ctx* ctx = GpuBroker::instance().contextWithNull(*dc, isBinaryOutcome(), &lastError);  // (the null model defines N on the device)
+  if (!ctx) return -1;
+  double* block = nullptr;
+  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
+    lastError = rvt_last_error(ctx);
+    if (block) rvt_block_free(ctx, block);
+    return -1;
+  }
+  const double* bp = block;
+  const int M = dc->M;
+  const int rc = rvt_vtprice_blocks(ctx, 1, &bp, &M, dc->markerFrequency.data(), dc->phenotype, nPerm, alpha, &rec);
+  rvt_block_free(ctx, block);
+  if (rc) {
+    lastError = rvt_last_error(ctx);
+    return -1;
+  }
+  fitOK = rec.fit_ok != 0;
+  if (!fitOK) return -1;  // genotype.cols == 0: nothing below was touched (src/Model.h:1758-1761)
+  zmax = rec.zmax;
+  optimalFreq = rec.opt_freq;
+  obs = rec.zmax;  // perm.init(fabs(zmax))
+  actualPerm = rec.actual_perm;
+  numX = rec.num_greater;
+  numEqual = rec.num_equal;
+  return 0;
+}
+void VariableThresholdPrice::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab());
+  fp->write("\tOptFreq\tZmax\t");  // (after writeHeaderTab's own tab: an empty column, src/Model.h:1808-1809)
+  fp->write("NumPerm\tActualPerm\tStat\tNumGreater\tNumEqual\tPermPvalue\n");
+}
+void VariableThresholdPrice::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.valueTab());
+  // Permutation::updateValue: ints via toString, doubles via floatToString (src/Result.h:52-63); getPvalue :95-98
+  const double p = actualPerm == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEqual) / actualPerm;
+  fp->write("\t" + formatG(optimalFreq) + "\t" + formatG(zmax) + "\t" + std::to_string(nPerm) + "\t" + std::to_string(actualPerm) +
+            "\t" + floatToString(obs) + "\t" + std::to_string(numX) + "\t" + std::to_string(numEqual) + "\t" + floatToString(p) +
+            "\n");
+}
+
 // ---- FamSkatTest ----------------------------------------------------------------------------------------------------------
 FamSkatTest::FamSkatTest(double, double) {
   modelName = "FamSkat";
@@ -1469,7 +1520,10 @@ int ModelManager::create(const std::string& type, const std::string& modelList) 
         model.push_back(new AnalyticVTTest(false));
       else if (modelName == "famanalytic")
         model.push_back(new AnalyticVTTest(true));
-      else {
+      else if (modelName == "price") {  // src/ModelManager.cpp vt switch: nPerm = 10000, alpha = 0.05
+        parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
+        model.push_back(new VariableThresholdPrice(nPerm, alpha));
+      } else {
         lastError = "Unknown model name: " + modelName + " .";
         return -1;
       }

@@ -327,6 +327,32 @@ class KbacTest : public ModelFitter {
   rvt_kbac_result rec{};
 };
 
+// `--vt price[nPerm=10000,alpha=0.05]` (src/ModelManager.cpp vt switch; VariableThresholdPrice, src/Model.h:1745-1882): Price's
+// variable-threshold permutation test for quantitative and binary traits (covariates are ignored, as the reference does
+// after its warning).  Columns: an EMPTY one (writeHeaderTab's tab followed by "\tOptFreq", src/Model.h:1807-1812), OptFreq,
+// Zmax with %g, then Permutation's NumPerm ActualPerm Stat NumGreater NumEqual PermPvalue.  A gene whose fit failed still
+// prints a row (:1814-1819 has no fitOK test): the Permutation fields as reset() leaves them and the OptFreq / Zmax of the
+// last successful fit (-1 before the first).  Synchronous: in exact mode the shuffles consume the process-wide random
+// stream gene by gene.
+class VariableThresholdPrice : public ModelFitter {
+ public:
+  VariableThresholdPrice(int nPerm, double alpha);
+  int fit(GeneData* dc) override;
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void reset() override;
+
+ private:
+  int nPerm;
+  double alpha;
+  bool fitOK = false;
+  double zmax = -1.0, optimalFreq = -1.0;  // members of the reference's class: they survive reset()
+  // Permutation's members (src/Permutation.h:150-156) as its constructor leaves them; reset() zeroes all but numPerm
+  double obs = -1.0;
+  int actualPerm = -1, numX = -1, numEqual = -1;
+  rvt_vtprice_result rec{};
+};
+
 // `--kernel famSkat[beta1:beta2]` (src/Model.h:3048-3145).  The reference ignores beta1 / beta2 for this model
 // (FamSkat.cpp:129-137 always uses Beta(1, 25)); so does this adapter.
 class FamSkatTest : public ModelFitter {

@@ -128,6 +128,7 @@ typedef GpuModel<rvt_host::FamBurdenTest> FamBurdenTest;
 typedef GpuModel<rvt_host::MetaCovTest> MetaCovTest;      // new MetaCovTest(windowSize)            :238-247
 typedef GpuModel<rvt_host::MetaScoreTest> MetaScoreTest;  // new MetaScoreTest()
 typedef GpuModel<rvt_host::KbacTest> KBACTest;            // new KBACTest(nPerm, alpha)
+typedef GpuModel<rvt_host::VariableThresholdPrice> VariableThresholdPrice;  // new VariableThresholdPrice(nPerm, alpha)
 typedef GpuModel<rvt_host::SingleVariantWaldTest> SingleVariantWaldTest;    // new SingleVariantWaldTest()   :54-98
 typedef GpuModel<rvt_host::SingleVariantScoreTest> SingleVariantScoreTest;  // new SingleVariantScoreTest()
 // the single-variant tests for related samples (src/ModelManager.cpp:63-84); familyModel = true as their constructors set it

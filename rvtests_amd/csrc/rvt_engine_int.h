@@ -51,6 +51,7 @@ void k2_launch_classify(dim3 grid, hipStream_t st, const double* G, long long N,
 #include "fam_kernels.hip.h"
 #include "rot_gemm.hip.h"
 #include "perm_kernels.hip.h"
+#include "vtprice_kernels.hip.h"
 #include "vcf_kernels.hip.h"
 #include "bgen_kernels.hip.h"
 #include "jacobi_kernels.hip.h"
@@ -334,6 +335,10 @@ struct rvt_ctx {
   uint64_t perm_seed = 1;
   DevBuf<double> d_pc_part;  // counter mode: partial products [slice][shuffle][variant]
   DevBuf<double> d_pc_Q;
+  // Price's variable-threshold test (vtprice_kernels.hip.h; grow-only): the gene's carrier list and tables, the partial sums
+  // [segment][shuffle] of a chunk, the chunk's zmax
+  DevBuf<char> d_vtp_ws, d_vtp_ent;
+  DevBuf<double> d_vtp_part, d_vtp_z;
   uint32_t rand_state[31];
   int64_t jump_N = -1;                 // J = A^(jump_N - 1) is cached for this sample count
   std::vector<uint32_t> jump;          // 31 x 31, row-major

@@ -50,6 +50,100 @@ static void free_perm(rvt_ctx* c) {
   c->perm_cap_B = 0;
 }
 
+// Shuffles per chunk of the exact mode: the chunk's permuted vectors (N x B doubles) stay under 6 GB
+static int exact_chunk(int nPerm, int64_t N) {
+  return std::max(1, std::min(nPerm, (int)std::min<int64_t>(2048, ((int64_t)6 << 30) / (8 * N))));
+}
+
+// The exact-mode permutation test shared by the SKAT and the variable-threshold stage: cumulative Fisher-Yates shuffles of
+// the vector d_start (N doubles on the device) on the emulated rand() stream, a chunk of B = exact_chunk() at a time.
+// stat(nb, B, &d_out) launches, on the context's stream, what turns the chunk's permuted vectors (columns of d_perm_R,
+// N x nb) into its nb statistics and names the device array that holds them; they are compared with obs under
+// Permutation's stop rule (src/Permutation.h:69-98).  m: columns of d_perm_C that the caller's statistic needs (0: none).
+// On return the stream stands behind the shuffles PERFORMED, whatever the chunk generated beyond them.
+extern "C++" {  // (this unit's functions sit inside extern "C"; a template cannot)
+template <class Stat>
+int exact_permutations(rvt_ctx* c, const double* d_start, int nPerm, double alpha, double obs, int m, Stat&& stat, int* actual_,
+                       int* numX_, int* numEq_) {
+  const int64_t N = c->nc.N;
+  hipStream_t st = c->stream;
+  // chunk buffers
+  const int B = exact_chunk(nPerm, N);
+  if (sizeof(uint32_t) * N * B > c->d_perm_idx.cap || B > c->perm_cap_B || sizeof(double) * N * B > c->d_perm_R.cap ||
+      sizeof(double) * B * m > c->d_perm_C.cap ||
+      sizeof(double) * N * 2 > c->d_perm_cur.cap) {  // (d_perm_cur holds 2 N doubles whatever B is: fewer shuffles of more samples must not keep it)
+    free_perm(c);
+    const size_t bm = (size_t)B * std::max(m, RVT_MAX_VARIANTS / 4);
+    HIP_TRY(c, c->d_perm_idx.alloc(sizeof(uint32_t) * (size_t)N * B));
+    HIP_TRY(c, c->d_perm_states.alloc(sizeof(uint32_t) * 31 * (size_t)B));
+    HIP_TRY(c, c->d_perm_R.alloc(sizeof(double) * (size_t)N * B));
+    HIP_TRY(c, c->d_perm_C.alloc(sizeof(double) * bm));
+    HIP_TRY(c, c->d_perm_Q.alloc(sizeof(double) * (size_t)B));
+    HIP_TRY(c, c->d_perm_cur.alloc(sizeof(double) * (size_t)N * 2));
+    c->perm_cap_B = B;
+  }
+  if (c->jump_N != N) {
+    c->jump.resize(31 * 31);
+    jump_matrix((uint64_t)(N - 1), c->jump.data());  // one shuffle draws N-1 numbers (LinearAlgebra.h:12-14)
+    c->jump_N = N;
+  }
+  double* cur = c->d_perm_cur;
+  double* nxt = c->d_perm_cur + N;
+  HIP_TRY(c, hipMemcpyAsync(cur, d_start, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
+  // Permutation::init — `threshold` is an INT member of the reference's class (src/Permutation.h:153): the product is truncated
+  // (nPerm = 100, alpha = 0.001 -> 0: the test stops before its first shuffle and reports p = 1; found by running the
+  // reference's compiled class beside this rule, tests/test_oracle_ref.py)
+  const double threshold = (double)(int)(1.0 * nPerm * alpha * 2);
+  int actual = 0, numX = 0, numEq = 0;
+  uint32_t s0[31];
+  std::memcpy(s0, c->rand_state, sizeof(s0));
+  std::vector<uint32_t> states((size_t)31 * (B + 1));
+  std::vector<double> Q(B);
+  bool more = true;
+  while (more) {
+    // Permutation::next() before every shuffle
+    if (actual >= nPerm || numX + numEq >= threshold) break;
+    const int nb = std::min(B, nPerm - actual);
+    std::memcpy(states.data(), s0, sizeof(s0));
+    for (int p = 0; p < nb; ++p) mat31_apply(c->jump.data(), &states[(size_t)31 * p], &states[(size_t)31 * (p + 1)]);
+    HIP_TRY(c, hipMemcpyAsync(c->d_perm_states, states.data(), sizeof(uint32_t) * 31 * (size_t)nb,
+                              hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(perm_init_kernel, dim3(2048), dim3(256), 0, st, c->d_perm_idx, (long long)N, B);
+    hipLaunchKernelGGL(perm_fisher_yates_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st,
+                       c->d_perm_states, c->d_perm_idx, (long long)N, B);
+    for (int p = 0; p < nb; ++p) {  // the shuffles are cumulative: apply them in order
+      hipLaunchKernelGGL(perm_apply_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_perm_idx, cur,
+                         nxt, c->d_perm_R, (long long)N, B, p);
+      std::swap(cur, nxt);
+    }
+    const double* d_out = nullptr;
+    const int rcs = stat(nb, B, &d_out);
+    if (rcs) return rcs;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(Q.data(), d_out, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    int used = 0;
+    for (; used < nb; ++used) {
+      if (actual >= nPerm || numX + numEq >= threshold) {
+        more = false;
+        break;
+      }
+      ++actual;  // Permutation::add
+      if (Q[used] > obs) ++numX;
+      if (Q[used] == obs) ++numEq;
+    }
+    std::memcpy(s0, &states[(size_t)31 * used], sizeof(s0));  // the stream continues after the shuffles performed
+    if (used < nb) {
+      // the vector of the next gene restarts from its own start anyway; nothing else carries over
+      more = false;
+    }
+  }
+  std::memcpy(c->rand_state, s0, sizeof(s0));
+  *actual_ = actual, *numX_ = numX, *numEq_ = numEq;
+  return RVT_OK;
+}
+}  // extern "C++"
+
 // The permutation test of one gene whose analytic SKAT result (obs = skat_Q) and weights are already on the device.
 //   dG: the gene's block (unflipped), g0: its descriptor of the batch that just finished (weights in its scratch)
 int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rvt_params& prm, rvt_gene_result* r) {
@@ -135,85 +229,25 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
     r->perm_pvalue = actual == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEq) / actual;
     return RVT_OK;
   }
-  // chunk buffers
-  const int B = std::max(1, std::min(nPerm, (int)std::min<int64_t>(2048, ((int64_t)6 << 30) / (8 * N))));
-  if (sizeof(uint32_t) * N * B > c->d_perm_idx.cap || B > c->perm_cap_B || sizeof(double) * B * m > c->d_perm_C.cap ||
-      sizeof(double) * N * 2 > c->d_perm_cur.cap) {  // (d_perm_cur holds 2 N doubles whatever B is: fewer shuffles of more samples must not keep it)
-    free_perm(c);
-    const size_t bm = (size_t)B * std::max(m, RVT_MAX_VARIANTS / 4);
-    HIP_TRY(c, c->d_perm_idx.alloc(sizeof(uint32_t) * (size_t)N * B));
-    HIP_TRY(c, c->d_perm_states.alloc(sizeof(uint32_t) * 31 * (size_t)B));
-    HIP_TRY(c, c->d_perm_R.alloc(sizeof(double) * (size_t)N * B));
-    HIP_TRY(c, c->d_perm_C.alloc(sizeof(double) * bm));
-    HIP_TRY(c, c->d_perm_Q.alloc(sizeof(double) * (size_t)B));
-    HIP_TRY(c, c->d_perm_cur.alloc(sizeof(double) * (size_t)N * 2));
-    c->perm_cap_B = B;
-  }
-  if (c->jump_N != N) {
-    c->jump.resize(31 * 31);
-    jump_matrix((uint64_t)(N - 1), c->jump.data());  // one shuffle draws N-1 numbers (LinearAlgebra.h:12-14)
-    c->jump_N = N;
-  }
   // permutedRes = res (src/Model.h:2708)
-  double* cur = c->d_perm_cur;
-  double* nxt = c->d_perm_cur + N;
-  HIP_TRY(c, hipMemcpyAsync(cur, c->d_res, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
-  const double obs = r->skat_Q;
-  // Permutation::init — `threshold` is an INT member of the reference's class (src/Permutation.h:153): the product is truncated
-    // (nPerm = 100, alpha = 0.001 -> 0: the test stops before its first shuffle and reports p = 1; found by running the
-    // reference's compiled class beside this rule, tests/test_oracle_ref.py)
-    const double threshold = (double)(int)(1.0 * nPerm * prm.skat_alpha * 2);
   int actual = 0, numX = 0, numEq = 0;
-  uint32_t s0[31];
-  std::memcpy(s0, c->rand_state, sizeof(s0));
-  std::vector<uint32_t> states((size_t)31 * (B + 1));
-  std::vector<double> Q(B);
-  bool more = true;
-  while (more) {
-    // Permutation::next() before every shuffle
-    if (actual >= nPerm || numX + numEq >= threshold) break;
-    const int nb = std::min(B, nPerm - actual);
-    std::memcpy(states.data(), s0, sizeof(s0));
-    for (int p = 0; p < nb; ++p) mat31_apply(c->jump.data(), &states[(size_t)31 * p], &states[(size_t)31 * (p + 1)]);
-    HIP_TRY(c, hipMemcpyAsync(c->d_perm_states, states.data(), sizeof(uint32_t) * 31 * (size_t)nb,
-                              hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(perm_init_kernel, dim3(2048), dim3(256), 0, st, c->d_perm_idx, (long long)N, B);
-    hipLaunchKernelGGL(perm_fisher_yates_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st,
-                       c->d_perm_states, c->d_perm_idx, (long long)N, B);
-    for (int p = 0; p < nb; ++p) {  // the shuffles are cumulative: apply them in order
-      hipLaunchKernelGGL(perm_apply_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_perm_idx, cur,
-                         nxt, c->d_perm_R, (long long)N, B, p);
-      std::swap(cur, nxt);
-    }
-    if (N <= 2048) {  // few samples: sums in sample order, so that exact ties with the observed Q resolve as in the reference
-      hipLaunchKernelGGL(perm_dot_sequential_kernel, dim3((unsigned)(((long long)nb * m + 255) / 256)), dim3(256), 0, st,
-                         c->d_perm_R, c->d_Gp, (long long)N, (long long)ld, nb, m, B, c->d_perm_C);
-    } else {  // C (nb x m) = Rp' G with Rp = the chunk's permuted residuals as columns (N x nb): integer-plane product
-      int rcg = gemm_tn_planes(c, c->d_perm_R, N, nb, c->d_Gp, ld, m, N, c->d_perm_C, B, st);
-      if (rcg) return rcg;
-    }
-    hipLaunchKernelGGL(perm_q_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, c->d_perm_C, d_bw, B, m,
-                       c->d_perm_Q);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(Q.data(), c->d_perm_Q, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, sync_stream(st));
-    int used = 0;
-    for (; used < nb; ++used) {
-      if (actual >= nPerm || numX + numEq >= threshold) {
-        more = false;
-        break;
-      }
-      ++actual;  // Permutation::add
-      if (Q[used] > obs) ++numX;
-      if (Q[used] == obs) ++numEq;
-    }
-    std::memcpy(s0, &states[(size_t)31 * used], sizeof(s0));  // the stream continues after the shuffles performed
-    if (used < nb) {
-      // the residual vector of the next gene restarts from res anyway; nothing else carries over
-      more = false;
-    }
-  }
-  std::memcpy(c->rand_state, s0, sizeof(s0));
+  rc = exact_permutations(
+      c, c->d_res, nPerm, prm.skat_alpha, r->skat_Q, m,
+      [&](int nb, int B, const double** d_out) -> int {
+        if (N <= 2048) {  // few samples: sums in sample order, so that exact ties with the observed Q resolve as in the reference
+          hipLaunchKernelGGL(perm_dot_sequential_kernel, dim3((unsigned)(((long long)nb * m + 255) / 256)), dim3(256), 0, st,
+                             c->d_perm_R, c->d_Gp, (long long)N, (long long)ld, nb, m, B, c->d_perm_C);
+        } else {  // C (nb x m) = Rp' G with Rp = the chunk's permuted residuals as columns (N x nb): integer-plane product
+          int rcg = gemm_tn_planes(c, c->d_perm_R, N, nb, c->d_Gp, ld, m, N, c->d_perm_C, B, st);
+          if (rcg) return rcg;
+        }
+        hipLaunchKernelGGL(perm_q_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, c->d_perm_C, d_bw, B, m,
+                           c->d_perm_Q);
+        *d_out = c->d_perm_Q;
+        return RVT_OK;
+      },
+      &actual, &numX, &numEq);
+  if (rc) return rc;
   r->perm_ok = 1;
   r->perm_num_perm = nPerm;
   r->perm_actual_perm = actual;
@@ -408,7 +442,268 @@ int kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std:
   return RVT_OK;
 }
 
+// Price's variable-threshold test (VariableThresholdPrice::fit, src/Model.h:1752-1805) of one gene; kernels and the form of
+// the statistic: vtprice_kernels.hip.h.  d_y: the phenotype on the device — centred (centerVector, src/LinearAlgebra.h:43-49)
+// for a quantitative trait, the 0 / 1 values themselves for a binary one, ybar then being their mean.
+// af[j] is taken as the frequency of column j of the FLIPPED, POLYMORPHIC block, as the reference's groupFrequency pairs
+// them (and as rvt_kbac_blocks does).
+int vtprice_stage(rvt_ctx* c, const double* dG, int M, const double* af, const double* d_y, double ybar, int nPerm, double alpha,
+                  rvt_vtprice_result* r) {
+  std::memset(r, 0, sizeof(*r));
+  r->num_perm = nPerm;  // what Permutation holds after reset() (src/Permutation.h:99-105)
+  r->perm_pvalue = 1.0;
+  r->opt_freq = r->zmax = -1.0;
+  const int64_t N = c->nc.N, ld = c->nc.ld;
+  hipStream_t st = c->stream;
+  // ---- flipped, polymorphic block (dc->getFlippedToMinorPolymorphicGenotype()) ---------------------------------------
+  std::vector<const double*> cols(M);
+  for (int j = 0; j < M; ++j) cols[j] = dG + (size_t)j * ld;
+  DevBuf<const double*> d_cols;
+  DevBuf<int> d_flags;
+  HIP_TRY(c, d_cols.alloc(sizeof(double*) * (size_t)M * 2));
+  HIP_TRY(c, d_flags.alloc(sizeof(int) * (size_t)M * 2));
+  HIP_TRY(c, hipMemcpyAsync(d_cols, cols.data(), sizeof(double*) * M, hipMemcpyHostToDevice, st));
+  k_fam_colstat(dim3((unsigned)M), st, d_cols, (long long)N, d_flags);
+  std::vector<int> flags(M);
+  HIP_TRY(c, hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * M, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  std::vector<const double*> kc;
+  std::vector<int> kf;
+  for (int j = 0; j < M; ++j)
+    if (flags[j] & 2) {
+      kc.push_back(cols[j]);
+      kf.push_back(flags[j] & 1);
+    }
+  const int m = (int)kc.size();
+  r->n_poly = m;
+  if (m == 0) return RVT_OK;  // genotype.cols == 0: fitOK = false before anything is drawn (src/Model.h:1758-1761)
+  int rc = ensure_fam_cols(c, (size_t)m, ld);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(d_cols + M, kc.data(), sizeof(double*) * m, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_flags + M, kf.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+  k_fam_flip_compact(dim3(64, (unsigned)m), st, d_cols + M, d_flags + M, (long long)N, (long long)ld, c->d_Gp);
+  // ---- frequency groups, ascending and cumulative (groupFrequency, src/Model.cpp:254-261; :311-338) ---------------------
+  std::map<double, std::vector<int>> fg;
+  for (int j = 0; j < m; ++j) fg[std::ceil(1000000. * af[j]) / 1000000].push_back(j);
+  const int T = (int)fg.size();
+  std::vector<double> freq;
+  std::vector<int> tab((size_t)3 * m);  // order | grp | gend
+  int *order = tab.data(), *grp = order + m, *gend = grp + m;
+  {
+    int k = 0;
+    for (const auto& kv : fg) {
+      for (int j : kv.second) {
+        order[k] = j;
+        grp[k] = (int)freq.size();
+        gend[k++] = 0;
+      }
+      gend[k - 1] = 1;
+      freq.push_back(kv.first);
+    }
+  }
+  r->n_threshold = T;
+  Layout L;
+  const size_t o_tab = L.take(sizeof(int) * 3 * (size_t)m), o_cnt = L.take(sizeof(int) * (size_t)m),
+               o_stat = L.take(sizeof(unsigned long long) * 2 * (size_t)T), o_off = L.take(sizeof(long long) * (size_t)m),
+               o_segoff = L.take(sizeof(int) * ((size_t)T + 1)), o_sd = L.take(sizeof(double) * 2 * (size_t)T),
+               o_obs = L.take(sizeof(double) + sizeof(int));
+  HIP_TRY(c, c->d_vtp_ws.grow(L.total, L.total + L.total / 2, st, true));
+  char* ws = c->d_vtp_ws;
+  int* d_tab = (int*)(ws + o_tab);
+  int* d_cnt = (int*)(ws + o_cnt);
+  unsigned long long* d_stat = (unsigned long long*)(ws + o_stat);
+  long long* d_off = (long long*)(ws + o_off);
+  int* d_segoff = (int*)(ws + o_segoff);
+  double* d_sd = (double*)(ws + o_sd);  // sd | shift
+  double* d_obs = (double*)(ws + o_obs);
+  HIP_TRY(c, hipMemcpyAsync(d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(d_stat, 0, sizeof(unsigned long long) * 2 * (size_t)T, st));
+  hipLaunchKernelGGL(vtp_count_kernel, dim3((unsigned)m), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, d_cnt);
+  hipLaunchKernelGGL(vtp_rowstat_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld,
+                     m, d_tab, d_tab + m, d_tab + 2 * m, T, d_stat);
+  HIP_TRY(c, hipGetLastError());
+  std::vector<int> cnt(m);
+  std::vector<unsigned long long> stat((size_t)2 * T);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(stat.data(), d_stat, sizeof(unsigned long long) * stat.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  // ---- the carrier list in group order, cut into segments that stay inside one group ------------------------------------
+  std::vector<long long> off(m), goff((size_t)T + 1, 0);
+  long long nnz = 0;
+  for (int k = 0; k < m; ++k) {
+    off[order[k]] = nnz;
+    nnz += cnt[order[k]];
+    goff[grp[k] + 1] = nnz;
+  }
+  if (nnz > 0x7fffffffLL) return fail(c, RVT_E_INVALID, "variable-threshold test: %lld carrier entries", nnz);
+  r->n_carrier_entries = nnz;
+  const int seglen = (int)std::min<long long>(4096, std::max<long long>(64, (nnz / 512 + 63) / 64 * 64));  // (a function of the gene alone)
+  std::vector<int2> segs;
+  std::vector<int> segoff((size_t)T + 1, 0);
+  std::vector<double> sds((size_t)2 * T);  // sd | shift
+  unsigned long long S1 = 0, S2 = 0;
+  for (int t = 0; t < T; ++t) {
+    if (goff[t + 1] - goff[t] != (long long)stat[t])
+      return fail(c, RVT_E_STATE, "variable-threshold test: group %d holds %lld carriers, the sample pass counted %llu", t,
+                  goff[t + 1] - goff[t], stat[t]);
+    for (long long e = goff[t]; e < goff[t + 1]; e += seglen)
+      segs.push_back(make_int2((int)e, (int)std::min<long long>(e + seglen, goff[t + 1])));
+    segoff[t + 1] = (int)segs.size();
+    S1 += stat[t];
+    S2 += stat[T + t];
+    // sum (b - mean)^2 / N = (N sum b^2 - (sum b)^2) / N^2, the numerator an exact integer: zero exactly when the row is
+    // constant, where the reference leaves z undivided (src/Model.h:1865-1868)
+    const unsigned __int128 num = (unsigned __int128)(unsigned long long)N * S2 - (unsigned __int128)S1 * S1;
+    sds[t] = std::sqrt((double)num / ((double)N * (double)N));
+    sds[T + t] = ybar * (double)S1;
+  }
+  const int nseg = (int)segs.size();
+  Layout E;
+  const size_t o_ent = E.take(sizeof(uint32_t) * (size_t)std::max<long long>(nnz, 1)),
+               o_segs = E.take(sizeof(int2) * (size_t)std::max(nseg, 1));
+  HIP_TRY(c, c->d_vtp_ent.grow(E.total, E.total + E.total / 2, st, true));
+  uint32_t* d_ent = (uint32_t*)(c->d_vtp_ent.get() + o_ent);
+  int2* d_segs = (int2*)(c->d_vtp_ent.get() + o_segs);
+  HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), sizeof(long long) * m, hipMemcpyHostToDevice, st));
+  if (nseg) {
+    HIP_TRY(c, hipMemcpyAsync(d_segs, segs.data(), sizeof(int2) * (size_t)nseg, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(d_segoff, segoff.data(), sizeof(int) * segoff.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_sd, sds.data(), sizeof(double) * sds.size(), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(vtp_fill_kernel, dim3((unsigned)m), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, d_off, d_cnt, d_ent);
+  // ---- observed statistic: the same two kernels, no shuffle --------------------------------------------------------------
+  constexpr int kChunk = 2048;
+  const int B = c->perm_exact ? exact_chunk(nPerm, N) : kChunk;  // shuffles whose partial sums d_vtp_part holds
+  {
+    const size_t need = sizeof(double) * (size_t)std::max(nseg, 1) * (size_t)B;
+    HIP_TRY(c, c->d_vtp_part.grow(need, need + need / 4, st, true));
+    HIP_TRY(c, c->d_vtp_z.grow(sizeof(double) * kChunk, sizeof(double) * kChunk, st, true));
+  }
+  if (nseg)
+    hipLaunchKernelGGL((vtp_segsum_kernel<kVtpIdentity>), dim3((unsigned)nseg, 1), dim3(64), 0, st, d_ent, d_segs, d_y, (long long)N,
+                       0ull, 0ull, 0u, 1, c->d_vtp_part);
+  hipLaunchKernelGGL(vtp_finish_kernel, dim3(1), dim3(64), 0, st, c->d_vtp_part, d_segoff, T, 1, d_sd, d_sd + T, d_obs,
+                     (int*)(d_obs + 1));
+  HIP_TRY(c, hipGetLastError());
+  struct {
+    double z;
+    int t;
+  } ob;
+  HIP_TRY(c, hipMemcpyAsync(&ob, d_obs, sizeof(double) + sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  const double obs = ob.z;  // perm.init(fabs(zmax)): already an absolute value
+  r->zmax = obs;
+  r->opt_freq = freq[ob.t];
+  // Permutation::init — `threshold` is an INT member of the reference's class (src/Permutation.h:153): the product is truncated
+  const double threshold = (double)(int)(1.0 * nPerm * alpha * 2);
+  int actual = 0, numX = 0, numEq = 0;
+  std::vector<double> Z(kChunk);
+  auto launch_statistics = [&](int srcKind, const double* src, unsigned shuffle0, int nb, uint64_t key) {
+    if (nseg) {
+      const dim3 grid((unsigned)nseg, (unsigned)((nb + 63) / 64));
+      if (srcKind == kVtpCounter)
+        hipLaunchKernelGGL((vtp_segsum_kernel<kVtpCounter>), grid, dim3(64), 0, st, d_ent, d_segs, src, (long long)N,
+                           (unsigned long long)c->perm_seed, (unsigned long long)key, shuffle0, nb, c->d_vtp_part);
+      else
+        hipLaunchKernelGGL((vtp_segsum_kernel<kVtpMatrix>), grid, dim3(64), 0, st, d_ent, d_segs, src, (long long)N, 0ull, 0ull,
+                           0u, nb, c->d_vtp_part);
+    }
+    hipLaunchKernelGGL(vtp_finish_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, c->d_vtp_part, d_segoff, T, nb, d_sd,
+                       d_sd + T, c->d_vtp_z, (int*)nullptr);
+  };
+  auto statistics = [&](int srcKind, const double* src, unsigned shuffle0, int nb, uint64_t key) -> int {
+    launch_statistics(srcKind, src, shuffle0, nb, key);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(Z.data(), c->d_vtp_z, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    return RVT_OK;
+  };
+  auto finish = [&]() {
+    r->fit_ok = 1;
+    r->actual_perm = actual;
+    r->num_greater = numX;
+    r->num_equal = numEq;
+    r->perm_pvalue = actual == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEq) / actual;
+    return RVT_OK;
+  };
+  if (!c->perm_exact) {
+    // ---- counter-based shuffles (perm_counter.h): keyed by a hash of the gene's frequencies, so that a gene draws the same
+    // shuffles wherever and whenever it runs (the call carries no gene ids)
+    uint64_t key = 0xcbf29ce484222325ull;  // FNV-1a over M and the bytes of af
+    auto mix = [&](const void* p, size_t n) {
+      for (size_t i = 0; i < n; ++i) key = (key ^ ((const unsigned char*)p)[i]) * 0x100000001b3ull;
+    };
+    mix(&M, sizeof(M));
+    mix(af, sizeof(double) * (size_t)M);
+    bool more = true;
+    while (more) {
+      if (actual >= nPerm || numX + numEq >= threshold) break;  // Permutation::next() before every shuffle
+      // the first chunk is short: a gene far from significance stops after ~2 threshold shuffles
+      const int want = actual == 0 ? std::min<int>(kChunk, (int)std::max(64.0, 2.5 * threshold)) : kChunk;
+      const int nb = std::min(want, nPerm - actual);
+      rc = statistics(kVtpCounter, d_y, (unsigned)actual, nb, key);
+      if (rc) return rc;
+      for (int u = 0; u < nb; ++u) {
+        if (actual >= nPerm || numX + numEq >= threshold) {
+          more = false;
+          break;
+        }
+        ++actual;  // Permutation::add
+        if (Z[u] > obs) ++numX;
+        if (Z[u] == obs) ++numEq;
+      }
+    }
+    return finish();
+  }
+  // ---- exact mode: the reference's rand() stream, N - 1 draws per shuffle, cumulative shuffles of the phenotype -------------
+  rc = exact_permutations(
+      c, d_y, nPerm, alpha, obs, 0,
+      [&](int nb, int, const double** d_out) -> int {
+        launch_statistics(kVtpMatrix, c->d_perm_R, 0u, nb, 0);
+        *d_out = c->d_vtp_z;
+        return RVT_OK;
+      },
+      &actual, &numX, &numEq);
+  if (rc) return rc;
+  return finish();
+}
+
 }  // namespace
+
+// ---- --vt price: Price's variable-threshold permutation test of device-resident blocks -------------------------------------
+int rvt_vtprice_blocks(rvt_ctx* c, int n, const double* const* dG, const int* M, const double* af, const double* y, int nperm,
+                       double alpha, rvt_vtprice_result* out) {
+  if (!c || n < 0 || (n > 0 && (!dG || !M || !af || !y || !out)) || nperm < 0) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set (it defines the sample count)");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  const int64_t N = c->nc.N;
+  // copyPhenotype + centerVector (src/LinearAlgebra.h:43-49): the mean as Vector::Average forms it, in sample order.  A 0 / 1
+  // phenotype stays as it is: its sums over carriers are then exact integers and the mean enters once, in vtp_finish_kernel.
+  bool binary = true;
+  double sum = 0.0;
+  for (int64_t i = 0; i < N; ++i) {
+    binary = binary && (y[i] == 0.0 || y[i] == 1.0);
+    sum += y[i];
+  }
+  const double avg = sum / (double)N;
+  std::vector<double> yv(y, y + N);
+  if (!binary)
+    for (int64_t i = 0; i < N; ++i) yv[i] -= avg;
+  DevBuf<double> d_y;
+  HIP_TRY(c, d_y.alloc(sizeof(double) * (size_t)N));
+  HIP_TRY(c, hipMemcpyAsync(d_y, yv.data(), sizeof(double) * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, sync_stream(c->stream));
+  size_t afo = 0;
+  for (int g = 0; g < n; ++g) {  // one gene at a time: the random stream is consumed in gene order
+    if (M[g] < 1 || M[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_INVALID, "gene %d has M=%d", g, M[g]);
+    rc = vtprice_stage(c, dG[g], M[g], af + afo, d_y, binary ? avg : 0.0, nperm, alpha, out + g);
+    if (rc) return rc;
+    afo += (size_t)M[g];
+  }
+  return RVT_OK;
+}
 
 // (kbac_stage for rvt_meta.hip's rvt_kbac_blocks)
 int rvt_kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std::vector<unsigned char>& y, int nPerm,

@@ -352,6 +352,12 @@ class KbacResult(C.Structure):
                 ("pvalue", C.c_double)]
 
 
+class VtPriceResult(C.Structure):
+    _fields_ = [("fit_ok", C.c_int), ("n_poly", C.c_int), ("n_threshold", C.c_int), ("n_carrier_entries", C.c_int64),
+                ("opt_freq", C.c_double), ("zmax", C.c_double), ("num_perm", C.c_int), ("actual_perm", C.c_int),
+                ("num_greater", C.c_int), ("num_equal", C.c_int), ("perm_pvalue", C.c_double)]
+
+
 class DecomposeInfo(C.Structure):
     _fields_ = [("sweeps", C.c_int), ("max_cosine", C.c_double), ("padded_order", C.c_int64), ("shift", C.c_double),
                 ("max_residual", C.c_double)]
@@ -649,6 +655,22 @@ class Engine:
         self.L.rvt_kbac_blocks.restype = C.c_int
         self._check(self.L.rvt_kbac_blocks(self.ctx, n, arr_p, arr_m.ctypes.data_as(c_int_p), _dp(af), _dp(y), int(nperm),
                                            C.c_double(alpha), out))
+        return list(out)
+
+    def vtprice_blocks(self, ptrs, Ms, afs, y, nperm=10000, alpha=0.05):
+        """Price's variable-threshold permutation test of device-resident blocks (rvt_vtprice_blocks); afs: list of per-gene
+        frequency arrays, y: the phenotype (quantitative or 0 / 1)."""
+        n = len(ptrs)
+        arr_p = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in ptrs])
+        arr_m = np.ascontiguousarray(Ms, dtype=np.int32)
+        af = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64) for a in afs]))
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        out = (VtPriceResult * n)()
+        self.L.rvt_vtprice_blocks.restype = C.c_int
+        self.L.rvt_vtprice_blocks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, c_int_p, c_double_p, c_double_p, C.c_int,
+                                              C.c_double, C.c_void_p]
+        self._check(self.L.rvt_vtprice_blocks(self.ctx, n, arr_p, arr_m.ctypes.data_as(c_int_p), _dp(af), _dp(y), int(nperm),
+                                              C.c_double(alpha), out))
         return list(out)
 
     def kinship_decompose(self, K, install=False, want_vectors=True):
