@@ -632,6 +632,49 @@ typedef struct rvt_vtprice_result {
 int rvt_vtprice_blocks(rvt_ctx* ctx, int n, const double* const* dG, const int* M, const double* af, const double* y,
                        int nperm, double alpha, rvt_vtprice_result* out);
 
+/* ---- the permutation burden tests for case-control data: --burden rarecover[nPerm=10000,alpha=0.05] (RareCoverTest
+ * src/Model.h:1419-1590) and --burden mb[nPerm=10000,alpha=0.05] (MadsonBrowningTest src/Model.h:1244-1340 over
+ * madsonBrowningCollapse / getMarkerFrequencyFromControl src/Model.cpp:47-66,155-175 and the two-argument
+ * LogisticRegressionScoreTest::TestCovariate regression/LogisticRegressionScoreTest.cpp:310-373; Permutation
+ * src/Permutation.h:48-158) --------------------------------------------------------------------------------------------------
+ * Calling shape of rvt_vtprice_blocks without af: the device holds the fp64 blocks, a null model must be set (it defines N),
+ * y = the host phenotype, genes run one at a time in call order.  y must be 0 / 1 with both classes present, else every record
+ * has fit_ok = 0 and nothing is drawn; a gene without polymorphic column draws nothing either.  Exact mode (default) replays the
+ * reference's cumulative Fisher-Yates shuffles on the emulated rand() stream (N - 1 draws per shuffle); rvt_set_perm_exact(ctx,
+ * 0) keys the shuffles by (seed, FNV-1a hash of n_poly and the per-column carrier / entry counts, shuffle index): the same record
+ * in any gene order on any context.  Stop rule: Permutation's, threshold (int)(2 nperm alpha).
+ * RareCover: a sample carries a column of the flipped, polymorphic block when g > 0 (a mean-imputed 0.37 IS a carrier, unlike in
+ * rvt_vtprice_blocks); the statistic is the greedy cover's largest correlation, computed from exact integer counts in the
+ * reference's expression order — bit-identical to the reference's fp64 evaluation, so NumGreater / NumEqual are exact.
+ * Madsen-Browning: per shuffle the columns are weighted by 1 / sqrt(f (1 - f) N), f = (allele count of the controls + 1) /
+ * (2 controls + 2) (a column with f outside (0, 1) is skipped), and stat = U^2 / V of the two-argument TestCovariate.  The
+ * OBSERVED statistic is the binary score test of the installed null model (covariates included) on the observed collapsed
+ * column, as TestCovariate(cov, pheno, collapsed) intends: the null model must be a binary one
+ * (rvt_fit_null / rvt_set_null with RVT_TRAIT_BINARY), else fit_ok = 0.  A permuted statistic below zero (impossible for valid
+ * input) is drawn but not added; the eleventh fails the gene, as in the reference.
+ * The rvt_group_* layer does not carry these tests. */
+typedef struct rvt_rarecover_result {
+  int fit_ok;     /* 0: no polymorphic column or no 0 / 1 phenotype (the other fields as after Permutation::reset; stat = -1) */
+  int n_poly;     /* columns after flip-to-minor + monomorphic removal */
+  int n_carrier;  /* samples that carry at least one column */
+  int n_selected; /* NumIncludeMarker: columns the observed greedy cover selected */
+  double stat;    /* observed statistic (the permutation test's Stat) */
+  int num_perm, actual_perm, num_greater, num_equal;
+  double perm_pvalue; /* (NumGreater + NumEqual / 2) / ActualPerm, 1 when no shuffle ran */
+} rvt_rarecover_result;
+int rvt_rarecover_blocks(rvt_ctx* ctx, int n, const double* const* dG, const int* M, const double* y, int nperm, double alpha,
+                         rvt_rarecover_result* out);
+typedef struct rvt_mb_result {
+  int fit_ok;        /* 0: no polymorphic column, no 0 / 1 phenotype, no binary null model, or a failed score test */
+  int n_poly;        /* columns after flip-to-minor + monomorphic removal */
+  int64_t n_entries; /* non-zero genotype entries of those columns */
+  double stat;       /* observed score statistic (the permutation test's Stat) */
+  int num_perm, actual_perm, num_greater, num_equal;
+  double perm_pvalue;
+} rvt_mb_result;
+int rvt_mb_blocks(rvt_ctx* ctx, int n, const double* const* dG, const int* M, const double* y, int nperm, double alpha,
+                  rvt_mb_result* out);
+
 /* ---- raw / packed genotypes at the boundary (SURVEY §8f "next" #1) --------------------------------------------------
  * Like rvt_submit_gene, but the block is what the genotype extractor produced, BEFORE DataConsolidator::consolidate:
  * missing genotypes are negative (-9, libVcf/VCFConstant.h:4).  The device then does what consolidate() does to the

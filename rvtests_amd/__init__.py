@@ -9,8 +9,9 @@ CPU fallback: if the HIP library is missing or there is no GPU, construction fai
 """
 from .engine import (Engine, Group, GeneResult, Params, Timing, RvtError, build_library, library_path, load_library,
                      TEST_SKAT, TEST_SKATO, TEST_CMC, TEST_ZEGGINI, TEST_ALL, TEST_ANALYTICVT, TRAIT_QUANTITATIVE,
-                     TRAIT_BINARY, MAX_INFLIGHT, KbacResult, DecomposeInfo, VtPriceResult)
+                     TRAIT_BINARY, MAX_INFLIGHT, KbacResult, DecomposeInfo, VtPriceResult, RareCoverResult,
+                     MbResult)
 
 __all__ = ["Engine", "Group", "GeneResult", "Params", "Timing", "RvtError", "build_library", "library_path", "load_library",
            "TEST_SKAT", "TEST_SKATO", "TEST_CMC", "TEST_ZEGGINI", "TEST_ALL", "TEST_ANALYTICVT", "TRAIT_QUANTITATIVE",
-           "TRAIT_BINARY", "MAX_INFLIGHT", "KbacResult", "DecomposeInfo", "VtPriceResult"]
+           "TRAIT_BINARY", "MAX_INFLIGHT", "KbacResult", "DecomposeInfo", "VtPriceResult", "RareCoverResult", "MbResult"]

@@ -680,6 +680,118 @@ void VariableThresholdPrice::writeOutput(TextSink* fp, const SiteInfo& siteInfo)
             "\n");
 }
 
+// ---- RareCoverTest / MadsonBrowningTest -----------------------------------------------------------------------------------------
+namespace {
+// Permutation::updateValue + Result::writeValue: ints via toString, doubles via floatToString (src/Result.h:52-63); getPvalue :95-98
+std::string permutationFields(int nPerm, int actualPerm, double obs, int numX, int numEqual) {
+  const double p = actualPerm == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEqual) / actualPerm;
+  return std::to_string(nPerm) + "\t" + std::to_string(actualPerm) + "\t" + floatToString(obs) + "\t" + std::to_string(numX) + "\t" +
+         std::to_string(numEqual) + "\t" + floatToString(p);
+}
+const char* const kPermutationHeader = "NumPerm\tActualPerm\tStat\tNumGreater\tNumEqual\tPermPvalue";
+}  // namespace
+
+RareCoverTest::RareCoverTest(int nPerm_, double alpha_) : nPerm(nPerm_), alpha(alpha_) { modelName = "RareCover"; }
+void RareCoverTest::reset() {  // src/Model.h:1477-1480 over Permutation::reset (src/Permutation.h:99-105)
+  obs = 0.0;
+  actualPerm = numX = numEqual = 0;
+}
+int RareCoverTest::fit(GeneData* dc) {
+  fitOK = false;
+  if (!isBinaryOutcome()) {  // src/Model.h:1432-1438
+    lastError = "Rarecover test does not support continuous outcomes. Results will be all NAs.";
+    return -1;
+  }
+  if (dc->ncov != 0) {  // src/Model.h:1439-1445
+    lastError = "Rarecover test does not support covariates. Results will be all NAs.";
+    return -1;
+  }
+  rvt_ctx* ctx = GpuBroker::instance().contextWithNull(*dc, true, &lastError);  // (the null model defines N on the device)
+  if (!ctx) return -1;
+  double* block = nullptr;
+  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
+    lastError = rvt_last_error(ctx);
+    if (block) rvt_block_free(ctx, block);
+    return -1;
+  }
+  const double* bp = block;
+  const int M = dc->M;
+  const int rc = rvt_rarecover_blocks(ctx, 1, &bp, &M, dc->phenotype, nPerm, alpha, &rec);
+  rvt_block_free(ctx, block);
+  if (rc) {
+    lastError = rvt_last_error(ctx);
+    return -1;
+  }
+  fitOK = rec.fit_ok != 0;
+  if (!fitOK) return -1;  // genotype.cols == 0: perm.init was not reached (src/Model.h:1448-1451)
+  numSelected = rec.n_selected;
+  obs = rec.stat;
+  actualPerm = rec.actual_perm;
+  numX = rec.num_greater;
+  numEqual = rec.num_equal;
+  return 0;
+}
+void RareCoverTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab());
+  fp->write(std::string("NumIncludeMarker\t") + kPermutationHeader + "\n");
+}
+void RareCoverTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.valueTab());
+  fp->write((fitOK ? std::to_string(numSelected) : std::string("NA")) + "\t" + permutationFields(nPerm, actualPerm, obs, numX, numEqual) +
+            "\n");
+}
+
+MadsonBrowningTest::MadsonBrowningTest(int nPerm_, double alpha_) : nPerm(nPerm_), alpha(alpha_) { modelName = "MadsonBrowning"; }
+void MadsonBrowningTest::reset() {  // src/Model.h:1306-1309
+  obs = 0.0;
+  actualPerm = numX = numEqual = 0;
+}
+int MadsonBrowningTest::fit(GeneData* dc) {
+  fitOK = false;
+  if (!isBinaryOutcome()) {  // src/Model.h:1257-1263
+    lastError = "Madsen-Browning test does not support continuous outcomes. Results will be all NAs.";
+    return -1;
+  }
+  rvt_ctx* ctx = GpuBroker::instance().contextWithNull(*dc, true, &lastError);  // the logistic null model, covariates included
+  if (!ctx) return -1;
+  double* block = nullptr;
+  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
+    lastError = rvt_last_error(ctx);
+    if (block) rvt_block_free(ctx, block);
+    return -1;
+  }
+  const double* bp = block;
+  const int M = dc->M;
+  const int rc = rvt_mb_blocks(ctx, 1, &bp, &M, dc->phenotype, nPerm, alpha, &rec);
+  rvt_block_free(ctx, block);
+  if (rc) {
+    lastError = rvt_last_error(ctx);
+    return -1;
+  }
+  if (rec.n_poly == 0 || (!rec.fit_ok && rec.actual_perm == 0 && rec.stat == 0.0)) return -1;  // perm.init was not reached
+  fitOK = rec.fit_ok != 0;  // (0 here: the eleventh failed shuffle — the counters printed are those reached)
+  obs = rec.stat;
+  actualPerm = rec.actual_perm;
+  numX = rec.num_greater;
+  numEqual = rec.num_equal;
+  return fitOK ? 0 : -1;
+}
+void MadsonBrowningTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab());
+  if (isBinaryOutcome())
+    fp->write(kPermutationHeader);  // perm.writeHeader: no line end of its own
+  else
+    fp->write("Pvalue\n");
+  fp->write("\n");  // (src/Model.h:1319: after "Pvalue\n" this leaves an empty line under the header)
+}
+void MadsonBrowningTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.valueTab());
+  if (isBinaryOutcome())
+    fp->write(permutationFields(nPerm, actualPerm, obs, numX, numEqual) + "\n");
+  else
+    fp->write("NA\n");
+}
+
 // ---- FamSkatTest ----------------------------------------------------------------------------------------------------------
 FamSkatTest::FamSkatTest(double, double) {
   modelName = "FamSkat";
@@ -1490,7 +1602,13 @@ int ModelManager::create(const std::string& type, const std::string& modelList) 
         model.push_back(new FamBurdenTest(false));
       else if (modelName == "famzeggini")
         model.push_back(new FamBurdenTest(true));
-      else {
+      else if (modelName == "rarecover") {  // src/ModelManager.cpp:115-121
+        parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
+        model.push_back(new RareCoverTest(nPerm, alpha));
+      } else if (modelName == "mb") {  // src/ModelManager.cpp:104-110
+        parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
+        model.push_back(new MadsonBrowningTest(nPerm, alpha));
+      } else {
         lastError = "Unknown model name: " + modelName + " .";
         return -1;
       }

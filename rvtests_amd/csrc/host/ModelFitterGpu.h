@@ -353,6 +353,50 @@ class VariableThresholdPrice : public ModelFitter {
   rvt_vtprice_result rec{};
 };
 
+// `--burden rarecover[nPerm=10000,alpha=0.05]` (src/ModelManager.cpp:115-121; RareCoverTest, src/Model.h:1419-1590): the greedy
+// cover's largest genotype-phenotype correlation under shuffles of a 0 / 1 phenotype.  Columns: NumIncludeMarker (NA unless the
+// fit succeeded), then Permutation's six.  A quantitative trait or covariates fail the fit after a warning; the row still prints
+// (:1488-1497 has no fitOK test around the Permutation fields).  Synchronous: in exact mode the shuffles consume the process-wide
+// random stream gene by gene.
+class RareCoverTest : public ModelFitter {
+ public:
+  RareCoverTest(int nPerm, double alpha);
+  int fit(GeneData* dc) override;
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void reset() override;
+
+ private:
+  int nPerm;
+  double alpha;
+  bool fitOK = false;
+  int numSelected = 0;
+  // Permutation's members (src/Permutation.h:150-156) as its constructor leaves them; reset() zeroes all but numPerm
+  double obs = -1.0;
+  int actualPerm = -1, numX = -1, numEqual = -1;
+  rvt_rarecover_result rec{};
+};
+
+// `--burden mb[nPerm=10000,alpha=0.05]` (src/ModelManager.cpp:104-110; MadsonBrowningTest, src/Model.h:1244-1340).  Binary trait:
+// the header is Permutation's six names and one "\n", a row its six values and "\n" (no fitOK test); quantitative trait: the header
+// is "Pvalue\n" followed by a second "\n" — an empty line — and every row is "NA" (:1311-1331).  Synchronous, as RareCoverTest.
+class MadsonBrowningTest : public ModelFitter {
+ public:
+  MadsonBrowningTest(int nPerm, double alpha);
+  int fit(GeneData* dc) override;
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void reset() override;
+
+ private:
+  int nPerm;
+  double alpha;
+  bool fitOK = false;
+  double obs = -1.0;
+  int actualPerm = -1, numX = -1, numEqual = -1;
+  rvt_mb_result rec{};
+};
+
 // `--kernel famSkat[beta1:beta2]` (src/Model.h:3048-3145).  The reference ignores beta1 / beta2 for this model
 // (FamSkat.cpp:129-137 always uses Beta(1, 25)); so does this adapter.
 class FamSkatTest : public ModelFitter {

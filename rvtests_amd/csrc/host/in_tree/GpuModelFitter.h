@@ -129,6 +129,8 @@ typedef GpuModel<rvt_host::MetaCovTest> MetaCovTest;      // new MetaCovTest(win
 typedef GpuModel<rvt_host::MetaScoreTest> MetaScoreTest;  // new MetaScoreTest()
 typedef GpuModel<rvt_host::KbacTest> KBACTest;            // new KBACTest(nPerm, alpha)
 typedef GpuModel<rvt_host::VariableThresholdPrice> VariableThresholdPrice;  // new VariableThresholdPrice(nPerm, alpha)
+typedef GpuModel<rvt_host::RareCoverTest> RareCoverTest;            // new RareCoverTest(nPerm, alpha)       :115-121
+typedef GpuModel<rvt_host::MadsonBrowningTest> MadsonBrowningTest;  // new MadsonBrowningTest(nPerm, alpha)  :104-110
 typedef GpuModel<rvt_host::SingleVariantWaldTest> SingleVariantWaldTest;    // new SingleVariantWaldTest()   :54-98
 typedef GpuModel<rvt_host::SingleVariantScoreTest> SingleVariantScoreTest;  // new SingleVariantScoreTest()
 // the single-variant tests for related samples (src/ModelManager.cpp:63-84); familyModel = true as their constructors set it

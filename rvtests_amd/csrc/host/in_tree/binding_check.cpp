@@ -40,6 +40,12 @@ int rvt_binding_check(DataConsolidator* dc, FileWriter* fp, const Result& siteIn
   parser.parse("price[nPerm=200,alpha=0.1]");
   parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
   model.push_back(new rvt_intree::VariableThresholdPrice(nPerm, alpha));
+  parser.parse("rarecover[nPerm=200,alpha=0.1]");
+  parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
+  model.push_back(new rvt_intree::RareCoverTest(nPerm, alpha));
+  parser.parse("mb");
+  parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
+  model.push_back(new rvt_intree::MadsonBrowningTest(nPerm, alpha));
   int rc = 0;
   for (size_t m = 0; m < model.size(); ++m) {  // src/ModelManager.cpp:273-282, src/Main.cpp:1207-1256
     model[m]->setParameter(parser);

@@ -52,6 +52,7 @@ void k2_launch_classify(dim3 grid, hipStream_t st, const double* G, long long N,
 #include "rot_gemm.hip.h"
 #include "perm_kernels.hip.h"
 #include "vtprice_kernels.hip.h"
+#include "burdenperm_kernels.hip.h"
 #include "vcf_kernels.hip.h"
 #include "bgen_kernels.hip.h"
 #include "jacobi_kernels.hip.h"
@@ -339,6 +340,12 @@ struct rvt_ctx {
   // [segment][shuffle] of a chunk, the chunk's zmax
   DevBuf<char> d_vtp_ws, d_vtp_ent;
   DevBuf<double> d_vtp_part, d_vtp_z;
+  // RareCover and Madsen-Browning (burdenperm_kernels.hip.h; grow-only, sized per gene from N, K and the entry count): the gene's
+  // tables | its carrier numbering and bit matrix, or its entry list | c and Y of a chunk's shuffles when they do not fit the LDS |
+  // the partial sums [segment][shuffle] | the weights [column][shuffle] | the chunk's statistics
+  DevBuf<char> d_bp_ws, d_bp_ent;
+  DevBuf<unsigned long long> d_bp_cy;
+  DevBuf<double> d_bp_part, d_bp_w, d_bp_stat;
   uint32_t rand_state[31];
   int64_t jump_N = -1;                 // J = A^(jump_N - 1) is cached for this sample count
   std::vector<uint32_t> jump;          // 31 x 31, row-major

@@ -61,10 +61,12 @@ static int exact_chunk(int nPerm, int64_t N) {
 // N x nb) into its nb statistics and names the device array that holds them; they are compared with obs under
 // Permutation's stop rule (src/Permutation.h:69-98).  m: columns of d_perm_C that the caller's statistic needs (0: none).
 // On return the stream stands behind the shuffles PERFORMED, whatever the chunk generated beyond them.
+// failed_ (optional, Madsen-Browning's loop, src/Model.h:1286-1299): a statistic below zero is a failed TestCovariate — the
+// shuffle is drawn but not added; the eleventh ends the test with *failed_ = 11.
 extern "C++" {  // (this unit's functions sit inside extern "C"; a template cannot)
 template <class Stat>
 int exact_permutations(rvt_ctx* c, const double* d_start, int nPerm, double alpha, double obs, int m, Stat&& stat, int* actual_,
-                       int* numX_, int* numEq_) {
+                       int* numX_, int* numEq_, int* failed_ = nullptr) {
   const int64_t N = c->nc.N;
   hipStream_t st = c->stream;
   // chunk buffers
@@ -125,6 +127,16 @@ int exact_permutations(rvt_ctx* c, const double* d_start, int nPerm, double alph
     int used = 0;
     for (; used < nb; ++used) {
       if (actual >= nPerm || numX + numEq >= threshold) {
+        more = false;
+        break;
+      }
+      if (failed_ && Q[used] < 0) {
+        if (*failed_ < 10) {
+          ++*failed_;
+          continue;
+        }
+        *failed_ = 11;
+        ++used;  // (this shuffle was drawn too)
         more = false;
         break;
       }
@@ -668,6 +680,336 @@ int vtprice_stage(rvt_ctx* c, const double* dG, int M, const double* af, const d
   return finish();
 }
 
+
+// ---- the permutation burden tests for a 0 / 1 phenotype (burdenperm_kernels.hip.h) -----------------------------------------------
+// dc->getFlippedToMinorPolymorphicGenotype() of one gene into c->d_Gp (ld x *m_)
+static int flipped_poly_block(rvt_ctx* c, const double* dG, int M, int* m_) {
+  const int64_t N = c->nc.N, ld = c->nc.ld;
+  hipStream_t st = c->stream;
+  std::vector<const double*> cols(M);
+  for (int j = 0; j < M; ++j) cols[j] = dG + (size_t)j * ld;
+  DevBuf<const double*> d_cols;
+  DevBuf<int> d_flags;
+  HIP_TRY(c, d_cols.alloc(sizeof(double*) * (size_t)M * 2));
+  HIP_TRY(c, d_flags.alloc(sizeof(int) * (size_t)M * 2));
+  HIP_TRY(c, hipMemcpyAsync(d_cols, cols.data(), sizeof(double*) * M, hipMemcpyHostToDevice, st));
+  k_fam_colstat(dim3((unsigned)M), st, d_cols, (long long)N, d_flags);
+  std::vector<int> flags(M);
+  HIP_TRY(c, hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * M, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  std::vector<const double*> kc;
+  std::vector<int> kf;
+  for (int j = 0; j < M; ++j)
+    if (flags[j] & 2) {
+      kc.push_back(cols[j]);
+      kf.push_back(flags[j] & 1);
+    }
+  const int m = (int)kc.size();
+  *m_ = m;
+  if (m == 0) return RVT_OK;
+  int rc = ensure_fam_cols(c, (size_t)m, ld);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(d_cols + M, kc.data(), sizeof(double*) * m, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_flags + M, kf.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+  k_fam_flip_compact(dim3(64, (unsigned)m), st, d_cols + M, d_flags + M, (long long)N, (long long)ld, c->d_Gp);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, sync_stream(st));  // (d_cols / d_flags are freed on return)
+  return RVT_OK;
+}
+
+// the key of a gene's counter-based shuffles: FNV-1a over the polymorphic column count and the per-column entry counts
+static uint64_t burdenperm_key(int m, const std::vector<int>& cnt) {
+  uint64_t key = 0xcbf29ce484222325ull;
+  auto mix = [&](const void* p, size_t n) {
+    for (size_t i = 0; i < n; ++i) key = (key ^ ((const unsigned char*)p)[i]) * 0x100000001b3ull;
+  };
+  mix(&m, sizeof(m));
+  mix(cnt.data(), sizeof(int) * cnt.size());
+  return key;
+}
+
+constexpr int kBpChunk = 2048;  // shuffles per launch, both modes (exact_chunk() never exceeds it)
+
+// Permutation's loop over counter-based shuffles, a chunk at a time.  launch(shuffle0, nb) leaves the chunk's statistics in
+// c->d_bp_stat.  failed (optional): Madsen-Browning's rule for a statistic below zero, as in exact_permutations.
+extern "C++" {
+template <class Launch>
+int counter_permutations(rvt_ctx* c, int nPerm, double alpha, double obs, Launch&& launch, int* actual_, int* numX_, int* numEq_,
+                         int* failed_ = nullptr) {
+  hipStream_t st = c->stream;
+  // Permutation::init — `threshold` is an INT member of the reference's class (src/Permutation.h:153): the product is truncated
+  const double threshold = (double)(int)(1.0 * nPerm * alpha * 2);
+  int actual = 0, numX = 0, numEq = 0;
+  unsigned drawn = 0;  // shuffle indices consumed (a failed statistic consumes one without being added)
+  std::vector<double> Q(kBpChunk);
+  bool more = true;
+  while (more) {
+    if (actual >= nPerm || numX + numEq >= threshold) break;  // Permutation::next() before every shuffle
+    // the first chunk is short: a gene far from significance stops after ~2 threshold shuffles
+    const int want = actual == 0 ? std::min<int>(kBpChunk, (int)std::max(64.0, 2.5 * threshold)) : kBpChunk;
+    const int nb = std::min(want, nPerm - actual);
+    launch(drawn, nb);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(Q.data(), c->d_bp_stat, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    for (int u = 0; u < nb; ++u) {
+      if (actual >= nPerm || numX + numEq >= threshold) {
+        more = false;
+        break;
+      }
+      ++drawn;
+      if (failed_ && Q[u] < 0) {
+        if (*failed_ < 10) {
+          ++*failed_;
+          continue;
+        }
+        *failed_ = 11;
+        more = false;
+        break;
+      }
+      ++actual;  // Permutation::add
+      if (Q[u] > obs) ++numX;
+      if (Q[u] == obs) ++numEq;
+    }
+  }
+  *actual_ = actual, *numX_ = numX, *numEq_ = numEq;
+  return RVT_OK;
+}
+}  // extern "C++"
+
+// RareCover (RareCoverTest::fit, src/Model.h:1427-1476) of one gene.  d_y: the 0 / 1 phenotype on the device, cases: its sum,
+// valid: it is 0 / 1 with both classes present.
+int rarecover_stage(rvt_ctx* c, const double* dG, int M, const double* d_y, double cases, bool valid, int nPerm, double alpha,
+                    rvt_rarecover_result* r) {
+  std::memset(r, 0, sizeof(*r));
+  r->num_perm = nPerm;  // what Permutation holds after reset() (src/Permutation.h:99-105)
+  r->perm_pvalue = 1.0;
+  r->stat = -1.0;
+  const int64_t N = c->nc.N, ld = c->nc.ld;
+  hipStream_t st = c->stream;
+  int m = 0;
+  int rc = flipped_poly_block(c, dG, M, &m);
+  if (rc) return rc;
+  r->n_poly = m;
+  if (m == 0 || !valid) return RVT_OK;  // genotype.cols == 0: fitOK = false before anything is drawn (src/Model.h:1448-1451)
+  // ---- the carrier union and the bit matrix ----------------------------------------------------------------------------------
+  const int nblk = (int)((N + 255) / 256);
+  Layout L;
+  const size_t o_cnt = L.take(sizeof(int) * (size_t)m), o_bcnt = L.take(sizeof(int) * (size_t)nblk),
+               o_obs = L.take(sizeof(double) + sizeof(int));
+  HIP_TRY(c, c->d_bp_ws.grow(L.total, L.total + L.total / 2, st, true));
+  char* ws = c->d_bp_ws;
+  int* d_cnt = (int*)(ws + o_cnt);
+  int* d_bcnt = (int*)(ws + o_bcnt);
+  double* d_obs = (double*)(ws + o_obs);
+  hipLaunchKernelGGL((bp_count_kernel<kBpPositive>), dim3((unsigned)m), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, d_cnt);
+  hipLaunchKernelGGL(bp_union_count_kernel, dim3((unsigned)nblk), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, m, d_bcnt);
+  HIP_TRY(c, hipGetLastError());
+  std::vector<int> cnt(m), boff(nblk);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(boff.data(), d_bcnt, sizeof(int) * nblk, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  long long K = 0;
+  for (int b = 0; b < nblk; ++b) {
+    const int n = boff[b];
+    boff[b] = (int)K;
+    K += n;
+  }
+  r->n_carrier = (int)K;
+  const int W = (int)std::max<long long>(1, (K + 63) / 64);
+  Layout E;
+  const size_t o_samp = E.take(sizeof(uint32_t) * (size_t)std::max<long long>(K, 1)),
+               o_bits = E.take(sizeof(unsigned long long) * (size_t)m * W);
+  HIP_TRY(c, c->d_bp_ent.grow(E.total, E.total + E.total / 2, st, true));
+  uint32_t* d_samp = (uint32_t*)(c->d_bp_ent.get() + o_samp);
+  unsigned long long* d_bits = (unsigned long long*)(c->d_bp_ent.get() + o_bits);
+  HIP_TRY(c, hipMemcpyAsync(d_bcnt, boff.data(), sizeof(int) * nblk, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(d_bits, 0, sizeof(unsigned long long) * (size_t)m * W, st));
+  hipLaunchKernelGGL(bp_union_pack_kernel, dim3((unsigned)nblk), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, m, d_bcnt,
+                     (int)K, W, d_samp, d_bits);
+  // c and Y of a shuffle: 16 W bytes of LDS when they fit the 64 KB a launch may ask for, else a slot of a global work space
+  const size_t lds = sizeof(unsigned long long) * 2 * (size_t)W;
+  const bool in_lds = lds <= 64 * 1024;
+  unsigned long long* d_cy = nullptr;
+  if (!in_lds) {
+    const size_t need = lds * kBpChunk;
+    HIP_TRY(c, c->d_bp_cy.grow(need, need, st, true));
+    d_cy = c->d_bp_cy;
+  }
+  HIP_TRY(c, c->d_bp_stat.grow(sizeof(double) * kBpChunk, sizeof(double) * kBpChunk, st, true));
+  const unsigned dyn = in_lds ? (unsigned)lds : 0u;
+  // ---- observed statistic and NumIncludeMarker: the same kernel, no shuffle -----------------------------------------------------
+  hipLaunchKernelGGL((rc_cover_kernel<kBpIdentity>), dim3(1), dim3(kRcThreads), dyn, st, d_bits, d_samp, (int)K, W, m, d_y,
+                     (long long)N, cases, 0ull, 0ull, 0u, d_cy, d_obs, (int*)(d_obs + 1));
+  HIP_TRY(c, hipGetLastError());
+  struct {
+    double s;
+    int n;
+  } ob;
+  HIP_TRY(c, hipMemcpyAsync(&ob, d_obs, sizeof(double) + sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  const double obs = ob.s;
+  r->stat = obs;
+  r->n_selected = ob.n;
+  int actual = 0, numX = 0, numEq = 0;
+  if (!c->perm_exact) {
+    const uint64_t key = burdenperm_key(m, cnt);
+    rc = counter_permutations(
+        c, nPerm, alpha, obs,
+        [&](unsigned shuffle0, int nb) {
+          hipLaunchKernelGGL((rc_cover_kernel<kBpCounter>), dim3((unsigned)nb), dim3(kRcThreads), dyn, st, d_bits, d_samp, (int)K, W, m,
+                             d_y, (long long)N, cases, (unsigned long long)c->perm_seed, (unsigned long long)key, shuffle0, d_cy,
+                             c->d_bp_stat.get(), (int*)nullptr);
+        },
+        &actual, &numX, &numEq);
+  } else {
+    // exact mode: the reference's rand() stream, N - 1 draws per shuffle, cumulative shuffles of the phenotype
+    rc = exact_permutations(
+        c, d_y, nPerm, alpha, obs, 0,
+        [&](int nb, int, const double** d_out) -> int {
+          hipLaunchKernelGGL((rc_cover_kernel<kBpMatrix>), dim3((unsigned)nb), dim3(kRcThreads), dyn, st, d_bits, d_samp, (int)K, W, m,
+                             c->d_perm_R.get(), (long long)N, cases, 0ull, 0ull, 0u, d_cy, c->d_bp_stat.get(), (int*)nullptr);
+          *d_out = c->d_bp_stat;
+          return RVT_OK;
+        },
+        &actual, &numX, &numEq);
+  }
+  if (rc) return rc;
+  r->fit_ok = 1;
+  r->actual_perm = actual;
+  r->num_greater = numX;
+  r->num_equal = numEq;
+  r->perm_pvalue = actual == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEq) / actual;
+  return RVT_OK;
+}
+
+// Madsen-Browning (MadsonBrowningTest::fit, src/Model.h:1252-1305) of one gene; arguments as rarecover_stage.
+int mb_stage(rvt_ctx* c, const double* dG, int M, const double* d_y, double cases, bool valid, int nPerm, double alpha,
+             rvt_mb_result* r) {
+  std::memset(r, 0, sizeof(*r));
+  r->num_perm = nPerm;  // what Permutation holds after reset() (src/Permutation.h:99-105)
+  r->perm_pvalue = 1.0;
+  const int64_t N = c->nc.N, ld = c->nc.ld;
+  hipStream_t st = c->stream;
+  int m = 0;
+  int rc = flipped_poly_block(c, dG, M, &m);
+  if (rc) return rc;
+  r->n_poly = m;
+  if (m == 0 || !valid || !c->nc.binary) return RVT_OK;  // (a quantitative null model: the observed score test has no model)
+  // ---- the entry list, column by column in sample order, cut into segments -------------------------------------------------------
+  Layout L;
+  const size_t o_cnt = L.take(sizeof(int) * (size_t)m), o_off = L.take(sizeof(long long) * (size_t)m),
+               o_segoff = L.take(sizeof(int) * ((size_t)m + 1)), o_ac = L.take(sizeof(double) * (size_t)m),
+               o_K = L.take(sizeof(double) * (size_t)m * m), o_col = L.take(sizeof(double) * (size_t)std::max(c->null_ld, ld));
+  HIP_TRY(c, c->d_bp_ws.grow(L.total, L.total + L.total / 2, st, true));
+  char* ws = c->d_bp_ws;
+  int* d_cnt = (int*)(ws + o_cnt);
+  long long* d_off = (long long*)(ws + o_off);
+  int* d_segoff = (int*)(ws + o_segoff);
+  double* d_AC = (double*)(ws + o_ac);
+  double* d_K = (double*)(ws + o_K);
+  double* d_col = (double*)(ws + o_col);
+  hipLaunchKernelGGL((bp_count_kernel<kBpNonZero>), dim3((unsigned)m), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, d_cnt);
+  HIP_TRY(c, hipGetLastError());
+  std::vector<int> cnt(m);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  std::vector<long long> off(m);
+  long long nnz = 0;
+  for (int j = 0; j < m; ++j) {
+    off[j] = nnz;
+    nnz += cnt[j];
+  }
+  if (nnz > 0x7fffffffLL) return fail(c, RVT_E_INVALID, "Madsen-Browning test: %lld genotype entries", nnz);
+  r->n_entries = nnz;
+  const int seglen = (int)std::min<long long>(4096, std::max<long long>(64, (nnz / 512 + 63) / 64 * 64));  // (a function of the gene alone)
+  std::vector<int2> segs;
+  std::vector<int> segoff((size_t)m + 1, 0);
+  for (int j = 0; j < m; ++j) {
+    for (long long e = off[j]; e < off[j] + cnt[j]; e += seglen)
+      segs.push_back(make_int2((int)e, (int)std::min<long long>(e + seglen, off[j] + cnt[j])));
+    segoff[j + 1] = (int)segs.size();
+  }
+  const int nseg = (int)segs.size();
+  Layout E;
+  const size_t o_ent = E.take(sizeof(uint32_t) * (size_t)std::max<long long>(nnz, 1)),
+               o_val = E.take(sizeof(double) * (size_t)std::max<long long>(nnz, 1)),
+               o_segs = E.take(sizeof(int2) * (size_t)std::max(nseg, 1));
+  HIP_TRY(c, c->d_bp_ent.grow(E.total, E.total + E.total / 2, st, true));
+  uint32_t* d_ent = (uint32_t*)(c->d_bp_ent.get() + o_ent);
+  double* d_val = (double*)(c->d_bp_ent.get() + o_val);
+  int2* d_segs = (int2*)(c->d_bp_ent.get() + o_segs);
+  HIP_TRY(c, hipMemcpyAsync(d_off, off.data(), sizeof(long long) * m, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_segs, segs.data(), sizeof(int2) * (size_t)nseg, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_segoff, segoff.data(), sizeof(int) * segoff.size(), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL((bp_fill_kernel<kBpNonZero>), dim3((unsigned)m), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, d_off, d_cnt,
+                     d_ent, d_val);
+  hipLaunchKernelGGL(mb_colsum_kernel, dim3((unsigned)m), dim3(256), 0, st, d_val, d_off, d_cnt, d_AC);
+  HIP_TRY(c, hipGetLastError());
+  // K = G'G through the integer planes: exact for hard calls (the product the SKAT permutations use)
+  rc = gemm_tn_planes(c, c->d_Gp, ld, m, c->d_Gp, ld, m, N, d_K, m, st);
+  if (rc) return rc;
+  {
+    const size_t need = sizeof(double) * (size_t)std::max(nseg, m) * kBpChunk;
+    HIP_TRY(c, c->d_bp_part.grow(need, need + need / 4, st, true));
+    const size_t nw = sizeof(double) * (size_t)m * kBpChunk;
+    HIP_TRY(c, c->d_bp_w.grow(nw, nw + nw / 4, st, true));
+    HIP_TRY(c, c->d_bp_stat.grow(sizeof(double) * kBpChunk, sizeof(double) * kBpChunk, st, true));
+  }
+  const double n = (double)N;
+  // ---- observed statistic: the binary score test of the fitted null model on the observed collapsed column ----------------------
+  hipLaunchKernelGGL((mb_segsum_kernel<kBpIdentity>), dim3((unsigned)nseg, 1), dim3(64), 0, st, d_ent, d_val, d_segs, d_y, (long long)N,
+                     0ull, 0ull, 0u, 1, c->d_bp_part.get());
+  hipLaunchKernelGGL(mb_finish_kernel, dim3(1), dim3(64), 0, st, c->d_bp_part.get(), d_segoff, m, 1, d_AC, d_K, n, cases,
+                     c->d_bp_w.get(), c->d_bp_stat.get(), 1);
+  const long long ld_col = (long long)std::max(c->null_ld, ld);
+  hipLaunchKernelGGL(mb_collapse_kernel, dim3((unsigned)((ld_col + 255) / 256)), dim3(256), 0, st, c->d_Gp, (long long)N, (long long)ld, m,
+                     c->d_bp_w.get(), ld_col, d_col);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, sync_stream(st));
+  int ok = 0;
+  double us = 0, vs = 0, eff = 0, se = 0, pv = 0;
+  rc = rvt_score_block(c, d_col, 1, &ok, &us, &vs, &eff, &se, &pv);
+  if (rc) return rc;
+  if (!ok || !(vs > 0.0)) return RVT_OK;  // TestCovariate failed: fitOK = false before anything is drawn
+  const double obs = us * us / vs;
+  r->stat = obs;
+  int actual = 0, numX = 0, numEq = 0, failed = 0;
+  auto launch = [&](int srcKind, const double* src, unsigned shuffle0, int nb, uint64_t key) {
+    const dim3 grid((unsigned)nseg, (unsigned)((nb + 63) / 64));
+    if (srcKind == kBpCounter)
+      hipLaunchKernelGGL((mb_segsum_kernel<kBpCounter>), grid, dim3(64), 0, st, d_ent, d_val, d_segs, src, (long long)N,
+                         (unsigned long long)c->perm_seed, (unsigned long long)key, shuffle0, nb, c->d_bp_part.get());
+    else
+      hipLaunchKernelGGL((mb_segsum_kernel<kBpMatrix>), grid, dim3(64), 0, st, d_ent, d_val, d_segs, src, (long long)N, 0ull, 0ull, 0u, nb,
+                         c->d_bp_part.get());
+    hipLaunchKernelGGL(mb_finish_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, c->d_bp_part.get(), d_segoff, m, nb, d_AC,
+                       d_K, n, cases, c->d_bp_w.get(), c->d_bp_stat.get(), 0);
+  };
+  if (!c->perm_exact) {
+    const uint64_t key = burdenperm_key(m, cnt);
+    rc = counter_permutations(
+        c, nPerm, alpha, obs, [&](unsigned shuffle0, int nb) { launch(kBpCounter, d_y, shuffle0, nb, key); }, &actual, &numX, &numEq,
+        &failed);
+  } else {
+    rc = exact_permutations(
+        c, d_y, nPerm, alpha, obs, 0,
+        [&](int nb, int, const double** d_out) -> int {
+          launch(kBpMatrix, c->d_perm_R, 0u, nb, 0);
+          *d_out = c->d_bp_stat;
+          return RVT_OK;
+        },
+        &actual, &numX, &numEq, &failed);
+  }
+  if (rc) return rc;
+  r->fit_ok = failed > 10 ? 0 : 1;  // the eleventh failed shuffle fails the gene; the counters stay as they stand
+  r->actual_perm = actual;
+  r->num_greater = numX;
+  r->num_equal = numEq;
+  r->perm_pvalue = actual == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEq) / actual;
+  return RVT_OK;
+}
+
 }  // namespace
 
 // ---- --vt price: Price's variable-threshold permutation test of device-resident blocks -------------------------------------
@@ -701,6 +1043,66 @@ int rvt_vtprice_blocks(rvt_ctx* c, int n, const double* const* dG, const int* M,
     rc = vtprice_stage(c, dG[g], M[g], af + afo, d_y, binary ? avg : 0.0, nperm, alpha, out + g);
     if (rc) return rc;
     afo += (size_t)M[g];
+  }
+  return RVT_OK;
+}
+
+// ---- --burden rarecover / mb: the permutation burden tests of device-resident blocks -----------------------------------------------
+namespace {
+// the 0 / 1 phenotype on the device; *valid: every value is 0 or 1 and both classes are present
+int binary_phenotype(rvt_ctx* c, const double* y, DevBuf<double>* d_y, double* cases, bool* valid) {
+  const int64_t N = c->nc.N;
+  bool binary = true;
+  long long n1 = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    binary = binary && (y[i] == 0.0 || y[i] == 1.0);
+    n1 += y[i] == 1.0;
+  }
+  *valid = binary && n1 > 0 && n1 < N;
+  *cases = (double)n1;
+  HIP_TRY(c, d_y->alloc(sizeof(double) * (size_t)N));
+  HIP_TRY(c, hipMemcpyAsync(d_y->get(), y, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, sync_stream(c->stream));
+  return RVT_OK;
+}
+}  // namespace
+
+int rvt_rarecover_blocks(rvt_ctx* c, int n, const double* const* dG, const int* M, const double* y, int nperm, double alpha,
+                         rvt_rarecover_result* out) {
+  if (!c || n < 0 || (n > 0 && (!dG || !M || !y || !out)) || nperm < 0) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set (it defines the sample count)");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  DevBuf<double> d_y;
+  double cases = 0.0;
+  bool valid = false;
+  rc = binary_phenotype(c, y, &d_y, &cases, &valid);
+  if (rc) return rc;
+  for (int g = 0; g < n; ++g) {  // one gene at a time: the random stream is consumed in gene order
+    if (M[g] < 1 || M[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_INVALID, "gene %d has M=%d", g, M[g]);
+    rc = rarecover_stage(c, dG[g], M[g], d_y, cases, valid, nperm, alpha, out + g);
+    if (rc) return rc;
+  }
+  return RVT_OK;
+}
+
+int rvt_mb_blocks(rvt_ctx* c, int n, const double* const* dG, const int* M, const double* y, int nperm, double alpha,
+                  rvt_mb_result* out) {
+  if (!c || n < 0 || (n > 0 && (!dG || !M || !y || !out)) || nperm < 0) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set (it defines the sample count)");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  DevBuf<double> d_y;
+  double cases = 0.0;
+  bool valid = false;
+  rc = binary_phenotype(c, y, &d_y, &cases, &valid);
+  if (rc) return rc;
+  for (int g = 0; g < n; ++g) {  // one gene at a time: the random stream is consumed in gene order
+    if (M[g] < 1 || M[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_INVALID, "gene %d has M=%d", g, M[g]);
+    rc = mb_stage(c, dG[g], M[g], d_y, cases, valid, nperm, alpha, out + g);
+    if (rc) return rc;
   }
   return RVT_OK;
 }

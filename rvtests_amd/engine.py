@@ -358,6 +358,17 @@ class VtPriceResult(C.Structure):
                 ("num_greater", C.c_int), ("num_equal", C.c_int), ("perm_pvalue", C.c_double)]
 
 
+class RareCoverResult(C.Structure):
+    _fields_ = [("fit_ok", C.c_int), ("n_poly", C.c_int), ("n_carrier", C.c_int), ("n_selected", C.c_int), ("stat", C.c_double),
+                ("num_perm", C.c_int), ("actual_perm", C.c_int), ("num_greater", C.c_int), ("num_equal", C.c_int),
+                ("perm_pvalue", C.c_double)]
+
+
+class MbResult(C.Structure):
+    _fields_ = [("fit_ok", C.c_int), ("n_poly", C.c_int), ("n_entries", C.c_int64), ("stat", C.c_double), ("num_perm", C.c_int),
+                ("actual_perm", C.c_int), ("num_greater", C.c_int), ("num_equal", C.c_int), ("perm_pvalue", C.c_double)]
+
+
 class DecomposeInfo(C.Structure):
     _fields_ = [("sweeps", C.c_int), ("max_cosine", C.c_double), ("padded_order", C.c_int64), ("shift", C.c_double),
                 ("max_residual", C.c_double)]
@@ -672,6 +683,27 @@ class Engine:
         self._check(self.L.rvt_vtprice_blocks(self.ctx, n, arr_p, arr_m.ctypes.data_as(c_int_p), _dp(af), _dp(y), int(nperm),
                                               C.c_double(alpha), out))
         return list(out)
+
+    def _burdenperm_blocks(self, name, Rec, ptrs, Ms, y, nperm, alpha):
+        n = len(ptrs)
+        arr_p = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in ptrs])
+        arr_m = np.ascontiguousarray(Ms, dtype=np.int32)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        out = (Rec * n)()
+        fn = getattr(self.L, name)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, c_int_p, c_double_p, C.c_int, C.c_double, C.c_void_p]
+        self._check(fn(self.ctx, n, arr_p, arr_m.ctypes.data_as(c_int_p), _dp(y), int(nperm), C.c_double(alpha), out))
+        return list(out)
+
+    def rarecover_blocks(self, ptrs, Ms, y, nperm=10000, alpha=0.05):
+        """RareCover permutation test of device-resident blocks (rvt_rarecover_blocks); y: the 0 / 1 phenotype."""
+        return self._burdenperm_blocks("rvt_rarecover_blocks", RareCoverResult, ptrs, Ms, y, nperm, alpha)
+
+    def mb_blocks(self, ptrs, Ms, y, nperm=10000, alpha=0.05):
+        """Madsen-Browning permutation test of device-resident blocks (rvt_mb_blocks); y: the 0 / 1 phenotype, the installed null
+        model a binary one."""
+        return self._burdenperm_blocks("rvt_mb_blocks", MbResult, ptrs, Ms, y, nperm, alpha)
 
     def kinship_decompose(self, K, install=False, want_vectors=True):
         """Eigendecomposition of the symmetric float kinship K on the device (rvt_kinship_decompose).
