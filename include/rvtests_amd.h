@@ -675,6 +675,52 @@ typedef struct rvt_mb_result {
 int rvt_mb_blocks(rvt_ctx* ctx, int n, const double* const* dG, const int* M, const double* y, int nperm, double alpha,
                   rvt_mb_result* out);
 
+/* ---- the analytic burden tests --burden cmcWald, zegginiWald, fp, exactCMC (src/ModelManager.cpp:99-142; CMCWaldTest,
+ * ZegginiWaldTest, CMCFisherExactTest src/Model.h:909-1168, FpTest :1344-1417 over cmcCollapse / zegginiCollapse / fpCollapse
+ * src/Model.cpp:73-89,115-130,177-197 and Table2by2::FullFastFisherExactTest regression/Table2by2.cpp:316-357) ---------------------
+ * Calling shape of rvt_kbac_blocks: the device holds the n imputed, UNFLIPPED fp64 blocks, af = the genes' frequencies back to
+ * back (sum of M entries; fpCollapse reads af by the FILTERED column's index, oracle quirk #3), `which` = the tests wanted.  The
+ * flip / keep decisions are those of getFlippedToMinorPolymorphicGenotype; then ONE launch streams every gene's block once and
+ * writes the collapsed columns asked for into N x n device blocks:
+ *   CMC      1 when any kept column has (int)g' > 0, else 0 (a mean-imputed 0.37 does not count)
+ *   Zeggini  the number of kept columns with (int)g' > 0
+ *   Fp       sum_m g'(p, m) / sqrt(f_m (1 - f_m)) in column order, columns with f <= 0 or f >= 1 skipped (an imputed 0.37 counts)
+ * and counts NonRefSite (samples whose CMC value is not 0) and exactCMC's 2 x 2 table N[geno][pheno], geno = (int)cmc, pheno =
+ * (int)y, samples outside 0 .. 1 skipped.  The fits run once per batch on those blocks:
+ *   cmcWald / zegginiWald  rvt_wald_block of the collapsed column: beta / se / pvalue[0] the collapsed genotype, then the
+ *                          covariates — CMCWaldTest::writeOutput's rows i = 1 .. X.cols - 1.  Needs rvt_fit_null (RVT_E_STATE).
+ *   fp                     rvt_score_block of the Fp column against the installed null model (any; units as rvt_score_block)
+ *   exactCMC               Fisher's exact test on the device; lgamma(n + 1) stands for the reference's cumulative log sums.  Needs
+ *                          y (N values, all 0 / 1) and a binary null model with d = 1, else exact_ok = 0 (the reference prints NA
+ *                          for a quantitative trait or covariates).  y is read for this test only and may be NULL otherwise.
+ * A gene without polymorphic column has every ok = 0; so has a test whose collapsed column is constant (every kept value an imputed
+ * fraction: the reference's fit fails too).  Fields of a test that failed or was not asked for: 0, p-values 1.
+ * Synchronous, like rvt_mb_blocks; the rvt_group_* layer does not carry it. */
+#define RVT_BURDEN_CMCWALD 1u
+#define RVT_BURDEN_ZEGGINIWALD 2u
+#define RVT_BURDEN_FP 4u
+#define RVT_BURDEN_EXACTCMC 8u
+typedef struct rvt_burden_wald_fit {
+  int ok;     /* 1: fitted */
+  int rounds; /* IRLS rounds executed (0 for a quantitative trait) */
+  double beta[RVT_MAX_COV], se[RVT_MAX_COV], pvalue[RVT_MAX_COV]; /* d entries: collapsed genotype, then the covariates */
+} rvt_burden_wald_fit;
+typedef struct rvt_burden_more_result {
+  int n_poly;      /* columns after flip-to-minor + monomorphic removal */
+  int nonref_site; /* CMCWaldTest::totalNonRefSite */
+  rvt_burden_wald_fit cmc_wald, zeggini_wald;
+  int fp_ok, exact_ok;
+  double fp_u, fp_v, fp_pvalue;
+  int n00, n01, n10, n11; /* [geno][pheno] */
+  double exact_p_two, exact_p_less, exact_p_greater;
+} rvt_burden_more_result;
+int rvt_burden_blocks(rvt_ctx* ctx, int n, const double* const* dG, const int* M, const double* af, const double* y,
+                      uint32_t which, rvt_burden_more_result* out);
+/* Tests: a column-major N x n host copy of one collapsed block that the last rvt_burden_blocks call of this context left on the
+ * device (test = one RVT_BURDEN_* bit with a block: CMCWALD, ZEGGINIWALD, FP; n = the genes of that call's last chunk.  A chunk
+ * is 256 MB / (8 ld) genes, at least 16 and at most 1024; the environment variable RVT_BURDEN_CHUNK, read per call, sets it). */
+int rvt_burden_last_columns(rvt_ctx* ctx, uint32_t test, int n, double* cols);
+
 /* ---- raw / packed genotypes at the boundary (SURVEY §8f "next" #1) --------------------------------------------------
  * Like rvt_submit_gene, but the block is what the genotype extractor produced, BEFORE DataConsolidator::consolidate:
  * missing genotypes are negative (-9, libVcf/VCFConstant.h:4).  The device then does what consolidate() does to the

@@ -10,8 +10,10 @@ CPU fallback: if the HIP library is missing or there is no GPU, construction fai
 from .engine import (Engine, Group, GeneResult, Params, Timing, RvtError, build_library, library_path, load_library,
                      TEST_SKAT, TEST_SKATO, TEST_CMC, TEST_ZEGGINI, TEST_ALL, TEST_ANALYTICVT, TRAIT_QUANTITATIVE,
                      TRAIT_BINARY, MAX_INFLIGHT, KbacResult, DecomposeInfo, VtPriceResult, RareCoverResult,
-                     MbResult)
+                     MbResult, BurdenMoreResult, BurdenWaldFit, BURDEN_CMCWALD, BURDEN_ZEGGINIWALD, BURDEN_FP,
+                     BURDEN_EXACTCMC, BURDEN_ALL)
 
 __all__ = ["Engine", "Group", "GeneResult", "Params", "Timing", "RvtError", "build_library", "library_path", "load_library",
            "TEST_SKAT", "TEST_SKATO", "TEST_CMC", "TEST_ZEGGINI", "TEST_ALL", "TEST_ANALYTICVT", "TRAIT_QUANTITATIVE",
-           "TRAIT_BINARY", "MAX_INFLIGHT", "KbacResult", "DecomposeInfo", "VtPriceResult", "RareCoverResult", "MbResult"]
+           "TRAIT_BINARY", "MAX_INFLIGHT", "KbacResult", "DecomposeInfo", "VtPriceResult", "RareCoverResult", "MbResult",
+           "BurdenMoreResult", "BurdenWaldFit", "BURDEN_CMCWALD", "BURDEN_ZEGGINIWALD", "BURDEN_FP", "BURDEN_EXACTCMC", "BURDEN_ALL"]

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <functional>
 #include <iterator>
+#include <mutex>
 #include <thread>
 
 namespace rvt_host {
@@ -223,6 +224,15 @@ void GpuBroker::registerTests(uint32_t mask, const rvt_params& p) {
 }
 
 void GpuBroker::shutdown() {
+  if (ctx)
+    for (auto& g : moreGenes) rvt_block_free(ctx, g.block);
+  moreGenes.clear();
+  moreRows.clear();
+  moreReady.clear();
+  moreY.clear();
+  moreBytes = 0;
+  moreSerial = -1;
+  moreTests = 0;
   if (grp) rvt_group_destroy(grp);
   grp = nullptr;
   ctx = nullptr;
@@ -243,6 +253,7 @@ void GpuBroker::shutdown() {
 
 // copyCovariateAndIntercept (src/ModelUtil.h:102-130) + the null fit SkatTest::fit caches (src/Model.h:2672-2699)
 int GpuBroker::installNull(const GeneData& gd, bool binary, std::string* err) {
+  flushBurdenMore();  // the analytic burden tests' pending genes belong to the null model installed so far
   const int d = 1 + gd.ncov;
   std::vector<double> X((size_t)gd.N * d);
   for (int64_t i = 0; i < gd.N; ++i) X[i] = 1.0;
@@ -434,7 +445,8 @@ int GpuBroker::flush() {
   writeReadyRows(true);
   ready.clear();
   failedSerial.clear();
-  return rc;
+  const int rcMore = flushBurdenMore();
+  return rc ? rc : rcMore;
 }
 
 int ModelFitter::deferredFit(GeneData* dc) {
@@ -790,6 +802,158 @@ void MadsonBrowningTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
     fp->write(permutationFields(nPerm, actualPerm, obs, numX, numEqual) + "\n");
   else
     fp->write("NA\n");
+}
+
+// ---- CMCWaldTest / ZegginiWaldTest / FpTest / CMCFisherExactTest -------------------------------------------------------------------
+namespace {
+// src/ModelFitter.h warnOnce: the reference prints these messages to stderr the first time each is seen and goes on (the models
+// above keep theirs in lastError, where the reference returns an error to its caller instead).  fit() runs on the caller's thread;
+// the lock keeps the list whole should two model sets ever be driven from two threads.
+void warnOnce(const std::string& msg) {
+  static std::mutex mu;
+  static std::vector<std::string> seen;
+  std::lock_guard<std::mutex> lock(mu);
+  if (std::find(seen.begin(), seen.end(), msg) != seen.end()) return;
+  seen.push_back(msg);
+  fprintf(stderr, "%s\n", msg.c_str());
+}
+}  // namespace
+
+int GpuBroker::submitBurdenMore(const GeneData& gd, bool binary, std::string* err) {
+  if (gd.serial == moreSerial) return moreOk ? 0 : -1;  // another of the four models already submitted this gene
+  moreSerial = gd.serial;
+  moreOk = false;
+  const size_t geneBytes = sizeof(double) * (size_t)gd.N * (size_t)gd.M;
+  if ((int)moreGenes.size() >= window || (!moreGenes.empty() && moreBytes + geneBytes > windowBytes)) flushBurdenMore();
+  rvt_ctx* cx = contextWithNull(gd, binary, err);  // (a new null model runs the pending genes first: installNull)
+  if (!cx) return -1;
+  if ((int)gd.markerFrequency.size() < gd.M) {
+    *err = "marker frequencies missing";
+    return -1;
+  }
+  MoreGene g{gd.serial, nullptr, gd.M, 1 + gd.ncov, {}};
+  if (rvt_block_alloc(cx, gd.M, &g.block) || rvt_block_upload(cx, g.block, gd.M, gd.genotype)) {
+    *err = rvt_last_error(cx);
+    if (g.block) rvt_block_free(cx, g.block);
+    return -1;
+  }
+  g.af.assign(gd.markerFrequency.begin(), gd.markerFrequency.begin() + gd.M);
+  if (moreGenes.empty()) moreY.assign(gd.phenotype, gd.phenotype + gd.N);
+  moreGenes.push_back(std::move(g));
+  moreBytes += geneBytes;
+  moreOk = true;
+  return 0;
+}
+
+void GpuBroker::enqueueBurdenMore(BurdenMoreTest* m, TextSink* fp, const std::string& siteTab, int64_t serial) {
+  moreRows.push_back(MoreRow{m, fp, siteTab, serial});
+  writeReadyMoreRows();  // (a gene that was not submitted has nothing to wait for)
+}
+
+// rows in call order, up to the first whose gene is still waiting for its call
+void GpuBroker::writeReadyMoreRows() {
+  size_t k = 0;
+  for (; k < moreRows.size(); ++k) {
+    const MoreRow& r = moreRows[k];
+    if (std::any_of(moreGenes.begin(), moreGenes.end(), [&](const MoreGene& g) { return g.serial == r.serial; })) break;
+    auto it = moreReady.find(r.serial);
+    const bool have = it != moreReady.end();
+    r.fp->write(r.model->formatRows(r.siteTab, have ? &it->second.rec : nullptr, have ? it->second.d : 0));
+  }
+  moreRows.erase(moreRows.begin(), moreRows.begin() + k);
+}
+
+int GpuBroker::flushBurdenMore() {
+  int rc = 0;
+  // the last call's records served the rows of its genes; the current gene's stays for the models that have yet to see it
+  for (auto it = moreReady.begin(); it != moreReady.end();) it = (it->first != moreSerial) ? moreReady.erase(it) : std::next(it);
+  if (ctx && !moreGenes.empty()) {
+    const int n = (int)moreGenes.size();
+    std::vector<const double*> ptr((size_t)n);
+    std::vector<int> Ms((size_t)n);
+    std::vector<double> af;
+    for (int g = 0; g < n; ++g) {
+      ptr[g] = moreGenes[g].block;
+      Ms[g] = moreGenes[g].M;
+      af.insert(af.end(), moreGenes[g].af.begin(), moreGenes[g].af.end());
+    }
+    std::vector<rvt_burden_more_result> recs((size_t)n);
+    rc = rvt_burden_blocks(ctx, n, ptr.data(), Ms.data(), af.data(), moreY.data(), moreTests, recs.data());
+    if (rc)
+      warnOnce(std::string("burden tests failed: ") + rvt_last_error(ctx) + ". Results will be all NAs.");
+    else
+      for (int g = 0; g < n; ++g) moreReady[moreGenes[g].serial] = MoreRecord{recs[g], moreGenes[g].d};
+    for (auto& g : moreGenes) rvt_block_free(ctx, g.block);
+  }
+  moreGenes.clear();
+  moreBytes = 0;
+  writeReadyMoreRows();
+  return rc;
+}
+
+BurdenMoreTest::BurdenMoreTest(uint32_t which) { GpuBroker::instance().registerBurdenMore(which); }
+int BurdenMoreTest::fit(GeneData* dc) {
+  curSerial = dc->serial;
+  return GpuBroker::instance().submitBurdenMore(*dc, isBinaryOutcome(), &lastError);
+}
+void BurdenMoreTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
+  GpuBroker::instance().enqueueBurdenMore(this, fp, siteInfo.valueTab(), curSerial);
+}
+void BurdenMoreTest::writeFootnote(TextSink*) { GpuBroker::instance().flushBurdenMore(); }
+
+BurdenWaldTest::BurdenWaldTest(const char* name, bool zeggini_)
+    : BurdenMoreTest(zeggini_ ? RVT_BURDEN_ZEGGINIWALD : RVT_BURDEN_CMCWALD), zeggini(zeggini_) {
+  modelName = name;
+}
+void BurdenWaldTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab() + (zeggini ? "Beta\tSE\tPvalue\n" : "NonRefSite\tBeta\tSE\tPvalue\n"));
+}
+std::string BurdenWaldTest::formatRows(const std::string& siteTab, const rvt_burden_more_result* r, int d) {
+  // genotype.cols == 0 fails BEFORE X is rebuilt: X keeps the previous gene's shape (src/Model.h:925-928)
+  if (r && r->n_poly > 0) xCols = 1 + d;  // [1, collapsed, covariates]
+  const rvt_burden_wald_fit* f = !r ? nullptr : zeggini ? &r->zeggini_wald : &r->cmc_wald;
+  const bool ok = r && r->n_poly > 0 && f->ok;
+  std::string rows;
+  for (int i = 1; i < xCols; ++i) {  // src/Model.h:959-978, 1050-1069
+    rows += siteTab;
+    if (ok) {
+      if (!zeggini) rows += std::to_string(r->nonref_site) + "\t";
+      rows += floatToString(f->beta[i - 1]) + "\t" + floatToString(f->se[i - 1]) + "\t" + floatToString(f->pvalue[i - 1]);
+    } else {
+      rows += zeggini ? "NA\tNA\tNA" : "NA\tNA\tNA\tNA";
+    }
+    rows += "\n";
+  }
+  return rows;
+}
+
+void FpTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) { fp->write(siteInfo.headerTab() + "Pvalue\n"); }
+std::string FpTest::formatRows(const std::string& siteTab, const rvt_burden_more_result* r, int) {
+  return siteTab + ((r && r->n_poly > 0 && r->fp_ok) ? floatToString(r->fp_pvalue) : std::string("NA")) + "\n";
+}
+
+int CMCFisherExactTest::fit(GeneData* dc) {
+  curSerial = dc->serial;
+  if (!isBinaryOutcome()) {  // src/Model.h:1099-1105
+    warnOnce("Fisher's exact test does not support continuous outcomes. Results will be all NAs.");
+    return -1;
+  }
+  if (dc->ncov != 0) {  // :1110-1116 (the reference tests genotype.cols == 0 first: the row is the same NA row either way)
+    warnOnce("Fisher's exact test does not support covariates. Results will be all NAs.");
+    return -1;
+  }
+  return BurdenMoreTest::fit(dc);
+}
+void CMCFisherExactTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab() + "N00\tN01\tN10\tN11\tPvalueTwoSide\tPvalueLess\tPvalueGreater\n");
+}
+// result.clearValue() first (:1147): nothing of an earlier gene survives.  (Another of the four models may have submitted a gene
+// this one skipped: the engine gives exact_ok = 0 for a quantitative null model or one with covariates.)
+std::string CMCFisherExactTest::formatRows(const std::string& siteTab, const rvt_burden_more_result* r, int) {
+  if (!r || r->n_poly == 0 || !r->exact_ok) return siteTab + "NA\tNA\tNA\tNA\tNA\tNA\tNA\n";
+  return siteTab + std::to_string(r->n00) + "\t" + std::to_string(r->n01) + "\t" + std::to_string(r->n10) + "\t" +
+         std::to_string(r->n11) + "\t" + floatToString(r->exact_p_two) + "\t" + floatToString(r->exact_p_less) + "\t" +
+         floatToString(r->exact_p_greater) + "\n";
 }
 
 // ---- FamSkatTest ----------------------------------------------------------------------------------------------------------
@@ -1602,6 +1766,14 @@ int ModelManager::create(const std::string& type, const std::string& modelList) 
         model.push_back(new FamBurdenTest(false));
       else if (modelName == "famzeggini")
         model.push_back(new FamBurdenTest(true));
+      else if (modelName == "cmcwald")  // src/ModelManager.cpp:99-142: the four analytic tests take no parameters
+        model.push_back(new CMCWaldTest());
+      else if (modelName == "zegginiwald")
+        model.push_back(new ZegginiWaldTest());
+      else if (modelName == "fp")
+        model.push_back(new FpTest());
+      else if (modelName == "exactcmc")
+        model.push_back(new CMCFisherExactTest());
       else if (modelName == "rarecover") {  // src/ModelManager.cpp:115-121
         parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
         model.push_back(new RareCoverTest(nPerm, alpha));

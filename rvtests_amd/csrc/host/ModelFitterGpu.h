@@ -125,6 +125,7 @@ class ModelParser {
 };
 
 class ModelFitter;
+class BurdenMoreTest;
 
 // ---- the engine shared by all GPU-backed models of one run ---------------------------------------------------
 // One device group per process (rvt_group_*: RVT_DEVICES=0,1,... lists the GPUs, default device 0): the gene tests'
@@ -167,6 +168,15 @@ class GpuBroker {
   // fit() sees a gene runs the union of the registered tests, the others read the cached record
   void registerFamTests(uint32_t mask) { famTests |= mask; }
   const rvt_gene_result* famResultFor(const GeneData& gd, std::string* err);
+  // the analytic burden tests (CMCWald, ZegginiWald, Fp, CMCFisherExact) share one device copy of each gene and one
+  // rvt_burden_blocks call per window of genes, with the union of the registered tests: the first model whose fit() sees a gene
+  // uploads it, writeOutput() only records (model, sink, site columns), and the rows are written in call order when the window
+  // (the one of the gene tests above: genes or bytes) is full, when a new null model is about to be installed, at writeFootnote()
+  // and at flush().  A gene that could not be submitted, or whose call failed, prints NA rows.
+  void registerBurdenMore(uint32_t mask) { moreTests |= mask; }
+  int submitBurdenMore(const GeneData& gd, bool binary, std::string* err);
+  void enqueueBurdenMore(BurdenMoreTest* m, TextSink* fp, const std::string& siteTab, int64_t serial);
+  int flushBurdenMore();
   // null model: fitted on the device (rvt_fit_null) unless the caller installs its own routine (e.g. the
   // reference's LinearRegression / LogisticRegression inside the rvtests tree); see INTEGRATION.md
   typedef int (*NullFitter)(bool binary, int64_t N, int d, const double* X, const double* y, double* res, double* v,
@@ -207,6 +217,31 @@ class GpuBroker {
   int64_t famSerial = -1;
   bool famOk = false;
   rvt_gene_result famRec{};
+  uint32_t moreTests = 0;
+  struct MoreGene {
+    int64_t serial;
+    double* block;  // rvt_block_alloc on member 0, freed by flushBurdenMore()
+    int M, d;
+    std::vector<double> af;
+  };
+  struct MoreRecord {
+    rvt_burden_more_result rec;
+    int d;  // 1 + the covariates of the gene's null model: the Wald tests print d rows
+  };
+  struct MoreRow {
+    BurdenMoreTest* model;
+    TextSink* fp;
+    std::string siteTab;
+    int64_t serial;
+  };
+  std::vector<MoreGene> moreGenes;           // uploaded and not yet run, submission order
+  std::vector<double> moreY;                 // the phenotype of the pending genes (exactCMC's table)
+  size_t moreBytes = 0;
+  std::map<int64_t, MoreRecord> moreReady;   // records of the last call, waiting for their rows
+  std::vector<MoreRow> moreRows;             // in writeOutput() order
+  int64_t moreSerial = -1;
+  bool moreOk = false;
+  void writeReadyMoreRows();
   int installNull(const GeneData& gd, bool binary, std::string* err);
 };
 
@@ -395,6 +430,63 @@ class MadsonBrowningTest : public ModelFitter {
   double obs = -1.0;
   int actualPerm = -1, numX = -1, numEqual = -1;
   rvt_mb_result rec{};
+};
+
+// `--burden cmcWald`, `zegginiWald`, `fp`, `exactCMC` (src/ModelManager.cpp:99-142; CMCWaldTest, ZegginiWaldTest, CMCFisherExactTest
+// src/Model.h:909-1168, FpTest :1344-1417): the analytic burden tests of rvt_burden_blocks.  No name takes parameters.  Batched
+// through GpuBroker like CMC and Zeggini: fit() submits the gene once for all four, writeOutput() records the row, the rows are
+// formatted from the records in call order (GpuBroker::submitBurdenMore).  Rows are the reference's:
+//   CMCWald / ZegginiWald  one row per column 1 .. X.cols - 1 of X = [1, collapsed, covariates] (site columns repeated), "NonRefSite
+//                          Beta SE Pvalue" / "Beta SE Pvalue"; NA fields when the fit failed.  A gene without polymorphic column
+//                          fails BEFORE X is rebuilt: it prints as many NA rows as the previous gene's X had columns, less one —
+//                          none when no gene has built X yet.
+//   Fp                     "Pvalue"
+//   CMCFisherExact         "N00 N01 N10 N11 PvalueTwoSide PvalueLess PvalueGreater"; a quantitative trait or covariates warn once
+//                          and print NA rows
+class BurdenMoreTest : public ModelFitter {
+ public:
+  int fit(GeneData* dc) override;
+  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeFootnote(TextSink* fp) override;
+  // the gene's rows, site columns and line ends included, from its record (r == nullptr: the gene was not run) and the d of its
+  // null model; called once per writeOutput(), in call order
+  virtual std::string formatRows(const std::string& siteTab, const rvt_burden_more_result* r, int d) = 0;
+
+ protected:
+  explicit BurdenMoreTest(uint32_t which);
+};
+class BurdenWaldTest : public BurdenMoreTest {
+ public:
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  std::string formatRows(const std::string& siteTab, const rvt_burden_more_result* r, int d) override;
+
+ protected:
+  BurdenWaldTest(const char* name, bool zeggini);
+
+ private:
+  bool zeggini;
+  int xCols = 0;  // this->X.cols as the last gene with a polymorphic column left it
+};
+class CMCWaldTest : public BurdenWaldTest {
+ public:
+  CMCWaldTest() : BurdenWaldTest("CMCWald", false) {}
+};
+class ZegginiWaldTest : public BurdenWaldTest {
+ public:
+  ZegginiWaldTest() : BurdenWaldTest("ZegginiWald", true) {}
+};
+class FpTest : public BurdenMoreTest {
+ public:
+  FpTest() : BurdenMoreTest(RVT_BURDEN_FP) { modelName = "Fp"; }
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  std::string formatRows(const std::string& siteTab, const rvt_burden_more_result* r, int d) override;
+};
+class CMCFisherExactTest : public BurdenMoreTest {
+ public:
+  CMCFisherExactTest() : BurdenMoreTest(RVT_BURDEN_EXACTCMC) { modelName = "CMCFisherExact"; }
+  int fit(GeneData* dc) override;
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  std::string formatRows(const std::string& siteTab, const rvt_burden_more_result* r, int d) override;
 };
 
 // `--kernel famSkat[beta1:beta2]` (src/Model.h:3048-3145).  The reference ignores beta1 / beta2 for this model

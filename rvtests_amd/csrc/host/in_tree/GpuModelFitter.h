@@ -131,6 +131,10 @@ typedef GpuModel<rvt_host::KbacTest> KBACTest;            // new KBACTest(nPerm,
 typedef GpuModel<rvt_host::VariableThresholdPrice> VariableThresholdPrice;  // new VariableThresholdPrice(nPerm, alpha)
 typedef GpuModel<rvt_host::RareCoverTest> RareCoverTest;            // new RareCoverTest(nPerm, alpha)       :115-121
 typedef GpuModel<rvt_host::MadsonBrowningTest> MadsonBrowningTest;  // new MadsonBrowningTest(nPerm, alpha)  :104-110
+typedef GpuModel<rvt_host::CMCWaldTest> CMCWaldTest;                // new CMCWaldTest()          :99-142
+typedef GpuModel<rvt_host::ZegginiWaldTest> ZegginiWaldTest;        // new ZegginiWaldTest()
+typedef GpuModel<rvt_host::FpTest> FpTest;                          // new FpTest()
+typedef GpuModel<rvt_host::CMCFisherExactTest> CMCFisherExactTest;  // new CMCFisherExactTest()
 typedef GpuModel<rvt_host::SingleVariantWaldTest> SingleVariantWaldTest;    // new SingleVariantWaldTest()   :54-98
 typedef GpuModel<rvt_host::SingleVariantScoreTest> SingleVariantScoreTest;  // new SingleVariantScoreTest()
 // the single-variant tests for related samples (src/ModelManager.cpp:63-84); familyModel = true as their constructors set it

@@ -46,6 +46,10 @@ int rvt_binding_check(DataConsolidator* dc, FileWriter* fp, const Result& siteIn
   parser.parse("mb");
   parser.assign("nPerm", &nPerm, 10000).assign("alpha", &alpha, 0.05);
   model.push_back(new rvt_intree::MadsonBrowningTest(nPerm, alpha));
+  model.push_back(new rvt_intree::CMCWaldTest());
+  model.push_back(new rvt_intree::ZegginiWaldTest());
+  model.push_back(new rvt_intree::FpTest());
+  model.push_back(new rvt_intree::CMCFisherExactTest());
   int rc = 0;
   for (size_t m = 0; m < model.size(); ++m) {  // src/ModelManager.cpp:273-282, src/Main.cpp:1207-1256
     model[m]->setParameter(parser);

@@ -346,6 +346,14 @@ struct rvt_ctx {
   DevBuf<char> d_bp_ws, d_bp_ent;
   DevBuf<unsigned long long> d_bp_cy;
   DevBuf<double> d_bp_part, d_bp_w, d_bp_stat;
+  // rvt_burden_blocks (burdencol_kernels.hip.h; grow-only): column pointers, flags, kept-column lists, gene table, counters, Fisher
+  // p-values and y | the collapsed N x n blocks of a chunk of genes (cmc, zeggini, fp: those asked for).  burden_cols_*: what the
+  // last call left there (rvt_burden_last_columns)
+  DevBuf<char> d_burden_ws;
+  DevBuf<double> d_burden_cols;
+  int burden_cols_n = 0, burden_cols_chunk = 0;
+  uint32_t burden_cols_which = 0;
+  unsigned long long burden_cols_gen = 0;
   uint32_t rand_state[31];
   int64_t jump_N = -1;                 // J = A^(jump_N - 1) is cached for this sample count
   std::vector<uint32_t> jump;          // 31 x 31, row-major

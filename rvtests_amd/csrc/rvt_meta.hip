@@ -7,6 +7,7 @@
 #include "gemm_f64.hip.h"
 #include "band_rows.hip.h"
 #include "wald_logistic.hip.h"
+#include "burdencol_kernels.hip.h"
 
 // row slices of MetaCov's column pass (cov_hc_prep_kernel): a function of N alone, so that a column's sums are the same numbers
 // whether it is treated inside a block or alone behind its upload (rvt_block_upload_columns)
@@ -178,10 +179,9 @@ static int score_slices(rvt_ctx* c, const double* dG, int V, const CovOut& proto
   return RVT_OK;
 }
 
-int rvt_score_block(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat, double* vstat, double* effect,
-                    double* effect_se, double* pvalue) {
-  if (!c || !dG || V < 1 || !ok || !ustat || !vstat || !effect || !effect_se || !pvalue)
-    return fail(c, RVT_E_INVALID, "bad arguments");
+// rvt_score_block behind its argument checks (rvt_burden_blocks runs the Fp columns through it)
+static int score_block_impl(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat, double* vstat, double* effect,
+                            double* effect_se, double* pvalue) {
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   CovOut co;
   co.ok = ok;
@@ -193,10 +193,22 @@ int rvt_score_block(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat,
   return score_slices(c, dG, V, co);
 }
 
+int rvt_score_block(rvt_ctx* c, const double* dG, int V, int* ok, double* ustat, double* vstat, double* effect,
+                    double* effect_se, double* pvalue) {
+  if (!c || !dG || V < 1 || !ok || !ustat || !vstat || !effect || !effect_se || !pvalue)
+    return fail(c, RVT_E_INVALID, "bad arguments");
+  return score_block_impl(c, dG, V, ok, ustat, vstat, effect, effect_se, pvalue);
+}
+
 // ---- SingleVariantWaldTest: the full regression of every column of a block on [1, g, cov] ----------------------------
+// (behind its argument checks: rvt_burden_blocks runs the collapsed columns through wald_block_impl)
+static int wald_block_impl(rvt_ctx* c, const double* dG, int V, int* ok, double* beta, double* se, double* pvalue, int* rounds);
 int rvt_wald_block(rvt_ctx* c, const double* dG, int V, int* ok, double* beta, double* se, double* pvalue, int* rounds) {
-  using namespace rvt_wald;
   if (!c || !dG || V < 1 || !ok || !beta || !se || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
+  return wald_block_impl(c, dG, V, ok, beta, se, pvalue, rounds);
+}
+static int wald_block_impl(rvt_ctx* c, const double* dG, int V, int* ok, double* beta, double* se, double* pvalue, int* rounds) {
+  using namespace rvt_wald;
   if (!c->have_null || !c->have_null_beta) return fail(c, RVT_E_STATE, "no null model fitted by rvt_fit_null");
   const NullConsts& nc = c->nc;
   const int d = nc.d;
@@ -275,6 +287,201 @@ int rvt_wald_block(rvt_ctx* c, const double* dG, int V, int* ok, double* beta, d
     HIP_TRY(c, hipMemcpyAsync(pvalue + (size_t)c0 * d, d_op, vd, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, sync_stream(st));
   }
+  return RVT_OK;
+}
+
+// ---- --burden cmcWald / zegginiWald / fp / exactCMC: the analytic burden tests of a batch of device-resident genes ---------------
+// (CMCWaldTest, ZegginiWaldTest, CMCFisherExactTest src/Model.h:909-1168, FpTest :1344-1417)
+// The flip / keep decisions of every column of the batch come from fam_colstat_kernel (what flipped_poly_block uses); the host
+// turns them into the kept-column lists and the Fp weights (af indexed by the FILTERED column, quirk #3); burden_columns_kernel
+// then streams every gene once and writes its collapsed columns; the fits run once per chunk of genes on the N x n blocks.
+// genes per chunk: three blocks of at most 256 MB each, at least 16 and at most 1024 genes (67 at N = 500 000).  RVT_BURDEN_CHUNK
+// sets it (read per call: the tests run a batch in several chunks with it).
+static int burden_chunk_genes(int64_t ld) {
+  if (const char* e = getenv("RVT_BURDEN_CHUNK")) return std::max(1, std::min(1024, atoi(e)));
+  return (int)std::max<int64_t>(16, std::min<int64_t>(1024, ((int64_t)256 << 20) / (int64_t)(sizeof(double) * ld)));
+}
+
+int rvt_burden_blocks(rvt_ctx* c, int n, const double* const* dG, const int* M, const double* af, const double* y, uint32_t which,
+                      rvt_burden_more_result* out) {
+  constexpr uint32_t kAll = RVT_BURDEN_CMCWALD | RVT_BURDEN_ZEGGINIWALD | RVT_BURDEN_FP | RVT_BURDEN_EXACTCMC;
+  if (!c || n < 0 || (n > 0 && (!dG || !M || !af || !out)) || which == 0 || (which & ~kAll) || ((which & RVT_BURDEN_EXACTCMC) && !y))
+    return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  const bool want_cmc = which & RVT_BURDEN_CMCWALD, want_zeg = which & RVT_BURDEN_ZEGGINIWALD, want_fp = which & RVT_BURDEN_FP,
+             want_exact = which & RVT_BURDEN_EXACTCMC;
+  if ((want_cmc || want_zeg) && (!c->have_null_beta || (c->nc.binary && !c->d_null_y)))
+    return fail(c, RVT_E_STATE, "no null model fitted by rvt_fit_null");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  c->burden_cols_n = 0;
+  if (n == 0) return RVT_OK;
+  hipStream_t st = c->stream;
+  const int64_t N = c->nc.N, ld = c->null_ld;
+  const int d = c->nc.d;
+  size_t T = 0;
+  for (int g = 0; g < n; ++g) {
+    if (M[g] < 1 || M[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_INVALID, "gene %d has M=%d", g, M[g]);
+    if (!dG[g]) return fail(c, RVT_E_INVALID, "gene %d has no block", g);
+    T += (size_t)M[g];
+  }
+  // exactCMC: a 0 / 1 phenotype, a binary null model without covariates (src/Model.h:1099-1116)
+  bool exact_valid = want_exact && c->nc.binary && d == 1;
+  if (exact_valid)
+    for (int64_t i = 0; i < N && exact_valid; ++i) exact_valid = y[i] == 0.0 || y[i] == 1.0;
+  std::memset(out, 0, sizeof(*out) * (size_t)n);
+  for (int g = 0; g < n; ++g) {
+    out[g].fp_pvalue = out[g].exact_p_two = out[g].exact_p_less = out[g].exact_p_greater = 1.0;
+    for (int k = 0; k < RVT_MAX_COV; ++k) out[g].cmc_wald.pvalue[k] = out[g].zeggini_wald.pvalue[k] = 1.0;
+  }
+  // ---- flip / keep flags of all T columns --------------------------------------------------------------------------------------
+  std::vector<const double*> cols(T);
+  {
+    size_t t = 0;
+    for (int g = 0; g < n; ++g)
+      for (int j = 0; j < M[g]; ++j) cols[t++] = dG[g] + (size_t)j * ld;
+  }
+  const int nchunk = std::min(n, burden_chunk_genes(ld));
+  Layout L;
+  const size_t o_cols = L.take(sizeof(double*) * T), o_flags = L.take(sizeof(int) * T), o_kc = L.take(sizeof(int) * T),
+               o_kw = L.take(sizeof(double) * T), o_genes = L.take(sizeof(BurdenColGene) * (size_t)n),
+               o_cnt = L.take(sizeof(int) * (size_t)n * kBurdenColCounters), o_pv = L.take(sizeof(double) * (size_t)n * 3),
+               o_y = L.take(sizeof(double) * (size_t)N);
+  HIP_TRY(c, c->d_burden_ws.grow(L.total, L.total + L.total / 4, st, true));
+  char* ws = c->d_burden_ws;
+  const double** d_cols = reinterpret_cast<const double**>(ws + o_cols);
+  int* d_flags = reinterpret_cast<int*>(ws + o_flags);
+  int* d_kc = reinterpret_cast<int*>(ws + o_kc);
+  double* d_kw = reinterpret_cast<double*>(ws + o_kw);
+  BurdenColGene* d_genes = reinterpret_cast<BurdenColGene*>(ws + o_genes);
+  int* d_cnt = reinterpret_cast<int*>(ws + o_cnt);
+  double* d_pv = reinterpret_cast<double*>(ws + o_pv);
+  double* d_y = reinterpret_cast<double*>(ws + o_y);
+  std::vector<int> flags(T);
+  HIP_TRY(c, hipMemcpyAsync(d_cols, cols.data(), sizeof(double*) * T, hipMemcpyHostToDevice, st));
+  for (size_t t0 = 0; t0 < T; t0 += 65535) {
+    const size_t nt = std::min<size_t>(65535, T - t0);
+    k_fam_colstat(dim3((unsigned)nt), st, d_cols + t0, (long long)N, d_flags + t0);
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * T, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  // ---- the kept columns of every gene and their Fp weights -------------------------------------------------------------------------
+  std::vector<int> kc;
+  std::vector<double> kw;
+  std::vector<BurdenColGene> genes((size_t)n);
+  kc.reserve(T), kw.reserve(T);
+  {
+    size_t t = 0;
+    for (int g = 0; g < n; ++g) {
+      genes[g].G = dG[g];
+      genes[g].kept0 = (int)kc.size();
+      int m = 0;
+      for (int j = 0; j < M[g]; ++j) {
+        const int f = flags[t + j];
+        if (!(f & 2)) continue;
+        const double freq = af[t + m];  // dc->getMarkerFrequency(m) of the filtered column m (fpCollapse, src/Model.cpp:188)
+        kc.push_back(j | ((f & 1) ? 0x40000000 : 0));
+        kw.push_back((freq <= 0.0 || freq >= 1.0) ? 0.0 : 1.0 / sqrt(freq * (1.0 - freq)));
+        ++m;
+      }
+      genes[g].m = m;
+      out[g].n_poly = m;
+      t += (size_t)M[g];
+    }
+  }
+  if (!kc.empty()) {
+    HIP_TRY(c, hipMemcpyAsync(d_kc, kc.data(), sizeof(int) * kc.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_kw, kw.data(), sizeof(double) * kw.size(), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(c, hipMemcpyAsync(d_genes, genes.data(), sizeof(BurdenColGene) * (size_t)n, hipMemcpyHostToDevice, st));
+  if (exact_valid) HIP_TRY(c, hipMemcpyAsync(d_y, y, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(int) * (size_t)n * kBurdenColCounters, st));
+  // ---- the collapsed blocks of a chunk of genes, then the fits on them ---------------------------------------------------------------
+  const int n_blocks = (want_cmc ? 1 : 0) + (want_zeg ? 1 : 0) + (want_fp ? 1 : 0);
+  const size_t blk = (size_t)ld * (size_t)nchunk;
+  if (n_blocks) HIP_TRY(c, c->d_burden_cols.grow(sizeof(double) * blk * n_blocks, sizeof(double) * blk * n_blocks, st, true));
+  double *d_cmc = nullptr, *d_zeg = nullptr, *d_fp = nullptr;
+  {
+    double* q = c->d_burden_cols;
+    if (want_cmc) d_cmc = q, q += blk;
+    if (want_zeg) d_zeg = q, q += blk;
+    if (want_fp) d_fp = q, q += blk;
+  }
+  std::vector<int> ok((size_t)nchunk), rounds((size_t)nchunk), cnt((size_t)nchunk * kBurdenColCounters);
+  std::vector<double> b((size_t)nchunk * d), s((size_t)nchunk * d), p((size_t)nchunk * d), pv((size_t)nchunk * 3);
+  std::vector<double> us((size_t)nchunk), vs((size_t)nchunk), ef((size_t)nchunk), es((size_t)nchunk), ps((size_t)nchunk);
+  const unsigned parts = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (ld / 2 + 255) / 256));
+  for (int g0 = 0; g0 < n; g0 += nchunk) {
+    const int ng = std::min(nchunk, n - g0);
+    hipLaunchKernelGGL(burden_columns_kernel, dim3(parts, (unsigned)ng), dim3(256), 0, st, d_genes + g0, d_kc, d_kw, (long long)N,
+                       (long long)ld, exact_valid ? d_y : (const double*)nullptr, d_cmc, d_zeg, d_fp,
+                       d_cnt + (size_t)g0 * kBurdenColCounters);
+    if (exact_valid)
+      hipLaunchKernelGGL(fisher_2x2_kernel, dim3((unsigned)ng), dim3(256), 0, st, d_cnt + (size_t)g0 * kBurdenColCounters, ng, d_pv);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt + (size_t)g0 * kBurdenColCounters, sizeof(int) * (size_t)ng * kBurdenColCounters,
+                              hipMemcpyDeviceToHost, st));
+    if (exact_valid) HIP_TRY(c, hipMemcpyAsync(pv.data(), d_pv, sizeof(double) * (size_t)ng * 3, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    c->burden_cols_n = ng, c->burden_cols_which = which, c->burden_cols_chunk = nchunk, c->burden_cols_gen = c->null_gen;
+    for (int g = 0; g < ng; ++g) {
+      rvt_burden_more_result& r = out[g0 + g];
+      const int* q = cnt.data() + (size_t)g * kBurdenColCounters;
+      r.nonref_site = q[0];
+      if (exact_valid && r.n_poly > 0) {
+        r.exact_ok = 1;
+        r.n00 = q[1], r.n01 = q[2], r.n10 = q[3], r.n11 = q[4];
+        r.exact_p_two = pv[(size_t)g * 3], r.exact_p_less = pv[(size_t)g * 3 + 1], r.exact_p_greater = pv[(size_t)g * 3 + 2];
+      }
+    }
+    for (int w = 0; w < 2; ++w) {
+      const double* blkp = w == 0 ? d_cmc : d_zeg;
+      if (!blkp) continue;
+      rc = wald_block_impl(c, blkp, ng, ok.data(), b.data(), s.data(), p.data(), rounds.data());
+      if (rc) return rc;
+      for (int g = 0; g < ng; ++g) {
+        rvt_burden_more_result& r = out[g0 + g];
+        rvt_burden_wald_fit& f = w == 0 ? r.cmc_wald : r.zeggini_wald;
+        if (r.n_poly == 0) continue;  // genotype.cols == 0: nothing is fitted
+        f.rounds = rounds[g];
+        if (ok[g] != 1) continue;     // a constant collapsed column or a failed fit
+        f.ok = 1;
+        for (int k = 0; k < d; ++k) f.beta[k] = b[(size_t)g * d + k], f.se[k] = s[(size_t)g * d + k], f.pvalue[k] = p[(size_t)g * d + k];
+      }
+    }
+    if (d_fp) {
+      rc = score_block_impl(c, d_fp, ng, ok.data(), us.data(), vs.data(), ef.data(), es.data(), ps.data());
+      if (rc) return rc;
+      for (int g = 0; g < ng; ++g) {
+        rvt_burden_more_result& r = out[g0 + g];
+        if (r.n_poly == 0 || !ok[g]) continue;
+        r.fp_ok = 1;
+        r.fp_u = us[g], r.fp_v = vs[g], r.fp_pvalue = ps[g];
+      }
+    }
+  }
+  return RVT_OK;
+}
+
+// Tests: column-major N x n copy of one collapsed block the last rvt_burden_blocks call of this context left on the device
+// (test = RVT_BURDEN_CMCWALD, _ZEGGINIWALD or _FP; n = the genes of the call's LAST chunk: all of them for a call of at most 16
+// genes, and whenever the call fits one chunk of burden_chunk_genes — 256 MB per block, 1024 genes at the most)
+int rvt_burden_last_columns(rvt_ctx* c, uint32_t test, int n, double* cols) {
+  if (!c || !cols || n < 1) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null || c->burden_cols_gen != c->null_gen || n != c->burden_cols_n || !(c->burden_cols_which & test) ||
+      (test != RVT_BURDEN_CMCWALD && test != RVT_BURDEN_ZEGGINIWALD && test != RVT_BURDEN_FP))
+    return fail(c, RVT_E_STATE, "no such block from the last rvt_burden_blocks call");
+  const int64_t N = c->nc.N, ld = c->null_ld;
+  const uint32_t w = c->burden_cols_which;
+  int idx = 0;  // blocks lie in the order cmc, zeggini, fp, those asked for only
+  if (test != RVT_BURDEN_CMCWALD && (w & RVT_BURDEN_CMCWALD)) ++idx;
+  if (test == RVT_BURDEN_FP && (w & RVT_BURDEN_ZEGGINIWALD)) ++idx;
+  const int nchunk = c->burden_cols_chunk;
+  const double* src = c->d_burden_cols.get() + (size_t)idx * (size_t)ld * nchunk;
+  HIP_TRY(c, hipMemcpy2D(cols, sizeof(double) * (size_t)N, src, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)N, (size_t)n,
+                         hipMemcpyDeviceToHost));
   return RVT_OK;
 }
 

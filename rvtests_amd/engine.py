@@ -369,6 +369,23 @@ class MbResult(C.Structure):
                 ("actual_perm", C.c_int), ("num_greater", C.c_int), ("num_equal", C.c_int), ("perm_pvalue", C.c_double)]
 
 
+MAX_COV = 16
+BURDEN_CMCWALD, BURDEN_ZEGGINIWALD, BURDEN_FP, BURDEN_EXACTCMC = 1, 2, 4, 8
+BURDEN_ALL = 15
+
+
+class BurdenWaldFit(C.Structure):
+    _fields_ = [("ok", C.c_int), ("rounds", C.c_int), ("beta", C.c_double * MAX_COV), ("se", C.c_double * MAX_COV),
+                ("pvalue", C.c_double * MAX_COV)]
+
+
+class BurdenMoreResult(C.Structure):
+    _fields_ = [("n_poly", C.c_int), ("nonref_site", C.c_int), ("cmc_wald", BurdenWaldFit), ("zeggini_wald", BurdenWaldFit),
+                ("fp_ok", C.c_int), ("exact_ok", C.c_int), ("fp_u", C.c_double), ("fp_v", C.c_double), ("fp_pvalue", C.c_double),
+                ("n00", C.c_int), ("n01", C.c_int), ("n10", C.c_int), ("n11", C.c_int), ("exact_p_two", C.c_double),
+                ("exact_p_less", C.c_double), ("exact_p_greater", C.c_double)]
+
+
 class DecomposeInfo(C.Structure):
     _fields_ = [("sweeps", C.c_int), ("max_cosine", C.c_double), ("padded_order", C.c_int64), ("shift", C.c_double),
                 ("max_residual", C.c_double)]
@@ -704,6 +721,31 @@ class Engine:
         """Madsen-Browning permutation test of device-resident blocks (rvt_mb_blocks); y: the 0 / 1 phenotype, the installed null
         model a binary one."""
         return self._burdenperm_blocks("rvt_mb_blocks", MbResult, ptrs, Ms, y, nperm, alpha)
+
+    def burden_blocks(self, ptrs, Ms, afs, y=None, which=BURDEN_ALL):
+        """The analytic burden tests cmcWald / zegginiWald / fp / exactCMC of device-resident blocks (rvt_burden_blocks): a list of
+        BurdenMoreResult.  y: the 0 / 1 phenotype, needed by exactCMC only."""
+        n = len(ptrs)
+        arr_p = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in ptrs])
+        arr_m = np.ascontiguousarray(Ms, dtype=np.int32)
+        af = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64) for a in afs]))
+        yy = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+        out = (BurdenMoreResult * n)()
+        fn = self.L.rvt_burden_blocks
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, c_int_p, c_double_p, c_double_p, C.c_uint32, C.c_void_p]
+        self._check(fn(self.ctx, n, arr_p, arr_m.ctypes.data_as(c_int_p), _dp(af), None if yy is None else _dp(yy),
+                       int(which), out))
+        return list(out)
+
+    def burden_last_columns(self, test, n):
+        """Tests: the N x n collapsed block (BURDEN_CMCWALD, BURDEN_ZEGGINIWALD or BURDEN_FP) the last burden_blocks call left."""
+        cols = np.zeros((self.N, n), order="F")
+        fn = self.L.rvt_burden_last_columns
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_uint32, C.c_int, c_double_p]
+        self._check(fn(self.ctx, int(test), int(n), _dp(cols)))
+        return cols
 
     def kinship_decompose(self, K, install=False, want_vectors=True):
         """Eigendecomposition of the symmetric float kinship K on the device (rvt_kinship_decompose).
