@@ -930,6 +930,10 @@ int rvt_debug_collapse(rvt_ctx* ctx, const double* dG, int M, double* cmc_out, d
  * colsum/min/max (M each); host outputs, row-major */
 int rvt_debug_suffstat(rvt_ctx* ctx, const double* dG, int M, double* S, double* T, double* u, double* colsum,
                        double* cmin, double* cmax);
+/* U'G as the family tests compute it: the first ncols columns of an uploaded block through the rotation with the installed
+ * kinship (rvt_set_kinship, and a null model for the block layout); out is a host N x ncols matrix, column-major.  Row k
+ * belongs to eigenpair k in the INSTALLED order (family-structured U: stably sorted by first non-zero row) */
+int rvt_debug_rotate(rvt_ctx* ctx, const double* dG, int ncols, double* out);
 int rvt_set_profiling(rvt_ctx* ctx, int on);
 int rvt_get_timing(rvt_ctx* ctx, rvt_timing* t, int reset);
 /* the HIP stream (hipStream_t) the engine launches on, for callers that record their own events */

@@ -358,12 +358,12 @@ __device__ __forceinline__ void rot_digits(long long q, int planes, signed char*
 }
 
 // float matrix (column-major, n x ncols, leading dimension lds_src) -> digit planes [plane][col][ldk]; entries scaled
-// by 2^sexp.  flag[0] is set when an entry does not fit (|u| * 2^sexp >= 2^(7 planes - 2)).
+// by 2^sexp.  flag[0] is set when an entry does not fit the digits (|u| * 2^sexp above 63 (128^planes - 1) / 127).
 #if !defined(RVT_K_SPLIT) || defined(RVT_K_FAM)
 static __global__ void rot_quantize_f32_kernel(const float* __restrict__ src, long long n, long long ncols, long long ld_src,
                                         int sexp, int planes, signed char* __restrict__ dst, long long ldk,
                                         long long plane_stride, long long col0, int* __restrict__ flag) {
-  const double scale = ldexp(1.0, sexp), lim = ldexp(1.0, 7 * planes - 2);
+  const double scale = ldexp(1.0, sexp), lim = ldexp(63.0 / 127.0, 7 * planes) - 1.0;
   for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n * ncols;
        idx += (long long)gridDim.x * blockDim.x) {
     const long long j = idx / n, i = idx % n;

@@ -50,11 +50,12 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
   c->have_kin = c->have_fam = c->have_grammar = false;
   HIP_TRY(c, c->d_S.alloc(sizeof(double) * N));
   HIP_TRY(c, c->d_u1.alloc(sizeof(double) * N));
-  // U -> fixed-point digit planes (rot_gemm.hip.h).  Eigenvectors have |u| <= 1; entries up to 2 are representable.
+  // U -> fixed-point digit planes (rot_gemm.hip.h): 40 fractional bits.  Eigenvectors have |u| <= 1; six digits in [-64, 63]
+  // hold every |u| < 1.98.
   c->uq_ldk = (N + 127) / 128 * 128;
   c->uq_rows_pad = (N + kRotBM - 1) / kRotBM * kRotBM;
   c->uq_plane = (size_t)c->uq_rows_pad * (size_t)c->uq_ldk;
-  c->uq_sexp = 7 * kRotPlanesU - 3;
+  c->uq_sexp = 7 * kRotPlanesU - 2;
   HIP_TRY(c, c->d_Uq.alloc(c->uq_plane * kRotPlanesU));
   HIP_TRY(c, hipMemsetAsync(c->d_Uq, 0, c->uq_plane * kRotPlanesU, c->stream));
   const long long csc_cap = 64ll * N;  // non-zeros the sparse form may hold
@@ -109,7 +110,7 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
     int bad = 0;
     HIP_TRY(c, hipMemcpy(&bad, d_flag, sizeof(int), hipMemcpyDeviceToHost));
     if (!csc_ok) free_csc(c);
-    if (bad) return fail(c, RVT_E_INVALID, "kinship eigenvectors have entries >= 2 in magnitude (not unit vectors)");
+    if (bad) return fail(c, RVT_E_INVALID, "kinship eigenvectors have entries >= 1.98 in magnitude (not unit vectors)");
   }
   c->h_S.resize(N);
   for (int64_t i = 0; i < N; ++i) c->h_S[i] = (double)S[i];
@@ -912,6 +913,28 @@ int rotate_columns(rvt_ctx* c, const double* d_src, int64_t ld_src, int ncols, d
                      nc, qb.sexp.data(), N, c->uq_ldk, d_dst + (size_t)c0 * ld_dst, ld_dst, st, c->d_uq_range);
     if (rc) return rc;
   }
+  return RVT_OK;
+}
+
+// Test hook: the first ncols columns of a device block through rotate_columns, N x ncols to the host (column-major, no padding).
+int rvt_debug_rotate(rvt_ctx* c, const double* dG, int ncols, double* out) {
+  if (!c || !dG || !out || ncols < 1) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_kin) return fail(c, RVT_E_STATE, "rvt_set_kinship first");
+  if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first (defines the block layout)");
+  const int64_t N = c->kin_N, ld = c->have_null ? c->null_ld : c->fam_nc.ld;  // (the layout rvt_block_alloc gave dG)
+  if ((c->have_null ? c->nc.N : c->fam_nc.N) != N) return fail(c, RVT_E_STATE, "the kinship and the null model differ in N");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  rc = ensure_fam_cols(c, (size_t)ncols, ld);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * ncols, st));
+  rc = rotate_columns(c, dG, ld, ncols, c->d_Gt, ld, st);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpy2DAsync(out, sizeof(double) * (size_t)N, c->d_Gt, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)N,
+                              (size_t)ncols, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
   return RVT_OK;
 }
 

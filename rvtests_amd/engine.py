@@ -935,6 +935,15 @@ class Engine:
                                               _dp(mn), _dp(mx)))
         return S, T, u, cs, mn, mx
 
+    def debug_rotate(self, ptr, ncols):
+        """U'G of the first ncols columns of a device block, N x ncols (rvt_debug_rotate); rows in the installed eigenpair
+        order."""
+        out = np.zeros((self.N, int(ncols)), order="F")
+        self.L.rvt_debug_rotate.restype = C.c_int
+        self.L.rvt_debug_rotate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, c_double_p]
+        self._check(self.L.rvt_debug_rotate(self.ctx, C.c_void_p(int(ptr)), int(ncols), _dp(out)))
+        return out
+
     def set_perm_exact(self, on):
         """True (the default of a single context): SKAT permutations replay the reference's rand() stream (bit-identical
         counters, sequential); False: counter-based permutations keyed by (seed, gene id, shuffle) — rvt_set_perm_exact."""

@@ -6,6 +6,7 @@ import pytest
 import orc
 import synth
 from test_fam_cpu import make_family_case
+from test_gpu_single_fam import grm_case
 
 pytestmark = pytest.mark.gpu
 
@@ -198,6 +199,98 @@ def test_fam_burden_matches_oracle(eng, n_fam, d):
         assert r.famskat_ok == (1 if rc == 0 else 0)
         if rc == 0:
             assert abs(r.famskat_Q - s.Q) <= 1e-7 * s.Q
+
+
+def dense_genes(N, seed):
+    """M = 1, 17 and 64 with 2 % missing calls, and one all-monomorphic gene."""
+    genes = [synth.make_gene(N, M, seed=seed + M, missing=0.02, common=True, mono=(M > 5), maf_hi=-0.8)[1] for M in (1, 17, 64)]
+    genes.append(np.ones((N, 3)))
+    return genes
+
+
+def device_null_for_oracle(nul, d):
+    onul = orc.FamNull()
+    onul.ok = 1
+    onul.delta, onul.sigma2 = nul.delta, nul.sigma2_g
+    for k in range(d):
+        onul.beta[k] = nul.beta[k]
+    return onul
+
+
+@pytest.mark.parametrize("N,d", [(300, 2), (515, 3)])
+def test_fam_tests_on_dense_kinship_match_oracle(eng, N, d):
+    """FamSKAT, FamCMC and FamZeggini on the eigenvectors of a GRM — every entry of U non-zero, so the rotation is the dense
+    integer GEMM (rot_gemm_i8_kernel; N = 515: K padded to 640 bytes, three row panels) and not the family-panel kernel the
+    nuclear-family cases above take.  Same oracle forms, same tolerances as those cases."""
+    N, K, U, S, X, y = grm_case(N, d, 41 + N)
+    eng.set_kinship(U, S)
+    assert eng.kinship_structure() == 1.0
+    nul = eng.fit_fam_null(X, y)
+    onul = device_null_for_oracle(nul, d)
+    genes = dense_genes(N, 500)
+    ptrs = [eng.upload_block(G) for G in genes]
+    out = eng.run_fam_blocks(ptrs, [G.shape[1] for G in genes], tests=16 | 32 | 64)
+    fitted = 0
+    for r, G in zip(out, genes):
+        rc, o = orc.famskat(G, X, y, U, S, onul)
+        assert r.n_variants == G.shape[1] and r.n_poly == o.n_poly
+        assert r.famskat_ok == (1 if rc == 0 else 0)
+        if rc == 0:
+            fitted += 1
+            assert abs(r.famskat_Q - o.Q) <= 1e-7 * o.Q
+            assert r.skat_nlambda == o.n_lambda
+            assert abs(r.famskat_p - o.pvalue) <= 2e-6 * abs(o.pvalue) + 1e-12
+        for which, ok, af, u, v, p in ((0, r.famcmc_ok, r.famcmc_af, r.famcmc_U, r.famcmc_V, r.famcmc_p),
+                                       (1, r.famzeg_ok, r.famzeg_af, r.famzeg_U, r.famzeg_V, r.famzeg_p)):
+            rc, o = orc.fam_burden(G, X, y, U, S, onul, which)
+            if rc != 0:
+                assert ok == 0
+                continue
+            fitted += 1
+            assert ok == 1 and r.n_poly == o.num_site
+            assert abs(u - o.U) <= 1e-8 * abs(o.U) + 1e-12
+            assert abs(v - o.V) <= 1e-8 * o.V
+            assert abs(af - o.af) <= 1e-9 * abs(o.af) + 1e-15
+            assert abs(p - o.pvalue) <= 1e-6 * o.pvalue
+    assert fitted == 9 and out[-1].famskat_ok == 0
+
+
+@pytest.mark.parametrize("N,d,col0,H", [(300, 2, 0, 64), (515, 3, 17, 30)])
+def test_metacov_fam_on_dense_kinship_matches_oracle(eng, N, d, col0, H):
+    """rvt_cov_block_fam and rvt_cov_rect_fam on a GRM's eigenvectors (the dense rotation), against the oracle's MetaCovFamQtl
+    restatement and each other; tolerances of the nuclear-family cases above."""
+    N, K, U, S, X, y = grm_case(N, d, 70 + N)
+    eng.set_kinship(U, S)
+    assert eng.kinship_structure() == 1.0
+    nul = eng.fit_fam_null(X, y)
+    onul = device_null_for_oracle(nul, d)
+    V = 64
+    _, G, af = synth.make_gene(N, V, seed=600 + N, missing=0.02, common=True, mono=True)
+    pos = np.cumsum(np.random.default_rng(5).integers(1, 300, V)).astype(np.int32)
+    chrom = np.ones(V, dtype=np.int32)
+    ptr = eng.upload_block(G)
+    cov, xz, zz, poly = eng.cov_block_fam(ptr, V, d)
+    rc, kept, ocov, row_end, oxz, ozz = orc.metacov_fam(G, chrom, pos, X, U, S, onul, 10 ** 7)
+    assert rc == 0
+    assert (poly == kept).all()
+    m = ~np.isnan(ocov)
+    assert m.sum() > V
+    assert np.abs(cov[m] - ocov[m]).max() < 1e-8 * np.abs(ocov[m]).max()
+    kk = kept.astype(bool)
+    assert np.allclose(xz[kk], oxz[kk], rtol=1e-8, atol=1e-9 * max(np.abs(oxz[kk]).max(), 1.0))
+    assert np.allclose(zz, ozz, rtol=1e-9)
+    W = V - col0
+    rcov, rxz, rzz, rpoly = eng.cov_rect_fam(ptr, col0, H, W, d)
+    assert (rpoly == poly[col0:]).all()
+    scale = np.abs(cov[~np.isnan(cov)]).max()
+    for h in range(H):
+        assert np.abs(rcov[h, h:] - cov[col0 + h, col0 + h:]).max() <= 1e-9 * scale, h
+    assert np.allclose(rxz, xz[col0:], rtol=1e-8, atol=1e-9 * max(np.abs(xz).max(), 1.0))
+    assert np.allclose(rzz, zz, rtol=1e-12)
+    sub = ocov[col0:col0 + H, col0:]
+    m = ~np.isnan(sub)
+    assert m.sum() > H
+    assert np.abs(rcov[m] - sub[m]).max() < 1e-8 * np.abs(sub[m]).max()
 
 
 def test_rotation_k_range_cut_is_exact(monkeypatch):

@@ -120,6 +120,50 @@ def test_score_block_fam_matches_oracle(engine_factory, n_fam, d, binary):
     eng.free_block(ptr)
 
 
+@pytest.mark.parametrize("binary", [0, 1])
+@pytest.mark.parametrize("N,d", [(300, 2), (515, 3)])
+def test_score_block_fam_on_dense_kinship_matches_oracle(engine_factory, N, d, binary):
+    """rvt_score_block_fam on the eigenvectors of a GRM: the rotation is the dense integer GEMM (N = 515: K padded to 640
+    bytes, three row panels), not the family-panel kernel of the nuclear-family cases above; same oracle, same tolerances."""
+    import synth
+    from test_gpu_single_fam import grm_case
+    N, K, U, S, X, y = grm_case(N, d, 120 + N)
+    b = 1.0
+    if binary:
+        y = (y > np.median(y)).astype(float)
+    eng = engine_factory()
+    eng.set_kinship(U, S)
+    assert eng.kinship_structure() == 1.0
+    nul = eng.fit_fam_null(X, y)
+    if binary:
+        alpha, b = eng.fam_binary_scale(int((y == 1).sum()), int((y == 0).sum()))
+        assert b == pytest.approx(orc.obtain_b(alpha), rel=1e-6)
+    onul = orc.FamNull()
+    onul.ok = 1
+    onul.delta, onul.sigma2 = nul.delta, nul.sigma2_g
+    for k in range(d):
+        onul.beta[k] = nul.beta[k]
+    G = synth.make_gene(N, 64, seed=4321, missing=0.02, common=True, mono=True, maf_hi=-0.8)[1]
+    ptr = eng.upload_block(G)
+    r = eng.score_block_fam(ptr, G.shape[1], binary)
+    tested = 0
+    for h in range(G.shape[1]):
+        rc, o = orc.fam_burden(G[:, [h]], X, y, U, S, onul, 3 if binary else 2)
+        assert r["ok"][h] == (1 if rc == 0 else 0)
+        if rc:
+            continue
+        tested += 1
+        assert abs(r["U"][h] - o.U * b) <= 1e-8 * abs(o.U * b) + 1e-12
+        assert abs(r["V"][h] - o.V * b * b) <= 1e-8 * o.V * b * b
+        assert abs(r["af"][h] - o.af) <= 1e-9 * abs(o.af) + 1e-15
+        assert abs(r["p"][h] - o.pvalue) <= 1e-6 * o.pvalue
+    assert 5 < tested < G.shape[1]
+    rc, covb = orc.fastlmm_covb(X, U, S, nul.delta)
+    assert rc == 0
+    assert np.allclose(eng.fam_null_summary(d), np.diag(covb), rtol=1e-8)
+    eng.free_block(ptr)
+
+
 def test_score_block_fam_chunks_beyond_one_block(engine_factory):
     """More raw columns than RVT_MAX_VARIANTS: rvt_score_block_fam walks the block in pieces; every column equals what a
     call on a small block that holds only its neighbourhood returns."""
