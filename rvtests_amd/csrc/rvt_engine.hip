@@ -30,6 +30,21 @@ int rvt_init(rvt_ctx** out, int device_id) {
   rvt_ctx* c = new rvt_ctx();
   c->device = device_id;
   std::memset(&c->timing, 0, sizeof(c->timing));
+  // launch shapes of the hard-call kernel (before anything is created that a failure would have to release)
+  if (const char* e = getenv("RVT_HC_FUSE")) c->hc_fuse = atoi(e) != 0;
+  if (const char* e = getenv("RVT_HC_CFG")) {  // "MT:DEPTHxWAVES,.."
+    for (const char* p = e; *p;) {
+      int mt = 0, dp = 0, w = 0, used = 0;
+      if (sscanf(p, "%d:%dx%d%n", &mt, &dp, &w, &used) != 3 || mt < 1 || mt > kHcMaxMT || !k2_hc_has_shape(mt, dp, w)) {
+        fprintf(stderr, "[rvt] RVT_HC_CFG=%s: no hard-call kernel of that class, ring depth and waves per SIMD at \"%s\"\n", e, p);
+        delete c;
+        return RVT_E_INVALID;
+      }
+      c->hc_shape[mt] = {dp, w};
+      p += used;
+      if (*p == ',') ++p;
+    }
+  }
   // Streams.  Every stream is created through hipExtStreamCreateWithCUMask, which gives it a hardware queue of its
   // own: the runtime multiplexes ordinary streams onto at most GPU_MAX_HW_QUEUES (default 4) queues, and with
   // five streams in use two of them would share a queue and serialise (measured: -8% throughput).
@@ -1210,7 +1225,9 @@ static int gene_path(const rvt_ctx* c, const BatchCaps& cp, const CovOut* cov, i
   const bool packed = k == kKindPacked;
   // an integer kernel: a single-pass tile class, and an fp64 block that one buffer descriptor of M x ld x 8 < 2^31 bytes
   // covers (packed rows are not doubles — four samples a byte — and have a descriptor of their own: no such bound)
-  if (!cp.hc_possible || MT > cp.hc_max_mt || !(packed || (uint64_t)M * (uint64_t)c->nc.ld * 8ull < (1ull << 31)))
+  // (the null tile's descriptor too: X and rr are d + 1 columns, and the pad lanes' offset 2^31 must lie beyond them)
+  if (!cp.hc_possible || MT > cp.hc_max_mt ||
+      !(packed || (uint64_t)std::max(M, c->nc.d + 1) * (uint64_t)c->nc.ld * 8ull < (1ull << 31)))
     return kPathGeneral;
   if (cp.score_hc)  // (packed: a slice of a resident .bed matrix, rvt_score_bed_dev)
     return packed ? kPathPacked : (cov->slice_hc[g] ? kPathHardCall : kPathGeneral);
@@ -1509,6 +1526,48 @@ static void launch_general_genes(rvt_ctx* c, const Batch& b, hipStream_t gst) {
   }
 }
 
+// the hard-call genes [k, e) of a batch on gene_suffstat_hc (quantitative trait; descriptors sorted widest class first).
+// The classes whose launch shape is the one-wave shape of gene_suffstat_hc_any share ONE launch, which goes first: it hands
+// out the longest wave-parts first and drains once.  A class whose shape keeps several waves per SIMD (and the widest class,
+// which gene_suffstat_hc_any does not carry) has a launch of its own after it.
+static int launch_hardcall_classes(rvt_ctx* c, const Batch& b, int k, int e, hipStream_t hst) {
+  const NullConsts& nc = c->nc;
+  const long long N = nc.N, ld = nc.ld;
+  const int d = nc.d;
+  const GeneDesc *h_desc = b.h_desc, *d_desc = b.d_desc;
+  const NullTile tile{c->d_nulltile, d + 2};
+  unsigned fused = 0;
+  int n_fused = 0, kf = e, ef = k;
+  for (int g = k; g < e && c->hc_fuse; ++g) {
+    const int MT = h_desc[g].MT;
+    if (MT > kHcMaxMT || k2_hc_any_depth(MT) == 0 || c->hc_shape[MT].waves != 1 || c->hc_shape[MT].depth != k2_hc_any_depth(MT))
+      continue;
+    if (!((fused >> MT) & 1u)) ++n_fused;
+    fused |= 1u << MT;
+    kf = std::min(kf, g);
+    ef = std::max(ef, g + 1);
+  }
+  if (n_fused < 2) fused = 0;  // (a single class: its own kernel, with its own registers and LDS)
+  if (fused) {
+    Scope sc(c, 4, hst);
+    k2_launch_hc_any(fused, dim3(b.n_wparts, ef - kf), hst, d_desc + kf, tile, N, ld, d);
+  }
+  for (int g = k; g < e;) {
+    const int MT = h_desc[g].MT;
+    int ge = g;
+    while (ge < e && h_desc[ge].MT == MT) ++ge;
+    if (!((fused >> MT) & 1u)) {
+      Scope sc(c, 4, hst);
+      const auto sh = c->hc_shape[std::min(MT, kHcMaxMT)];
+      if (!k2_launch_hc(MT, sh.depth, sh.waves, dim3(b.n_wparts, ge - g), hst, d_desc + g, tile, N, ld, d))
+        return fail(c, RVT_E_INVALID, "RVT_HC_CFG: no hard-call kernel of class %d with ring depth %d x %d waves per SIMD", MT,
+                    sh.depth, sh.waves);
+    }
+    g = ge;
+  }
+  return RVT_OK;
+}
+
 // descriptors [n_gen, n) on the shared streaming stream: one launch per path and tile class (contiguous runs, widest class
 // first)
 static int launch_integer_genes(rvt_ctx* c, const Batch& b) {
@@ -1521,11 +1580,18 @@ static int launch_integer_genes(rvt_ctx* c, const Batch& b) {
   for (int k = b.n_gen; k < n;) {
     int e = k;
     const int path = h_desc[k].hc, MT = h_desc[k].MT;
+    hipStream_t hst = c->k2_stream;
+    if (path == kPathHardCall && !hcx && !b.caps.hcw) {  // every class of the run: gene_suffstat_hc / gene_suffstat_hc_any
+      while (e < n && h_desc[e].hc == path) ++e;
+      const int rch = launch_hardcall_classes(c, b, k, e, hst);
+      if (rch) return rch;
+      k = e;
+      continue;
+    }
     // (gene_suffstat_hcx_any / gene_suffstat_fdx_any: every class at once)
     const bool one_launch = c->hcx_fused && ((hcx && path == kPathHardCall) || path == kPathFloatDigit);
     while (e < n && (one_launch || h_desc[e].MT == MT) && h_desc[e].hc == path && h_desc[e].hcp_planes == h_desc[k].hcp_planes)
       ++e;
-    hipStream_t hst = c->k2_stream;
     Scope sc(c, 4, hst);
     const dim3 grid(b.n_wparts, e - k);
     const NullTile tile{c->d_nulltile, d + 2};
@@ -1548,10 +1614,8 @@ static int launch_integer_genes(rvt_ctx* c, const Batch& b) {
       k2_launch_lat(MT, grid, hst, d_desc + k, tile, (double)c->lattice_den, N, ld, d);
     else if (hcx)
       k2_launch_hcx(one_launch ? 0 : MT, grid, hst, d_desc + k, c->hcx_tile, N, ld, d);
-    else if (b.caps.hcw)
-      k2_launch_hcw(MT, grid, hst, d_desc + k, NullTileW{c->d_nulltile_w, d + 3, c->d_vq}, N, ld, d);
     else
-      k2_launch_hc(MT, grid, hst, d_desc + k, tile, N, ld, d);
+      k2_launch_hcw(MT, grid, hst, d_desc + k, NullTileW{c->d_nulltile_w, d + 3, c->d_vq}, N, ld, d);
     k = e;
   }
   return RVT_OK;

@@ -34,8 +34,13 @@ void k2_launch_panel_w0(dim3 grid, hipStream_t st, const GeneDesc* d_desc, NullD
                         int d);
 void k2_launch_panel_w1(dim3 grid, hipStream_t st, const GeneDesc* d_desc, NullDev nd, long long N, long long ld,
                         int d);
-void k2_launch_hc(int MT, dim3 grid, hipStream_t st, const GeneDesc* d_desc, NullTile nt, long long N, long long ld,
-                  int d);
+// (false: no kernel of that launch shape is compiled in)
+bool k2_launch_hc(int MT, int depth, int waves, dim3 grid, hipStream_t st, const GeneDesc* d_desc, NullTile nt, long long N,
+                  long long ld, int d);
+bool k2_hc_has_shape(int MT, int depth, int waves);
+int k2_hc_any_depth(int MT);
+void k2_launch_hc_any(unsigned classes, dim3 grid, hipStream_t st, const GeneDesc* d_desc, NullTile nt, long long N,
+                      long long ld, int d);
 void k2_launch_hcw(int MT, dim3 grid, hipStream_t st, const GeneDesc* d_desc, NullTileW nt, long long N, long long ld,
                    int d);
 void k2_launch_hcx(int MT, dim3 grid, hipStream_t st, const GeneDesc* d_desc, const NullTileX& nt, long long N, long long ld,
@@ -418,6 +423,14 @@ struct rvt_ctx {
                           // keep M threads busy while the rest wait at the barriers, and with the eigenvalue stage cut down its
                           // resident waves were 56 % of the per-gene tail (configs[1]: 347 k -> 369 k; the other shapes unchanged)
   bool hcx_fused = true;  // one launch for every tile class of a batch (gene_suffstat_hcx_any); RVT_HCX_FUSED=0: one per class
+  // launch shape of gene_suffstat_hc per tile class (k2_hardcall.hip has the rule; RVT_HC_CFG = "3:3x1,4:2x2,.." overrides
+  // classes; a shape that is not compiled in fails rvt_init), and whether the classes whose shape is the one-wave shape of gene_suffstat_hc_any share that one launch
+  // (RVT_HC_FUSE=0: one launch per class).  Read when the context is created.
+  struct HcShape {
+    int depth, waves;
+  };
+  HcShape hc_shape[kHcMaxMT + 1] = {{0, 0}, {2, 4}, {4, 1}, {3, 1}, {2, 2}, {1, 1}, {1, 1}};
+  bool hc_fuse = true;
   int64_t null_ld = 0;
   // Which sufficient-statistics kernel a gene STARTS on is a prediction, never a trust: the hard-call kernel tests every
   // double it loads and hands back genes that hold anything but hard calls and one imputed value per column

@@ -294,7 +294,8 @@ __device__ __forceinline__ void suffstat_hc_body(const GeneDesc& gd, const NullT
   // genotype block: a pad variant (column >= M) gets an offset beyond num_records and reads zeros
   const unsigned gbytes = (unsigned)((unsigned long long)M * (unsigned long long)ld * 8ull);  // < 2^31 (host checks)
   const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(uniform(gd.G), 0, gbytes, 0x00020000);
-  const unsigned xbytes = (unsigned)((unsigned long long)nt.cols * (unsigned long long)ld * 8ull);
+  // null tile: the descriptor covers X_0 .. X_{d-1} and rr; the tile's zero column is never fetched (pad lanes below)
+  const unsigned xbytes = (unsigned)((unsigned long long)(d + 1) * (unsigned long long)ld * 8ull);
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(uniform(nt.base), 0, xbytes, 0x00020000);
   const unsigned lane_off = (unsigned)(q * 32);  // 4 samples of 8 B per 16-lane row
   const unsigned col_bytes = (unsigned)((unsigned long long)ld * 8ull);
@@ -304,8 +305,10 @@ __device__ __forceinline__ void suffstat_hc_body(const GeneDesc& gd, const NullT
     const int col = c * 16 + v;
     vbase[c] = (col < M) ? (unsigned)col * col_bytes + lane_off : 0x80000000u;
   }
-  const int xcol = (v <= d) ? v : d + 1;  // X_k, rr, or the zero column
-  const unsigned xbase = (unsigned)xcol * col_bytes + lane_off;
+  // X_k or rr; a pad lane (v > d) gets an offset beyond num_records like a pad variant: zeros without a memory request
+  // (xbytes < 2^31: the host keeps a gene off this kernel otherwise, gene_path; the ring and the remainder path both add
+  // less than 2^31 to the offset)
+  const unsigned xbase = (v <= d) ? (unsigned)v * col_bytes + lane_off : 0x80000000u;
   unsigned fx[MT];
 #pragma unroll
   for (int c = 0; c < MT; ++c) fx[c] = ((gd.pflip[c] >> v) & 1) ? 0x02020202u : 0u;
@@ -526,7 +529,7 @@ __device__ __forceinline__ void suffstat_hc_body(const GeneDesc& gd, const NullT
   }
 }
 
-// One kernel per tile class and register budget: the engine picks per class (see suffstat_hc_config).
+// One kernel per tile class and launch shape (ring depth, waves per SIMD): the engine picks per class (k2_hardcall.hip).
 template <int MT, int DEPTH, int WAVES, bool NT>
 __global__ __launch_bounds__(64, WAVES) void gene_suffstat_hc(const GeneDesc* __restrict__ genes, NullTile nt,
                                                               long long N, long long ld, int d) {
@@ -534,6 +537,42 @@ __global__ __launch_bounds__(64, WAVES) void gene_suffstat_hc(const GeneDesc* __
   const GeneDesc gd = genes[blockIdx.y];
   if (gd.MT != MT) return;
   suffstat_hc_body<MT, DEPTH, NT>(gd, nt, N, ld, d, lds);
+}
+
+// The one-wave shapes of the narrower classes.  A shape below 257 registers would be given a second wave per SIMD by the
+// hardware, which defeats the purpose — room for the tail kernels beside ONE streaming wave — so the occupancy is stated:
+// exactly one wave per SIMD (the compiler then requests at least 257 registers for the wave).
+#define RVT_HC_ONE_WAVE __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
+template <int MT, int DEPTH, bool NT>
+__global__ RVT_HC_ONE_WAVE void gene_suffstat_hc_one(const GeneDesc* __restrict__ genes, NullTile nt, long long N,
+                                                     long long ld, int d) {
+  __shared__ unsigned lds[hc_lds_words(MT)];
+  const GeneDesc gd = genes[blockIdx.y];
+  if (gd.MT != MT) return;
+  suffstat_hc_body<MT, DEPTH, NT>(gd, nt, N, ld, d, lds);
+}
+
+// The classes that run ONE wave per SIMD, in one launch: the wave takes the body of its gene's class (a scalar branch — the
+// descriptor comes through scalar loads) at that class's one-wave ring depth.  A batch's genes are sorted widest class first,
+// so the launch hands out its longest wave-parts first and ends on the shortest: one drain per batch instead of one per class.
+// Registers and LDS are those of the widest class — one wave per SIMD whatever the class.  `classes`: bit MT set = this launch
+// computes class MT; the genes of the other classes (their shape keeps several waves per SIMD: a launch of their own) are left
+// alone.
+constexpr int kHcAnyMaxMT = 5;
+constexpr int hc_any_depth(int MT) { return MT == 2 ? 4 : (MT == 3 ? 3 : (MT == 4 ? 2 : (MT == 5 ? 1 : 0))); }
+template <bool NT>
+__global__ RVT_HC_ONE_WAVE void gene_suffstat_hc_any(const GeneDesc* __restrict__ genes, NullTile nt, long long N,
+                                                              long long ld, int d, unsigned classes) {
+  __shared__ unsigned lds[hc_lds_words(kHcAnyMaxMT)];
+  const GeneDesc gd = genes[blockIdx.y];
+  if (!((classes >> gd.MT) & 1u)) return;
+  switch (gd.MT) {
+    case 2: suffstat_hc_body<2, hc_any_depth(2), NT>(gd, nt, N, ld, d, lds); break;
+    case 3: suffstat_hc_body<3, hc_any_depth(3), NT>(gd, nt, N, ld, d, lds); break;
+    case 4: suffstat_hc_body<4, hc_any_depth(4), NT>(gd, nt, N, ld, d, lds); break;
+    case 5: suffstat_hc_body<5, hc_any_depth(5), NT>(gd, nt, N, ld, d, lds); break;
+    default: break;
+  }
 }
 
 // ---- block classification: is every entry of an N x M block exactly 0.0, 1.0 or 2.0? -------------------------------

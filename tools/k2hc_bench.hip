@@ -72,19 +72,26 @@ __global__ void fill_null(double* T, long long N, long long ld, int d, unsigned 
 }
 
 
-// candidate configurations per tile class: (MT, DEPTH, WAVES)
+// candidate launch shapes per tile class: (MT, DEPTH, WAVES); CFG1 = the stated one-wave kernel (gene_suffstat_hc_one), ANY = the
+// class's body inside gene_suffstat_hc_any (the registers and LDS of the widest class)
 typedef void (*hc_kernel_t)(const GeneDesc*, NullTile, long long, long long, int);
 struct HcCfg {
   int MT, depth, waves;
   hc_kernel_t k[2];  // nt off / on
+  bool any;
 };
-#define CFG(mt, dp, w) {mt, dp, w, {gene_suffstat_hc<mt, dp, w, false>, gene_suffstat_hc<mt, dp, w, true>}}
+#define CFG(mt, dp, w) {mt, dp, w, {gene_suffstat_hc<mt, dp, w, false>, gene_suffstat_hc<mt, dp, w, true>}, false}
+#define CFG1(mt, dp) {mt, dp, 1, {gene_suffstat_hc_one<mt, dp, false>, gene_suffstat_hc_one<mt, dp, true>}, false}
+#define ANY(mt) {mt, hc_any_depth(mt), 1, {nullptr, nullptr}, true}
 static const HcCfg kCfgs[] = {
-    CFG(1, 2, 4), CFG(1, 2, 5), CFG(2, 2, 3), CFG(2, 3, 2), CFG(3, 2, 2), CFG(3, 3, 1),
-    CFG(4, 2, 2), CFG(4, 3, 1), CFG(5, 2, 1), CFG(5, 1, 1), CFG(5, 1, 2), CFG(6, 2, 1), CFG(6, 1, 1),
+    CFG(1, 2, 4), CFG(1, 2, 5), CFG(2, 2, 3), CFG(2, 4, 2), CFG1(2, 4), ANY(2), CFG(3, 2, 2), CFG1(3, 3), ANY(3),
+    CFG(4, 2, 2), CFG1(4, 2), CFG1(4, 3), ANY(4), CFG(5, 2, 1), CFG(5, 1, 1), CFG(5, 1, 2), ANY(5), CFG(6, 2, 1), CFG(6, 1, 1),
 };
 static void launch_cfg(const HcCfg& c, int nt_on, dim3 grid, const GeneDesc* dgd, NullTile nt, long long N, long long ld, int d) {
-  hipLaunchKernelGGL(c.k[nt_on], grid, dim3(64), 0, 0, dgd, nt, N, ld, d);
+  if (c.any)
+    hipLaunchKernelGGL(gene_suffstat_hc_any<false>, grid, dim3(64), 0, 0, dgd, nt, N, ld, d, 1u << c.MT);
+  else
+    hipLaunchKernelGGL(c.k[nt_on], grid, dim3(64), 0, 0, dgd, nt, N, ld, d);
 }
 
 struct Gene {
@@ -336,8 +343,8 @@ int main(int argc, char** argv) {
       for (int k = 0; k < 2 * rl; ++k) worstB = fmax(worstB, fabs(bg[k] - br[k]) / fmax(fabs(br[k]), 1.0));
       const bool ok = worstI == 0 && worstS < 1e-14 && worstT < 1e-12 && badstat == 0 && worstB < 1e-11 &&
                       inconsistent == 0 && (flag_or & 2u) == 0 && ((flag_or & 1u) != 0) == (cs.miss > 0);
-      printf("check N=%lld M=%d miss %.3g (MT=%d depth %d waves %d, wparts=%d x %d steps) flipcol=%d: int pieces abs %lld  S rel %.3g  T rel %.3g  colstat bad %d  burden rel %.3g  flags %u  %s\n",
-             N, M, cs.miss, MT, cf.depth, cf.waves, nw, spw, cs.flip, worstI, worstS, worstT, badstat, worstB, flag_or,
+      printf("check N=%lld M=%d miss %.3g (MT=%d depth %d waves %d%s, wparts=%d x %d steps) flipcol=%d: int pieces abs %lld  S rel %.3g  T rel %.3g  colstat bad %d  burden rel %.3g  flags %u  %s\n",
+             N, M, cs.miss, MT, cf.depth, cf.waves, cf.any ? " any" : "", nw, spw, cs.flip, worstI, worstS, worstT, badstat, worstB, flag_or,
              ok ? "OK" : "FAIL");
       if (!ok) ++fails;
       }
@@ -410,8 +417,8 @@ int main(int argc, char** argv) {
           float ms = 0;
           CK(hipEventElapsedTime(&ms, e0, e1));
           const double bytes = (8.0 * N * M + 8.0 * N * (d + 2)) * ngenes * reps;
-          printf("bench M=%d MT=%d depth=%d waves=%d miss=%.3g: %.3f ms per %d genes, %.2f TB/s algorithmic\n", M, MT, cf.depth,
-                 cf.waves, miss, ms / reps, ngenes, bytes / (ms * 1e-3) / 1e12);
+          printf("bench M=%d MT=%d depth=%d waves=%d%s miss=%.3g: %.3f ms per %d genes, %.2f TB/s algorithmic\n", M, MT, cf.depth,
+                 cf.waves, cf.any ? " any" : "", miss, ms / reps, ngenes, bytes / (ms * 1e-3) / 1e12);
         }
       }
       CK(hipFree(dG)); CK(hipFree(parts)); CK(hipFree(colstat)); CK(hipFree(bparts)); CK(hipFree(dgd));
