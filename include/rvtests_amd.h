@@ -411,6 +411,36 @@ int rvt_wald_block(rvt_ctx* ctx, const double* dG, int V, int* ok, double* beta,
 /* dimensions of the installed null model: samples, columns of X (with the intercept) */
 int rvt_null_dims(rvt_ctx* ctx, int64_t* N, int* d);
 int rvt_null_summary(rvt_ctx* ctx, double* beta, double* covb_diag, double* sigma2);
+/* ---- the multiple-trait score test (`--single fastmtscore`, FastMultipleTraitScoreTest src/Model.h:4935-5125) -------------
+ * Every variant of a block against T tests, each a phenotype column with its own covariate list and its own missing values.
+ * The arithmetic is the reference's (regression/FastMultipleTraitLinearRegressionScoreTest.cpp) in fp64 — the reference
+ * computes in float (Eigen MatrixXf); the sample-length sums are exact integer products of fixed-point digits.
+ *
+ * rvt_mt_fit_null replaces FitNullModel (:233-377).  Y: N x P phenotypes, Z: N x Q covariates WITHOUT an intercept column
+ * (Z may be NULL when Q = 0), both column-major doubles with NaN = missing.  Test t is phenotype test_pheno[t] with the
+ * covariates test_cov[test_cov_ptr[t] .. test_cov_ptr[t + 1]) (indices into Z; at most RVT_MAX_COV - 1 per test).  The call
+ * centres every column over its observed entries (center(), :93-126), keeps [Yc | Zc] and the DISTINCT observed patterns
+ * indModel = indY prod indZ (:336; compared by content: tests with the same pattern share one row) resident on the device, and
+ * forms per test OBS, scale_xy, scale_xz, scale_xx, zz_inv, zy and sigma2 (:339-367).  Optional outputs (may be NULL), T entries
+ * each: obs = OBS, sigma2, and ok = 0 for a test whose OBS, sum indY or a sum indZ is 0 or whose scaled Z'Z is not positive
+ * definite (the reference divides by zero or prints what its LDLT left): such a test yields NaN for u, v and p of every
+ * variant and sigma2 = NaN; it does not fail the call.  An index outside [0, P) / [0, Q) or a longer covariate list:
+ * RVT_E_INVALID; more than 32768 resident rows (P + Q + patterns): RVT_E_TOO_LARGE.  Replaces an earlier multiple-trait null of
+ * the context; the null models of rvt_set_null / rvt_fit_null / rvt_fit_fam_null are left alone.  A context whose only model
+ * is this one can allocate and fill blocks (rvt_block_alloc, rvt_block_upload; leading dimension rvt_padded_ld(N)).
+ *
+ * rvt_mt_score_block replaces TestCovariateBlock (:391-470) for the V columns of a device block (any V: wide blocks are walked
+ * in pieces of 1024 columns), taken as stored (imputed, not flipped): hard calls, mean-imputed columns, dosages.  ustat, vstat,
+ * pvalue: V x T row-major (GetU / GetV / GetPvalue); pvalue is NaN where vstat == 0 (:461-463).  RVT_E_STATE without a
+ * multiple-trait null, or when the context also holds a null model of another sample count.  Synchronous.
+ *
+ * rvt_mt_clear frees the resident planes (rvt_mt_score_block then answers RVT_E_STATE).
+ * rvt_mt_last_timing: host milliseconds the last rvt_mt_score_block spent in {genotype pass, products, finishing} (measurement). */
+int rvt_mt_fit_null(rvt_ctx* ctx, int64_t N, int P, const double* Y, int Q, const double* Z, int T, const int* test_pheno,
+                    const int* test_cov_ptr, const int* test_cov, int* ok, double* obs, double* sigma2);
+int rvt_mt_score_block(rvt_ctx* ctx, const double* dG, int V, double* ustat, double* vstat, double* pvalue);
+int rvt_mt_clear(rvt_ctx* ctx);
+int rvt_mt_last_timing(rvt_ctx* ctx, double* ms3);
 /* MetaScore with kinship (MetaFamQtl, src/Model.h:3398-3499; MetaFamBinary, :3556-3668): FastLMM::TestCovariate in its
  * SCORE branch (regression/FastLMM.cpp:215-247) and FastLMM::FastGetAF (:400-424) of every raw column of a device
  * block, after rvt_set_kinship + rvt_fit_fam_null.

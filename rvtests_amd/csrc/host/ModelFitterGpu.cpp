@@ -292,6 +292,14 @@ rvt_ctx* GpuBroker::contextWithNull(const GeneData& gd, bool binary, std::string
   return ctx;
 }
 
+rvt_ctx* GpuBroker::context(std::string* err) {
+  if (ensureContext(0)) {
+    *err = "no MI355X device: the GPU models have no CPU fallback";
+    return nullptr;
+  }
+  return ctx;
+}
+
 rvt_ctx* GpuBroker::contextWithFamNull(const GeneData& gd, std::string* err) {
   if (ensureContext(0)) {
     *err = "no MI355X device: the GPU models have no CPU fallback";
@@ -1395,6 +1403,151 @@ std::string SingleVariantScoreTest::formatSingleRow(const Row& r) {
          "\t" + SE + "\t" + P + "\n";
 }
 
+// ---- FastMultipleTraitScoreTest (src/Model.h:4935-5125) ------------------------------------------------------------------------
+FastMultipleTraitScoreTest::FastMultipleTraitScoreTest() {
+  modelName = "FastMultipleTraitScore";
+  if (const char* e = getenv("RVT_SINGLE_BLOCK")) capacity = std::max(1, std::min(65536, atoi(e)));
+}
+FastMultipleTraitScoreTest::~FastMultipleTraitScoreTest() {
+  if (fout) flush();
+  if (ctx && block) rvt_block_free(ctx, block);
+}
+void FastMultipleTraitScoreTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
+  fp->write(siteInfo.headerTab() + "U_STAT\tV_STAT\tPVALUE\n");
+}
+// FitNullModel's bookkeeping (regression/FastMultipleTraitLinearRegressionScoreTest.cpp:245-283): names to columns, "1" and
+// "intercept" dropped; the arithmetic is rvt_mt_fit_null's
+int FastMultipleTraitScoreTest::fitNull(GeneData* dc) {
+  if (!dc->phenotypeMatrix || dc->nPheno < 1 || dc->formula.empty()) {
+    lastError = "Multiple trait score test needs the phenotype matrix and the formulae";
+    return -1;
+  }
+  auto find = [](const std::vector<std::string>& labels, const std::string& name) {
+    for (size_t i = 0; i < labels.size(); ++i)
+      if (labels[i] == name) return (int)i;
+    return -1;
+  };
+  std::vector<int> pheno, ptr(1, 0), cov;
+  for (const GeneData::Formula& f : dc->formula) {
+    const int y = find(dc->phenotypeLabel, f.phenotype);
+    if (y < 0 || y >= dc->nPheno) {
+      lastError = "Multiple trait score test: unknown phenotype " + f.phenotype;
+      return -1;
+    }
+    pheno.push_back(y);
+    for (const std::string& name : f.covariate) {
+      std::string low = name;
+      for (char& ch : low) ch = (char)tolower((unsigned char)ch);
+      if (name == "1" || low == "intercept") continue;
+      const int z = find(dc->covariateLabel, name);
+      if (z < 0 || z >= dc->ncov) {
+        lastError = "Multiple trait score test: unknown covariate " + name;
+        return -1;
+      }
+      cov.push_back(z);
+    }
+    ptr.push_back((int)cov.size());
+  }
+  cov.push_back(0);  // (never read: keeps the pointer valid for tests without covariates)
+  if (rvt_mt_fit_null(ctx, dc->N, dc->nPheno, dc->phenotypeMatrix, dc->ncov, dc->covariate, (int)pheno.size(), pheno.data(),
+                      ptr.data(), cov.data(), nullptr, nullptr, nullptr)) {
+    lastError = rvt_last_error(ctx);
+    return -1;
+  }
+  nTest = (int)pheno.size();
+  haveNull = true;
+  return 0;
+}
+int FastMultipleTraitScoreTest::fit(GeneData* dc) {
+  fitOK = false;
+  if (isBinaryOutcome()) {  // warnOnce (src/Model.h:4981-4983)
+    lastError = "Multiple trait score test model does not support binary trait yet.";
+    return -1;
+  }
+  if (dc->M != 1 || dc->N == 0) return -1;  // genotype.cols != 1
+  if (nSample >= 0 && nSample != dc->N) {
+    lastError = "Sample size changed";
+    return -1;
+  }
+  if (used >= capacity && flush()) return -1;
+  if (used >= capacity) {  // flush() could not run: no writeOutput() has named the output sink yet
+    lastError = getModelName() + ": the device block is full and no output was requested for its sites";
+    return -1;
+  }
+  if (!ctx) ctx = GpuBroker::instance().context(&lastError);
+  if (!ctx) return -1;
+  if (!haveNull || dc->phenotypeUpdated || dc->covariateUpdated) {
+    if (used > 0 && flush()) return -1;  // the columns so far belong to the previous null
+    if (fitNull(dc)) return -1;
+  }
+  if (nSample < 0) {
+    if (rvt_block_alloc(ctx, capacity, &block)) {
+      lastError = rvt_last_error(ctx);
+      return -1;
+    }
+    nSample = dc->N;
+  }
+  // the caller overwrites the genotype buffer for the next site: copy the column into the device block now
+  if (rvt_block_upload(ctx, block + (size_t)used * (size_t)rvt_padded_ld(nSample), 1, dc->genotype)) {
+    lastError = rvt_last_error(ctx);
+    return -1;
+  }
+  rows.emplace_back();
+  written.push_back(0);
+  ++used;
+  fitOK = true;
+  return 0;
+}
+void FastMultipleTraitScoreTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
+  fout = fp;
+  if (!fitOK) return;  // a site whose fit() failed prints no row
+  fitOK = false;
+  rows.back() = siteInfo.valueTab();
+  written.back() = 1;
+  if (used >= capacity) flush();  // numResult == blockSize (src/Model.h:5033-5035)
+}
+void FastMultipleTraitScoreTest::writeFootnote(TextSink* fp) {
+  fout = fp;
+  flush();
+}
+int FastMultipleTraitScoreTest::flush() {
+  if (!fout) return 0;
+  if (used == 0) return 0;
+  const size_t cells = (size_t)used * (size_t)nTest;
+  u.assign(cells, NAN);
+  v.assign(cells, NAN);
+  pv.assign(cells, NAN);
+  const bool ran = rvt_mt_score_block(ctx, block, used, u.data(), v.data(), pv.data()) == 0;
+  if (!ran) {
+    lastError = rvt_last_error(ctx);
+    std::fill(u.begin(), u.end(), NAN), std::fill(v.begin(), v.end(), NAN), std::fill(pv.begin(), pv.end(), NAN);
+  }
+  char num[32];
+  auto join = [&](const std::vector<double>& m, int row, std::string* out) {  // formatValue (src/Model.h:5091-5100)
+    for (int t = 0; t < nTest; ++t) {
+      if (t) *out += ',';
+      const double x = m[(size_t)row * nTest + t];
+      if (std::isnan(x)) *out += "nan";
+      else out->append(num, formatG(x, num));
+    }
+  };
+  for (int k = 0; k < used; ++k) {
+    if (!written[(size_t)k]) continue;  // main calls writeOutput after every fit(); a row never written is never printed
+    std::string line = rows[(size_t)k];
+    join(u, k, &line);
+    line += '\t';
+    join(v, k, &line);
+    line += '\t';
+    join(pv, k, &line);
+    line += '\n';
+    fout->write(line);
+  }
+  rows.clear();
+  written.clear();
+  used = 0;
+  return ran ? 0 : -1;
+}
+
 // ---- SingleVariantFamilyScore / LRT / GrammarGamma (src/Model.h:525-805), related samples ------------------------------------
 SingleVariantFamilyTest::SingleVariantFamilyTest(const char* name, const char* header_, const char* what_)
     : header(header_), what(what_) {
@@ -1829,8 +1982,11 @@ int ModelManager::create(const std::string& type, const std::string& modelList) 
         return -1;
       }
     } else if (modelType == "single") {
-      // src/ModelManager.cpp:54-98 (exact, dominantexact, firth and the multiple-trait tests are not provided)
-      if (modelName == "wald")
+      // src/ModelManager.cpp:54-98 (exact, dominantexact, firth and mtscore — the multiple-trait test that drops rows per
+      // missingness group — are not provided)
+      if (modelName == "fastmtscore")
+        model.push_back(new FastMultipleTraitScoreTest());
+      else if (modelName == "wald")
         model.push_back(new SingleVariantWaldTest());
       else if (modelName == "score")
         model.push_back(new SingleVariantScoreTest());

@@ -67,6 +67,17 @@ struct GeneData {
   const float* kinshipS = nullptr;
   // MetaScoreTest: raw-genotype counters of the current site — all samples, cases, controls (binary traits only)
   SiteCounts counter, caseCounter, ctrlCounter;
+  // FastMultipleTraitScoreTest (`--multiplePheno`): dc->getPhenotype() as the N x nPheno matrix it then is (column-major,
+  // NaN = missing) with its column labels, the labels of dc->getCovariate()'s columns (`covariate` above, NaN = missing) and
+  // dc->getFormula(): per test the phenotype's name and the covariates' names ("1" / "intercept" are dropped by the model)
+  const double* phenotypeMatrix = nullptr;
+  int nPheno = 0;
+  std::vector<std::string> phenotypeLabel, covariateLabel;
+  struct Formula {
+    std::string phenotype;
+    std::vector<std::string> covariate;
+  };
+  std::vector<Formula> formula;
 };
 
 // ---- FileWriter stand-in (base/IO.h FileWriter::write / printf) -------------------------------------------
@@ -162,6 +173,8 @@ class GpuBroker {
   void shutdown();
   // context + null model for models that drive the C ABI themselves (MetaCovTest)
   rvt_ctx* contextWithNull(const GeneData& gd, bool binary, std::string* err);
+  // the bare context, for a model that installs a null of its own kind (FastMultipleTraitScoreTest: rvt_mt_fit_null)
+  rvt_ctx* context(std::string* err);
   // context + kinship + FastLMM null for FamSkatTest (refitted when the caller flags new phenotype / covariates)
   rvt_ctx* contextWithFamNull(const GeneData& gd, std::string* err);
   // the related-sample gene tests (FamSkat, FamCMC, FamZeggini) share one rotation per gene: the first model whose
@@ -724,6 +737,38 @@ class SingleVariantFamilyGrammarGamma final : public SingleVariantFamilyTest {
   bool afKinship = false;
   bool haveNull = false;
   const float* nullKinship = nullptr;  // the decomposition the GrammarGamma null was fitted on
+};
+
+// FastMultipleTraitScoreTest (src/Model.h:4935-5125, `--single fastmtscore` under --multiplePheno): every site against the T
+// tests of GeneData::formula, "U_STAT V_STAT PVALUE" with the T numbers of a site joined by ",", each printed as the reference's
+// toString(double) prints it (%g; NaN as "nan").  The block pattern of SingleVariantBlockTest: fit() copies the site's column
+// into a device ring of `capacity` columns (1024, RVT_SINGLE_BLOCK), a full block — and writeFootnote / the destructor — runs ONE
+// rvt_mt_score_block and writes the rows in file order.  The null (rvt_mt_fit_null) is made by the first fit() and again when the
+// caller flags an updated phenotype / covariate.  fit() fails on a binary trait (the reference's warnOnce) and on a genotype
+// with other than one column; such a site prints NO row (the reference counts it into its block without a genotype column).
+class FastMultipleTraitScoreTest final : public ModelFitter {
+ public:
+  FastMultipleTraitScoreTest();
+  ~FastMultipleTraitScoreTest() override;
+  int fit(GeneData* dc) override;
+  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeFootnote(TextSink* fp) override;
+
+ private:
+  int fitNull(GeneData* dc);
+  int flush();
+  int capacity = 1024;  // RVT_SINGLE_BLOCK
+  int64_t nSample = -1;
+  int nTest = 0;
+  int used = 0;
+  bool haveNull = false, fitOK = false;
+  rvt_ctx* ctx = nullptr;
+  double* block = nullptr;
+  std::vector<std::string> rows;  // the site columns of the block's columns, in file order ("" until writeOutput names them)
+  std::vector<char> written;
+  std::vector<double> u, v, pv;
+  TextSink* fout = nullptr;
 };
 
 // ---- ModelManager::create -----------------------------------------------------------------------------------------

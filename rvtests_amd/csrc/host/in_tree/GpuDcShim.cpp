@@ -5,8 +5,11 @@
 // extractor's buffer, which the next gene overwrites: src/Main.cpp:1086,1225).
 #include "GpuModelFitter.h"
 
+#include <set>
+
 #include "DataConsolidator.h"
 #include "GenotypeCounter.h"
+#include "regression/Formula.h"
 
 namespace parameter {
 extern bool FLAG_hideCovar;  // DECLARE_BOOL_PARAMETER(hideCovar), src/Model.h:55
@@ -55,6 +58,26 @@ void fillGeneData(DataConsolidator* dc, bool familyModel, const void* who, rvt_h
   if (familyModel && dc->hasKinshipForAuto()) {
     gd->kinshipU = eigenMatrixData(dc->getKinshipUForAuto());
     gd->kinshipS = eigenMatrixData(dc->getKinshipSForAuto());
+  }
+  // --multiplePheno (FastMultipleTraitScoreTest, src/Model.h:4950-4953): the phenotype is an N x P matrix and dc->getFormula()
+  // lists the tests.  The matrix is read in place; the labels and the formulae are copied when the model will fit its null —
+  // its first call and whenever the caller flags an update — not once per site.
+  gd->phenotypeMatrix = y.data.data();
+  gd->nPheno = y.cols;
+  static std::set<const void*> seen;
+  const bool first = seen.insert(who).second;
+  const FormulaVector* fv = dc->getFormula();
+  if (fv && (first || gd->phenotypeUpdated || gd->covariateUpdated)) {
+    gd->phenotypeLabel.resize(y.cols);
+    for (int k = 0; k < y.cols; ++k) gd->phenotypeLabel[k] = y.GetColumnLabel(k);
+    gd->covariateLabel.resize(Z.cols);
+    for (int k = 0; k < Z.cols; ++k) gd->covariateLabel[k] = Z.GetColumnLabel(k);
+    gd->formula.resize(fv->size());
+    for (size_t t = 0; t < fv->size(); ++t) {
+      const std::vector<std::string>& ph = fv->getPhenotype((int)t);
+      gd->formula[t].phenotype = ph.empty() ? std::string() : ph[0];
+      gd->formula[t].covariate = fv->getCovariate((int)t);
+    }
   }
   if (G.cols == 1) gd->genotypeLabel = G.GetColumnLabel(0);  // (empty: the adapters use CHROM:POS)
   if (G.cols == 1) {  // single-variant models print the raw-genotype counters (src/Model.h:3211-3230)

@@ -137,6 +137,7 @@ typedef GpuModel<rvt_host::FpTest> FpTest;                          // new FpTes
 typedef GpuModel<rvt_host::CMCFisherExactTest> CMCFisherExactTest;  // new CMCFisherExactTest()
 typedef GpuModel<rvt_host::SingleVariantWaldTest> SingleVariantWaldTest;    // new SingleVariantWaldTest()   :54-98
 typedef GpuModel<rvt_host::SingleVariantScoreTest> SingleVariantScoreTest;  // new SingleVariantScoreTest()
+typedef GpuModel<rvt_host::FastMultipleTraitScoreTest> FastMultipleTraitScoreTest;  // new FastMultipleTraitScoreTest()  :89-90
 // the single-variant tests for related samples (src/ModelManager.cpp:63-84); familyModel = true as their constructors set it
 class SingleVariantFamilyScore : public GpuModel<rvt_host::SingleVariantFamilyScore> {
  public:

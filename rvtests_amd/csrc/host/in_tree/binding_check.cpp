@@ -50,6 +50,7 @@ int rvt_binding_check(DataConsolidator* dc, FileWriter* fp, const Result& siteIn
   model.push_back(new rvt_intree::ZegginiWaldTest());
   model.push_back(new rvt_intree::FpTest());
   model.push_back(new rvt_intree::CMCFisherExactTest());
+  model.push_back(new rvt_intree::FastMultipleTraitScoreTest());  // src/ModelManager.cpp:89-90 (single fastmtscore)
   int rc = 0;
   for (size_t m = 0; m < model.size(); ++m) {  // src/ModelManager.cpp:273-282, src/Main.cpp:1207-1256
     model[m]->setParameter(parser);

@@ -15,6 +15,7 @@
 #include "perm_counter.h"
 #include "rvt_pvalue.h"
 #include "rvt_mvn.h"
+#include "rvt_mtscore.h"
 
 using namespace rvt;
 
@@ -40,6 +41,24 @@ void rvt_dv_key(int kind, double u) {
 extern "C" {
 
 double hc_chisq_Q(double x, double nu) { return chisq_Q(x, nu); }
+// one (variant, test) cell of the multiple-trait score test (rvt_mtscore.h: what mt_finish_kernel runs per thread); out3 = u, v, p
+void hc_mt_cell(double n, double nm, double gy, const double* gz, double gg, int ncov, int ok, double obs, double scale_xy,
+                double scale_xx, double sigma2, const double* scale_xz, const double* zy, const double* zz_inv, double* out3) {
+  MtTest t;
+  std::memset(&t, 0, sizeof(t));
+  t.ncov = ncov;
+  t.ok = ok;
+  t.obs = obs;
+  t.scale_xy = scale_xy;
+  t.scale_xx = scale_xx;
+  t.sigma2 = sigma2;
+  for (int a = 0; a < ncov && a < kMtMaxCov; ++a) {
+    t.scale_xz[a] = scale_xz[a];
+    t.zy[a] = zy[a];
+    for (int b = 0; b < ncov; ++b) t.zz_inv[a * ncov + b] = zz_inv[a * ncov + b];
+  }
+  mt_cell(n, nm, gy, gz, gg, t, out3, out3 + 1, out3 + 2);
+}
 double hc_chisq_P(double x, double nu) { return chisq_P(x, nu); }
 double hc_chisq_Qinv(double q, double nu) { return chisq_quantile_Q(q, nu); }
 double hc_chisq_pdf(double x, double nu) { return chisq_density(x, nu); }

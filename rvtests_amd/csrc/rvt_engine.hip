@@ -542,9 +542,10 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
 
 int rvt_block_alloc(rvt_ctx* c, int M, double** out) {
   if (!c || !out || M < 1) return fail(c, RVT_E_INVALID, "bad block");
-  if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first (defines N)");
+  // (a context whose only model is the multiple-trait one, rvt_mt_fit_null: the same layout, ld = rvt_padded_ld(N))
+  if (!c->have_null && !c->have_fam && !c->have_mt) return fail(c, RVT_E_STATE, "set the null model first (defines N)");
   hipSetDevice(c->device);
-  const size_t bytes = sizeof(double) * (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld) * M;
+  const size_t bytes = sizeof(double) * (size_t)(c->have_null ? c->null_ld : (c->have_fam ? c->fam_nc.ld : c->mt_ld)) * M;
   HIP_TRY(c, hipMalloc((void**)out, bytes));
   // cleared on the stream the streaming entry points write blocks on, and complete on return: a hipMemset on the null
   // stream is not ordered against that (non-blocking) stream and could land after a decoder had filled the block
@@ -950,7 +951,7 @@ int staged_h2d_2d(rvt_ctx* c, void* dst, size_t dpitch, const void* src, size_t 
 // (enqueued on io_stream: the block is complete in stream order behind the call, see staged_h2d_2d)
 int upload_block_data(rvt_ctx* c, double* dG, int M, const double* G) {
   if (!c || !dG || !G || M < 1) return fail(c, RVT_E_INVALID, "bad upload");
-  if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first");
+  if (!c->have_null && !c->have_fam && !c->have_mt) return fail(c, RVT_E_STATE, "set the null model first");
   hipSetDevice(c->device);
   if (c->colq.n > 0) {
     int rcq = flush_col_queue(c);
@@ -960,8 +961,8 @@ int upload_block_data(rvt_ctx* c, double* dG, int M, const double* G) {
     auto it = c->col_kind.find(dG);
     if (it != c->col_kind.end()) clear_col_kind(it->second);
   }
-  const size_t N = (size_t)(c->have_null ? c->nc.N : c->fam_nc.N);
-  const size_t bld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
+  const size_t N = (size_t)(c->have_null ? c->nc.N : (c->have_fam ? c->fam_nc.N : c->mt_N));
+  const size_t bld = (size_t)(c->have_null ? c->null_ld : (c->have_fam ? c->fam_nc.ld : c->mt_ld));
   return staged_h2d_2d(c, dG, sizeof(double) * bld, G, sizeof(double) * N, sizeof(double) * N, (size_t)M);
 }
 

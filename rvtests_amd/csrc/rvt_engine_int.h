@@ -467,6 +467,20 @@ struct rvt_ctx {
   int64_t gg_N = 0;
   int gg_d = 0;
   double gg_delta = 0.0, gg_gamma = 0.0, gg_ysy = 0.0, gg_sumty = 0.0, gg_afden = 0.0;
+  // the multiple-trait score test (rvt_mtscore.hip): the centred [Yc | Zc] as kMtPlanes digit planes [plane][row][mt_ldk] (the A
+  // operand of rot_gemm.hip.h, mt_plane bytes apart, per-row exponents mt_row_exp), the distinct indModel patterns as one 0 / 1
+  // plane, the row sums of the stored values, the MtTest constants of the mt_T tests — resident from rvt_mt_fit_null to
+  // rvt_mt_clear, in buffers of their own (d_rotA / d_rotB are rewritten by every integer-plane product) — and the grow-only
+  // work space of rvt_mt_score_block (d_mt_B: the int8 copy of a piece's columns)
+  bool have_mt = false;
+  int64_t mt_N = 0, mt_ld = 0, mt_ldk = 0;
+  int mt_R = 0, mt_K = 0, mt_T = 0;
+  size_t mt_plane = 0;
+  DevBuf<signed char> d_mt_planes, d_mt_pat, d_mt_B;
+  DevBuf<double> d_mt_rowsum;
+  DevBuf<char> d_mt_tests, d_mt_ws;
+  std::vector<int> mt_row_exp;
+  double mt_ms[3] = {0.0, 0.0, 0.0};  // rvt_mt_last_timing
   // streaming interface
   struct Pending {
     int64_t id;
@@ -759,6 +773,10 @@ RVT_INTERNAL int gemm_tn_planes(rvt_ctx* c, const double* dA, int64_t ldA, int n
 RVT_INTERNAL int rvt_planes_gemm(rvt_ctx* c, const signed char* A, size_t a_stride, int PA, int nA, const int* row_exp, int a_exp,
                                  const signed char* B, size_t b_stride, int PB, int nB, const int* col_exp, int64_t n_rows,
                                  int64_t ldk, double* C, int64_t ldc, hipStream_t st, const int2* a_krange = nullptr);
+// quantize_columns into the context's d_mt_B (rvt_mt_score_block's pieces that hold more than hard calls), zero columns up to a
+// multiple of `pad`: the planes, the bytes between them, their number and the ncols column exponents
+RVT_INTERNAL int quantize_columns_mt(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld_src, int ncols, int pad, int64_t ldk,
+                                     hipStream_t st, signed char** planes, size_t* plane_stride, int* n_planes, int* col_exp);
 // ---- defined in rvt_meta.hip: C = A' D [B | B2] in fp64 on the matrix cores (gemm_f64.hip.h)
 RVT_INTERNAL int gemm_tn_f64(rvt_ctx* c, const double* A, int64_t lda, int M, const double* B, int64_t ldb, int Nb, const double* B2,
                              int64_t ldb2, int Nb2, const double* w, int64_t N, double* C, int64_t ldc, bool symmetric,

@@ -890,6 +890,19 @@ int rvt_planes_gemm(rvt_ctx* c, const signed char* A, size_t a_stride, int PA, i
                     double* C, int64_t ldc, hipStream_t st, const int2* a_krange) {
   return planes_gemm(c, A, a_stride, PA, nA, row_exp, a_exp, B, b_stride, PB, nB, col_exp, n_rows, ldk, C, ldc, st, a_krange);
 }
+// (quantize_columns for rvt_mtscore.hip: the B operand of a piece of dosage columns, in the context's d_mt_B)
+int quantize_columns_mt(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld_src, int ncols, int pad, int64_t ldk,
+                        hipStream_t st, signed char** planes, size_t* plane_stride, int* n_planes, int* col_exp) {
+  if (ncols > kRotMaxCols) return fail(c, RVT_E_TOO_LARGE, "integer-plane product: too many columns");
+  QuantCols q;
+  int rc = quantize_columns(c, d_src, n_rows, ld_src, ncols, pad, ldk, c->d_mt_B, st, &q);
+  if (rc) return rc;
+  *planes = q.d;
+  *plane_stride = q.plane_stride;
+  *n_planes = q.planes;
+  std::copy(q.sexp.begin(), q.sexp.end(), col_exp);
+  return RVT_OK;
+}
 int rotate_columns(rvt_ctx* c, const double* d_src, int64_t ld_src, int ncols, double* d_dst, int64_t ld_dst,
                           hipStream_t st) {
   const int64_t N = c->kin_N;

@@ -90,7 +90,7 @@ def build_library(force=False, verbose=False):
     # one object per translation unit, compiled in parallel (the fully unrolled K2 bodies dominate the compile time), then one
     # link.  Every unit leaves a dependency file (-MMD): a unit whose sources are older than its object is not compiled again.
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-function"]
-    units = ["rvt_engine.hip", "rvt_stream.hip", "rvt_fam.hip", "rvt_perm.hip", "rvt_meta.hip", "k2_unweighted.hip", "k2_weighted.hip", "k2_hardcall.hip", "k2_hardcall_w.hip",
+    units = ["rvt_engine.hip", "rvt_stream.hip", "rvt_fam.hip", "rvt_perm.hip", "rvt_meta.hip", "rvt_mtscore.hip", "k2_unweighted.hip", "k2_weighted.hip", "k2_hardcall.hip", "k2_hardcall_w.hip",
              "k2_hardcall_x.hip", "k2_lattice.hip", "k2_packed.hip", "k2_floatdigit.hip"]
 
     def fresh(obj, dep):
@@ -243,6 +243,15 @@ def load_library():
     L.rvt_cov_block_fam.argtypes = [vp, vp, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p]
     L.rvt_score_block.restype = C.c_int
     L.rvt_score_block.argtypes = [vp, vp, C.c_int, c_int_p] + [c_double_p] * 5
+    L.rvt_mt_fit_null.restype = C.c_int
+    L.rvt_mt_fit_null.argtypes = [vp, C.c_int64, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p,
+                                  c_double_p, c_double_p]
+    L.rvt_mt_score_block.restype = C.c_int
+    L.rvt_mt_score_block.argtypes = [vp, vp, C.c_int] + [c_double_p] * 3
+    L.rvt_mt_clear.restype = C.c_int
+    L.rvt_mt_clear.argtypes = [vp]
+    L.rvt_mt_last_timing.restype = C.c_int
+    L.rvt_mt_last_timing.argtypes = [vp, c_double_p]
     L.rvt_wald_block.restype = C.c_int
     L.rvt_wald_block.argtypes = [vp, vp, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
     L.rvt_null_summary.restype = C.c_int
@@ -1025,6 +1034,44 @@ class Engine:
         self._check(self.L.rvt_wald_block(self.ctx, C.c_void_p(int(ptr)), V, ok.ctypes.data_as(c_int_p),
                                           *[_dp(a) for a in arr], rounds.ctypes.data_as(c_int_p)))
         return dict(ok=ok, rounds=rounds, beta=arr[0], se=arr[1], p=arr[2])
+
+    # ---- the multiple-trait score test (--single fastmtscore) ---------------------------------------------------------
+    def mt_fit_null(self, Y, Z, tests):
+        """rvt_mt_fit_null: Y (N x P) and Z (N x Q or None) with NaN = missing, tests = [(phenotype column, [covariate columns]), ..].
+        Returns dict of ok, obs, sigma2 (one entry per test) and sets self.N."""
+        Y = np.asfortranarray(Y, dtype=np.float64)
+        N, P = Y.shape
+        Q = 0 if Z is None else int(np.shape(Z)[1])
+        Zf = np.asfortranarray(Z, dtype=np.float64) if Q else None
+        T = len(tests)
+        pheno = np.array([int(t[0]) for t in tests], dtype=np.int32)
+        ptr = np.zeros(T + 1, dtype=np.int32)
+        ptr[1:] = np.cumsum([len(t[1]) for t in tests])
+        cov = np.array([int(z) for t in tests for z in t[1]] + [0], dtype=np.int32)
+        ok = np.zeros(T, dtype=np.int32)
+        obs, s2 = np.zeros(T), np.zeros(T)
+        self._check(self.L.rvt_mt_fit_null(self.ctx, N, P, _dp(Y), Q, _dp(Zf) if Q else None, T, pheno.ctypes.data_as(c_int_p),
+                                           ptr.ctypes.data_as(c_int_p), cov.ctypes.data_as(c_int_p), ok.ctypes.data_as(c_int_p),
+                                           _dp(obs), _dp(s2)))
+        self.N = N
+        self._mt_T = T
+        return dict(ok=ok, obs=obs, sigma2=s2)
+
+    def mt_score_block(self, ptr, V):
+        """rvt_mt_score_block of the V columns of a device block: dict of U, V, p as V x T arrays."""
+        V, T = int(V), int(getattr(self, "_mt_T", 0) or 1)
+        arr = [np.zeros((V, T)) for _ in range(3)]
+        self._check(self.L.rvt_mt_score_block(self.ctx, C.c_void_p(int(ptr)), V, *[_dp(a) for a in arr]))
+        return dict(U=arr[0], V=arr[1], p=arr[2])
+
+    def mt_clear(self):
+        self._check(self.L.rvt_mt_clear(self.ctx))
+
+    def mt_last_timing(self):
+        """Host milliseconds of the last mt_score_block: genotype pass, products, finishing."""
+        ms = np.zeros(3)
+        self._check(self.L.rvt_mt_last_timing(self.ctx, _dp(ms)))
+        return ms
 
     def score_block_fam(self, ptr, V, binary=0):
         """MetaFamQtl (binary=1: MetaFamBinary) statistics of the V raw columns of a device block (after set_kinship +
