@@ -164,6 +164,37 @@ const ModelParser& ModelParser::assign(const std::string& tag, bool* v, bool def
   return *this;
 }
 
+// ---- pieces the models share --------------------------------------------------------------------------------------------
+namespace {
+const char* const kNoDevice = "no MI355X device: the GPU models have no CPU fallback";
+const rvt_params kDefaultParams{1.0, 25.0, 1.0, 25.0, 0, 0.05};
+const char* const kPermutationHeader = "NumPerm\tActualPerm\tStat\tNumGreater\tNumEqual\tPermPvalue";
+
+// copyCovariateAndIntercept (src/ModelUtil.h:102-130): X = [1 | covariates], N x (1 + ncov) column-major
+std::vector<double> interceptAndCovariates(const GeneData& gd) {
+  std::vector<double> X((size_t)gd.N * (1 + gd.ncov));
+  for (int64_t i = 0; i < gd.N; ++i) X[i] = 1.0;
+  if (gd.ncov) std::memcpy(X.data() + gd.N, gd.covariate, sizeof(double) * (size_t)gd.N * gd.ncov);
+  return X;
+}
+
+// the 1s and the 0s of the phenotype, for rvt_fam_binary_scale's alpha = log(nCase / nCtrl)
+void caseControlCounts(const GeneData& gd, int64_t* nCase, int64_t* nCtrl) {
+  *nCase = *nCtrl = 0;
+  for (int64_t i = 0; i < gd.N; ++i) {
+    if (gd.phenotype[i] == 1) ++*nCase;
+    else if (gd.phenotype[i] == 0) ++*nCtrl;
+  }
+}
+}  // namespace
+
+// Permutation::updateValue + Result::writeValue: ints via toString, doubles via floatToString (src/Result.h:52-63); getPvalue :95-98
+std::string PermutationState::fields(int nPerm) const {
+  const double p = actualPerm == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEqual) / actualPerm;
+  return std::to_string(nPerm) + "\t" + std::to_string(actualPerm) + "\t" + floatToString(obs) + "\t" + std::to_string(numX) + "\t" +
+         std::to_string(numEqual) + "\t" + floatToString(p);
+}
+
 // ---- GpuBroker ----------------------------------------------------------------------------------------------------
 GpuBroker& GpuBroker::instance() {
   static GpuBroker b;
@@ -224,9 +255,7 @@ void GpuBroker::registerTests(uint32_t mask, const rvt_params& p) {
 }
 
 void GpuBroker::shutdown() {
-  if (ctx)
-    for (auto& g : moreGenes) rvt_block_free(ctx, g.block);
-  moreGenes.clear();
+  moreGenes.clear();  // frees their device blocks, while the group still exists
   moreRows.clear();
   moreReady.clear();
   moreY.clear();
@@ -255,9 +284,7 @@ void GpuBroker::shutdown() {
 int GpuBroker::installNull(const GeneData& gd, bool binary, std::string* err) {
   flushBurdenMore();  // the analytic burden tests' pending genes belong to the null model installed so far
   const int d = 1 + gd.ncov;
-  std::vector<double> X((size_t)gd.N * d);
-  for (int64_t i = 0; i < gd.N; ++i) X[i] = 1.0;
-  if (gd.ncov) std::memcpy(X.data() + gd.N, gd.covariate, sizeof(double) * (size_t)gd.N * gd.ncov);
+  const std::vector<double> X = interceptAndCovariates(gd);
   const int trait = binary ? RVT_TRAIT_BINARY : RVT_TRAIT_QUANTITATIVE;
   int rc;
   if (!fitter) {
@@ -283,10 +310,7 @@ int GpuBroker::installNull(const GeneData& gd, bool binary, std::string* err) {
 }
 
 rvt_ctx* GpuBroker::contextWithNull(const GeneData& gd, bool binary, std::string* err) {
-  if (ensureContext(0)) {
-    *err = "no MI355X device: the GPU models have no CPU fallback";
-    return nullptr;
-  }
+  if (!context(err)) return nullptr;
   if (!haveNull || gd.phenotypeUpdated || gd.covariateUpdated)
     if (installNull(gd, binary, err)) return nullptr;
   return ctx;
@@ -294,17 +318,14 @@ rvt_ctx* GpuBroker::contextWithNull(const GeneData& gd, bool binary, std::string
 
 rvt_ctx* GpuBroker::context(std::string* err) {
   if (ensureContext(0)) {
-    *err = "no MI355X device: the GPU models have no CPU fallback";
+    *err = kNoDevice;
     return nullptr;
   }
   return ctx;
 }
 
 rvt_ctx* GpuBroker::contextWithFamNull(const GeneData& gd, std::string* err) {
-  if (ensureContext(0)) {
-    *err = "no MI355X device: the GPU models have no CPU fallback";
-    return nullptr;
-  }
+  if (!context(err)) return nullptr;
   if (kinU != gd.kinshipU) {  // a new decomposition (autosomes vs X region in the reference): install it once
     if (rvt_set_kinship(ctx, gd.N, gd.kinshipU, gd.kinshipS)) {
       *err = rvt_last_error(ctx);
@@ -314,11 +335,7 @@ rvt_ctx* GpuBroker::contextWithFamNull(const GeneData& gd, std::string* err) {
     haveFamNull = false;
   }
   if (!haveFamNull || gd.phenotypeUpdated || gd.covariateUpdated) {
-    const int d = 1 + gd.ncov;  // copyCovariateAndIntercept (src/ModelUtil.h:102-130)
-    std::vector<double> X((size_t)gd.N * d);
-    for (int64_t i = 0; i < gd.N; ++i) X[i] = 1.0;
-    if (gd.ncov) std::memcpy(X.data() + gd.N, gd.covariate, sizeof(double) * (size_t)gd.N * gd.ncov);
-    if (rvt_fit_fam_null(ctx, gd.N, d, X.data(), gd.phenotype, &famNull)) {
+    if (rvt_fit_fam_null(ctx, gd.N, 1 + gd.ncov, interceptAndCovariates(gd).data(), gd.phenotype, &famNull)) {
       *err = "SKAT test (for related individuals) failed in fitting null model (SKAT)";
       return nullptr;
     }
@@ -332,22 +349,25 @@ const rvt_gene_result* GpuBroker::famResultFor(const GeneData& gd, std::string* 
   famSerial = gd.serial;
   famOk = false;
   rvt_ctx* cx = contextWithFamNull(gd, err);
-  if (!cx) return nullptr;
-  double* block = nullptr;
-  if (rvt_block_alloc(cx, gd.M, &block) || rvt_block_upload(cx, block, gd.M, gd.genotype)) {
-    *err = rvt_last_error(cx);
-    if (block) rvt_block_free(cx, block);
+  if (withGene(cx, gd, err, [&](const double* const* block, const int* M) {
+        return rvt_run_fam_tests(cx, 1, block, M, &gd.serial, famTests, &famRec);
+      }))
     return nullptr;
-  }
-  const double* p = block;
-  const int rc = rvt_run_fam_tests(cx, 1, &p, &gd.M, &gd.serial, famTests, &famRec);
-  rvt_block_free(cx, block);
-  if (rc) {
-    *err = rvt_last_error(cx);
-    return nullptr;
-  }
   famOk = true;
   return &famRec;
+}
+
+int GpuBroker::withGene(rvt_ctx* cx, const GeneData& gd, std::string* err, const GeneCall& call) {
+  if (!cx) return -1;
+  int rc;
+  {
+    DeviceBlock block;
+    if (block.alloc(cx, gd.M, err) || block.upload(gd.M, gd.genotype, err)) return -1;
+    const double* p = block.get();
+    rc = call(&p, &gd.M);
+  }  // (the block is freed before the call's error text is read)
+  if (rc) *err = rvt_last_error(cx);
+  return rc ? -1 : 0;
 }
 
 int GpuBroker::submit(const GeneData& gd, bool binary, std::string* err) {
@@ -369,7 +389,7 @@ int GpuBroker::submit(const GeneData& gd, bool binary, std::string* err) {
     return -1;
   };
   if (ensureContext(0)) {
-    *err = "no MI355X device: the GPU models have no CPU fallback";
+    *err = kNoDevice;
     return failed();
   }
   if (!haveNull || gd.phenotypeUpdated || gd.covariateUpdated) {
@@ -398,7 +418,7 @@ int GpuBroker::submit(const GeneData& gd, bool binary, std::string* err) {
   return 0;
 }
 
-void GpuBroker::enqueue(ModelFitter* m, TextSink* fp, const std::string& siteTab, int64_t serial) {
+void GpuBroker::enqueue(DeferredGeneTest* m, TextSink* fp, const std::string& siteTab, int64_t serial) {
   rows.push_back(Row{m, fp, siteTab, serial});
 }
 
@@ -457,30 +477,28 @@ int GpuBroker::flush() {
   return rc ? rc : rcMore;
 }
 
-int ModelFitter::deferredFit(GeneData* dc) {
+// ---- DeferredGeneTest ------------------------------------------------------------------------------------------------------
+DeferredGeneTest::DeferredGeneTest(const char* name, uint32_t test, const rvt_params& p, const std::string& header_)
+    : header(header_) {
+  modelName = name;
+  if (test) GpuBroker::instance().registerTests(test, p);
+}
+int DeferredGeneTest::fit(GeneData* dc) {
   curSerial = dc->serial;
   return GpuBroker::instance().submit(*dc, isBinaryOutcome(), &lastError);
 }
-void ModelFitter::deferredOutput(TextSink* fp, const SiteInfo& siteInfo) {
+void DeferredGeneTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) { fp->write(siteInfo.headerTab() + header); }
+void DeferredGeneTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   GpuBroker::instance().enqueue(this, fp, siteInfo.valueTab(), curSerial);
 }
+void DeferredGeneTest::writeFootnote(TextSink*) { GpuBroker::instance().flush(); }
 
 // ---- SkatTest ----------------------------------------------------------------------------------------------------------
-SkatTest::SkatTest(int nPerm, double alpha, double beta1, double beta2) : usePermutation(nPerm > 0) {
-  modelName = "Skat";
-  rvt_params p{beta1, beta2, 1.0, 25.0, nPerm, alpha};
-  GpuBroker::instance().registerTests(RVT_TEST_SKAT, p);
-}
-int SkatTest::fit(GeneData* dc) { return deferredFit(dc); }
-void SkatTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  if (!usePermutation)
-    fp->write("Q\tPvalue\n");
-  else  // Permutation::writeHeader (src/Permutation.h:51-56,99-104)
-    fp->write("Q\tPvalue\tNumPerm\tActualPerm\tStat\tNumGreater\tNumEqual\tPermPvalue\n");
-}
-void SkatTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) { deferredOutput(fp, siteInfo); }
-void SkatTest::writeFootnote(TextSink*) { GpuBroker::instance().flush(); }
+SkatTest::SkatTest(int nPerm, double alpha, double beta1, double beta2)
+    : DeferredGeneTest("Skat", RVT_TEST_SKAT, rvt_params{beta1, beta2, 1.0, 25.0, nPerm, alpha},
+                       // with permutations: Permutation::writeHeader (src/Permutation.h:51-56,99-104)
+                       nPerm > 0 ? std::string("Q\tPvalue\t") + kPermutationHeader + "\n" : "Q\tPvalue\n"),
+      usePermutation(nPerm > 0) {}
 std::string SkatTest::formatRow(const rvt_gene_result* res) const {
   // fitOK: genotype.cols == 0 after filtering -> NA row (src/Model.h:2665-2668)
   if (!res || !res->skat_ok || (usePermutation && !res->perm_ok))
@@ -494,18 +512,8 @@ std::string SkatTest::formatRow(const rvt_gene_result* res) const {
 }
 
 // ---- SkatOTest -----------------------------------------------------------------------------------------------------------
-SkatOTest::SkatOTest(double beta1, double beta2) {
-  modelName = "SkatO";
-  rvt_params p{1.0, 25.0, beta1, beta2, 0, 0.05};
-  GpuBroker::instance().registerTests(RVT_TEST_SKATO, p);
-}
-int SkatOTest::fit(GeneData* dc) { return deferredFit(dc); }
-void SkatOTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write("Q\trho\tPvalue\n");
-}
-void SkatOTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) { deferredOutput(fp, siteInfo); }
-void SkatOTest::writeFootnote(TextSink*) { GpuBroker::instance().flush(); }
+SkatOTest::SkatOTest(double beta1, double beta2)
+    : DeferredGeneTest("SkatO", RVT_TEST_SKATO, rvt_params{1.0, 25.0, beta1, beta2, 0, 0.05}, "Q\trho\tPvalue\n") {}
 std::string SkatOTest::formatRow(const rvt_gene_result* res) const {
   // fitOK = (skato.Fit(...) == 0) (src/Model.h:2853-2859)
   if (!res || res->n_poly == 0 || !res->skato_ok) return "NA\tNA\tNA\n";
@@ -513,44 +521,24 @@ std::string SkatOTest::formatRow(const rvt_gene_result* res) const {
 }
 
 // ---- CMCTest / ZegginiTest -------------------------------------------------------------------------------------------------
-CMCTest::CMCTest() {
-  modelName = "CMC";
-  GpuBroker::instance().registerTests(RVT_TEST_CMC, rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05});
-}
-int CMCTest::fit(GeneData* dc) { return deferredFit(dc); }
-void CMCTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write("NonRefSite\tPvalue\n");
-}
-void CMCTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) { deferredOutput(fp, siteInfo); }
-void CMCTest::writeFootnote(TextSink*) { GpuBroker::instance().flush(); }
+CMCTest::CMCTest() : DeferredGeneTest("CMC", RVT_TEST_CMC, kDefaultParams, "NonRefSite\tPvalue\n") {}
 std::string CMCTest::formatRow(const rvt_gene_result* res) const {
   if (!res || !res->cmc_ok) return "NA\tNA\n";
   return std::to_string(res->cmc_nonref) + "\t" + floatToString(res->cmc_p) + "\n";
 }
 
-ZegginiTest::ZegginiTest() {
-  modelName = "Zeggini";
-  GpuBroker::instance().registerTests(RVT_TEST_ZEGGINI, rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05});
-}
-int ZegginiTest::fit(GeneData* dc) { return deferredFit(dc); }
-void ZegginiTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write("Pvalue\n");
-}
-void ZegginiTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) { deferredOutput(fp, siteInfo); }
-void ZegginiTest::writeFootnote(TextSink*) { GpuBroker::instance().flush(); }
+ZegginiTest::ZegginiTest() : DeferredGeneTest("Zeggini", RVT_TEST_ZEGGINI, kDefaultParams, "Pvalue\n") {}
 std::string ZegginiTest::formatRow(const rvt_gene_result* res) const {
   return (res && res->zeg_ok) ? floatToString(res->zeg_p) + "\n" : std::string("NA\n");
 }
 
 // ---- AnalyticVTTest ---------------------------------------------------------------------------------------------------------
-AnalyticVTTest::AnalyticVTTest(bool related_) : related(related_) {
-  modelName = related ? "FamAnalyticVT" : "AnalyticVT";
-  if (!related) GpuBroker::instance().registerTests(RVT_TEST_ANALYTICVT, rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05});
-}
+AnalyticVTTest::AnalyticVTTest(bool related_)
+    : DeferredGeneTest(related_ ? "FamAnalyticVT" : "AnalyticVT", related_ ? 0 : RVT_TEST_ANALYTICVT, kDefaultParams,
+                       "MinMAF\tMaxMAF\tOptimMAF\tOptimNumVar\tU\tV\tStat\tPvalue\n"),  // result.addHeader order, src/Model.h:2123-2130
+      related(related_) {}
 int AnalyticVTTest::fit(GeneData* dc) {
-  if (!related) return deferredFit(dc);
+  if (!related) return DeferredGeneTest::fit(dc);
   fitOK = false;
   if (isBinaryOutcome()) {  // src/Model.h:2143-2149
     lastError = "Analytic VT test does not support binary outcomes. Results will be all NAs.";
@@ -561,38 +549,22 @@ int AnalyticVTTest::fit(GeneData* dc) {
     return -1;
   }
   rvt_ctx* ctx = GpuBroker::instance().contextWithFamNull(*dc, &lastError);
-  if (!ctx) return -1;
-  double* block = nullptr;
-  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    if (block) rvt_block_free(ctx, block);
+  if (GpuBroker::withGene(ctx, *dc, &lastError,
+                          [&](const double* const* block, const int* M) { return rvt_fam_analytic_vt(ctx, 1, block, M, &rec); }))
     return -1;
-  }
-  const double* bp = block;
-  const int M = dc->M;
-  const int rc = rvt_fam_analytic_vt(ctx, 1, &bp, &M, &rec);
-  rvt_block_free(ctx, block);
-  if (rc) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
   fitOK = rec.vt_ok != 0;
   return fitOK ? 0 : -1;
 }
-void AnalyticVTTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write("MinMAF\tMaxMAF\tOptimMAF\tOptimNumVar\tU\tV\tStat\tPvalue\n");  // result.addHeader order, src/Model.h:2123-2130
-}
 void AnalyticVTTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   if (!related) {
-    deferredOutput(fp, siteInfo);
+    DeferredGeneTest::writeOutput(fp, siteInfo);
     return;
   }
   fp->write(siteInfo.valueTab());
   fp->write(formatRow(fitOK ? &rec : nullptr));
 }
-void AnalyticVTTest::writeFootnote(TextSink*) {
-  if (!related) GpuBroker::instance().flush();
+void AnalyticVTTest::writeFootnote(TextSink* fp) {
+  if (!related) DeferredGeneTest::writeFootnote(fp);
 }
 std::string AnalyticVTTest::formatRow(const rvt_gene_result* r) const {
   // not fitted (binary trait, no polymorphic site, no usable threshold, integral not converged to 1e-3): the Result keeps
@@ -616,28 +588,14 @@ int KbacTest::fit(GeneData* dc) {
     return -1;
   }
   rvt_ctx* ctx = GpuBroker::instance().contextWithNull(*dc, true, &lastError);  // (the null model defines N on the device)
-  if (!ctx) return -1;
-  double* block = nullptr;
-  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    if (block) rvt_block_free(ctx, block);
+  if (GpuBroker::withGene(ctx, *dc, &lastError, [&](const double* const* block, const int* M) {
+        return rvt_kbac_blocks(ctx, 1, block, M, dc->markerFrequency.data(), dc->phenotype, nPerm, alpha, &rec);
+      }))
     return -1;
-  }
-  const double* bp = block;
-  const int M = dc->M;
-  const int rc = rvt_kbac_blocks(ctx, 1, &bp, &M, dc->markerFrequency.data(), dc->phenotype, nPerm, alpha, &rec);
-  rvt_block_free(ctx, block);
-  if (rc) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
   fitOK = rec.fit_ok != 0;
   return fitOK ? 0 : -1;
 }
-void KbacTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write("Pvalue\n");
-}
+void KbacTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) { fp->write(siteInfo.headerTab() + "Pvalue\n"); }
 void KbacTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.valueTab());
   if (!fitOK) {
@@ -653,69 +611,31 @@ void KbacTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
 VariableThresholdPrice::VariableThresholdPrice(int nPerm_, double alpha_) : nPerm(nPerm_), alpha(alpha_) {
   modelName = "VariableThresholdPrice";
 }
-void VariableThresholdPrice::reset() {  // src/Model.h:1820-1824 over Permutation::reset (src/Permutation.h:99-105)
-  fitOK = false;
-  obs = 0.0;
-  actualPerm = numX = numEqual = 0;
-}
 int VariableThresholdPrice::fit(GeneData* dc) {
   fitOK = false;
   rvt_ctx* ctx = GpuBroker::instance().contextWithNull(*dc, isBinaryOutcome(), &lastError);  // (the null model defines N on the device)
-  if (!ctx) return -1;
-  double* block = nullptr;
-  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    if (block) rvt_block_free(ctx, block);
+  if (GpuBroker::withGene(ctx, *dc, &lastError, [&](const double* const* block, const int* M) {
+        return rvt_vtprice_blocks(ctx, 1, block, M, dc->markerFrequency.data(), dc->phenotype, nPerm, alpha, &rec);
+      }))
     return -1;
-  }
-  const double* bp = block;
-  const int M = dc->M;
-  const int rc = rvt_vtprice_blocks(ctx, 1, &bp, &M, dc->markerFrequency.data(), dc->phenotype, nPerm, alpha, &rec);
-  rvt_block_free(ctx, block);
-  if (rc) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
   fitOK = rec.fit_ok != 0;
   if (!fitOK) return -1;  // genotype.cols == 0: nothing below was touched (src/Model.h:1758-1761)
   zmax = rec.zmax;
   optimalFreq = rec.opt_freq;
-  obs = rec.zmax;  // perm.init(fabs(zmax))
-  actualPerm = rec.actual_perm;
-  numX = rec.num_greater;
-  numEqual = rec.num_equal;
+  perm.take(rec, rec.zmax);  // perm.init(fabs(zmax))
   return 0;
 }
 void VariableThresholdPrice::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write("\tOptFreq\tZmax\t");  // (after writeHeaderTab's own tab: an empty column, src/Model.h:1808-1809)
-  fp->write("NumPerm\tActualPerm\tStat\tNumGreater\tNumEqual\tPermPvalue\n");
+  // (after writeHeaderTab's own tab: an empty column, src/Model.h:1808-1809)
+  fp->write(siteInfo.headerTab() + "\tOptFreq\tZmax\t" + kPermutationHeader + "\n");
 }
 void VariableThresholdPrice::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.valueTab());
-  // Permutation::updateValue: ints via toString, doubles via floatToString (src/Result.h:52-63); getPvalue :95-98
-  const double p = actualPerm == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEqual) / actualPerm;
-  fp->write("\t" + formatG(optimalFreq) + "\t" + formatG(zmax) + "\t" + std::to_string(nPerm) + "\t" + std::to_string(actualPerm) +
-            "\t" + floatToString(obs) + "\t" + std::to_string(numX) + "\t" + std::to_string(numEqual) + "\t" + floatToString(p) +
-            "\n");
+  fp->write("\t" + formatG(optimalFreq) + "\t" + formatG(zmax) + "\t" + perm.fields(nPerm) + "\n");
 }
 
 // ---- RareCoverTest / MadsonBrowningTest -----------------------------------------------------------------------------------------
-namespace {
-// Permutation::updateValue + Result::writeValue: ints via toString, doubles via floatToString (src/Result.h:52-63); getPvalue :95-98
-std::string permutationFields(int nPerm, int actualPerm, double obs, int numX, int numEqual) {
-  const double p = actualPerm == 0 ? 1.0 : 1.0 * (numX + 0.5 * numEqual) / actualPerm;
-  return std::to_string(nPerm) + "\t" + std::to_string(actualPerm) + "\t" + floatToString(obs) + "\t" + std::to_string(numX) + "\t" +
-         std::to_string(numEqual) + "\t" + floatToString(p);
-}
-const char* const kPermutationHeader = "NumPerm\tActualPerm\tStat\tNumGreater\tNumEqual\tPermPvalue";
-}  // namespace
-
 RareCoverTest::RareCoverTest(int nPerm_, double alpha_) : nPerm(nPerm_), alpha(alpha_) { modelName = "RareCover"; }
-void RareCoverTest::reset() {  // src/Model.h:1477-1480 over Permutation::reset (src/Permutation.h:99-105)
-  obs = 0.0;
-  actualPerm = numX = numEqual = 0;
-}
 int RareCoverTest::fit(GeneData* dc) {
   fitOK = false;
   if (!isBinaryOutcome()) {  // src/Model.h:1432-1438
@@ -727,45 +647,25 @@ int RareCoverTest::fit(GeneData* dc) {
     return -1;
   }
   rvt_ctx* ctx = GpuBroker::instance().contextWithNull(*dc, true, &lastError);  // (the null model defines N on the device)
-  if (!ctx) return -1;
-  double* block = nullptr;
-  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    if (block) rvt_block_free(ctx, block);
+  if (GpuBroker::withGene(ctx, *dc, &lastError, [&](const double* const* block, const int* M) {
+        return rvt_rarecover_blocks(ctx, 1, block, M, dc->phenotype, nPerm, alpha, &rec);
+      }))
     return -1;
-  }
-  const double* bp = block;
-  const int M = dc->M;
-  const int rc = rvt_rarecover_blocks(ctx, 1, &bp, &M, dc->phenotype, nPerm, alpha, &rec);
-  rvt_block_free(ctx, block);
-  if (rc) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
   fitOK = rec.fit_ok != 0;
   if (!fitOK) return -1;  // genotype.cols == 0: perm.init was not reached (src/Model.h:1448-1451)
   numSelected = rec.n_selected;
-  obs = rec.stat;
-  actualPerm = rec.actual_perm;
-  numX = rec.num_greater;
-  numEqual = rec.num_equal;
+  perm.take(rec, rec.stat);
   return 0;
 }
 void RareCoverTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write(std::string("NumIncludeMarker\t") + kPermutationHeader + "\n");
+  fp->write(siteInfo.headerTab() + "NumIncludeMarker\t" + kPermutationHeader + "\n");
 }
 void RareCoverTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.valueTab());
-  fp->write((fitOK ? std::to_string(numSelected) : std::string("NA")) + "\t" + permutationFields(nPerm, actualPerm, obs, numX, numEqual) +
-            "\n");
+  fp->write((fitOK ? std::to_string(numSelected) : std::string("NA")) + "\t" + perm.fields(nPerm) + "\n");
 }
 
 MadsonBrowningTest::MadsonBrowningTest(int nPerm_, double alpha_) : nPerm(nPerm_), alpha(alpha_) { modelName = "MadsonBrowning"; }
-void MadsonBrowningTest::reset() {  // src/Model.h:1306-1309
-  obs = 0.0;
-  actualPerm = numX = numEqual = 0;
-}
 int MadsonBrowningTest::fit(GeneData* dc) {
   fitOK = false;
   if (!isBinaryOutcome()) {  // src/Model.h:1257-1263
@@ -773,27 +673,13 @@ int MadsonBrowningTest::fit(GeneData* dc) {
     return -1;
   }
   rvt_ctx* ctx = GpuBroker::instance().contextWithNull(*dc, true, &lastError);  // the logistic null model, covariates included
-  if (!ctx) return -1;
-  double* block = nullptr;
-  if (rvt_block_alloc(ctx, dc->M, &block) || rvt_block_upload(ctx, block, dc->M, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    if (block) rvt_block_free(ctx, block);
+  if (GpuBroker::withGene(ctx, *dc, &lastError, [&](const double* const* block, const int* M) {
+        return rvt_mb_blocks(ctx, 1, block, M, dc->phenotype, nPerm, alpha, &rec);
+      }))
     return -1;
-  }
-  const double* bp = block;
-  const int M = dc->M;
-  const int rc = rvt_mb_blocks(ctx, 1, &bp, &M, dc->phenotype, nPerm, alpha, &rec);
-  rvt_block_free(ctx, block);
-  if (rc) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
   if (rec.n_poly == 0 || (!rec.fit_ok && rec.actual_perm == 0 && rec.stat == 0.0)) return -1;  // perm.init was not reached
   fitOK = rec.fit_ok != 0;  // (0 here: the eleventh failed shuffle — the counters printed are those reached)
-  obs = rec.stat;
-  actualPerm = rec.actual_perm;
-  numX = rec.num_greater;
-  numEqual = rec.num_equal;
+  perm.take(rec, rec.stat);
   return fitOK ? 0 : -1;
 }
 void MadsonBrowningTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
@@ -807,7 +693,7 @@ void MadsonBrowningTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
 void MadsonBrowningTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.valueTab());
   if (isBinaryOutcome())
-    fp->write(permutationFields(nPerm, actualPerm, obs, numX, numEqual) + "\n");
+    fp->write(perm.fields(nPerm) + "\n");
   else
     fp->write("NA\n");
 }
@@ -839,12 +725,8 @@ int GpuBroker::submitBurdenMore(const GeneData& gd, bool binary, std::string* er
     *err = "marker frequencies missing";
     return -1;
   }
-  MoreGene g{gd.serial, nullptr, gd.M, 1 + gd.ncov, {}};
-  if (rvt_block_alloc(cx, gd.M, &g.block) || rvt_block_upload(cx, g.block, gd.M, gd.genotype)) {
-    *err = rvt_last_error(cx);
-    if (g.block) rvt_block_free(cx, g.block);
-    return -1;
-  }
+  MoreGene g{gd.serial, DeviceBlock(), gd.M, 1 + gd.ncov, {}};
+  if (g.block.alloc(cx, gd.M, err) || g.block.upload(gd.M, gd.genotype, err)) return -1;
   g.af.assign(gd.markerFrequency.begin(), gd.markerFrequency.begin() + gd.M);
   if (moreGenes.empty()) moreY.assign(gd.phenotype, gd.phenotype + gd.N);
   moreGenes.push_back(std::move(g));
@@ -881,7 +763,7 @@ int GpuBroker::flushBurdenMore() {
     std::vector<int> Ms((size_t)n);
     std::vector<double> af;
     for (int g = 0; g < n; ++g) {
-      ptr[g] = moreGenes[g].block;
+      ptr[g] = moreGenes[g].block.get();
       Ms[g] = moreGenes[g].M;
       af.insert(af.end(), moreGenes[g].af.begin(), moreGenes[g].af.end());
     }
@@ -891,9 +773,8 @@ int GpuBroker::flushBurdenMore() {
       warnOnce(std::string("burden tests failed: ") + rvt_last_error(ctx) + ". Results will be all NAs.");
     else
       for (int g = 0; g < n; ++g) moreReady[moreGenes[g].serial] = MoreRecord{recs[g], moreGenes[g].d};
-    for (auto& g : moreGenes) rvt_block_free(ctx, g.block);
   }
-  moreGenes.clear();
+  moreGenes.clear();  // frees their device blocks
   moreBytes = 0;
   writeReadyMoreRows();
   return rc;
@@ -986,10 +867,7 @@ int FamSkatTest::fit(GeneData* dc) {
   fitOK = true;
   return 0;
 }
-void FamSkatTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write("Q\tPvalue\n");
-}
+void FamSkatTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) { fp->write(siteInfo.headerTab() + "Q\tPvalue\n"); }
 void FamSkatTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.valueTab());
   if (!fitOK)
@@ -1023,8 +901,7 @@ int FamBurdenTest::fit(GeneData* dc) {
   return 0;
 }
 void FamBurdenTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
-  fp->write(siteInfo.headerTab());
-  fp->write(zeggini ? "NumSite\tMeanBurden\tU\tV\tEffect\tPvalue\n" : "NumSite\tAF\tU\tV\tEffect\tPvalue\n");
+  fp->write(siteInfo.headerTab() + (zeggini ? "NumSite\tMeanBurden\tU\tV\tEffect\tPvalue\n" : "NumSite\tAF\tU\tV\tEffect\tPvalue\n"));
 }
 void FamBurdenTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.valueTab());
@@ -1038,14 +915,38 @@ void FamBurdenTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
             floatToString(v) + "\t" + floatToString(effect) + "\t" + floatToString(p) + "\n");
 }
 
-// ---- MetaScoreTest (src/Model.h:3155-3398), unrelated samples ------------------------------------------------------------
-MetaScoreTest::MetaScoreTest() {
-  modelName = "MetaScore";
-  if (const char* e = getenv("RVT_METASCORE_BLOCK")) capacity = std::max(1, std::min(65536, atoi(e)));
+// ---- ColumnBlockTest: one site per fit(), one device call per block of sites ------------------------------------------------
+ColumnBlockTest::ColumnBlockTest(const char* capacityEnv) {
+  if (const char* e = getenv(capacityEnv)) capacity = std::max(1, std::min(65536, atoi(e)));
 }
+int ColumnBlockTest::makeRoom(size_t pendingRows) {
+  if ((int)pendingRows >= capacity && used > 0 && flush()) return -1;
+  if (used >= capacity) {  // flush() could not run: no writeOutput() has named the output sink yet
+    lastError = getModelName() + ": the device block is full and no output was requested for its sites";
+    return -1;
+  }
+  return 0;
+}
+int ColumnBlockTest::sameSampleSize(const GeneData& dc) {
+  if (nSample < 0 || nSample == dc.N) return 0;
+  lastError = "Sample size changed";
+  return -1;
+}
+int ColumnBlockTest::allocateOnFirstUse(const GeneData& dc) {
+  if (nSample >= 0) return 0;
+  nSample = dc.N;
+  nCovariate = dc.ncov + 1;
+  return block.alloc(ctx, capacity, &lastError);
+}
+void ColumnBlockTest::writeFootnote(TextSink* fp) {
+  fout = fp;
+  flush();
+}
+
+// ---- MetaScoreTest (src/Model.h:3155-3398), unrelated samples ------------------------------------------------------------
+MetaScoreTest::MetaScoreTest() : ColumnBlockTest("RVT_METASCORE_BLOCK") { modelName = "MetaScore"; }
 MetaScoreTest::~MetaScoreTest() {
   if (fout) flush();
-  if (ctx && block) rvt_block_free(ctx, block);
 }
 int MetaScoreTest::setParameter(const ModelParser& parser) {
   outputSE = parser.hasTag("se");  // src/Model.h:3177-3182 ("gwama" / "bolt" are not provided)
@@ -1053,11 +954,7 @@ int MetaScoreTest::setParameter(const ModelParser& parser) {
 }
 int MetaScoreTest::fit(GeneData* dc) {
   useFamilyModel = dc->kinshipU != nullptr;  // dc->hasKinship(): MetaFamQtl / MetaFamBinary (src/Model.h:3398-3668)
-  if ((int)rows.size() >= capacity && used > 0 && flush()) return -1;
-  if (used >= capacity) {  // flush() could not run: no writeOutput() has named the output sink yet
-    lastError = "MetaScore: the device block is full and no output was requested for its sites";
-    return -1;
-  }
+  if (makeRoom(rows.size())) return -1;
   rows.emplace_back();
   Row& row = rows.back();
   row.all = dc->counter;  // site statistics are printed whether or not the test runs (src/Model.h:3211-3230)
@@ -1066,47 +963,25 @@ int MetaScoreTest::fit(GeneData* dc) {
     row.ctrls = dc->ctrlCounter;
   }
   if (dc->N == 0) return -1;
-  if (nSample >= 0 && nSample != dc->N) {
-    lastError = "Sample size changed";
-    return -1;
-  }
-  if ((nSample >= 0) && (dc->phenotypeUpdated || dc->covariateUpdated) && used > 0) {
-    // rows tested so far belong to the previous null model: finish them before it is replaced
-    Row keep = row;
-    rows.pop_back();
-    if (flush()) return -1;
-    rows.push_back(keep);
-  }
+  if (sameSampleSize(*dc)) return -1;
+  if (flushBeforeNewNull(*dc, &rows)) return -1;
   ctx = useFamilyModel ? GpuBroker::instance().contextWithFamNull(*dc, &lastError)
                        : GpuBroker::instance().contextWithNull(*dc, isBinaryOutcome(), &lastError);
   if (!ctx) return -1;
   if (useFamilyModel && isBinaryOutcome() && (nSample < 0 || dc->phenotypeUpdated)) {
     // MetaFamBinary::FitNullModel (src/Model.h:3566-3581): alpha = log(nCase / nCtrl), b = calculateB()
-    int64_t nCase = 0, nCtrl = 0;
-    for (int64_t i = 0; i < dc->N; ++i) {
-      if (dc->phenotype[i] == 1) ++nCase;
-      else if (dc->phenotype[i] == 0) ++nCtrl;
-    }
+    int64_t nCase, nCtrl;
+    caseControlCounts(*dc, &nCase, &nCtrl);
     if (rvt_fam_binary_scale(ctx, nCase, nCtrl, nullptr, &famB)) {
       lastError = rvt_last_error(ctx);
       return -1;
     }
   }
-  if (nSample < 0) {
-    nSample = dc->N;
-    nCovariate = dc->ncov + 1;
-    if (rvt_block_alloc(ctx, capacity, &block)) {
-      lastError = rvt_last_error(ctx);
-      return -1;
-    }
-  }
+  if (allocateOnFirstUse(*dc)) return -1;
   if (dc->M != 1) return -1;  // "sanity check, this should not happen" (src/Model.h:3241-3244)
   // the caller overwrites the genotype buffer for the next site: copy the column into the device block now; whether
   // the site is monomorphic (src/Model.h:3246-3250) is decided on the device when the block is processed
-  if (rvt_block_upload_columns(ctx, block, used, 1, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
+  if (block.uploadColumn(used, dc->genotype, &lastError)) return -1;
   rows.back().column = used++;
   rows.back().tested = true;
   return 0;
@@ -1121,10 +996,6 @@ void MetaScoreTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo) {
   if (rows.empty() || rows.back().written) rows.emplace_back();  // writeOutput without a fit(): counters unknown
   rows.back().siteTab = siteInfo.valueTab();
   rows.back().written = true;
-}
-void MetaScoreTest::writeFootnote(TextSink* fp) {
-  fout = fp;
-  flush();
 }
 
 namespace {
@@ -1148,9 +1019,9 @@ int MetaScoreTest::flush() {
   std::vector<double> famAf(ok.size());
   if (used > 0) {
     const int rc = useFamilyModel
-                       ? rvt_score_block_fam(ctx, block, used, isBinaryOutcome() ? 1 : 0, ok.data(), u.data(), v.data(),
+                       ? rvt_score_block_fam(ctx, block.get(), used, isBinaryOutcome() ? 1 : 0, ok.data(), u.data(), v.data(),
                                              famAf.data(), pv.data())
-                       : rvt_score_block(ctx, block, used, ok.data(), u.data(), v.data(), eff.data(), se.data(),
+                       : rvt_score_block(ctx, block.get(), used, ok.data(), u.data(), v.data(), eff.data(), se.data(),
                                          pv.data());
     if (rc) {
       lastError = rvt_last_error(ctx);
@@ -1245,18 +1116,8 @@ std::string GeneData::columnLabel() const {
   return site->get("CHROM") + ":" + site->get("POS");
 }
 
-SingleVariantBlockTest::SingleVariantBlockTest() {
-  if (const char* e = getenv("RVT_SINGLE_BLOCK")) capacity = std::max(1, std::min(65536, atoi(e)));
-}
-SingleVariantBlockTest::~SingleVariantBlockTest() {
-  if (ctx && block) rvt_block_free(ctx, block);
-}
 int SingleVariantBlockTest::fit(GeneData* dc) {
-  if ((int)rows.size() >= capacity && used > 0 && flush()) return -1;
-  if (used >= capacity) {  // flush() could not run: no writeOutput() has named the output sink yet
-    lastError = getModelName() + ": the device block is full and no output was requested for its sites";
-    return -1;
-  }
+  if (makeRoom(rows.size())) return -1;
   rows.emplace_back();
   Row& row = rows.back();
   // X = [1, g, cov] is built (and its labels with it) before the monomorphic check (src/Model.h:117-129)
@@ -1264,33 +1125,14 @@ int SingleVariantBlockTest::fit(GeneData* dc) {
   for (int k = 0; k < dc->ncov; ++k) row.labels.push_back(k < (int)covLabel.size() ? covLabel[k] : std::string());
   row.af = dc->M == 1 && dc->markerFrequency.size() == 1 ? dc->markerFrequency[0] : dc->counter.af;  // getMarkerFrequency(dc, 0)
   if (dc->M != 1 || dc->N == 0) return -1;  // genotype.cols != 1
-  if (nSample >= 0 && nSample != dc->N) {
-    lastError = "Sample size changed";
-    return -1;
-  }
-  if (nSample >= 0 && (dc->phenotypeUpdated || dc->covariateUpdated) && used > 0) {
-    // rows tested so far belong to the previous null model: finish them before it is replaced
-    Row keep = row;
-    rows.pop_back();
-    if (flush()) return -1;
-    rows.push_back(keep);
-  }
+  if (sameSampleSize(*dc)) return -1;
+  if (flushBeforeNewNull(*dc, &rows)) return -1;
   ctx = acquireContext(dc);
   if (!ctx) return -1;
-  if (nSample < 0) {
-    nSample = dc->N;
-    nCovariate = dc->ncov + 1;
-    if (rvt_block_alloc(ctx, capacity, &block)) {
-      lastError = rvt_last_error(ctx);
-      return -1;
-    }
-  }
+  if (allocateOnFirstUse(*dc)) return -1;
   // the caller overwrites the genotype buffer for the next site: copy the column into the device block now; whether the site
   // is monomorphic is decided on the device when the block is processed
-  if (rvt_block_upload_columns(ctx, block, used, 1, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
+  if (block.uploadColumn(used, dc->genotype, &lastError)) return -1;
   rows.back().column = used++;
   return 0;
 }
@@ -1303,14 +1145,11 @@ void SingleVariantBlockTest::writeOutput(TextSink* fp, const SiteInfo& siteInfo)
   rows.back().siteTab = siteInfo.valueTab();
   rows.back().written = true;
 }
-void SingleVariantBlockTest::writeFootnote(TextSink* fp) {
-  fout = fp;
-  flush();
-}
 int SingleVariantBlockTest::flush() {
   if (!fout) return 0;
   ok.assign(std::max(used, 1), 0);
-  const bool ran = used > 0 && runBlock();
+  const bool ran = used > 0 && runBlock() == 0;
+  if (used > 0 && !ran) lastError = rvt_last_error(ctx);
   if (!ran) std::fill(ok.begin(), ok.end(), 0);
   for (const Row& r : rows) {
     if (!r.written) continue;  // main calls writeOutput after every fit(); a row never written is never printed
@@ -1328,16 +1167,12 @@ SingleVariantWaldTest::~SingleVariantWaldTest() {
 void SingleVariantWaldTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.headerTab() + "Test\tBeta\tSE\tPvalue\n");
 }
-bool SingleVariantWaldTest::runBlock() {
+int SingleVariantWaldTest::runBlock() {
   const size_t n = (size_t)used * (size_t)nCovariate;
   beta.assign(n, 0.0);
   se.assign(n, 0.0);
   pv.assign(n, 0.0);
-  if (rvt_wald_block(ctx, block, used, ok.data(), beta.data(), se.data(), pv.data(), nullptr)) {
-    lastError = rvt_last_error(ctx);
-    return false;
-  }
-  return true;
+  return rvt_wald_block(ctx, block.get(), used, ok.data(), beta.data(), se.data(), pv.data(), nullptr);
 }
 std::string SingleVariantWaldTest::formatSingleRow(const Row& r) {
   std::string out;
@@ -1363,7 +1198,7 @@ SingleVariantScoreTest::~SingleVariantScoreTest() {
 void SingleVariantScoreTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.headerTab() + "AF\tU\tV\tSTAT\tDIRECTION\tEFFECT\tSE\tPVALUE\n");
 }
-bool SingleVariantScoreTest::runBlock() {
+int SingleVariantScoreTest::runBlock() {
   const size_t n = (size_t)used;
   u.assign(n, 0.0);
   v.assign(n, 0.0);
@@ -1371,12 +1206,8 @@ bool SingleVariantScoreTest::runBlock() {
   se.assign(n, 0.0);
   pv.assign(n, 0.0);
   std::vector<double> beta0(nCovariate), covb(nCovariate);
-  if (rvt_score_block(ctx, block, used, ok.data(), u.data(), v.data(), eff.data(), se.data(), pv.data()) ||
-      rvt_null_summary(ctx, beta0.data(), covb.data(), &sigma2)) {
-    lastError = rvt_last_error(ctx);
-    return false;
-  }
-  return true;
+  const int rc = rvt_score_block(ctx, block.get(), used, ok.data(), u.data(), v.data(), eff.data(), se.data(), pv.data());
+  return rc ? rc : rvt_null_summary(ctx, beta0.data(), covb.data(), &sigma2);
 }
 std::string SingleVariantScoreTest::formatSingleRow(const Row& r) {
   const int k = r.column;
@@ -1404,13 +1235,11 @@ std::string SingleVariantScoreTest::formatSingleRow(const Row& r) {
 }
 
 // ---- FastMultipleTraitScoreTest (src/Model.h:4935-5125) ------------------------------------------------------------------------
-FastMultipleTraitScoreTest::FastMultipleTraitScoreTest() {
+FastMultipleTraitScoreTest::FastMultipleTraitScoreTest() : ColumnBlockTest("RVT_SINGLE_BLOCK") {
   modelName = "FastMultipleTraitScore";
-  if (const char* e = getenv("RVT_SINGLE_BLOCK")) capacity = std::max(1, std::min(65536, atoi(e)));
 }
 FastMultipleTraitScoreTest::~FastMultipleTraitScoreTest() {
   if (fout) flush();
-  if (ctx && block) rvt_block_free(ctx, block);
 }
 void FastMultipleTraitScoreTest::writeHeader(TextSink* fp, const SiteInfo& siteInfo) {
   fp->write(siteInfo.headerTab() + "U_STAT\tV_STAT\tPVALUE\n");
@@ -1465,30 +1294,22 @@ int FastMultipleTraitScoreTest::fit(GeneData* dc) {
     return -1;
   }
   if (dc->M != 1 || dc->N == 0) return -1;  // genotype.cols != 1
-  if (nSample >= 0 && nSample != dc->N) {
-    lastError = "Sample size changed";
-    return -1;
-  }
-  if (used >= capacity && flush()) return -1;
-  if (used >= capacity) {  // flush() could not run: no writeOutput() has named the output sink yet
-    lastError = getModelName() + ": the device block is full and no output was requested for its sites";
-    return -1;
-  }
+  if (sameSampleSize(*dc)) return -1;
+  if (makeRoom(rows.size())) return -1;  // (one entry of `rows` per column in use)
   if (!ctx) ctx = GpuBroker::instance().context(&lastError);
   if (!ctx) return -1;
   if (!haveNull || dc->phenotypeUpdated || dc->covariateUpdated) {
     if (used > 0 && flush()) return -1;  // the columns so far belong to the previous null
     if (fitNull(dc)) return -1;
   }
-  if (nSample < 0) {
-    if (rvt_block_alloc(ctx, capacity, &block)) {
-      lastError = rvt_last_error(ctx);
-      return -1;
-    }
+  if (nSample < 0) {  // (N is fixed only once the block exists: a failed allocation is tried again by the next site)
+    if (block.alloc(ctx, capacity, &lastError)) return -1;
     nSample = dc->N;
   }
-  // the caller overwrites the genotype buffer for the next site: copy the column into the device block now
-  if (rvt_block_upload(ctx, block + (size_t)used * (size_t)rvt_padded_ld(nSample), 1, dc->genotype)) {
+  // the caller overwrites the genotype buffer for the next site: copy the column into the device block now.  Not
+  // DeviceBlock::uploadColumn: rvt_block_upload_columns takes N from the score tests' null models, which this context
+  // does not have (its null is rvt_mt_fit_null's)
+  if (rvt_block_upload(ctx, block.get() + (size_t)used * (size_t)rvt_padded_ld(nSample), 1, dc->genotype)) {
     lastError = rvt_last_error(ctx);
     return -1;
   }
@@ -1506,10 +1327,6 @@ void FastMultipleTraitScoreTest::writeOutput(TextSink* fp, const SiteInfo& siteI
   written.back() = 1;
   if (used >= capacity) flush();  // numResult == blockSize (src/Model.h:5033-5035)
 }
-void FastMultipleTraitScoreTest::writeFootnote(TextSink* fp) {
-  fout = fp;
-  flush();
-}
 int FastMultipleTraitScoreTest::flush() {
   if (!fout) return 0;
   if (used == 0) return 0;
@@ -1517,7 +1334,7 @@ int FastMultipleTraitScoreTest::flush() {
   u.assign(cells, NAN);
   v.assign(cells, NAN);
   pv.assign(cells, NAN);
-  const bool ran = rvt_mt_score_block(ctx, block, used, u.data(), v.data(), pv.data()) == 0;
+  const bool ran = rvt_mt_score_block(ctx, block.get(), used, u.data(), v.data(), pv.data()) == 0;
   if (!ran) {
     lastError = rvt_last_error(ctx);
     std::fill(u.begin(), u.end(), NAN), std::fill(v.begin(), v.end(), NAN), std::fill(pv.begin(), pv.end(), NAN);
@@ -1567,6 +1384,10 @@ rvt_ctx* SingleVariantFamilyTest::acquireContext(GeneData* dc) {
   }
   return GpuBroker::instance().contextWithFamNull(*dc, &lastError);
 }
+int SingleVariantFamilyTest::runBlock() {
+  for (auto& v : col) v.assign((size_t)used, 0.0);
+  return blockEntry();
+}
 std::string SingleVariantFamilyTest::formatSingleRow(const Row& r) {
   const int k = r.column;
   if (k >= 0 && ok[k] == 1)  // (Result::updateValue; never cleared in between)
@@ -1579,13 +1400,8 @@ SingleVariantFamilyScore::SingleVariantFamilyScore()
 SingleVariantFamilyScore::~SingleVariantFamilyScore() {
   if (fout) flush();
 }
-bool SingleVariantFamilyScore::runBlock() {
-  for (auto& v : col) v.assign((size_t)used, 0.0);
-  if (rvt_score_block_fam(ctx, block, used, 0, ok.data(), col[1].data(), col[2].data(), col[0].data(), col[3].data())) {
-    lastError = rvt_last_error(ctx);
-    return false;
-  }
-  return true;
+int SingleVariantFamilyScore::blockEntry() {  // (this entry returns U and V before AF, the first column printed)
+  return rvt_score_block_fam(ctx, block.get(), used, 0, ok.data(), col[1].data(), col[2].data(), col[0].data(), col[3].data());
 }
 
 SingleVariantFamilyLRT::SingleVariantFamilyLRT()
@@ -1593,13 +1409,8 @@ SingleVariantFamilyLRT::SingleVariantFamilyLRT()
 SingleVariantFamilyLRT::~SingleVariantFamilyLRT() {
   if (fout) flush();
 }
-bool SingleVariantFamilyLRT::runBlock() {
-  for (auto& v : col) v.assign((size_t)used, 0.0);
-  if (rvt_lrt_block_fam(ctx, block, used, ok.data(), col[0].data(), col[1].data(), col[2].data(), col[3].data())) {
-    lastError = rvt_last_error(ctx);
-    return false;
-  }
-  return true;
+int SingleVariantFamilyLRT::blockEntry() {
+  return rvt_lrt_block_fam(ctx, block.get(), used, ok.data(), col[0].data(), col[1].data(), col[2].data(), col[3].data());
 }
 
 SingleVariantFamilyGrammarGamma::SingleVariantFamilyGrammarGamma(bool afKinship_)
@@ -1612,13 +1423,9 @@ rvt_ctx* SingleVariantFamilyGrammarGamma::acquireContext(GeneData* dc) {
   rvt_ctx* cx = SingleVariantFamilyTest::acquireContext(dc);
   if (!cx) return nullptr;
   if (!haveNull || nullKinship != dc->kinshipU || dc->phenotypeUpdated || dc->covariateUpdated) {
-    const int d = 1 + dc->ncov;  // copyCovariateAndIntercept (src/ModelUtil.h:102-130)
-    std::vector<double> X((size_t)dc->N * d);
-    for (int64_t i = 0; i < dc->N; ++i) X[i] = 1.0;
-    if (dc->ncov) std::memcpy(X.data() + dc->N, dc->covariate, sizeof(double) * (size_t)dc->N * dc->ncov);
     rvt_grammar_null gn;
     haveNull = false;
-    if (rvt_fit_grammar_null(cx, dc->N, d, X.data(), dc->phenotype, &gn)) {
+    if (rvt_fit_grammar_null(cx, dc->N, 1 + dc->ncov, interceptAndCovariates(*dc).data(), dc->phenotype, &gn)) {
       lastError = rvt_last_error(cx);
       return nullptr;
     }
@@ -1627,14 +1434,9 @@ rvt_ctx* SingleVariantFamilyGrammarGamma::acquireContext(GeneData* dc) {
   }
   return cx;
 }
-bool SingleVariantFamilyGrammarGamma::runBlock() {
-  for (auto& v : col) v.assign((size_t)used, 0.0);
-  if (rvt_grammar_block(ctx, block, used, afKinship ? 1 : 0, ok.data(), col[0].data(), col[1].data(), col[2].data(),
-                        col[3].data())) {
-    lastError = rvt_last_error(ctx);
-    return false;
-  }
-  return true;
+int SingleVariantFamilyGrammarGamma::blockEntry() {
+  return rvt_grammar_block(ctx, block.get(), used, afKinship ? 1 : 0, ok.data(), col[0].data(), col[1].data(), col[2].data(),
+                           col[3].data());
 }
 
 // ---- MetaCovTest ---------------------------------------------------------------------------------------------------------
@@ -1649,8 +1451,7 @@ MetaCovTest::MetaCovTest(int windowSize_) : windowSize(windowSize_) {
 }
 MetaCovTest::~MetaCovTest() {
   if (fout) flush(true);
-  if (ctx && bandReg) rvt_host_unregister(ctx, bandReg);
-  if (ctx && block) rvt_block_free(ctx, block);
+  if (ctx && bandReg) rvt_host_unregister(ctx, bandReg);  // (the ring is freed behind this, by its member's destructor)
 }
 int MetaCovTest::setParameter(const ModelParser& parser) {
   outputGwama = parser.hasTag("gwama");
@@ -1673,11 +1474,8 @@ int MetaCovTest::fit(GeneData* dc) {
   if (!ctx) return -1;
   if (useFamilyModel && isBinaryOutcome() && (nSample < 0 || dc->phenotypeUpdated)) {
     // MetaCovFamBinary::FitNullModel (src/Model.cpp:598-640): alpha = log(nCase / nCtrl), b = obtainB(alpha)
-    int64_t nCase = 0, nCtrl = 0;
-    for (int64_t i = 0; i < dc->N; ++i) {
-      if (dc->phenotype[i] == 1) ++nCase;
-      else if (dc->phenotype[i] == 0) ++nCtrl;
-    }
+    int64_t nCase, nCtrl;
+    caseControlCounts(*dc, &nCase, &nCtrl);
     if (rvt_fam_binary_scale(ctx, nCase, nCtrl, nullptr, nullptr)) {
       lastError = rvt_last_error(ctx);
       return -1;
@@ -1695,10 +1493,7 @@ int MetaCovTest::fit(GeneData* dc) {
       if (cols < (double)maxColumns) maxColumns = std::max(std::min(capacity, 1024), (int)cols);
       if (capacity > maxColumns) capacity = maxColumns;
     }
-    if (rvt_block_alloc(ctx, capacity, &block)) {
-      lastError = rvt_last_error(ctx);
-      return -1;
-    }
+    if (block.alloc(ctx, capacity, &lastError)) return -1;
   }
   if ((int)sites.size() == capacity) {
     const int before = (int)sites.size();
@@ -1719,10 +1514,7 @@ int MetaCovTest::fit(GeneData* dc) {
   }
   // the caller overwrites the genotype buffer for the next site: copy the column into the device ring now — into the physical
   // column behind the tail; nothing in the ring ever moves (RingMemoryPool::allocate, base/RingMemoryPool.cpp:31-47)
-  if (rvt_block_upload_columns(ctx, block, (head + (int)sites.size()) % capacity, 1, dc->genotype)) {
-    lastError = rvt_last_error(ctx);
-    return -1;
-  }
+  if (block.uploadColumn((head + (int)sites.size()) % capacity, dc->genotype, &lastError)) return -1;
   sites.push_back(Site{dc->site->get("CHROM"), atoi(dc->site->get("POS").c_str())});
   fitOK = true;  // whether the site is monomorphic (and therefore skipped) is decided on the device at flush time
   return 0;
@@ -1744,16 +1536,15 @@ int MetaCovTest::grow() {
     lastError = "MetaCov: one window holds more sites than RVT_METACOV_MAX_COLUMNS allows";
     return -1;
   }
-  double* bigger = nullptr;
+  DeviceBlock bigger;
   const int V = (int)sites.size(), first = std::min(V, capacity - head);
-  if (rvt_block_alloc(ctx, want, &bigger) || rvt_block_copy_columns(ctx, bigger, 0, block, head, first) ||
-      (V > first && rvt_block_copy_columns(ctx, bigger, first, block, 0, V - first))) {
+  if (bigger.alloc(ctx, want, &lastError)) return -1;
+  if (rvt_block_copy_columns(ctx, bigger.get(), 0, block.get(), head, first) ||
+      (V > first && rvt_block_copy_columns(ctx, bigger.get(), first, block.get(), 0, V - first))) {
     lastError = rvt_last_error(ctx);
-    if (bigger) rvt_block_free(ctx, bigger);
     return -1;
   }
-  rvt_block_free(ctx, block);
-  block = bigger;
+  block = std::move(bigger);  // frees the old ring
   capacity = want;
   head = 0;
   return 0;
@@ -1812,8 +1603,8 @@ int MetaCovTest::flush(bool final) {
     xz.assign((size_t)W * d, 0.0);
     poly.assign((size_t)W, 0);
     const int col0 = (head + h0) % capacity;
-    if (useFamilyModel ? rvt_cov_band_fam(ctx, block, capacity, col0, nh, W, halo, scale, bandBuf.data(), xz.data(), zz.data(), poly.data())
-                       : rvt_cov_band(ctx, block, capacity, col0, nh, W, halo, scale, bandBuf.data(), xz.data(), zz.data(), poly.data())) {
+    if (useFamilyModel ? rvt_cov_band_fam(ctx, block.get(), capacity, col0, nh, W, halo, scale, bandBuf.data(), xz.data(), zz.data(), poly.data())
+                       : rvt_cov_band(ctx, block.get(), capacity, col0, nh, W, halo, scale, bandBuf.data(), xz.data(), zz.data(), poly.data())) {
       lastError = rvt_last_error(ctx);
       return -1;
     }

@@ -18,6 +18,7 @@
 #pragma once
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -135,8 +136,54 @@ class ModelParser {
   std::map<std::string, std::string> param;
 };
 
-class ModelFitter;
+class DeferredGeneTest;
 class BurdenMoreTest;
+
+// ---- a device block (rvt_block_alloc) and the context it lives on ------------------------------------------------------------
+// Move-only, empty after a move.  The destructor frees the block it holds and does nothing else: a block must go out of scope,
+// or its owner be cleared, before its context is destroyed.  alloc / upload / uploadColumn return 0, or -1 with the context's
+// error text in *err.
+class DeviceBlock {
+ public:
+  DeviceBlock() = default;
+  DeviceBlock(DeviceBlock&& o) noexcept : ctx(o.ctx), ptr(o.release()) {}
+  DeviceBlock& operator=(DeviceBlock&& o) noexcept {
+    if (this != &o) {
+      free();
+      ctx = o.ctx;
+      ptr = o.release();
+    }
+    return *this;
+  }
+  ~DeviceBlock() { free(); }
+  int alloc(rvt_ctx* cx, int columns, std::string* err) {  // (whatever was held is freed first)
+    free();
+    ctx = cx;
+    return done(rvt_block_alloc(ctx, columns, &ptr), err);
+  }
+  // the first M columns, complete on return
+  int upload(int M, const double* host, std::string* err) { return done(rvt_block_upload(ctx, ptr, M, host), err); }
+  // one column, through the engine's column queue
+  int uploadColumn(int col, const double* host, std::string* err) { return done(rvt_block_upload_columns(ctx, ptr, col, 1, host), err); }
+  double* get() const { return ptr; }
+  double* release() {  // for a caller that frees the block itself, later
+    double* p = ptr;
+    ptr = nullptr;
+    return p;
+  }
+
+ private:
+  int done(int rc, std::string* err) const {
+    if (rc) *err = rvt_last_error(ctx);
+    return rc ? -1 : 0;
+  }
+  void free() {
+    if (ptr) rvt_block_free(ctx, ptr);
+    ptr = nullptr;
+  }
+  rvt_ctx* ctx = nullptr;
+  double* ptr = nullptr;
+};
 
 // ---- the engine shared by all GPU-backed models of one run ---------------------------------------------------
 // One device group per process (rvt_group_*: RVT_DEVICES=0,1,... lists the GPUs, default device 0): the gene tests'
@@ -167,7 +214,7 @@ class GpuBroker {
     dosageDecimals = decimals;
   }
   int submit(const GeneData& gd, bool binary, std::string* err);
-  void enqueue(ModelFitter* m, TextSink* fp, const std::string& siteTab, int64_t serial);
+  void enqueue(DeferredGeneTest* m, TextSink* fp, const std::string& siteTab, int64_t serial);
   int flush();       // wait for everything pending and write all rows
   int drainReady();  // take the finished prefix without waiting (rvt_collect_ready) and write the rows it completes
   void shutdown();
@@ -177,6 +224,11 @@ class GpuBroker {
   rvt_ctx* context(std::string* err);
   // context + kinship + FastLMM null for FamSkatTest (refitted when the caller flags new phenotype / covariates)
   rvt_ctx* contextWithFamNull(const GeneData& gd, std::string* err);
+  // The synchronous gene tests: upload the gene's N x M block to `cx`, run one rvt_* entry on it (`call`: one gene, its block
+  // pointer and its M), free the block.  -1 with *err set when the upload or the call fails, and when `cx` is null (*err is then
+  // what the context* call above left).
+  typedef std::function<int(const double* const* block, const int* M)> GeneCall;
+  static int withGene(rvt_ctx* cx, const GeneData& gd, std::string* err, const GeneCall& call);
   // the related-sample gene tests (FamSkat, FamCMC, FamZeggini) share one rotation per gene: the first model whose
   // fit() sees a gene runs the union of the registered tests, the others read the cached record
   void registerFamTests(uint32_t mask) { famTests |= mask; }
@@ -212,7 +264,7 @@ class GpuBroker {
   size_t windowBytes = (size_t)64 << 30;        // ... and the bytes of their device blocks (RVT_ADAPTER_BATCH_GB)
   size_t pendingBytes = 0;
   struct Row {
-    ModelFitter* model;
+    DeferredGeneTest* model;
     TextSink* fp;
     std::string siteTab;
     int64_t serial;
@@ -233,7 +285,7 @@ class GpuBroker {
   uint32_t moreTests = 0;
   struct MoreGene {
     int64_t serial;
-    double* block;  // rvt_block_alloc on member 0, freed by flushBurdenMore()
+    DeviceBlock block;  // on member 0; freed when flushBurdenMore() / shutdown() clear the vector
     int M, d;
     std::vector<double> af;
   };
@@ -267,11 +319,6 @@ class ModelFitter {
   virtual void writeFootnote(TextSink*) {}
   virtual int setParameter(const ModelParser&) { return 0; }
   virtual void reset() {}
-  // one output row (without the site columns, with the newline) from a collected record; r == nullptr -> NA row
-  virtual std::string formatRow(const rvt_gene_result* r) const {
-    (void)r;
-    return "\n";
-  }
   virtual ~ModelFitter() {}
   const std::string& getModelName() const { return modelName; }
   bool isBinaryOutcome() const { return binaryOutcome; }
@@ -283,58 +330,50 @@ class ModelFitter {
   bool binaryOutcome = false;
   int64_t curSerial = -1;  // gene handed to the last fit()
   std::string lastError;
-  // shared by the gene-level GPU models: fit() = submit, writeOutput() = enqueue, writeFootnote() = flush
-  int deferredFit(GeneData* dc);
-  void deferredOutput(TextSink* fp, const SiteInfo& siteInfo);
 };
 
-class SkatTest : public ModelFitter {
+// The gene tests that run batched through GpuBroker: fit() = submit, writeOutput() = enqueue, writeFootnote() = flush.  A model
+// is its registration (test bit and parameters), the header text after the site columns, and formatRow.
+class DeferredGeneTest : public ModelFitter {
  public:
-  std::string formatRow(const rvt_gene_result* r) const override;
-  void writeFootnote(TextSink* fp) override;
-  SkatTest(int nPerm, double alpha, double beta1, double beta2);
   int fit(GeneData* dc) override;
   void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeFootnote(TextSink* fp) override;
+  // one output row (without the site columns, with the newline) from a collected record; r == nullptr -> NA row
+  virtual std::string formatRow(const rvt_gene_result* r) const = 0;
+
+ protected:
+  // test == 0 registers nothing (AnalyticVTTest for related samples, which runs synchronously)
+  DeferredGeneTest(const char* name, uint32_t test, const rvt_params& p, const std::string& header);
+  std::string header;  // the column names after the site columns, with the newline
+};
+
+class SkatTest : public DeferredGeneTest {
+ public:
+  SkatTest(int nPerm, double alpha, double beta1, double beta2);
+  std::string formatRow(const rvt_gene_result* r) const override;
 
  private:
   bool usePermutation;
 };
 
-class SkatOTest : public ModelFitter {
+class SkatOTest : public DeferredGeneTest {
  public:
-  std::string formatRow(const rvt_gene_result* r) const override;
-  void writeFootnote(TextSink* fp) override;
   SkatOTest(double beta1, double beta2);
-  int fit(GeneData* dc) override;
-  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
-  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-
- private:
+  std::string formatRow(const rvt_gene_result* r) const override;
 };
 
-class CMCTest : public ModelFitter {
+class CMCTest : public DeferredGeneTest {
  public:
-  std::string formatRow(const rvt_gene_result* r) const override;
-  void writeFootnote(TextSink* fp) override;
   CMCTest();
-  int fit(GeneData* dc) override;
-  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
-  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-
- private:
+  std::string formatRow(const rvt_gene_result* r) const override;
 };
 
-class ZegginiTest : public ModelFitter {
+class ZegginiTest : public DeferredGeneTest {
  public:
-  std::string formatRow(const rvt_gene_result* r) const override;
-  void writeFootnote(TextSink* fp) override;
   ZegginiTest();
-  int fit(GeneData* dc) override;
-  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
-  void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-
- private:
+  std::string formatRow(const rvt_gene_result* r) const override;
 };
 
 // `--vt analytic` (src/ModelManager.cpp:158-159; AnalyticVT(UNRELATED), src/Model.h:2105-2259): quantitative traits only,
@@ -343,14 +382,13 @@ class ZegginiTest : public ModelFitter {
 // integral is evaluated deterministically and the row is NA when ITS error estimate exceeds 1e-3.
 // `--vt famanalytic` (AnalyticVT(RELATED), :160-161): the same columns from FastLMM's frequencies, scores and variances
 // (rvt_fam_analytic_vt); synchronous, one gene per call.
-class AnalyticVTTest : public ModelFitter {
+class AnalyticVTTest : public DeferredGeneTest {
  public:
-  std::string formatRow(const rvt_gene_result* r) const override;
-  void writeFootnote(TextSink* fp) override;
   explicit AnalyticVTTest(bool related = false);
+  std::string formatRow(const rvt_gene_result* r) const override;
   int fit(GeneData* dc) override;
-  void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
+  void writeFootnote(TextSink* fp) override;
 
  private:
   bool related;
@@ -375,6 +413,25 @@ class KbacTest : public ModelFitter {
   rvt_kbac_result rec{};
 };
 
+// Permutation's members (src/Permutation.h:150-156) as its constructor leaves them; reset() zeroes all but numPerm (:99-105),
+// which the models keep themselves
+struct PermutationState {
+  double obs = -1.0;
+  int actualPerm = -1, numX = -1, numEqual = -1;
+  void reset() {
+    obs = 0.0;
+    actualPerm = numX = numEqual = 0;
+  }
+  template <class Rec>
+  void take(const Rec& r, double stat) {  // perm.init(stat), then the counters of a permutation entry's record
+    obs = stat;
+    actualPerm = r.actual_perm;
+    numX = r.num_greater;
+    numEqual = r.num_equal;
+  }
+  std::string fields(int nPerm) const;  // NumPerm ActualPerm Stat NumGreater NumEqual PermPvalue, tab-separated
+};
+
 // `--vt price[nPerm=10000,alpha=0.05]` (src/ModelManager.cpp vt switch; VariableThresholdPrice, src/Model.h:1745-1882): Price's
 // variable-threshold permutation test for quantitative and binary traits (covariates are ignored, as the reference does
 // after its warning).  Columns: an EMPTY one (writeHeaderTab's tab followed by "\tOptFreq", src/Model.h:1807-1812), OptFreq,
@@ -388,16 +445,17 @@ class VariableThresholdPrice : public ModelFitter {
   int fit(GeneData* dc) override;
   void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-  void reset() override;
+  void reset() override {  // src/Model.h:1820-1824 over Permutation::reset (src/Permutation.h:99-105)
+    fitOK = false;
+    perm.reset();
+  }
 
  private:
   int nPerm;
   double alpha;
   bool fitOK = false;
   double zmax = -1.0, optimalFreq = -1.0;  // members of the reference's class: they survive reset()
-  // Permutation's members (src/Permutation.h:150-156) as its constructor leaves them; reset() zeroes all but numPerm
-  double obs = -1.0;
-  int actualPerm = -1, numX = -1, numEqual = -1;
+  PermutationState perm;
   rvt_vtprice_result rec{};
 };
 
@@ -412,16 +470,14 @@ class RareCoverTest : public ModelFitter {
   int fit(GeneData* dc) override;
   void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-  void reset() override;
+  void reset() override { perm.reset(); }  // src/Model.h:1477-1480 over Permutation::reset (src/Permutation.h:99-105)
 
  private:
   int nPerm;
   double alpha;
   bool fitOK = false;
   int numSelected = 0;
-  // Permutation's members (src/Permutation.h:150-156) as its constructor leaves them; reset() zeroes all but numPerm
-  double obs = -1.0;
-  int actualPerm = -1, numX = -1, numEqual = -1;
+  PermutationState perm;
   rvt_rarecover_result rec{};
 };
 
@@ -434,14 +490,13 @@ class MadsonBrowningTest : public ModelFitter {
   int fit(GeneData* dc) override;
   void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-  void reset() override;
+  void reset() override { perm.reset(); }  // src/Model.h:1306-1309
 
  private:
   int nPerm;
   double alpha;
   bool fitOK = false;
-  double obs = -1.0;
-  int actualPerm = -1, numX = -1, numEqual = -1;
+  PermutationState perm;
   rvt_mb_result rec{};
 };
 
@@ -572,8 +627,44 @@ class MetaCovTest : public ModelFitter {
   int64_t nSample = -1;
   int nCovariate = 0;
   rvt_ctx* ctx = nullptr;
-  double* block = nullptr;   // the device ring: `capacity` columns, never compacted
+  DeviceBlock block;         // the device ring: `capacity` columns, never compacted
   std::vector<Site> sites;   // variants currently in the ring, file order
+  TextSink* fout = nullptr;
+};
+
+// What the models that test one site per fit() share (MetaScoreTest, the single-variant tests, FastMultipleTraitScoreTest):
+// fit() copies the site's column into a device block of `capacity` columns; a full block, writeFootnote() and the destructor
+// of the concrete class run flush(): ONE device call over the `used` columns, whose rows are then written in file order.
+// The head of fit() is offered as steps: each model runs them in its own order, which decides what row a failing site prints.
+class ColumnBlockTest : public ModelFitter {
+ public:
+  void writeFootnote(TextSink* fp) override;
+
+ protected:
+  explicit ColumnBlockTest(const char* capacityEnv);  // the environment variable that overrides `capacity`
+  // Rows still pending are written by the destructors of the concrete classes (flush() is theirs: a base destructor could no
+  // longer reach it); the block is freed behind them, by its member's destructor.
+  virtual int flush() = 0;
+  int makeRoom(size_t pendingRows);        // flush a full block; -1 also when it stays full (no sink named yet)
+  int sameSampleSize(const GeneData& dc);  // -1: "Sample size changed"
+  // the rows tested so far belong to the previous null model: finish them before a new one replaces it (the current site's
+  // row, already the last of `rows`, stays)
+  template <class Row>
+  int flushBeforeNewNull(const GeneData& dc, std::vector<Row>* rows) {
+    if (nSample < 0 || !(dc.phenotypeUpdated || dc.covariateUpdated) || used == 0) return 0;
+    Row keep = rows->back();
+    rows->pop_back();
+    if (flush()) return -1;
+    rows->push_back(keep);
+    return 0;
+  }
+  int allocateOnFirstUse(const GeneData& dc);  // the first site that gets this far fixes N and the null's columns
+  int capacity = 1024;
+  int64_t nSample = -1;
+  int nCovariate = 0;  // columns of the null X, intercept included
+  int used = 0;        // columns of the block in use
+  rvt_ctx* ctx = nullptr;
+  DeviceBlock block;
   TextSink* fout = nullptr;
 };
 
@@ -581,7 +672,7 @@ class MetaCovTest : public ModelFitter {
 // caller hands over a kinship decomposition (the BOLT variants are not provided).  Sites are copied
 // into a device block as fit() sees them; a full block (or writeFootnote / the destructor) runs ONE rvt_score_block
 // over all of them and writes their rows in file order, after the summary header with the null-model estimates.
-class MetaScoreTest : public ModelFitter {
+class MetaScoreTest : public ColumnBlockTest {
  public:
   MetaScoreTest();
   ~MetaScoreTest() override;
@@ -589,7 +680,6 @@ class MetaScoreTest : public ModelFitter {
   int fit(GeneData* dc) override;
   void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-  void writeFootnote(TextSink* fp) override;
   std::vector<std::string> covLabel;  // g_SummaryHeader->getCovLabel() (src/Model.h:3287-3289): set by the caller
 
  private:
@@ -600,31 +690,22 @@ class MetaScoreTest : public ModelFitter {
     bool written = false;           // writeOutput was called for this site
     int column = -1;                // column in the device block
   };
-  int flush();
-  int capacity = 1024;              // RVT_METASCORE_BLOCK
+  int flush() override;             // capacity: RVT_METASCORE_BLOCK
   bool outputSE = false;
   bool useFamilyModel = false;
   double famB = 1.0;                // MetaFamBinary: b
   bool headerOutputted = false;
   std::string siteHeaderTab;
-  int64_t nSample = -1;
-  int nCovariate = 0;
-  int used = 0;                     // columns of the block in use
-  rvt_ctx* ctx = nullptr;
-  double* block = nullptr;
   std::vector<Row> rows;
-  TextSink* fout = nullptr;
 };
 
 // `--single wald,score` for unrelated samples.  fit() is called once per variant (genotype.cols == 1) and copies the column
 // into a device block; a full block (or writeFootnote / the destructor) runs ONE device call over all of them and writes their
 // rows in file order, as MetaScoreTest does.  The null model is the device fit of rvt_fit_null.
-class SingleVariantBlockTest : public ModelFitter {
+class SingleVariantBlockTest : public ColumnBlockTest {
  public:
-  ~SingleVariantBlockTest() override;
   int fit(GeneData* dc) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-  void writeFootnote(TextSink* fp) override;
   std::vector<std::string> covLabel;  // covariate column labels (cov.GetColumnLabel(k)): set by the caller
 
  protected:
@@ -635,25 +716,16 @@ class SingleVariantBlockTest : public ModelFitter {
     int column = -1;       // column in the device block; -1: not tested (fit() failed before the test)
     bool written = false;  // writeOutput was called for this site
   };
-  SingleVariantBlockTest();
-  // Rows still pending are written by the destructors of the concrete classes (flush() calls the virtual members below,
-  // which a base destructor could no longer reach); this one only frees the device block.
-  // the device call over the first `used` columns; false when it failed (its rows then print NA)
-  virtual bool runBlock() = 0;
+  SingleVariantBlockTest() : ColumnBlockTest("RVT_SINGLE_BLOCK") {}
+  // the device call over the first `used` columns; its return code (not 0: the block's rows print NA)
+  virtual int runBlock() = 0;
   virtual std::string formatSingleRow(const Row& r) = 0;
   // the context with this model's null installed (default: rvt_fit_null's); nullptr with lastError set when the site
   // cannot be tested
   virtual rvt_ctx* acquireContext(GeneData* dc);
-  int flush();
-  int capacity = 1024;  // RVT_SINGLE_BLOCK
-  int64_t nSample = -1;
-  int nCovariate = 0;   // columns of the null X, intercept included
-  int used = 0;
-  rvt_ctx* ctx = nullptr;
-  double* block = nullptr;
+  int flush() override;
   std::vector<Row> rows;
   std::vector<int> ok;
-  TextSink* fout = nullptr;
 };
 
 // SingleVariantWaldTest (src/Model.h:98-180): "Test Beta SE Pvalue", one row per column of X after the intercept (only the
@@ -667,7 +739,7 @@ class SingleVariantWaldTest final : public SingleVariantBlockTest {
   bool hideCovar = false;
 
  private:
-  bool runBlock() override;
+  int runBlock() override;
   std::string formatSingleRow(const Row& r) override;
   std::vector<double> beta, se, pv;
   std::string lastBeta = "NA", lastSE = "NA", lastP = "NA";
@@ -683,7 +755,7 @@ class SingleVariantScoreTest final : public SingleVariantBlockTest {
   void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
 
  private:
-  bool runBlock() override;
+  int runBlock() override;
   std::string formatSingleRow(const Row& r) override;
   std::vector<double> u, v, eff, se, pv;
   double sigma2 = 1.0;
@@ -701,6 +773,8 @@ class SingleVariantFamilyTest : public SingleVariantBlockTest {
  protected:
   SingleVariantFamilyTest(const char* name, const char* header, const char* what);
   rvt_ctx* acquireContext(GeneData* dc) override;
+  int runBlock() override;
+  virtual int blockEntry() = 0;  // the model's rvt_*_block entry over the first `used` columns, into ok and col
   std::string formatSingleRow(const Row& r) override;
   std::vector<double> col[4];  // the four printed values per column of the block
   std::string last[4] = {"NA", "NA", "NA", "NA"};
@@ -714,7 +788,7 @@ class SingleVariantFamilyScore final : public SingleVariantFamilyTest {
   ~SingleVariantFamilyScore() override;
 
  private:
-  bool runBlock() override;
+  int blockEntry() override;
 };
 
 class SingleVariantFamilyLRT final : public SingleVariantFamilyTest {
@@ -723,7 +797,7 @@ class SingleVariantFamilyLRT final : public SingleVariantFamilyTest {
   ~SingleVariantFamilyLRT() override;
 
  private:
-  bool runBlock() override;
+  int blockEntry() override;
 };
 
 class SingleVariantFamilyGrammarGamma final : public SingleVariantFamilyTest {
@@ -733,7 +807,7 @@ class SingleVariantFamilyGrammarGamma final : public SingleVariantFamilyTest {
 
  private:
   rvt_ctx* acquireContext(GeneData* dc) override;
-  bool runBlock() override;
+  int blockEntry() override;
   bool afKinship = false;
   bool haveNull = false;
   const float* nullKinship = nullptr;  // the decomposition the GrammarGamma null was fitted on
@@ -746,29 +820,22 @@ class SingleVariantFamilyGrammarGamma final : public SingleVariantFamilyTest {
 // rvt_mt_score_block and writes the rows in file order.  The null (rvt_mt_fit_null) is made by the first fit() and again when the
 // caller flags an updated phenotype / covariate.  fit() fails on a binary trait (the reference's warnOnce) and on a genotype
 // with other than one column; such a site prints NO row (the reference counts it into its block without a genotype column).
-class FastMultipleTraitScoreTest final : public ModelFitter {
+class FastMultipleTraitScoreTest final : public ColumnBlockTest {
  public:
   FastMultipleTraitScoreTest();
   ~FastMultipleTraitScoreTest() override;
   int fit(GeneData* dc) override;
   void writeHeader(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
-  void writeFootnote(TextSink* fp) override;
 
  private:
   int fitNull(GeneData* dc);
-  int flush();
-  int capacity = 1024;  // RVT_SINGLE_BLOCK
-  int64_t nSample = -1;
+  int flush() override;
   int nTest = 0;
-  int used = 0;
   bool haveNull = false, fitOK = false;
-  rvt_ctx* ctx = nullptr;
-  double* block = nullptr;
   std::vector<std::string> rows;  // the site columns of the block's columns, in file order ("" until writeOutput names them)
   std::vector<char> written;
   std::vector<double> u, v, pv;
-  TextSink* fout = nullptr;
 };
 
 // ---- ModelManager::create -----------------------------------------------------------------------------------------
