@@ -485,8 +485,37 @@ int rvt_block_copy_columns(rvt_ctx* ctx, double* dst, int dst_col, const double*
  * MetaCov calls start on the integer kernels then) and, under an unweighted null model, keeps with the block what MetaCov's
  * column pass would compute for the column — its int8 copy, sum, polymorphic flag and row of T = G'X — so that rvt_cov_block /
  * rvt_cov_rect on such a block start at the integer product (same numbers, bit for bit, as for a block uploaded at once;
- * not used after the null model changed).  N more bytes of device memory per column. */
+ * not used after the null model changed).  About 2 N more bytes of device memory per column (the int8 copy and two 4-bit
+ * stores).  A single column (ncols = 1) of hard calls plus at most one other value — inside [0, 2], or negative: the missing
+ * code of raw calls — is packed on the host and QUEUED: it becomes visible in the block after rvt_sync,
+ * rvt_block_download_columns or another engine call on the block — a consumer outside the engine that reads the block's
+ * memory before that sees what the column held before. */
 int rvt_block_upload_columns(rvt_ctx* ctx, double* dG, int col0, int ncols, const double* G);
+/* Copy columns [col0, col0+ncols) of a device block to host memory (N doubles per column, contiguous): queued single-column
+ * uploads are flushed and the upload stream is waited for first, so the copy is what the engine's own calls would read. */
+int rvt_block_download_columns(rvt_ctx* ctx, const double* dG, int col0, int ncols, double* G_host);
+/* Dominant / recessive recoding of genotype columns on the device, for `--meta dominant` / `--meta recessive`
+ * (DataConsolidator::codeGenotypeForDominantModel / codeGenotypeForRecessiveModel, src/DataConsolidator.cpp:390-472, which read
+ * originalGenotype; the models src/Model.h:3880-3902, 4098-4124).  Per raw column x: a value is missing iff x < 0 (NaN and -0.0
+ * are not); a non-missing value codes to 1 if x > 0.5 (dominant) resp. x > 1.5 (recessive), else 0; a missing value codes to
+ * avg = (double)carriers / (double)nonmissing of the column (0 when nothing is called) — both counts exact integers, the
+ * reference's s / numGeno bit for bit.  The reference's DROP branch (which writes outside its one-column matrix) is not
+ * carried: missing calls are always imputed. */
+#define RVT_CODING_DOMINANT 1
+#define RVT_CODING_RECESSIVE 2
+/* Columns [src_col, src_col+ncols) of device block src, recoded, into columns [dst_col, dst_col+ncols) of device block dst
+ * (rows N .. ld of dst stay as they were).  src and dst may be the same block, then with the same columns (in place) or with
+ * ranges that do not overlap.  Queued single-column uploads are flushed first.  Afterwards the engine knows the columns as it
+ * knows a packed upload of them (hard calls plus at most one other value, avg): rvt_score_block starts on the integer kernels,
+ * rvt_cov_band keeps them on the MXFP4 band.  counts (optional, 2 ncols entries): per column the non-missing calls and the
+ * carriers.  Complete on return.  RVT_E_INVALID: a bad coding or a range that leaves a block; RVT_E_STATE: no null model. */
+int rvt_block_recode(rvt_ctx* ctx, double* dst, int dst_col, const double* src, int src_col, int ncols, int coding,
+                     long long* counts);
+/* Measurement (tools/bench_meta_coded.py; cf. rvt_mt_last_timing): with rvt_set_profiling on, the device milliseconds between HIP
+ * events recorded directly around the count launches and directly around the write / expand launches of the last
+ * rvt_block_recode or rvt_bed_recode_block (the two loops of src/DataConsolidator.cpp:390-472); the host's division between
+ * the passes is in neither figure. */
+int rvt_recode_last_timing(rvt_ctx* ctx, double* ms2);
 /* Move columns [src_col, src_col+ncols) of a device block down to dst_col <= src_col (ring compaction; the per-column records
  * move with them). */
 int rvt_block_move_columns(rvt_ctx* ctx, double* dG, int dst_col, int src_col, int ncols);
@@ -809,6 +838,12 @@ int rvt_submit_gene_bed_dev(rvt_ctx* ctx, int64_t gene_id, int M, const unsigned
  * (src/Model.h:3211-3230).  Quantitative traits (the packed-row kernel's domain; RVT_E_STATE otherwise).  Synchronous. */
 int rvt_score_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int* ok, double* ustat, double* vstat, double* effect,
                       double* effect_se, double* pvalue, long long* counts);
+/* V consecutive rows of a resident .bed matrix, recoded dominant / recessive (RVT_CODING_*, see rvt_block_recode;
+ * src/DataConsolidator.cpp:390-472 on the calls of libVcf/PlinkInputFile.cpp:24-47), into columns [col0, col0 + V) of a device
+ * block as doubles: N/2 + 8 N bytes of device traffic per row.  The same bookkeeping as behind rvt_block_recode, for either
+ * trait.  counts (optional, 4 V entries): per row the numbers of 0 / 1 / 2 / missing calls, as rvt_score_bed_dev reports them;
+ * the padding bits of a row's last byte are not counted.  Synchronous. */
+int rvt_bed_recode_block(rvt_ctx* ctx, const unsigned char* d_rows, int V, int coding, double* dG, int col0, long long* counts);
 
 /* ---- VCF text at the boundary (SURVEY §8f "next" #1: the genotype front end) -------------------------------------------
  * Replaces the per-sample loop of VCFGenotypeExtractor::extractMultipleGenotype (src/VCFGenotypeExtractor.cpp:29-140) for

@@ -952,16 +952,20 @@ int MetaScoreTest::setParameter(const ModelParser& parser) {
   outputSE = parser.hasTag("se");  // src/Model.h:3177-3182 ("gwama" / "bolt" are not provided)
   return 0;
 }
-int MetaScoreTest::fit(GeneData* dc) {
-  useFamilyModel = dc->kinshipU != nullptr;  // dc->hasKinship(): MetaFamQtl / MetaFamBinary (src/Model.h:3398-3668)
+int MetaScoreTest::beginRow(const GeneData& dc) {
   if (makeRoom(rows.size())) return -1;
   rows.emplace_back();
   Row& row = rows.back();
-  row.all = dc->counter;  // site statistics are printed whether or not the test runs (src/Model.h:3211-3230)
+  row.all = dc.counter;  // site statistics are printed whether or not the test runs (src/Model.h:3211-3230)
   if (isBinaryOutcome()) {
-    row.cases = dc->caseCounter;
-    row.ctrls = dc->ctrlCounter;
+    row.cases = dc.caseCounter;
+    row.ctrls = dc.ctrlCounter;
   }
+  return 0;
+}
+int MetaScoreTest::fit(GeneData* dc) {
+  useFamilyModel = dc->kinshipU != nullptr;  // dc->hasKinship(): MetaFamQtl / MetaFamBinary (src/Model.h:3398-3668)
+  if (beginRow(*dc)) return -1;
   if (dc->N == 0) return -1;
   if (sameSampleSize(*dc)) return -1;
   if (flushBeforeNewNull(*dc, &rows)) return -1;
@@ -981,7 +985,7 @@ int MetaScoreTest::fit(GeneData* dc) {
   if (dc->M != 1) return -1;  // "sanity check, this should not happen" (src/Model.h:3241-3244)
   // the caller overwrites the genotype buffer for the next site: copy the column into the device block now; whether
   // the site is monomorphic (src/Model.h:3246-3250) is decided on the device when the block is processed
-  if (block.uploadColumn(used, dc->genotype, &lastError)) return -1;
+  if (putSiteColumn(dc, used)) return -1;
   rows.back().column = used++;
   rows.back().tested = true;
   return 0;
@@ -1017,7 +1021,7 @@ int MetaScoreTest::flush() {
   std::vector<double> u(ok.size()), v(ok.size()), eff(ok.size()), se(ok.size()), pv(ok.size());
   bool scored = false;
   std::vector<double> famAf(ok.size());
-  if (used > 0) {
+  if (used > 0 && columnsReady() == 0) {  // (a failed recoding has set lastError: NA rows)
     const int rc = useFamilyModel
                        ? rvt_score_block_fam(ctx, block.get(), used, isBinaryOutcome() ? 1 : 0, ok.data(), u.data(), v.data(),
                                              famAf.data(), pv.data())
@@ -1514,7 +1518,7 @@ int MetaCovTest::fit(GeneData* dc) {
   }
   // the caller overwrites the genotype buffer for the next site: copy the column into the device ring now — into the physical
   // column behind the tail; nothing in the ring ever moves (RingMemoryPool::allocate, base/RingMemoryPool.cpp:31-47)
-  if (block.uploadColumn((head + (int)sites.size()) % capacity, dc->genotype, &lastError)) return -1;
+  if (putSiteColumn(dc, (head + (int)sites.size()) % capacity)) return -1;
   sites.push_back(Site{dc->site->get("CHROM"), atoi(dc->site->get("POS").c_str())});
   fitOK = true;  // whether the site is monomorphic (and therefore skipped) is decided on the device at flush time
   return 0;
@@ -1536,6 +1540,7 @@ int MetaCovTest::grow() {
     lastError = "MetaCov: one window holds more sites than RVT_METACOV_MAX_COLUMNS allows";
     return -1;
   }
+  if (columnsReady()) return -1;  // (the columns are copied as the device calls will read them)
   DeviceBlock bigger;
   const int V = (int)sites.size(), first = std::min(V, capacity - head);
   if (bigger.alloc(ctx, want, &lastError)) return -1;
@@ -1566,6 +1571,7 @@ int MetaCovTest::flush(bool final) {
     if (!complete) break;
   }
   if (H == 0) return 0;  // nothing can be written yet: the caller enlarges the ring
+  if (columnsReady()) return -1;
   // whole row panels of the band kernel (256 heads): a panel of 24 heads costs the tiles of a full one; the rest waits in the
   // ring — nothing moves, so keeping them costs nothing
   if (!final && H > 256) H -= H % 256;
@@ -1669,6 +1675,53 @@ int MetaCovTest::flush(bool final) {
   return 0;
 }
 
+// ---- the dominant / recessive meta models (src/Model.h:3880-3902, 4098-4124) -------------------------------------------------------
+namespace {
+// why a coded model cannot take this site (empty: it can)
+std::string codedRefusal(const GeneData& dc, const std::string& modelName) {
+  // the family score file's AF comes from the additive genotype (src/Model.h:3256-3258), which the recoded block does not hold
+  if (dc.kinshipU) return modelName + ": related samples (a kinship) are not supported by the dominant / recessive models";
+  if (!dc.rawGenotype) return modelName + " needs the genotypes before imputation (GeneData::rawGenotype)";
+  return "";
+}
+// the recoder's two device operations on a block
+int putRaw(ColumnRecoder& r, DeviceBlock& block, const GeneData& dc, int c, int coding, std::string* err) {
+  return r.put(c, [&](int col) { return block.uploadColumn(col, dc.rawGenotype, err); },
+               [&](int start, int n) { return block.recodeColumns(start, n, coding, err); });
+}
+int recodePending(ColumnRecoder& r, DeviceBlock& block, int coding, std::string* err) {
+  return r.ready([&](int start, int n) { return block.recodeColumns(start, n, coding, err); });
+}
+}  // namespace
+
+MetaCodedScoreTest::MetaCodedScoreTest(int coding_, const char* name) : coding(coding_) { modelName = name; }
+MetaCodedScoreTest::~MetaCodedScoreTest() {
+  if (fout) flush();
+}
+int MetaCodedScoreTest::fit(GeneData* dc) {
+  lastError = codedRefusal(*dc, modelName);
+  if (!lastError.empty()) {  // the row keeps its counters and prints NA; no null model is fitted for it
+    beginRow(*dc);
+    return -1;
+  }
+  return MetaScoreTest::fit(dc);
+}
+int MetaCodedScoreTest::putSiteColumn(GeneData* dc, int c) { return putRaw(recoder, block, *dc, c, coding, &lastError); }
+int MetaCodedScoreTest::columnsReady() { return recodePending(recoder, block, coding, &lastError); }
+
+MetaCodedCovTest::MetaCodedCovTest(int windowSize, int coding_, const char* name) : MetaCovTest(windowSize), coding(coding_) {
+  modelName = name;
+}
+MetaCodedCovTest::~MetaCodedCovTest() {
+  if (fout) flush(true);
+}
+int MetaCodedCovTest::fit(GeneData* dc) {
+  lastError = codedRefusal(*dc, modelName);
+  return lastError.empty() ? MetaCovTest::fit(dc) : -1;
+}
+int MetaCodedCovTest::putSiteColumn(GeneData* dc, int c) { return putRaw(recoder, block, *dc, c, coding, &lastError); }
+int MetaCodedCovTest::columnsReady() { return recodePending(recoder, block, coding, &lastError); }
+
 // ---- ModelManager (src/ModelManager.cpp:26-44 tokeniser, :46-271 switch) --------------------------------------------------------
 ModelManager::~ModelManager() {
   GpuBroker::instance().flush();  // rows still pending refer to the models
@@ -1768,6 +1821,18 @@ int ModelManager::create(const std::string& type, const std::string& modelList) 
         int windowSize;
         parser.assign("windowSize", &windowSize, 1000000);  // src/ModelManager.cpp:227-233
         model.push_back(new MetaCovTest(windowSize));
+      } else if (modelName == "dominant" || modelName == "recessive") {  // src/ModelManager.cpp:211-226: a score and a cov model
+        int windowSize;
+        parser.assign("windowSize", &windowSize, 1000000);
+        if (modelName == "dominant") {
+          model.push_back(new MetaDominantTest());
+          model.back()->setParameter(parser);
+          model.push_back(new MetaDominantCovTest(windowSize));
+        } else {
+          model.push_back(new MetaRecessiveTest());
+          model.back()->setParameter(parser);
+          model.push_back(new MetaRecessiveCovTest(windowSize));
+        }
       } else {
         lastError = "Unknown model name: " + modelName + " .";
         return -1;

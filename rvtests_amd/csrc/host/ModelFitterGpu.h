@@ -47,6 +47,9 @@ struct GeneData {
   int64_t N = 0;
   int M = 0;
   const double* genotype = nullptr;   // dc->getGenotype(): imputed, unflipped, N x M column-major
+  // dc->getOriginalGenotype() (src/DataConsolidator.h:133): the calls BEFORE imputation, N x M column-major, negative =
+  // missing.  Read by the dominant / recessive meta models only (DataConsolidator::codeGenotypeFor*Model read it).
+  const double* rawGenotype = nullptr;
   // Optional, INSTEAD of `genotype` for the gene tests (SKAT / SKAT-O / CMC / Zeggini): the gene as the extractor of a PLINK
   // file holds it BEFORE consolidation — M rows of ceil(N / 4) bytes, SNP-major 2-bit codes (libVcf/PlinkInputFile.cpp:24-47;
   // 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing).  The device then does what DataConsolidator::consolidate does (allele
@@ -165,6 +168,10 @@ class DeviceBlock {
   int upload(int M, const double* host, std::string* err) { return done(rvt_block_upload(ctx, ptr, M, host), err); }
   // one column, through the engine's column queue
   int uploadColumn(int col, const double* host, std::string* err) { return done(rvt_block_upload_columns(ctx, ptr, col, 1, host), err); }
+  // columns [col, col + n) recoded in place (RVT_CODING_*), queued uploads of them included
+  int recodeColumns(int col, int n, int coding, std::string* err) {
+    return done(rvt_block_recode(ctx, ptr, col, ptr, col, n, coding, nullptr), err);
+  }
   double* get() const { return ptr; }
   double* release() {  // for a caller that frees the block itself, later
     double* p = ptr;
@@ -183,6 +190,38 @@ class DeviceBlock {
   }
   rvt_ctx* ctx = nullptr;
   double* ptr = nullptr;
+};
+
+// What the dominant / recessive meta models share: a site's RAW column goes into the block by rvt_block_upload_columns — the
+// engine's column queue packs it, its negative missing code included, and keeps batching — and is remembered as pending; a
+// pending run — consecutive physical columns — is recoded in place by ONE rvt_block_recode before any device call reads the
+// block, before a column that does not continue it (the ring wrapping) and at the latest when it holds kMaxPending columns.
+// The decisions are made here without a device: `upload(col)` and `recode(start, n)` are the caller's two device operations
+// (0 = done), which a stand-alone program replaces by its own.
+class ColumnRecoder {
+ public:
+  static constexpr int kMaxPending = 32;  // = the engine's column queue: one recoding per queue flush
+  // the site's raw column into block column c
+  template <class Upload, class Recode>
+  int put(int c, Upload upload, Recode recode) {
+    if (n > 0 && c != start + n && ready(recode)) return -1;  // (the ring wrapped)
+    if (upload(c)) return -1;
+    if (n == 0) start = c;
+    ++n;
+    return n >= kMaxPending ? ready(recode) : 0;
+  }
+  // recode what is pending
+  template <class Recode>
+  int ready(Recode recode) {
+    if (n == 0) return 0;
+    const int s = start, k = n;
+    n = 0;  // (also after a failure: the columns are not recoded twice)
+    return recode(s, k) ? -1 : 0;
+  }
+  int pending() const { return n; }
+
+ private:
+  int start = 0, n = 0;
 };
 
 // ---- the engine shared by all GPU-backed models of one run ---------------------------------------------------
@@ -606,12 +645,20 @@ class MetaCovTest : public ModelFitter {
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
   void writeFootnote(TextSink* fp) override;
 
+ protected:
+  // put this site's column into column c of the ring (the coded models upload the raw calls and recode them on the device)
+  virtual int putSiteColumn(GeneData* dc, int c) { return block.uploadColumn(c, dc->genotype, &lastError); }
+  // called before any device call on the ring (flush, grow)
+  virtual int columnsReady() { return 0; }
+  int flush(bool final);
+  TextSink* fout = nullptr;
+  DeviceBlock block;         // the device ring: `capacity` columns, never compacted
+
  private:
   struct Site {
     std::string chrom;
     int pos;
   };
-  int flush(bool final);
   int grow();
   int windowSize;
   int capacity = 4096;                 // columns of the device ring (grows until it holds four windows)
@@ -627,9 +674,7 @@ class MetaCovTest : public ModelFitter {
   int64_t nSample = -1;
   int nCovariate = 0;
   rvt_ctx* ctx = nullptr;
-  DeviceBlock block;         // the device ring: `capacity` columns, never compacted
   std::vector<Site> sites;   // variants currently in the ring, file order
-  TextSink* fout = nullptr;
 };
 
 // What the models that test one site per fit() share (MetaScoreTest, the single-variant tests, FastMultipleTraitScoreTest):
@@ -682,6 +727,14 @@ class MetaScoreTest : public ColumnBlockTest {
   void writeOutput(TextSink* fp, const SiteInfo& siteInfo) override;
   std::vector<std::string> covLabel;  // g_SummaryHeader->getCovLabel() (src/Model.h:3287-3289): set by the caller
 
+ protected:
+  // put this site's column into column c of the block (the coded models upload the raw calls and recode them on the device)
+  virtual int putSiteColumn(GeneData* dc, int c) { return block.uploadColumn(c, dc->genotype, &lastError); }
+  // called before the device call of flush()
+  virtual int columnsReady() { return 0; }
+  int flush() override;             // capacity: RVT_METASCORE_BLOCK
+  int beginRow(const GeneData& dc);  // the site's row with its counters (printed whether or not the test runs); -1: no room
+
  private:
   struct Row {
     std::string siteTab;            // filled by writeOutput
@@ -690,13 +743,64 @@ class MetaScoreTest : public ColumnBlockTest {
     bool written = false;           // writeOutput was called for this site
     int column = -1;                // column in the device block
   };
-  int flush() override;             // capacity: RVT_METASCORE_BLOCK
   bool outputSE = false;
   bool useFamilyModel = false;
   double famB = 1.0;                // MetaFamBinary: b
   bool headerOutputted = false;
   std::string siteHeaderTab;
   std::vector<Row> rows;
+};
+
+// `--meta dominant` / `--meta recessive` (src/ModelManager.cpp:211-226): the score file and the covariance file of the
+// RAREMETAL dominant / recessive models (MetaDominantTest / MetaRecessiveTest src/Model.h:3880-3902, MetaDominantCovTest /
+// MetaRecessiveCovTest :4098-4124) — MetaScoreTest / MetaCovTest on the column DataConsolidator::codeGenotypeForDominantModel /
+// ...RecessiveModel make of the site's calls before imputation (src/DataConsolidator.cpp:390-472), recoded on the device
+// (rvt_block_recode).  The site counters stay those of the raw additive calls (fitWithGivenGenotype, src/Model.h:3211-3230).
+// Not carried: the reference's DROP branch (missing calls are always imputed to the recoded mean), and related samples — with a
+// kinship the fit fails with a message and the rows print NA.
+class MetaCodedScoreTest : public MetaScoreTest {
+ public:
+  ~MetaCodedScoreTest() override;  // (the pending rows are written here: the base's destructor no longer reaches the hooks)
+  int fit(GeneData* dc) override;  // refuses a kinship and a site without raw calls before anything is fitted
+
+ protected:
+  MetaCodedScoreTest(int coding, const char* name);
+  int putSiteColumn(GeneData* dc, int c) override;
+  int columnsReady() override;
+
+ private:
+  int coding;
+  ColumnRecoder recoder;
+};
+class MetaDominantTest final : public MetaCodedScoreTest {
+ public:
+  MetaDominantTest() : MetaCodedScoreTest(RVT_CODING_DOMINANT, "MetaDominant") {}
+};
+class MetaRecessiveTest final : public MetaCodedScoreTest {
+ public:
+  MetaRecessiveTest() : MetaCodedScoreTest(RVT_CODING_RECESSIVE, "MetaRecessive") {}
+};
+class MetaCodedCovTest : public MetaCovTest {
+ public:
+  ~MetaCodedCovTest() override;
+  int fit(GeneData* dc) override;
+
+ protected:
+  MetaCodedCovTest(int windowSize, int coding, const char* name);
+  int putSiteColumn(GeneData* dc, int c) override;
+  int columnsReady() override;
+
+ private:
+  int coding;
+  ColumnRecoder recoder;
+};
+class MetaDominantCovTest final : public MetaCodedCovTest {
+ public:
+  explicit MetaDominantCovTest(int windowSize) : MetaCodedCovTest(windowSize, RVT_CODING_DOMINANT, "MetaDominantCov") {}
+};
+class MetaRecessiveCovTest final : public MetaCodedCovTest {
+ public:
+  explicit MetaRecessiveCovTest(int windowSize) : MetaCodedCovTest(windowSize, RVT_CODING_RECESSIVE, "MetaRecessiveCov") {}
 };
 
 // `--single wald,score` for unrelated samples.  fit() is called once per variant (genotype.cols == 1) and copies the column

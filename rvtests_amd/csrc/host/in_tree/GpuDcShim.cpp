@@ -47,6 +47,10 @@ void fillGeneData(DataConsolidator* dc, bool familyModel, const void* who, rvt_h
   gd->N = G.rows;
   gd->M = G.cols;
   gd->genotype = G.cols ? G.data.data() : NULL;
+  {  // the calls before imputation (src/DataConsolidator.h:133), what codeGenotypeForDominantModel / ...RecessiveModel read
+    const Matrix& raw = dc->getOriginalGenotype();
+    gd->rawGenotype = (G.cols && raw.rows == G.rows && raw.cols == G.cols) ? raw.data.data() : NULL;
+  }
   gd->phenotype = y.data.data();
   gd->ncov = Z.cols;
   gd->covariate = Z.cols ? Z.data.data() : NULL;

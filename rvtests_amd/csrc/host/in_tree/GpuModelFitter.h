@@ -127,6 +127,10 @@ typedef GpuModel<rvt_host::FamSkatTest> FamSkatTest;  // new FamSkatTest(beta1, 
 typedef GpuModel<rvt_host::FamBurdenTest> FamBurdenTest;
 typedef GpuModel<rvt_host::MetaCovTest> MetaCovTest;      // new MetaCovTest(windowSize)            :238-247
 typedef GpuModel<rvt_host::MetaScoreTest> MetaScoreTest;  // new MetaScoreTest()
+typedef GpuModel<rvt_host::MetaDominantTest> MetaDominantTest;    // new MetaDominantTest()          :211-226
+typedef GpuModel<rvt_host::MetaRecessiveTest> MetaRecessiveTest;  // new MetaRecessiveTest()
+typedef GpuModel<rvt_host::MetaDominantCovTest> MetaDominantCovTest;    // new MetaDominantCovTest(windowSize)
+typedef GpuModel<rvt_host::MetaRecessiveCovTest> MetaRecessiveCovTest;  // new MetaRecessiveCovTest(windowSize)
 typedef GpuModel<rvt_host::KbacTest> KBACTest;            // new KBACTest(nPerm, alpha)
 typedef GpuModel<rvt_host::VariableThresholdPrice> VariableThresholdPrice;  // new VariableThresholdPrice(nPerm, alpha)
 typedef GpuModel<rvt_host::RareCoverTest> RareCoverTest;            // new RareCoverTest(nPerm, alpha)       :115-121

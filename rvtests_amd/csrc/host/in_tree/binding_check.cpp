@@ -35,6 +35,10 @@ int rvt_binding_check(DataConsolidator* dc, FileWriter* fp, const Result& siteIn
   model.push_back(new rvt_intree::SingleVariantFamilyLRT());
   model.push_back(new rvt_intree::SingleVariantFamilyGrammarGamma(GrammarGamma::AF_MEAN));
   model.push_back(new rvt_intree::MetaScoreTest());
+  model.push_back(new rvt_intree::MetaDominantTest());  // src/ModelManager.cpp:211-226
+  model.push_back(new rvt_intree::MetaDominantCovTest(windowSize));
+  model.push_back(new rvt_intree::MetaRecessiveTest());
+  model.push_back(new rvt_intree::MetaRecessiveCovTest(windowSize));
   model.push_back(new rvt_intree::AnalyticVT(rvt_intree::AnalyticVT::UNRELATED));  // src/ModelManager.cpp:158-159
   model.push_back(new rvt_intree::KBACTest(nPerm, alpha));
   parser.parse("price[nPerm=200,alpha=0.1]");

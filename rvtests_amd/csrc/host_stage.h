@@ -311,9 +311,11 @@ __attribute__((target("avx512f,bmi2,popcnt"))) inline bool pack16_avx512(const d
 #endif
 
 // g[0 .. n) -> out[0 .. ceil(n / 4)), then zeros up to `pitch` bytes.  isa: -1 = the widest the CPU has, 0 scalar, 1 AVX2,
-// 2 AVX-512 (tests compare them)
+// 2 AVX-512 (tests compare them).  negative_mu: the one other value may also be negative — the missing code of a column of raw
+// calls on its way into a block (rvt_block_upload_columns: the expansion kernel writes any value back); the gene kernels that
+// read packed rows need it inside [0, 2].
 inline PackedColumn pack_column_f64(const double* g, size_t n, unsigned char* out, size_t pitch, const std::atomic<int>* stop,
-                                    int isa = -1) {
+                                    int isa = -1, bool negative_mu = false) {
   PackedColumn r;
   unsigned long long mu_bits = 0x7FF8DEADBEEF0001ull;  // (no double of a genotype block: a NaN payload)
   bool has_mu = false, ok = true;
@@ -354,7 +356,7 @@ inline PackedColumn pack_column_f64(const double* g, size_t n, unsigned char* ou
   double mu = 0.0;
   if (has_mu) {
     std::memcpy(&mu, &mu_bits, 8);
-    if (!(mu >= 0.0 && mu <= 2.0)) return r;  // (NaN, negative, > 2: the device's packed kernel does not take it)
+    if (!(mu <= 2.0 && (negative_mu || mu >= 0.0))) return r;  // (NaN, > 2, negative unless asked for: the packed kernels do not take it)
   }
   r.ok = true;
   r.has_mu = has_mu;
@@ -492,9 +494,10 @@ struct StageRing {
     return 0;
   }
   // `nc` columns packed into rows of `dpitch` bytes at `base` (host memory) by the pool's threads; out[j] describes column j.
-  // Returns false when a column is not representable (a second other value, an other value outside [0, 2]).
+  // Returns false when a column is not representable (a second other value, an other value outside [0, 2] — with negative_mu:
+  // above 2).
   static bool pack_columns_to(char* base, size_t dpitch, const double* src, size_t spitch_doubles, size_t n, size_t nc,
-                              CopyPool& pool, PackedColumn* out) {
+                              CopyPool& pool, PackedColumn* out, bool negative_mu = false) {
     std::atomic<int> stop{0};
     // a column is cut into `segs` runs of rows (multiples of 1 024 samples = 256 bytes of codes) so that the pool's threads
     // stay busy to the end — 50 columns on 16 threads were four rounds, the last one with two columns (round 6) —; a
@@ -506,7 +509,8 @@ struct StageRing {
       if (stop.load(std::memory_order_relaxed)) return;
       const size_t j = item / nseg, q = item % nseg, r0 = q * seg, len = std::min(seg, n - r0);
       unsigned char* o = reinterpret_cast<unsigned char*>(base + j * dpitch) + r0 / 4;
-      part[item] = pack_column_f64(src + j * spitch_doubles + r0, len, o, q + 1 == nseg ? dpitch - r0 / 4 : len / 4, &stop);
+      part[item] = pack_column_f64(src + j * spitch_doubles + r0, len, o, q + 1 == nseg ? dpitch - r0 / 4 : len / 4, &stop, -1,
+                                   negative_mu);
       if (!part[item].ok) stop.store(1, std::memory_order_relaxed);
     };
     pool.run_items(nc * nseg, fn);

@@ -286,6 +286,8 @@ void rvt_destroy(rvt_ctx* c) {
     if (c->ev_band_fin[i]) hipEventDestroy(c->ev_band_fin[i]);
     if (c->ev_band_copied[i]) hipEventDestroy(c->ev_band_copied[i]);
   }
+  for (auto& e : c->ev_recode)
+    if (e) hipEventDestroy(e);
   // device memory: the blocks of the streaming interface (raw: the caller's blocks share their pools), then every buffer
   // the context owns (its members' destructors)
   for (auto& p : c->queue)

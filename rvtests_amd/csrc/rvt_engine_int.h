@@ -263,6 +263,9 @@ struct rvt_ctx {
   int band_last_path = -1;       // which product the last rvt_cov_band took (rvt_cov_band_last_path)
   DevBuf<double> d_mu_nan;    // packed_columns_pass: the other values of up to kColQueue columns (NaN = none)
   DevBuf<char> d_colpack;     // rvt_block_upload_columns: the columns as 2-bit rows + their other values, before they are expanded
+  DevBuf<char> d_recode_ws;   // rvt_block_recode / rvt_bed_recode_block: the columns' integer counts and their avg (grow-only)
+  hipEvent_t ev_recode[4] = {};  // with profiling on: around the count pass (0, 1) and the write pass (2, 3) of the last recoding
+  double recode_ms[2] = {0.0, 0.0};
   // single columns uploaded one call at a time (MetaCovTest / MetaScoreTest: one site per fit()) are packed into pinned memory
   // and QUEUED: the DMA, the expansion and the column pass run once per kColQueue consecutive columns (flush_col_queue) — the
   // per-call device work (eight HIP calls, ~70 us) was what held the adapter at 9 k sites/s.  Everything that reads a block

@@ -8,6 +8,7 @@
 #include "band_rows.hip.h"
 #include "wald_logistic.hip.h"
 #include "burdencol_kernels.hip.h"
+#include "recode_kernels.hip.h"
 
 // row slices of MetaCov's column pass (cov_hc_prep_kernel): a function of N alone, so that a column's sums are the same numbers
 // whether it is treated inside a block or alone behind its upload (rvt_block_upload_columns)
@@ -1333,7 +1334,7 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
     }
     PackedColumn pc;
     if (StageRing::pack_columns_to(reinterpret_cast<char*>(q.h[q.cur].get()) + pitch * (size_t)q.n, pitch, G, N, N, 1,
-                                   CopyPool::column_instance(), &pc)) {
+                                   CopyPool::column_instance(), &pc, /*negative_mu=*/true)) {
       // whatever the engine knew about the overwritten column is void from here on
       auto itq = c->col_kind.find(dG);
       if (itq != c->col_kind.end() && (size_t)col0 < itq->second.valid.size()) itq->second.valid[(size_t)col0] = 0;
@@ -1448,6 +1449,212 @@ int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const 
       ck.valid[(size_t)col] = 1;
     }
   }
+  return RVT_OK;
+}
+
+// ---- dominant / recessive recoding on the device (recode_kernels.hip.h) ---------------------------------------------------------
+// Whatever the engine knew about columns [col0, col0 + ncols) of dG is void (as behind rvt_block_upload_columns)
+static int invalidate_columns(rvt_ctx* c, double* dG, int col0, int ncols) {
+  auto it = c->col_kind.find(dG);
+  if (it == c->col_kind.end()) return RVT_OK;
+  rvt_ctx::ColKind& ck = it->second;
+  for (int k = 0; k < ncols && !ck.valid.empty(); ++k)
+    if ((size_t)(col0 + k) < ck.valid.size()) ck.valid[(size_t)(col0 + k)] = 0;
+  if (ck.d_flags && !c->hc_enabled && col0 < ck.cols)  // (flags are not rewritten by packed_columns_pass then: unknown = not hard calls)
+    HIP_TRY(c, hipMemsetAsync(ck.d_flags + col0, 0, sizeof(int) * (size_t)std::min(ncols, ck.cols - col0), c->io_stream));
+  return RVT_OK;
+}
+
+// measurement (rvt_set_profiling): HIP events directly in front of and behind the count pass (0, 1) and the write pass (2, 3)
+static int recode_mark(rvt_ctx* c, int k, hipStream_t st) {
+  if (!c->profiling) return RVT_OK;
+  if (!c->ev_recode[k]) HIP_TRY(c, hipEventCreate(&c->ev_recode[k]));
+  HIP_TRY(c, hipEventRecord(c->ev_recode[k], st));
+  return RVT_OK;
+}
+static int recode_times(rvt_ctx* c) {  // (behind the call's last synchronisation)
+  if (!c->profiling) return RVT_OK;
+  float a = 0.0f, b = 0.0f;
+  HIP_TRY(c, hipEventElapsedTime(&a, c->ev_recode[0], c->ev_recode[1]));
+  HIP_TRY(c, hipEventElapsedTime(&b, c->ev_recode[2], c->ev_recode[3]));
+  c->recode_ms[0] = a, c->recode_ms[1] = b;
+  return RVT_OK;
+}
+int rvt_recode_last_timing(rvt_ctx* c, double* ms2) {
+  if (!c || !ms2) return RVT_E_INVALID;
+  ms2[0] = c->recode_ms[0], ms2[1] = c->recode_ms[1];
+  return RVT_OK;
+}
+
+// avg = carriers / nonmissing (0 when nothing is called): the one division of the reference's s / numGeno, on exact integers.
+// The recoded column holds 0 / 1 and, where a call was missing, avg — "hard calls plus one other value" unless avg is 0 or 1.
+static void recode_avg(long long nonmissing, long long carriers, long long N, double* avg, double* mu, int* hard) {
+  *avg = nonmissing > 0 ? (double)carriers / (double)nonmissing : 0.0;
+  *hard = (nonmissing == N || *avg == 0.0 || *avg == 1.0) ? 1 : 0;
+  *mu = *hard ? 0.0 : *avg;
+}
+
+// the columns' bookkeeping behind a recoding, kColQueue columns at a time (what a packed upload of the same columns leaves)
+static int recoded_columns_pass(rvt_ctx* c, double* dG, int col0, int ncols, const double* mu, const int* hard) {
+  for (int k0 = 0; k0 < ncols; k0 += rvt_ctx::kColQueue) {
+    const int nk = std::min(rvt_ctx::kColQueue, ncols - k0);
+    int rc = packed_columns_pass(c, dG, col0 + k0, nk, mu + k0, hard + k0);
+    if (rc) return rc;
+  }
+  return RVT_OK;
+}
+
+int rvt_block_recode(rvt_ctx* c, double* dst, int dst_col, const double* src, int src_col, int ncols, int coding, long long* counts) {
+  if (!c || !dst || !src || dst_col < 0 || src_col < 0 || ncols < 0) return fail(c, RVT_E_INVALID, "bad recode");
+  if (coding != RVT_CODING_DOMINANT && coding != RVT_CODING_RECESSIVE)
+    return fail(c, RVT_E_INVALID, "coding %d: 1 = dominant, 2 = recessive", coding);
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  for (int side = 0; side < 2; ++side) {  // (blocks of rvt_block_alloc know their width)
+    auto it = c->col_kind.find(side ? dst : src);
+    const int first = side ? dst_col : src_col;
+    if (it != c->col_kind.end() && (long long)first + ncols > it->second.cols)
+      return fail(c, RVT_E_INVALID, "columns [%d, %d) leave the block (%d columns)", first, first + ncols, it->second.cols);
+  }
+  // one block, two ranges that overlap without being the same: a workgroup would read columns another one is writing
+  if (dst == src && dst_col != src_col && std::abs(dst_col - src_col) < ncols)
+    return fail(c, RVT_E_INVALID, "source and target columns overlap without being the same");
+  if (ncols == 0) return RVT_OK;
+  hipSetDevice(c->device);
+  if (c->colq.n > 0) {  // (the source columns may still be queued)
+    int rc = flush_col_queue(c);
+    if (rc) return rc;
+  }
+  hipStream_t st = c->io_stream;  // behind the uploads and the passes that follow them
+  const int64_t N = c->nc.N, ld = c->null_ld;
+  const double threshold = coding == RVT_CODING_DOMINANT ? 0.5 : 1.5;
+  Layout L;
+  const size_t o_cnt = L.take(sizeof(unsigned long long) * 2 * (size_t)ncols), o_avg = L.take(sizeof(double) * (size_t)ncols);
+  // (no poison fill: it would run on the null stream, unordered against the clearing of the counts on this one)
+  HIP_TRY(c, c->d_recode_ws.grow(L.total, L.total + L.total / 2, st));
+  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->d_recode_ws + o_cnt);
+  double* d_avg = reinterpret_cast<double*>(c->d_recode_ws + o_avg);
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 2 * (size_t)ncols, st));
+  if (int rcm = recode_mark(c, 0, st)) return rcm;
+  constexpr int kCols = 32768;  // columns per launch (gridDim.y)
+  for (int k0 = 0; k0 < ncols; k0 += kCols) {
+    const int nk = std::min(kCols, ncols - k0);
+    hipLaunchKernelGGL(recode_count_kernel, dim3(recode_slices(N / 2, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                       src + (size_t)(src_col + k0) * (size_t)ld, (long long)N, (long long)ld, threshold, d_cnt + 2 * (size_t)k0);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (int rcm = recode_mark(c, 1, st)) return rcm;
+  std::vector<unsigned long long> cnt(2 * (size_t)ncols);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  std::vector<double> avg((size_t)ncols), mu((size_t)ncols);
+  std::vector<int> hard((size_t)ncols);
+  for (int k = 0; k < ncols; ++k) {
+    recode_avg((long long)cnt[2 * (size_t)k], (long long)cnt[2 * (size_t)k + 1], N, &avg[(size_t)k], &mu[(size_t)k], &hard[(size_t)k]);
+    if (counts) counts[2 * (size_t)k] = (long long)cnt[2 * (size_t)k], counts[2 * (size_t)k + 1] = (long long)cnt[2 * (size_t)k + 1];
+  }
+  int rc = small_h2d(c, d_avg, avg.data(), sizeof(double) * (size_t)ncols);
+  if (rc) return rc;
+  rc = invalidate_columns(c, dst, dst_col, ncols);
+  if (rc) return rc;
+  if (int rcm = recode_mark(c, 2, st)) return rcm;
+  for (int k0 = 0; k0 < ncols; k0 += kCols) {
+    const int nk = std::min(kCols, ncols - k0);
+    hipLaunchKernelGGL(recode_write_kernel, dim3(recode_slices(N / 2, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                       src + (size_t)(src_col + k0) * (size_t)ld, dst + (size_t)(dst_col + k0) * (size_t)ld, (long long)N, (long long)ld,
+                       threshold, d_avg + k0);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (int rcm = recode_mark(c, 3, st)) return rcm;
+  rc = recoded_columns_pass(c, dst, dst_col, ncols, mu.data(), hard.data());
+  if (rc) return rc;
+  HIP_TRY(c, sync_stream(st));  // complete on return, as rvt_block_copy_columns: the device calls run on other streams
+  return recode_times(c);
+}
+
+int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int coding, double* dG, int col0, long long* counts) {
+  if (!c || !d_rows || !dG || V < 0 || col0 < 0) return fail(c, RVT_E_INVALID, "bad recode");
+  if (coding != RVT_CODING_DOMINANT && coding != RVT_CODING_RECESSIVE)
+    return fail(c, RVT_E_INVALID, "coding %d: 1 = dominant, 2 = recessive", coding);
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  {
+    auto it = c->col_kind.find(dG);
+    if (it != c->col_kind.end() && (long long)col0 + V > it->second.cols)
+      return fail(c, RVT_E_INVALID, "columns [%d, %d) leave the block (%d columns)", col0, col0 + V, it->second.cols);
+  }
+  if (V == 0) return RVT_OK;
+  hipSetDevice(c->device);
+  if (c->colq.n > 0) {  // (queued columns of the target land first and are then overwritten)
+    int rc = flush_col_queue(c);
+    if (rc) return rc;
+  }
+  hipStream_t st = c->io_stream;
+  const int64_t N = c->nc.N, ld = c->null_ld, cb = (N + 3) / 4;
+  Layout L;
+  const size_t o_cnt = L.take(sizeof(unsigned long long) * 4 * (size_t)V), o_avg = L.take(sizeof(double) * (size_t)V);
+  // (no poison fill: it would run on the null stream, unordered against the clearing of the counts on this one)
+  HIP_TRY(c, c->d_recode_ws.grow(L.total, L.total + L.total / 2, st));
+  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->d_recode_ws + o_cnt);
+  double* d_avg = reinterpret_cast<double*>(c->d_recode_ws + o_avg);
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * (size_t)V, st));
+  if (int rcm = recode_mark(c, 0, st)) return rcm;
+  constexpr int kCols = 32768;
+  for (int k0 = 0; k0 < V; k0 += kCols) {
+    const int nk = std::min(kCols, V - k0);
+    hipLaunchKernelGGL(recode_bed_count_kernel, dim3(recode_slices((cb + 3) / 4, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                       d_rows + (size_t)k0 * (size_t)cb, (long long)cb, (long long)N, d_cnt + 4 * (size_t)k0);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (int rcm = recode_mark(c, 1, st)) return rcm;
+  std::vector<unsigned long long> cnt(4 * (size_t)V);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  std::vector<double> avg((size_t)V), mu((size_t)V);
+  std::vector<int> hard((size_t)V);
+  for (int k = 0; k < V; ++k) {
+    const unsigned long long* q = cnt.data() + 4 * (size_t)k;
+    const long long carriers = (long long)(coding == RVT_CODING_DOMINANT ? q[1] + q[2] : q[2]);
+    recode_avg((long long)(q[0] + q[1] + q[2]), carriers, N, &avg[(size_t)k], &mu[(size_t)k], &hard[(size_t)k]);
+    if (counts)
+      for (int e = 0; e < 4; ++e) counts[4 * (size_t)k + e] = (long long)q[e];
+  }
+  int rc = small_h2d(c, d_avg, avg.data(), sizeof(double) * (size_t)V);
+  if (rc) return rc;
+  rc = invalidate_columns(c, dG, col0, V);
+  if (rc) return rc;
+  if (int rcm = recode_mark(c, 2, st)) return rcm;
+  for (int k0 = 0; k0 < V; k0 += kCols) {
+    const int nk = std::min(kCols, V - k0);
+    hipLaunchKernelGGL(recode_bed_expand_kernel, dim3(recode_slices(cb, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                       d_rows + (size_t)k0 * (size_t)cb, (long long)cb, (long long)N, (long long)ld, coding == RVT_CODING_RECESSIVE ? 1 : 0,
+                       d_avg + k0, dG + (size_t)(col0 + k0) * (size_t)ld);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (int rcm = recode_mark(c, 3, st)) return rcm;
+  rc = recoded_columns_pass(c, dG, col0, V, mu.data(), hard.data());
+  if (rc) return rc;
+  HIP_TRY(c, sync_stream(st));  // synchronous
+  return recode_times(c);
+}
+
+int rvt_block_download_columns(rvt_ctx* c, const double* dG, int col0, int ncols, double* G_host) {
+  if (!c || !dG || !G_host || col0 < 0 || ncols < 0) return fail(c, RVT_E_INVALID, "bad download");
+  if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first");
+  {
+    auto it = c->col_kind.find(dG);
+    if (it != c->col_kind.end() && (long long)col0 + ncols > it->second.cols)
+      return fail(c, RVT_E_INVALID, "columns [%d, %d) leave the block (%d columns)", col0, col0 + ncols, it->second.cols);
+  }
+  if (ncols == 0) return RVT_OK;
+  hipSetDevice(c->device);
+  if (c->colq.n > 0) {
+    int rc = flush_col_queue(c);
+    if (rc) return rc;
+  }
+  HIP_TRY(c, sync_stream(c->io_stream));  // (queued uploads, expansions and recodings write what is copied here)
+  const size_t N = (size_t)(c->have_null ? c->nc.N : c->fam_nc.N);
+  const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
+  HIP_TRY(c, hipMemcpy2D(G_host, sizeof(double) * N, dG + (size_t)col0 * ld, sizeof(double) * ld, sizeof(double) * N, (size_t)ncols,
+                         hipMemcpyDeviceToHost));
   return RVT_OK;
 }
 

@@ -16,6 +16,7 @@ TEST_SKAT, TEST_SKATO, TEST_CMC, TEST_ZEGGINI, TEST_ALL = 1, 2, 4, 8, 15
 TEST_ANALYTICVT = 128
 MAX_INFLIGHT = int(os.environ.get("RVT_PY_MAX_INFLIGHT", 8))  # RVT_MAX_INFLIGHT (include/rvtests_amd.h; the env only for tools/build_variant.sh builds)
 TRAIT_QUANTITATIVE, TRAIT_BINARY = 0, 1
+CODING_DOMINANT, CODING_RECESSIVE = 1, 2   # RVT_CODING_* (rvt_block_recode / rvt_bed_recode_block)
 
 c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int)
@@ -1192,6 +1193,44 @@ class Engine:
         if G.ndim == 1:
             G = G.reshape(-1, 1, order="F")
         self._check(self.L.rvt_block_upload_columns(self.ctx, C.c_void_p(int(ptr)), int(col0), G.shape[1], _dp(G)))
+
+    def download_columns(self, ptr, col0, ncols):
+        """Columns [col0, col0 + ncols) of a device block as an N x ncols array (rvt_block_download_columns: queued uploads are
+        flushed first)."""
+        out = np.zeros((self.N, int(ncols)), order="F")
+        self.L.rvt_block_download_columns.restype = C.c_int
+        self.L.rvt_block_download_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_double_p]
+        self._check(self.L.rvt_block_download_columns(self.ctx, C.c_void_p(int(ptr)), int(col0), int(ncols), _dp(out)))
+        return out
+
+    def block_recode(self, dst, dst_col, src, src_col, ncols, coding, want_counts=True):
+        """Dominant / recessive recoding (CODING_DOMINANT / CODING_RECESSIVE) of columns [src_col, src_col + ncols) of block src
+        into columns [dst_col, ...) of block dst, in place when they are the same (rvt_block_recode).  Returns the counts
+        (ncols, 2): non-missing calls, carriers."""
+        cnt = np.zeros((int(ncols), 2), dtype=np.int64) if want_counts else None
+        self.L.rvt_block_recode.restype = C.c_int
+        self.L.rvt_block_recode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        self._check(self.L.rvt_block_recode(self.ctx, C.c_void_p(int(dst)), int(dst_col), C.c_void_p(int(src)), int(src_col),
+                                            int(ncols), int(coding), cnt.ctypes.data_as(C.c_void_p) if want_counts else None))
+        return cnt
+
+    def bed_recode_block(self, d_rows, V, coding, ptr, col0, want_counts=True):
+        """V consecutive rows of a resident .bed matrix, recoded, into columns [col0, col0 + V) of a device block
+        (rvt_bed_recode_block).  Returns the counts (V, 4): calls of 0, 1, 2, missing."""
+        cnt = np.zeros((int(V), 4), dtype=np.int64) if want_counts else None
+        self.L.rvt_bed_recode_block.restype = C.c_int
+        self.L.rvt_bed_recode_block.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        self._check(self.L.rvt_bed_recode_block(self.ctx, C.c_void_p(int(d_rows)), int(V), int(coding), C.c_void_p(int(ptr)),
+                                                int(col0), cnt.ctypes.data_as(C.c_void_p) if want_counts else None))
+        return cnt
+
+    def recode_last_timing(self):
+        """(count pass ms, write / expand pass ms) of the last recoding, measured with set_profiling(True)."""
+        ms = np.zeros(2)
+        self.L.rvt_recode_last_timing.restype = C.c_int
+        self.L.rvt_recode_last_timing.argtypes = [C.c_void_p, c_double_p]
+        self._check(self.L.rvt_recode_last_timing(self.ctx, _dp(ms)))
+        return float(ms[0]), float(ms[1])
 
     def move_columns(self, ptr, dst, src, n):
         self._check(self.L.rvt_block_move_columns(self.ctx, C.c_void_p(int(ptr)), int(dst), int(src), int(n)))
