@@ -477,8 +477,12 @@ int rvt_fit_grammar_null(rvt_ctx* ctx, int64_t N, int d, const double* X, const 
  * 1/2 sum (lambda + delta) u1 ug / sum (lambda + delta) u1^2 (:199-213).  ok[h] = 0 for a monomorphic column. */
 int rvt_grammar_block(rvt_ctx* ctx, const double* dG, int V, int af_kinship, int* ok, double* af, double* beta,
                       double* beta_var, double* pvalue);
-/* Copy columns between two device blocks (growing the adapter's ring).  What the engine keeps per uploaded column (below)
- * travels with them when both blocks came from rvt_block_alloc. */
+/* The column operations (copy, upload, download, recode, move) check their column ranges before any device work: a range
+ * that leaves a block of rvt_block_alloc is refused with RVT_E_INVALID, "columns [a, b) leave the block (M columns)", and
+ * nothing is written.  Only a block the engine knows can be checked: a pointer from elsewhere (a torch tensor with the block
+ * layout) is taken on trust, its width is the caller's business.
+ * Copy columns between two device blocks (growing the adapter's ring).  What the engine keeps per uploaded column (below)
+ * travels with them when both blocks came from rvt_block_alloc.  Either range is checked. */
 int rvt_block_copy_columns(rvt_ctx* ctx, double* dst, int dst_col, const double* src, int src_col, int ncols);
 /* Fill columns [col0, col0+ncols) of a device block from host memory (N doubles per column, contiguous).  Behind the copy the
  * engine reads the column once on the device: it records whether the column holds hard calls only (rvt_score_block / the
@@ -489,10 +493,12 @@ int rvt_block_copy_columns(rvt_ctx* ctx, double* dst, int dst_col, const double*
  * stores).  A single column (ncols = 1) of hard calls plus at most one other value — inside [0, 2], or negative: the missing
  * code of raw calls — is packed on the host and QUEUED: it becomes visible in the block after rvt_sync,
  * rvt_block_download_columns or another engine call on the block — a consumer outside the engine that reads the block's
- * memory before that sees what the column held before. */
+ * memory before that sees what the column held before.  A call that replaces the null model sends queued columns to their
+ * block first, under the model they were packed for.  RVT_E_INVALID: [col0, col0+ncols) leaves the block. */
 int rvt_block_upload_columns(rvt_ctx* ctx, double* dG, int col0, int ncols, const double* G);
 /* Copy columns [col0, col0+ncols) of a device block to host memory (N doubles per column, contiguous): queued single-column
- * uploads are flushed and the upload stream is waited for first, so the copy is what the engine's own calls would read. */
+ * uploads are flushed and the upload stream is waited for first, so the copy is what the engine's own calls would read.
+ * RVT_E_INVALID: [col0, col0+ncols) leaves the block. */
 int rvt_block_download_columns(rvt_ctx* ctx, const double* dG, int col0, int ncols, double* G_host);
 /* Dominant / recessive recoding of genotype columns on the device, for `--meta dominant` / `--meta recessive`
  * (DataConsolidator::codeGenotypeForDominantModel / codeGenotypeForRecessiveModel, src/DataConsolidator.cpp:390-472, which read
@@ -517,7 +523,7 @@ int rvt_block_recode(rvt_ctx* ctx, double* dst, int dst_col, const double* src, 
  * the passes is in neither figure. */
 int rvt_recode_last_timing(rvt_ctx* ctx, double* ms2);
 /* Move columns [src_col, src_col+ncols) of a device block down to dst_col <= src_col (ring compaction; the per-column records
- * move with them). */
+ * move with them).  RVT_E_INVALID: [src_col, src_col+ncols) leaves the block. */
 int rvt_block_move_columns(rvt_ctx* ctx, double* dG, int dst_col, int src_col, int ncols);
 
 /* ---- null models of unrelated samples on the device ---------------------------------------------------------------

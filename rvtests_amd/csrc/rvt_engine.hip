@@ -212,14 +212,6 @@ static void free_null(rvt_ctx* c) {
   c->have_null = false;
 }
 
-// a block whose content is new: its column flags and cache go (its column count and whether its cache could be allocated stay)
-static void clear_col_kind(rvt_ctx::ColKind& ck) {
-  rvt_ctx::ColKind fresh;
-  fresh.cols = ck.cols;
-  fresh.cache_failed = ck.cache_failed;
-  ck = std::move(fresh);
-}
-
 void rvt_destroy(rvt_ctx* c) {
   if (!c) return;
   if (c->trace_submit && c->tr_genes > 0)
@@ -280,8 +272,6 @@ void rvt_destroy(rvt_ctx* c) {
     if (c->ev_text_free[k]) hipEventDestroy(c->ev_text_free[k]);
     if (c->ev_text_copied[k]) hipEventDestroy(c->ev_text_copied[k]);
   }
-  for (int i = 0; i < 2; ++i)
-    if (c->colq.ev[i]) hipEventDestroy(c->colq.ev[i]);
   for (int i = 0; i < 2; ++i) {
     if (c->ev_band_fin[i]) hipEventDestroy(c->ev_band_fin[i]);
     if (c->ev_band_copied[i]) hipEventDestroy(c->ev_band_copied[i]);
@@ -315,6 +305,8 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
   hipSetDevice(c->device);
   for (auto& sl : c->slots) HIP_TRY(c, finish_slot(c, sl) ? hipErrorUnknown : hipSuccess);
   if (!c->queue.empty()) return fail(c, RVT_E_STATE, "collect the submitted genes before changing the null model");
+  // (queued columns were packed for the model that goes away: they reach their block under it, or the old model stays)
+  if (int rc = flush_col_queue_wait(c, false)) return rc;
   for (auto& bp : c->block_pool) hipFree(bp.second);  // pooled blocks were laid out for the previous N
   c->block_pool.clear();
   for (auto& bp : c->pk_pool) hipFree(bp.second);
@@ -547,17 +539,13 @@ int rvt_block_alloc(rvt_ctx* c, int M, double** out) {
   // (a context whose only model is the multiple-trait one, rvt_mt_fit_null: the same layout, ld = rvt_padded_ld(N))
   if (!c->have_null && !c->have_fam && !c->have_mt) return fail(c, RVT_E_STATE, "set the null model first (defines N)");
   hipSetDevice(c->device);
-  const size_t bytes = sizeof(double) * (size_t)(c->have_null ? c->null_ld : (c->have_fam ? c->fam_nc.ld : c->mt_ld)) * M;
+  const size_t bytes = sizeof(double) * (size_t)block_dims(c).ld * M;
   HIP_TRY(c, hipMalloc((void**)out, bytes));
   // cleared on the stream the streaming entry points write blocks on, and complete on return: a hipMemset on the null
   // stream is not ordered against that (non-blocking) stream and could land after a decoder had filled the block
   HIP_TRY(c, hipMemsetAsync(*out, 0, bytes, c->io_stream));
   HIP_TRY(c, sync_stream(c->io_stream));
-  {  // (flags are allocated by the first column upload; a zeroed block holds hard calls only)
-    rvt_ctx::ColKind& ck = c->col_kind[*out];
-    clear_col_kind(ck);  // (an earlier block at the same address that was freed behind our back)
-    ck.cols = M;
-  }
+  block_register(c, *out, M);
   return RVT_OK;
 }
 
@@ -579,7 +567,7 @@ int rvt_block_classify(rvt_ctx* c, const double* dG, int M, int* is_hard_call) {
   if (!c || !dG || M < 1) return fail(c, RVT_E_INVALID, "bad block");
   if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first (defines N)");
   hipSetDevice(c->device);
-  const int64_t N = c->have_null ? c->nc.N : c->fam_nc.N, ld = c->have_null ? c->null_ld : c->fam_nc.ld;
+  const int64_t N = block_dims(c).N, ld = block_dims(c).ld;
   HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int)));
   int rc = enqueue_classify(c, dG, M, N, ld, c->io_stream, c->d_kind);
   if (rc) return rc;
@@ -630,15 +618,7 @@ int rvt_set_content_hint(rvt_ctx* c, int hint) {
 int rvt_block_free(rvt_ctx* c, double* dG) {
   if (!c) return RVT_E_INVALID;
   hipSetDevice(c->device);
-  if (c->colq.n > 0) {
-    if (c->colq.dG == dG) c->colq.n = 0;  // (queued columns of the block that goes away)
-    else if (int rc = flush_col_queue(c)) return rc;
-  }
-  (void)sync_stream(c->io_stream);
-  {
-    auto it = c->col_kind.find(dG);
-    if (it != c->col_kind.end()) c->col_kind.erase(it);
-  }
+  if (int rc = block_forget(c, dG)) return rc;
   if (dG) HIP_TRY(c, hipFree(dG));
   return RVT_OK;
 }
@@ -955,16 +935,9 @@ int upload_block_data(rvt_ctx* c, double* dG, int M, const double* G) {
   if (!c || !dG || !G || M < 1) return fail(c, RVT_E_INVALID, "bad upload");
   if (!c->have_null && !c->have_fam && !c->have_mt) return fail(c, RVT_E_STATE, "set the null model first");
   hipSetDevice(c->device);
-  if (c->colq.n > 0) {
-    int rcq = flush_col_queue(c);
-    if (rcq) return rcq;
-  }
-  {  // per-column flags of an earlier column-wise fill no longer describe the block
-    auto it = c->col_kind.find(dG);
-    if (it != c->col_kind.end()) clear_col_kind(it->second);
-  }
-  const size_t N = (size_t)(c->have_null ? c->nc.N : (c->have_fam ? c->fam_nc.N : c->mt_N));
-  const size_t bld = (size_t)(c->have_null ? c->null_ld : (c->have_fam ? c->fam_nc.ld : c->mt_ld));
+  if (int rcq = flush_col_queue(c)) return rcq;
+  block_replaced(c, dG);  // per-column flags of an earlier column-wise fill no longer describe the block
+  const size_t N = (size_t)block_dims(c).N, bld = (size_t)block_dims(c).ld;
   return staged_h2d_2d(c, dG, sizeof(double) * bld, G, sizeof(double) * N, sizeof(double) * N, (size_t)M);
 }
 
@@ -1331,11 +1304,8 @@ static size_t batch_stage_bytes(int n, size_t af_total) {
 
 // flush the column queue, take the slot that was launched longest ago and drain it
 static int acquire_slot(rvt_ctx* c, Batch& b) {
-  if (c->colq.n > 0) {  // (columns queued by rvt_block_upload_columns may belong to a block of this batch)
-    int rcq = flush_col_queue(c);
-    if (rcq) return rcq;
-    HIP_TRY(c, sync_stream(c->io_stream));
-  }
+  // (columns queued by rvt_block_upload_columns may belong to a block of this batch)
+  if (int rcq = flush_col_queue_wait(c, false)) return rcq;
   // pick the slot that was launched longest ago; if its batch is still in flight, finish it first
   Slot* slp = &c->slots[0];
   for (int i = 1; i < kSlots; ++i)
@@ -1944,11 +1914,8 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
 int rvt_sync(rvt_ctx* c) {
   if (!c) return RVT_E_INVALID;
   hipSetDevice(c->device);
-  if (c->colq.n > 0) {  // columns queued by rvt_block_upload_columns reach their block before anything reads it
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
-  }
-  if (c->colq.used[0] || c->colq.used[1]) HIP_TRY(c, sync_stream(c->io_stream));  // (the uploads' device work is on io_stream)
+  // columns queued by rvt_block_upload_columns reach their block before anything reads it
+  if (int rc = flush_col_queue_wait(c, true)) return rc;
   // oldest batch first, so records reach the caller in launch order
   Slot* order[kSlots];
   for (int i = 0; i < kSlots; ++i) order[i] = &c->slots[i];

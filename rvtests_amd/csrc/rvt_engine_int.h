@@ -268,8 +268,8 @@ struct rvt_ctx {
   double recode_ms[2] = {0.0, 0.0};
   // single columns uploaded one call at a time (MetaCovTest / MetaScoreTest: one site per fit()) are packed into pinned memory
   // and QUEUED: the DMA, the expansion and the column pass run once per kColQueue consecutive columns (flush_col_queue) — the
-  // per-call device work (eight HIP calls, ~70 us) was what held the adapter at 9 k sites/s.  Everything that reads a block
-  // flushes first (rvt_sync, the column operations).
+  // per-call device work (eight HIP calls, ~70 us) was what held the adapter at 9 k sites/s.  ONE RULE: whatever reads a block,
+  // or replaces the model the queue was packed for, flushes first (flush_col_queue returns at once on an empty queue).
   static constexpr int kColQueue = 32;
   struct ColQueue {
     PinBuf<unsigned char> h[2];  // kColQueue rows of `pitch` bytes each
@@ -280,28 +280,32 @@ struct rvt_ctx {
     double* dG = nullptr;
     double mu[kColQueue];
     int hard[kColQueue];
+    ~ColQueue() {
+      for (hipEvent_t e : ev)
+        if (e) hipEventDestroy(e);
+    }
   } colq;
   DevBuf<char> d_cov_work;    // work space of the MetaCov rectangles (S, T, the band, column statistics): grow-only
   hipEvent_t ev_band_fin[2] = {}, ev_band_copied[2] = {};  // rvt_cov_band: a pass's rows are copied out while the next pass multiplies
-  // per-column content flags of blocks filled column by column (rvt_block_upload_columns): nonzero = hard calls only
-  // Round 5: ... and, for a ring that MetaCov will read (unweighted model), what the column pass of the hard-call band would
-  // compute for the column anyway — the int8 copy, the column sum, the polymorphic flag and its row of T = G'X — made by the
-  // pass that classifies the column behind its PCIe copy and kept with the block (moved and copied with its columns), so that a
-  // flush starts at the integer product.  `valid[j]`: column j's entries were made under null model number `gen`.
+  // What the engine knows about a block of rvt_block_alloc, and the one owner of it (the operations are in rvt_meta.hip, "column
+  // blocks"): its width; per-column content flags (nonzero = hard calls only; allocated by the first column upload); and, for a
+  // ring that MetaCov will read (unweighted model), what the column pass of the hard-call band would compute for a column
+  // anyway — int8 copy, E2M1 codes, the mask of the ONE other value, sum, polymorphic flag, row of T = G'X — made behind the
+  // column's upload and moved and copied with it, so that a covariance call starts at the integer product.  The cache is an
+  // optimisation: a failed allocation leaves the block without one, it does not fail a call.
   struct ColKind {
     int cols = 0;
     DevBuf<int> d_flags;
     DevBuf<signed char> d_i8;    // [cols rounded up + a tile of slack][ldk]
     DevBuf<unsigned char> d_i4;  // [cols][ldk4]: the same hard calls as E2M1 codes, two per byte (band_gemm.hip.h, FP4)
-    DevBuf<unsigned char> d_m4;  // [cols][ldk4]: round 6 — the mask of a column's ONE other value (the imputed mean), same codes
+    DevBuf<unsigned char> d_m4;  // [cols][ldk4]: the mask of a column's ONE other value (the imputed mean), same codes
     DevBuf<double> d_mu;         // [cols]: that other value (0 for a column without one)
-    int64_t ldk4 = 0;
-    bool cache_failed = false;  // the cache could not be allocated once: not retried for this block
-    DevBuf<double> d_cs;    // [cols] column sums
-    DevBuf<int> d_poly;     // [cols]
-    DevBuf<double> d_T;     // [cols][RVT_MAX_COV]
-    int64_t ldk = 0;
-    uint64_t gen = 0;
+    DevBuf<double> d_cs;         // [cols] column sums
+    DevBuf<int> d_poly;          // [cols]
+    DevBuf<double> d_T;          // [cols][RVT_MAX_COV]
+    int64_t ldk = 0, ldk4 = 0;
+    uint64_t gen = 0;            // the cache was made under null model number `gen`
+    bool cache_failed = false;   // the cache could not be allocated once: not retried for this block
     std::vector<unsigned char> valid;  // per column: 0 nothing known / not usable, 1 hard calls only, 2 hard calls + one other value
   };
   int handed_back_recently = 0;   // > 0: a hard-call gene was handed back within the last 16 batches (launch_suffstat's list grid)
@@ -522,6 +526,16 @@ struct rvt_ctx {
   size_t eigen_lds_max = 48 * 1024;
 };
 
+// N and ld of the layout that blocks (rvt_block_alloc) have under the installed model: the null model's, else the family
+// model's, else the multiple-trait model's
+struct BlockDims {
+  int64_t N, ld;
+};
+inline BlockDims block_dims(const rvt_ctx* c) {
+  if (c->have_null) return {c->nc.N, c->null_ld};
+  return c->have_fam ? BlockDims{c->fam_nc.N, c->fam_nc.ld} : BlockDims{c->mt_N, c->mt_ld};
+}
+
 namespace {
 
 int fail(rvt_ctx* c, int code, const char* fmt, ...) {
@@ -741,7 +755,12 @@ void choose_split(int64_t ld, int n_genes, bool weighted, int* n_wparts, int* st
 // header and gets the bodies of that family alone (tools and the host harness define nothing and get everything).  The few
 // kernels that two units launch live in one of them; the other goes through these host launchers (tools/kernel_units.sh
 // lists which object carries which kernel).
-extern "C" RVT_INTERNAL int flush_col_queue(rvt_ctx* c);                                                      // rvt_meta.hip
+// the column blocks' bookkeeping (rvt_meta.hip): the queue of single columns, and a block that is new / goes away / is refilled
+extern "C" RVT_INTERNAL int flush_col_queue(rvt_ctx* c);
+extern "C" RVT_INTERNAL int flush_col_queue_wait(rvt_ctx* c, bool earlier_flushes_too);
+RVT_INTERNAL void block_register(rvt_ctx* c, const double* dG, int cols);
+RVT_INTERNAL int block_forget(rvt_ctx* c, const double* dG);
+RVT_INTERNAL void block_replaced(rvt_ctx* c, const double* dG);
 RVT_INTERNAL void k_lmm_sums(dim3 grid, hipStream_t st, const double* uxy, const double* lam, long long N, int d, double delta,
                              int take_abs, double* partial);                                                   // rvt_fam.hip
 RVT_INTERNAL void k_fam_colstat(dim3 grid, hipStream_t st, const double* const* cols, long long N, int* flags);  // rvt_fam.hip

@@ -934,8 +934,8 @@ int rvt_debug_rotate(rvt_ctx* c, const double* dG, int ncols, double* out) {
   if (!c || !dG || !out || ncols < 1) return fail(c, RVT_E_INVALID, "bad arguments");
   if (!c->have_kin) return fail(c, RVT_E_STATE, "rvt_set_kinship first");
   if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first (defines the block layout)");
-  const int64_t N = c->kin_N, ld = c->have_null ? c->null_ld : c->fam_nc.ld;  // (the layout rvt_block_alloc gave dG)
-  if ((c->have_null ? c->nc.N : c->fam_nc.N) != N) return fail(c, RVT_E_STATE, "the kinship and the null model differ in N");
+  const int64_t N = c->kin_N, ld = block_dims(c).ld;  // (the layout rvt_block_alloc gave dG)
+  if (block_dims(c).N != N) return fail(c, RVT_E_STATE, "the kinship and the null model differ in N");
   hipSetDevice(c->device);
   int rc = rvt_sync(c);
   if (rc) return rc;

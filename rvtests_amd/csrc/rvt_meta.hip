@@ -14,6 +14,171 @@
 // whether it is treated inside a block or alone behind its upload (rvt_block_upload_columns)
 static constexpr int kCovSlices = 16;
 
+// ---- column blocks: what the engine knows about a block of rvt_block_alloc (rvt_ctx::ColKind), every operation written once ----
+using ColKind = rvt_ctx::ColKind;
+
+static ColKind* find_block(rvt_ctx* c, const double* dG) {
+  auto it = c->col_kind.find(dG);
+  return it == c->col_kind.end() ? nullptr : &it->second;
+}
+
+// Columns [col0, col0 + ncols) lie inside the block — asked of every column operation before any device work.  Only a block
+// the engine knows can be checked: a pointer it does not know (a caller's own allocation) is taken on trust.
+static int check_columns(rvt_ctx* c, const double* dG, int col0, int ncols) {
+  const ColKind* ck = find_block(c, dG);
+  if (ck && (long long)col0 + ncols > ck->cols)
+    return fail(c, RVT_E_INVALID, "columns [%d, %d) leave the block (%d columns)", col0, col0 + ncols, ck->cols);
+  return RVT_OK;
+}
+
+// What was known about columns [col0, col0 + ncols) is void, they are being overwritten: their cache entries (a stale one
+// would hand the OLD column to the integer product, which no longer tests what it reads once an entry is marked valid) and
+// their content flags — unless a column pass behind the caller rewrites those (pass_follows: it does while hard calls are
+// switched on).  Unknown = not hard calls.
+static int invalidate_columns(rvt_ctx* c, ColKind* ck, int col0, int ncols, bool pass_follows) {
+  if (!ck) return RVT_OK;
+  if (!ck->valid.empty()) std::fill_n(ck->valid.begin() + col0, (size_t)ncols, (unsigned char)0);
+  if (ck->d_flags && !(pass_follows && c->hc_enabled))
+    HIP_TRY(c, hipMemsetAsync(ck->d_flags + col0, 0, sizeof(int) * (size_t)ncols, c->io_stream));
+  return RVT_OK;
+}
+
+// (flags are allocated by the first column that arrives; the zeroed block of rvt_block_alloc holds hard calls only)
+static int ensure_flags(rvt_ctx* c, ColKind& ck) {
+  if (ck.d_flags) return RVT_OK;
+  HIP_TRY(c, ck.d_flags.alloc(sizeof(int) * (size_t)ck.cols));
+  HIP_TRY(c, hipMemsetAsync(ck.d_flags, 0x01, sizeof(int) * (size_t)ck.cols, c->io_stream));
+  return RVT_OK;
+}
+
+static void free_col_cache(ColKind& ck) {
+  ck.d_i8.reset();
+  ck.d_i4.reset();
+  ck.d_m4.reset();
+  ck.d_mu.reset();
+  ck.d_cs.reset();
+  ck.d_poly.reset();
+  ck.d_T.reset();
+  std::fill(ck.valid.begin(), ck.valid.end(), 0);
+}
+static bool alloc_col_cache(ColKind& ck, int64_t ldk, int64_t ldk4, uint64_t gen, hipStream_t st) {
+  const size_t cap = ((size_t)ck.cols + 255) / 256 * 256 + 256;  // (the products read whole tiles of columns)
+  bool ok = ck.d_i8.alloc(cap * (size_t)ldk) == hipSuccess &&
+            ck.d_i4.alloc(cap * (size_t)ldk4) == hipSuccess &&
+            ck.d_m4.alloc(cap * (size_t)ldk4) == hipSuccess &&
+            ck.d_mu.alloc(sizeof(double) * (size_t)ck.cols) == hipSuccess &&
+            ck.d_cs.alloc(sizeof(double) * (size_t)ck.cols) == hipSuccess &&
+            ck.d_poly.alloc(sizeof(int) * (size_t)ck.cols) == hipSuccess &&
+            ck.d_T.alloc(sizeof(double) * (size_t)ck.cols * RVT_MAX_COV) == hipSuccess;
+  ok = ok && hipMemsetAsync(ck.d_i8, 0, cap * (size_t)ldk, st) == hipSuccess &&
+       hipMemsetAsync(ck.d_i4, 0, cap * (size_t)ldk4, st) == hipSuccess &&
+       hipMemsetAsync(ck.d_m4, 0, cap * (size_t)ldk4, st) == hipSuccess &&
+       hipMemsetAsync(ck.d_mu, 0, sizeof(double) * (size_t)ck.cols, st) == hipSuccess;
+  ck.valid.assign((size_t)ck.cols, 0);
+  if (!ok) {
+    (void)hipGetLastError();
+    free_col_cache(ck);
+    return false;
+  }
+  ck.ldk = ldk;
+  ck.ldk4 = ldk4;
+  ck.gen = gen;
+  return true;
+}
+
+// bytes between the int8 columns of a cache made for N samples (its E2M1 columns: two codes per byte)
+static int64_t cache_ldk(int64_t N) { return (N + 127) / 128 * 128; }
+
+// Make sure the block has a column cache of the INSTALLED model (unweighted null models only; one made under another model is
+// freed, nothing of it is used; an allocation that failed once is not tried again) and say whether it has one.
+static bool ensure_cache(rvt_ctx* c, ColKind& ck) {
+  if (!c->have_null || c->nc.binary || getenv("RVT_METACOV_NO_CACHE")) return false;
+  const int64_t ldk = cache_ldk(c->nc.N), ldk4 = cache_ldk((c->nc.N + 1) / 2);
+  if (ck.d_i8 && (ck.ldk != ldk || ck.gen != c->null_gen || !ck.d_i4)) free_col_cache(ck);
+  if (!ck.d_i8 && !ck.cache_failed && !alloc_col_cache(ck, ldk, ldk4, c->null_gen, c->io_stream)) ck.cache_failed = true;
+  return ck.d_i8 != nullptr;
+}
+
+// The block's cache when a covariance call can start from it, else nullptr: made under the installed model, and every one of
+// the W columns from col0 (of a ring of `ring` columns when ring > 0) has an entry.  State 1 (hard calls only) always counts;
+// state 2 (hard calls plus one other value) where the caller can use the mask — it passes `masked` and multiplies E2M1 codes
+// (fp4) — and *masked then says whether some column is in state 2.
+static const ColKind* usable_cache(rvt_ctx* c, const double* dG, int ring, int col0, int W, bool fp4, bool* masked) {
+  if (masked) *masked = false;
+  const ColKind* ck = find_block(c, dG);
+  if (!ck || !ck->d_i8 || ck->gen != c->null_gen || ck->ldk != cache_ldk(c->nc.N) || (fp4 && !ck->d_i4) ||
+      (ring > 0 ? ring : col0 + W) > ck->cols || getenv("RVT_METACOV_NO_CACHE"))
+    return nullptr;
+  bool any2 = false;
+  for (int j = 0; j < W; ++j) {
+    int p = col0 + j;
+    if (ring > 0 && p >= ring) p -= ring;
+    const unsigned char v = ck->valid[(size_t)p];
+    if (v == 0 || (v == 2 && !(masked && fp4 && ck->d_m4))) return nullptr;
+    any2 = any2 || v == 2;
+  }
+  if (masked) *masked = any2;
+  return ck;
+}
+
+// the cache entries of ncols columns from (block s, column sc) to (block t, column tc), both ranges inside their blocks; t == s
+// allowed (a forward move: tc < sc); s == nullptr: nothing is known about the source.  Columns whose source has no valid entry
+// become invalid in the target.
+static int move_col_cache(rvt_ctx* c, ColKind* t, int tc, const ColKind* s, int sc, int ncols, hipStream_t st) {
+  const bool usable = s && s->d_i8 && !(t->d_i8 && (t->ldk != s->ldk || t->gen != s->gen)) &&
+                      (t->d_i8 || (s->d_i4 && alloc_col_cache(*t, s->ldk, s->ldk4, s->gen, st)));  // (no cache yet: one shaped as the source's)
+  if (!usable) {
+    if (!t->valid.empty()) std::fill_n(t->valid.begin() + tc, (size_t)ncols, (unsigned char)0);
+    return RVT_OK;
+  }
+  // (forward, in pieces no longer than the shift: a piece never overwrites what it has not read)
+  const int shift = (t == s) ? sc - tc : ncols;
+  for (int k0 = 0; k0 < ncols; k0 += std::max(shift, 1)) {
+    const int nk = std::min(std::max(shift, 1), ncols - k0);
+    HIP_TRY(c, hipMemcpyAsync(t->d_i8 + (size_t)(tc + k0) * (size_t)s->ldk, s->d_i8 + (size_t)(sc + k0) * (size_t)s->ldk,
+                              (size_t)nk * (size_t)s->ldk, hipMemcpyDeviceToDevice, st));
+    if (t->d_i4 && s->d_i4)
+      HIP_TRY(c, hipMemcpyAsync(t->d_i4 + (size_t)(tc + k0) * (size_t)s->ldk4, s->d_i4 + (size_t)(sc + k0) * (size_t)s->ldk4,
+                                (size_t)nk * (size_t)s->ldk4, hipMemcpyDeviceToDevice, st));
+    if (t->d_m4 && s->d_m4) {
+      HIP_TRY(c, hipMemcpyAsync(t->d_m4 + (size_t)(tc + k0) * (size_t)s->ldk4, s->d_m4 + (size_t)(sc + k0) * (size_t)s->ldk4,
+                                (size_t)nk * (size_t)s->ldk4, hipMemcpyDeviceToDevice, st));
+      HIP_TRY(c, hipMemcpyAsync(t->d_mu + tc + k0, s->d_mu + sc + k0, sizeof(double) * (size_t)nk, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(c, hipMemcpyAsync(t->d_cs + tc + k0, s->d_cs + sc + k0, sizeof(double) * (size_t)nk, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(t->d_poly + tc + k0, s->d_poly + sc + k0, sizeof(int) * (size_t)nk, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(t->d_T + (size_t)(tc + k0) * RVT_MAX_COV, s->d_T + (size_t)(sc + k0) * RVT_MAX_COV,
+                              sizeof(double) * (size_t)nk * RVT_MAX_COV, hipMemcpyDeviceToDevice, st));
+  }
+  std::copy_n(s->valid.begin() + sc, (size_t)ncols, t->valid.begin() + tc);  // (forward: tc < sc inside one block)
+  return RVT_OK;
+}
+
+// rvt_block_alloc made dG (nothing of an earlier block at the same address, freed behind the engine's back, survives)
+void block_register(rvt_ctx* c, const double* dG, int cols) {
+  ColKind& ck = c->col_kind[dG];
+  ck = ColKind();
+  ck.cols = cols;
+}
+// rvt_block_free: queued columns of the block that goes away are dropped, another block's reach it first
+int block_forget(rvt_ctx* c, const double* dG) {
+  if (c->colq.dG == dG) c->colq.n = 0;
+  else if (int rc = flush_col_queue(c)) return rc;
+  (void)sync_stream(c->io_stream);
+  c->col_kind.erase(dG);
+  return RVT_OK;
+}
+// the block's whole content is replaced (rvt_block_upload): its flags and cache go, its width and whether its cache could be
+// allocated stay
+void block_replaced(rvt_ctx* c, const double* dG) {
+  ColKind* ck = find_block(c, dG);
+  if (!ck) return;
+  ColKind fresh;
+  fresh.cols = ck->cols;
+  fresh.cache_failed = ck->cache_failed;
+  *ck = std::move(fresh);
+}
+
 extern "C" {
 // C (M x (Nb + Nb2), column-major, leading dimension ldc) = A' D [B | B2] in fp64 on the matrix cores (gemm_f64.hip.h).
 // A: M columns (lda apart), B: Nb columns, B2: Nb2 further columns (the null-model columns), all N samples long and
@@ -73,14 +238,14 @@ static int block_hard_calls(rvt_ctx* c, const double* dG, int V, std::vector<int
   if (colflag) colflag->clear();
   if (any) *any = false;
   if (!c->hc_enabled) return 0;
-  auto it = c->col_kind.find(dG);
-  if (it == c->col_kind.end() || !it->second.d_flags || V > it->second.cols) {
+  const ColKind* ck = find_block(c, dG);
+  if (!ck || !ck->d_flags || V > ck->cols) {
     if (c->content_hint == 0) return 0;  // the caller said dosages (rvt_set_content_hint): do not try the integer path first
     if (any) *any = true;
     return -1;
   }
   std::vector<int> f((size_t)V);
-  if (hipMemcpyAsync(f.data(), it->second.d_flags, sizeof(int) * (size_t)V, hipMemcpyDeviceToHost, c->io_stream) != hipSuccess ||
+  if (hipMemcpyAsync(f.data(), ck->d_flags, sizeof(int) * (size_t)V, hipMemcpyDeviceToHost, c->io_stream) != hipSuccess ||
       sync_stream(c->io_stream) != hipSuccess)
     return 0;
   bool all = true, some = false;
@@ -623,16 +788,8 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
   }
   // the block's own column cache (rvt_block_upload_columns made it behind the PCIe copies): every column of the window has its
   // int8 copy, sum, flag and row of T under THIS null model -> the call starts at the integer product
-  const rvt_ctx::ColKind* ckc = nullptr;
-  if (fast) {
-    auto itc = c->col_kind.find(dG);
-    if (itc != c->col_kind.end() && itc->second.d_i8 && itc->second.gen == c->null_gen &&
-        itc->second.ldk == (N + 127) / 128 * 128 && col0 + W <= itc->second.cols && !getenv("RVT_METACOV_NO_CACHE")) {
-      bool all = true;
-      for (int j = col0; j < col0 + W && all; ++j) all = itc->second.valid[(size_t)j] == 1;  // (2 = hard calls + an other value: MXFP4 band only)
-      if (all) ckc = &itc->second;
-    }
-  }
+  // (state 1 only; 2 = hard calls + an other value: MXFP4 band only)
+  const ColKind* ckc = fast ? usable_cache(c, dG, 0, col0, W, false, nullptr) : nullptr;
   if (fast && ckc) {
     const int64_t ldk = ckc->ldk;
     hipLaunchKernelGGL(cov_cache_gather_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, ckc->d_cs + col0,
@@ -728,11 +885,11 @@ static void launch_cov_prep(hipStream_t st, int d, bool pack, dim3 grid, const d
 //  upload, counts as usable although its content flag says "not hard calls only")
 static int ring_hard_calls(rvt_ctx* c, const double* dG, int ring, int col0, int W, const unsigned char* masked_ok = nullptr) {
   if (!c->hc_enabled) return 0;
-  auto it = c->col_kind.find(dG);
+  const ColKind* ck = find_block(c, dG);
   const int span = ring > 0 ? ring : col0 + W;
-  if (it == c->col_kind.end() || !it->second.d_flags || span > it->second.cols) return c->content_hint == 0 ? 0 : -1;
+  if (!ck || !ck->d_flags || span > ck->cols) return c->content_hint == 0 ? 0 : -1;
   std::vector<int> f((size_t)span);
-  if (hipMemcpyAsync(f.data(), it->second.d_flags, sizeof(int) * (size_t)span, hipMemcpyDeviceToHost, c->io_stream) != hipSuccess ||
+  if (hipMemcpyAsync(f.data(), ck->d_flags, sizeof(int) * (size_t)span, hipMemcpyDeviceToHost, c->io_stream) != hipSuccess ||
       sync_stream(c->io_stream) != hipSuccess)
     return 0;
   for (int j = 0; j < W; ++j) {
@@ -750,11 +907,8 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   if (ring > 0 && (col0 >= ring || W > ring)) return fail(c, RVT_E_INVALID, "window of %d columns from %d in a ring of %d", W, col0, ring);
   if ((long long)W > (long long)H + halo) W = H + halo;  // (markers behind the last head's window are never read)
-  {
-    auto it = c->col_kind.find(dG);
-    if (it != c->col_kind.end() && (ring > 0 ? ring : col0 + W) > it->second.cols)
-      return fail(c, RVT_E_INVALID, "the window leaves the block (%d columns)", it->second.cols);
-  }
+  if (const ColKind* ck = find_block(c, dG))
+    if ((ring > 0 ? ring : col0 + W) > ck->cols) return fail(c, RVT_E_INVALID, "the window leaves the block (%d columns)", ck->cols);
   hipSetDevice(c->device);
   int rc = rvt_sync(c);
   if (rc) return rc;
@@ -772,24 +926,8 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
   const bool fp4 = !getenv("RVT_BAND_INT8");
   // the ring's own column cache (rvt_block_upload_columns made it behind the uploads): usable when every column of the window
   // has an entry made under THIS null model — state 1 hard calls only, state 2 hard calls plus one other value (MXFP4 only)
-  const rvt_ctx::ColKind* ckc = nullptr;
   bool masked = false;
-  {
-    auto itc = c->col_kind.find(dG);
-    if (itc != c->col_kind.end() && itc->second.d_i8 && itc->second.gen == c->null_gen &&
-        itc->second.ldk == (N + 127) / 128 * 128 && !getenv("RVT_METACOV_NO_CACHE") && (!fp4 || itc->second.d_i4)) {
-      bool all = true;
-      for (int j = 0; j < W && all; ++j) {
-        int p = col0 + j;
-        if (ring > 0 && p >= ring) p -= ring;
-        const unsigned char v = itc->second.valid[(size_t)p];
-        all = v != 0 && (v == 1 || (fp4 && itc->second.d_m4));
-        masked = masked || v == 2;
-      }
-      if (all) ckc = &itc->second;
-      else masked = false;
-    }
-  }
+  const ColKind* ckc = usable_cache(c, dG, ring, col0, W, fp4, &masked);
   const bool fast = allow_fast && !nc.binary && !getenv("RVT_METACOV_FP64") &&
                     ring_hard_calls(c, dG, ring, col0, W, (ckc && masked) ? ckc->valid.data() : nullptr) != 0;
   if (!fast) {
@@ -1085,386 +1223,257 @@ int rvt_cov_band_fam(rvt_ctx* c, const double* dG, int ring_cols, int col0, int 
   return RVT_OK;
 }
 
-// the column cache of a block (int8 copy, E2M1 copy, sums, flags, rows of T): an optimisation — a failed allocation leaves the
-// block without one (every column invalid; the covariance calls then run their own column pass), it does not fail the call
-static void free_col_cache(rvt_ctx::ColKind& ck) {
-  ck.d_i8.reset();
-  ck.d_i4.reset();
-  ck.d_m4.reset();
-  ck.d_mu.reset();
-  ck.d_cs.reset();
-  ck.d_poly.reset();
-  ck.d_T.reset();
-  std::fill(ck.valid.begin(), ck.valid.end(), 0);
-}
-static bool alloc_col_cache(rvt_ctx* c, rvt_ctx::ColKind& ck, int64_t ldk, int64_t ldk4, uint64_t gen, hipStream_t st) {
-  const size_t cap = ((size_t)ck.cols + 255) / 256 * 256 + 256;  // (the products read whole tiles of columns)
-  bool ok = ck.d_i8.alloc(cap * (size_t)ldk) == hipSuccess &&
-            ck.d_i4.alloc(cap * (size_t)ldk4) == hipSuccess &&
-            ck.d_m4.alloc(cap * (size_t)ldk4) == hipSuccess &&
-            ck.d_mu.alloc(sizeof(double) * (size_t)ck.cols) == hipSuccess &&
-            ck.d_cs.alloc(sizeof(double) * (size_t)ck.cols) == hipSuccess &&
-            ck.d_poly.alloc(sizeof(int) * (size_t)ck.cols) == hipSuccess &&
-            ck.d_T.alloc(sizeof(double) * (size_t)ck.cols * RVT_MAX_COV) == hipSuccess;
-  ok = ok && hipMemsetAsync(ck.d_i8, 0, cap * (size_t)ldk, st) == hipSuccess &&
-       hipMemsetAsync(ck.d_i4, 0, cap * (size_t)ldk4, st) == hipSuccess &&
-       hipMemsetAsync(ck.d_m4, 0, cap * (size_t)ldk4, st) == hipSuccess &&
-       hipMemsetAsync(ck.d_mu, 0, sizeof(double) * (size_t)ck.cols, st) == hipSuccess;
-  ck.valid.assign((size_t)ck.cols, 0);
-  if (!ok) {
-    (void)hipGetLastError();
-    free_col_cache(ck);
-    return false;
-  }
-  ck.ldk = ldk;
-  ck.ldk4 = ldk4;
-  ck.gen = gen;
-  (void)c;
-  return true;
-}
-
-// the column cache of ncols columns from (block s, column sc) to (block t, column tc), t == s allowed (a forward move: tc < sc);
-// columns whose source has no valid entry become invalid in the target
-static int move_col_cache(rvt_ctx* c, rvt_ctx::ColKind* t, int tc, const rvt_ctx::ColKind* s, int sc, int ncols, hipStream_t st) {
-  if (!t || tc + ncols > t->cols) return RVT_OK;
-  const bool src_ok = s && s->d_i8 && sc + ncols <= s->cols;
-  if (!src_ok || (t->d_i8 && (t->ldk != s->ldk || t->gen != s->gen))) {
-    if (!t->valid.empty())
-      for (int k = 0; k < ncols; ++k) t->valid[(size_t)(tc + k)] = 0;
-    return RVT_OK;
-  }
-  if (!t->d_i8) {  // the target block has no cache yet: same shape as the source's
-    if (!s->d_i4 || !alloc_col_cache(c, *t, s->ldk, s->ldk4, s->gen, st)) {
-      if (!t->valid.empty())
-        for (int k = 0; k < ncols; ++k) t->valid[(size_t)(tc + k)] = 0;
-      return RVT_OK;
-    }
-  }
-  // (forward, in pieces no longer than the shift: a piece never overwrites what it has not read)
-  const int shift = (t == s) ? sc - tc : ncols;
-  for (int k0 = 0; k0 < ncols; k0 += std::max(shift, 1)) {
-    const int nk = std::min(std::max(shift, 1), ncols - k0);
-    HIP_TRY(c, hipMemcpyAsync(t->d_i8 + (size_t)(tc + k0) * (size_t)s->ldk, s->d_i8 + (size_t)(sc + k0) * (size_t)s->ldk,
-                              (size_t)nk * (size_t)s->ldk, hipMemcpyDeviceToDevice, st));
-    if (t->d_i4 && s->d_i4)
-      HIP_TRY(c, hipMemcpyAsync(t->d_i4 + (size_t)(tc + k0) * (size_t)s->ldk4, s->d_i4 + (size_t)(sc + k0) * (size_t)s->ldk4,
-                                (size_t)nk * (size_t)s->ldk4, hipMemcpyDeviceToDevice, st));
-    if (t->d_m4 && s->d_m4) {
-      HIP_TRY(c, hipMemcpyAsync(t->d_m4 + (size_t)(tc + k0) * (size_t)s->ldk4, s->d_m4 + (size_t)(sc + k0) * (size_t)s->ldk4,
-                                (size_t)nk * (size_t)s->ldk4, hipMemcpyDeviceToDevice, st));
-      HIP_TRY(c, hipMemcpyAsync(t->d_mu + tc + k0, s->d_mu + sc + k0, sizeof(double) * (size_t)nk, hipMemcpyDeviceToDevice, st));
-    }
-    HIP_TRY(c, hipMemcpyAsync(t->d_cs + tc + k0, s->d_cs + sc + k0, sizeof(double) * (size_t)nk, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(t->d_poly + tc + k0, s->d_poly + sc + k0, sizeof(int) * (size_t)nk, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(t->d_T + (size_t)(tc + k0) * RVT_MAX_COV, s->d_T + (size_t)(sc + k0) * RVT_MAX_COV,
-                              sizeof(double) * (size_t)nk * RVT_MAX_COV, hipMemcpyDeviceToDevice, st));
-  }
-  for (int k = 0; k < ncols; ++k) t->valid[(size_t)(tc + k)] = s->valid[(size_t)(sc + k)];
-  return RVT_OK;
-}
-
+// ---- the column operations of the adapters' device ring ---------------------------------------------------------------------
 int rvt_block_copy_columns(rvt_ctx* c, double* dst, int dst_col, const double* src, int src_col, int ncols) {
   if (!c || !dst || !src || dst_col < 0 || src_col < 0 || ncols < 0) return fail(c, RVT_E_INVALID, "bad copy");
+  if (int rc = check_columns(c, dst, dst_col, ncols)) return rc;
+  if (int rc = check_columns(c, src, src_col, ncols)) return rc;
   if (ncols == 0) return RVT_OK;
   hipSetDevice(c->device);
-  if (c->colq.n > 0) {
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
-  }
+  if (int rc = flush_col_queue(c)) return rc;
   HIP_TRY(c, sync_stream(c->io_stream));  // (queued uploads and the passes behind them write what is copied here)
-  const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
+  const size_t ld = (size_t)block_dims(c).ld;
   HIP_TRY(c, hipMemcpy(dst + (size_t)dst_col * ld, src + (size_t)src_col * ld, sizeof(double) * ld * ncols,
                        hipMemcpyDeviceToDevice));
   // what the engine knows about the columns travels with them: content flags and the column cache
-  auto itd = c->col_kind.find(dst);
-  auto its = c->col_kind.find(src);
-  if (itd != c->col_kind.end() && dst == src) {
-    // a copy inside one block (not the forward move of rvt_block_move_columns): the target columns' flags and cache entries
-    // describe what was there before — unknown from here on
-    rvt_ctx::ColKind& t = itd->second;
-    for (int k = 0; k < ncols && !t.valid.empty(); ++k)
-      if ((size_t)(dst_col + k) < t.valid.size()) t.valid[(size_t)(dst_col + k)] = 0;
-    if (t.d_flags && dst_col < t.cols) {
-      HIP_TRY(c, hipMemsetAsync(t.d_flags + dst_col, 0, sizeof(int) * (size_t)std::min(ncols, t.cols - dst_col), c->io_stream));
-      HIP_TRY(c, sync_stream(c->io_stream));
-    }
+  ColKind* t = find_block(c, dst);
+  if (!t) return RVT_OK;
+  const ColKind* s = find_block(c, src);
+  if (s && s->d_flags && dst != src) {
+    if (int rc = ensure_flags(c, *t)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(t->d_flags + dst_col, s->d_flags + src_col, sizeof(int) * (size_t)ncols, hipMemcpyDeviceToDevice,
+                              c->io_stream));
+  } else {
+    // nothing known about the source — or a copy inside one block (not the forward move of rvt_block_move_columns), where the
+    // target's flags and cache entries describe what was there before
+    if (int rc = invalidate_columns(c, t, dst_col, ncols, false)) return rc;
   }
-  if (itd != c->col_kind.end() && dst != src) {
-    rvt_ctx::ColKind& t = itd->second;
-    const rvt_ctx::ColKind* s = its != c->col_kind.end() ? &its->second : nullptr;
-    if (dst_col + ncols <= t.cols) {
-      if (s && s->d_flags && src_col + ncols <= s->cols) {
-        if (!t.d_flags) {
-          HIP_TRY(c, t.d_flags.alloc(sizeof(int) * (size_t)t.cols));
-          HIP_TRY(c, hipMemsetAsync(t.d_flags, 0x01, sizeof(int) * (size_t)t.cols, c->io_stream));
-        }
-        HIP_TRY(c, hipMemcpyAsync(t.d_flags + dst_col, s->d_flags + src_col, sizeof(int) * (size_t)ncols, hipMemcpyDeviceToDevice,
-                                  c->io_stream));
-      } else if (t.d_flags) {
-        HIP_TRY(c, hipMemsetAsync(t.d_flags + dst_col, 0, sizeof(int) * (size_t)ncols, c->io_stream));  // (unknown: not hard calls)
-      }
-      int rc = move_col_cache(c, &t, dst_col, s, src_col, ncols, c->io_stream);
-      if (rc) return rc;
-      HIP_TRY(c, sync_stream(c->io_stream));
-    }
-  }
+  if (dst != src)
+    if (int rc = move_col_cache(c, t, dst_col, s, src_col, ncols, c->io_stream)) return rc;
+  HIP_TRY(c, sync_stream(c->io_stream));
   return RVT_OK;
 }
 
-// What the engine keeps per column of a block filled by rvt_block_upload_columns, for n <= kColQueue columns that crossed PCIe
-// PACKED (their content is known from the packing: hard[k] = hard calls only, otherwise hard calls plus the one other value
-// mu[k]) and have been expanded into dG on io_stream: the content flags, and under an unweighted null model the column pass
-// of MetaCov's band on these columns (int8 copy, E2M1 codes of the hard calls and of the other value's mask, sum, flag, row of
-// T) — cache state 1 / 2.
+// What the engine keeps per column of a block, for n <= kColQueue columns whose content is KNOWN (they crossed PCIe packed, or
+// were recoded: hard[k] = hard calls only, otherwise hard calls plus the one other value mu[k]) and which have been written
+// into dG on io_stream: the content flags, and under an unweighted null model the column pass of MetaCov's band on these
+// columns (int8 copy, E2M1 codes of the hard calls and of the other value's mask, sum, flag, row of T) — cache state 1 / 2.
 static int packed_columns_pass(rvt_ctx* c, double* dG, int col0, int n, const double* mu, const int* hard) {
+  ColKind* ck = find_block(c, dG);
+  if (!ck || !c->hc_enabled) return RVT_OK;
   hipStream_t st = c->io_stream;
-  const size_t N = (size_t)(c->have_null ? c->nc.N : c->fam_nc.N);
-  const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
-  auto it = c->col_kind.find(dG);
-  if (it == c->col_kind.end() || !c->hc_enabled || col0 + n > it->second.cols) return RVT_OK;
-  rvt_ctx::ColKind& ck = it->second;
-  if (!ck.d_flags) {
-    HIP_TRY(c, ck.d_flags.alloc(sizeof(int) * (size_t)ck.cols));
-    HIP_TRY(c, hipMemsetAsync(ck.d_flags, 0x01, sizeof(int) * (size_t)ck.cols, st));
-  }
-  // the content of a packed column is KNOWN: hard calls only unless it has an other value
-  int rc = small_h2d(c, ck.d_flags + col0, hard, sizeof(int) * (size_t)n);
+  const size_t N = (size_t)block_dims(c).N, ld = (size_t)block_dims(c).ld;
+  int rc = ensure_flags(c, *ck);
+  if (!rc) rc = small_h2d(c, ck->d_flags + col0, hard, sizeof(int) * (size_t)n);
+  if (rc || !ensure_cache(c, *ck)) return rc;
+  const int d = c->nc.d, dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
+  const int64_t ldk = ck->ldk, ldk4 = ck->ldk4;
+  const size_t part_doubles = (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
+  HIP_TRY(c, c->d_cc_part.grow(sizeof(double) * part_doubles, sizeof(double) * part_doubles));
+  const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, (int64_t)N / 4096 + 1));
+  // (the columns' other values, NaN where a column has none: the pass splits g = h + mu m by them)
+  double mu_nan[rvt_ctx::kColQueue];
+  for (int k = 0; k < n; ++k) mu_nan[k] = hard[k] ? (double)NAN : mu[k];
+  HIP_TRY(c, c->d_mu_nan.grow(sizeof(double) * (size_t)rvt_ctx::kColQueue, sizeof(double) * (size_t)rvt_ctx::kColQueue));
+  double* d_mu_nan = c->d_mu_nan;
+  rc = small_h2d(c, d_mu_nan, mu_nan, sizeof(double) * (size_t)n);
+  if (!rc) rc = small_h2d(c, ck->d_mu + col0, mu, sizeof(double) * (size_t)n);
   if (rc) return rc;
-  bool cache = c->have_null && !c->nc.binary && !getenv("RVT_METACOV_NO_CACHE");
-  if (cache) {
-    const int d = c->nc.d, dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
-    const int64_t ldk = ((int64_t)N + 127) / 128 * 128, ldk4 = (((int64_t)N + 1) / 2 + 127) / 128 * 128;
-    if (ck.d_i8 && (ck.ldk != ldk || ck.gen != c->null_gen || !ck.d_i4)) free_col_cache(ck);
-    if (!ck.d_i8 && !ck.cache_failed && !alloc_col_cache(c, ck, ldk, ldk4, c->null_gen, st)) ck.cache_failed = true;
-    cache = ck.d_i8 != nullptr;
-    if (cache) {
-      const size_t part_doubles = (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
-      HIP_TRY(c, c->d_cc_part.grow(sizeof(double) * part_doubles, sizeof(double) * part_doubles));
-      const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, (int64_t)N / 4096 + 1));
-      // (the columns' other values, NaN where a column has none: the pass splits g = h + mu m by them)
-      double mu_nan[rvt_ctx::kColQueue];
-      for (int k = 0; k < n; ++k) mu_nan[k] = hard[k] ? (double)NAN : mu[k];
-      HIP_TRY(c, c->d_mu_nan.grow(sizeof(double) * (size_t)rvt_ctx::kColQueue, sizeof(double) * (size_t)rvt_ctx::kColQueue));
-      double* d_mu_nan = c->d_mu_nan;
-      rc = small_h2d(c, d_mu_nan, mu_nan, sizeof(double) * (size_t)n);
-      if (rc) return rc;
-      rc = small_h2d(c, ck.d_mu + col0, mu, sizeof(double) * (size_t)n);
-      if (rc) return rc;
-      launch_cov_prep(st, d, true, dim3((unsigned)((n + kCovHcCols - 1) / kCovHcCols), (unsigned)slices), dG + (size_t)col0 * ld,
-                      (int64_t)N, (int64_t)ld, n, c->d_X, ck.d_i8 + (size_t)col0 * (size_t)ldk, ldk, c->d_cc_part, nullptr, nullptr,
-                      nullptr, 0, 0, ck.d_i4 + (size_t)col0 * (size_t)ldk4, ldk4, d_mu_nan, ck.d_m4 + (size_t)col0 * (size_t)ldk4);
-      hipLaunchKernelGGL(cov_hc_finish_kernel, dim3((unsigned)((n * (dmax + 3) + 255) / 256)), dim3(256), 0, st, c->d_cc_part, slices,
-                         n, d, dmax, ck.d_cs + col0, ck.d_poly + col0, ck.d_T + (size_t)col0 * RVT_MAX_COV, RVT_MAX_COV);
-      HIP_TRY(c, hipGetLastError());
-      for (int k = 0; k < n; ++k) ck.valid[(size_t)(col0 + k)] = (unsigned char)(hard[k] ? 1 : 2);
-    }
+  launch_cov_prep(st, d, true, dim3((unsigned)((n + kCovHcCols - 1) / kCovHcCols), (unsigned)slices), dG + (size_t)col0 * ld,
+                  (int64_t)N, (int64_t)ld, n, c->d_X, ck->d_i8 + (size_t)col0 * (size_t)ldk, ldk, c->d_cc_part, nullptr, nullptr,
+                  nullptr, 0, 0, ck->d_i4 + (size_t)col0 * (size_t)ldk4, ldk4, d_mu_nan, ck->d_m4 + (size_t)col0 * (size_t)ldk4);
+  hipLaunchKernelGGL(cov_hc_finish_kernel, dim3((unsigned)((n * (dmax + 3) + 255) / 256)), dim3(256), 0, st, c->d_cc_part, slices,
+                     n, d, dmax, ck->d_cs + col0, ck->d_poly + col0, ck->d_T + (size_t)col0 * RVT_MAX_COV, RVT_MAX_COV);
+  HIP_TRY(c, hipGetLastError());
+  for (int k = 0; k < n; ++k) ck->valid[(size_t)(col0 + k)] = (unsigned char)(hard[k] ? 1 : 2);
+  return RVT_OK;
+}
+// ... of any number of such columns, kColQueue at a time
+static int packed_columns_passes(rvt_ctx* c, double* dG, int col0, int ncols, const double* mu, const int* hard) {
+  for (int k0 = 0; k0 < ncols; k0 += rvt_ctx::kColQueue) {
+    int rc = packed_columns_pass(c, dG, col0 + k0, std::min(rvt_ctx::kColQueue, ncols - k0), mu + k0, hard + k0);
+    if (rc) return rc;
   }
   return RVT_OK;
 }
 
-static void free_col_cache(rvt_ctx::ColKind& ck);
-static bool alloc_col_cache(rvt_ctx* c, rvt_ctx::ColKind& ck, int64_t ldk, int64_t ldk4, uint64_t gen, hipStream_t st);
+// n columns that lie in d_colpack as 2-bit rows, `pitch` bytes apart, become the doubles of columns [col0, col0 + n) of dG on
+// io_stream; their other values mu (0 for a column without one) go behind `rows_cap` rows of the same buffer first
+static int expand_packed_rows(rvt_ctx* c, size_t pitch, size_t rows_cap, const double* mu, int n, double* dG, int col0) {
+  const size_t N = (size_t)block_dims(c).N, ld = (size_t)block_dims(c).ld;
+  double* d_mu = reinterpret_cast<double*>(c->d_colpack + pitch * rows_cap);
+  int rc = small_h2d(c, d_mu, mu, sizeof(double) * (size_t)n);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)n), dim3(256), 0, c->io_stream,
+                     reinterpret_cast<const unsigned char*>(c->d_colpack.get()), (long long)pitch, d_mu, (long long)N, (long long)ld,
+                     dG + (size_t)col0 * ld);
+  HIP_TRY(c, hipGetLastError());
+  return RVT_OK;
+}
+
 // What rvt_block_upload_columns queued (rvt_ctx::ColQueue: up to 32 consecutive columns of one block, packed to 2-bit rows in
 // pinned memory, their other values and hard-call flags known on the host) goes to the device: ONE DMA of the rows, the other
 // values, the flags; the expansion to doubles; and — when the block keeps a column cache — the column pass over all of them.
+// Nothing queued: nothing happens.
 int flush_col_queue(rvt_ctx* c) {
   rvt_ctx::ColQueue& q = c->colq;
   const int n = q.n;
   if (n == 0) return RVT_OK;
   q.n = 0;
   hipSetDevice(c->device);
-  const size_t N = (size_t)(c->have_null ? c->nc.N : c->fam_nc.N);
-  const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
-  const size_t pitch = q.pitch;
-  const size_t need = pitch * (size_t)rvt_ctx::kColQueue + 2 * sizeof(double) * (size_t)rvt_ctx::kColQueue;
+  const size_t need = q.pitch * (size_t)rvt_ctx::kColQueue + 2 * sizeof(double) * (size_t)rvt_ctx::kColQueue;
   HIP_TRY(c, c->d_colpack.grow(need, need + need / 2, c->io_stream));
-  hipStream_t st = c->io_stream;
-  double* dG = q.dG;
-  const int col0 = q.col0;
-  double* d_mu = reinterpret_cast<double*>(c->d_colpack + pitch * (size_t)rvt_ctx::kColQueue);
-  HIP_TRY(c, hipMemcpyAsync(c->d_colpack, q.h[q.cur], pitch * (size_t)n, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(c->d_colpack, q.h[q.cur], q.pitch * (size_t)n, hipMemcpyHostToDevice, c->io_stream));
   if (!q.ev[q.cur]) HIP_TRY(c, hipEventCreateWithFlags(&q.ev[q.cur], hipEventDisableTiming));
-  HIP_TRY(c, hipEventRecord(q.ev[q.cur], st));
+  HIP_TRY(c, hipEventRecord(q.ev[q.cur], c->io_stream));
   q.used[q.cur] = true;
   q.cur ^= 1;
-  int rc = small_h2d(c, d_mu, q.mu, sizeof(double) * (size_t)n);
+  int rc = expand_packed_rows(c, q.pitch, rvt_ctx::kColQueue, q.mu, n, q.dG, q.col0);
+  return rc ? rc : packed_columns_pass(c, q.dG, q.col0, n, q.mu, q.hard);
+}
+// ... and wait until what was flushed is in its block (earlier_flushes_too: also what earlier calls flushed — rvt_sync)
+int flush_col_queue_wait(rvt_ctx* c, bool earlier_flushes_too) {
+  const bool queued = c->colq.n > 0;
+  if (int rc = flush_col_queue(c)) return rc;
+  if (queued || (earlier_flushes_too && (c->colq.used[0] || c->colq.used[1]))) HIP_TRY(c, sync_stream(c->io_stream));
+  return RVT_OK;
+}
+
+// rvt_block_upload_columns, ONE column (a site of MetaCovTest / MetaScoreTest::fit): packed by the staging threads into pinned
+// memory and queued; the device work runs once per 32 consecutive columns (flush_col_queue).  *queued = false: the column is
+// not representable (a dosage) and has to cross as doubles.
+static int queue_column(rvt_ctx* c, double* dG, int col0, const double* G, bool* queued) {
+  *queued = false;
+  rvt_ctx::ColQueue& q = c->colq;
+  const size_t N = (size_t)block_dims(c).N, pitch = hcp_row_pitch(N);
+  if (q.n > 0 && (q.dG != dG || col0 != q.col0 + q.n || q.n == rvt_ctx::kColQueue || q.pitch != pitch)) {
+    int rc = flush_col_queue(c);
+    if (rc) return rc;
+  }
+  if (q.pitch != pitch) {  // (another N: new pinned rows)
+    HIP_TRY(c, sync_stream(c->io_stream));
+    for (int i = 0; i < 2; ++i) {
+      q.h[i].reset();
+      q.used[i] = false;
+    }
+    q.pitch = pitch;
+  }
+  for (int i = 0; i < 2; ++i)
+    HIP_TRY(c, q.h[i].grow(pitch * (size_t)rvt_ctx::kColQueue, pitch * (size_t)rvt_ctx::kColQueue));
+  if (q.n == 0) {
+    if (q.used[q.cur]) {  // the DMA that last read these rows has finished?
+      while (hipEventQuery(q.ev[q.cur]) == hipErrorNotReady) {
+        struct timespec ts = {0, 20000};
+        nanosleep(&ts, nullptr);
+      }
+      (void)hipGetLastError();
+    }
+    q.dG = dG;
+    q.col0 = col0;
+  }
+  PackedColumn pc;
+  if (!StageRing::pack_columns_to(reinterpret_cast<char*>(q.h[q.cur].get()) + pitch * (size_t)q.n, pitch, G, N, N, 1,
+                                  CopyPool::column_instance(), &pc, /*negative_mu=*/true))
+    return RVT_OK;
+  q.mu[q.n] = pc.has_mu ? pc.mu : 0.0;
+  q.hard[q.n] = pc.has_mu ? 0 : 1;
+  ++q.n;
+  *queued = true;
+  return invalidate_columns(c, find_block(c, dG), col0, 1, true);
+}
+
+// rvt_block_upload_columns, columns that are what consolidate() almost always leaves — hard calls plus at most one other value
+// per column (the imputed mean): they cross PCIe as 2-bit codes.  The staging threads pack them (host_stage.h pack_column_f64,
+// as for the genes of rvt_submit_gene), 1/32 of the bytes go over the link, a small kernel writes the doubles of the block
+// back; their content is known from the packing, so the same column pass follows as behind the queued single columns.
+// *packed = false: some column holds more (dosages) — nothing has been written.
+static int upload_packed_columns(rvt_ctx* c, double* dG, int col0, int ncols, const double* G, bool* packed) {
+  *packed = false;
+  int rc = stage_ready(c);
   if (rc) return rc;
-  hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)n), dim3(256), 0, st,
-                     reinterpret_cast<const unsigned char*>(c->d_colpack.get()), (long long)pitch, d_mu, (long long)N, (long long)ld,
-                     dG + (size_t)col0 * ld);
-  HIP_TRY(c, hipGetLastError());
-  return packed_columns_pass(c, dG, col0, n, q.mu, q.hard);
+  const size_t N = (size_t)block_dims(c).N, pitch = hcp_row_pitch(N);
+  const size_t need = pitch * (size_t)ncols + sizeof(double) * (size_t)ncols;
+  HIP_TRY(c, c->d_colpack.grow(need, need + need / 2));
+  if (pitch > c->stage.chunk_bytes) return RVT_OK;
+  std::vector<PackedColumn> pc((size_t)ncols);
+  const int prc = c->stage.pack_f64(c->d_colpack, pitch, G, N, N, (size_t)ncols, CopyPool::pack_instance(), pc.data());
+  if (prc == 1) return fail(c, RVT_E_HIP, "packing the uploaded columns failed");
+  if (prc != 0) return RVT_OK;
+  std::vector<double> mu((size_t)ncols);
+  std::vector<int> hard((size_t)ncols);
+  for (int j = 0; j < ncols; ++j) {
+    mu[(size_t)j] = pc[(size_t)j].has_mu ? pc[(size_t)j].mu : 0.0;
+    hard[(size_t)j] = pc[(size_t)j].has_mu ? 0 : 1;
+  }
+  *packed = true;
+  rc = expand_packed_rows(c, pitch, (size_t)ncols, mu.data(), ncols, dG, col0);
+  if (!rc) rc = invalidate_columns(c, find_block(c, dG), col0, ncols, true);
+  return rc ? rc : packed_columns_passes(c, dG, col0, ncols, mu.data(), hard.data());
+}
+
+// rvt_block_upload_columns, anything else (dosages; hard calls switched off; N below 4096): the columns cross as doubles, and
+// their content (hard calls or not) is found by one read of data that has just crossed PCIe at a hundredth of the rate —
+// rvt_score_block picks its kernel by it.  Under an unweighted null model that read is the column pass of MetaCov's hard-call
+// band itself (cov_hc_prep_kernel on the one column): int8 copy, sum and the row of T = G'X stay with the block, the flag
+// falls out of its value test.
+static int upload_fp64_columns(rvt_ctx* c, double* dG, int col0, int ncols, const double* G) {
+  const size_t N = (size_t)block_dims(c).N, ld = (size_t)block_dims(c).ld;
+  HIP_TRY(c, hipMemcpy2D(dG + (size_t)col0 * ld, sizeof(double) * ld, G, sizeof(double) * N, sizeof(double) * N, ncols,
+                         hipMemcpyHostToDevice));
+  ColKind* ck = find_block(c, dG);
+  int rc = invalidate_columns(c, ck, col0, ncols, true);
+  if (rc || !ck || !c->hc_enabled) return rc;
+  if ((rc = ensure_flags(c, *ck))) return rc;
+  const bool cache = ensure_cache(c, *ck);
+  const int d = c->nc.d, dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
+  const int64_t ldk = ck->ldk, ldk4 = ck->ldk4;
+  const size_t part_bytes = sizeof(double) * (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
+  if (cache) HIP_TRY(c, c->d_cc_part.grow(part_bytes, part_bytes));
+  for (int col = col0; col < col0 + ncols; ++col) {
+    if (!cache) {
+      rc = enqueue_classify(c, dG + (size_t)col * ld, 1, (int64_t)N, (int64_t)ld, c->io_stream, ck->d_flags + col);
+      if (rc) return rc;
+      continue;
+    }
+    static const int one = 1;
+    HIP_TRY(c, hipMemcpyAsync(ck->d_flags + col, &one, sizeof(int), hipMemcpyHostToDevice, c->io_stream));
+    // (this pass knows no other value: the slot's mask of an earlier occupant must not survive it — a window that mixes
+    //  this column with mean-imputed ones reads the masks of all its columns)
+    if (ck->d_m4) HIP_TRY(c, hipMemsetAsync(ck->d_m4 + (size_t)col * (size_t)ldk4, 0, (size_t)ldk4, c->io_stream));
+    const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, (int64_t)N / 4096 + 1));
+    launch_cov_prep(c->io_stream, d, true, dim3(1, (unsigned)slices), dG + (size_t)col * ld, (int64_t)N, (int64_t)ld, 1, c->d_X,
+                    ck->d_i8 + (size_t)col * (size_t)ldk, ldk, c->d_cc_part, nullptr, nullptr, ck->d_flags + col, 0, 0,
+                    ck->d_i4 + (size_t)col * (size_t)ldk4, ldk4);
+    hipLaunchKernelGGL(cov_hc_finish_kernel, dim3(1), dim3(256), 0, c->io_stream, c->d_cc_part, slices, 1, d, dmax,
+                       ck->d_cs + col, ck->d_poly + col, ck->d_T + (size_t)col * RVT_MAX_COV);
+    HIP_TRY(c, hipGetLastError());
+    ck->valid[(size_t)col] = 1;
+  }
+  return RVT_OK;
 }
 
 int rvt_block_upload_columns(rvt_ctx* c, double* dG, int col0, int ncols, const double* G) {
   if (!c || !dG || !G || col0 < 0 || ncols < 1) return fail(c, RVT_E_INVALID, "bad upload");
   if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first");
+  if (int rc = check_columns(c, dG, col0, ncols)) return rc;
   hipSetDevice(c->device);
-  const size_t N = (size_t)(c->have_null ? c->nc.N : c->fam_nc.N);
-  const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
-  // ONE column (a site of MetaCovTest / MetaScoreTest::fit): packed by the staging threads into pinned memory and queued; the
-  // device work runs once per 32 consecutive columns (flush_col_queue)
-  if (ncols == 1 && c->hc_enabled && !getenv("RVT_UPLOAD_FP64") && !getenv("RVT_UPLOAD_NO_QUEUE") && N >= 4096) {
-    rvt_ctx::ColQueue& q = c->colq;
-    const size_t pitch = hcp_row_pitch(N);
-    if (q.n > 0 && (q.dG != dG || col0 != q.col0 + q.n || q.n == rvt_ctx::kColQueue || q.pitch != pitch)) {
-      int rc = flush_col_queue(c);
-      if (rc) return rc;
-    }
-    if (q.pitch != pitch) {  // (another N: new pinned rows)
-      HIP_TRY(c, sync_stream(c->io_stream));
-      for (int i = 0; i < 2; ++i) {
-        q.h[i].reset();
-        q.used[i] = false;
-      }
-      q.pitch = pitch;
-    }
-    for (int i = 0; i < 2; ++i)
-      HIP_TRY(c, q.h[i].grow(pitch * (size_t)rvt_ctx::kColQueue, pitch * (size_t)rvt_ctx::kColQueue));
-    if (q.n == 0) {
-      if (q.used[q.cur]) {  // the DMA that last read these rows has finished?
-        while (hipEventQuery(q.ev[q.cur]) == hipErrorNotReady) {
-          struct timespec ts = {0, 20000};
-          nanosleep(&ts, nullptr);
-        }
-        (void)hipGetLastError();
-      }
-      q.dG = dG;
-      q.col0 = col0;
-    }
-    PackedColumn pc;
-    if (StageRing::pack_columns_to(reinterpret_cast<char*>(q.h[q.cur].get()) + pitch * (size_t)q.n, pitch, G, N, N, 1,
-                                   CopyPool::column_instance(), &pc, /*negative_mu=*/true)) {
-      // whatever the engine knew about the overwritten column is void from here on
-      auto itq = c->col_kind.find(dG);
-      if (itq != c->col_kind.end() && (size_t)col0 < itq->second.valid.size()) itq->second.valid[(size_t)col0] = 0;
-      q.mu[q.n] = pc.has_mu ? pc.mu : 0.0;
-      q.hard[q.n] = pc.has_mu ? 0 : 1;
-      ++q.n;
-      return RVT_OK;
-    }
-    // not representable (dosages): this column crosses as doubles — behind whatever was queued before it
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
-  } else if (c->colq.n > 0) {
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
+  const bool pack = c->hc_enabled && !getenv("RVT_UPLOAD_FP64") && block_dims(c).N >= 4096;
+  if (pack && ncols == 1 && !getenv("RVT_UPLOAD_NO_QUEUE")) {
+    bool queued = false;
+    int rc = queue_column(c, dG, col0, G, &queued);
+    if (rc || queued) return rc;
   }
-  // The columns cross PCIe as 2-bit codes when they are what consolidate() almost always leaves — hard calls plus at most one
-  // other value per column (the imputed mean): the staging threads pack them (host_stage.h pack_column_f64, as for the genes
-  // of rvt_submit_gene), 1/32 of the bytes go over the link, a small kernel writes the doubles of the block back.  Until round 6
-  // every site's column crossed as 4 MB of doubles out of pageable memory (~120 us per site at N = 500 000: the adapter's
-  // `--meta cov` ran at 8 k sites/s whatever the window).  Dosages (a second other value) cross as doubles, as before.
-  bool packed = false;
-  std::vector<double> pmu;   // (packed: the columns' other values and whether they have none)
-  std::vector<int> phard;
-  if (c->hc_enabled && !getenv("RVT_UPLOAD_FP64") && N >= 4096) {
-    int rc = stage_ready(c);
-    if (rc) return rc;
-    const size_t pitch = hcp_row_pitch(N);
-    const size_t need = pitch * (size_t)ncols + sizeof(double) * (size_t)ncols;
-    HIP_TRY(c, c->d_colpack.grow(need, need + need / 2));
-    if (pitch <= c->stage.chunk_bytes) {
-      std::vector<PackedColumn> pc((size_t)ncols);
-      const int prc = c->stage.pack_f64(c->d_colpack, pitch, G, N, N, (size_t)ncols, CopyPool::pack_instance(), pc.data());
-      if (prc == 1) return fail(c, RVT_E_HIP, "packing the uploaded columns failed");
-      if (prc == 0) {
-        double* d_mu = reinterpret_cast<double*>(c->d_colpack + pitch * (size_t)ncols);
-        std::vector<double> mu((size_t)ncols);
-        for (int j = 0; j < ncols; ++j) mu[(size_t)j] = pc[(size_t)j].has_mu ? pc[(size_t)j].mu : 0.0;
-        rc = small_h2d(c, d_mu, mu.data(), sizeof(double) * (size_t)ncols);
-        if (rc) return rc;
-        hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)ncols), dim3(256), 0, c->io_stream,
-                           reinterpret_cast<const unsigned char*>(c->d_colpack.get()), (long long)pitch, d_mu, (long long)N, (long long)ld,
-                           dG + (size_t)col0 * ld);
-        HIP_TRY(c, hipGetLastError());
-        packed = true;
-        pmu = mu;
-        phard.resize((size_t)ncols);
-        for (int j = 0; j < ncols; ++j) phard[(size_t)j] = pc[(size_t)j].has_mu ? 0 : 1;
-      }
-    }
+  // (a column that cannot be packed goes behind whatever was queued before it)
+  if (int rc = flush_col_queue(c)) return rc;
+  if (pack) {
+    bool packed = false;
+    int rc = upload_packed_columns(c, dG, col0, ncols, G, &packed);
+    if (rc || packed) return rc;
   }
-  if (!packed)
-    HIP_TRY(c, hipMemcpy2D(dG + (size_t)col0 * ld, sizeof(double) * ld, G, sizeof(double) * N, sizeof(double) * N, ncols,
-                           hipMemcpyHostToDevice));
-  // content of the new columns (hard calls or not), recorded per column: rvt_score_block picks its kernel by it.  One
-  // read of data that has just crossed PCIe at a hundredth of the rate.  Under an unweighted null model that read is the
-  // column pass of MetaCov's hard-call band itself (cov_hc_prep_kernel on the one column): int8 copy, sum, min / max and the
-  // row of T = G'X stay with the block (ColKind), the flag falls out of its value test.
-  auto it = c->col_kind.find(dG);
-  if (it != c->col_kind.end()) {
-    // whatever the engine knew about the overwritten columns is void from here on — also when the passes below do not run
-    // (hard calls switched off, RVT_METACOV_NO_CACHE): a stale cache entry would hand the OLD column to the integer product,
-    // which no longer tests what it reads once the entry is marked valid
-    rvt_ctx::ColKind& ck = it->second;
-    for (int k = 0; k < ncols && !ck.valid.empty(); ++k)
-      if ((size_t)(col0 + k) < ck.valid.size()) ck.valid[(size_t)(col0 + k)] = 0;
-    if (ck.d_flags && !c->hc_enabled && col0 < ck.cols)  // (flags are not recomputed below: unknown = not hard calls)
-      HIP_TRY(c, hipMemsetAsync(ck.d_flags + col0, 0, sizeof(int) * (size_t)std::min(ncols, ck.cols - col0), c->io_stream));
-  }
-  if (packed) {  // content known from the packing: the same pass as behind the queued single columns, 32 columns at a time
-    for (int k0 = 0; k0 < ncols; k0 += rvt_ctx::kColQueue) {
-      const int nk = std::min(rvt_ctx::kColQueue, ncols - k0);
-      int rc = packed_columns_pass(c, dG, col0 + k0, nk, pmu.data() + k0, phard.data() + k0);
-      if (rc) return rc;
-    }
-    return RVT_OK;
-  }
-  if (it != c->col_kind.end() && c->hc_enabled && col0 + ncols <= it->second.cols) {
-    rvt_ctx::ColKind& ck = it->second;
-    if (!ck.d_flags) {
-      HIP_TRY(c, ck.d_flags.alloc(sizeof(int) * (size_t)ck.cols));
-      HIP_TRY(c, hipMemsetAsync(ck.d_flags, 0x01, sizeof(int) * (size_t)ck.cols, c->io_stream));
-    }
-    bool cache = c->have_null && !c->nc.binary && !getenv("RVT_METACOV_NO_CACHE");
-    const int d = c->nc.d, dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
-    const int64_t ldk = ((int64_t)N + 127) / 128 * 128, ldk4 = (((int64_t)N + 1) / 2 + 127) / 128 * 128;
-    if (cache) {
-      if (ck.d_i8 && (ck.ldk != ldk || ck.gen != c->null_gen || !ck.d_i4)) free_col_cache(ck);  // another model: nothing of the old cache is used
-      if (!ck.d_i8 && !ck.cache_failed && !alloc_col_cache(c, ck, ldk, ldk4, c->null_gen, c->io_stream)) ck.cache_failed = true;
-      cache = ck.d_i8 != nullptr;
-      const size_t part_bytes = sizeof(double) * (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
-      if (cache) HIP_TRY(c, c->d_cc_part.grow(part_bytes, part_bytes));
-    }
-    for (int k = 0; k < ncols; ++k) {
-      const int col = col0 + k;
-      if (!cache) {
-        int rc = enqueue_classify(c, dG + (size_t)col * ld, 1, (int64_t)N, (int64_t)ld, c->io_stream, ck.d_flags + col);
-        if (rc) return rc;
-        continue;
-      }
-      static const int one = 1;
-      HIP_TRY(c, hipMemcpyAsync(ck.d_flags + col, &one, sizeof(int), hipMemcpyHostToDevice, c->io_stream));
-      // (this pass knows no other value: the slot's mask of an earlier occupant must not survive it — a window that mixes
-      //  this column with mean-imputed ones reads the masks of all its columns)
-      if (ck.d_m4) HIP_TRY(c, hipMemsetAsync(ck.d_m4 + (size_t)col * (size_t)ldk4, 0, (size_t)ldk4, c->io_stream));
-      const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, (int64_t)N / 4096 + 1));
-      launch_cov_prep(c->io_stream, d, true, dim3(1, (unsigned)slices), dG + (size_t)col * ld, (int64_t)N, (int64_t)ld, 1, c->d_X,
-                      ck.d_i8 + (size_t)col * (size_t)ldk, ldk, c->d_cc_part, nullptr, nullptr, ck.d_flags + col, 0, 0,
-                      ck.d_i4 + (size_t)col * (size_t)ldk4, ldk4);
-      hipLaunchKernelGGL(cov_hc_finish_kernel, dim3(1), dim3(256), 0, c->io_stream, c->d_cc_part, slices, 1, d, dmax,
-                         ck.d_cs + col, ck.d_poly + col, ck.d_T + (size_t)col * RVT_MAX_COV);
-      HIP_TRY(c, hipGetLastError());
-      ck.valid[(size_t)col] = 1;
-    }
-  }
-  return RVT_OK;
+  return upload_fp64_columns(c, dG, col0, ncols, G);
 }
 
 // ---- dominant / recessive recoding on the device (recode_kernels.hip.h) ---------------------------------------------------------
-// Whatever the engine knew about columns [col0, col0 + ncols) of dG is void (as behind rvt_block_upload_columns)
-static int invalidate_columns(rvt_ctx* c, double* dG, int col0, int ncols) {
-  auto it = c->col_kind.find(dG);
-  if (it == c->col_kind.end()) return RVT_OK;
-  rvt_ctx::ColKind& ck = it->second;
-  for (int k = 0; k < ncols && !ck.valid.empty(); ++k)
-    if ((size_t)(col0 + k) < ck.valid.size()) ck.valid[(size_t)(col0 + k)] = 0;
-  if (ck.d_flags && !c->hc_enabled && col0 < ck.cols)  // (flags are not rewritten by packed_columns_pass then: unknown = not hard calls)
-    HIP_TRY(c, hipMemsetAsync(ck.d_flags + col0, 0, sizeof(int) * (size_t)std::min(ncols, ck.cols - col0), c->io_stream));
-  return RVT_OK;
-}
-
 // measurement (rvt_set_profiling): HIP events directly in front of and behind the count pass (0, 1) and the write pass (2, 3)
 static int recode_mark(rvt_ctx* c, int k, hipStream_t st) {
   if (!c->profiling) return RVT_OK;
@@ -1486,89 +1495,88 @@ int rvt_recode_last_timing(rvt_ctx* c, double* ms2) {
   return RVT_OK;
 }
 
-// avg = carriers / nonmissing (0 when nothing is called): the one division of the reference's s / numGeno, on exact integers.
-// The recoded column holds 0 / 1 and, where a call was missing, avg — "hard calls plus one other value" unless avg is 0 or 1.
-static void recode_avg(long long nonmissing, long long carriers, long long N, double* avg, double* mu, int* hard) {
-  *avg = nonmissing > 0 ? (double)carriers / (double)nonmissing : 0.0;
-  *hard = (nonmissing == N || *avg == 0.0 || *avg == 1.0) ? 1 : 0;
-  *mu = *hard ? 0.0 : *avg;
-}
-
-// the columns' bookkeeping behind a recoding, kColQueue columns at a time (what a packed upload of the same columns leaves)
-static int recoded_columns_pass(rvt_ctx* c, double* dG, int col0, int ncols, const double* mu, const int* hard) {
-  for (int k0 = 0; k0 < ncols; k0 += rvt_ctx::kColQueue) {
-    const int nk = std::min(rvt_ctx::kColQueue, ncols - k0);
-    int rc = packed_columns_pass(c, dG, col0 + k0, nk, mu + k0, hard + k0);
-    if (rc) return rc;
+// The skeleton of both recodings of ncols columns into [dst_col, dst_col + ncols) of dst, the arguments checked by the caller:
+// a count pass over the source (`per` integer counts per column; count(k0, nk, d_cnt) launches it for columns [k0, k0 + nk)),
+// the counts to the host (and to `counts`), tally(q, &nonmissing, &carriers) on a column's counts, avg = carriers / nonmissing
+// (0 when nothing is called): the one division of the reference's s / numGeno, on exact integers; then the write pass
+// (write(k0, nk, d_avg)) and the columns' bookkeeping.  The recoded column holds 0 / 1 and, where a call was missing, avg —
+// "hard calls plus one other value" unless avg is 0 or 1: what a packed upload of the same columns leaves.  Synchronous, as
+// rvt_block_copy_columns: the device calls run on other streams.
+}  // extern "C"
+template <class Count, class Tally, class Write>
+static int recode_columns(rvt_ctx* c, double* dst, int dst_col, int ncols, int per, long long* counts, Count count, Tally tally,
+                          Write write) {
+  if (ncols == 0) return RVT_OK;
+  hipSetDevice(c->device);
+  if (int rc = flush_col_queue(c)) return rc;  // (source columns may still be queued; the target's land first and are overwritten)
+  hipStream_t st = c->io_stream;               // behind the uploads and the passes that follow them
+  Layout L;
+  const size_t n_cnt = (size_t)per * (size_t)ncols;
+  const size_t o_cnt = L.take(sizeof(unsigned long long) * n_cnt), o_avg = L.take(sizeof(double) * (size_t)ncols);
+  // (no poison fill: it would run on the null stream, unordered against the clearing of the counts on this one)
+  HIP_TRY(c, c->d_recode_ws.grow(L.total, L.total + L.total / 2, st));
+  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->d_recode_ws + o_cnt);
+  double* d_avg = reinterpret_cast<double*>(c->d_recode_ws + o_avg);
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * n_cnt, st));
+  if (int rc = recode_mark(c, 0, st)) return rc;
+  constexpr int kCols = 32768;  // columns per launch (gridDim.y)
+  for (int k0 = 0; k0 < ncols; k0 += kCols) count(k0, std::min(kCols, ncols - k0), d_cnt + (size_t)per * (size_t)k0, st);
+  HIP_TRY(c, hipGetLastError());
+  if (int rc = recode_mark(c, 1, st)) return rc;
+  std::vector<unsigned long long> cnt(n_cnt);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * n_cnt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  const long long N = c->nc.N;
+  std::vector<double> avg((size_t)ncols), mu((size_t)ncols);
+  std::vector<int> hard((size_t)ncols);
+  for (int k = 0; k < ncols; ++k) {
+    long long nonmissing = 0, carriers = 0;
+    tally(cnt.data() + (size_t)per * (size_t)k, &nonmissing, &carriers);
+    avg[(size_t)k] = nonmissing > 0 ? (double)carriers / (double)nonmissing : 0.0;
+    hard[(size_t)k] = (nonmissing == N || avg[(size_t)k] == 0.0 || avg[(size_t)k] == 1.0) ? 1 : 0;
+    mu[(size_t)k] = hard[(size_t)k] ? 0.0 : avg[(size_t)k];
   }
-  return RVT_OK;
+  if (counts)
+    for (size_t i = 0; i < n_cnt; ++i) counts[i] = (long long)cnt[i];
+  int rc = small_h2d(c, d_avg, avg.data(), sizeof(double) * (size_t)ncols);
+  if (!rc) rc = invalidate_columns(c, find_block(c, dst), dst_col, ncols, true);
+  if (!rc) rc = recode_mark(c, 2, st);
+  if (rc) return rc;
+  for (int k0 = 0; k0 < ncols; k0 += kCols) write(k0, std::min(kCols, ncols - k0), d_avg + k0, st);
+  HIP_TRY(c, hipGetLastError());
+  if ((rc = recode_mark(c, 3, st))) return rc;
+  if ((rc = packed_columns_passes(c, dst, dst_col, ncols, mu.data(), hard.data()))) return rc;
+  HIP_TRY(c, sync_stream(st));
+  return recode_times(c);
 }
+extern "C" {
 
 int rvt_block_recode(rvt_ctx* c, double* dst, int dst_col, const double* src, int src_col, int ncols, int coding, long long* counts) {
   if (!c || !dst || !src || dst_col < 0 || src_col < 0 || ncols < 0) return fail(c, RVT_E_INVALID, "bad recode");
   if (coding != RVT_CODING_DOMINANT && coding != RVT_CODING_RECESSIVE)
     return fail(c, RVT_E_INVALID, "coding %d: 1 = dominant, 2 = recessive", coding);
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
-  for (int side = 0; side < 2; ++side) {  // (blocks of rvt_block_alloc know their width)
-    auto it = c->col_kind.find(side ? dst : src);
-    const int first = side ? dst_col : src_col;
-    if (it != c->col_kind.end() && (long long)first + ncols > it->second.cols)
-      return fail(c, RVT_E_INVALID, "columns [%d, %d) leave the block (%d columns)", first, first + ncols, it->second.cols);
-  }
+  if (int rc = check_columns(c, src, src_col, ncols)) return rc;
+  if (int rc = check_columns(c, dst, dst_col, ncols)) return rc;
   // one block, two ranges that overlap without being the same: a workgroup would read columns another one is writing
   if (dst == src && dst_col != src_col && std::abs(dst_col - src_col) < ncols)
     return fail(c, RVT_E_INVALID, "source and target columns overlap without being the same");
-  if (ncols == 0) return RVT_OK;
-  hipSetDevice(c->device);
-  if (c->colq.n > 0) {  // (the source columns may still be queued)
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
-  }
-  hipStream_t st = c->io_stream;  // behind the uploads and the passes that follow them
-  const int64_t N = c->nc.N, ld = c->null_ld;
+  const long long N = c->nc.N, ld = c->null_ld;
   const double threshold = coding == RVT_CODING_DOMINANT ? 0.5 : 1.5;
-  Layout L;
-  const size_t o_cnt = L.take(sizeof(unsigned long long) * 2 * (size_t)ncols), o_avg = L.take(sizeof(double) * (size_t)ncols);
-  // (no poison fill: it would run on the null stream, unordered against the clearing of the counts on this one)
-  HIP_TRY(c, c->d_recode_ws.grow(L.total, L.total + L.total / 2, st));
-  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->d_recode_ws + o_cnt);
-  double* d_avg = reinterpret_cast<double*>(c->d_recode_ws + o_avg);
-  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 2 * (size_t)ncols, st));
-  if (int rcm = recode_mark(c, 0, st)) return rcm;
-  constexpr int kCols = 32768;  // columns per launch (gridDim.y)
-  for (int k0 = 0; k0 < ncols; k0 += kCols) {
-    const int nk = std::min(kCols, ncols - k0);
-    hipLaunchKernelGGL(recode_count_kernel, dim3(recode_slices(N / 2, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
-                       src + (size_t)(src_col + k0) * (size_t)ld, (long long)N, (long long)ld, threshold, d_cnt + 2 * (size_t)k0);
-  }
-  HIP_TRY(c, hipGetLastError());
-  if (int rcm = recode_mark(c, 1, st)) return rcm;
-  std::vector<unsigned long long> cnt(2 * (size_t)ncols);
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, sync_stream(st));
-  std::vector<double> avg((size_t)ncols), mu((size_t)ncols);
-  std::vector<int> hard((size_t)ncols);
-  for (int k = 0; k < ncols; ++k) {
-    recode_avg((long long)cnt[2 * (size_t)k], (long long)cnt[2 * (size_t)k + 1], N, &avg[(size_t)k], &mu[(size_t)k], &hard[(size_t)k]);
-    if (counts) counts[2 * (size_t)k] = (long long)cnt[2 * (size_t)k], counts[2 * (size_t)k + 1] = (long long)cnt[2 * (size_t)k + 1];
-  }
-  int rc = small_h2d(c, d_avg, avg.data(), sizeof(double) * (size_t)ncols);
-  if (rc) return rc;
-  rc = invalidate_columns(c, dst, dst_col, ncols);
-  if (rc) return rc;
-  if (int rcm = recode_mark(c, 2, st)) return rcm;
-  for (int k0 = 0; k0 < ncols; k0 += kCols) {
-    const int nk = std::min(kCols, ncols - k0);
-    hipLaunchKernelGGL(recode_write_kernel, dim3(recode_slices(N / 2, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
-                       src + (size_t)(src_col + k0) * (size_t)ld, dst + (size_t)(dst_col + k0) * (size_t)ld, (long long)N, (long long)ld,
-                       threshold, d_avg + k0);
-  }
-  HIP_TRY(c, hipGetLastError());
-  if (int rcm = recode_mark(c, 3, st)) return rcm;
-  rc = recoded_columns_pass(c, dst, dst_col, ncols, mu.data(), hard.data());
-  if (rc) return rc;
-  HIP_TRY(c, sync_stream(st));  // complete on return, as rvt_block_copy_columns: the device calls run on other streams
-  return recode_times(c);
+  return recode_columns(
+      c, dst, dst_col, ncols, 2, counts,
+      [&](int k0, int nk, unsigned long long* d_cnt, hipStream_t st) {
+        hipLaunchKernelGGL(recode_count_kernel, dim3(recode_slices(N / 2, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                           src + (size_t)(src_col + k0) * (size_t)ld, N, ld, threshold, d_cnt);
+      },
+      [](const unsigned long long* q, long long* nonmissing, long long* carriers) {
+        *nonmissing = (long long)q[0], *carriers = (long long)q[1];
+      },
+      [&](int k0, int nk, const double* d_avg, hipStream_t st) {
+        hipLaunchKernelGGL(recode_write_kernel, dim3(recode_slices(N / 2, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                           src + (size_t)(src_col + k0) * (size_t)ld, dst + (size_t)(dst_col + k0) * (size_t)ld, N, ld, threshold,
+                           d_avg);
+      });
 }
 
 int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int coding, double* dG, int col0, long long* counts) {
@@ -1576,83 +1584,34 @@ int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int cod
   if (coding != RVT_CODING_DOMINANT && coding != RVT_CODING_RECESSIVE)
     return fail(c, RVT_E_INVALID, "coding %d: 1 = dominant, 2 = recessive", coding);
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
-  {
-    auto it = c->col_kind.find(dG);
-    if (it != c->col_kind.end() && (long long)col0 + V > it->second.cols)
-      return fail(c, RVT_E_INVALID, "columns [%d, %d) leave the block (%d columns)", col0, col0 + V, it->second.cols);
-  }
-  if (V == 0) return RVT_OK;
-  hipSetDevice(c->device);
-  if (c->colq.n > 0) {  // (queued columns of the target land first and are then overwritten)
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
-  }
-  hipStream_t st = c->io_stream;
-  const int64_t N = c->nc.N, ld = c->null_ld, cb = (N + 3) / 4;
-  Layout L;
-  const size_t o_cnt = L.take(sizeof(unsigned long long) * 4 * (size_t)V), o_avg = L.take(sizeof(double) * (size_t)V);
-  // (no poison fill: it would run on the null stream, unordered against the clearing of the counts on this one)
-  HIP_TRY(c, c->d_recode_ws.grow(L.total, L.total + L.total / 2, st));
-  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->d_recode_ws + o_cnt);
-  double* d_avg = reinterpret_cast<double*>(c->d_recode_ws + o_avg);
-  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * (size_t)V, st));
-  if (int rcm = recode_mark(c, 0, st)) return rcm;
-  constexpr int kCols = 32768;
-  for (int k0 = 0; k0 < V; k0 += kCols) {
-    const int nk = std::min(kCols, V - k0);
-    hipLaunchKernelGGL(recode_bed_count_kernel, dim3(recode_slices((cb + 3) / 4, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
-                       d_rows + (size_t)k0 * (size_t)cb, (long long)cb, (long long)N, d_cnt + 4 * (size_t)k0);
-  }
-  HIP_TRY(c, hipGetLastError());
-  if (int rcm = recode_mark(c, 1, st)) return rcm;
-  std::vector<unsigned long long> cnt(4 * (size_t)V);
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, sync_stream(st));
-  std::vector<double> avg((size_t)V), mu((size_t)V);
-  std::vector<int> hard((size_t)V);
-  for (int k = 0; k < V; ++k) {
-    const unsigned long long* q = cnt.data() + 4 * (size_t)k;
-    const long long carriers = (long long)(coding == RVT_CODING_DOMINANT ? q[1] + q[2] : q[2]);
-    recode_avg((long long)(q[0] + q[1] + q[2]), carriers, N, &avg[(size_t)k], &mu[(size_t)k], &hard[(size_t)k]);
-    if (counts)
-      for (int e = 0; e < 4; ++e) counts[4 * (size_t)k + e] = (long long)q[e];
-  }
-  int rc = small_h2d(c, d_avg, avg.data(), sizeof(double) * (size_t)V);
-  if (rc) return rc;
-  rc = invalidate_columns(c, dG, col0, V);
-  if (rc) return rc;
-  if (int rcm = recode_mark(c, 2, st)) return rcm;
-  for (int k0 = 0; k0 < V; k0 += kCols) {
-    const int nk = std::min(kCols, V - k0);
-    hipLaunchKernelGGL(recode_bed_expand_kernel, dim3(recode_slices(cb, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
-                       d_rows + (size_t)k0 * (size_t)cb, (long long)cb, (long long)N, (long long)ld, coding == RVT_CODING_RECESSIVE ? 1 : 0,
-                       d_avg + k0, dG + (size_t)(col0 + k0) * (size_t)ld);
-  }
-  HIP_TRY(c, hipGetLastError());
-  if (int rcm = recode_mark(c, 3, st)) return rcm;
-  rc = recoded_columns_pass(c, dG, col0, V, mu.data(), hard.data());
-  if (rc) return rc;
-  HIP_TRY(c, sync_stream(st));  // synchronous
-  return recode_times(c);
+  if (int rc = check_columns(c, dG, col0, V)) return rc;
+  const long long N = c->nc.N, ld = c->null_ld, cb = (N + 3) / 4;
+  return recode_columns(
+      c, dG, col0, V, 4, counts,
+      [&](int k0, int nk, unsigned long long* d_cnt, hipStream_t st) {
+        hipLaunchKernelGGL(recode_bed_count_kernel, dim3(recode_slices((cb + 3) / 4, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                           d_rows + (size_t)k0 * (size_t)cb, cb, N, d_cnt);
+      },
+      [&](const unsigned long long* q, long long* nonmissing, long long* carriers) {
+        *nonmissing = (long long)(q[0] + q[1] + q[2]);
+        *carriers = (long long)(coding == RVT_CODING_DOMINANT ? q[1] + q[2] : q[2]);
+      },
+      [&](int k0, int nk, const double* d_avg, hipStream_t st) {
+        hipLaunchKernelGGL(recode_bed_expand_kernel, dim3(recode_slices(cb, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
+                           d_rows + (size_t)k0 * (size_t)cb, cb, N, ld, coding == RVT_CODING_RECESSIVE ? 1 : 0, d_avg,
+                           dG + (size_t)(col0 + k0) * (size_t)ld);
+      });
 }
 
 int rvt_block_download_columns(rvt_ctx* c, const double* dG, int col0, int ncols, double* G_host) {
   if (!c || !dG || !G_host || col0 < 0 || ncols < 0) return fail(c, RVT_E_INVALID, "bad download");
   if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first");
-  {
-    auto it = c->col_kind.find(dG);
-    if (it != c->col_kind.end() && (long long)col0 + ncols > it->second.cols)
-      return fail(c, RVT_E_INVALID, "columns [%d, %d) leave the block (%d columns)", col0, col0 + ncols, it->second.cols);
-  }
+  if (int rc = check_columns(c, dG, col0, ncols)) return rc;
   if (ncols == 0) return RVT_OK;
   hipSetDevice(c->device);
-  if (c->colq.n > 0) {
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
-  }
+  if (int rc = flush_col_queue(c)) return rc;
   HIP_TRY(c, sync_stream(c->io_stream));  // (queued uploads, expansions and recodings write what is copied here)
-  const size_t N = (size_t)(c->have_null ? c->nc.N : c->fam_nc.N);
-  const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
+  const size_t N = (size_t)block_dims(c).N, ld = (size_t)block_dims(c).ld;
   HIP_TRY(c, hipMemcpy2D(G_host, sizeof(double) * N, dG + (size_t)col0 * ld, sizeof(double) * ld, sizeof(double) * N, (size_t)ncols,
                          hipMemcpyDeviceToHost));
   return RVT_OK;
@@ -1660,39 +1619,30 @@ int rvt_block_download_columns(rvt_ctx* c, const double* dG, int col0, int ncols
 
 int rvt_block_move_columns(rvt_ctx* c, double* dG, int dst_col, int src_col, int ncols) {
   if (!c || !dG || dst_col < 0 || src_col < dst_col || ncols < 0) return fail(c, RVT_E_INVALID, "bad move");
+  if (int rc = check_columns(c, dG, src_col, ncols)) return rc;  // (dst_col <= src_col: the target lies inside then)
   if (ncols == 0 || dst_col == src_col) return RVT_OK;
   hipSetDevice(c->device);
-  if (c->colq.n > 0) {
-    int rc = flush_col_queue(c);
-    if (rc) return rc;
-  }
-  const size_t ld = (size_t)(c->have_null ? c->null_ld : c->fam_nc.ld);
+  if (int rc = flush_col_queue(c)) return rc;
+  const size_t ld = (size_t)block_dims(c).ld;
   HIP_TRY(c, sync_stream(c->io_stream));  // (the passes behind the last uploads write the cache this call moves)
   // forward move of a possibly overlapping range: in pieces no longer than the shift, in increasing order — a piece never
   // overwrites data that has not been read (a ring that drops more than it keeps moves in ONE copy)
-  {
-    const int shift = src_col - dst_col;
-    for (int k0 = 0; k0 < ncols; k0 += shift) {
-      const int nk = std::min(shift, ncols - k0);
-      HIP_TRY(c, hipMemcpyAsync(dG + (size_t)(dst_col + k0) * ld, dG + (size_t)(src_col + k0) * ld, sizeof(double) * ld * (size_t)nk,
-                                hipMemcpyDeviceToDevice, c->stream));
-    }
+  const int shift = src_col - dst_col;
+  for (int k0 = 0; k0 < ncols; k0 += shift) {
+    const int nk = std::min(shift, ncols - k0);
+    HIP_TRY(c, hipMemcpyAsync(dG + (size_t)(dst_col + k0) * ld, dG + (size_t)(src_col + k0) * ld, sizeof(double) * ld * (size_t)nk,
+                              hipMemcpyDeviceToDevice, c->stream));
   }
-  {
-    auto itc = c->col_kind.find(dG);
-    if (itc != c->col_kind.end()) {
-      int rc = move_col_cache(c, &itc->second, dst_col, &itc->second, src_col, ncols, c->stream);
-      if (rc) return rc;
-    }
-  }
+  ColKind* ck = find_block(c, dG);
+  if (ck)
+    if (int rc = move_col_cache(c, ck, dst_col, ck, src_col, ncols, c->stream)) return rc;
   HIP_TRY(c, sync_stream(c->stream));
-  auto it = c->col_kind.find(dG);
-  if (it != c->col_kind.end() && it->second.d_flags && src_col + ncols <= it->second.cols) {
-    std::vector<int> f((size_t)it->second.cols);
-    HIP_TRY(c, hipMemcpyAsync(f.data(), it->second.d_flags, sizeof(int) * f.size(), hipMemcpyDeviceToHost, c->io_stream));
+  if (ck && ck->d_flags) {
+    std::vector<int> f((size_t)ck->cols);
+    HIP_TRY(c, hipMemcpyAsync(f.data(), ck->d_flags, sizeof(int) * f.size(), hipMemcpyDeviceToHost, c->io_stream));
     HIP_TRY(c, sync_stream(c->io_stream));
     std::memmove(f.data() + dst_col, f.data() + src_col, sizeof(int) * (size_t)ncols);
-    HIP_TRY(c, hipMemcpyAsync(it->second.d_flags, f.data(), sizeof(int) * f.size(), hipMemcpyHostToDevice, c->io_stream));
+    HIP_TRY(c, hipMemcpyAsync(ck->d_flags, f.data(), sizeof(int) * f.size(), hipMemcpyHostToDevice, c->io_stream));
     HIP_TRY(c, sync_stream(c->io_stream));
   }
   return RVT_OK;

@@ -311,7 +311,7 @@ int rvt_mt_score_block(rvt_ctx* c, const double* dG, int V, double* ustat, doubl
   if (!c || !dG || V < 1 || !ustat || !vstat || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
   if (!c->have_mt) return fail(c, RVT_E_STATE, "no multiple-trait null model (rvt_mt_fit_null)");
   // the layout rvt_block_alloc gave the block
-  const int64_t N = c->mt_N, ld = c->have_null ? c->null_ld : (c->have_fam ? c->fam_nc.ld : c->mt_ld);
+  const int64_t N = c->mt_N, ld = block_dims(c).ld;
   if ((c->have_null && c->nc.N != N) || (!c->have_null && c->have_fam && c->fam_nc.N != N))
     return fail(c, RVT_E_STATE, "the multiple-trait null and the context's null model differ in N");
   hipSetDevice(c->device);
