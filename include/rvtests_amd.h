@@ -841,7 +841,18 @@ int rvt_submit_gene_bed_dev(rvt_ctx* ctx, int64_t gene_id, int M, const unsigned
  * 173-263) computed from the 2-bit rows where they lie — N/4 bytes of device traffic per site instead of 8 N — with missing calls
  * imputed to the column mean as DataConsolidator does (src/DataConsolidator.cpp:217-245).  counts (optional, 4 V entries):
  * per variant the numbers of 0 / 1 / 2 / missing calls, what the adapter's AF / call-rate / HWE columns are made of
- * (src/Model.h:3211-3230).  Quantitative traits (the packed-row kernel's domain; RVT_E_STATE otherwise).  Synchronous. */
+ * (src/Model.h:3211-3230).  Either trait, from rvt_fit_null or rvt_set_null.  Under a binary null model the per-variant body is
+ * LogisticRegressionScoreTest::TestCovariate on one column (regression/LogisticRegressionScoreTest.cpp:220-302), as
+ * rvt_score_block's: with v = p (1 - p), res = y - p and C = X'VX of the installed model, per row
+ *   t_k = sum g v X_k,  u = sum g res,  s = sum g^2 v,  SS = s - t'C^-1 t;  U = u, V = SS, effect = u / SS, se = 1 / sqrt(SS),
+ *   p = chisq_Q(u^2 / SS, 1);  ok = polymorphic and SS > 0
+ * formed on the int8 matrix cores from the codes and eight digit planes per column of the tile [v X | res | v] (built at the
+ * first call under a null model); the counts and the polymorphism decision are unweighted, as for a quantitative trait.
+ * RVT_E_STATE, with a message that says which, when: the model has more than 13 covariates; the hard-call kernels are switched
+ * off (RVT_HARDCALL=0); RVT_PACKED=0; another null tile than the context's own is installed; or — binary trait — a column of
+ * [v X | res | v] is not finite or has a largest entry beyond 2^16 times its typical one, which the digit planes cannot carry
+ * (there is no fp64 product of packed rows with a weighted tile behind them: score such a model's rows as an fp64 block).
+ * Synchronous. */
 int rvt_score_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int* ok, double* ustat, double* vstat, double* effect,
                       double* effect_se, double* pvalue, long long* counts);
 /* V consecutive rows of a resident .bed matrix, recoded dominant / recessive (RVT_CODING_*, see rvt_block_recode;

@@ -48,4 +48,10 @@ void k2_launch_hcp(int MT, dim3 grid, hipStream_t st, const GeneDesc* d_desc, Nu
   }
 }
 
+// rvt_score_bed_dev under a binary trait: the weighted tile's planes, three passes, a complete record per wave-part.  Every
+// slice is described as two row tiles (a short last slice has pad rows, which read zeros)
+void k2_launch_hcp_binary_score(dim3 grid, hipStream_t st, const GeneDesc* d_desc, const HcpPlanes& pl, long long N, long long ld) {
+  hipLaunchKernelGGL((gene_tnull_hcp<2, true, true>), grid, dim3(64), 0, st, d_desc, pl, N, ld);
+}
+
 }  // namespace rvt

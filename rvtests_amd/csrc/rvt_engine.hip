@@ -1093,15 +1093,29 @@ struct BatchTrace {
 // twice the column's largest entry, in operand order.  Built from the device's null tile the first time a batch asks for it
 // (c->hcp_planes_state: 0 not built, 1 ready, -1 this model cannot: a column whose largest entry exceeds 2^16 x the median of
 // its non-zero magnitudes would leave its typical entries fewer than 39 bits — such a model keeps the fp64 product).
-static int ensure_hcp_planes(rvt_ctx* c) {
+// Under a binary null model the planes are those of the weighted tile Z = [v X_0 .. v X_{d-1} | res | v], d + 2 columns, which
+// rvt_score_bed_dev multiplies with the 2-bit rows (gene_tnull_hcp<.., true, true>): same digits, same order, same rule — and
+// no fp64 product behind it, so there state -1 is a refusal of the call.
+int ensure_hcp_planes(rvt_ctx* c) {
   if (c->hcp_planes_state != 0) return RVT_OK;
   c->hcp_planes_state = -1;
   const NullConsts& nc = c->nc;
   const int64_t N = nc.N, ld = nc.ld;
-  const int d = nc.d, ncx = d + 1;
-  if (nc.binary || !c->d_nulltile || ncx > 16) return RVT_OK;
+  const int d = nc.d, ncx = nc.binary ? d + 2 : d + 1;
+  if (!c->d_nulltile || ncx > 16) return RVT_OK;
   std::vector<double> tile((size_t)ld * ncx);
-  HIP_TRY(c, hipMemcpy(tile.data(), c->d_nulltile, sizeof(double) * tile.size(), hipMemcpyDeviceToHost));  // [X | rr], ld apart
+  if (nc.binary) {
+    if (!c->d_X || !c->d_res || !c->d_v) return RVT_OK;
+    std::vector<double> v((size_t)ld);
+    HIP_TRY(c, hipMemcpy(tile.data(), c->d_X, sizeof(double) * (size_t)ld * d, hipMemcpyDeviceToHost));  // X, ld apart
+    HIP_TRY(c, hipMemcpy(tile.data() + (size_t)ld * d, c->d_res, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(v.data(), c->d_v, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost));
+    for (int k = 0; k < d; ++k)
+      for (int64_t i = 0; i < N; ++i) tile[(size_t)k * ld + i] *= v[i];
+    std::memcpy(tile.data() + (size_t)ld * (d + 1), v.data(), sizeof(double) * (size_t)ld);
+  } else {
+    HIP_TRY(c, hipMemcpy(tile.data(), c->d_nulltile, sizeof(double) * tile.size(), hipMemcpyDeviceToHost));  // [X | rr], ld apart
+  }
   double scale[16];
   int shift[16];
   for (int k = 0; k < 16; ++k) {
@@ -1111,8 +1125,12 @@ static int ensure_hcp_planes(rvt_ctx* c) {
   for (int k = 0; k < ncx; ++k) {
     const double* col = tile.data() + (size_t)k * ld;
     double mx = 0.0;
-    for (int64_t i = 0; i < N; ++i) mx = std::max(mx, std::fabs(col[i]));
-    if (!std::isfinite(mx)) return RVT_OK;
+    bool finite = true;  // (a NaN would pass through std::max unseen)
+    for (int64_t i = 0; i < N; ++i) {
+      mx = std::max(mx, std::fabs(col[i]));
+      finite = finite && std::isfinite(col[i]);
+    }
+    if (!finite) return RVT_OK;
     if (mx > 0.0) {
       // the fixed point is 56 bits below twice the LARGEST entry: the column's typical entry — the median of its non-zero
       // magnitudes (a root mean square follows a single outlier) — must keep 39 of them

@@ -51,6 +51,7 @@ void k2_launch_lat(int MT, dim3 grid, hipStream_t st, const GeneDesc* d_desc, Nu
                    long long ld, int d);
 void k2_launch_hcp(int MT, dim3 grid, hipStream_t st, const GeneDesc* d_desc, NullTile nt, long long N, long long ld,
                    int d, const HcpPlanes* planes = nullptr, bool score_only = false);
+void k2_launch_hcp_binary_score(dim3 grid, hipStream_t st, const GeneDesc* d_desc, const HcpPlanes& pl, long long N, long long ld);
 void k2_launch_classify(dim3 grid, hipStream_t st, const double* G, long long N, long long ld, int M, int* flag);
 }  // namespace rvt
 #include "fam_kernels.hip.h"
@@ -234,9 +235,11 @@ struct rvt_ctx {
   DevBuf<double> d_Gt;  // ... rotated by U'
   DevBuf<char> d_bedbatch;   // rvt_submit_genes kind 7: row / gene references and partial counts of one call
   bool no_i8_pack = false;      // submit_common: this int8 gene holds a value above 2 — send its bytes
-  // gene_tnull_hcp: eight digit planes of [X | rr] in operand order + the columns' scales (quantitative null models)
+  // gene_tnull_hcp: eight digit planes of [X | rr] in operand order + the columns' scales (quantitative null models); under a
+  // binary null model those of [v X | res | v] (rvt_score_bed_dev) — a context holds one null model at a time
   DevBuf<unsigned char> d_hcp_xq;
   DevBuf<double> d_hcp_scale;
+  DevBuf<char> d_score_bed_w;   // rvt_score_bed_dev, binary trait: descriptors, wave-part records, statistics and results of a chunk
   int hcp_planes_state = 0;     // 0 not built for this null model, 1 ready, -1 the model's columns cannot be carried
   int submit_group = 32;   // genes per asynchronous sub-batch of the streaming interface (RVT_SUBMIT_GROUP, rvt_set_submit_group)
   int64_t fam_cols_ld = 0;  // (the leading dimension d_Gp / d_Gt were sized for)
@@ -809,6 +812,7 @@ RVT_INTERNAL int rvt_kbac_stage(rvt_ctx* c, const double* dG, int M, const doubl
 // ---- defined in rvt_engine.hip (continued)
 RVT_INTERNAL int enqueue_classify(rvt_ctx* c, const double* dG, int M, int64_t N, int64_t ld, hipStream_t st, int* d_flag);
 RVT_INTERNAL int cov_constants(rvt_ctx* c, bool fam, CovConsts* ccp, std::vector<double>* zzp);
+RVT_INTERNAL int ensure_hcp_planes(rvt_ctx* c);
 RVT_INTERNAL int run_blocks_with_perm(rvt_ctx* c, int n, const double* const* dG, const int* M, const double* af,
                                       const int64_t* ids, uint32_t tests, const rvt_params* prm, rvt_gene_result* out);
 }

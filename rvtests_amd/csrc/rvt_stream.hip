@@ -1056,6 +1056,115 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
   TraceScope ts_l(c, &c->tr_launch);
   return launch_pending(c, c->queue.size(), true);
 }
+
+// ---- rvt_score_bed_dev under a binary trait: the finisher and one chunk of slices -----------------------------------------------
+// LogisticRegressionScoreTest::TestCovariate on one column (regression/LogisticRegressionScoreTest.cpp:220-302), the units of
+// score_finish_kernel's binary branch, from the records gene_tnull_hcp<2, true, true> leaves per wave-part: 16 doubles a row,
+// t_0 .. t_{d-1}, u and the FINISHED weighted s = g'Vg — so nothing is repaired by counts here (slice_column_sums does that for
+// the unweighted diagonal: with weights it would be wrong).  The polymorphism decision is slice_column_sums': minimum and
+// maximum over the hard calls, and the imputed value when a call is missing.  One workgroup per slice, one thread per row;
+// wave-parts summed in their order.  out: ustat | vstat | effect | se | pval, vt entries each.
+__global__ __launch_bounds__(64) void score_bed_binary_finish_kernel(const GeneDesc* __restrict__ genes,
+                                                                     const NullConsts* __restrict__ ncp, long long vt,
+                                                                     double* __restrict__ out, int* __restrict__ ok) {
+  const GeneDesc gd = genes[blockIdx.x];
+  const int h = threadIdx.x;
+  if (h >= gd.M) return;
+  const long long col = gd.gene_id + h;
+  const int d = ncp->d;
+  double mn = INFINITY, mx = -INFINITY, cm = 0.0, s = 0.0, u = 0.0, t[RVT_MAX_COV];
+  unsigned long long orb = 0ull;
+  for (int k = 0; k < d; ++k) t[k] = 0.0;
+  for (int p = 0; p < gd.n_wparts; ++p) {
+    const double* cs = gd.colstat + (long long)p * kHcColstatRows * gd.Mp;
+    mn = fmin(mn, cs[gd.Mp + h]);
+    mx = fmax(mx, cs[2 * gd.Mp + h]);
+    cm += cs[3 * gd.Mp + h];
+    orb |= reinterpret_cast<const unsigned long long*>(cs)[4 * gd.Mp + h];
+    const double* row = gd.parts + ((long long)p * gd.Mp + h) * 16;
+    for (int k = 0; k < d; ++k) t[k] += row[k];
+    u += row[d];
+    s += row[d + 1];
+  }
+  if (cm > 0.0) {  // mean-imputed column: one value for every missing call
+    const double mu = rvt_bits_to_double(orb);
+    mn = fmin(mn, mu);
+    mx = fmax(mx, mu);
+  }
+  double q = 0.0;
+  for (int k = 0; k < d; ++k) {
+    double w = 0.0;
+    for (int l = 0; l < d; ++l) w += ncp->Cinv[k * d + l] * t[l];
+    q += t[k] * w;
+  }
+  const double SS = s - q;
+  const int fit = !(mn == mx) && SS > 0.0;
+  out[col] = fit ? u : 0.0;
+  out[vt + col] = fit ? SS : 0.0;
+  out[2 * vt + col] = (fit && u != 0.0) ? u / SS : 0.0;
+  out[3 * vt + col] = fit ? 1.0 / sqrt(SS) : 0.0;
+  out[4 * vt + col] = fit ? chisq_Q(u * (1.0 / SS) * u, 1.0) : 1.0;
+  ok[col] = fit;
+}
+
+// Why rvt_score_bed_dev cannot take the context's null model, or nullptr.  (Quantitative: packed_eligible's conditions for a
+// slice, one by one; a binary trait has the same ones — its planes are looked at when they are built, ensure_hcp_planes.)
+const char* score_bed_refusal(const rvt_ctx* c) {
+  if (getenv("RVT_PACKED") && atoi(getenv("RVT_PACKED")) == 0) return "the packed-row kernel is switched off (RVT_PACKED=0)";
+  if (!c->hc_enabled) return "the packed-row kernel needs the hard-call kernels, which are switched off (RVT_HARDCALL=0)";
+  if (c->nc.d > kHcMaxD) return "the packed-row kernel takes at most 13 covariates (the null-model tile is one 16-column tile)";
+  if (!null_is_default(c)) return "the packed-row kernel reads the context's own null tile, and another one is installed";
+  return nullptr;
+}
+
+// n slices (blk[g]: header + rows, filled by the count-and-copy pass on stream st) of `cols` rows in all: one launch of the
+// three-pass kernel, one of the finisher, the five statistics and ok to the caller's arrays at [0, cols).
+int score_bed_binary_chunk(rvt_ctx* c, hipStream_t st, int n, double* const* blk, const int* Ms, int slice, int cols, int* ok,
+                           double* const (&outs)[5]) {
+  const NullConsts& nc = c->nc;
+  const int d = nc.d;
+  int n_wparts = 0, steps_per = 0;
+  choose_split(nc.ld, n, false, &n_wparts, &steps_per);  // (as the quantitative slices: short wave-parts, many waves)
+  if ((long long)steps_per * 16 > kHcpPlaneMaxSamples) return fail(c, RVT_E_STATE, "a wave-part beyond the digit planes' int32 range");
+  Layout L;
+  const size_t o_desc = L.take(sizeof(GeneDesc) * (size_t)n);
+  const size_t o_parts = L.take(sizeof(double) * (size_t)n * n_wparts * slice * 16);
+  const size_t o_cst = L.take(sizeof(double) * (size_t)n * n_wparts * kHcColstatRows * slice);
+  const size_t o_out = L.take(sizeof(double) * 5 * (size_t)cols);
+  const size_t o_ok = L.take(sizeof(int) * (size_t)cols);
+  HIP_TRY(c, c->d_score_bed_w.grow(L.total, L.total + L.total / 4, st, true));
+  char* w = c->d_score_bed_w;
+  std::vector<GeneDesc> desc((size_t)n);
+  for (int g = 0; g < n; ++g) {
+    GeneDesc& gd = desc[(size_t)g];
+    std::memset(&gd, 0, sizeof(gd));
+    gd.G = blk[g];
+    gd.M = Ms[g];
+    gd.MT = slice / 16;
+    gd.CT = 1;
+    gd.Mp = slice;
+    gd.Cp = 16;
+    gd.n_wparts = n_wparts;
+    gd.steps_per_wpart = steps_per;
+    gd.gene_id = (long long)g * slice;
+    gd.pk_pitch = (int)hcp_row_pitch(nc.N);
+    gd.parts = reinterpret_cast<double*>(w + o_parts) + (size_t)g * n_wparts * slice * 16;
+    gd.colstat = reinterpret_cast<double*>(w + o_cst) + (size_t)g * n_wparts * kHcColstatRows * slice;
+  }
+  GeneDesc* d_desc = reinterpret_cast<GeneDesc*>(w + o_desc);
+  double* d_out = reinterpret_cast<double*>(w + o_out);
+  int* d_ok = reinterpret_cast<int*>(w + o_ok);
+  HIP_TRY(c, hipMemcpyAsync(d_desc, desc.data(), sizeof(GeneDesc) * (size_t)n, hipMemcpyHostToDevice, st));
+  const HcpPlanes pl{c->d_hcp_xq, c->d_hcp_scale, d + 2};
+  k2_launch_hcp_binary_score(dim3((unsigned)n_wparts, (unsigned)n), st, d_desc, pl, (long long)nc.N, (long long)nc.ld);
+  hipLaunchKernelGGL(score_bed_binary_finish_kernel, dim3((unsigned)n), dim3(64), 0, st, d_desc, c->d_nc, (long long)cols, d_out, d_ok);
+  HIP_TRY(c, hipGetLastError());
+  for (int k = 0; k < 5; ++k)
+    HIP_TRY(c, hipMemcpyAsync(outs[k], d_out + (size_t)k * cols, sizeof(double) * (size_t)cols, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(ok, d_ok, sizeof(int) * (size_t)cols, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));  // (desc goes out of scope: the copy of it has been made)
+  return RVT_OK;
+}
 }  // namespace
 
 // ---- single-variant score tests of a resident .bed matrix ------------------------------------------------------------------------
@@ -1063,19 +1172,31 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
 // MetaScoreTest::fit prints per site, src/Model.h:3246-3258) for V consecutive rows of a .bed matrix in device memory: slices
 // of 32 rows go through the packed-row machinery as "genes" of 32 variants — counts and imputation values per row, the rows
 // copied into pitched blocks (two launches per 256 slices), gene_suffstat_hcp + gene_tnull_hcp, then the score finisher that
-// rvt_score_block uses — so a site costs N/4 bytes of HBM traffic instead of 8 N.  Quantitative traits (the packed kernel's
-// domain); same outputs as rvt_score_block plus, optionally, the genotype counts (n0, n1, n2, missing per variant) the
-// adapter's AF / call rate / HWE columns are made of.  Synchronous.
+// rvt_score_block uses — so a site costs N/4 bytes of HBM traffic instead of 8 N.  Under a binary trait
+// (LogisticRegressionScoreTest::TestCovariate, regression/LogisticRegressionScoreTest.cpp:220-302) the same slices, blocks and
+// count-and-copy pass, then gene_tnull_hcp<2, true, true> on the planes of the weighted tile [v X | res | v] and a finisher of
+// its own (score_bed_binary_chunk), not run_batch.  Same outputs as rvt_score_block plus, optionally, the genotype counts (n0,
+// n1, n2, missing per variant) the adapter's AF / call rate / HWE columns are made of.  Synchronous.
 int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* ok, double* ustat, double* vstat, double* effect,
                       double* effect_se, double* pvalue, long long* counts) {
   if (!c || !d_rows || V < 1 || !ok || !ustat || !vstat || !effect || !effect_se || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   constexpr int kSlice = 32;
   static const int kChunk = getenv("RVT_SCORE_BED_CHUNK") ? std::max(16, std::min(2048, atoi(getenv("RVT_SCORE_BED_CHUNK")))) : 256;
-  if (!packed_eligible(c, kSlice, 0u, nullptr)) return fail(c, RVT_E_STATE, "the packed-row kernel does not take this null model (binary trait, too many covariates, hard calls switched off)");
+  if (const char* why = score_bed_refusal(c)) return fail(c, RVT_E_STATE, "rvt_score_bed_dev: %s", why);
+  const bool binary = c->nc.binary != 0;
   hipSetDevice(c->device);
   int rc = rvt_sync(c);
   if (rc) return rc;
+  if (binary) {
+    // the planes of [v X | res | v], built at the first call under this null model.  There is no fp64 product of packed rows
+    // with a weighted tile to fall back on, and a weaker result is not returned: a model they cannot carry is refused.
+    rc = ensure_hcp_planes(c);
+    if (rc) return rc;
+    if (c->hcp_planes_state != 1)
+      return fail(c, RVT_E_STATE, "rvt_score_bed_dev: the digit planes cannot carry this binary null model — a column of [v X | res | v] "
+                  "is not finite or its largest entry exceeds 2^16 times its typical one; score the rows as an fp64 block (rvt_score_block)");
+  }
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
   const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
@@ -1167,6 +1288,11 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
     if (e != hipSuccess) {
       release();
       return fail(c, RVT_E_HIP, "resident .bed score: %s", hipGetErrorString(e));
+    }
+    if (binary) {  // the weighted tile: its own kernel variant and finisher, launched here (run_batch is the quantitative path's)
+      double* const outs[5] = {ustat + v0, vstat + v0, effect + v0, effect_se + v0, pvalue + v0};
+      rc = score_bed_binary_chunk(c, st, n, blk.data(), Ms.data(), kSlice, cols, ok + v0, outs);
+      continue;
     }
     CovOut co;
     co.score = true;

@@ -308,7 +308,7 @@ constexpr long long kHcpPlaneMaxSamples = 131072;  // (int32 range of a pair sum
 struct HcpPlanes {
   const unsigned char* xq;
   const double* scale;  // (device, 16 entries) value of column k = integer x scale[k]
-  int ncx;              // d + 1 columns: X_0 .. X_{d-1}, rr
+  int ncx;              // d + 1 columns: X_0 .. X_{d-1}, rr; binary trait: d + 2, v X_0 .. v X_{d-1}, res, v
 };
 // two digit planes of one tile and one 64-sample operand: acc = 128 (A'B0) + A'B1 + acc, exactly, in int32 (as hcx_pair_step)
 __device__ __forceinline__ void hcp_pair_step(i4_t& acc, const i4_t& a, const i4_t& b0, const i4_t& b1) {
@@ -319,9 +319,11 @@ __device__ __forceinline__ void hcp_pair_step(i4_t& acc, const i4_t& a, const i4
   acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b1, t, 0, 0, 0);
 }
 
+// OP: the operand a pass forms from the codes — H (0 / 1 / 2, 0 where missing), m (1 where missing) or D2 (1 where H = 2)
+constexpr int kHcpOpH = 0, kHcpOpMask = 1, kHcpOpTwo = 2;
 // (STATS: also the column statistics gene_suffstat_hcp keeps — sum of H, sum of H^2, number of missing calls per column and
 //  lane — for callers that need nothing else of that kernel, see gene_tnull_hcp<MT, true>)
-template <int MT, bool MASK, bool STATS = false>
+template <int MT, int OP, bool STATS = false>
 __device__ __forceinline__ bool hcp_tnull_pass(i4_t (&acc)[kHcpPairs][MT], const __amdgpu_buffer_rsrc_t& rp, const unsigned (&cbase)[MT],
                                                const unsigned char* xq_lane, long long plane_stride, bool has_col,
                                                long long s_begin, long long s_end, int q, unsigned (*st)[3] = nullptr) {
@@ -348,7 +350,7 @@ __device__ __forceinline__ bool hcp_tnull_pass(i4_t (&acc)[kHcpPairs][MT], const
         hcp_decode((cw[c][u] >> (8 * q)) & 0xffu, pv, mv);
         if (s + u >= s_end) pv = mv = 0u;
         anym |= mv;
-        a[u] = (int)(MASK ? mv : pv);
+        a[u] = (int)(OP == kHcpOpMask ? mv : (OP == kHcpOpTwo ? (pv >> 1) & 0x01010101u : pv));
         if constexpr (STATS) {
           st[c][0] = __builtin_amdgcn_sad_u8(pv, 0u, st[c][0]);                                        // sum H
           st[c][1] = __builtin_amdgcn_sad_u8(pv + (((pv >> 1) & 0x01010101u) << 1), 0u, st[c][1]);    // sum H^2 (2 -> 4)
@@ -365,7 +367,16 @@ __device__ __forceinline__ bool hcp_tnull_pass(i4_t (&acc)[kHcpPairs][MT], const
 // SCORE = true: the single-variant score test needs of a slice only its columns' T rows, the diagonal of its Gram tile and the
 // column statistics (score_finish_kernel) — all of which this kernel has in hand: sum H^2 + 16 nm is the diagonal entry of the
 // operand's Gram tile, the statistics rows are those gene_suffstat_hcp writes.  gene_suffstat_hcp is then not launched at all.
-template <int MT, bool SCORE = false>
+//
+// BINARY = true (with SCORE; rvt_score_bed_dev under a logistic null): the planes are those of the WEIGHTED tile
+// Z = [v X_0 .. v X_{d-1} | res | v], pl.ncx = d + 2, and the wave-part's record is complete in itself — per row h
+//   t_k = H'Z_k + mu m'Z_k,   u = H'Z_res + mu m'Z_res,   s = g'Vg = H'Z_v + 2 D2'Z_v + mu^2 m'Z_v   (D2 = [H = 2]: H^2 = H + 2 D2)
+// written as 16 doubles a row, out[row 16 + k] (Cp = 16: t_0 .. t_{d-1}, u, s).  The third pass has the 0 / 1 operand D2 and
+// not H^2: an entry of 4 would halve the samples whose pair sums fit int32 (kHcpPlaneMaxSamples); it is skipped when the
+// wave-part holds no 2.  No diagonal of the unweighted operand is written: with weights a count cannot repair it
+// (slice_column_sums), so the finisher of this path (score_bed_binary_finish_kernel) takes s as it stands.  The column
+// statistics — counts, hence the polymorphism decision — are unweighted and exactly those of SCORE.
+template <int MT, bool SCORE = false, bool BINARY = false>
 __global__ __launch_bounds__(64) void gene_tnull_hcp(const GeneDesc* __restrict__ genes, HcpPlanes pl, long long N, long long ld) {
   const GeneDesc gd = genes[blockIdx.y];
   if (gd.MT != MT) return;
@@ -407,30 +418,47 @@ __global__ __launch_bounds__(64) void gene_tnull_hcp(const GeneDesc* __restrict_
   unsigned st[MT][3];
 #pragma unroll
   for (int c = 0; c < MT; ++c) st[c][0] = st[c][1] = st[c][2] = 0u;
-  const bool masked = hcp_tnull_pass<MT, false, SCORE>(acc, rp, cbase, xq_lane, plane_stride, has_col, s_begin, s_end, q, st);
+  static_assert(SCORE || !BINARY, "the weighted tile is the score test's");
+  const bool masked = hcp_tnull_pass<MT, kHcpOpH, SCORE>(acc, rp, cbase, xq_lane, plane_stride, has_col, s_begin, s_end, q, st);
   double t[MT][4];
 #pragma unroll
   for (int c = 0; c < MT; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) t[c][i] = value(c, i);
+  const bool vcol = BINARY && v == pl.ncx - 1;  // this lane's column of the tile is v = p (1 - p)
   if (masked) {  // (wave-uniform)
     clear();
-    (void)hcp_tnull_pass<MT, true>(acc, rp, cbase, xq_lane, plane_stride, has_col, s_begin, s_end, q);
+    (void)hcp_tnull_pass<MT, kHcpOpMask>(acc, rp, cbase, xq_lane, plane_stride, has_col, s_begin, s_end, q);
 #pragma unroll
     for (int c = 0; c < MT; ++c)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = c * 16 + q * 4 + i;
-        t[c][i] += (row < M ? hdr->mu[row] : 0.0) * value(c, i);
+        const double mu = row < M ? hdr->mu[row] : 0.0;
+        t[c][i] += (vcol ? mu * mu : mu) * value(c, i);
       }
   }
-  double* out = gd.parts + (long long)wpart * gd.Mp * gd.Cp;
-  const int Cp = gd.Cp;
-  if (M + v < Cp) {
+  if constexpr (BINARY) {
+    bool two = false;  // sum H^2 > sum H: the lane met a 2
+#pragma unroll
+    for (int c = 0; c < MT; ++c) two = two || st[c][1] != st[c][0];
+    if (__any(two)) {  // (wave-uniform)
+      clear();
+      (void)hcp_tnull_pass<MT, kHcpOpTwo>(acc, rp, cbase, xq_lane, plane_stride, has_col, s_begin, s_end, q);
+#pragma unroll
+      for (int c = 0; c < MT; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t[c][i] += vcol ? 2.0 * value(c, i) : 0.0;
+    }
+  }
+  // (BINARY: a record of 16 doubles a row that starts at the tile's first column; else behind the M columns of the Gram tile)
+  const int Cp = BINARY ? 16 : gd.Cp, col0 = BINARY ? 0 : M;
+  double* out = gd.parts + (long long)wpart * gd.Mp * Cp;
+  if (BINARY ? has_col : M + v < Cp) {
 #pragma unroll
     for (int c = 0; c < MT; ++c)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) out[(long long)(c * 16 + q * 4 + i) * Cp + M + v] = t[c][i];  // (i32 C/D map: row 4 q + i, column v)
+      for (int i = 0; i < 4; ++i) out[(long long)(c * 16 + q * 4 + i) * Cp + col0 + v] = t[c][i];  // (i32 C/D map: row 4 q + i, column v)
   }
   if constexpr (SCORE) {
     // (what gene_suffstat_hcp leaves for gene_flags_hc_kernel: "no entry of this wave-part is outside the codes" — the word lives in
@@ -461,7 +489,7 @@ __global__ __launch_bounds__(64) void gene_tnull_hcp(const GeneDesc* __restrict_
         unsigned long long* bits = reinterpret_cast<unsigned long long*>(cst);
         bits[4 * gd.Mp + j] = nm > 0 ? mb : 0ull;
         bits[5 * gd.Mp + j] = nm > 0 ? mb : ~0ull;
-        if (j < M) out[(long long)j * Cp + j] = (double)((long long)hh + 16 * nm);  // the diagonal of (H + 4 m)'(H + 4 m)
+        if (!BINARY && j < M) out[(long long)j * Cp + j] = (double)((long long)hh + 16 * nm);  // the diagonal of (H + 4 m)'(H + 4 m)
       }
     }
   }

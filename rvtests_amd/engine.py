@@ -633,7 +633,12 @@ class Engine:
 
     def score_bed_dev(self, d_rows, V, want_counts=True):
         """Single-variant score tests of V consecutive rows of a resident .bed matrix (rvt_score_bed_dev):
-        (ok, ustat, vstat, effect, se, pvalue[, counts (V, 4): n0 n1 n2 missing])."""
+        (ok, ustat, vstat, effect, se, pvalue[, counts (V, 4): n0 n1 n2 missing]).  Under either trait, after fit_null or
+        set_null: a quantitative null model gives the linear score test, a binary one the logistic score test (U = g'(y - p),
+        V = g'Vg - g'VX (X'VX)^-1 X'Vg, effect = U / V, se = 1 / sqrt(V)) — rvt_score_block's numbers from the 2-bit rows.
+        Raises RvtError (the message says which) with more than 13 covariates, with the hard-call kernels or the packed
+        rows switched off (RVT_HARDCALL=0, RVT_PACKED=0), and for a binary null model whose weighted columns
+        [v X | res | v] the digit planes cannot carry (an entry 2^16 times beyond the column's typical one)."""
         ok = np.zeros(V, dtype=np.int32)
         outs = [np.zeros(V) for _ in range(5)]
         cnt = np.zeros((V, 4), dtype=np.int64) if want_counts else None
