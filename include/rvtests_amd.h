@@ -639,6 +639,36 @@ typedef struct rvt_decompose_info {
 } rvt_decompose_info;
 int rvt_kinship_decompose(rvt_ctx* ctx, int64_t N, const float* K, float* U_out, float* S_out, int install,
                           rvt_decompose_info* info);
+/* The empirical kinship of `vcf2kinship --ibs` / `--bn` from V consecutive rows of a resident .bed matrix (rvt_bed_alloc /
+ * rvt_bed_upload; d_rows = d_bed + first_row * ceil(N/4), N = the installed null model's sample count): the step in front of
+ * rvt_kinship_decompose.  Synchronous.  K_out: N x N doubles in host memory (need not be registered), symmetric, every entry
+ * written.
+ * Sites are filtered as the tool's site loop does (vcfUtils/vcf2kinship.cpp:943-960), in its order, and a site is counted in
+ * the first category that drops it: nMiss > max_missing * N; af < min_maf || af > 1 - min_maf with af = ac / (2 nonmissing), 0
+ * when nothing is called; no non-zero call.  min_maf and max_missing are taken literally (the tool's turning 0 into 0.05,
+ * :672-679, is the caller's): min_maf = 0, max_missing = 1 filter nothing.
+ *   RVT_KINSHIP_IBS  K_ij = sum (2 - |g_i - g_j|) / c_ij over the used sites where both are called, c_ij their number; 0 when
+ *                    c_ij = 0.  Exact integers on the int8 matrix cores, one division per entry: bit-equal to the reference.
+ *   RVT_KINSHIP_BN   K_ij = sum z_i z_j / n, z = (g - mean) sqrt(1 / (1 - mean/2) / mean) with the mean of the site's called
+ *                    genotypes, 0 for a missing call; n = the used sites; n = 0 leaves K zero.  fp64 matrix cores;
+ *                    |K_ij - ref_ij| <= (n + 16) 2^-52 sqrt(ref_ii ref_jj).  A site whose calls are all 2 (scale = inf: the
+ *                    reference's K turns NaN) is skipped and counted as monomorphic.
+ * Not provided: BaldingNicolsKinshipForX, dosages, the choice of autosomal sites, the .kinship text.
+ * RVT_E_INVALID: null context or pointers, V < 1, unknown method, min_maf outside [0, 0.5], max_missing outside [0, 1];
+ * RVT_E_STATE: no null model; RVT_E_TOO_LARGE: V > 2^30 (the integer sums are int32); RVT_E_HIP: a failed allocation (the
+ * message names the size). */
+#define RVT_KINSHIP_IBS 0   /* IBSKinship,           vcfUtils/vcf2kinship.cpp:138-182 */
+#define RVT_KINSHIP_BN  1   /* BaldingNicolsKinship, vcfUtils/vcf2kinship.cpp:187-266 */
+typedef struct rvt_kinship_info {
+  int64_t sites;             /* V */
+  int64_t sites_used;        /* BN: the reference's n (divisor); IBS: sites that passed the filters */
+  int64_t filtered_missing;  /* nMiss > max_missing * N                     (vcf2kinship.cpp:943-946) */
+  int64_t filtered_maf;      /* af < min_maf || af > 1 - min_maf            (:949-956) */
+  int64_t monomorphic;       /* no non-zero call (:957-960; BN's "sum == 0", :214) or — BN — every call 2 */
+  double  ms_stats, ms_product, ms_finish;   /* device time of the three stages (hipEvents); the finish includes the copy to K_out */
+} rvt_kinship_info;
+int rvt_kinship_from_bed(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int method, double min_maf, double max_missing,
+                         double* K_out, rvt_kinship_info* info);
 
 /* FamAnalyticVT (--vt famanalytic: AnalyticVT(RELATED), src/Model.h:2189-2214) after rvt_set_kinship + rvt_fit_fam_null:
  * frequencies from FastLMM::FastGetAF, (u, v) from FastLMM::CalculateUandV on the flipped, polymorphic columns of every

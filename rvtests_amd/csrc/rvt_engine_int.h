@@ -115,7 +115,11 @@ struct DevBuf {
     e = Pinned ? hipHostMalloc(&q, want, flags) : hipMalloc(&q, want);
     if (e != hipSuccess) return e;
     p = static_cast<T*>(q), cap = want;
-    if (const char* v = poison ? getenv("RVT_POISON") : nullptr) e = hipMemset(q, atoi(v) & 0xff, want);
+    // With a stream given the fill is queued there — the stream the block's users run on, so they see it done.  On the null
+    // stream it may still be pending when hipMemset returns, and a non-blocking stream does not wait for it: a late fill
+    // overwrote the first results written into the block.  Without a stream the blocking fill stays as it was.
+    if (const char* v = poison ? getenv("RVT_POISON") : nullptr)
+      e = sync ? hipMemsetAsync(q, atoi(v) & 0xff, want, sync) : hipMemset(q, atoi(v) & 0xff, want);
     return e;
   }
   hipError_t alloc(size_t bytes, unsigned flags = 0) {  // a fresh block of `bytes`
@@ -752,12 +756,14 @@ void choose_split(int64_t ld, int n_genes, bool weighted, int* n_wparts, int* st
 // ---- defined in rvt_engine.hip, called from the other translation units (hidden: not part of the ABI) ------------------------
 #define RVT_INTERNAL __attribute__((visibility("hidden")))
 // ---- kernel families -----------------------------------------------------------------------------------------------------
-// Every non-template kernel of the engine is `static` in a header that all five rvt_*.hip units see through this file; until
+// Every non-template kernel of the engine is `static` in a header that all rvt_*.hip units see through this file; until
 // round 6 each unit therefore compiled and shipped its own copy of all of them (76 kernels x 5 code objects).  Now a unit
 // defines RVT_K_SPLIT and ONE of RVT_K_ENGINE / RVT_K_STREAM / RVT_K_FAM / RVT_K_PERM / RVT_K_META before including this
-// header and gets the bodies of that family alone (tools and the host harness define nothing and get everything).  The few
-// kernels that two units launch live in one of them; the other goes through these host launchers (tools/kernel_units.sh
-// lists which object carries which kernel).
+// header and gets the bodies of that family alone (tools and the host harness define nothing and get everything).  The two
+// later units name a family no shared header knows — RVT_K_MT (rvt_mtscore.hip), RVT_K_KINSHIP (rvt_kinship.hip) — so they
+// get none of those bodies, only the kernels of the header each includes for itself (mtscore_kernels.hip.h,
+// kinship_kernels.hip.h).  The few kernels that two units launch live in one of them; the other goes through these host
+// launchers (tools/kernel_units.sh lists which object carries which kernel; it reads every .o it finds).
 // the column blocks' bookkeeping (rvt_meta.hip): the queue of single columns, and a block that is new / goes away / is refilled
 extern "C" RVT_INTERNAL int flush_col_queue(rvt_ctx* c);
 extern "C" RVT_INTERNAL int flush_col_queue_wait(rvt_ctx* c, bool earlier_flushes_too);
@@ -806,6 +812,9 @@ RVT_INTERNAL int quantize_columns_mt(rvt_ctx* c, const double* d_src, int64_t n_
 RVT_INTERNAL int gemm_tn_f64(rvt_ctx* c, const double* A, int64_t lda, int M, const double* B, int64_t ldb, int Nb, const double* B2,
                              int64_t ldb2, int Nb2, const double* w, int64_t N, double* C, int64_t ldc, bool symmetric,
                              hipStream_t st, bool subtract = false, int halo = -1, int ring = 0, int col0 = 0);
+// the calls of 0 / 1 / 2 / missing of n_rows rows of a resident .bed matrix, added to d_cnt[4 r + k] (recode_bed_count_kernel)
+RVT_INTERNAL void bed_row_counts(hipStream_t st, const unsigned char* d_rows, long long cb, long long N, int n_rows,
+                                 unsigned long long* d_cnt);
 // ---- defined in rvt_perm.hip
 RVT_INTERNAL int rvt_kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std::vector<unsigned char>& y,
                                 int nPerm, double alpha, rvt_kbac_result* r);

@@ -1579,6 +1579,13 @@ int rvt_block_recode(rvt_ctx* c, double* dst, int dst_col, const double* src, in
       });
 }
 
+// counts[4 r + (0 .. 3)] += the calls of 0 / 1 / 2 / missing of row r of n_rows (at most 65 535) consecutive .bed rows; the
+// counts must be zero before.  rvt_kinship.hip's site pass counts with the same kernel through this launcher.
+void bed_row_counts(hipStream_t st, const unsigned char* d_rows, long long cb, long long N, int n_rows, unsigned long long* d_cnt) {
+  hipLaunchKernelGGL(recode_bed_count_kernel, dim3(recode_slices((cb + 3) / 4, n_rows), (unsigned)n_rows), dim3(kRecodeThreads), 0, st,
+                     d_rows, cb, N, d_cnt);
+}
+
 int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int coding, double* dG, int col0, long long* counts) {
   if (!c || !d_rows || !dG || V < 0 || col0 < 0) return fail(c, RVT_E_INVALID, "bad recode");
   if (coding != RVT_CODING_DOMINANT && coding != RVT_CODING_RECESSIVE)
@@ -1589,8 +1596,7 @@ int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int cod
   return recode_columns(
       c, dG, col0, V, 4, counts,
       [&](int k0, int nk, unsigned long long* d_cnt, hipStream_t st) {
-        hipLaunchKernelGGL(recode_bed_count_kernel, dim3(recode_slices((cb + 3) / 4, nk), (unsigned)nk), dim3(kRecodeThreads), 0, st,
-                           d_rows + (size_t)k0 * (size_t)cb, cb, N, d_cnt);
+        bed_row_counts(st, d_rows + (size_t)k0 * (size_t)cb, cb, N, nk, d_cnt);
       },
       [&](const unsigned long long* q, long long* nonmissing, long long* carriers) {
         *nonmissing = (long long)(q[0] + q[1] + q[2]);

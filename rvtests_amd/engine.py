@@ -91,7 +91,7 @@ def build_library(force=False, verbose=False):
     # one object per translation unit, compiled in parallel (the fully unrolled K2 bodies dominate the compile time), then one
     # link.  Every unit leaves a dependency file (-MMD): a unit whose sources are older than its object is not compiled again.
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-function"]
-    units = ["rvt_engine.hip", "rvt_stream.hip", "rvt_fam.hip", "rvt_perm.hip", "rvt_meta.hip", "rvt_mtscore.hip", "k2_unweighted.hip", "k2_weighted.hip", "k2_hardcall.hip", "k2_hardcall_w.hip",
+    units = ["rvt_engine.hip", "rvt_stream.hip", "rvt_fam.hip", "rvt_perm.hip", "rvt_meta.hip", "rvt_mtscore.hip", "rvt_kinship.hip", "k2_unweighted.hip", "k2_weighted.hip", "k2_hardcall.hip", "k2_hardcall_w.hip",
              "k2_hardcall_x.hip", "k2_lattice.hip", "k2_packed.hip", "k2_floatdigit.hip"]
 
     def fresh(obj, dep):
@@ -308,6 +308,8 @@ def load_library():
     L.rvt_kinship_decompose.restype = C.c_int
     L.rvt_kinship_decompose.argtypes = [vp, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.c_int, C.POINTER(DecomposeInfo)]
+    L.rvt_kinship_from_bed.restype = C.c_int
+    L.rvt_kinship_from_bed.argtypes = KINSHIP_FROM_BED_ARGTYPES
     L.rvt_vcf_set_dosage.restype = C.c_int
     L.rvt_vcf_set_dosage.argtypes = [vp, C.c_int]
     L.rvt_vcf_format_index.restype = C.c_int
@@ -399,6 +401,17 @@ class BurdenMoreResult(C.Structure):
 class DecomposeInfo(C.Structure):
     _fields_ = [("sweeps", C.c_int), ("max_cosine", C.c_double), ("padded_order", C.c_int64), ("shift", C.c_double),
                 ("max_residual", C.c_double)]
+
+
+class KinshipInfo(C.Structure):
+    """rvt_kinship_info: what rvt_kinship_from_bed did with the V sites, and the device time of its three stages."""
+    _fields_ = [("sites", C.c_int64), ("sites_used", C.c_int64), ("filtered_missing", C.c_int64), ("filtered_maf", C.c_int64),
+                ("monomorphic", C.c_int64), ("ms_stats", C.c_double), ("ms_product", C.c_double), ("ms_finish", C.c_double)]
+
+
+KINSHIP_IBS, KINSHIP_BN = 0, 1   # RVT_KINSHIP_* (rvt_kinship_from_bed)
+# (ctx, d_rows, V, method, min_maf, max_missing, K_out, info)
+KINSHIP_FROM_BED_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, c_double_p, C.POINTER(KinshipInfo)]
 
 
 def vcf_locate(L, line):
@@ -777,6 +790,24 @@ class Engine:
         if install:
             self.N = N
         return U, S, info
+
+    def kinship_from_bed(self, d_rows, V, method="bn", min_maf=0.0, max_missing=1.0, install=False):
+        """The empirical kinship of V consecutive rows of a resident .bed matrix (rvt_kinship_from_bed): what
+        `vcf2kinship --bn` (method "bn") or `--ibs` ("ibs") computes from the same hard calls.  min_maf and max_missing are
+        applied literally (0 and 1 filter nothing; the tool's own defaults are the caller's).  Returns (K float64 (N, N),
+        KinshipInfo); with install=True K is cast to float — KinshipHolder::load's cast — and handed to
+        kinship_decompose(install=True), whose (U, S, DecomposeInfo) comes back as a third item."""
+        methods = {"ibs": KINSHIP_IBS, "bn": KINSHIP_BN}
+        if method not in methods:
+            raise ValueError("method %r: 'ibs' or 'bn'" % (method,))
+        n = self.N or 1   # (without a null model the library refuses before it touches K)
+        K = np.zeros((n, n))
+        info = KinshipInfo()
+        self._check(self.L.rvt_kinship_from_bed(self.ctx, C.c_void_p(int(d_rows)), int(V), methods[method], float(min_maf),
+                                                float(max_missing), _dp(K), C.byref(info)))
+        if install:
+            return K, info, self.kinship_decompose(K.astype(np.float32), install=True)
+        return K, info
 
     def vcf_set_samples(self, row_of_sample):
         rows = np.ascontiguousarray(row_of_sample, dtype=np.int32)
