@@ -12,6 +12,7 @@
 #include <chrono>
 #include "host_stage.h"
 #include "band_tiles.h"
+#include "block_pool.h"
 #include "perm_counter.h"
 #include "rvt_pvalue.h"
 #include "rvt_mvn.h"
@@ -445,6 +446,43 @@ int hc_pack_column_i8(const signed char* g, size_t n, unsigned char* out, size_t
   for (int k = 0; k < (reps < 1 ? 1 : reps); ++k) ok = rvt::pack_column_i8(g, n, out, pitch, isa);
   return ok ? 1 : 0;
 }
+// ---- block_pool.h: the free lists of the streaming interface's blocks.  Blocks are named by small integers (the "pointer") -------
+void* hc_pool_new() { return new rvt::BlockPool(); }
+void hc_pool_delete(void* p) { delete static_cast<rvt::BlockPool*>(p); }
+void hc_pool_give(void* p, size_t bytes, long long id) { static_cast<rvt::BlockPool*>(p)->give(bytes, reinterpret_cast<double*>(id)); }
+// the chosen block's name (0: none fits) and capacity
+long long hc_pool_take(void* p, size_t need, int bounded, size_t* bytes) {
+  const rvt::BlockPool::Entry e = static_cast<rvt::BlockPool*>(p)->take(need, bounded != 0);
+  *bytes = e.bytes;
+  return reinterpret_cast<long long>(e.ptr);
+}
+// the free blocks in the pool's order; returns their number
+int hc_pool_entries(void* p, size_t* bytes, long long* ids, int cap) {
+  const auto& fb = static_cast<rvt::BlockPool*>(p)->free_blocks;
+  for (int i = 0; i < (int)fb.size() && i < cap; ++i) bytes[i] = fb[i].bytes, ids[i] = reinterpret_cast<long long>(fb[i].ptr);
+  return (int)fb.size();
+}
+// returns the number of blocks freed, their names in the order they were freed in freed[]
+int hc_pool_trim(void* p, size_t max_bytes, size_t max_count, long long* freed, int cap) {
+  int n = 0;
+  static_cast<rvt::BlockPool*>(p)->trim(max_bytes, max_count, [&](double* q) {
+    if (n < cap) freed[n] = reinterpret_cast<long long>(q);
+    ++n;
+  });
+  return n;
+}
+// one lease from the pool (a block that has to be allocated is named fresh_id), dropped at the end of the call, or released to
+// the caller with keep != 0: the block's name, its capacity and whether it was fresh
+long long hc_pool_lease(void* p, size_t need, int bounded, long long fresh_id, int keep, size_t* bytes, int* fresh) {
+  rvt::BlockLease l(*static_cast<rvt::BlockPool*>(p), need, bounded != 0, [&](size_t) { return reinterpret_cast<double*>(fresh_id); });
+  *bytes = l.bytes();
+  *fresh = l.fresh() ? 1 : 0;
+  const long long id = reinterpret_cast<long long>(l.get());
+  size_t b = 0;
+  if (keep) (void)l.release(&b);
+  return id;
+}
+
 int hc_cpu_has(int isa) {
 #if defined(__x86_64__)
   if (isa == 1) return __builtin_cpu_supports("avx2") ? 1 : 0;

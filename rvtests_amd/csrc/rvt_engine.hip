@@ -282,8 +282,8 @@ void rvt_destroy(rvt_ctx* c) {
   // the context owns (its members' destructors)
   for (auto& p : c->queue)
     if (p.dG) hipFree(p.dG);
-  for (auto& bp : c->block_pool) hipFree(bp.second);
-  for (auto& bp : c->pk_pool) hipFree(bp.second);
+  c->block_pool.clear(hipFree);
+  c->pk_pool.clear(hipFree);
   delete c;
 }
 
@@ -307,10 +307,8 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
   if (!c->queue.empty()) return fail(c, RVT_E_STATE, "collect the submitted genes before changing the null model");
   // (queued columns were packed for the model that goes away: they reach their block under it, or the old model stays)
   if (int rc = flush_col_queue_wait(c, false)) return rc;
-  for (auto& bp : c->block_pool) hipFree(bp.second);  // pooled blocks were laid out for the previous N
-  c->block_pool.clear();
-  for (auto& bp : c->pk_pool) hipFree(bp.second);
-  c->pk_pool.clear();
+  c->block_pool.clear(hipFree);  // pooled blocks were laid out for the previous N
+  c->pk_pool.clear(hipFree);
   free_null(c);
   c->have_null_beta = false;
   const int64_t ld = rvt_padded_ld(N);
@@ -1917,7 +1915,7 @@ int run_batch(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const d
   if (n == 0) return RVT_OK;
   hipSetDevice(c->device);
   b.n = n, b.dG = dG, b.Ms = Ms, b.af = af, b.ids = ids, b.tests = tests, b.dbg = dbg, b.cov = cov, b.kind = kind;
-  b.params = prm ? *prm : rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05};
+  b.params = prm ? *prm : kDefaultParams;
   int rc = acquire_slot(c, b);
   if (rc) return rc;
   plan_batch(c, b);

@@ -24,6 +24,7 @@
 #include "suffstat_hcx.hip.h"
 #include "suffstat_fdx.hip.h"
 #include "host_stage.h"
+#include "block_pool.h"
 
 namespace rvt {  // defined in k2_unweighted.hip / k2_weighted.hip
 void k2_launch_group_w0(int group, dim3 grid, hipStream_t st, const GeneDesc* d_desc, const int* list, int n_wparts,
@@ -183,6 +184,38 @@ inline KindBits decode_kind(const signed char* kind, int g) {
   return {kind[g] & 0xf, (kind[g] & kKindPlanesFlag) != 0};
 }
 
+// What a streaming entry point is handed (submit_common's `in`).  The values of kRaw, kI8, kBed and kBedDev are public: they are
+// the `kind` of rvt_submit_genes.
+enum class GeneInput : int {
+  kF64 = 0,        // imputed doubles and the caller's allele frequencies (rvt_submit_gene)
+  kRaw = 1,        // doubles with missing codes, consolidated on the device
+  kI8 = 2,         // one byte per hard call
+  kBed = 3,        // PLINK 2-bit rows in host memory
+  kVcfGt = 4,      // VCF record text, genotypes
+  kVcfDosage = 5,  // VCF record text, a dosage tag
+  kBgen = 6,       // BGEN probability blocks
+  kBedDev = 7,     // PLINK 2-bit rows of a matrix resident on the device
+};
+struct GeneInputTraits {
+  BlockKind expanded;  // what the gene's fp64 block holds when the input is expanded
+  int decoded;         // Pending::decoded: 1 VCF text, 2 BGEN blocks (the submission has an input-error word), else 0
+  bool packs;          // may stay a block of 2-bit rows when the gene's tests allow it (packed_eligible)
+};
+inline GeneInputTraits gene_input_traits(GeneInput in) {
+  switch (in) {
+    case GeneInput::kF64: return {kKindUnknown, 0, true};
+    case GeneInput::kRaw: return {kKindUnknown, 0, false};
+    case GeneInput::kI8: return {kKindHardCall, 0, true};
+    case GeneInput::kBed: return {kKindHardCall, 0, true};
+    case GeneInput::kVcfGt: return {kKindHardCall, 1, false};
+    case GeneInput::kVcfDosage: return {kKindDecimal, 1, false};
+    case GeneInput::kBgen: return {kKindDosage, 2, false};
+    case GeneInput::kBedDev: return {kKindHardCall, 0, true};
+  }
+  return {kKindUnknown, 0, false};
+}
+constexpr rvt_params kDefaultParams{1.0, 25.0, 1.0, 25.0, 0, 0.05};
+
 struct rvt_ctx {
   int device = 0;
   Slot slots[kSlots];
@@ -238,7 +271,6 @@ struct rvt_ctx {
   DevBuf<double> d_Gp;  // flipped / filtered genotypes of a FamSKAT batch (ld x T)
   DevBuf<double> d_Gt;  // ... rotated by U'
   DevBuf<char> d_bedbatch;   // rvt_submit_genes kind 7: row / gene references and partial counts of one call
-  bool no_i8_pack = false;      // submit_common: this int8 gene holds a value above 2 — send its bytes
   // gene_tnull_hcp: eight digit planes of [X | rr] in operand order + the columns' scales (quantitative null models); under a
   // binary null model those of [v X | res | v] (rvt_score_bed_dev) — a context holds one null model at a time
   DevBuf<unsigned char> d_hcp_xq;
@@ -511,11 +543,16 @@ struct rvt_ctx {
     int decoded = 0;      // 1: VCF text, 2: BGEN blocks (the submission has an input-error word in its ring slot)
     bool planes = false;  // kind 3 only: G'[X | rr] on the int8 matrix cores from the null tile's digit planes (resident .bed genes)
     int kind = kKindUnknown;  // what the engine's decoder wrote (a BlockKind)
+    // the fields every route sets; the block, the frequencies and the kind follow
+    Pending(int64_t id_, int M_, uint32_t tests_, const rvt_params* prm_)
+        : id(id_), M(M_), dG(nullptr), bytes(0), tests(tests_), prm(prm_ ? *prm_ : kDefaultParams), launched(false) {
+      std::memset(&res, 0, sizeof(res));
+    }
   };
   std::deque<Pending> queue;
-  std::vector<std::pair<size_t, double*>> block_pool;  // free device blocks of the streaming interface (bytes, ptr)
-  std::vector<std::pair<size_t, double*>> pk_pool;     // free PACKED blocks (2-bit rows): never handed out as fp64 blocks,
-                                                       // whose pad rows must be zero
+  // free device blocks of the streaming interface (block_pool.h; taken through a BlockLease): fp64 blocks, and PACKED blocks
+  // (2-bit rows), which are never handed out as fp64 blocks, whose pad rows must be zero
+  BlockPool block_pool, pk_pool;
   // results of launched sub-batches land in contiguous arrays, then move into Pending::res at collect time
   struct Launched {
     size_t first;  // index into the queue at launch time (adjusted when the queue is popped)

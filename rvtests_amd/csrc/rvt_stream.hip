@@ -200,8 +200,6 @@ static int text_upload(rvt_ctx* c, const std::vector<StageRing::Piece>& pieces, 
   return rc;
 }
 
-// mode 0: imputed doubles + caller's af; 1: raw doubles (consolidated on the device); 2: packed int8 (ditto);
-// 3: PLINK 2-bit codes (ditto)
 // VCF text of one gene -> N x M signed bytes in c->d_consol_i8 (vcf_kernels.hip.h), on stream st
 struct VcfGene {
   const char* const* text;  // per record: first byte of the first sample column
@@ -462,375 +460,403 @@ static bool packed_eligible(const rvt_ctx* c, int M, uint32_t tests, const rvt_p
   return true;
 }
 
-// rvt_submit_gene's block of doubles packed on the way (host_stage.h, round 5): when the gene may take the packed kernel
-// (packed_eligible) and the content hint does not say dosages, the staging threads turn every column into 2-bit codes
-// + its one other value while they read it, 6 MB cross the link instead of 200, and the gene continues exactly as a
-// rvt_submit_gene_bed gene whose imputed values are GIVEN (the doubles the caller's consolidate() wrote) instead of
-// computed.  Returns 1 = submitted (rc_out holds the result), 0 = not applicable / not representable: the caller goes on with
-// the plain copy.  RVT_PACK_FP64=0 switches it off.
-int try_submit_packed_f64(rvt_ctx* c, int64_t gene_id, int M, const double* G, const double* af, uint32_t tests,
-                          const rvt_params* prm, int* rc_out) {
-  const char* sw = getenv("RVT_PACK_FP64");  // (read per call: tests switch it inside one process)
-  const bool on = !(sw && atoi(sw) == 0);
-  if (!on || !c->stage_on || c->content_hint == 0 || !packed_eligible(c, M, tests, prm)) return 0;
-  // (a page-locked caller buffer is packed like any other: the threads read 200 MB of host memory at 200+ GB/s and 6 MB cross
-  //  the link, where the DMA of the doubles themselves is bound by the link — 290 against 1 400 gene-sets/s; until round 6 a
-  //  registered fp64 block always took the DMA.  It still does when the block cannot be packed: dosages, RVT_PACK_FP64=0.)
-  const int64_t N = c->nc.N;
-  if (N < 4096) return 0;  // small blocks: nothing to gain
-  const size_t pk_pitch = hcp_row_pitch(N);
-  if (stage_ready(c) != RVT_OK || pk_pitch > c->stage.chunk_bytes) return 0;
-  const size_t need = (size_t)kHcpHeaderBytes + pk_pitch * M + 16;
-  rvt_ctx::Pending p;
-  p.id = gene_id;
-  p.M = M;
-  p.dG = nullptr;
-  p.launched = false;
-  std::memset(&p.res, 0, sizeof(p.res));
-  bool fresh = false;
-  int best = -1;
-  auto& pool = c->pk_pool;
-  for (int i = 0; i < (int)pool.size(); ++i)
-    if (pool[i].first >= need && pool[i].first <= 4 * need && (best < 0 || pool[i].first < pool[best].first)) best = i;
-  if (best >= 0) {
-    p.dG = pool[best].second;
-    p.bytes = pool[best].first;
-    pool.erase(pool.begin() + best);
-  } else {
-    if (hipMalloc((void**)&p.dG, need) != hipSuccess) {
+// ---- one gene through the streaming interface ------------------------------------------------------------------------------
+// submit_common: validate, choose the route, lease a block, set up where the frequencies come back, fill the block, finish.
+// ("Packed hand-off", has the routes, the lease and the pad-zero invariant of packed blocks.)
+extern "C++" {  // (a template and functions that return a lease)
+struct Submit {  // the arguments of one submission
+  rvt_ctx* c;
+  int64_t id;
+  int M;
+  const void* G;
+  GeneInput in;
+  const double* af;  // kF64: the caller's frequencies
+  double* af_out;    // the others: where the caller waits for the device's (may be NULL)
+  uint32_t tests;
+  const rvt_params* prm;
+};
+// expanded to an fp64 block, or kept as 2-bit rows: as they come, made of int8 / of fp64 by the staging threads on the way, or
+// copied from a matrix resident on the device
+enum class Route { kExpand, kPackRows, kPackI8, kPackF64, kPackResident };
+// what a packing route answers when the gene cannot cross as 2-bit rows after all (no RVT_E_* code is positive)
+constexpr int kRetryExpanded = 0x7e7e;
+
+static bool env_on(const char* name) {  // (read per call: tests switch these inside one process)
+  const char* v = getenv(name);
+  return !(v && atoi(v) == 0);
+}
+Route choose_route(const Submit& s, bool may_pack) {
+  rvt_ctx* c = s.c;
+  if (!may_pack || !gene_input_traits(s.in).packs) return Route::kExpand;
+  switch (s.in) {
+    case GeneInput::kF64:
+      // hard calls + one other value per column (what consolidate() leaves), unless the content hint says dosages: 6 MB cross
+      // the link instead of 200, from page-locked memory too (the threads read at 200+ GB/s, the DMA of the doubles is bound by
+      // the link).  Small blocks: nothing to gain.  RVT_PACK_FP64=0 switches it off.
+      if (!env_on("RVT_PACK_FP64") || !c->stage_on || c->content_hint == 0 || !packed_eligible(c, s.M, s.tests, s.prm)) break;
+      if (c->nc.N < 4096 || stage_ready(c) != RVT_OK || hcp_row_pitch(c->nc.N) > c->stage.chunk_bytes) break;
+      return Route::kPackF64;
+    case GeneInput::kI8:  // RVT_PACK_I8=0 sends the bytes
+      if (!c->stage_on || c->nc.N < 4096 || !env_on("RVT_PACK_I8") || !packed_eligible(c, s.M, s.tests, s.prm)) break;
+      return Route::kPackI8;
+    case GeneInput::kBed:
+      if (packed_eligible(c, s.M, s.tests, s.prm)) return Route::kPackRows;
+      break;
+    case GeneInput::kBedDev:
+      if (packed_eligible(c, s.M, s.tests, s.prm)) return Route::kPackResident;
+      break;
+    default:
+      break;
+  }
+  return Route::kExpand;
+}
+
+// ---- the gene's block: on lease from the context's pools until the gene is queued
+size_t packed_block_bytes(int64_t N, int M) { return (size_t)kHcpHeaderBytes + hcp_row_pitch(N) * M + 16; }
+// header + M padded rows.  A block that had to be allocated is fresh(): the caller clears it on the stream that fills it.  Empty
+// when the allocation fails.
+BlockLease lease_packed(rvt_ctx* c, int M) {
+  return BlockLease(c->pk_pool, packed_block_bytes(c->nc.N, M), true, [](size_t bytes) {
+    double* p = nullptr;
+    if (hipMalloc((void**)&p, bytes) != hipSuccess) {
       (void)hipGetLastError();
-      return 0;
+      p = nullptr;
     }
-    p.bytes = need;
-    fresh = true;
+    return p;
+  });
+}
+// M columns of doubles; a new one comes cleared and complete from rvt_block_alloc (*rc and the message are its own)
+BlockLease lease_expanded(rvt_ctx* c, int M, int* rc) {
+  return BlockLease(c->block_pool, sizeof(double) * (size_t)c->null_ld * M, false, [&](size_t) {
+    double* p = nullptr;
+    *rc = rvt_block_alloc(c, M, &p);
+    return *rc ? nullptr : p;
+  });
+}
+
+// ---- DataConsolidator::consolidate's genotype part on the device: counter AF + mean imputation ---------------------------------
+int consol_nparts(int64_t N) { return (int)((N + kConsolChunk - 1) / kConsolChunk); }
+hipError_t consol_parts_ready(rvt_ctx* c, int M) {
+  const int nparts = consol_nparts(c->nc.N);
+  return c->d_consol_parts.grow(sizeof(ConsolPart) * M * nparts, sizeof(ConsolPart) * std::max(M, 128) * nparts);
+}
+struct ConsolOut {
+  double* d_af;       // the allele frequencies; NULL: the imputation values are GIVEN (c->d_consol_af's second half), no fill pass
+  double* expand;     // the fp64 block the imputed columns are written into, or (NULL)
+  HcpHeader* header;  // ... the header of the packed block whose rows were counted
+};
+// M columns of T at `src`, `pitch` apart (in the units of consolidate_count_kernel<T>), on stream st: the count pass (counted:
+// the caller has run it — bed_count_copy_kernel), the fill pass, then consolidate_write_kernel or hcp_header_kernel
+template <class T>
+void launch_consolidation(rvt_ctx* c, hipStream_t st, const T* src, long long pitch, int M, const ConsolOut& out,
+                          bool counted = false) {
+  const long long N = c->nc.N;
+  const int nparts = consol_nparts(N);
+  double* d_fill = c->d_consol_af + RVT_MAX_VARIANTS;
+  const dim3 cgrid((unsigned)nparts, (unsigned)M);
+  if (!counted)
+    hipLaunchKernelGGL((consolidate_count_kernel<T>), cgrid, dim3(256), 0, st, src, pitch, N, c->d_consol_parts);
+  if (out.d_af)
+    hipLaunchKernelGGL((consolidate_fill_kernel<T>), dim3((unsigned)M), dim3(64), 0, st, src, pitch, N, nparts,
+                       c->d_consol_parts, out.d_af, d_fill);
+  if (out.expand)
+    hipLaunchKernelGGL((consolidate_write_kernel<T>), cgrid, dim3(256), 0, st, src, pitch, N, (long long)c->null_ld, d_fill,
+                       out.expand);
+  else
+    hipLaunchKernelGGL(hcp_header_kernel, dim3(1), dim3(128), 0, st, c->d_consol_parts, nparts, M, N, d_fill, out.header);
+}
+int consol_failed(rvt_ctx* c, hipError_t e) {
+  return fail(c, RVT_E_HIP, "genotype consolidation failed: %s", hipGetErrorString(e));
+}
+
+// Where a gene's allele frequencies (and, for VCF text / BGEN blocks, its input-error word) come back: through a slot of the
+// device-mapped pinned ring when nobody waits for them — consolidate_fill_kernel writes through the mapping, resolve_af reads
+// the slot at launch time — through the device buffer and the synchronous word when the caller does.
+struct AfReturn {
+  int ring_slot = -1;
+  double* d_af = nullptr;
+  int err_slot = rvt_ctx::kAfSlots;
+};
+hipError_t af_return(rvt_ctx* c, bool caller_waits, bool decodes, AfReturn* r) {
+  r->d_af = c->d_consol_af;
+  if (!caller_waits) {
+    hipError_t e = c->h_af_ring.grow(kAfRingBytes, kAfRingBytes, nullptr, false, hipHostMallocMapped);
+    if (e == hipSuccess && c->af_unresolved >= rvt_ctx::kAfSlots && resolve_af(c)) e = hipErrorUnknown;
+    if (e != hipSuccess) return e;
+    r->ring_slot = r->err_slot = (int)(c->af_seq++ % rvt_ctx::kAfSlots);
+    double* mapped = nullptr;
+    e = hipHostGetDevicePointer((void**)&mapped, c->h_af_ring, 0);
+    if (e != hipSuccess) return e;
+    r->d_af = mapped + (size_t)r->ring_slot * RVT_MAX_VARIANTS;
   }
-  auto give_back = [&]() { c->pk_pool.emplace_back(p.bytes, p.dG); };
+  if (decodes) {
+    if (io_err_ready(c) != RVT_OK) return hipErrorUnknown;
+    c->h_io_err[r->err_slot] = 0;  // (the slot's previous user has been resolved; nothing on the device refers to it)
+  }
+  return hipSuccess;
+}
+
+// ---- the routes: each fills the leased block on the io stream (host copies on the copy stream, waited for by event) ------------
+int next_pack_slot(rvt_ctx* c) {  // of the ring of landing buffers and their events
+  const int k = c->pack_next;
+  c->pack_next = (k + 1) % rvt_ctx::kPack;
+  return k;
+}
+// the kernels queued on the io stream from here on wait for what the copy stream holds now
+hipError_t io_waits_for_copies(rvt_ctx* c, int k) {
+  hipError_t e = hipEventRecord(c->ev_pack_copied[k], c->copy_stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(c->io_stream, c->ev_pack_copied[k], 0);
+  return e;
+}
+unsigned char* packed_rows(const BlockLease& blk) { return reinterpret_cast<unsigned char*>(blk.get()) + kHcpHeaderBytes; }
+HcpHeader* packed_header(const BlockLease& blk) { return reinterpret_cast<HcpHeader*>(blk.get()); }
+
+// 2-bit rows from host memory, as they are (kPackRows) or made of int8 hard calls by the staging threads while they read them
+// (kPackI8): straight into the gene's own block (copy stream, pitch padded to 16 bytes); the count pass and the header follow on
+// the io stream.  Nothing is expanded.
+int fill_packed_host(const Submit& s, Route route, const BlockLease& blk, const AfReturn& ar) {
+  rvt_ctx* c = s.c;
+  const size_t N = (size_t)c->nc.N, cb = (N + 3) / 4, pk_pitch = hcp_row_pitch(c->nc.N);
+  unsigned char* rows = packed_rows(blk);
+  const int ek = next_pack_slot(c);
+  if (blk.fresh()) {
+    const hipError_t e = hipMemsetAsync(blk.get(), 0, blk.bytes(), c->copy_stream);
+    if (e != hipSuccess) return consol_failed(c, e);
+  }
+  int prc = route == Route::kPackI8 ? (stage_ready(c) == RVT_OK ? 0 : 1) : 0;
+  if (prc == 0) {
+    c->h2d_stream = c->copy_stream;
+    if (route == Route::kPackI8)
+      prc = c->stage.pack_i8(rows, pk_pitch, (const signed char*)s.G, N, N, (size_t)s.M, CopyPool::pack_instance());
+    else  // (pad_zero: the pad bytes of a packed row are zero anyway)
+      prc = staged_h2d_2d(c, rows, pk_pitch, s.G, cb, cb, (size_t)s.M, true) != RVT_OK;
+    c->h2d_stream = c->io_stream;
+  }
+  if (route == Route::kPackI8 && prc == 2) {
+    // a value above 2 (not a hard call), or rows longer than a staging chunk: this gene crosses as bytes
+    (void)hipStreamSynchronize(c->copy_stream);  // (rows already on their way land before the block is handed out again)
+    return kRetryExpanded;
+  }
+  const hipError_t e = prc ? hipErrorUnknown : io_waits_for_copies(c, ek);
+  if (e != hipSuccess) return consol_failed(c, e);
+  launch_consolidation(c, c->io_stream, reinterpret_cast<const bed2_t*>(rows), (long long)pk_pitch, s.M,
+                       ConsolOut{ar.d_af, nullptr, packed_header(blk)});
+  return RVT_OK;
+}
+
+// rows of a .bed matrix RESIDENT on the device: the count pass copies them into the gene's block as it reads them — 6 MB of HBM
+// traffic instead of the link, three launches per gene on one stream
+int fill_packed_resident(const Submit& s, const BlockLease& blk, const AfReturn& ar) {
+  rvt_ctx* c = s.c;
   hipStream_t st = c->io_stream;
-  hipError_t e = hipSuccess;
-  e = c->d_consol_af.grow(sizeof(double) * 2 * M, sizeof(double) * 2 * RVT_MAX_VARIANTS);
-  const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
-  if (e == hipSuccess)
-    e = c->d_consol_parts.grow(sizeof(ConsolPart) * M * nparts, sizeof(ConsolPart) * std::max(M, 128) * nparts);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    give_back();
-    return 0;
+  const long long N = c->nc.N, cb = (N + 3) / 4, pk_pitch = (long long)hcp_row_pitch(c->nc.N);
+  if (blk.fresh()) {
+    const hipError_t e = hipMemsetAsync(blk.get(), 0, blk.bytes(), st);
+    if (e != hipSuccess) return consol_failed(c, e);
   }
-  unsigned char* rows = reinterpret_cast<unsigned char*>(p.dG) + kHcpHeaderBytes;
-  const int ek = c->pack_next;
-  c->pack_next = (ek + 1) % rvt_ctx::kPack;
-  if (fresh) e = hipMemsetAsync(p.dG, 0, need, c->copy_stream);
+  hipLaunchKernelGGL(bed_count_copy_kernel, dim3((unsigned)consol_nparts(N), (unsigned)s.M), dim3(256), 0, st,
+                     (const unsigned char*)s.G, cb, N, c->d_consol_parts, packed_rows(blk), pk_pitch);
+  launch_consolidation(c, st, reinterpret_cast<const bed2_t*>(packed_rows(blk)), pk_pitch, s.M,
+                       ConsolOut{ar.d_af, nullptr, packed_header(blk)}, true);
+  return RVT_OK;
+}
+
+// rvt_submit_gene's block of doubles packed on the way (host_stage.h): the staging threads turn every column into 2-bit codes
+// + its one other value while they read it, and the gene continues as a rvt_submit_gene_bed gene whose imputed values are GIVEN
+// (the doubles the caller's consolidate() wrote) instead of computed.  kRetryExpanded: not representable (dosages, a column with
+// two other values) or no room for the work space — the block crosses as doubles.
+int fill_packed_f64(const Submit& s, const BlockLease& blk) {
+  rvt_ctx* c = s.c;
+  const size_t N = (size_t)c->nc.N, pk_pitch = hcp_row_pitch(c->nc.N);
+  const int M = s.M;
+  if (c->d_consol_af.grow(sizeof(double) * 2 * M, sizeof(double) * 2 * RVT_MAX_VARIANTS) != hipSuccess ||
+      consol_parts_ready(c, M) != hipSuccess) {
+    (void)hipGetLastError();
+    return kRetryExpanded;
+  }
+  unsigned char* rows = packed_rows(blk);
+  const int ek = next_pack_slot(c);
+  hipError_t e = blk.fresh() ? hipMemsetAsync(blk.get(), 0, blk.bytes(), c->copy_stream) : hipSuccess;
   std::vector<PackedColumn> cols((size_t)M);
   int prc = 1;
   if (e == hipSuccess) {
     TraceScope ts(c, &c->tr_copy);
     c->h2d_stream = c->copy_stream;
-    prc = c->stage.pack_f64(rows, pk_pitch, G, (size_t)N, (size_t)N, (size_t)M, CopyPool::pack_instance(), cols.data());
+    prc = c->stage.pack_f64(rows, pk_pitch, (const double*)s.G, N, N, (size_t)M, CopyPool::pack_instance(), cols.data());
     c->h2d_stream = c->io_stream;
   }
-  if (prc == 2) {  // dosages, or a column with two other values: the block crosses as doubles
-    give_back();
-    return 0;
-  }
-  if (prc != 0 || e != hipSuccess) {
-    give_back();
-    *rc_out = fail(c, RVT_E_HIP, "packing the fp64 block failed");
-    return 1;
-  }
+  if (prc == 2) return kRetryExpanded;
+  if (prc != 0 || e != hipSuccess) return fail(c, RVT_E_HIP, "packing the fp64 block failed");
   // the other value of every column (0 where it has none) where the header kernel reads the imputed values
   double mu[RVT_MAX_VARIANTS > 96 ? 96 : RVT_MAX_VARIANTS];
   for (int j = 0; j < M; ++j) mu[j] = cols[j].has_mu ? cols[j].mu : 0.0;
-  double* d_fill = c->d_consol_af + RVT_MAX_VARIANTS;
-  e = hipEventRecord(c->ev_pack_copied[ek], c->copy_stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(st, c->ev_pack_copied[ek], 0);
-  if (e == hipSuccess && small_h2d(c, d_fill, mu, sizeof(double) * (size_t)M) != RVT_OK) e = hipErrorUnknown;
+  e = io_waits_for_copies(c, ek);
+  if (e == hipSuccess && small_h2d(c, c->d_consol_af + RVT_MAX_VARIANTS, mu, sizeof(double) * (size_t)M) != RVT_OK)
+    e = hipErrorUnknown;
   if (e == hipSuccess) {
-    const bed2_t* sb = reinterpret_cast<const bed2_t*>(rows);
-    const dim3 cgrid((unsigned)nparts, (unsigned)M);
-    hipLaunchKernelGGL((consolidate_count_kernel<bed2_t>), cgrid, dim3(256), 0, st, sb, (long long)pk_pitch, (long long)N,
-                       c->d_consol_parts);
-    hipLaunchKernelGGL(hcp_header_kernel, dim3(1), dim3(128), 0, st, c->d_consol_parts, nparts, M, (long long)N, d_fill,
-                       reinterpret_cast<HcpHeader*>(p.dG));
+    launch_consolidation(c, c->io_stream, reinterpret_cast<const bed2_t*>(rows), (long long)pk_pitch, M,
+                         ConsolOut{nullptr, nullptr, packed_header(blk)});
     e = hipGetLastError();
   }
-  if (e != hipSuccess) {
-    give_back();
-    *rc_out = fail(c, RVT_E_HIP, "packed fp64 gene: %s", hipGetErrorString(e));
-    return 1;
+  if (e != hipSuccess) return fail(c, RVT_E_HIP, "packed fp64 gene: %s", hipGetErrorString(e));
+  return RVT_OK;
+}
+
+// doubles with missing codes — the caller's, or decoded from VCF dosage text / BGEN blocks into the block — imputed in place
+int fill_expanded_doubles(const Submit& s, const BlockLease& blk, const AfReturn& ar) {
+  rvt_ctx* c = s.c;
+  hipStream_t st = c->io_stream;
+  const int64_t N = c->nc.N, ld = c->null_ld;
+  double* dG = blk.get();
+  const int rc = s.in == GeneInput::kRaw          ? upload_block_data(c, dG, s.M, (const double*)s.G)
+                 : s.in == GeneInput::kVcfDosage ? vcf_decode_gene(c, (const VcfGene*)s.G, s.M, N, st, ar.err_slot, dG, ld)
+                                                 : bgen_decode_gene(c, (const BgenGene*)s.G, s.M, N, st, ar.err_slot, dG, ld);
+  if (rc) return rc;
+  launch_consolidation(c, st, (const double*)dG, (long long)ld, s.M, ConsolOut{ar.d_af, dG, nullptr});
+  return RVT_OK;
+}
+
+// hard calls expanded on the device: one byte per genotype (int8; VCF genotype text is decoded into that form first) or PLINK's
+// 2-bit codes, ceil(N/4) bytes per variant (host rows, resident rows)
+int fill_expanded_hardcalls(const Submit& s, const BlockLease& blk, const AfReturn& ar) {
+  rvt_ctx* c = s.c;
+  hipStream_t st = c->io_stream;
+  const int64_t N = c->nc.N;
+  const bool two_bit = s.in == GeneInput::kBed || s.in == GeneInput::kBedDev;
+  const size_t col_bytes = two_bit ? (size_t)((N + 3) / 4) : (size_t)N, bytes8 = col_bytes * s.M;
+  const void* d_packed = nullptr;  // where the packed genotypes of this gene are on the device
+  int pk = -1;
+  hipError_t e;
+  if (s.in == GeneInput::kVcfGt) {
+    e = c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4);
+    if (e == hipSuccess && vcf_decode_gene(c, (const VcfGene*)s.G, s.M, N, st, ar.err_slot) != RVT_OK) e = hipErrorUnknown;
+    d_packed = c->d_consol_i8;
+  } else {
+    // host copy on the copy stream into the next landing buffer of the ring (free once the consolidation kernels of the gene
+    // that used it last have run); the kernels of THIS gene wait for the copy by event
+    pk = next_pack_slot(c);
+    e = c->d_pack[pk].grow(bytes8, bytes8 + bytes8 / 4);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_pack_free[pk], 0);
+    if (e == hipSuccess && s.in == GeneInput::kBedDev) {  // (device-resident rows: into the same landing buffer, whatever their alignment)
+      e = hipMemcpyAsync(c->d_pack[pk], s.G, bytes8, hipMemcpyDeviceToDevice, c->copy_stream);
+    } else if (e == hipSuccess) {
+      c->h2d_stream = c->copy_stream;
+      const int rcs = staged_h2d(c, c->d_pack[pk], s.G, bytes8);
+      c->h2d_stream = c->io_stream;
+      if (rcs != RVT_OK) e = hipErrorUnknown;
+    }
+    if (e == hipSuccess) e = io_waits_for_copies(c, pk);
+    d_packed = c->d_pack[pk];
   }
-  p.kind = kKindPacked;
-  p.decoded = 0;
-  p.af.assign(af, af + M);
-  p.tests = tests;
-  p.prm = prm ? *prm : rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05};
+  if (e != hipSuccess) return consol_failed(c, e);
+  const ConsolOut out{ar.d_af, blk.get(), nullptr};
+  if (two_bit)
+    launch_consolidation(c, st, (const bed2_t*)d_packed, (long long)col_bytes, s.M, out);
+  else
+    launch_consolidation(c, st, (const signed char*)d_packed, (long long)N, s.M, out);
+  if (pk >= 0) e = hipEventRecord(c->ev_pack_free[pk], st);  // the landing buffer may be refilled
+  return e == hipSuccess ? RVT_OK : consol_failed(c, e);
+}
+
+// ---- finish: the gene joins the queue with its block; complete groups start computing now and overlap the host-side copies of
+// the following genes
+int enqueue(rvt_ctx* c, rvt_ctx::Pending&& p, BlockLease& blk) {
+  p.dG = blk.release(&p.bytes);
   c->queue.push_back(std::move(p));
   if (c->trace_submit) ++c->tr_genes;
   TraceScope ts_l(c, &c->tr_launch);
-  *rc_out = launch_pending(c, c->queue.size(), true);
-  return 1;
+  return launch_pending(c, c->queue.size(), true);
+}
+// a consolidated gene: its frequencies to the caller who waits for them (a malformed text / block then refuses this very gene),
+// else the ring slot is parked in the queue entry
+int finish_consolidated(const Submit& s, rvt_ctx::Pending&& p, BlockLease& blk, const AfReturn& ar) {
+  rvt_ctx* c = s.c;
+  const size_t afb = sizeof(double) * (size_t)s.M;
+  p.af.resize(s.M);
+  if (s.af_out) {
+    hipError_t e = hipMemcpyAsync(p.af.data(), c->d_consol_af, afb, hipMemcpyDeviceToHost, c->io_stream);
+    if (e == hipSuccess) e = sync_stream(c->io_stream);
+    if (e != hipSuccess) return consol_failed(c, e);
+    if (p.decoded && c->h_io_err[ar.err_slot]) {
+      io_err_message(c, c->h_io_err[ar.err_slot], s.in == GeneInput::kBgen, "");
+      c->h_io_err[ar.err_slot] = 0;
+      return RVT_E_INVALID;
+    }
+    std::memcpy(s.af_out, p.af.data(), afb);
+  } else {
+    // nobody waits for the frequencies: the host copy of the block is already consumed (a copy from pageable memory returns
+    // once the source has been read), so return now and pick the frequencies up at launch time
+    p.af_slot = ar.ring_slot;
+    ++c->af_unresolved;
+  }
+  return enqueue(c, std::move(p), blk);
 }
 
-int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, int mode, const double* af, double* af_out,
+// one pass over the steps; kRetryExpanded when the packing route it chose cannot carry this gene
+int submit_routed(const Submit& s, bool may_pack) {
+  rvt_ctx* c = s.c;
+  const Route route = choose_route(s, may_pack);
+  const bool packed = route != Route::kExpand;
+  const GeneInputTraits traits = gene_input_traits(s.in);
+  int rc = RVT_OK;
+  BlockLease blk = packed ? lease_packed(c, s.M) : lease_expanded(c, s.M, &rc);
+  if (!blk) {
+    if (!packed) return rc;
+    if (route == Route::kPackF64) return kRetryExpanded;
+    return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed gene", packed_block_bytes(c->nc.N, s.M));
+  }
+  rvt_ctx::Pending p(s.id, s.M, s.tests, s.prm);
+  // what this entry point writes into the block: 2-bit rows, or hard calls with imputed means / dosages / the caller's doubles
+  p.kind = packed ? kKindPacked : traits.expanded;
+  p.planes = route == Route::kPackResident;  // (nothing waits for a link: the sufficient-statistics kernel is the bound)
+  p.decoded = traits.decoded;
+  if (s.in == GeneInput::kF64) {  // the caller's frequencies: nothing comes back
+    // (not packed: a synchronous copy — the caller may overwrite G on return)
+    rc = packed ? fill_packed_f64(s, blk) : upload_block_data(c, blk.get(), s.M, (const double*)s.G);
+    if (rc) return rc;
+    p.af.assign(s.af, s.af + s.M);
+    return enqueue(c, std::move(p), blk);
+  }
+  // the consolidation runs on a stream of its own: the set-up stream is also slot 0's batch stream, and waiting on it would
+  // wait for a whole batch
+  if (c->d_consol_af.grow(sizeof(double) * 2 * s.M, sizeof(double) * 2 * RVT_MAX_VARIANTS) != hipSuccess)
+    return fail(c, RVT_E_HIP, "hipMalloc failed");
+  AfReturn ar;
+  hipError_t e = consol_parts_ready(c, s.M);
+  if (e == hipSuccess) e = af_return(c, s.af_out != nullptr, traits.decoded != 0, &ar);
+  if (e != hipSuccess) return consol_failed(c, e);
+  switch (route) {
+    case Route::kPackRows:
+    case Route::kPackI8:
+      rc = fill_packed_host(s, route, blk, ar);
+      break;
+    case Route::kPackResident:
+      rc = fill_packed_resident(s, blk, ar);
+      break;
+    default:
+      rc = (s.in == GeneInput::kRaw || s.in == GeneInput::kVcfDosage || s.in == GeneInput::kBgen)
+               ? fill_expanded_doubles(s, blk, ar)
+               : fill_expanded_hardcalls(s, blk, ar);
+  }
+  if (rc) return rc;
+  return finish_consolidated(s, std::move(p), blk, ar);
+}
+
+int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, GeneInput in, const double* af, double* af_out,
                   uint32_t tests, const rvt_params* prm) {
   RegWait reg_wait_on_return(c);
-  if (!c || !G || M < 1 || (mode == 0 && !af)) return fail(c, RVT_E_INVALID, "bad gene");
+  if (!c || !G || M < 1 || (in == GeneInput::kF64 && !af)) return fail(c, RVT_E_INVALID, "bad gene");
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   if (tests & RVT_TEST_FAMSKAT) return fail(c, RVT_E_INVALID, "FamSKAT runs through rvt_run_fam_blocks");
   if (M > RVT_MAX_VARIANTS) return fail(c, RVT_E_TOO_LARGE, "gene of %d variants exceeds RVT_MAX_VARIANTS", M);
   hipSetDevice(c->device);
   TraceScope ts_all(c, &c->tr_block);  // (the whole call; "block" in the trace line = total per gene)
-  if (mode == 0) {  // the fp64 boundary: packed on the way when the block allows it
-    int rcp = RVT_OK;
-    if (try_submit_packed_f64(c, gene_id, M, (const double*)G, af, tests, prm, &rcp)) return rcp;
-  }
-  if (c->trace_submit) ++c->tr_genes;
-  rvt_ctx::Pending p;
-  p.id = gene_id;
-  p.M = M;
-  p.dG = nullptr;
-  p.launched = false;
-  std::memset(&p.res, 0, sizeof(p.res));
-  // device block from the pool (smallest that fits) or a fresh zeroed allocation; pad rows stay zero because only
-  // the N data rows of a column are ever written
-  // PLINK 2-bit rows stay packed when the gene's tests allow it (gene_suffstat_hcp): a block of header + M padded rows
-  // (7: the rows are on the device already; 2: int8 hard calls, turned into 2-bit rows by the staging threads on the way —
-  //  RVT_PACK_I8=0 sends the bytes)
-  const bool i8_packs = mode == 2 && !c->no_i8_pack && c->stage_on && c->nc.N >= 4096 &&
-                        !(getenv("RVT_PACK_I8") && atoi(getenv("RVT_PACK_I8")) == 0);
-  const bool packed = (mode == 3 || mode == 7 || i8_packs) && packed_eligible(c, M, tests, prm);
-  const size_t pk_pitch = hcp_row_pitch(c->nc.N);
-  const size_t need = packed ? (size_t)kHcpHeaderBytes + pk_pitch * M + 16 : sizeof(double) * (size_t)c->null_ld * M;
-  bool fresh_packed = false;
-  int best = -1;
-  auto& pool = packed ? c->pk_pool : c->block_pool;
-  for (int i = 0; i < (int)pool.size(); ++i)
-    if (pool[i].first >= need && (!packed || pool[i].first <= 4 * need) && (best < 0 || pool[i].first < pool[best].first))
-      best = i;
-  if (best >= 0) {
-    p.dG = pool[best].second;
-    p.bytes = pool[best].first;
-    pool.erase(pool.begin() + best);
-  } else if (packed) {
-    if (hipMalloc((void**)&p.dG, need) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed gene", need);
-    }
-    p.bytes = need;
-    fresh_packed = true;
-  } else {
-    int rc = rvt_block_alloc(c, M, &p.dG);
-    if (rc) return rc;
-    p.bytes = need;
-  }
-  auto give_back = [&]() { (packed ? c->pk_pool : c->block_pool).emplace_back(p.bytes, p.dG); };
-  const int64_t N = c->nc.N, ld = c->null_ld;
-  // what this entry point writes into the block: hard calls with imputed means (packed / text genotypes), dosages
-  // (dosage text, BGEN), or whatever the caller's doubles are
-  p.kind = packed ? kKindPacked
-                  : ((mode == 2 || mode == 3 || mode == 4 || mode == 7)
-                         ? kKindHardCall
-                         : (mode == 5 ? kKindDecimal : (mode == 6 ? kKindDosage : kKindUnknown)));
-  p.planes = packed && mode == 7;
-  p.decoded = (mode == 4 || mode == 5) ? 1 : (mode == 6 ? 2 : 0);
-  if (mode == 0) {
-    int rc = upload_block_data(c, p.dG, M, (const double*)G);  // synchronous copy: the caller may overwrite G on return
-    if (rc) {
-      give_back();
-      return rc;
-    }
-    p.af.assign(af, af + M);
-  } else {
-    // DataConsolidator::consolidate's genotype part on the device: counter AF + mean imputation.  On a stream of its
-    // own: the set-up stream is also slot 0's batch stream, and waiting on it would wait for a whole batch.
-    hipStream_t st = c->io_stream;
-    const size_t afb = sizeof(double) * (size_t)M;
-    if (c->d_consol_af.grow(sizeof(double) * 2 * M, sizeof(double) * 2 * RVT_MAX_VARIANTS) != hipSuccess) {
-      give_back();
-      return fail(c, RVT_E_HIP, "hipMalloc failed");
-    }
-    const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
-    hipError_t e = c->d_consol_parts.grow(sizeof(ConsolPart) * M * nparts, sizeof(ConsolPart) * std::max(M, 128) * nparts);
-    double* d_fill = c->d_consol_af + RVT_MAX_VARIANTS;
-    const dim3 cgrid((unsigned)nparts, (unsigned)M);
-    // where this gene's allele frequencies (and, for VCF text / BGEN blocks, its input-error word) come back: through a
-    // ring slot when nobody waits for them, through the synchronous word otherwise
-    int ring_slot = -1;
-    if (!af_out && e == hipSuccess) {
-      e = c->h_af_ring.grow(kAfRingBytes, kAfRingBytes, nullptr, false, hipHostMallocMapped);
-      if (e == hipSuccess && c->af_unresolved >= rvt_ctx::kAfSlots && resolve_af(c)) e = hipErrorUnknown;
-      if (e == hipSuccess) ring_slot = (int)(c->af_seq++ % rvt_ctx::kAfSlots);
-    }
-    // the frequencies go straight into the (device-mapped) ring slot, or into the device buffer the caller waits for
-    double* d_af_dst = c->d_consol_af;
-    if (ring_slot >= 0 && e == hipSuccess) {
-      double* mapped = nullptr;
-      e = hipHostGetDevicePointer((void**)&mapped, c->h_af_ring, 0);
-      if (e == hipSuccess) d_af_dst = mapped + (size_t)ring_slot * RVT_MAX_VARIANTS;
-    }
-    const int err_slot = ring_slot >= 0 ? ring_slot : rvt_ctx::kAfSlots;
-    const bool decodes = mode == 4 || mode == 5 || mode == 6;
-    if (decodes && e == hipSuccess) {
-      if (io_err_ready(c) != RVT_OK)
-        e = hipErrorUnknown;
-      else
-        c->h_io_err[err_slot] = 0;  // (the slot's previous user has been resolved; nothing on the device refers to it)
-    }
-    if (e != hipSuccess) {
-      // fall through to the error return below
-    } else if (packed) {
-      // the rows go straight into the gene's own block (copy stream, 2-D: pitch padded to 16 bytes); the count pass and the
-      // header follow on the io stream.  Nothing is expanded.
-      unsigned char* rows = reinterpret_cast<unsigned char*>(p.dG) + kHcpHeaderBytes;
-      const size_t cb = (size_t)((N + 3) / 4);
-      const int ek = c->pack_next;
-      c->pack_next = (ek + 1) % rvt_ctx::kPack;
-      // The pad bytes of a row read as zeros.  Invariant: a block is cleared once, when it is allocated, and the pool hands a
-      // block out again only for the same (N, M) — the same pk_pitch — so a later gene's rows land on the same offsets; the
-      // staged copy (pad_zero) writes zeros into the pads BETWEEN rows of a chunk and nothing into the pad behind a chunk's last
-      // row, which therefore still holds the allocation's zeros.
-      if (mode == 7) {
-        // rows of a .bed matrix RESIDENT on the device (rvt_submit_gene_bed_dev): the count pass copies them into the gene's
-        // block as it reads them — 6 MB of HBM traffic instead of the link, three launches per gene on one stream
-        if (fresh_packed) e = hipMemsetAsync(p.dG, 0, need, st);
-        if (e == hipSuccess) {
-          hipLaunchKernelGGL(bed_count_copy_kernel, cgrid, dim3(256), 0, st, (const unsigned char*)G, (long long)cb, (long long)N,
-                             c->d_consol_parts, rows, (long long)pk_pitch);
-          const bed2_t* sb = reinterpret_cast<const bed2_t*>(rows);
-          hipLaunchKernelGGL((consolidate_fill_kernel<bed2_t>), dim3((unsigned)M), dim3(64), 0, st, sb, (long long)pk_pitch,
-                             (long long)N, nparts, c->d_consol_parts, d_af_dst, d_fill);
-          hipLaunchKernelGGL(hcp_header_kernel, dim3(1), dim3(128), 0, st, c->d_consol_parts, nparts, M, (long long)N, d_fill,
-                             reinterpret_cast<HcpHeader*>(p.dG));
-        }
-      } else {
-      if (fresh_packed) e = hipMemsetAsync(p.dG, 0, need, c->copy_stream);
-      if (e == hipSuccess && mode == 2) {
-        // int8 hard calls: the staging threads write the gene's .bed rows into the pinned ring while they read its bytes
-        int prc = stage_ready(c) == RVT_OK ? 0 : 1;
-        if (prc == 0) {
-          c->h2d_stream = c->copy_stream;
-          prc = c->stage.pack_i8(rows, pk_pitch, (const signed char*)G, (size_t)N, (size_t)N, (size_t)M, CopyPool::pack_instance());
-          c->h2d_stream = c->io_stream;
-        }
-        if (prc == 2) {  // a value above 2 (not a hard call), or rows longer than a staging chunk: this gene crosses as bytes
-          (void)hipStreamSynchronize(c->copy_stream);  // (rows already on their way land before the block is handed out again)
-          give_back();
-          c->no_i8_pack = true;
-          const int rc2 = submit_common(c, gene_id, M, G, mode, af, af_out, tests, prm);
-          c->no_i8_pack = false;
-          return rc2;
-        }
-        if (prc != 0) e = hipErrorUnknown;
-      } else if (e == hipSuccess) {
-        c->h2d_stream = c->copy_stream;
-        const int rcs = staged_h2d_2d(c, rows, pk_pitch, G, cb, cb, (size_t)M, true);  // (pad bytes of a packed row are zero anyway)
-        c->h2d_stream = c->io_stream;
-        if (rcs != RVT_OK) e = hipErrorUnknown;
-      }
-      if (e == hipSuccess) e = hipEventRecord(c->ev_pack_copied[ek], c->copy_stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(st, c->ev_pack_copied[ek], 0);
-      if (e == hipSuccess) {
-        const bed2_t* sb = reinterpret_cast<const bed2_t*>(rows);
-        hipLaunchKernelGGL((consolidate_count_kernel<bed2_t>), cgrid, dim3(256), 0, st, sb, (long long)pk_pitch, (long long)N,
-                           c->d_consol_parts);
-        hipLaunchKernelGGL((consolidate_fill_kernel<bed2_t>), dim3((unsigned)M), dim3(64), 0, st, sb, (long long)pk_pitch,
-                           (long long)N, nparts, c->d_consol_parts, d_af_dst, d_fill);
-        hipLaunchKernelGGL(hcp_header_kernel, dim3(1), dim3(128), 0, st, c->d_consol_parts, nparts, M, (long long)N, d_fill,
-                           reinterpret_cast<HcpHeader*>(p.dG));
-      }
-      }
-    } else if (mode == 1 || mode == 5 || mode == 6) {
-      int rc = mode == 1   ? upload_block_data(c, p.dG, M, (const double*)G)
-               : mode == 5 ? vcf_decode_gene(c, (const VcfGene*)G, M, N, st, err_slot, p.dG, ld)  // VCF dosage text -> doubles
-                           : bgen_decode_gene(c, (const BgenGene*)G, M, N, st, err_slot, p.dG, ld);  // BGEN blocks -> doubles
-      if (rc) {
-        give_back();
-        return rc;
-      }
-      hipLaunchKernelGGL((consolidate_count_kernel<double>), cgrid, dim3(256), 0, st, p.dG, (long long)ld, (long long)N,
-                         c->d_consol_parts);
-      hipLaunchKernelGGL((consolidate_fill_kernel<double>), dim3((unsigned)M), dim3(64), 0, st, p.dG, (long long)ld,
-                         (long long)N, nparts, c->d_consol_parts, d_af_dst, d_fill);
-      hipLaunchKernelGGL((consolidate_write_kernel<double>), cgrid, dim3(256), 0, st, p.dG, (long long)ld, (long long)N,
-                         (long long)ld, d_fill, p.dG);
-    } else {
-      // packed hard calls: one byte per genotype (mode 2; mode 4 decodes VCF text into that form first) or PLINK's
-      // 2-bit codes, ceil(N/4) bytes per variant (mode 3)
-      const size_t col_bytes = (mode == 3 || mode == 7) ? (size_t)((N + 3) / 4) : (size_t)N;
-      const size_t bytes8 = col_bytes * M;
-      const void* d_packed = nullptr;  // where the packed genotypes of this gene are on the device
-      int pk = -1;
-      if (mode == 4) {
-        e = c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4);
-        if (e == hipSuccess && vcf_decode_gene(c, (const VcfGene*)G, M, N, st, err_slot) != RVT_OK) e = hipErrorUnknown;
-        d_packed = c->d_consol_i8;
-      } else {
-        // host copy on the copy stream into the next landing buffer of the ring (free once the consolidation kernels of
-        // the gene that used it last have run); the kernels of THIS gene wait for the copy by event
-        pk = c->pack_next;
-        c->pack_next = (pk + 1) % rvt_ctx::kPack;
-        e = c->d_pack[pk].grow(bytes8, bytes8 + bytes8 / 4);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_pack_free[pk], 0);
-        if (e == hipSuccess && mode == 7) {  // (device-resident rows: into the same landing buffer, whatever their alignment)
-          e = hipMemcpyAsync(c->d_pack[pk], G, bytes8, hipMemcpyDeviceToDevice, c->copy_stream);
-        } else if (e == hipSuccess) {
-          c->h2d_stream = c->copy_stream;
-          const int rcs = staged_h2d(c, c->d_pack[pk], G, bytes8);
-          c->h2d_stream = c->io_stream;
-          if (rcs != RVT_OK) e = hipErrorUnknown;
-        }
-        if (e == hipSuccess) e = hipEventRecord(c->ev_pack_copied[pk], c->copy_stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(st, c->ev_pack_copied[pk], 0);
-        d_packed = c->d_pack[pk];
-      }
-      if (e == hipSuccess && (mode == 3 || mode == 7)) {
-        const bed2_t* sb = (const bed2_t*)d_packed;
-        const long long cb = (long long)col_bytes;
-        hipLaunchKernelGGL((consolidate_count_kernel<bed2_t>), cgrid, dim3(256), 0, st, sb, cb, (long long)N,
-                           c->d_consol_parts);
-        hipLaunchKernelGGL((consolidate_fill_kernel<bed2_t>), dim3((unsigned)M), dim3(64), 0, st, sb, cb, (long long)N,
-                           nparts, c->d_consol_parts, d_af_dst, d_fill);
-        hipLaunchKernelGGL((consolidate_write_kernel<bed2_t>), cgrid, dim3(256), 0, st, sb, cb, (long long)N,
-                           (long long)ld, d_fill, p.dG);
-      } else if (e == hipSuccess) {
-        const signed char* s8 = (const signed char*)d_packed;
-        hipLaunchKernelGGL((consolidate_count_kernel<signed char>), cgrid, dim3(256), 0, st, s8, (long long)N,
-                           (long long)N, c->d_consol_parts);
-        hipLaunchKernelGGL((consolidate_fill_kernel<signed char>), dim3((unsigned)M), dim3(64), 0, st, s8, (long long)N,
-                           (long long)N, nparts, c->d_consol_parts, d_af_dst, d_fill);
-        hipLaunchKernelGGL((consolidate_write_kernel<signed char>), cgrid, dim3(256), 0, st, s8, (long long)N,
-                           (long long)N, (long long)ld, d_fill, p.dG);
-      }
-      if (pk >= 0 && e == hipSuccess) e = hipEventRecord(c->ev_pack_free[pk], st);  // the landing buffer may be refilled
-    }
-    p.af.resize(M);
-    if (af_out) {
-      if (e == hipSuccess) e = hipMemcpyAsync(p.af.data(), c->d_consol_af, afb, hipMemcpyDeviceToHost, st);
-      if (e == hipSuccess) e = sync_stream(st);
-      if (e == hipSuccess && decodes && c->h_io_err[err_slot]) {  // malformed text / block: this very gene is refused
-        io_err_message(c, c->h_io_err[err_slot], mode == 6, "");
-        c->h_io_err[err_slot] = 0;
-        give_back();
-        return RVT_E_INVALID;
-      }
-    } else if (e == hipSuccess) {
-      // nobody waits for the frequencies: the host copy of the block is already consumed (a copy from pageable memory
-      // returns once the source has been read), so return now and pick the frequencies up at launch time
-      p.af_slot = ring_slot;  // (written by consolidate_fill_kernel through the mapping; read after the stream is waited for)
-      ++c->af_unresolved;
-    }
-    if (e != hipSuccess) {
-      give_back();
-      return fail(c, RVT_E_HIP, "genotype consolidation failed: %s", hipGetErrorString(e));
-    }
-    if (af_out) std::memcpy(af_out, p.af.data(), afb);
-  }
-  p.tests = tests;
-  p.prm = prm ? *prm : rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05};
-  c->queue.push_back(std::move(p));
-  // complete groups start computing now and overlap the host-side copies of the following genes
-  TraceScope ts_l(c, &c->tr_launch);
-  return launch_pending(c, c->queue.size(), true);
+  const Submit s{c, gene_id, M, G, in, af, af_out, tests, prm};
+  int rc = submit_routed(s, true);
+  if (rc == kRetryExpanded) rc = submit_routed(s, false);  // (the packed block is back in its pool)
+  return rc;
 }
+}  // extern "C++"
 }  // namespace
 
 // ---- several genes of a device-resident .bed matrix per call (rvt_submit_genes, kind 7) -----------------------------------------
@@ -956,6 +982,41 @@ __global__ __launch_bounds__(128) void bed_fill_header_kernel(const BedGeneRef* 
   }
 }
 
+// The two launches over the rows of n genes, on stream st: the references go into the call's work space (c->d_bedbatch, carved
+// for up to max_rows rows and max_genes genes: row references | gene references | partial counts | frequency sink | counts) and
+// every block named by them gets its rows and its header.  d_counts (rvt_score_bed_dev): nobody wants the frequencies — they go
+// to the sink — and *d_counts is where the kernel leaves n0, n1, n2 and missing of every row; NULL (rvt_submit_genes): the
+// frequencies go where the gene references say.  `what` names the caller in the message of a failure.
+int bed_rows_consolidate(rvt_ctx* c, hipStream_t st, const char* what, const std::vector<BedRowRef>& rows,
+                         std::vector<BedGeneRef>& genes, int max_rows, int max_genes, long long** d_counts) {
+  auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+  const long long N = c->nc.N;
+  const int nparts = consol_nparts(N), R = (int)rows.size(), n = (int)genes.size();
+  const size_t b_rows = pad(sizeof(BedRowRef) * (size_t)max_rows), b_genes = pad(sizeof(BedGeneRef) * (size_t)max_genes);
+  const size_t b_parts = pad(sizeof(ConsolPart) * (size_t)max_rows * nparts);
+  const size_t b_af = d_counts ? sizeof(double) * (size_t)max_rows : 0, b_cnt = d_counts ? sizeof(long long) * 4 * (size_t)max_rows : 0;
+  const size_t need = b_rows + b_genes + b_parts + b_af + b_cnt;
+  HIP_TRY(c, c->d_bedbatch.grow(need, need + need / 2, st));
+  char* w = c->d_bedbatch;
+  BedRowRef* d_rows = reinterpret_cast<BedRowRef*>(w);
+  BedGeneRef* d_genes = reinterpret_cast<BedGeneRef*>(w + b_rows);
+  ConsolPart* d_parts = reinterpret_cast<ConsolPart*>(w + b_rows + b_genes);
+  if (d_counts) {
+    double* d_afsink = reinterpret_cast<double*>(w + b_rows + b_genes + b_parts);
+    *d_counts = reinterpret_cast<long long*>(w + b_rows + b_genes + b_parts + b_af);
+    for (BedGeneRef& g : genes) g.af_dst = d_afsink + g.row0, g.cnt_dst = *d_counts + 4 * (size_t)g.row0;
+  }
+  hipError_t e = hipMemcpyAsync(d_rows, rows.data(), sizeof(BedRowRef) * (size_t)R, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_genes, genes.data(), sizeof(BedGeneRef) * (size_t)n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(bed_count_copy_rows_kernel, dim3((unsigned)nparts, (unsigned)R), dim3(256), 0, st, d_rows, N, d_parts);
+    hipLaunchKernelGGL(bed_fill_header_kernel, dim3((unsigned)n), dim3(128), 0, st, d_genes, d_parts, nparts, N);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return fail(c, RVT_E_HIP, "%s: %s", what, hipGetErrorString(e));
+  return RVT_OK;
+}
+
 // returns -1 when the call does not apply (a gene that has to be expanded): the caller submits gene by gene
 int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, const void* const* data, uint32_t tests,
                          const rvt_params* prm) {
@@ -971,7 +1032,6 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
   const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
-  const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
   HIP_TRY(c, c->h_af_ring.grow(kAfRingBytes, kAfRingBytes, nullptr, false, hipHostMallocMapped));
   if (c->af_unresolved + n > rvt_ctx::kAfSlots) {
     int rc = resolve_af(c);
@@ -979,76 +1039,32 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
   }
   double* mapped = nullptr;
   HIP_TRY(c, hipHostGetDevicePointer((void**)&mapped, c->h_af_ring, 0));
-  // device work space of the call: row and gene references, the rows' partial counts
-  const size_t b_rows = (sizeof(BedRowRef) * (size_t)R + 255) / 256 * 256, b_genes = (sizeof(BedGeneRef) * (size_t)n + 255) / 256 * 256;
-  const size_t need = b_rows + b_genes + sizeof(ConsolPart) * (size_t)R * nparts;
-  HIP_TRY(c, c->d_bedbatch.grow(need, need + need / 2, st));
-  std::vector<BedRowRef> rows((size_t)R);
-  std::vector<BedGeneRef> genes((size_t)n);
-  std::vector<rvt_ctx::Pending> pend((size_t)n);
-  auto give_back = [&](int upto) {
-    for (int g = 0; g < upto; ++g) c->pk_pool.emplace_back(pend[(size_t)g].bytes, pend[(size_t)g].dG);
-  };
-  int r0 = 0;
+  std::vector<BedRowRef> rows;
+  std::vector<BedGeneRef> genes;
+  std::vector<rvt_ctx::Pending> pend;
+  std::vector<BlockLease> blk;  // (an early return hands every block taken so far back)
+  rows.reserve((size_t)R), genes.reserve((size_t)n), pend.reserve((size_t)n), blk.reserve((size_t)n);
   for (int g = 0; g < n; ++g) {
-    rvt_ctx::Pending& p = pend[(size_t)g];
-    const int M = Ms[g];
-    p.id = ids[g];
-    p.M = M;
-    p.launched = false;
-    std::memset(&p.res, 0, sizeof(p.res));
-    const size_t gene_bytes = (size_t)kHcpHeaderBytes + pk_pitch * M + 16;
-    int best = -1;
-    for (int i = 0; i < (int)c->pk_pool.size(); ++i)
-      if (c->pk_pool[i].first >= gene_bytes && c->pk_pool[i].first <= 4 * gene_bytes &&
-          (best < 0 || c->pk_pool[i].first < c->pk_pool[best].first))
-        best = i;
-    if (best >= 0) {
-      p.dG = c->pk_pool[best].second;
-      p.bytes = c->pk_pool[best].first;
-      c->pk_pool.erase(c->pk_pool.begin() + best);
-    } else {
-      if (hipMalloc((void**)&p.dG, gene_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        give_back(g);
-        return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed gene", gene_bytes);
-      }
-      p.bytes = gene_bytes;
-      if (hipMemsetAsync(p.dG, 0, gene_bytes, st) != hipSuccess) {
-        give_back(g + 1);
-        return fail(c, RVT_E_HIP, "clearing a packed gene's block failed");
-      }
-    }
-    unsigned char* dst = reinterpret_cast<unsigned char*>(p.dG) + kHcpHeaderBytes;
+    const int M = Ms[g], r0 = (int)rows.size();
+    blk.push_back(lease_packed(c, M));
+    const BlockLease& b = blk.back();
+    if (!b) return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed gene", packed_block_bytes(N, M));
+    if (b.fresh() && hipMemsetAsync(b.get(), 0, b.bytes(), st) != hipSuccess)
+      return fail(c, RVT_E_HIP, "clearing a packed gene's block failed");
     const unsigned char* src = static_cast<const unsigned char*>(data[g]);
-    for (int j = 0; j < M; ++j) rows[(size_t)(r0 + j)] = BedRowRef{src + cb * (size_t)j, dst + pk_pitch * (size_t)j};
+    for (int j = 0; j < M; ++j) rows.push_back(BedRowRef{src + cb * (size_t)j, packed_rows(b) + pk_pitch * (size_t)j});
     const int slot = (int)(c->af_seq++ % rvt_ctx::kAfSlots);
-    genes[(size_t)g] = BedGeneRef{r0, M, reinterpret_cast<HcpHeader*>(p.dG), mapped + (size_t)slot * RVT_MAX_VARIANTS, nullptr};
+    genes.push_back(BedGeneRef{r0, M, packed_header(b), mapped + (size_t)slot * RVT_MAX_VARIANTS, nullptr});
+    pend.emplace_back(ids[g], M, tests, prm);
+    rvt_ctx::Pending& p = pend.back();
     p.af_slot = slot;
     p.af.resize((size_t)M);
     p.kind = kKindPacked;
     p.planes = true;  // (resident rows: nothing waits for a link, the sufficient-statistics kernel is the bound)
-    p.decoded = 0;
-    p.tests = tests;
-    p.prm = prm ? *prm : rvt_params{1.0, 25.0, 1.0, 25.0, 0, 0.05};
-    r0 += M;
   }
-  char* w = c->d_bedbatch;
-  BedRowRef* d_rows = reinterpret_cast<BedRowRef*>(w);
-  BedGeneRef* d_genes = reinterpret_cast<BedGeneRef*>(w + b_rows);
-  ConsolPart* d_parts = reinterpret_cast<ConsolPart*>(w + b_rows + b_genes);
-  hipError_t e = hipMemcpyAsync(d_rows, rows.data(), sizeof(BedRowRef) * (size_t)R, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_genes, genes.data(), sizeof(BedGeneRef) * (size_t)n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(bed_count_copy_rows_kernel, dim3((unsigned)nparts, (unsigned)R), dim3(256), 0, st, d_rows, (long long)N, d_parts);
-    hipLaunchKernelGGL(bed_fill_header_kernel, dim3((unsigned)n), dim3(128), 0, st, d_genes, d_parts, nparts, (long long)N);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) {
-    give_back(n);
-    return fail(c, RVT_E_HIP, "resident .bed genes: %s", hipGetErrorString(e));
-  }
+  if (int rc = bed_rows_consolidate(c, st, "resident .bed genes", rows, genes, R, n, nullptr)) return rc;
   for (int g = 0; g < n; ++g) {
+    pend[(size_t)g].dG = blk[(size_t)g].release(&pend[(size_t)g].bytes);
     c->queue.push_back(std::move(pend[(size_t)g]));
     ++c->af_unresolved;
     if (c->trace_submit) ++c->tr_genes;
@@ -1200,50 +1216,21 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
   const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
-  const int nparts = (int)((N + kConsolChunk - 1) / kConsolChunk);
-  const size_t gene_bytes = (size_t)kHcpHeaderBytes + pk_pitch * kSlice + 16;
-  // work space: row / gene references, partial counts (as submit_bed_dev_batch), a frequency sink, the counts
-  const int Rmax = kSlice * kChunk;
-  const size_t b_rows = (sizeof(BedRowRef) * (size_t)Rmax + 255) / 256 * 256, b_genes = (sizeof(BedGeneRef) * (size_t)kChunk + 255) / 256 * 256;
-  const size_t b_parts = (sizeof(ConsolPart) * (size_t)Rmax * nparts + 255) / 256 * 256, b_af = sizeof(double) * (size_t)Rmax;
-  const size_t need = b_rows + b_genes + b_parts + b_af + sizeof(long long) * 4 * (size_t)Rmax;
-  HIP_TRY(c, c->d_bedbatch.grow(need, need + need / 2, st));
-  char* w = c->d_bedbatch;
-  BedRowRef* d_rref = reinterpret_cast<BedRowRef*>(w);
-  BedGeneRef* d_gref = reinterpret_cast<BedGeneRef*>(w + b_rows);
-  ConsolPart* d_parts = reinterpret_cast<ConsolPart*>(w + b_rows + b_genes);
-  double* d_afsink = reinterpret_cast<double*>(w + b_rows + b_genes + b_parts);
-  long long* d_cnt = reinterpret_cast<long long*>(w + b_rows + b_genes + b_parts + b_af);
-  // the slices' blocks: kChunk of them, reused chunk after chunk (the batch is synchronous)
+  // the slices' blocks: kChunk of them, reused chunk after chunk (the batch is synchronous); back in the pool on every return
+  std::vector<BlockLease> leases;
   std::vector<double*> blk;
-  auto release = [&]() {
-    for (double* b : blk) c->pk_pool.emplace_back(gene_bytes, b);
-    blk.clear();
-  };
   const int64_t n_slices_all = (V + kSlice - 1) / kSlice;
   const int n_blk = (int)std::min<int64_t>(kChunk, n_slices_all);
+  leases.reserve((size_t)n_blk);
   for (int g = 0; g < n_blk; ++g) {
-    double* b = nullptr;
-    int best = -1;
-    for (int i = 0; i < (int)c->pk_pool.size(); ++i)
-      if (c->pk_pool[i].first >= gene_bytes && c->pk_pool[i].first <= 4 * gene_bytes && (best < 0 || c->pk_pool[i].first < c->pk_pool[best].first)) best = i;
-    if (best >= 0) {
-      b = c->pk_pool[best].second;
-      c->pk_pool.erase(c->pk_pool.begin() + best);
-    } else {
-      if (hipMalloc((void**)&b, gene_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        release();
-        return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed slice", gene_bytes);
-      }
-      if (hipMemsetAsync(b, 0, gene_bytes, st) != hipSuccess) {
-        blk.push_back(b);
-        release();
-        return fail(c, RVT_E_HIP, "clearing a packed slice failed");
-      }
-    }
-    blk.push_back(b);
+    leases.push_back(lease_packed(c, kSlice));
+    const BlockLease& b = leases.back();
+    if (!b) return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed slice", packed_block_bytes(N, kSlice));
+    if (b.fresh() && hipMemsetAsync(b.get(), 0, b.bytes(), st) != hipSuccess)
+      return fail(c, RVT_E_HIP, "clearing a packed slice failed");
+    blk.push_back(b.get());
   }
+  long long* d_cnt = nullptr;  // (in the call's work space: 4 counts per row of the chunk)
   std::vector<BedRowRef> rows;
   std::vector<BedGeneRef> genes;
   std::vector<const double*> ptr;
@@ -1269,26 +1256,17 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
       const int r0 = (int)rows.size();
       for (int j = 0; j < M; ++j) rows.push_back(BedRowRef{src + cb * (size_t)j, dst + pk_pitch * (size_t)j});
       // (a shorter last slice: the rows behind it in the block keep an earlier slice's codes — beyond M, never read)
-      genes.push_back(BedGeneRef{r0, M, reinterpret_cast<HcpHeader*>(blk[(size_t)g]), d_afsink + r0, d_cnt + 4 * (size_t)r0});
+      genes.push_back(BedGeneRef{r0, M, reinterpret_cast<HcpHeader*>(blk[(size_t)g]), nullptr, nullptr});  // (sinks: the work space's)
       ptr.push_back(blk[(size_t)g]);
       Ms.push_back(M);
       ids.push_back((int64_t)g * kSlice);
     }
-    const int R = (int)rows.size();
-    hipError_t e = hipMemcpyAsync(d_rref, rows.data(), sizeof(BedRowRef) * (size_t)R, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_gref, genes.data(), sizeof(BedGeneRef) * (size_t)n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(bed_count_copy_rows_kernel, dim3((unsigned)nparts, (unsigned)R), dim3(256), 0, st, d_rref, (long long)N, d_parts);
-      hipLaunchKernelGGL(bed_fill_header_kernel, dim3((unsigned)n), dim3(128), 0, st, d_gref, d_parts, nparts, (long long)N);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && counts)
-      e = hipMemcpyAsync(counts + 4 * v0, d_cnt, sizeof(long long) * 4 * (size_t)R, hipMemcpyDeviceToHost, st);
+    rc = bed_rows_consolidate(c, st, "resident .bed score", rows, genes, kSlice * kChunk, kChunk, &d_cnt);
+    if (rc) return rc;
+    hipError_t e = hipSuccess;
+    if (counts) e = hipMemcpyAsync(counts + 4 * v0, d_cnt, sizeof(long long) * 4 * rows.size(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // (run_batch launches on its own streams)
-    if (e != hipSuccess) {
-      release();
-      return fail(c, RVT_E_HIP, "resident .bed score: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, RVT_E_HIP, "resident .bed score: %s", hipGetErrorString(e));
     if (binary) {  // the weighted tile: its own kernel variant and finisher, launched here (run_batch is the quantitative path's)
       double* const outs[5] = {ustat + v0, vstat + v0, effect + v0, effect_se + v0, pvalue + v0};
       rc = score_bed_binary_chunk(c, st, n, blk.data(), Ms.data(), kSlice, cols, ok + v0, outs);
@@ -1305,17 +1283,16 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
     co.pval = pvalue + v0;
     rc = run_batch(c, n, ptr.data(), Ms.data(), af.data(), ids.data(), 0u, nullptr, rs.data(), nullptr, &co, kinds.data());
   }
-  release();
   return rc;
 }
 
 int rvt_submit_gene(rvt_ctx* c, int64_t gene_id, int M, const double* G, const double* af, uint32_t tests,
                     const rvt_params* prm) {
-  return submit_common(c, gene_id, M, G, 0, af, nullptr, tests, prm);
+  return submit_common(c, gene_id, M, G, GeneInput::kF64, af, nullptr, tests, prm);
 }
 int rvt_submit_gene_bed(rvt_ctx* c, int64_t gene_id, int M, const unsigned char* bed, uint32_t tests,
                         const rvt_params* prm, double* af_out) {
-  return submit_common(c, gene_id, M, bed, 3, nullptr, af_out, tests, prm);
+  return submit_common(c, gene_id, M, bed, GeneInput::kBed, nullptr, af_out, tests, prm);
 }
 // ---- a .bed matrix resident in HBM ---------------------------------------------------------------------------------------
 // 500 000 samples x 2 000 000 variants of PLINK 2-bit rows are 250 GB: a whole exome-scale cohort fits the 288 GB of one
@@ -1354,15 +1331,15 @@ int rvt_bed_free(rvt_ctx* c, unsigned char* d_bed) {
 }
 int rvt_submit_gene_bed_dev(rvt_ctx* c, int64_t gene_id, int M, const unsigned char* d_rows, uint32_t tests,
                             const rvt_params* prm, double* af_out) {
-  return submit_common(c, gene_id, M, d_rows, 7, nullptr, af_out, tests, prm);
+  return submit_common(c, gene_id, M, d_rows, GeneInput::kBedDev, nullptr, af_out, tests, prm);
 }
 int rvt_submit_gene_raw(rvt_ctx* c, int64_t gene_id, int M, const double* Graw, uint32_t tests,
                         const rvt_params* prm, double* af_out) {
-  return submit_common(c, gene_id, M, Graw, 1, nullptr, af_out, tests, prm);
+  return submit_common(c, gene_id, M, Graw, GeneInput::kRaw, nullptr, af_out, tests, prm);
 }
 int rvt_submit_gene_i8(rvt_ctx* c, int64_t gene_id, int M, const int8_t* G8, uint32_t tests, const rvt_params* prm,
                        double* af_out) {
-  return submit_common(c, gene_id, M, G8, 2, nullptr, af_out, tests, prm);
+  return submit_common(c, gene_id, M, G8, GeneInput::kI8, nullptr, af_out, tests, prm);
 }
 
 // Several genes per call (the same hand-off as rvt_submit_gene_raw / _i8 / _bed, gene after gene): for callers whose
@@ -1370,12 +1347,13 @@ int rvt_submit_gene_i8(rvt_ctx* c, int64_t gene_id, int M, const int8_t* G8, uin
 int rvt_submit_genes(rvt_ctx* c, int kind, int n, const int64_t* gene_ids, const int* M, const void* const* data,
                      uint32_t tests, const rvt_params* prm) {
   if (!c || n < 0 || (n > 0 && (!gene_ids || !M || !data))) return fail(c, RVT_E_INVALID, "bad gene list");
-  if ((kind < 1 || kind > 3) && kind != 7)
+  const GeneInput in = static_cast<GeneInput>(kind);
+  if (in != GeneInput::kRaw && in != GeneInput::kI8 && in != GeneInput::kBed && in != GeneInput::kBedDev)
     return fail(c, RVT_E_INVALID, "kind %d: 1 = doubles with missing codes, 2 = int8, 3 = PLINK 2-bit rows, 7 = PLINK 2-bit rows on the device", kind);
   // The genes' transfers out of page-locked caller memory (rvt_host_register) are queued back to back and waited for ONCE:
   // the call returns when the last of them has been read (a gene-by-gene submission waits per gene — the buffer may be
   // rewritten on return — which leaves the link idle between two genes).
-  if (kind == 7) {
+  if (in == GeneInput::kBedDev) {
     // resident rows: whole calls at once where every gene may stay packed, groups of up to 256 genes per batch of the pipeline
     // (nothing waits for a link here: the larger the batch, the fuller the chip)
     const int group0 = c->submit_group;
@@ -1387,7 +1365,7 @@ int rvt_submit_genes(rvt_ctx* c, int kind, int n, const int64_t* gene_ids, const
       if (rc == -1) {
         rc = RVT_OK;
         for (int g = g0; g < g0 + ng && !rc; ++g)
-          rc = submit_common(c, gene_ids[g], M[g], data[g], 7, nullptr, nullptr, tests, prm);
+          rc = submit_common(c, gene_ids[g], M[g], data[g], in, nullptr, nullptr, tests, prm);
       }
     }
     c->submit_group = group0;
@@ -1396,7 +1374,7 @@ int rvt_submit_genes(rvt_ctx* c, int kind, int n, const int64_t* gene_ids, const
   c->reg_defer = true;
   int rc = RVT_OK;
   for (int g = 0; g < n && !rc; ++g)
-    rc = submit_common(c, gene_ids[g], M[g], data[g], kind, nullptr, nullptr, tests, prm);  // (genes [0, g) are queued on failure)
+    rc = submit_common(c, gene_ids[g], M[g], data[g], in, nullptr, nullptr, tests, prm);  // (genes [0, g) are queued on failure)
   c->reg_defer = false;
   const int rcw = reg_wait(c);
   return rc ? rc : rcw;
@@ -1478,7 +1456,7 @@ int rvt_submit_gene_vcf(rvt_ctx* c, int64_t gene_id, int M, const char* const* s
   for (int j = 0; j < M; ++j)
     if (!sample_text[j] || text_len[j] < 0) return fail(c, RVT_E_INVALID, "record %d: no text", j);
   VcfGene vg{sample_text, text_len, gt_index, gd_index, gq_index};
-  return submit_common(c, gene_id, M, &vg, c->vcf_dosage ? 5 : 4, nullptr, af_out, tests, prm);
+  return submit_common(c, gene_id, M, &vg, c->vcf_dosage ? GeneInput::kVcfDosage : GeneInput::kVcfGt, nullptr, af_out, tests, prm);
 }
 
 // Decode only: the N x M signed bytes (column-major) the device reads out of the text, copied back to the caller.
@@ -1526,7 +1504,7 @@ int rvt_submit_gene_bgen(rvt_ctx* c, int64_t gene_id, int M, const unsigned char
     return fail(c, RVT_E_STATE, "the sample map addresses %lld rows, the null model has %lld samples",
                 (long long)c->vcf_n_rows, (long long)c->nc.N);
   BgenGene bg{block, block_len, layout};
-  return submit_common(c, gene_id, M, &bg, 6, nullptr, af_out, tests, prm);
+  return submit_common(c, gene_id, M, &bg, GeneInput::kBgen, nullptr, af_out, tests, prm);
 }
 
 // Decode only: the N x M raw genotypes (column-major doubles, -9 = missing) the device reads out of the blocks
@@ -1694,7 +1672,7 @@ static void pop_collected(rvt_ctx* c, int n, rvt_gene_result* out) {
       snprintf(who, sizeof(who), " of gene %lld", (long long)c->queue[g].id);
       io_err_message(c, c->queue[g].io_error, c->queue[g].decoded == 2, who);
     }
-    (c->queue[g].kind == kKindPacked ? c->pk_pool : c->block_pool).emplace_back(c->queue[g].bytes, c->queue[g].dG);
+    (c->queue[g].kind == kKindPacked ? c->pk_pool : c->block_pool).give(c->queue[g].bytes, c->queue[g].dG);
   }
   c->queue.erase(c->queue.begin(), c->queue.begin() + n);
   for (auto& L : c->launched) L.first -= (size_t)n;
@@ -1704,17 +1682,8 @@ static void pop_collected(rvt_ctx* c, int n, rvt_gene_result* out) {
       size_t fr = 0, tot = 0;
       return (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) ? tot / 3 : (size_t)16 << 30;
     }();
-    size_t total = 0;
-    for (auto& bp : c->block_pool) total += bp.first;
-    while (!c->block_pool.empty() && (total > kPoolBytes || c->block_pool.size() > 4096)) {
-      total -= c->block_pool.back().first;
-      hipFree(c->block_pool.back().second);
-      c->block_pool.pop_back();
-    }
-    while (c->pk_pool.size() > 4096) {
-      hipFree(c->pk_pool.back().second);
-      c->pk_pool.pop_back();
-    }
+    c->block_pool.trim(kPoolBytes, 4096, hipFree);
+    c->pk_pool.trim(SIZE_MAX, 4096, hipFree);
   }
 }
 
