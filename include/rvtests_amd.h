@@ -1042,6 +1042,18 @@ int rvt_debug_collapse(rvt_ctx* ctx, const double* dG, int M, double* cmc_out, d
  * colsum/min/max (M each); host outputs, row-major */
 int rvt_debug_suffstat(rvt_ctx* ctx, const double* dG, int M, double* S, double* T, double* u, double* colsum,
                        double* cmin, double* cmax);
+/* the spectrum stage of ONE block as the per-gene tail kernels left it, run as a batch of its own under RVT_TEST_ALL with
+ * the caller's allele frequencies af (M entries; the two calls above use a constant 0.01).  rec: the gene's record.
+ * lambda (2 M doubles, may be NULL): the gene's eigenvalue side buffer — the kept SKAT eigenvalues, descending, from
+ * stats[61], and those of SKAT-O's Z(I-M)Z' from stats[62]; entries behind the kept ones are not defined.
+ * stats (64 doubles, may be NULL): [0..10] Q_rho, [11..21] / [22..32] / [33..43] the rho problems' moments mu / var / df,
+ * [44..54] tau_rho, [55] muQ, [56] varQ, [57] varZeta, [58] df, [59] kept eigenvalues of Z(I-M)Z', [60] kept SKAT
+ * eigenvalues, [61] / [62] the two offsets into lambda; the rest is zero.
+ * dG_beside (may be NULL; then M_beside and af_beside are ignored): a second block that shares the batch, so that the tail
+ * kernels take the launch paths of a batch whose widest gene has max(M, M_beside) columns; rec then holds TWO records, the
+ * second one the second block's.  lambda and stats always describe the first block. */
+int rvt_debug_spectrum(rvt_ctx* ctx, const double* dG, int M, const double* af, const double* dG_beside, int M_beside,
+                       const double* af_beside, rvt_gene_result* rec, double* lambda, double* stats);
 /* U'G as the family tests compute it: the first ncols columns of an uploaded block through the rotation with the installed
  * kinship (rvt_set_kinship, and a null model for the block layout); out is a host N x ncols matrix, column-major.  Row k
  * belongs to eigenpair k in the INSTALLED order (family-structured U: stably sorted by first non-zero row) */

@@ -279,6 +279,8 @@ int hc_gene(int trait, int64_t N, int d, double sigma2, double rss, double rsum,
     dbg[58] = gs.df;
     dbg[59] = gs.zimz_nlambda;
     dbg[60] = gs.skat_nlambda;
+    dbg[61] = gs.skat_lambda_off;  // (slots as rvt_debug_spectrum's)
+    dbg[62] = gs.zimz_lambda_off;
   }
   return 0;
 }

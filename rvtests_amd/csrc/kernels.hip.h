@@ -1659,7 +1659,12 @@ __global__ __launch_bounds__(64, FAST ? RVT_PV_WAVES : 2) void gene_pvalue_kerne
   for (int i = lane; i < n_skat; i += 64) lam_skat[i] = gd.lambda[gs.skat_lambda_off + i];
   for (int i = lane; i < n_zimz; i += 64) lam_zimz[i] = gd.lambda[gs.zimz_lambda_off + i];
   __syncthreads();
-  if (lane == 0) pvalue_init_result(gs, gd.gene_id, out);
+  if (lane == 0) {
+    pvalue_init_result(gs, gd.gene_id, out);
+    // (with the test: gene_vt_kernel has written them before this kernel; without it nobody does, and the record would carry
+    //  what an earlier batch left at its place in the work space)
+    if (!(tests & RVT_TEST_ANALYTICVT)) pvalue_clear_vt(out);
+  }
   if (gs.n_poly == 0) return;
   wave_davies_sorted(lam_skat, n_skat, ls_skat, lane);
   wave_davies_sorted(lam_zimz, n_zimz, ls_zimz, lane);

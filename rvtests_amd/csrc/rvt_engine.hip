@@ -2157,6 +2157,49 @@ int rvt_debug_suffstat(rvt_ctx* c, const double* dG, int M, double* S, double* T
   return RVT_OK;
 }
 
+// the spectrum stage of ONE gene as the tail kernels left it: the record, the eigenvalue side buffer and the GeneStats fields
+// the host harness reports (hostcheck.cpp hc_gene, same slots).  A second block rides in the same batch when the caller wants
+// the launch paths of a wider batch (they go by the batch's widest gene); the inspected gene stays gene 0.
+int rvt_debug_spectrum(rvt_ctx* c, const double* dG, int M, const double* af, const double* dG_beside, int M_beside,
+                       const double* af_beside, rvt_gene_result* rec, double* lambda, double* stats) {
+  if (!c || !dG || !af || !rec || M < 1 || M > RVT_MAX_VARIANTS) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (dG_beside && (!af_beside || M_beside < 1 || M_beside > RVT_MAX_VARIANTS)) return fail(c, RVT_E_INVALID, "bad arguments");
+  const int n = dG_beside ? 2 : 1;
+  const double* ps[2] = {dG, dG_beside};
+  const int Ms[2] = {M, dG_beside ? M_beside : 0};
+  std::vector<double> afs(af, af + M);
+  if (dG_beside) afs.insert(afs.end(), af_beside, af_beside + M_beside);
+  DebugOut dbg;
+  GeneDesc g0;
+  dbg.desc0 = &g0;
+  int rc = run_batch(c, n, ps, Ms, afs.data(), nullptr, RVT_TEST_ALL, nullptr, rec, &dbg);
+  if (rc) return rc;
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  GeneStats gs;
+  HIP_TRY(c, hipMemcpy(&gs, g0.stats, sizeof(gs), hipMemcpyDeviceToHost));
+  if (lambda) HIP_TRY(c, hipMemcpy(lambda, g0.lambda, sizeof(double) * 2 * (size_t)M, hipMemcpyDeviceToHost));
+  if (stats) {
+    std::fill(stats, stats + 64, 0.0);
+    for (int i = 0; i < 11; ++i) {
+      stats[i] = gs.Qs[i];
+      stats[11 + i] = gs.mom_mu[i];
+      stats[22 + i] = gs.mom_var[i];
+      stats[33 + i] = gs.mom_df[i];
+      stats[44 + i] = gs.tau[i];
+    }
+    stats[55] = gs.muQ;
+    stats[56] = gs.varQ;
+    stats[57] = gs.varZeta;
+    stats[58] = gs.df;
+    stats[59] = gs.zimz_nlambda;
+    stats[60] = gs.skat_nlambda;
+    stats[61] = gs.skat_lambda_off;
+    stats[62] = gs.zimz_lambda_off;
+  }
+  return RVT_OK;
+}
+
 // ---- unrelated null models on the device -----------------------------------------------------------------------
 int rvt_fit_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const double* y, double* beta_out,
                  double* sigma2_out) {

@@ -54,6 +54,13 @@ RVT_HD void pvalue_init_result(const GeneStats& gs, int64_t gene_id, rvt_gene_re
   r->davies_terms = 0.0;
 }
 
+// the record's AnalyticVT fields as a batch without that test leaves them
+RVT_HD void pvalue_clear_vt(rvt_gene_result* r) {
+  r->vt_ok = r->vt_optnum = r->vt_ncutoff = 0;
+  r->vt_minmaf = r->vt_maxmaf = r->vt_optmaf = 0.0;
+  r->vt_U = r->vt_V = r->vt_stat = r->vt_p = r->vt_p_error = 0.0;
+}
+
 // SkatO bookkeeping between the per-rho p-values and the integral: min-p, rho, Q (SkatO.cpp:216-233)
 RVT_HD void skato_select(const GeneStats& gs, const double* pvals, double* minP_out, int* minIndex_out) {
   double minP = pvals[0];

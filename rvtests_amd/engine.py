@@ -214,6 +214,9 @@ def load_library():
     L.rvt_debug_suffstat.restype = C.c_int
     L.rvt_debug_suffstat.argtypes = [vp, vp, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                      c_double_p]
+    L.rvt_debug_spectrum.restype = C.c_int
+    L.rvt_debug_spectrum.argtypes = [vp, vp, C.c_int, c_double_p, vp, C.c_int, c_double_p, C.POINTER(GeneResult), c_double_p,
+                                     c_double_p]
     L.rvt_fit_null.restype = C.c_int
     L.rvt_fit_null.argtypes = [vp, C.c_int, C.c_int64, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
     L.rvt_rand_seed.restype = C.c_int
@@ -980,6 +983,29 @@ class Engine:
         self._check(self.L.rvt_debug_suffstat(self.ctx, C.c_void_p(int(ptr)), M, _dp(S), _dp(T), _dp(u), _dp(cs),
                                               _dp(mn), _dp(mx)))
         return S, T, u, cs, mn, mx
+
+    def debug_spectrum(self, ptr, M, af, beside=None):
+        """The spectrum stage of one block as the per-gene tail kernels left it (rvt_debug_spectrum), under the caller's
+        allele frequencies: a dict of the record `rec`, the kept SKAT eigenvalues `lam` (descending) and those of SKAT-O's
+        Z(I-M)Z' `lam_zimz`, the 64 `stats` slots of the ABI (the layout of hc.gene's dbg), and `beside_rec`.  beside =
+        (ptr, M, af) puts a second block into the same batch — the launch paths go by the batch's widest gene — and
+        beside_rec is its record."""
+        af = np.ascontiguousarray(af, dtype=np.float64)
+        assert af.size == M
+        rec = (GeneResult * 2)()
+        lam = np.zeros(2 * M)
+        stats = np.zeros(64)
+        if beside is None:
+            bp, bM, baf = None, 0, None
+        else:
+            bp, bM = C.c_void_p(int(beside[0])), int(beside[1])
+            baf = np.ascontiguousarray(beside[2], dtype=np.float64)
+            assert baf.size == bM
+        self._check(self.L.rvt_debug_spectrum(self.ctx, C.c_void_p(int(ptr)), int(M), _dp(af), bp, bM,
+                                              _dp(baf) if baf is not None else None, rec, _dp(lam), _dp(stats)))
+        n_skat, n_zimz, o_skat, o_zimz = (int(stats[k]) for k in (60, 59, 61, 62))
+        return dict(rec=rec[0], beside_rec=rec[1] if beside is not None else None, stats=stats,
+                    lam=lam[o_skat:o_skat + n_skat].copy(), lam_zimz=lam[o_zimz:o_zimz + n_zimz].copy())
 
     def debug_rotate(self, ptr, ncols):
         """U'G of the first ncols columns of a device block, N x ncols (rvt_debug_rotate); rows in the installed eigenpair

@@ -177,12 +177,13 @@ def burden_sums(c_cmc, c_zeg, X, res, v, binary):
     return np.ascontiguousarray(np.vstack(out))
 
 
-def gene(G, af, X, res, v, binary, sigma2, tests=15, params=None, bstats=None):
+def gene(G, af, X, res, v, binary, sigma2, tests=15, params=None, bstats=None, stats=None):
+    """stats: (R, colstat) in suffstats()' layout to use instead of numpy's — e.g. the device's own (Engine.debug_suffstat)."""
     G = np.asarray(G, dtype=np.float64)
     N, M = G.shape
     d = X.shape[1]
     Cm, Cinv, rss, rsum = null_consts(X, res, v, binary)
-    R, colstat = suffstats(G, X, res, v, binary)
+    R, colstat = suffstats(G, X, res, v, binary) if stats is None else (np.ascontiguousarray(s, dtype=np.float64) for s in stats)
     prm = params or default_params()
     out = GeneResult()
     flip = np.zeros(M, dtype=np.int32)
