@@ -583,6 +583,31 @@ int rvt_set_kinship(rvt_ctx* ctx, int64_t N, const float* U, const float* S);
  * zeros, so the rotated values are those of the dense product (the statistics sum the eigenpairs in the new order: equal to
  * rounding).  RVT_KINSHIP_DENSE=1 in the environment disables the detection. */
 int rvt_kinship_structure(rvt_ctx* ctx, double* visited_fraction);
+/* The FAMILY FORM of a decomposition: a pedigree kinship handed over family by family, never as an N x N matrix.  The N samples
+ * are split into n_fam families of 1 .. 64 members: fam_ptr[n_fam + 1] (fam_ptr[0] = 0, fam_ptr[n_fam] = N, increasing) and
+ * members[N], a permutation of 0 .. N-1 — the samples of family f are members[fam_ptr[f] .. fam_ptr[f+1]), in any order.
+ * Matrices travel as blocks: family f's k x k block is column-major float (as Eigen::MatrixXf lays it out), row r = sample
+ * members[fam_ptr[f] + r], the blocks concatenated in family order.  Eigenpair fam_ptr[f] + j is column j of family f's block
+ * and S[fam_ptr[f] + j] its eigenvalue; the equivalent dense matrix has U[members[fam_ptr[f] + r], fam_ptr[f] + j] =
+ * block_f[r, j] and zeros elsewhere.
+ * rvt_set_kinship_families installs the decomposition as rvt_set_kinship would install that dense U: every later family call
+ * behaves the same (both sum the same products, in ascending sample order inside a family), the fitted null models
+ * are dropped the same way.  Nothing of order N^2 is allocated or touched: the device holds sum k^2 doubles and as many row
+ * indices, O(N) descriptors, S and U'1 (at most 64 N entries of 12 bytes; 4 N for nuclear families of four), the rotation U'G
+ * streams the fp64 columns once through a kernel of its own (rot_fam_kernel, rvtests_amd/csrc/rot_gemm.hip.h; bit-reproducible),
+ * and rvt_kinship_structure reports sum k^2 / N^2.  RVT_E_INVALID with a message naming the first offending family or index:
+ * a fam_ptr that does not increase from 0 to N, an empty family or one above 64, a members that is no permutation, a
+ * non-finite entry.  A refused call leaves the installed decomposition as it was.
+ * Not covered: families above 64 and a dense kinship such as a GRM (both: rvt_set_kinship / rvt_kinship_decompose). */
+int rvt_set_kinship_families(rvt_ctx* ctx, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                             const float* U_blocks, const float* S);
+/* The connected components of a list of related pairs (i[e], j[e]), e < n_pairs, over N samples — the families of a sparse
+ * kinship file, ready for the two family-form calls.  Host only, no context.  Self-pairs and repeats are harmless, a sample in
+ * no pair is a family of its own.  Members ascending inside a family, families in the order of their first member; *n_fam
+ * families, fam_ptr needs N + 1 entries (n_fam + 1 are written), members N.  RVT_E_INVALID for an index outside 0 .. N-1.
+ * Families are NOT limited to 64 here: the caller sees from fam_ptr what the family-form calls would refuse. */
+int rvt_kinship_components(int64_t N, int64_t n_pairs, const int32_t* i, const int32_t* j, int64_t* n_fam, int64_t* fam_ptr,
+                           int32_t* members);
 int rvt_fit_fam_null(rvt_ctx* ctx, int64_t N, int d, const double* X, const double* y, rvt_fam_null* out);
 int rvt_run_fam_blocks(rvt_ctx* ctx, int n_genes, const double* const* dG, const int* M, const int64_t* gene_ids,
                        rvt_gene_result* out);
@@ -639,6 +664,16 @@ typedef struct rvt_decompose_info {
 } rvt_decompose_info;
 int rvt_kinship_decompose(rvt_ctx* ctx, int64_t N, const float* K, float* U_out, float* S_out, int install,
                           rvt_decompose_info* info);
+/* The same for a kinship in the family form (see rvt_set_kinship_families): K_blocks holds every family's k x k kinship block,
+ * U_blocks_out (sum k^2 floats) and S_out (N floats) receive the eigenvectors and eigenvalues block by block (either may be
+ * NULL), eigenvalues ASCENDING within each family — the statistics do not depend on the order of the eigenpairs.  The blocks
+ * are packed into 64 x 64 tiles and diagonalised by the same kernel and code as the family-wise path of rvt_kinship_decompose,
+ * a bounded number of tiles at a time; install != 0 installs the result through the family form.  Nothing of order N^2 is
+ * formed on either side.  A block that is not symmetric or not finite is RVT_E_INVALID, and so is a residual above the bar of
+ * rvt_kinship_decompose (1e-9 x 4 x the largest absolute row sum): there is no dense iteration to fall back to here. */
+int rvt_kinship_decompose_families(rvt_ctx* ctx, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                                   const float* K_blocks, float* U_blocks_out, float* S_out, int install,
+                                   rvt_decompose_info* info);
 /* The empirical kinship of `vcf2kinship --ibs` / `--bn` from V consecutive rows of a resident .bed matrix (rvt_bed_alloc /
  * rvt_bed_upload; d_rows = d_bed + first_row * ceil(N/4), N = the installed null model's sample count): the step in front of
  * rvt_kinship_decompose.  Synchronous.  K_out: N x N doubles in host memory (need not be registered), symmetric, every entry
@@ -1030,6 +1065,9 @@ int rvt_group_collect_ready(rvt_group* group, rvt_gene_result* out, int cap, int
  * deals HOST genotype blocks (N x M[g] doubles, imputed, unflipped) to the members in contiguous shares balanced by column
  * count, every member uploads and runs its share concurrently (one host thread per member inside the call). */
 int rvt_group_set_kinship(rvt_group* group, int64_t N, const float* U, const float* S);
+/* the family form on every member (rvt_set_kinship_families: sum k^2 values each instead of 6 N^2 bytes) */
+int rvt_group_set_kinship_families(rvt_group* group, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                                   const float* U_blocks, const float* S);
 int rvt_group_fit_fam_null(rvt_group* group, int64_t N, int d, const double* X, const double* y, rvt_fam_null* out);
 int rvt_group_run_fam_tests_host(rvt_group* group, int n_genes, const double* const* G_host, const int* M,
                                  const int64_t* gene_ids, uint32_t tests, rvt_gene_result* out);
@@ -1058,6 +1096,9 @@ int rvt_debug_spectrum(rvt_ctx* ctx, const double* dG, int M, const double* af, 
  * kinship (rvt_set_kinship, and a null model for the block layout); out is a host N x ncols matrix, column-major.  Row k
  * belongs to eigenpair k in the INSTALLED order (family-structured U: stably sorted by first non-zero row) */
 int rvt_debug_rotate(rvt_ctx* ctx, const double* dG, int ncols, double* out);
+/* Measurement (tools/bench_fam_families.py): the same rotation without the copy to the host; *ms = the device milliseconds
+ * between HIP events recorded directly around it. */
+int rvt_debug_rotate_timed(rvt_ctx* ctx, const double* dG, int ncols, double* ms);
 int rvt_set_profiling(rvt_ctx* ctx, int on);
 int rvt_get_timing(rvt_ctx* ctx, rvt_timing* t, int reset);
 /* the HIP stream (hipStream_t) the engine launches on, for callers that record their own events */

@@ -11,10 +11,11 @@ from .engine import (Engine, Group, GeneResult, Params, Timing, RvtError, build_
                      TEST_SKAT, TEST_SKATO, TEST_CMC, TEST_ZEGGINI, TEST_ALL, TEST_ANALYTICVT, TRAIT_QUANTITATIVE,
                      TRAIT_BINARY, MAX_INFLIGHT, KbacResult, DecomposeInfo, VtPriceResult, RareCoverResult,
                      MbResult, BurdenMoreResult, BurdenWaldFit, BURDEN_CMCWALD, BURDEN_ZEGGINIWALD, BURDEN_FP,
-                     BURDEN_EXACTCMC, BURDEN_ALL, CODING_DOMINANT, CODING_RECESSIVE, KinshipInfo, KINSHIP_IBS, KINSHIP_BN)
+                     BURDEN_EXACTCMC, BURDEN_ALL, CODING_DOMINANT, CODING_RECESSIVE, KinshipInfo, KINSHIP_IBS, KINSHIP_BN,
+                     kinship_components, family_form)
 
 __all__ = ["Engine", "Group", "GeneResult", "Params", "Timing", "RvtError", "build_library", "library_path", "load_library",
            "TEST_SKAT", "TEST_SKATO", "TEST_CMC", "TEST_ZEGGINI", "TEST_ALL", "TEST_ANALYTICVT", "TRAIT_QUANTITATIVE",
            "TRAIT_BINARY", "MAX_INFLIGHT", "KbacResult", "DecomposeInfo", "VtPriceResult", "RareCoverResult", "MbResult",
            "BurdenMoreResult", "BurdenWaldFit", "BURDEN_CMCWALD", "BURDEN_ZEGGINIWALD", "BURDEN_FP", "BURDEN_EXACTCMC", "BURDEN_ALL",
-           "CODING_DOMINANT", "CODING_RECESSIVE", "KinshipInfo", "KINSHIP_IBS", "KINSHIP_BN"]
+           "CODING_DOMINANT", "CODING_RECESSIVE", "KinshipInfo", "KINSHIP_IBS", "KINSHIP_BN", "kinship_components", "family_form"]

@@ -326,12 +326,14 @@ rvt_ctx* GpuBroker::context(std::string* err) {
 
 rvt_ctx* GpuBroker::contextWithFamNull(const GeneData& gd, std::string* err) {
   if (!context(err)) return nullptr;
-  if (kinU != gd.kinshipU) {  // a new decomposition (autosomes vs X region in the reference): install it once
-    if (rvt_set_kinship(ctx, gd.N, gd.kinshipU, gd.kinshipS)) {
+  if (kinU != gd.kinshipIdentity()) {  // a new decomposition (autosomes vs X region in the reference): install it once
+    const GeneData::KinshipFamilies& kf = gd.kinshipFamilies;
+    if (gd.hasDenseKinship() ? rvt_set_kinship(ctx, gd.N, gd.kinshipU, gd.kinshipS)
+                             : rvt_set_kinship_families(ctx, gd.N, kf.nFam, kf.famPtr, kf.members, kf.blocks, kf.S)) {
       *err = rvt_last_error(ctx);
       return nullptr;
     }
-    kinU = gd.kinshipU;
+    kinU = gd.kinshipIdentity();
     haveFamNull = false;
   }
   if (!haveFamNull || gd.phenotypeUpdated || gd.covariateUpdated) {
@@ -544,7 +546,7 @@ int AnalyticVTTest::fit(GeneData* dc) {
     lastError = "Analytic VT test does not support binary outcomes. Results will be all NAs.";
     return -1;
   }
-  if (!dc->kinshipU || !dc->kinshipS) {  // model and data do not match (src/Model.h:2156-2160)
+  if (!dc->hasKinship()) {  // model and data do not match (src/Model.h:2156-2160)
     lastError = "Analytic VT test has internal error!";
     return -1;
   }
@@ -856,7 +858,7 @@ int FamSkatTest::fit(GeneData* dc) {
     lastError = "SKAT test (for related individuals) does not support binary outcomes. Results will be all NAs.";
     return -1;
   }
-  if (!dc->kinshipU || !dc->kinshipS) {  // src/Model.h:3079-3087
+  if (!dc->hasKinship()) {  // src/Model.h:3079-3087
     lastError = "SKAT test (for related individuals) cannot find kinship. Results will be all NAs.";
     return -1;
   }
@@ -887,7 +889,7 @@ int FamBurdenTest::fit(GeneData* dc) {
     lastError = "burden test (for related individuals) does not support binary outcomes. Results will be all NAs.";
     return -1;
   }
-  if (!dc->kinshipU || !dc->kinshipS) {
+  if (!dc->hasKinship()) {
     lastError = "burden test (for related individuals) cannot find kinship.";
     return -1;
   }
@@ -964,7 +966,7 @@ int MetaScoreTest::beginRow(const GeneData& dc) {
   return 0;
 }
 int MetaScoreTest::fit(GeneData* dc) {
-  useFamilyModel = dc->kinshipU != nullptr;  // dc->hasKinship(): MetaFamQtl / MetaFamBinary (src/Model.h:3398-3668)
+  useFamilyModel = dc->hasKinship();  // dc->hasKinship(): MetaFamQtl / MetaFamBinary (src/Model.h:3398-3668)
   if (beginRow(*dc)) return -1;
   if (dc->N == 0) return -1;
   if (sameSampleSize(*dc)) return -1;
@@ -1382,7 +1384,7 @@ rvt_ctx* SingleVariantFamilyTest::acquireContext(GeneData* dc) {
     lastError = "Single variant " + what + " does not support binary outcomes. Results will be all NAs.";
     return nullptr;
   }
-  if (!dc->kinshipU || !dc->kinshipS) {  // as FamSkatTest
+  if (!dc->hasKinship()) {  // as FamSkatTest
     lastError = "Single variant " + what + " cannot find kinship. Results will be all NAs.";
     return nullptr;
   }
@@ -1426,7 +1428,7 @@ SingleVariantFamilyGrammarGamma::~SingleVariantFamilyGrammarGamma() {
 rvt_ctx* SingleVariantFamilyGrammarGamma::acquireContext(GeneData* dc) {
   rvt_ctx* cx = SingleVariantFamilyTest::acquireContext(dc);
   if (!cx) return nullptr;
-  if (!haveNull || nullKinship != dc->kinshipU || dc->phenotypeUpdated || dc->covariateUpdated) {
+  if (!haveNull || nullKinship != dc->kinshipIdentity() || dc->phenotypeUpdated || dc->covariateUpdated) {
     rvt_grammar_null gn;
     haveNull = false;
     if (rvt_fit_grammar_null(cx, dc->N, 1 + dc->ncov, interceptAndCovariates(*dc).data(), dc->phenotype, &gn)) {
@@ -1434,7 +1436,7 @@ rvt_ctx* SingleVariantFamilyGrammarGamma::acquireContext(GeneData* dc) {
       return nullptr;
     }
     haveNull = true;
-    nullKinship = dc->kinshipU;
+    nullKinship = dc->kinshipIdentity();
   }
   return cx;
 }
@@ -1472,7 +1474,7 @@ int MetaCovTest::fit(GeneData* dc) {
     lastError = "Sample size changed at [ " + dc->site->get("CHROM") + ":" + dc->site->get("POS") + " ]";
     return -1;
   }
-  useFamilyModel = dc->kinshipU != nullptr;  // dc->hasKinship(): MetaCovFamQtl instead of MetaCovUnrelatedQtl
+  useFamilyModel = dc->hasKinship();  // dc->hasKinship(): MetaCovFamQtl instead of MetaCovUnrelatedQtl
   ctx = useFamilyModel ? GpuBroker::instance().contextWithFamNull(*dc, &lastError)
                        : GpuBroker::instance().contextWithNull(*dc, isBinaryOutcome(), &lastError);
   if (!ctx) return -1;
@@ -1680,7 +1682,7 @@ namespace {
 // why a coded model cannot take this site (empty: it can)
 std::string codedRefusal(const GeneData& dc, const std::string& modelName) {
   // the family score file's AF comes from the additive genotype (src/Model.h:3256-3258), which the recoded block does not hold
-  if (dc.kinshipU) return modelName + ": related samples (a kinship) are not supported by the dominant / recessive models";
+  if (dc.hasKinship()) return modelName + ": related samples (a kinship) are not supported by the dominant / recessive models";
   if (!dc.rawGenotype) return modelName + " needs the genotypes before imputation (GeneData::rawGenotype)";
   return "";
 }

@@ -69,6 +69,23 @@ struct GeneData {
   // Eigen::MatrixXf, i.e. float, column-major N x N and N x 1
   const float* kinshipU = nullptr;
   const float* kinshipS = nullptr;
+  // The same decomposition family by family, INSTEAD of the two dense matrices, for a pedigree kinship of separate families
+  // of at most 64 samples (the layout: rvt_set_kinship_families in rvtests_amd.h).  The reference has no such form — its
+  // DataConsolidator only ever holds the N x N matrices — so only a caller built on this library fills it.
+  struct KinshipFamilies {
+    int64_t nFam = 0;
+    const int64_t* famPtr = nullptr;   // nFam + 1
+    const int32_t* members = nullptr;  // N
+    const float* blocks = nullptr;     // every family's k x k block of eigenvectors, column-major, concatenated
+    const float* S = nullptr;          // N eigenvalues, family by family
+  } kinshipFamilies;
+  bool hasDenseKinship() const { return kinshipU && kinshipS; }
+  bool hasFamilyKinship() const {
+    return kinshipFamilies.nFam > 0 && kinshipFamilies.famPtr && kinshipFamilies.members && kinshipFamilies.blocks && kinshipFamilies.S;
+  }
+  bool hasKinship() const { return hasDenseKinship() || hasFamilyKinship(); }  // dc->hasKinship()
+  // what tells one installed decomposition from the next (the broker installs once per decomposition, by pointer identity)
+  const float* kinshipIdentity() const { return hasDenseKinship() ? kinshipU : hasFamilyKinship() ? kinshipFamilies.blocks : nullptr; }
   // MetaScoreTest: raw-genotype counters of the current site — all samples, cases, controls (binary traits only)
   SiteCounts counter, caseCounter, ctrlCounter;
   // FastMultipleTraitScoreTest (`--multiplePheno`): dc->getPhenotype() as the N x nPheno matrix it then is (column-major,
@@ -867,7 +884,7 @@ class SingleVariantScoreTest final : public SingleVariantBlockTest {
 
 // The single-variant tests for related samples (src/Model.h:525-805): FamScore "AF U.Stat V.Stat Pvalue" (rvt_score_block_fam),
 // FamLRT "AF NullLogLik AltLogLik Pvalue" (rvt_lrt_block_fam) and FamGrammarGamma "AF Beta BetaVar Pvalue"
-// (rvt_grammar_block).  The kinship is GeneData::kinshipU / kinshipS through the broker's install; a binary trait or a missing
+// (rvt_grammar_block).  The kinship is GeneData's (either form) through the broker's install; a binary trait or a missing
 // kinship fails every fit().  Like the reference's writeOutput these never clear their Result: a failed or monomorphic site
 // prints the values the previous row left (NA before the first fitted row).
 class SingleVariantFamilyTest : public SingleVariantBlockTest {

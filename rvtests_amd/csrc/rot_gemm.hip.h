@@ -481,6 +481,87 @@ static __global__ __launch_bounds__(256) void rot_sparse_kernel(const long long*
 }
 #endif  // RVT_K_FAM
 
+// ---- eigenvectors handed over family by family (rvt_set_kinship_families) ---------------------------------------------------
+// U is block diagonal under the permutation `members`: eigenpair e = fam_ptr[f] + j is column j of family f's k x k block
+// (k <= 64, column-major fp64 at vals + colptr[e], i.e. the column-compressed arrays with every entry of the block kept)
+// and touches the samples members[fam_ptr[f] .. fam_ptr[f] + k) only.  The installation sorts every family's members (and the
+// rows of its block with them) into ascending sample order, the order in which the gather over a dense installation's
+// column-compressed U (rot_sparse_kernel) adds the same products: the two agree bit for bit.
+//       out[e + t ld_dst] = sum_{r < k} vals[colptr[e] + r] * G[members[fam_ptr[f] + r] + t ld_src]
+// Workgroup (kRotFamRows = 256 threads) = one RUN of consecutive families (run_ptr, made at the installation: as many whole
+// families as fit kRotFamRows eigenpairs) x one tile of kRotFamCols columns; grid (runs, column tiles).  Thread t owns
+// eigenpair run_ptr[run] + t for every column of the tile:
+//   1. the tile's genotype values go to LDS once, g[col][t] = G[members[run_ptr[run] + t] + col ld_src] — the member index
+//      is read once per thread; families listed contiguously make this a coalesced copy, interleaved families (member r of
+//      family i at i + r n_fam) read k runs of consecutive doubles per wave, whole cache lines either way;
+//   2. the thread's column of U is read ONCE, eight entries at a time into registers (a thread's k doubles are contiguous;
+//      the threads of a run cover one contiguous stretch of vals), and every entry is used for all kRotFamCols columns;
+//   3. acc[col] = fma(u_r, g[col][row0 + r], acc[col]) for r = 0 .. k-1 in this order: one fp64 chain per output, no atomics,
+//      the same bits on every call.  The k threads of a family read the same LDS address (broadcast); neighbouring families
+//      read neighbouring doubles — at most 256 consecutive doubles per column, 64 banks of 8 bytes: no two addresses of a
+//      32-lane group 32 doubles apart unless the families are singletons next to a long one (2-way, rare);
+//   4. every output is written once, coalesced along e.
+// Traffic per column: 8 N bytes of G and 8 N bytes of output, plus U (8 sum k^2 bytes) and 12 N bytes of indices once per
+// column tile.  A family of one is the scaled copy it should be (k = 1).  LDS: 16 x 256 doubles = 32 KB, 5 workgroups per CU.
+constexpr int kRotFamRows = 256, kRotFamCols = 16;
+#if !defined(RVT_K_SPLIT) || defined(RVT_K_FAM)
+static __global__ __launch_bounds__(kRotFamRows) void rot_fam_kernel(
+    const int* __restrict__ run_ptr, const int* __restrict__ pair_fam, const long long* __restrict__ fam_ptr,
+    const int* __restrict__ members, const long long* __restrict__ colptr, const double* __restrict__ vals,
+    const double* __restrict__ G, long long ld_src, int ncols, double* __restrict__ out, long long ld_dst) {
+  __shared__ double g[kRotFamCols][kRotFamRows];
+  const int e0 = run_ptr[blockIdx.x], rows = run_ptr[blockIdx.x + 1] - e0;  // rows <= kRotFamRows
+  const int t = threadIdx.x, col0 = blockIdx.y * kRotFamCols;
+  const int nc = min(kRotFamCols, ncols - col0);
+  const bool active = t < rows;
+  int k = 0, row0 = 0;
+  const double* u = vals;
+  if (active) {
+    const int e = e0 + t, f = pair_fam[e];
+    const long long fs = fam_ptr[f];
+    k = (int)(fam_ptr[f + 1] - fs);
+    row0 = (int)(fs - e0);  // the family's first row inside the run
+    u = vals + colptr[e];
+    const double* src = G + members[e] + (long long)col0 * ld_src;
+#pragma unroll
+    for (int c = 0; c < kRotFamCols; ++c)
+      if (c < nc) g[c][t] = src[(long long)c * ld_src];
+  }
+  __syncthreads();
+  if (!active) return;
+  double acc[kRotFamCols];
+#pragma unroll
+  for (int c = 0; c < kRotFamCols; ++c) acc[c] = 0.0;
+  for (int r0 = 0; r0 < k; r0 += 8) {
+    double ur[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ur[i] = (r0 + i < k) ? u[r0 + i] : 0.0;
+    const int nr = min(8, k - r0);
+#pragma unroll
+    for (int c = 0; c < kRotFamCols; ++c) {
+      const double* gc = &g[c][row0 + r0];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (i < nr) acc[c] = fma(ur[i], gc[i], acc[c]);
+    }
+  }
+  double* dst = out + (e0 + t) + (long long)col0 * ld_dst;
+#pragma unroll
+  for (int c = 0; c < kRotFamCols; ++c)
+    if (c < nc) dst[(long long)c * ld_dst] = acc[c];
+}
+
+// U'1 of the family form: u1[e] = the sum of eigenpair e's column, in fp64 in the block's row order; any thread count
+static __global__ void rot_fam_colsum_kernel(const long long* __restrict__ colptr, const double* __restrict__ vals, long long n,
+                                             double* __restrict__ u1) {
+  const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  double s = 0.0;
+  for (long long p = colptr[e]; p < colptr[e + 1]; ++p) s += vals[p];
+  u1[e] = s;
+}
+#endif  // RVT_K_FAM
+
 // per-column max |x| of a double matrix (column-major, ld)
 #if !defined(RVT_K_SPLIT) || defined(RVT_K_FAM)
 static __global__ void rot_colmax_kernel(const double* __restrict__ src, long long n, long long ld, double* __restrict__ out) {

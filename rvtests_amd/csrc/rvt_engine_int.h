@@ -241,6 +241,15 @@ struct rvt_ctx {
   DevBuf<double> d_csr_vals;
   DevBuf<int> d_csc_rows;
   DevBuf<double> d_csc_vals;
+  // family form (rvt_set_kinship_families): d_csc_* then hold every entry of every family's block (eigenpair fam_ptr[f] + j =
+  // column j of block f, rows = the family's members in ascending sample order), d_Uq / d_uq_range stay null, and the rotation
+  // takes rot_fam_kernel over the descriptors below; all null after a dense installation
+  DevBuf<long long> d_fam_ptr;  // n_fam + 1
+  DevBuf<int> d_fam_members;    // N: the permutation `members`, ascending inside every family
+  DevBuf<int> d_fam_of;         // N: family of every eigenpair
+  DevBuf<int> d_fam_run;        // fam_runs + 1: first eigenpair of every run of whole families (<= kRotFamRows eigenpairs)
+  int64_t fam_count = 0;
+  int fam_runs = 0;
   DevBuf<int2> d_uq_range;  // per 256-row panel of the planes: K chunks [x, y) that hold its non-zeros; null = dense U
   double uq_visit = 1.0;       // fraction of the K chunks the rotation visits (1 = dense)
   size_t uq_plane = 0;

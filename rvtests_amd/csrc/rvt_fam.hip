@@ -14,7 +14,88 @@ static void free_csc(rvt_ctx* c) {  // the column-compressed form of U
   c->d_csc_vals.reset();
 }
 
+static void clear_kinship(rvt_ctx* c) {  // what both forms of the installation start from
+  c->d_S.reset();
+  c->d_u1.reset();
+  c->d_Uq.reset();
+  c->d_uq_range.reset();
+  free_csc(c);
+  c->d_csr_ptr.reset();
+  c->d_csr_cols.reset();
+  c->d_csr_vals.reset();
+  c->d_fam_ptr.reset();
+  c->d_fam_members.reset();
+  c->d_fam_of.reset();
+  c->d_fam_run.reset();
+  c->fam_count = 0;
+  c->fam_runs = 0;
+  c->uq_visit = 1.0;
+  c->have_kin = c->have_fam = c->have_grammar = false;
+}
+
+// connected components of a list of pairs over n items (union by size, path halving).  cap > 0: stop as soon as a
+// component outgrows it (false).  Components in the order of their first member, members ascending.
+namespace {
+struct Components {
+  std::vector<int> parent, csize;
+  explicit Components(int64_t n) : parent((size_t)n), csize((size_t)n, 1) {
+    for (int64_t i = 0; i < n; ++i) parent[i] = (int)i;
+  }
+  int find(int x) {
+    while (parent[x] != x) {
+      parent[x] = parent[parent[x]];
+      x = parent[x];
+    }
+    return x;
+  }
+  bool join(int p, int q, int cap) {
+    int a = find(p), b = find(q);
+    if (a == b) return true;
+    if (csize[a] < csize[b]) std::swap(a, b);
+    parent[b] = a;
+    csize[a] += csize[b];
+    return cap <= 0 || csize[a] <= cap;
+  }
+  void list(std::vector<int64_t>* fam_ptr, std::vector<int>* members) {
+    const int64_t n = (int64_t)parent.size();
+    std::vector<int> first_of((size_t)n, -1), fam_of((size_t)n);
+    std::vector<int64_t> count;
+    for (int64_t i = 0; i < n; ++i) {
+      const int r = find((int)i);
+      if (first_of[r] < 0) {
+        first_of[r] = (int)count.size();
+        count.push_back(0);
+      }
+      fam_of[i] = first_of[r];
+      ++count[first_of[r]];
+    }
+    fam_ptr->assign(count.size() + 1, 0);
+    for (size_t f = 0; f < count.size(); ++f) (*fam_ptr)[f + 1] = (*fam_ptr)[f] + count[f];
+    std::vector<int64_t> fill(fam_ptr->begin(), fam_ptr->end() - 1);
+    members->resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) (*members)[fill[fam_of[i]]++] = (int)i;  // i ascending: members ascending per family
+  }
+};
+}  // namespace
+
 extern "C" {
+
+int rvt_kinship_components(int64_t N, int64_t n_pairs, const int32_t* pi, const int32_t* pj, int64_t* n_fam,
+                           int64_t* fam_ptr, int32_t* members) {
+  if (N < 1 || N > INT32_MAX || n_pairs < 0 || (n_pairs && (!pi || !pj)) || !n_fam || !fam_ptr || !members) return RVT_E_INVALID;
+  for (int64_t e = 0; e < n_pairs; ++e)
+    if (pi[e] < 0 || pi[e] >= N || pj[e] < 0 || pj[e] >= N) return RVT_E_INVALID;
+  Components cc(N);
+  for (int64_t e = 0; e < n_pairs; ++e) cc.join(pi[e], pj[e], 0);
+  std::vector<int64_t> fp;
+  std::vector<int> mem;
+  cc.list(&fp, &mem);
+  *n_fam = (int64_t)fp.size() - 1;
+  std::copy(fp.begin(), fp.end(), fam_ptr);
+  std::copy(mem.begin(), mem.end(), members);
+  return RVT_OK;
+}
+
 
 int ensure_fam_cols(rvt_ctx* c, size_t T, int64_t ld) {
   // (the capacity is columns OF THIS LEADING DIMENSION: a context whose null model was replaced by one with more samples
@@ -38,16 +119,7 @@ int rvt_set_kinship(rvt_ctx* c, int64_t N, const float* U, const float* S) {
   hipSetDevice(c->device);
   int rc = rvt_sync(c);
   if (rc) return rc;
-  c->d_S.reset();
-  c->d_u1.reset();
-  c->d_Uq.reset();
-  c->d_uq_range.reset();
-  free_csc(c);
-  c->d_csr_ptr.reset();
-  c->d_csr_cols.reset();
-  c->d_csr_vals.reset();
-  c->uq_visit = 1.0;
-  c->have_kin = c->have_fam = c->have_grammar = false;
+  clear_kinship(c);
   HIP_TRY(c, c->d_S.alloc(sizeof(double) * N));
   HIP_TRY(c, c->d_u1.alloc(sizeof(double) * N));
   // U -> fixed-point digit planes (rot_gemm.hip.h): 40 fractional bits.  Eigenvectors have |u| <= 1; six digits in [-64, 63]
@@ -195,110 +267,261 @@ int rvt_kinship_structure(rvt_ctx* c, double* visited_fraction) {
   return RVT_OK;
 }
 
+// ---- the family form: U as one k x k block per family, never N x N ----------------------------------------------------------
+// The descriptors of the family form as the caller hands them over; blk_off[f] = where family f's block starts in `blocks`.
+static int check_families(rvt_ctx* c, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                          std::vector<long long>* blk_off) {
+  if (!fam_ptr || !members || N < 2 || N > INT32_MAX || n_fam < 1 || n_fam > N) return fail(c, RVT_E_INVALID, "bad kinship families");
+  if (fam_ptr[0] != 0) return fail(c, RVT_E_INVALID, "kinship families: fam_ptr[0] is %lld, not 0", (long long)fam_ptr[0]);
+  blk_off->assign((size_t)n_fam + 1, 0);
+  for (int64_t f = 0; f < n_fam; ++f) {
+    const int64_t k = fam_ptr[f + 1] - fam_ptr[f];
+    if (k < 1) return fail(c, RVT_E_INVALID, "kinship families: family %lld is empty (fam_ptr must increase)", (long long)f);
+    if (k > kJacP)
+      return fail(c, RVT_E_INVALID, "kinship families: family %lld has %lld members (at most %d)", (long long)f, (long long)k, kJacP);
+    if (fam_ptr[f + 1] > N)
+      return fail(c, RVT_E_INVALID, "kinship families: family %lld ends at %lld, past N = %lld", (long long)f,
+                  (long long)fam_ptr[f + 1], (long long)N);
+    (*blk_off)[f + 1] = (*blk_off)[f] + k * k;
+  }
+  if (fam_ptr[n_fam] != N)
+    return fail(c, RVT_E_INVALID, "kinship families: fam_ptr[n_fam] is %lld, not N = %lld", (long long)fam_ptr[n_fam], (long long)N);
+  std::vector<bool> seen((size_t)N, false);
+  for (int64_t i = 0; i < N; ++i) {
+    const int32_t m = members[i];
+    if (m < 0 || m >= N) return fail(c, RVT_E_INVALID, "kinship families: members[%lld] = %d is not a sample index", (long long)i, m);
+    if (seen[m]) return fail(c, RVT_E_INVALID, "kinship families: members[%lld] = %d is listed twice", (long long)i, m);
+    seen[m] = true;
+  }
+  return RVT_OK;
+}
+
+// first non-finite entry of the blocks: RVT_E_INVALID naming its family
+static int check_blocks_finite(rvt_ctx* c, int64_t n_fam, const int64_t* fam_ptr, const std::vector<long long>& blk_off,
+                               const float* blocks, const char* what) {
+  for (int64_t f = 0; f < n_fam; ++f) {
+    const int k = (int)(fam_ptr[f + 1] - fam_ptr[f]);
+    const float* b = blocks + blk_off[f];
+    for (int e = 0; e < k * k; ++e)
+      if (!std::isfinite(b[e]))
+        return fail(c, RVT_E_INVALID, "kinship families: %s of family %lld holds a non-finite entry (row %d, column %d)", what,
+                    (long long)f, e % k, e / k);
+  }
+  return RVT_OK;
+}
+
+// the installation itself, arguments checked: column-compressed U straight from the blocks (every entry kept, zeros too),
+// U'1 from them in fp64 on the device, the descriptors and the runs of rot_fam_kernel
+static int install_families(rvt_ctx* c, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                            const std::vector<long long>& blk_off, const float* blocks, const float* S) {
+  hipStream_t st = c->stream;
+  clear_kinship(c);
+  const size_t total = (size_t)blk_off[n_fam];
+  std::vector<long long> csc_ptr((size_t)N + 1), fp(fam_ptr, fam_ptr + n_fam + 1);
+  std::vector<int> rows(total), fam_of((size_t)N), run, sorted((size_t)N);
+  std::vector<float> vals(total);
+  for (int64_t f = 0; f < n_fam; ++f) {
+    const int64_t fs = fam_ptr[f];
+    const int k = (int)(fam_ptr[f + 1] - fs);
+    if (run.empty() || fam_ptr[f + 1] - run.back() > kRotFamRows) run.push_back((int)fs);
+    // the rows of a block go to ascending sample order: every sum over a family then runs in the order in which the dense
+    // installation's column-compressed form (rot_nnz_fill_kernel) would run it
+    int perm[kJacP];
+    for (int r = 0; r < k; ++r) perm[r] = r;
+    std::sort(perm, perm + k, [&](int a, int b) { return members[fs + a] < members[fs + b]; });
+    for (int r = 0; r < k; ++r) sorted[fs + r] = members[fs + perm[r]];
+    for (int j = 0; j < k; ++j) {
+      csc_ptr[fs + j] = blk_off[f] + (long long)j * k;
+      fam_of[fs + j] = (int)f;
+      int* rw = rows.data() + blk_off[f] + (size_t)j * k;
+      float* vw = vals.data() + blk_off[f] + (size_t)j * k;
+      const float* bw = blocks + blk_off[f] + (size_t)j * k;
+      for (int r = 0; r < k; ++r) {
+        rw[r] = sorted[fs + r];
+        vw[r] = bw[perm[r]];
+      }
+    }
+  }
+  csc_ptr[N] = (long long)total;
+  run.push_back((int)N);
+  DevBuf<float> d_tmp;
+  HIP_TRY(c, c->d_S.alloc(sizeof(double) * N));
+  HIP_TRY(c, c->d_u1.alloc(sizeof(double) * N));
+  HIP_TRY(c, c->d_csc_ptr.alloc(sizeof(long long) * ((size_t)N + 1)));
+  HIP_TRY(c, c->d_csc_rows.alloc(sizeof(int) * total));
+  HIP_TRY(c, c->d_csc_vals.alloc(sizeof(double) * total));
+  HIP_TRY(c, c->d_fam_ptr.alloc(sizeof(long long) * fp.size()));
+  HIP_TRY(c, c->d_fam_members.alloc(sizeof(int) * (size_t)N));
+  HIP_TRY(c, c->d_fam_of.alloc(sizeof(int) * (size_t)N));
+  HIP_TRY(c, c->d_fam_run.alloc(sizeof(int) * run.size()));
+  HIP_TRY(c, d_tmp.alloc(sizeof(float) * total));
+  HIP_TRY(c, hipMemcpyAsync(c->d_csc_ptr, csc_ptr.data(), sizeof(long long) * csc_ptr.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(c->d_csc_rows, rows.data(), sizeof(int) * total, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(c->d_fam_ptr, fp.data(), sizeof(long long) * fp.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(c->d_fam_members, sorted.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(c->d_fam_of, fam_of.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(c->d_fam_run, run.data(), sizeof(int) * run.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_tmp, vals.data(), sizeof(float) * total, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(cvt_f32_f64_kernel, dim3(1024), dim3(256), 0, st, d_tmp, c->d_csc_vals, total);
+  hipLaunchKernelGGL(rot_fam_colsum_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, c->d_csc_ptr, c->d_csc_vals,
+                     (long long)N, c->d_u1);
+  HIP_TRY(c, hipGetLastError());
+  c->h_S.resize(N);
+  for (int64_t i = 0; i < N; ++i) c->h_S[i] = (double)S[i];
+  c->h_u1.resize(N);
+  HIP_TRY(c, hipMemcpyAsync(c->d_S, c->h_S.data(), sizeof(double) * N, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(c->h_u1.data(), c->d_u1, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));  // (the host vectors above go out of scope)
+  c->uq_plane = 0;
+  c->uq_ldk = c->uq_rows_pad = 0;
+  c->uq_visit = (double)total / ((double)N * (double)N);
+  c->fam_count = n_fam;
+  c->fam_runs = (int)run.size() - 1;
+  c->kin_N = N;
+  c->have_kin = true;
+  return RVT_OK;
+}
+
+int rvt_set_kinship_families(rvt_ctx* c, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                             const float* U_blocks, const float* S) {
+  if (!c || !U_blocks || !S) return fail(c, RVT_E_INVALID, "bad kinship families");
+  std::vector<long long> blk_off;
+  int rc = check_families(c, N, n_fam, fam_ptr, members, &blk_off);
+  if (rc) return rc;
+  rc = check_blocks_finite(c, n_fam, fam_ptr, blk_off, U_blocks, "the eigenvector block");
+  if (rc) return rc;
+  for (int64_t i = 0; i < N; ++i)
+    if (!std::isfinite(S[i])) return fail(c, RVT_E_INVALID, "kinship families: eigenvalue S[%lld] is not finite", (long long)i);
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  return install_families(c, N, n_fam, fam_ptr, members, blk_off, U_blocks, S);
+}
+
 // Family-wise form of rvt_kinship_decompose.  When the sparsity pattern of K splits the samples into groups that do not
 // interact (the connected components of its non-zeros: families, in whatever order the samples are listed) and none is
 // larger than 64, the eigenproblem is that of its blocks: families are packed into 64 x 64 tiles (block diagonal inside a
 // tile, distinct negative pads on the rest of the diagonal: zero off-diagonals are never rotated, so nothing mixes),
 // every tile is diagonalised by the two-sided cyclic Jacobi kernel of the dense iteration (jac_small_eig_kernel) and the
 // eigenpairs are merged in ascending order.  *done = false: K is not of that form, take the dense iteration.
+//
+// The part both entries share — rvt_kinship_decompose, which finds the families in a dense K, and
+// rvt_kinship_decompose_families, which is handed them with their blocks: FamTiles packs consecutive families into tiles,
+// run() diagonalises the tiles [t0, t1) and checks the residual of every eigenpair.  kval(f, r, q): the entry of K between
+// members r and q of family f.
+namespace {
+struct FamTiles {
+  const std::vector<int64_t>& fam_ptr;
+  std::vector<int64_t> tile_fam;  // first family of every tile, nt + 1 entries
+  struct Bufs {
+    DevBuf<double> A, R, lam;
+    DevBuf<unsigned long long> maxcos;
+  } b;
+  std::vector<double> A, R, lam;  // host copies of the tiles of the last run(): input, eigenvectors (row-major), eigenvalues
+  double worst = 0.0;             // largest || K u - lambda u || so far
+
+  explicit FamTiles(const std::vector<int64_t>& fp) : fam_ptr(fp) {
+    int64_t rows = 0;
+    for (size_t f = 0; f + 1 < fp.size(); ++f) {
+      const int64_t k = fp[f + 1] - fp[f];
+      if (tile_fam.empty() || rows + k > kJacP) {
+        tile_fam.push_back((int64_t)f);
+        rows = 0;
+      }
+      rows += k;
+    }
+    tile_fam.push_back((int64_t)fp.size() - 1);
+  }
+  size_t tiles() const { return tile_fam.size() - 1; }
+  int64_t first_row(size_t t) const { return fam_ptr[tile_fam[t]]; }  // position in `members` of the tile's first row
+  int len(size_t t) const { return (int)(fam_ptr[tile_fam[t + 1]] - fam_ptr[tile_fam[t]]); }
+
+  int run(rvt_ctx* c, size_t t0, size_t t1, const std::function<double(int64_t, int, int)>& kval, double mu) {
+    hipStream_t st = c->stream;
+    const size_t n = t1 - t0, tile = (size_t)kJacP * kJacP, tile_bytes = sizeof(double) * tile;
+    A.assign(n * tile, 0.0);
+    for (size_t t = t0; t < t1; ++t) {
+      double* a = A.data() + (t - t0) * tile;
+      for (int64_t f = tile_fam[t]; f < tile_fam[t + 1]; ++f) {  // block diagonal inside the tile: K is zero between families
+        const int k = (int)(fam_ptr[f + 1] - fam_ptr[f]), o = (int)(fam_ptr[f] - first_row(t));
+        for (int q = 0; q < k; ++q)
+          for (int r = 0; r < k; ++r) a[(size_t)(o + r) * kJacP + o + q] = kval(f, r, q);
+      }
+      for (int r = len(t); r < kJacP; ++r) a[(size_t)r * kJacP + r] = -mu * (1.0 + (double)r / kJacP);  // pads: last, apart
+    }
+    HIP_TRY(c, b.A.grow(tile_bytes * n, tile_bytes * n));
+    HIP_TRY(c, b.R.grow(tile_bytes * n, tile_bytes * n));
+    HIP_TRY(c, b.lam.grow(sizeof(double) * kJacP * n, sizeof(double) * kJacP * n));
+    HIP_TRY(c, b.maxcos.grow(sizeof(unsigned long long), sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemsetAsync(b.maxcos, 0, sizeof(unsigned long long), st));
+    HIP_TRY(c, hipMemcpyAsync(b.A, A.data(), tile_bytes * n, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(jac_small_eig_kernel, dim3((unsigned)n), dim3(256), 0, st, b.A, 1, 1e-14, b.R, b.maxcos, 1, b.lam);
+    HIP_TRY(c, hipGetLastError());
+    R.resize(n * tile);
+    lam.resize(n * (size_t)kJacP);
+    HIP_TRY(c, hipMemcpyAsync(R.data(), b.R, tile_bytes * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(lam.data(), b.lam, sizeof(double) * kJacP * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    // the first len(t) output columns of a tile are its own eigenpairs (decreasing; the pads are below all of them)
+    for (size_t t = t0; t < t1; ++t) {
+      const double* a = A.data() + (t - t0) * tile;
+      const double* r = R.data() + (t - t0) * tile;
+      const int tl = len(t);
+      for (int q = 0; q < tl; ++q) {
+        const double l = lam[(t - t0) * kJacP + q];
+        double res2 = 0.0;  // || K u - lambda u || inside the tile (K is zero outside)
+        for (int i = 0; i < tl; ++i) {
+          double s = 0.0;
+          for (int k = 0; k < tl; ++k) s += a[(size_t)i * kJacP + k] * r[(size_t)k * kJacP + q];
+          s -= l * r[(size_t)i * kJacP + q];
+          res2 += s * s;
+        }
+        worst = std::max(worst, std::sqrt(res2));
+      }
+    }
+    return RVT_OK;
+  }
+};
+}  // namespace
+
 static int decompose_by_family(rvt_ctx* c, int64_t N, const float* K,
                                const std::vector<std::vector<std::pair<int, int>>>& edges, double mu, int64_t np,
                                float* U_out, float* S_out, int install, rvt_decompose_info* info, bool* done) {
   *done = false;
   // families = connected components of the sparsity pattern (union-find over the off-diagonal non-zeros)
-  std::vector<int> parent((size_t)N), csize((size_t)N, 1);
-  for (int64_t i = 0; i < N; ++i) parent[i] = (int)i;
-  auto find = [&](int x) {
-    while (parent[x] != x) {
-      parent[x] = parent[parent[x]];
-      x = parent[x];
-    }
-    return x;
-  };
+  Components cc(N);
   for (const auto& ed : edges)
-    for (const auto& e : ed) {
-      int a = find(e.first), b = find(e.second);
-      if (a == b) continue;
-      if (csize[a] < csize[b]) std::swap(a, b);
-      parent[b] = a;
-      csize[a] += csize[b];
-      if (csize[a] > kJacP) return RVT_OK;  // a family larger than a tile: the dense iteration
-    }
+    for (const auto& e : ed)
+      if (!cc.join(e.first, e.second, kJacP)) return RVT_OK;  // a family larger than a tile: the dense iteration
   // members of every family in ascending order; families in the order of their first member
-  std::vector<int> first_of((size_t)N, -1);
-  std::vector<std::vector<int>> fam;
-  for (int64_t i = 0; i < N; ++i) {
-    const int r = find((int)i);
-    if (first_of[r] < 0) {
-      first_of[r] = (int)fam.size();
-      fam.emplace_back();
-    }
-    fam[first_of[r]].push_back((int)i);
-  }
-  if (fam.size() < 2) return RVT_OK;
-  // tiles of consecutive families: trow[t] = the sample index behind every row of the tile
-  std::vector<std::vector<int>> trow;
-  for (const auto& f : fam) {
-    if (!trow.empty() && trow.back().size() + f.size() <= (size_t)kJacP)
-      trow.back().insert(trow.back().end(), f.begin(), f.end());
-    else
-      trow.push_back(f);
-  }
+  std::vector<int64_t> fam_ptr;
+  std::vector<int> members;
+  cc.list(&fam_ptr, &members);
+  if (fam_ptr.size() < 3) return RVT_OK;
+  // tiles of consecutive families: the sample index behind row r of tile t is members[first_row(t) + r]
+  FamTiles ft(fam_ptr);
+  const size_t nt = ft.tiles();
   std::vector<int> tlen;
-  for (const auto& r : trow) tlen.push_back((int)r.size());
-  const size_t nt = trow.size();
-  std::vector<double> A(nt * (size_t)kJacP * kJacP, 0.0);
-  for (size_t t = 0; t < nt; ++t) {
-    double* a = A.data() + t * (size_t)kJacP * kJacP;
-    const std::vector<int>& rows = trow[t];
-    for (int q = 0; q < tlen[t]; ++q)
-      for (int r = 0; r < tlen[t]; ++r) a[(size_t)r * kJacP + q] = (double)K[(size_t)rows[r] + (size_t)rows[q] * N];
-    for (int r = tlen[t]; r < kJacP; ++r) a[(size_t)r * kJacP + r] = -mu * (1.0 + (double)r / kJacP);  // pads: last, apart
-  }
+  for (size_t t = 0; t < nt; ++t) tlen.push_back(ft.len(t));
+  int rc = ft.run(c, 0, nt, [&](int64_t f, int r, int q) {
+    const int* m = members.data() + fam_ptr[f];
+    return (double)K[(size_t)m[r] + (size_t)m[q] * N];
+  }, mu);
+  if (rc) return rc;
   hipStream_t st = c->stream;
   struct Bufs {
-    DevBuf<double> A, R, lam;
-    DevBuf<unsigned long long> maxcos;
     DevBuf<float> dU;
     DevBuf<int> meta;
   } b;
-  const size_t tile_bytes = sizeof(double) * (size_t)kJacP * kJacP;
-  HIP_TRY(c, b.A.alloc(tile_bytes * nt));
-  HIP_TRY(c, b.R.alloc(tile_bytes * nt));
-  HIP_TRY(c, b.lam.alloc(sizeof(double) * kJacP * nt));
-  HIP_TRY(c, b.maxcos.alloc(sizeof(unsigned long long)));
-  HIP_TRY(c, hipMemsetAsync(b.maxcos, 0, sizeof(unsigned long long), st));
-  HIP_TRY(c, hipMemcpyAsync(b.A, A.data(), tile_bytes * nt, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(jac_small_eig_kernel, dim3((unsigned)nt), dim3(256), 0, st, b.A, 1, 1e-14, b.R, b.maxcos, 1, b.lam);
-  HIP_TRY(c, hipGetLastError());
-  std::vector<double> R(nt * (size_t)kJacP * kJacP), lam(nt * (size_t)kJacP);
-  HIP_TRY(c, hipMemcpyAsync(R.data(), b.R, tile_bytes * nt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, hipMemcpyAsync(lam.data(), b.lam, sizeof(double) * kJacP * nt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, sync_stream(st));
-  // the first tlen[t] output columns of a tile are its own eigenpairs (decreasing; the pads are below all of them)
   struct Pair {
     double lam;
     int tile, col;
   };
   std::vector<Pair> pairs;
   pairs.reserve((size_t)N);
-  double worst = 0.0;
-  for (size_t t = 0; t < nt; ++t) {
-    const double* a = A.data() + t * (size_t)kJacP * kJacP;
-    const double* r = R.data() + t * (size_t)kJacP * kJacP;
-    for (int q = 0; q < tlen[t]; ++q) {
-      const double l = lam[t * kJacP + q];
-      pairs.push_back({l, (int)t, q});
-      double res2 = 0.0;  // || K u - lambda u || inside the tile (K is zero outside)
-      for (int i = 0; i < tlen[t]; ++i) {
-        double s = 0.0;
-        for (int k = 0; k < tlen[t]; ++k) s += a[(size_t)i * kJacP + k] * r[(size_t)k * kJacP + q];
-        s -= l * r[(size_t)i * kJacP + q];
-        res2 += s * s;
-      }
-      worst = std::max(worst, std::sqrt(res2));
-    }
-  }
+  for (size_t t = 0; t < nt; ++t)
+    for (int q = 0; q < tlen[t]; ++q) pairs.push_back({ft.lam[t * kJacP + q], (int)t, q});
+  const double worst = ft.worst;
   if ((int64_t)pairs.size() != N) return fail(c, RVT_E_STATE, "family-wise decomposition lost eigenpairs");
   // the 30 cyclic sweeps of jac_small_eig_kernel converge for every family tile seen so far; should one not have, the
   // dense iteration (which checks its own convergence and residuals) takes the matrix instead
@@ -313,13 +536,13 @@ static int decompose_by_family(rvt_ctx* c, int64_t N, const float* K,
     meta[2 * (size_t)N + k] = tlen[pairs[k].tile];
   }
   for (size_t t = 0; t < nt; ++t)
-    for (int r = 0; r < tlen[t]; ++r) meta[3 * (size_t)N + t * kJacP + r] = trow[t][r];
+    for (int r = 0; r < tlen[t]; ++r) meta[3 * (size_t)N + t * kJacP + r] = members[ft.first_row(t) + r];
   if (U_out || install) {
     HIP_TRY(c, b.dU.alloc(sizeof(float) * (size_t)N * (size_t)N));
     HIP_TRY(c, hipMemsetAsync(b.dU, 0, sizeof(float) * (size_t)N * (size_t)N, st));
     HIP_TRY(c, b.meta.alloc(sizeof(int) * meta.size()));
     HIP_TRY(c, hipMemcpyAsync(b.meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(jac_scatter_blocks_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, b.R, b.meta,
+    hipLaunchKernelGGL(jac_scatter_blocks_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, ft.b.R, b.meta,
                        b.meta + N, b.meta + 2 * N, b.meta + 3 * N, (long long)N, b.dU);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, sync_stream(st));
@@ -743,6 +966,92 @@ int rvt_kinship_decompose(rvt_ctx* c, int64_t N, const float* K, float* U_out, f
   return RVT_OK;
 }
 
+// The family-wise decomposition fed from blocks: the tiles of decompose_by_family (FamTiles), a bounded number at a time, the
+// eigenvectors written back as blocks and installed through the family form.  Nothing of order N^2 exists at any point.
+int rvt_kinship_decompose_families(rvt_ctx* c, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                                   const float* K_blocks, float* U_blocks_out, float* S_out, int install,
+                                   rvt_decompose_info* info) {
+  if (!c || !K_blocks) return fail(c, RVT_E_INVALID, "bad kinship families");
+  std::vector<long long> blk_off;
+  int rc = check_families(c, N, n_fam, fam_ptr, members, &blk_off);
+  if (rc) return rc;
+  rc = check_blocks_finite(c, n_fam, fam_ptr, blk_off, K_blocks, "the kinship block");
+  if (rc) return rc;
+  double mu = 0.0;  // 4 x the largest absolute row sum, as rvt_kinship_decompose scales its pads and its residual bar
+  for (int64_t f = 0; f < n_fam; ++f) {
+    const int k = (int)(fam_ptr[f + 1] - fam_ptr[f]);
+    const float* b = K_blocks + blk_off[f];
+    for (int r = 0; r < k; ++r) {
+      double s = 0.0;
+      for (int q = 0; q < k; ++q) {
+        if (b[r + (size_t)q * k] != b[q + (size_t)r * k])
+          return fail(c, RVT_E_INVALID, "kinship families: the kinship block of family %lld is not symmetric", (long long)f);
+        s += std::fabs((double)b[r + (size_t)q * k]);
+      }
+      mu = std::max(mu, s);
+    }
+  }
+  mu = 4.0 * std::max(mu, 1e-300);
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  const std::vector<int64_t> fp(fam_ptr, fam_ptr + n_fam + 1);
+  FamTiles ft(fp);
+  const bool want_u = U_blocks_out || install;
+  std::vector<float> Ub(want_u && !U_blocks_out ? (size_t)blk_off[n_fam] : 0), Sb(S_out ? 0 : (size_t)N);
+  float* U = U_blocks_out ? U_blocks_out : Ub.data();
+  float* S = S_out ? S_out : Sb.data();
+  const auto kval = [&](int64_t f, int r, int q) {
+    return (double)K_blocks[blk_off[f] + r + (size_t)q * (size_t)(fp[f + 1] - fp[f])];
+  };
+  constexpr size_t kChunk = 2048;  // tiles per pass: 64 MB of tiles each way
+  std::vector<int> cols;
+  for (size_t t0 = 0; t0 < ft.tiles(); t0 += kChunk) {
+    const size_t t1 = std::min(ft.tiles(), t0 + kChunk);
+    rc = ft.run(c, t0, t1, kval, mu);
+    if (rc) return rc;
+    for (size_t t = t0; t < t1; ++t) {
+      const double* r = ft.R.data() + (t - t0) * (size_t)kJacP * kJacP;
+      const double* lam = ft.lam.data() + (t - t0) * (size_t)kJacP;
+      const int tl = ft.len(t);
+      for (int64_t f = ft.tile_fam[t]; f < ft.tile_fam[t + 1]; ++f) {
+        // the family's eigenpairs among the tile's: the columns whose largest entry lies in the family's rows (zero
+        // off-diagonals are never rotated, so a column is non-zero inside one family only)
+        const int k = (int)(fp[f + 1] - fp[f]), o = (int)(fp[f] - ft.first_row(t));
+        cols.clear();
+        for (int q = 0; q < tl; ++q) {
+          int best = 0;
+          for (int i = 1; i < tl; ++i)
+            if (std::fabs(r[(size_t)i * kJacP + q]) > std::fabs(r[(size_t)best * kJacP + q])) best = i;
+          if (best >= o && best < o + k) cols.push_back(q);
+        }
+        if ((int)cols.size() != k)
+          return fail(c, RVT_E_STATE, "family-wise decomposition: family %lld got %zu of its %d eigenpairs", (long long)f,
+                      cols.size(), k);
+        std::stable_sort(cols.begin(), cols.end(), [&](int x, int y) { return lam[x] < lam[y]; });  // ascending
+        for (int j = 0; j < k; ++j) {
+          S[fp[f] + j] = (float)lam[cols[j]];
+          if (want_u)
+            for (int i = 0; i < k; ++i) U[blk_off[f] + i + (size_t)j * k] = (float)r[(size_t)(o + i) * kJacP + cols[j]];
+        }
+      }
+    }
+  }
+  if (ft.worst > 1e-9 * mu)
+    return fail(c, RVT_E_INVALID, "family-wise kinship decomposition did not converge: residual %.3g against %.3g", ft.worst,
+                1e-9 * mu);
+  if (info) {
+    info->sweeps = 0;  // no block sweeps: every family is an eigenproblem of its own
+    info->max_cosine = 0.0;
+    info->padded_order = (N + kJacP - 1) / kJacP * kJacP;
+    info->shift = 0.0;
+    info->max_residual = ft.worst;
+  }
+  if (!install) return RVT_OK;
+  ft.b = FamTiles::Bufs();  // (the tiles' device buffers: not needed any more)
+  return install_families(c, N, n_fam, fam_ptr, members, blk_off, U, S);
+}
+
 // ---- integer-plane GEMMs (rot_gemm.hip.h) ---------------------------------------------------------------------------
 namespace {
 constexpr int kRotMaxCols = 1 << 15;
@@ -906,6 +1215,18 @@ int quantize_columns_mt(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t
 int rotate_columns(rvt_ctx* c, const double* d_src, int64_t ld_src, int ncols, double* d_dst, int64_t ld_dst,
                           hipStream_t st) {
   const int64_t N = c->kin_N;
+  if (c->d_fam_run) {  // the family form: one workgroup per run of families and tile of columns (rot_fam_kernel)
+    const int per = 65535 * kRotFamCols;  // (gridDim.y holds at most 65535 column tiles)
+    for (int c0 = 0; c0 < ncols; c0 += per) {
+      const int nc = std::min(per, ncols - c0);
+      hipLaunchKernelGGL(rot_fam_kernel, dim3((unsigned)c->fam_runs, (unsigned)((nc + kRotFamCols - 1) / kRotFamCols)),
+                         dim3(kRotFamRows), 0, st, c->d_fam_run, c->d_fam_of, c->d_fam_ptr, c->d_fam_members, c->d_csc_ptr,
+                         c->d_csc_vals, d_src + (size_t)c0 * ld_src, (long long)ld_src, nc, d_dst + (size_t)c0 * ld_dst,
+                         (long long)ld_dst);
+      HIP_TRY(c, hipGetLastError());
+    }
+    return RVT_OK;
+  }
   if (c->d_csc_ptr && !c->d_uq_range) {  // sparse U, scattered supports: a gather per output (fp64 products and sums)
     for (int c0 = 0; c0 < ncols; c0 += 65535) {  // (gridDim.y holds at most 65535 columns)
       const int nc = std::min(65535, ncols - c0);
@@ -948,6 +1269,38 @@ int rvt_debug_rotate(rvt_ctx* c, const double* dG, int ncols, double* out) {
   HIP_TRY(c, hipMemcpy2DAsync(out, sizeof(double) * (size_t)N, c->d_Gt, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)N,
                               (size_t)ncols, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, sync_stream(st));
+  return RVT_OK;
+}
+
+// Measurement hook: the same rotation without the copy to the host, between two HIP events recorded directly around it
+int rvt_debug_rotate_timed(rvt_ctx* c, const double* dG, int ncols, double* ms) {
+  if (!c || !dG || !ms || ncols < 1) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_kin) return fail(c, RVT_E_STATE, "rvt_set_kinship first");
+  if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first (defines the block layout)");
+  const int64_t N = c->kin_N, ld = block_dims(c).ld;
+  if (block_dims(c).N != N) return fail(c, RVT_E_STATE, "the kinship and the null model differ in N");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  rc = ensure_fam_cols(c, (size_t)ncols, ld);
+  if (rc) return rc;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(c, hipEventCreate(&ev[0]));
+  hipError_t e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+  if (e == hipSuccess) {
+    rc = rotate_columns(c, dG, ld, ncols, c->d_Gt, ld, st);
+    if (!rc) e = hipEventRecord(ev[1], st);
+    if (!rc && e == hipSuccess) e = sync_stream(st);
+    float t = 0.0f;
+    if (!rc && e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+    *ms = t;
+  }
+  hipEventDestroy(ev[0]);
+  if (ev[1]) hipEventDestroy(ev[1]);
+  if (rc) return rc;
+  HIP_TRY(c, e);
   return RVT_OK;
 }
 

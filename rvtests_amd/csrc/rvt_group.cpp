@@ -503,6 +503,17 @@ int rvt_group_set_kinship(rvt_group* g, int64_t N, const float* U, const float* 
   return RVT_OK;
 }
 
+int rvt_group_set_kinship_families(rvt_group* g, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                                   const float* U_blocks, const float* S) {
+  if (!g) return RVT_E_INVALID;
+  if (int rcf = group_flush(g)) return rcf;
+  for (rvt_ctx* m : g->member) {
+    const int rc = rvt_set_kinship_families(m, N, n_fam, fam_ptr, members, U_blocks, S);
+    if (rc) return gfail(g, rc, "rvt_set_kinship_families", m);
+  }
+  return RVT_OK;
+}
+
 int rvt_group_fit_fam_null(rvt_group* g, int64_t N, int d, const double* X, const double* y, rvt_fam_null* out) {
   if (!g) return RVT_E_INVALID;
   if (int rcf = group_flush(g)) return rcf;

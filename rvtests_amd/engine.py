@@ -20,6 +20,7 @@ CODING_DOMINANT, CODING_RECESSIVE = 1, 2   # RVT_CODING_* (rvt_block_recode / rv
 
 c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int)
+c_i64_p = C.POINTER(C.c_int64)
 
 
 class RvtError(RuntimeError):
@@ -225,6 +226,16 @@ def load_library():
     L.rvt_set_kinship.argtypes = [vp, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.rvt_fit_fam_null.restype = C.c_int
     L.rvt_fit_fam_null.argtypes = [vp, C.c_int64, C.c_int, c_double_p, c_double_p, C.POINTER(FamNull)]
+    fam_form = [C.c_int64, C.c_int64, c_i64_p, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    L.rvt_set_kinship_families.restype = C.c_int
+    L.rvt_set_kinship_families.argtypes = [vp] + fam_form + [C.POINTER(C.c_float)]
+    L.rvt_kinship_decompose_families.restype = C.c_int
+    L.rvt_kinship_decompose_families.argtypes = [vp] + fam_form + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_void_p]
+    L.rvt_kinship_components.restype = C.c_int
+    L.rvt_kinship_components.argtypes = [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i64_p, c_i64_p,
+                                         C.POINTER(C.c_int32)]
+    L.rvt_debug_rotate_timed.restype = C.c_int
+    L.rvt_debug_rotate_timed.argtypes = [vp, vp, C.c_int, c_double_p]
     L.rvt_run_fam_blocks.restype = C.c_int
     L.rvt_run_fam_blocks.argtypes = [vp, C.c_int, C.POINTER(vp), c_int_p, C.POINTER(C.c_int64),
                                      C.POINTER(GeneResult)]
@@ -298,7 +309,6 @@ def load_library():
     L.rvt_group_submit_gene_i8.restype = C.c_int
     L.rvt_group_submit_gene_i8.argtypes = [gp, C.c_int64, C.c_int, C.POINTER(C.c_int8), C.c_uint32, C.POINTER(Params),
                                            c_double_p]
-    c_i64_p = C.POINTER(C.c_int64)
     L.rvt_vcf_locate.restype = C.c_int
     L.rvt_vcf_locate.argtypes = [C.c_char_p, C.c_int64, c_i64_p, c_int_p, c_int_p, c_int_p]
     L.rvt_vcf_set_samples.restype = C.c_int
@@ -342,6 +352,8 @@ def load_library():
     L.rvt_group_collect_ready.argtypes = [gp, C.POINTER(GeneResult), C.c_int, c_int_p]
     L.rvt_group_set_kinship.restype = C.c_int
     L.rvt_group_set_kinship.argtypes = [gp, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.rvt_group_set_kinship_families.restype = C.c_int
+    L.rvt_group_set_kinship_families.argtypes = [gp] + fam_form + [C.POINTER(C.c_float)]
     L.rvt_group_fit_fam_null.restype = C.c_int
     L.rvt_group_fit_fam_null.argtypes = [gp, C.c_int64, C.c_int, c_double_p, c_double_p, C.POINTER(FamNull)]
     L.rvt_group_run_fam_tests_host.restype = C.c_int
@@ -415,6 +427,60 @@ class KinshipInfo(C.Structure):
 KINSHIP_IBS, KINSHIP_BN = 0, 1   # RVT_KINSHIP_* (rvt_kinship_from_bed)
 # (ctx, d_rows, V, method, min_maf, max_missing, K_out, info)
 KINSHIP_FROM_BED_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, c_double_p, C.POINTER(KinshipInfo)]
+
+
+def family_form(fam_ptr, members, blocks, S=None):
+    """The family form of a kinship (rvt_set_kinship_families) as the library takes it, checked on the host before any device
+    call: fam_ptr (n_fam + 1 integers from 0 to N), members (N integers), blocks (sum k^2 floats: every family's k x k block,
+    column-major, concatenated) and, when given, S (N floats).  Returns (N, n_fam, fam_ptr int64, members int32, blocks
+    float32, S float32 or None); TypeError for a wrong kind of number, ValueError for a wrong shape."""
+    fam_ptr, members, blocks = np.asarray(fam_ptr), np.asarray(members), np.asarray(blocks)
+    if fam_ptr.dtype.kind not in "iu" or members.dtype.kind not in "iu":
+        raise TypeError("fam_ptr and members must be integer arrays, not %s / %s" % (fam_ptr.dtype, members.dtype))
+    if blocks.dtype.kind != "f":
+        raise TypeError("the blocks must be a floating-point array, not %s" % blocks.dtype)
+    if fam_ptr.ndim != 1 or members.ndim != 1 or blocks.ndim != 1 or fam_ptr.size < 2:
+        raise ValueError("fam_ptr (n_fam + 1), members (N) and the blocks (sum k^2) are one-dimensional")
+    fam_ptr = np.ascontiguousarray(fam_ptr, dtype=np.int64)
+    n_fam, N = fam_ptr.size - 1, members.size
+    if N >= 2 ** 31 or (members.size and (members.max() >= 2 ** 31 or members.min() < 0)):
+        raise ValueError("members holds sample indices (0 .. N-1, below 2^31)")
+    size = np.diff(fam_ptr)
+    if fam_ptr[-1] == N and size.min() >= 0 and blocks.size != int((size * size).sum()):
+        raise ValueError("the blocks hold %d values, the family sizes ask for %d" % (blocks.size, int((size * size).sum())))
+    if fam_ptr[-1] != N or size.min() < 0:      # (the library names the offending family; the blocks must still be readable)
+        need = int((np.abs(size) ** 2).sum())
+        if blocks.size < need:
+            raise ValueError("the blocks hold %d values, fam_ptr asks for %d" % (blocks.size, need))
+    if S is not None:
+        S = np.asarray(S)
+        if S.dtype.kind != "f":
+            raise TypeError("S must be a floating-point array, not %s" % S.dtype)
+        if S.shape != (N,):
+            raise ValueError("S has shape %s, not (%d,)" % (S.shape, N))
+        S = np.ascontiguousarray(S, dtype=np.float32)
+    return (N, n_fam, fam_ptr, np.ascontiguousarray(members, dtype=np.int32), np.ascontiguousarray(blocks, dtype=np.float32), S)
+
+
+def kinship_components(N, i, j):
+    """The families of a list of related pairs (rvt_kinship_components; host only): (fam_ptr int64 (n_fam + 1), members int32
+    (N)) — members ascending inside a family, families in the order of their first member."""
+    i, j = np.asarray(i), np.asarray(j)
+    if i.size and (i.dtype.kind not in "iu" or j.dtype.kind not in "iu"):
+        raise TypeError("the pairs must be integer arrays")
+    if i.ndim != 1 or i.shape != j.shape:
+        raise ValueError("i and j are one-dimensional and of one length")
+    i, j = np.ascontiguousarray(i, dtype=np.int32), np.ascontiguousarray(j, dtype=np.int32)
+    N = int(N)
+    fam_ptr = np.zeros(max(N, 0) + 1, dtype=np.int64)
+    members = np.zeros(max(N, 0), dtype=np.int32)
+    n_fam = C.c_int64(0)
+    ip = C.POINTER(C.c_int32)
+    rc = load_library().rvt_kinship_components(N, i.size, i.ctypes.data_as(ip), j.ctypes.data_as(ip), C.byref(n_fam),
+                                               fam_ptr.ctypes.data_as(c_i64_p), members.ctypes.data_as(ip))
+    if rc != 0:
+        raise RvtError("rvt_kinship_components failed (%d): N < 1 or a pair outside 0 .. N-1" % rc)
+    return fam_ptr[: n_fam.value + 1].copy(), members
 
 
 def vcf_locate(L, line):
@@ -794,6 +860,23 @@ class Engine:
             self.N = N
         return U, S, info
 
+    def kinship_decompose_families(self, fam_ptr, members, K_blocks, install=False):
+        """Eigendecomposition of a kinship in the family form (rvt_kinship_decompose_families): K_blocks holds every family's
+        k x k block (see family_form).  Returns (U_blocks float32, S float32 — ascending within each family — , DecomposeInfo);
+        install=True also installs the result through the family form."""
+        N, n_fam, fam_ptr, members, K_blocks, _ = family_form(fam_ptr, members, K_blocks)
+        U = np.zeros(K_blocks.size, dtype=np.float32)
+        S = np.zeros(N, dtype=np.float32)
+        info = DecomposeInfo()
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        self._check(self.L.rvt_kinship_decompose_families(self.ctx, N, n_fam, fam_ptr.ctypes.data_as(c_i64_p),
+                                                          members.ctypes.data_as(ip), K_blocks.ctypes.data_as(fp),
+                                                          U.ctypes.data_as(fp), S.ctypes.data_as(fp), 1 if install else 0,
+                                                          C.cast(C.byref(info), C.c_void_p)))
+        if install:
+            self.N = N
+        return U, S, info
+
     def kinship_from_bed(self, d_rows, V, method="bn", min_maf=0.0, max_missing=1.0, install=False):
         """The empirical kinship of V consecutive rows of a resident .bed matrix (rvt_kinship_from_bed): what
         `vcf2kinship --bn` (method "bn") or `--ibs` ("ibs") computes from the same hard calls.  min_maf and max_missing are
@@ -1036,6 +1119,21 @@ class Engine:
         fp = C.POINTER(C.c_float)
         self._check(self.L.rvt_set_kinship(self.ctx, N, U.ctypes.data_as(fp), S.ctypes.data_as(fp)))
         self.N = N
+
+    def set_kinship_families(self, fam_ptr, members, U_blocks, S):
+        """Install a decomposition handed over family by family (rvt_set_kinship_families; the layout: family_form)."""
+        N, n_fam, fam_ptr, members, U_blocks, S = family_form(fam_ptr, members, U_blocks, S)
+        fp = C.POINTER(C.c_float)
+        self._check(self.L.rvt_set_kinship_families(self.ctx, N, n_fam, fam_ptr.ctypes.data_as(c_i64_p),
+                                                    members.ctypes.data_as(C.POINTER(C.c_int32)), U_blocks.ctypes.data_as(fp),
+                                                    S.ctypes.data_as(fp)))
+        self.N = N
+
+    def debug_rotate_timed(self, ptr, ncols):
+        """Device milliseconds of the rotation of the first ncols columns of a device block (rvt_debug_rotate_timed)."""
+        ms = C.c_double(0.0)
+        self._check(self.L.rvt_debug_rotate_timed(self.ctx, C.c_void_p(int(ptr)), int(ncols), C.cast(C.byref(ms), c_double_p)))
+        return ms.value
 
     def kinship_structure(self):
         """Share of the N x N rotation product that is computed (1 = dense eigenvectors; small for family structure)."""
@@ -1427,6 +1525,14 @@ class Group:
         S = np.ascontiguousarray(S, dtype=np.float32)
         fp = C.POINTER(C.c_float)
         self._check(self.L.rvt_group_set_kinship(self.g, U.shape[0], U.ctypes.data_as(fp), S.ctypes.data_as(fp)))
+
+    def set_kinship_families(self, fam_ptr, members, U_blocks, S):
+        """The family form on every member (rvt_group_set_kinship_families; the layout: family_form)."""
+        N, n_fam, fam_ptr, members, U_blocks, S = family_form(fam_ptr, members, U_blocks, S)
+        fp = C.POINTER(C.c_float)
+        self._check(self.L.rvt_group_set_kinship_families(self.g, N, n_fam, fam_ptr.ctypes.data_as(c_i64_p),
+                                                          members.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          U_blocks.ctypes.data_as(fp), S.ctypes.data_as(fp)))
 
     def fit_fam_null(self, X, y):
         X = np.asfortranarray(X, dtype=np.float64)
