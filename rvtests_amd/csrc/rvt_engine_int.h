@@ -62,7 +62,7 @@ void k2_launch_classify(dim3 grid, hipStream_t st, const double* G, long long N,
 #include "burdenperm_kernels.hip.h"
 #include "vcf_kernels.hip.h"
 #include "bgen_kernels.hip.h"
-#include "jacobi_kernels.hip.h"
+#include "jacobi_tile.h"
 #include "rvt_hyper.h"
 
 using namespace rvt;
@@ -805,10 +805,10 @@ void choose_split(int64_t ld, int n_genes, bool weighted, int* n_wparts, int* st
 // Every non-template kernel of the engine is `static` in a header that all rvt_*.hip units see through this file; until
 // round 6 each unit therefore compiled and shipped its own copy of all of them (76 kernels x 5 code objects).  Now a unit
 // defines RVT_K_SPLIT and ONE of RVT_K_ENGINE / RVT_K_STREAM / RVT_K_FAM / RVT_K_PERM / RVT_K_META before including this
-// header and gets the bodies of that family alone (tools and the host harness define nothing and get everything).  The two
-// later units name a family no shared header knows — RVT_K_MT (rvt_mtscore.hip), RVT_K_KINSHIP (rvt_kinship.hip) — so they
-// get none of those bodies, only the kernels of the header each includes for itself (mtscore_kernels.hip.h,
-// kinship_kernels.hip.h).  The few kernels that two units launch live in one of them; the other goes through these host
+// header and gets the bodies of that family alone (tools and the host harness define nothing and get everything).  The
+// later units name a family no shared header knows — RVT_K_MT (rvt_mtscore.hip), RVT_K_KINSHIP (rvt_kinship.hip),
+// RVT_K_DECOMPOSE (rvt_decompose.hip) — so they get none of those bodies, only the kernels of the headers each includes for
+// itself (mtscore_kernels.hip.h; kinship_kernels.hip.h; jacobi_kernels.hip.h and tridiag_kernels.hip.h).  The few kernels that two units launch live in one of them; the other goes through these host
 // launchers (tools/kernel_units.sh lists which object carries which kernel; it reads every .o it finds).
 // the column blocks' bookkeeping (rvt_meta.hip): the queue of single columns, and a block that is new / goes away / is refilled
 extern "C" RVT_INTERNAL int flush_col_queue(rvt_ctx* c);
@@ -854,6 +854,14 @@ RVT_INTERNAL int rvt_planes_gemm(rvt_ctx* c, const signed char* A, size_t a_stri
 // multiple of `pad`: the planes, the bytes between them, their number and the ncols column exponents
 RVT_INTERNAL int quantize_columns_mt(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld_src, int ncols, int pad, int64_t ldk,
                                      hipStream_t st, signed char** planes, size_t* plane_stride, int* n_planes, int* col_exp);
+// the family form of the kinship for rvt_kinship_decompose_families (rvt_decompose.hip): the descriptors checked (blk_off[f] =
+// where family f's block starts), the blocks checked for non-finite entries, the installation itself
+RVT_INTERNAL int check_families(rvt_ctx* c, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                                std::vector<long long>* blk_off);
+RVT_INTERNAL int check_blocks_finite(rvt_ctx* c, int64_t n_fam, const int64_t* fam_ptr, const std::vector<long long>& blk_off,
+                                     const float* blocks, const char* what);
+RVT_INTERNAL int install_families(rvt_ctx* c, int64_t N, int64_t n_fam, const int64_t* fam_ptr, const int32_t* members,
+                                  const std::vector<long long>& blk_off, const float* blocks, const float* S);
 // ---- defined in rvt_meta.hip: C = A' D [B | B2] in fp64 on the matrix cores (gemm_f64.hip.h)
 RVT_INTERNAL int gemm_tn_f64(rvt_ctx* c, const double* A, int64_t lda, int M, const double* B, int64_t ldb, int Nb, const double* B2,
                              int64_t ldb2, int Nb2, const double* w, int64_t N, double* C, int64_t ldc, bool symmetric,

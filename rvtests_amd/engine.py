@@ -92,7 +92,7 @@ def build_library(force=False, verbose=False):
     # one object per translation unit, compiled in parallel (the fully unrolled K2 bodies dominate the compile time), then one
     # link.  Every unit leaves a dependency file (-MMD): a unit whose sources are older than its object is not compiled again.
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-function"]
-    units = ["rvt_engine.hip", "rvt_stream.hip", "rvt_fam.hip", "rvt_perm.hip", "rvt_meta.hip", "rvt_mtscore.hip", "rvt_kinship.hip", "k2_unweighted.hip", "k2_weighted.hip", "k2_hardcall.hip", "k2_hardcall_w.hip",
+    units = ["rvt_engine.hip", "rvt_stream.hip", "rvt_fam.hip", "rvt_perm.hip", "rvt_meta.hip", "rvt_mtscore.hip", "rvt_kinship.hip", "rvt_decompose.hip", "k2_unweighted.hip", "k2_weighted.hip", "k2_hardcall.hip", "k2_hardcall_w.hip",
              "k2_hardcall_x.hip", "k2_lattice.hip", "k2_packed.hip", "k2_floatdigit.hip"]
 
     def fresh(obj, dep):

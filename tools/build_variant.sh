@@ -7,7 +7,7 @@ TAG=$1; shift
 cd "$(dirname "$0")/../rvtests_amd/csrc"
 OUT=variant_$TAG
 mkdir -p $OUT
-UNITS="rvt_engine rvt_stream rvt_fam rvt_perm rvt_meta k2_unweighted k2_weighted k2_hardcall k2_hardcall_w k2_hardcall_x k2_lattice k2_packed k2_floatdigit"
+UNITS="rvt_engine rvt_stream rvt_fam rvt_perm rvt_meta rvt_mtscore rvt_kinship rvt_decompose k2_unweighted k2_weighted k2_hardcall k2_hardcall_w k2_hardcall_x k2_lattice k2_packed k2_floatdigit"
 for u in $UNITS; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-function "$@" -c $u.hip -o $OUT/$u.o &
 done
