@@ -926,6 +926,36 @@ int rvt_score_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int*
  * trait.  counts (optional, 4 V entries): per row the numbers of 0 / 1 / 2 / missing calls, as rvt_score_bed_dev reports them;
  * the padding bits of a row's last byte are not counted.  Synchronous. */
 int rvt_bed_recode_block(rvt_ctx* ctx, const unsigned char* d_rows, int V, int coding, double* dG, int col0, long long* counts);
+/* The single-variant tests for related samples of V consecutive rows of a resident .bed matrix, after rvt_set_kinship* (or
+ * rvt_kinship_from_bed / rvt_kinship_decompose* with install) + rvt_fit_fam_null: the outputs of rvt_score_block_fam (famScore and
+ * --meta score with kinship: MetaFamQtl, src/Model.h:3398-3499; MetaFamBinary, :3556-3668; FastLMM::TestCovariate's SCORE branch,
+ * regression/FastLMM.cpp:215-247, and FastLMM::FastGetAF, :400-424) and of rvt_lrt_block_fam (SingleVariantFamilyLRT,
+ * src/Model.h:620-712; FastLMM.cpp:150-212 and :362-400) on the columns a caller would have uploaded — the calls of
+ * libVcf/PlinkInputFile.cpp:24-47 (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing) with missing imputed to the mean of the called ones
+ * (src/DataConsolidator.cpp:217-245) — computed from the 2-bit rows where they lie.  The rows have the pitch ceil(N / 4) bytes,
+ * N the family null model's sample count; they start at any byte, and the padding bits of a row's last byte are ignored whatever
+ * they hold.  One front stage serves both calls, at most RVT_MAX_VARIANTS rows at a time: the counts per row give the fill value
+ * mu = (n1 + 2 n2) / (N - missing), the column sum n1 + 2 n2 + missing mu and the polymorphic flag (at least two of n0, n1, n2
+ * non-zero; a row with no called sample is monomorphic, ok = 0, and is rotated with mu = 0), and the rotation U'g goes by the
+ * installed form of U:
+ *   family form (rvt_set_kinship_families)   the family-blocked kernel fills its tile from the codes: N / 4 bytes read per
+ *                                            column instead of 8 N, and the fp64 route's results bit for bit
+ *   dense U on digit planes                  g = c + mu m, c = the calls with missing -> 0, m = the missing indicator: U'c and
+ *                                            U'm are exact single-plane integer products (6 x 2 plane pairs where the quantised
+ *                                            imputed column takes 6 x 6), U'g = fma(mu, U'm, U'c) with mu rounded to the fixed
+ *                                            point those planes give the column (2^-38 or 2^-39): the same integer product as
+ *                                            the fp64 route's; a piece without a missing call skips the m half
+ *   column-compressed U, scattered supports  the piece is expanded to fp64 columns on the device and takes the fp64 route's gather
+ * binary and rvt_fam_binary_scale as in rvt_score_block_fam; ok as in rvt_score_block_fam / rvt_lrt_block_fam.  counts (optional,
+ * 4 V entries): per row the numbers of 0 / 1 / 2 / missing calls, as rvt_score_bed_dev reports them.  RVT_E_INVALID: a null
+ * argument (counts excepted) or V < 1.  RVT_E_STATE: no family null model, or an ordinary null model is installed whose N differs
+ * from the family null model's (the rows would have another pitch).  A refused call writes nothing.  Synchronous.
+ * Not covered from resident rows: famGrammarGamma, FamSKAT and the family burden tests, the family MetaCov calls, the rvt_group_*
+ * layer and the host adapter classes — they take fp64 blocks. */
+int rvt_score_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int binary, int* ok, double* ustat, double* vstat,
+                          double* af, double* pvalue, long long* counts);
+int rvt_lrt_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int* ok, double* af, double* null_loglik,
+                        double* alt_loglik, double* pvalue, long long* counts);
 
 /* ---- VCF text at the boundary (SURVEY §8f "next" #1: the genotype front end) -------------------------------------------
  * Replaces the per-sample loop of VCFGenotypeExtractor::extractMultipleGenotype (src/VCFGenotypeExtractor.cpp:29-140) for
@@ -1099,6 +1129,13 @@ int rvt_debug_rotate(rvt_ctx* ctx, const double* dG, int ncols, double* out);
 /* Measurement (tools/bench_fam_families.py): the same rotation without the copy to the host; *ms = the device milliseconds
  * between HIP events recorded directly around it. */
 int rvt_debug_rotate_timed(rvt_ctx* ctx, const double* dG, int ncols, double* ms);
+/* U'G as rvt_score_bed_dev_fam / rvt_lrt_bed_dev_fam compute it (test hook, cf. rvt_debug_rotate): the first ncols rows of a
+ * resident .bed matrix through their front stage — missing calls imputed to the row's mean — after rvt_fit_fam_null; out is a
+ * host N x ncols matrix, column-major, rows in the installed eigenpair order.  The same refusals as those calls. */
+int rvt_debug_rotate_bed(rvt_ctx* ctx, const unsigned char* d_rows, int ncols, double* out);
+/* Measurement (tools/bench_fam_bed.py): the same front stage without the copy to the host; *ms = the device milliseconds
+ * between HIP events recorded directly around it. */
+int rvt_debug_rotate_bed_timed(rvt_ctx* ctx, const unsigned char* d_rows, int ncols, double* ms);
 int rvt_set_profiling(rvt_ctx* ctx, int on);
 int rvt_get_timing(rvt_ctx* ctx, rvt_timing* t, int reset);
 /* the HIP stream (hipStream_t) the engine launches on, for callers that record their own events */

@@ -1,0 +1,130 @@
+// rvtests_amd — the family tests' front stage over rows of a resident .bed matrix (rvt_score_bed_dev_fam, rvt_lrt_bed_dev_fam):
+// what raw_colstat_kernel + rotate_columns give for fp64 columns — the rotated columns U'G, the raw column sums and the
+// polymorphic flags — formed from the 2-bit codes where they lie (rvt_bed_alloc: row r at rows + r * pitch, pitch = ceil(N / 4)
+// bytes, no alignment; PLINK codes 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing, sample i in bits 2 (i & 3) of byte i >> 2, as
+// bed_expand_columns_kernel reads them).  The column a caller would have uploaded is the calls with missing imputed to the
+// mean of the called ones (DataConsolidator.cpp:217-245), i.e. exactly  g = c + mu m  with c = the calls (missing -> 0), m = the
+// missing indicator and mu = (n1 + 2 n2) / (N - missing):
+//   * family form (rvt_set_kinship_families): rot_fam_bed_kernel, rot_fam_kernel's tile filled from the codes;
+//   * dense U on digit planes: fam_bed_unpack_kernel writes c and m as single-plane int8 operands of planes_gemm, U'c and U'm
+//     are exact integer products and fam_bed_combine_kernel forms U'c + mu U'm (mu in the planes' fixed point, see
+//     fam_bed_site_kernel) — 6 x 2 plane pairs where the fp64 route's quantised imputed column costs 6 x 6, and no fp64 read
+//     of the column at all;
+//   * column-compressed U with scattered supports: no kernel here — the piece is expanded to fp64 columns with
+//     bed_expand_columns_kernel and goes through rotate_columns (rot_sparse_kernel); the form is not worth one of its own.
+// Bytes per column: N / 4 of codes instead of 8 N of doubles in, 8 N out (family form; the dense form adds 2 N of planes).
+// Rows start at any byte address (N = 515: pitch 129), so every kernel here loads single bytes; the padding pairs of a row's
+// last byte are never looked at (family form: no member index reaches them) or masked out.
+// Included by rvt_fam.hip alone.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace rvt {
+
+// The site pass: counts[4 v ..] = n0 n1 n2 missing of row v (recode_bed_count_kernel) -> the fill value, the column sum and the
+// polymorphic flag of the imputed column.  sum = n1 + 2 n2 + missing mu; polymorphic = at least two of n0, n1, n2 non-zero,
+// which is raw_colstat_kernel's min != max on the imputed column (one called value: the mean is that value).  A row with no
+// called sample gets mu = 0 and is monomorphic: its rotated column is all zero and no NaN reaches a neighbour.
+// muq = mu in the fixed point the digit planes give a non-integer column (quantize_columns: entries scaled by 2^s, s =
+// 7 kRotPlanesG - 3 - ilogb(max |g|), and the largest entry of an imputed column is its largest call): rint(mu 2^s) 2^-s.  The
+// dense rotation multiplies with it, so that it stays the integer product the fp64 route forms of the same column (tests/rotref.py
+// states it) — U'g = 2^-s (2^s U'c + rint(mu 2^s) U'm) — whose bound then holds here as well; the other forms take mu itself.
+static __global__ __launch_bounds__(256) void fam_bed_site_kernel(const unsigned long long* __restrict__ counts, int n,
+                                                                  double* __restrict__ mu, double* __restrict__ muq,
+                                                                  double* __restrict__ colsum, int* __restrict__ poly) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n) return;
+  const long long n0 = (long long)counts[4 * v], n1 = (long long)counts[4 * v + 1], n2 = (long long)counts[4 * v + 2],
+                  nm = (long long)counts[4 * v + 3];
+  const long long called = n0 + n1 + n2, ac = n1 + 2 * n2;
+  const double m = called > 0 ? (double)ac / (double)called : 0.0;
+  mu[v] = m;
+  const int s = 7 * kRotPlanesG - 3 - (n2 > 0 ? 1 : 0);  // (ac > 0: the largest call is 1 or 2; ac == 0: m is 0 anyway)
+  muq[v] = ldexp(rint(ldexp(m, s)), -s);
+  colsum[v] = fma((double)nm, m, (double)ac);
+  poly[v] = ((n0 > 0) + (n1 > 0) + (n2 > 0)) >= 2 ? 1 : 0;
+}
+
+// the value of the 2-bit code q with the fill value m for a missing call
+__device__ __forceinline__ double fam_bed_value(unsigned q, double m) {
+  return q == 0u ? 0.0 : (q == 2u ? 1.0 : (q == 3u ? 2.0 : m));
+}
+
+// rot_fam_kernel over codes: the same grid (runs of families x tiles of kRotFamCols columns), the same thread-to-eigenpair
+// map, the same fma chain (rot_fam_chain) and the same stores; only step 1 differs — thread t decodes the pair of sample
+// members[e0 + t] from byte members[e0 + t] >> 2 of each of the tile's rows, missing -> mu[col].  A tile therefore holds the very
+// doubles the fp64 route reads from an uploaded imputed column, and the outputs agree with it bit for bit.
+// Traffic per column: the bytes of the members' pairs (N / 4 when every sample belongs to a family of the run) and 8 N out.
+static __global__ __launch_bounds__(kRotFamRows) void rot_fam_bed_kernel(
+    const int* __restrict__ run_ptr, const int* __restrict__ pair_fam, const long long* __restrict__ fam_ptr,
+    const int* __restrict__ members, const long long* __restrict__ colptr, const double* __restrict__ vals,
+    const unsigned char* __restrict__ rows, long long pitch, const double* __restrict__ mu, int ncols,
+    double* __restrict__ out, long long ld_dst) {
+  __shared__ double g[kRotFamCols][kRotFamRows];
+  const int e0 = run_ptr[blockIdx.x], nrows = run_ptr[blockIdx.x + 1] - e0;  // nrows <= kRotFamRows
+  const int t = threadIdx.x, col0 = blockIdx.y * kRotFamCols;
+  const int nc = min(kRotFamCols, ncols - col0);
+  const bool active = t < nrows;
+  int k = 0, row0 = 0;
+  const double* u = vals;
+  if (active) {
+    const int e = e0 + t, f = pair_fam[e];
+    const long long fs = fam_ptr[f];
+    k = (int)(fam_ptr[f + 1] - fs);
+    row0 = (int)(fs - e0);
+    u = vals + colptr[e];
+    const int s = members[e], sh = 2 * (s & 3);
+    const unsigned char* src = rows + (long long)col0 * pitch + (s >> 2);
+#pragma unroll
+    for (int c = 0; c < kRotFamCols; ++c)
+      if (c < nc) g[c][t] = fam_bed_value(((unsigned)src[(long long)c * pitch] >> sh) & 3u, mu[col0 + c]);
+  }
+  __syncthreads();
+  if (!active) return;
+  double acc[kRotFamCols];
+  rot_fam_chain(u, k, row0, g, acc);
+  double* dst = out + (e0 + t) + (long long)col0 * ld_dst;
+#pragma unroll
+  for (int c = 0; c < kRotFamCols; ++c)
+    if (c < nc) dst[(long long)c * ld_dst] = acc[c];
+}
+
+// n rows -> the B operand of planes_gemm, one int8 plane: column j = the calls of row j with missing -> 0, and — with_m — column
+// n + j = its missing indicator; column j at B + j * ldk, sample i at byte i.  A thread takes one byte of a row (four samples)
+// and stores four int8 per column as one dword (ldk is a multiple of 128 and 4 ceil(N / 4) <= ldk); the pairs past sample N - 1
+// are written as zeros whatever the byte holds.  The rest of B (bytes from 4 ceil(N / 4) on, the pad columns) is zeroed by the
+// caller.  grid (ceil(pitch / 256), n).
+static __global__ __launch_bounds__(256) void fam_bed_unpack_kernel(const unsigned char* __restrict__ rows, long long pitch,
+                                                                    long long N, int n, int with_m,
+                                                                    signed char* __restrict__ B, long long ldk) {
+  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (b >= pitch) return;
+  const int j = blockIdx.y;
+  const unsigned code = rows[(long long)j * pitch + b];
+  const long long left = N - 4 * b;  // > 0
+  uint32_t cw = 0u, mw = 0u;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned q = (code >> (2 * e)) & 3u;
+    if (e < left) {
+      cw |= (q == 2u ? 1u : (q == 3u ? 2u : 0u)) << (8 * e);
+      mw |= (q == 1u ? 1u : 0u) << (8 * e);
+    }
+  }
+  *reinterpret_cast<uint32_t*>(B + (long long)j * ldk + 4 * b) = cw;
+  if (with_m) *reinterpret_cast<uint32_t*>(B + (long long)(n + j) * ldk + 4 * b) = mw;
+}
+
+// out[:, h] = fma(mu[h], C[:, n + h], C[:, h]) for the N rows of n columns: U'g = U'c + mu U'm (the caller passes muq).
+// grid (ceil(N / 256), n).
+static __global__ __launch_bounds__(256) void fam_bed_combine_kernel(const double* __restrict__ C, long long ldc, long long N,
+                                                                     int n, const double* __restrict__ mu,
+                                                                     double* __restrict__ out, long long ld_dst) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const int h = blockIdx.y;
+  out[i + (long long)h * ld_dst] = fma(mu[h], C[i + (long long)(n + h) * ldc], C[i + (long long)h * ldc]);
+}
+
+}  // namespace rvt

@@ -505,6 +505,27 @@ static __global__ __launch_bounds__(256) void rot_sparse_kernel(const long long*
 // column tile.  A family of one is the scaled copy it should be (k = 1).  LDS: 16 x 256 doubles = 32 KB, 5 workgroups per CU.
 constexpr int kRotFamRows = 256, kRotFamCols = 16;
 #if !defined(RVT_K_SPLIT) || defined(RVT_K_FAM)
+// steps 2 and 3 of one thread: acc[col] = sum_r u[r] g[col][row0 + r], r ascending, one fma chain per column.  Shared by
+// rot_fam_kernel and its sibling over 2-bit codes (rot_fam_bed_kernel, fam_bed_kernels.hip.h): the same tile gives the same bits.
+__device__ __forceinline__ void rot_fam_chain(const double* __restrict__ u, int k, int row0,
+                                              const double (*g)[kRotFamRows], double (&acc)[kRotFamCols]) {
+#pragma unroll
+  for (int c = 0; c < kRotFamCols; ++c) acc[c] = 0.0;
+  for (int r0 = 0; r0 < k; r0 += 8) {
+    double ur[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ur[i] = (r0 + i < k) ? u[r0 + i] : 0.0;
+    const int nr = min(8, k - r0);
+#pragma unroll
+    for (int c = 0; c < kRotFamCols; ++c) {
+      const double* gc = &g[c][row0 + r0];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        if (i < nr) acc[c] = fma(ur[i], gc[i], acc[c]);
+    }
+  }
+}
+
 static __global__ __launch_bounds__(kRotFamRows) void rot_fam_kernel(
     const int* __restrict__ run_ptr, const int* __restrict__ pair_fam, const long long* __restrict__ fam_ptr,
     const int* __restrict__ members, const long long* __restrict__ colptr, const double* __restrict__ vals,
@@ -530,21 +551,7 @@ static __global__ __launch_bounds__(kRotFamRows) void rot_fam_kernel(
   __syncthreads();
   if (!active) return;
   double acc[kRotFamCols];
-#pragma unroll
-  for (int c = 0; c < kRotFamCols; ++c) acc[c] = 0.0;
-  for (int r0 = 0; r0 < k; r0 += 8) {
-    double ur[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ur[i] = (r0 + i < k) ? u[r0 + i] : 0.0;
-    const int nr = min(8, k - r0);
-#pragma unroll
-    for (int c = 0; c < kRotFamCols; ++c) {
-      const double* gc = &g[c][row0 + r0];
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (i < nr) acc[c] = fma(ur[i], gc[i], acc[c]);
-    }
-  }
+  rot_fam_chain(u, k, row0, g, acc);
   double* dst = out + (e0 + t) + (long long)col0 * ld_dst;
 #pragma unroll
   for (int c = 0; c < kRotFamCols; ++c)

@@ -517,6 +517,7 @@ struct rvt_ctx {
   DevBuf<char> d_lrt_ws;
   uint64_t lrt_gen = 0;        // fam_gen the famLRT constants were formed for (0: none)
   double lrt_ssr0 = 0.0, lrt_slog = 0.0;
+  DevBuf<char> d_fam_bed_ws;   // the family tests over resident .bed rows: counts, fill values, sums and flags of a piece (grow-only)
   DevBuf<char> d_gg_ws;
   bool have_grammar = false;
   int64_t gg_N = 0;
@@ -869,6 +870,9 @@ RVT_INTERNAL int gemm_tn_f64(rvt_ctx* c, const double* A, int64_t lda, int M, co
 // the calls of 0 / 1 / 2 / missing of n_rows rows of a resident .bed matrix, added to d_cnt[4 r + k] (recode_bed_count_kernel)
 RVT_INTERNAL void bed_row_counts(hipStream_t st, const unsigned char* d_rows, long long cb, long long N, int n_rows,
                                  unsigned long long* d_cnt);
+// n_rows rows of a resident .bed matrix as fp64 columns (leading dimension ld), missing -> d_mu[row] (bed_expand_columns_kernel)
+RVT_INTERNAL void bed_rows_expand(hipStream_t st, const unsigned char* d_rows, long long cb, const double* d_mu, long long N,
+                                  long long ld, int n_rows, double* G);
 // ---- defined in rvt_perm.hip
 RVT_INTERNAL int rvt_kbac_stage(rvt_ctx* c, const double* dG, int M, const double* af, const std::vector<unsigned char>& y,
                                 int nPerm, double alpha, rvt_kbac_result* r);

@@ -7,6 +7,7 @@
 #define RVT_K_FAM
 #include "rvt_engine_int.h"
 #include "fam_single.hip.h"
+#include "fam_bed_kernels.hip.h"
 
 static void free_csc(rvt_ctx* c) {  // the column-compressed form of U
   c->d_csc_ptr.reset();
@@ -1491,15 +1492,17 @@ void fs_launch_lrt(hipStream_t st, int n, const double* Gt, long long ld, long l
 }  // extern "C++"
 }  // namespace
 
-int rvt_lrt_block_fam(rvt_ctx* c, const double* dG, int V, int* ok, double* af, double* null_loglik, double* alt_loglik,
-                      double* pvalue) {
-  if (!c || !dG || V < 1 || !ok || !af || !null_loglik || !alt_loglik || !pvalue)
-    return fail(c, RVT_E_INVALID, "bad arguments");
-  if (!c->have_fam) return fail(c, RVT_E_STATE, "rvt_set_kinship + rvt_fit_fam_null first");
-  hipSetDevice(c->device);
-  int rc = rvt_sync(c);
-  if (rc) return rc;
-  hipStream_t st = c->stream;
+namespace {
+// famLRT's work space (d_lrt_ws) as a piece of columns uses it, and the constants of the null fit
+struct LrtWs {
+  double *vec, *ainv, *cs, *af, *nll, *all, *pv;
+  int *poly, *ok;
+  LrtConsts k;
+};
+
+// The work space and, once per null fit, its constants (lrt_gen).  Shared by rvt_lrt_block_fam and rvt_lrt_bed_dev_fam.
+int lrt_prepare(rvt_ctx* c, hipStream_t st, LrtWs* w) {
+  int rc = RVT_OK;
   const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
   const int d = c->fam_nc.d - 1;
   const int MV = RVT_MAX_VARIANTS;
@@ -1553,37 +1556,285 @@ int rvt_lrt_block_fam(rvt_ctx* c, const double* dG, int V, int* ok, double* af, 
     c->lrt_ssr0 = sums[0];
     c->lrt_gen = c->fam_gen;
   }
-  LrtConsts k;
+  LrtConsts& k = w->k;
   k.n = (double)N;
   k.ssr0 = c->lrt_ssr0;
   k.sigma2 = c->fam_sigma2;
   k.slog = c->lrt_slog;
   k.afden = c->fam_nc.rss;  // u1' |S|^-1 u1 (rvt_fit_fam_null)
   k.d = d;
+  w->vec = d_vec, w->ainv = d_ainv, w->cs = d_cs, w->poly = d_poly, w->ok = d_ok;
+  w->af = d_af, w->nll = d_nll, w->all = d_all, w->pv = d_pv;
+  return RVT_OK;
+}
+
+// n <= RVT_MAX_VARIANTS rotated columns in c->d_Gt with their polymorphic flags on the device -> the outputs on the host
+int lrt_piece(rvt_ctx* c, hipStream_t st, const LrtWs& w, int n, const int* d_poly, int* ok, double* af, double* null_loglik,
+              double* alt_loglik, double* pvalue) {
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
+  const int d = c->fam_nc.d - 1;
+  if (d <= 4)
+    fs_launch_lrt<4, 4>(st, n, c->d_Gt, ld, N, c->d_uxy, w.vec, ld, w.ainv, d_poly, w.k, w.ok, w.af, w.nll, w.all, w.pv);
+  else if (d <= 8)
+    fs_launch_lrt<8, 2>(st, n, c->d_Gt, ld, N, c->d_uxy, w.vec, ld, w.ainv, d_poly, w.k, w.ok, w.af, w.nll, w.all, w.pv);
+  else
+    fs_launch_lrt<RVT_MAX_COV, 1>(st, n, c->d_Gt, ld, N, c->d_uxy, w.vec, ld, w.ainv, d_poly, w.k, w.ok, w.af, w.nll, w.all,
+                                  w.pv);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(ok, w.ok, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(af, w.af, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(null_loglik, w.nll, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(alt_loglik, w.all, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(pvalue, w.pv, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  return RVT_OK;
+}
+}  // namespace
+
+int rvt_lrt_block_fam(rvt_ctx* c, const double* dG, int V, int* ok, double* af, double* null_loglik, double* alt_loglik,
+                      double* pvalue) {
+  if (!c || !dG || V < 1 || !ok || !af || !null_loglik || !alt_loglik || !pvalue)
+    return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_fam) return fail(c, RVT_E_STATE, "rvt_set_kinship + rvt_fit_fam_null first");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
+  const int MV = RVT_MAX_VARIANTS;
+  LrtWs w;
+  rc = lrt_prepare(c, st, &w);
+  if (rc) return rc;
   for (int c0 = 0; c0 < V; c0 += MV) {
     const int n = std::min(MV, V - c0);
     const double* g = dG + (size_t)c0 * ld;
     rc = ensure_fam_cols(c, (size_t)n, ld);
     if (rc) return rc;
-    hipLaunchKernelGGL(raw_colstat_kernel, dim3((unsigned)n), dim3(256), 0, st, g, (long long)N, (long long)ld, d_cs, d_poly);
+    hipLaunchKernelGGL(raw_colstat_kernel, dim3((unsigned)n), dim3(256), 0, st, g, (long long)N, (long long)ld, w.cs, w.poly);
     HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * n, st));
     rc = rotate_columns(c, g, ld, n, c->d_Gt, ld, st);
     if (rc) return rc;
-    if (d <= 4)
-      fs_launch_lrt<4, 4>(st, n, c->d_Gt, ld, N, c->d_uxy, d_vec, ld, d_ainv, d_poly, k, d_ok, d_af, d_nll, d_all, d_pv);
-    else if (d <= 8)
-      fs_launch_lrt<8, 2>(st, n, c->d_Gt, ld, N, c->d_uxy, d_vec, ld, d_ainv, d_poly, k, d_ok, d_af, d_nll, d_all, d_pv);
-    else
-      fs_launch_lrt<RVT_MAX_COV, 1>(st, n, c->d_Gt, ld, N, c->d_uxy, d_vec, ld, d_ainv, d_poly, k, d_ok, d_af, d_nll, d_all,
-                                    d_pv);
+    rc = lrt_piece(c, st, w, n, w.poly, ok + c0, af + c0, null_loglik + c0, alt_loglik + c0, pvalue + c0);
+    if (rc) return rc;
+  }
+  return RVT_OK;
+}
+
+// ---- famScore / famLRT over rows of a resident .bed matrix (fam_bed_kernels.hip.h) ----------------------------------------------
+namespace {
+// what the front stage leaves on the device for a consumer (in d_fam_bed_ws), per row of the piece
+struct FamBedPiece {
+  unsigned long long* cnt;  // n0 n1 n2 missing
+  double *mu, *muq, *cs;    // the fill value of a missing call, the same in the digit planes' fixed point; the column sum
+  int* poly;
+};
+
+// The state both calls need.  The rows' pitch is ceil(N / 4) bytes with the N of the null model rvt_bed_alloc saw: an ordinary
+// null model of another N beside the family null means rows of another pitch.
+int fam_bed_check(rvt_ctx* c, const char* who) {
+  if (!c->have_fam) return fail(c, RVT_E_STATE, "%s: rvt_set_kinship + rvt_fit_fam_null first", who);
+  if (c->have_null && c->nc.N != c->fam_nc.N)
+    return fail(c, RVT_E_STATE, "%s: the null model has N = %lld, the family null model N = %lld (the resident rows have the former's pitch)",
+                who, (long long)c->nc.N, (long long)c->fam_nc.N);
+  return RVT_OK;
+}
+
+int fam_bed_ws(rvt_ctx* c, FamBedPiece* p) {
+  const int MV = RVT_MAX_VARIANTS;
+  Layout L;
+  const size_t o_cnt = L.take(sizeof(unsigned long long) * 4 * MV), o_mu = L.take(sizeof(double) * MV),
+               o_muq = L.take(sizeof(double) * MV), o_cs = L.take(sizeof(double) * MV), o_poly = L.take(sizeof(int) * MV);
+  HIP_TRY(c, c->d_fam_bed_ws.grow(L.total, L.total, nullptr, true));
+  char* ws = c->d_fam_bed_ws;
+  p->cnt = reinterpret_cast<unsigned long long*>(ws + o_cnt);
+  p->mu = reinterpret_cast<double*>(ws + o_mu);
+  p->muq = reinterpret_cast<double*>(ws + o_muq);
+  p->cs = reinterpret_cast<double*>(ws + o_cs);
+  p->poly = reinterpret_cast<int*>(ws + o_poly);
+  return RVT_OK;
+}
+
+// The front stage of both calls: n <= RVT_MAX_VARIANTS consecutive rows -> what raw_colstat_kernel + rotate_columns give for
+// the imputed fp64 columns of the same calls: the rotated columns in c->d_Gt (leading dimension fam_nc.ld, rows N .. ld - 1
+// zero), their raw sums in p.cs and polymorphic flags in p.poly.  counts (host, 4 n entries, optional): n0 n1 n2 missing per row.
+// The rotation goes by the installed form of U (fam_bed_kernels.hip.h); enqueued on st, which is synchronised on the way (the
+// counts decide on the host whether the piece has a missing call at all).
+int fam_bed_front(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int n, const FamBedPiece& p, long long* counts) {
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld, cb = (N + 3) / 4;
+  // 1. the site pass over the codes
+  HIP_TRY(c, hipMemsetAsync(p.cnt, 0, sizeof(unsigned long long) * 4 * (size_t)n, st));
+  bed_row_counts(st, d_rows, cb, N, n, p.cnt);
+  hipLaunchKernelGGL(fam_bed_site_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p.cnt, n, p.mu, p.muq,
+                     p.cs, p.poly);
+  HIP_TRY(c, hipGetLastError());
+  std::vector<unsigned long long> cnt(4 * (size_t)n);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), p.cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  bool any_missing = false;
+  for (int h = 0; h < n; ++h) any_missing = any_missing || cnt[4 * (size_t)h + 3] != 0;
+  if (counts)
+    for (size_t i = 0; i < cnt.size(); ++i) counts[i] = (long long)cnt[i];
+  // 2. the rotation, by the installed form
+  const bool dense = !c->d_fam_run && !(c->d_csc_ptr && !c->d_uq_range);
+  int rc = ensure_fam_cols(c, (size_t)(dense && any_missing ? 2 * n : n), ld);  // (d_Gp holds [U'c | U'm] of a dense piece)
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * n, st));
+  if (c->d_fam_run) {  // the family form
+    hipLaunchKernelGGL(rot_fam_bed_kernel, dim3((unsigned)c->fam_runs, (unsigned)((n + kRotFamCols - 1) / kRotFamCols)),
+                       dim3(kRotFamRows), 0, st, c->d_fam_run, c->d_fam_of, c->d_fam_ptr, c->d_fam_members, c->d_csc_ptr,
+                       c->d_csc_vals, d_rows, (long long)cb, p.mu, n, c->d_Gt, (long long)ld);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(ok + c0, d_ok, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(af + c0, d_af, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(null_loglik + c0, d_nll, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(alt_loglik + c0, d_all, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(pvalue + c0, d_pv, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    return RVT_OK;
+  }
+  if (!dense) {  // column-compressed U, scattered supports: fp64 columns on the device, then the gather of rotate_columns
+    bed_rows_expand(st, d_rows, cb, p.mu, N, ld, n, c->d_Gp);
+    HIP_TRY(c, hipGetLastError());
+    return rotate_columns(c, c->d_Gp, ld, n, c->d_Gt, ld, st);
+  }
+  // dense U on digit planes: B = [c | m], one plane each (the m half only when the piece has a missing call); the operands are
+  // 0 / 1 / 2, inside the 127 x 127 bound planes_gemm cuts its int32 ranges by
+  const int64_t ldk = c->uq_ldk;
+  const int nB = any_missing ? 2 * n : n;
+  const size_t need = (size_t)(((int64_t)nB + kRotBN - 1) / kRotBN * kRotBN) * (size_t)ldk;
+  HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
+  HIP_TRY(c, hipMemsetAsync(c->d_rotB, 0, need, st));
+  hipLaunchKernelGGL(fam_bed_unpack_kernel, dim3((unsigned)((cb + 255) / 256), (unsigned)n), dim3(256), 0, st, d_rows,
+                     (long long)cb, (long long)N, n, any_missing ? 1 : 0, c->d_rotB.get(), (long long)ldk);
+  HIP_TRY(c, hipGetLastError());
+  const std::vector<int> zero_exp((size_t)nB, 0);
+  double* C = any_missing ? c->d_Gp.get() : c->d_Gt.get();
+  rc = planes_gemm(c, c->d_Uq, c->uq_plane, kRotPlanesU, (int)N, nullptr, c->uq_sexp, c->d_rotB, need, 1, nB, zero_exp.data(), N,
+                   ldk, C, ld, st, c->d_uq_range);
+  if (rc) return rc;
+  if (any_missing) {
+    hipLaunchKernelGGL(fam_bed_combine_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)n), dim3(256), 0, st, C,
+                       (long long)ld, (long long)N, n, p.muq, c->d_Gt.get(), (long long)ld);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return RVT_OK;
+}
+}  // namespace
+
+// MetaScore with kinship from resident rows: rvt_score_block_fam's loop with the front stage in place of the fp64 prefix.
+int rvt_score_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int binary, int* ok, double* ustat, double* vstat,
+                          double* af, double* pvalue, long long* counts) {
+  if (!c || !d_rows || V < 1 || !ok || !ustat || !vstat || !af || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
+  int rc = fam_bed_check(c, "rvt_score_bed_dev_fam");
+  if (rc) return rc;
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const size_t cb = (size_t)((c->fam_nc.N + 3) / 4);
+  FamBedPiece p;
+  rc = fam_bed_ws(c, &p);
+  if (rc) return rc;
+  for (int64_t v0 = 0; v0 < V; v0 += RVT_MAX_VARIANTS) {
+    const int n = (int)std::min<int64_t>(RVT_MAX_VARIANTS, V - v0);
+    rc = fam_bed_front(c, st, d_rows + cb * (size_t)v0, n, p, counts ? counts + 4 * v0 : nullptr);
+    if (rc) return rc;
+    HIP_TRY(c, sync_stream(st));
+    CovOut co;
+    co.poly = ok + v0;
+    co.ustat = ustat + v0;
+    co.vstat = vstat + v0;
+    co.af = af + v0;
+    co.pval = pvalue + v0;
+    co.uncentred = binary != 0;
+    rc = famcov_run(c, c->d_Gt, n, p.cs, p.poly, &co);
+    if (rc) return rc;
+  }
+  if (binary) {  // MetaFamBinary::GetU / GetV (src/Model.h:3647-3648), as rvt_score_block_fam
+    const double b2 = c->famcov_b2, b = std::sqrt(b2);
+    for (int64_t h = 0; h < V; ++h) {
+      ustat[h] *= b;
+      vstat[h] *= b2;
+    }
+  }
+  return RVT_OK;
+}
+
+// famLRT from resident rows: rvt_lrt_block_fam's loop from the rotated piece onward, behind the front stage.
+int rvt_lrt_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* ok, double* af, double* null_loglik,
+                        double* alt_loglik, double* pvalue, long long* counts) {
+  if (!c || !d_rows || V < 1 || !ok || !af || !null_loglik || !alt_loglik || !pvalue)
+    return fail(c, RVT_E_INVALID, "bad arguments");
+  int rc = fam_bed_check(c, "rvt_lrt_bed_dev_fam");
+  if (rc) return rc;
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const size_t cb = (size_t)((c->fam_nc.N + 3) / 4);
+  FamBedPiece p;
+  LrtWs w;
+  rc = fam_bed_ws(c, &p);
+  if (!rc) rc = lrt_prepare(c, st, &w);
+  if (rc) return rc;
+  for (int64_t v0 = 0; v0 < V; v0 += RVT_MAX_VARIANTS) {
+    const int n = (int)std::min<int64_t>(RVT_MAX_VARIANTS, V - v0);
+    rc = fam_bed_front(c, st, d_rows + cb * (size_t)v0, n, p, counts ? counts + 4 * v0 : nullptr);
+    if (!rc) rc = lrt_piece(c, st, w, n, p.poly, ok + v0, af + v0, null_loglik + v0, alt_loglik + v0, pvalue + v0);
+    if (rc) return rc;
+  }
+  return RVT_OK;
+}
+
+namespace {
+// the front stage of the first ncols rows, piece by piece; out (host, N x ncols, optional) takes the rotated columns
+int fam_bed_rotate_all(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int ncols, double* out) {
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
+  const size_t cb = (size_t)((N + 3) / 4);
+  FamBedPiece p;
+  int rc = fam_bed_ws(c, &p);
+  for (int v0 = 0; v0 < ncols && !rc; v0 += RVT_MAX_VARIANTS) {
+    const int n = std::min(RVT_MAX_VARIANTS, ncols - v0);
+    rc = fam_bed_front(c, st, d_rows + cb * (size_t)v0, n, p, nullptr);
+    if (rc || !out) continue;
+    HIP_TRY(c, hipMemcpy2DAsync(out + (size_t)N * v0, sizeof(double) * (size_t)N, c->d_Gt, sizeof(double) * (size_t)ld,
+                                sizeof(double) * (size_t)N, (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, sync_stream(st));
   }
+  return rc;
+}
+}  // namespace
+
+// Test hook: the first ncols rows through the front stage, the rotated columns N x ncols to the host (cf. rvt_debug_rotate)
+int rvt_debug_rotate_bed(rvt_ctx* c, const unsigned char* d_rows, int ncols, double* out) {
+  if (!c || !d_rows || !out || ncols < 1) return fail(c, RVT_E_INVALID, "bad arguments");
+  int rc = fam_bed_check(c, "rvt_debug_rotate_bed");
+  if (rc) return rc;
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  return fam_bed_rotate_all(c, c->stream, d_rows, ncols, out);
+}
+
+// Measurement hook: the same front stage without the copy to the host, between two HIP events (cf. rvt_debug_rotate_timed)
+int rvt_debug_rotate_bed_timed(rvt_ctx* c, const unsigned char* d_rows, int ncols, double* ms) {
+  if (!c || !d_rows || !ms || ncols < 1) return fail(c, RVT_E_INVALID, "bad arguments");
+  int rc = fam_bed_check(c, "rvt_debug_rotate_bed_timed");
+  if (rc) return rc;
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(c, hipEventCreate(&ev[0]));
+  hipError_t e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+  if (e == hipSuccess) {
+    rc = fam_bed_rotate_all(c, st, d_rows, ncols, nullptr);
+    if (!rc) e = hipEventRecord(ev[1], st);
+    if (!rc && e == hipSuccess) e = sync_stream(st);
+    float t = 0.0f;
+    if (!rc && e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+    *ms = t;
+  }
+  hipEventDestroy(ev[0]);
+  if (ev[1]) hipEventDestroy(ev[1]);
+  if (rc) return rc;
+  HIP_TRY(c, e);
   return RVT_OK;
 }
 

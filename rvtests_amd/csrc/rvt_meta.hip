@@ -1586,6 +1586,14 @@ void bed_row_counts(hipStream_t st, const unsigned char* d_rows, long long cb, l
                      d_rows, cb, N, d_cnt);
 }
 
+// n_rows (at most 65 535) consecutive .bed rows as fp64 columns of leading dimension ld, missing calls -> d_mu[row]
+// (bed_expand_columns_kernel).  rvt_fam.hip's front stage over resident rows expands with it when U is column-compressed.
+void bed_rows_expand(hipStream_t st, const unsigned char* d_rows, long long cb, const double* d_mu, long long N, long long ld,
+                     int n_rows, double* G) {
+  hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)n_rows), dim3(256), 0, st, d_rows,
+                     cb, d_mu, N, ld, G);
+}
+
 int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int coding, double* dG, int col0, long long* counts) {
   if (!c || !d_rows || !dG || V < 0 || col0 < 0) return fail(c, RVT_E_INVALID, "bad recode");
   if (coding != RVT_CODING_DOMINANT && coding != RVT_CODING_RECESSIVE)

@@ -1254,6 +1254,51 @@ class Engine:
                                              *[_dp(a) for a in arr]))
         return dict(ok=ok, af=arr[0], null_ll=arr[1], alt_ll=arr[2], p=arr[3])
 
+    def score_bed_dev_fam(self, d_rows, V, binary=0, want_counts=True):
+        """score_block_fam's dict for V consecutive rows of a resident .bed matrix (rvt_score_bed_dev_fam: missing calls imputed
+        to the row's mean, nothing expanded to fp64 on the host), plus counts (V, 4): n0 n1 n2 missing (None without
+        want_counts).  After set_kinship* / kinship_from_bed(install=True) + fit_fam_null [+ fam_binary_scale]."""
+        V = int(V)
+        ok = np.zeros(V, dtype=np.int32)
+        arr = [np.zeros(V) for _ in range(4)]
+        cnt = np.zeros((V, 4), dtype=np.int64) if want_counts else None
+        self.L.rvt_score_bed_dev_fam.restype = C.c_int
+        self.L.rvt_score_bed_dev_fam.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, c_int_p] + [c_double_p] * 4 + [C.c_void_p]
+        self._check(self.L.rvt_score_bed_dev_fam(self.ctx, C.c_void_p(int(d_rows)), V, int(binary), ok.ctypes.data_as(c_int_p),
+                                                 *[_dp(a) for a in arr], cnt.ctypes.data_as(C.c_void_p) if want_counts else None))
+        return dict(ok=ok, U=arr[0], V=arr[1], af=arr[2], p=arr[3], counts=cnt)
+
+    def lrt_bed_dev_fam(self, d_rows, V, want_counts=True):
+        """lrt_block_fam's dict for V consecutive rows of a resident .bed matrix (rvt_lrt_bed_dev_fam), plus counts (V, 4):
+        n0 n1 n2 missing (None without want_counts)."""
+        V = int(V)
+        ok = np.zeros(V, dtype=np.int32)
+        arr = [np.zeros(V) for _ in range(4)]
+        cnt = np.zeros((V, 4), dtype=np.int64) if want_counts else None
+        self.L.rvt_lrt_bed_dev_fam.restype = C.c_int
+        self.L.rvt_lrt_bed_dev_fam.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, c_int_p] + [c_double_p] * 4 + [C.c_void_p]
+        self._check(self.L.rvt_lrt_bed_dev_fam(self.ctx, C.c_void_p(int(d_rows)), V, ok.ctypes.data_as(c_int_p),
+                                               *[_dp(a) for a in arr], cnt.ctypes.data_as(C.c_void_p) if want_counts else None))
+        return dict(ok=ok, af=arr[0], null_ll=arr[1], alt_ll=arr[2], p=arr[3], counts=cnt)
+
+    def debug_rotate_bed(self, d_rows, ncols):
+        """U'G of the first ncols rows of a resident .bed matrix as the two calls above form it, N x ncols
+        (rvt_debug_rotate_bed); rows in the installed eigenpair order."""
+        out = np.zeros((self.N, int(ncols)), order="F")
+        self.L.rvt_debug_rotate_bed.restype = C.c_int
+        self.L.rvt_debug_rotate_bed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, c_double_p]
+        self._check(self.L.rvt_debug_rotate_bed(self.ctx, C.c_void_p(int(d_rows)), int(ncols), _dp(out)))
+        return out
+
+    def debug_rotate_bed_timed(self, d_rows, ncols):
+        """Device milliseconds of that front stage on the first ncols rows (rvt_debug_rotate_bed_timed)."""
+        ms = C.c_double(0.0)
+        self.L.rvt_debug_rotate_bed_timed.restype = C.c_int
+        self.L.rvt_debug_rotate_bed_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, c_double_p]
+        self._check(self.L.rvt_debug_rotate_bed_timed(self.ctx, C.c_void_p(int(d_rows)), int(ncols),
+                                                      C.cast(C.byref(ms), c_double_p)))
+        return ms.value
+
     def fit_grammar_null(self, X, y):
         """GrammarGamma::FitNullModel on the installed kinship (rvt_fit_grammar_null)."""
         X = np.asfortranarray(X, dtype=np.float64)
