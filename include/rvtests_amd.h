@@ -1122,6 +1122,13 @@ int rvt_debug_suffstat(rvt_ctx* ctx, const double* dG, int M, double* S, double*
  * second one the second block's.  lambda and stats always describe the first block. */
 int rvt_debug_spectrum(rvt_ctx* ctx, const double* dG, int M, const double* af, const double* dG_beside, int M_beside,
                        const double* af_beside, rvt_gene_result* rec, double* lambda, double* stats);
+/* the statistics the SKAT permutation stage hands to its stop rule: arms a trace for the NEXT gene that runs that stage
+ * (rvt_run_blocks with skat_nperm > 0; a gene without a polymorphic column runs none), in either permutation mode.  The
+ * stage writes the statistic of every shuffle it ADDS, in order, to stats[0 .. cap) — what a chunk generated past the stop
+ * is not recorded —, then *n_written = min(ActualPerm, cap), and the trace is disarmed.  stats and n_written are host
+ * memory of the caller's and stay valid until that gene's call has returned.  stats == NULL disarms.  The gene's record is
+ * what it is without the trace. */
+int rvt_debug_perm_trace(rvt_ctx* ctx, double* stats, int cap, int* n_written);
 /* U'G as the family tests compute it: the first ncols columns of an uploaded block through the rotation with the installed
  * kinship (rvt_set_kinship, and a null model for the block layout); out is a host N x ncols matrix, column-major.  Row k
  * belongs to eigenpair k in the INSTALLED order (family-structured U: stably sorted by first non-zero row) */

@@ -112,6 +112,11 @@ void orc_rand_seed(unsigned seed);
 int orc_rand(void);
 int orc_skat_permute(const double* G, const double* af, int64_t N, int M, const double* res, double beta1,
                      double beta2, double obs, int nPerm, double alpha, int use_float, orc_perm_result* out);
+/* the same loop on the same stream, and a record of the first `cap` shuffles it adds: stats[s] = the statistic handed to the
+   stop rule, order[s * N + i] = which sample's residual stands at position i after shuffle s (either may be NULL) */
+int orc_skat_permute_trace(const double* G, const double* af, int64_t N, int M, const double* res, double beta1,
+                           double beta2, double obs, int nPerm, double alpha, int use_float, orc_perm_result* out,
+                           int cap, double* stats, int32_t* order);
 
 /* ---- related samples (orc_fam.cpp): FastLMM null model (MLE, score) and FamSKAT ----
         U: N x N column-major eigenvectors of the kinship, S: N eigenvalues (EigenMatrix holds them as float; here

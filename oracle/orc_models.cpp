@@ -930,8 +930,9 @@ extern "C" double orc_perm_stop_run(int nPerm, double alpha, double obs, const d
   return p.pvalue();
 }
 
-int orc_skat_permute(const double* Gp, const double* af, int64_t N, int M, const double* res, double beta1,
-                     double beta2, double obs, int nPerm, double alpha, int use_float, orc_perm_result* out) {
+int orc_skat_permute_trace(const double* Gp, const double* af, int64_t N, int M, const double* res, double beta1,
+                           double beta2, double obs, int nPerm, double alpha, int use_float, orc_perm_result* out,
+                           int cap, double* stats, int32_t* order) {
   Mat G0 = wrap(Gp, N, M);
   std::vector<int> fl, kp;
   Mat G = flip_poly(G0, &fl, &kp);
@@ -945,18 +946,27 @@ int orc_skat_permute(const double* Gp, const double* af, int64_t N, int M, const
     for (int64_t i = 0; i < N; ++i) Ks(j, i) = F(ws * F(G(i, j)));
   }
   std::vector<double> pr(res, res + N);
+  std::vector<int32_t> who(order ? N : 0);  // who[i]: the sample whose residual pr[i] is
+  for (size_t i = 0; i < who.size(); ++i) who[i] = (int32_t)i;
   PermStop stop;
   stop.init(nPerm, alpha, obs);
   while (stop.next()) {
     for (int64_t i = N - 1; i >= 1; --i) {
       const int64_t j = orc_rand() % (i + 1);
-      if (i != j) std::swap(pr[i], pr[j]);
+      if (i != j) {
+        std::swap(pr[i], pr[j]);
+        if (order) std::swap(who[i], who[j]);
+      }
     }
     double Q = 0;
     for (int j = 0; j < m; ++j) {
       double s = 0;
       for (int64_t i = 0; i < N; ++i) s = F(s + F(Ks(j, i) * F(pr[i])));
       Q = F(Q + F(s * s));
+    }
+    if (stop.actualPerm < cap) {
+      if (stats) stats[stop.actualPerm] = Q;
+      if (order) std::memcpy(order + (size_t)stop.actualPerm * N, who.data(), sizeof(int32_t) * (size_t)N);
     }
     stop.add(Q);
   }
@@ -967,6 +977,11 @@ int orc_skat_permute(const double* Gp, const double* af, int64_t N, int M, const
   out->threshold = stop.threshold;
   out->pvalue = stop.pvalue();
   return 0;
+}
+
+int orc_skat_permute(const double* Gp, const double* af, int64_t N, int M, const double* res, double beta1,
+                     double beta2, double obs, int nPerm, double alpha, int use_float, orc_perm_result* out) {
+  return orc_skat_permute_trace(Gp, af, N, M, res, beta1, beta2, obs, nPerm, alpha, use_float, out, 0, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

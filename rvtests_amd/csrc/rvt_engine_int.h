@@ -421,6 +421,11 @@ struct rvt_ctx {
   DevBuf<uint32_t> d_perm_states;   // B x 31
   DevBuf<double> d_perm_R, d_perm_C, d_perm_Q, d_perm_cur;
   int perm_cap_B = 0;
+  // rvt_debug_perm_trace (test-only): where the next SKAT permutation stage writes the statistics it hands to the stop rule
+  // (caller-owned host memory; perm_stage takes the three over and clears them)
+  double* perm_trace_stats = nullptr;
+  int perm_trace_cap = 0;
+  int* perm_trace_n = nullptr;
   hipEvent_t ev_in[kSlots] = {}, ev_k2[kSlots] = {}, ev_k2b[kSlots] = {};
   // The p-value kernel on CUs of its own (RVT_PV_CUS, see rvt_init): two streams restricted to the first pv_cus mask bits,
   // used by alternate batches; the batch's stream hands over by event and takes the records back by event.

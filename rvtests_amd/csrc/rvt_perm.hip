@@ -55,6 +55,25 @@ static int exact_chunk(int nPerm, int64_t N) {
   return std::max(1, std::min(nPerm, (int)std::min<int64_t>(2048, ((int64_t)6 << 30) / (8 * N))));
 }
 
+// rvt_debug_perm_trace: the statistics a SKAT permutation stage hands to the stop rule, in order, into the caller's array
+struct PermTrace {
+  double* stats = nullptr;
+  int cap = 0;
+  int* n_written = nullptr;
+  void add(int actual, double q) const {  // after ++actual
+    if (stats && actual <= cap) stats[actual - 1] = q;
+  }
+  void done(int actual) const {
+    if (n_written) *n_written = std::min(actual, cap);
+  }
+};
+static PermTrace take_perm_trace(rvt_ctx* c) {  // (and disarm: one gene per arming)
+  PermTrace t;
+  t.stats = c->perm_trace_stats, t.cap = c->perm_trace_cap, t.n_written = c->perm_trace_n;
+  c->perm_trace_stats = nullptr, c->perm_trace_cap = 0, c->perm_trace_n = nullptr;
+  return t;
+}
+
 // The exact-mode permutation test shared by the SKAT and the variable-threshold stage: cumulative Fisher-Yates shuffles of
 // the vector d_start (N doubles on the device) on the emulated rand() stream, a chunk of B = exact_chunk() at a time.
 // stat(nb, B, &d_out) launches, on the context's stream, what turns the chunk's permuted vectors (columns of d_perm_R,
@@ -63,10 +82,11 @@ static int exact_chunk(int nPerm, int64_t N) {
 // On return the stream stands behind the shuffles PERFORMED, whatever the chunk generated beyond them.
 // failed_ (optional, Madsen-Browning's loop, src/Model.h:1286-1299): a statistic below zero is a failed TestCovariate — the
 // shuffle is drawn but not added; the eleventh ends the test with *failed_ = 11.
+// trace (optional): rvt_debug_perm_trace's record of the statistics added.
 extern "C++" {  // (this unit's functions sit inside extern "C"; a template cannot)
 template <class Stat>
 int exact_permutations(rvt_ctx* c, const double* d_start, int nPerm, double alpha, double obs, int m, Stat&& stat, int* actual_,
-                       int* numX_, int* numEq_, int* failed_ = nullptr) {
+                       int* numX_, int* numEq_, int* failed_ = nullptr, const PermTrace* trace = nullptr) {
   const int64_t N = c->nc.N;
   hipStream_t st = c->stream;
   // chunk buffers
@@ -141,6 +161,7 @@ int exact_permutations(rvt_ctx* c, const double* d_start, int nPerm, double alph
         break;
       }
       ++actual;  // Permutation::add
+      if (trace) trace->add(actual, Q[used]);
       if (Q[used] > obs) ++numX;
       if (Q[used] == obs) ++numEq;
     }
@@ -151,6 +172,7 @@ int exact_permutations(rvt_ctx* c, const double* d_start, int nPerm, double alph
     }
   }
   std::memcpy(c->rand_state, s0, sizeof(s0));
+  if (trace) trace->done(actual);
   *actual_ = actual, *numX_ = numX, *numEq_ = numEq;
   return RVT_OK;
 }
@@ -162,6 +184,7 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
   const int64_t N = c->nc.N, ld = c->nc.ld;
   const int nPerm = prm.skat_nperm;
   hipStream_t st = c->stream;
+  const PermTrace trace = take_perm_trace(c);
   // flipped, polymorphic genotype block (K_sqrt = diag(w^1/2) G', Skat.cpp:42-47)
   std::vector<const double*> cols(M);
   for (int j = 0; j < M; ++j) cols[j] = dG + (size_t)j * ld;
@@ -229,10 +252,12 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
           break;
         }
         ++actual;  // Permutation::add
+        trace.add(actual, Q[u]);
         if (Q[u] > obs) ++numX;
         if (Q[u] == obs) ++numEq;
       }
     }
+    trace.done(actual);
     r->perm_ok = 1;
     r->perm_num_perm = nPerm;
     r->perm_actual_perm = actual;
@@ -258,7 +283,7 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
         *d_out = c->d_perm_Q;
         return RVT_OK;
       },
-      &actual, &numX, &numEq);
+      &actual, &numX, &numEq, nullptr, &trace);
   if (rc) return rc;
   r->perm_ok = 1;
   r->perm_num_perm = nPerm;
@@ -1144,6 +1169,17 @@ int rvt_rand_seed(rvt_ctx* c, unsigned seed) {
 int rvt_set_perm_exact(rvt_ctx* c, int on) {
   if (!c) return RVT_E_INVALID;
   c->perm_exact = on != 0;
+  return RVT_OK;
+}
+
+// Test hook: arm (stats == NULL: disarm) the trace of the next gene's SKAT permutation stage
+int rvt_debug_perm_trace(rvt_ctx* c, double* stats, int cap, int* n_written) {
+  if (!c) return RVT_E_INVALID;
+  if (stats && (cap < 0 || !n_written)) return fail(c, RVT_E_INVALID, "bad arguments");
+  c->perm_trace_stats = stats;
+  c->perm_trace_cap = stats ? cap : 0;
+  c->perm_trace_n = stats ? n_written : nullptr;
+  if (stats) *n_written = 0;
   return RVT_OK;
 }
 

@@ -218,6 +218,8 @@ def load_library():
     L.rvt_debug_spectrum.restype = C.c_int
     L.rvt_debug_spectrum.argtypes = [vp, vp, C.c_int, c_double_p, vp, C.c_int, c_double_p, C.POINTER(GeneResult), c_double_p,
                                      c_double_p]
+    L.rvt_debug_perm_trace.restype = C.c_int
+    L.rvt_debug_perm_trace.argtypes = [vp, c_double_p, C.c_int, c_int_p]
     L.rvt_fit_null.restype = C.c_int
     L.rvt_fit_null.argtypes = [vp, C.c_int, C.c_int64, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]
     L.rvt_rand_seed.restype = C.c_int
@@ -1089,6 +1091,20 @@ class Engine:
         n_skat, n_zimz, o_skat, o_zimz = (int(stats[k]) for k in (60, 59, 61, 62))
         return dict(rec=rec[0], beside_rec=rec[1] if beside is not None else None, stats=stats,
                     lam=lam[o_skat:o_skat + n_skat].copy(), lam_zimz=lam[o_zimz:o_zimz + n_zimz].copy())
+
+    def debug_perm_trace(self, cap):
+        """Arm the trace of the next gene that runs the SKAT permutation stage (rvt_debug_perm_trace); cap = None disarms.
+        Returns a function: called after that gene's run_blocks has returned, it gives the statistics the stage handed to
+        its stop rule, in order (at most cap of them).  The engine keeps the buffer alive until the next arming."""
+        if cap is None:
+            self._check(self.L.rvt_debug_perm_trace(self.ctx, None, 0, None))
+            self._perm_trace = None
+            return None
+        buf = np.zeros(max(int(cap), 1))
+        n = C.c_int(0)
+        self._perm_trace = (buf, n)
+        self._check(self.L.rvt_debug_perm_trace(self.ctx, _dp(buf), int(cap), C.byref(n)))
+        return lambda: buf[:n.value].copy()
 
     def debug_rotate(self, ptr, ncols):
         """U'G of the first ncols columns of a device block, N x ncols (rvt_debug_rotate); rows in the installed eigenpair

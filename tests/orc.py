@@ -425,6 +425,38 @@ def skat_permute(G, af, res, obs, n_perm, alpha, b1=1.0, b2=25.0, use_float=Fals
     return rc, out
 
 
+def skat_permute_trace(G, af, res, obs, n_perm, alpha, cap, want_order=True, b1=1.0, b2=25.0):
+    """skat_permute with a record of the first `cap` shuffles it adds: (rc, PermResult, stats[n], order[n, N]) with
+    n = min(actual_perm, cap); order[s, i] = the sample whose residual stands at position i after shuffle s (None unless
+    want_order).  Consumes the oracle's stream exactly as skat_permute does."""
+    G = F(G)
+    N, M = G.shape
+    af = np.ascontiguousarray(af, dtype=np.float64)
+    res = np.ascontiguousarray(res, dtype=np.float64)
+    out = PermResult()
+    stats = np.zeros(max(cap, 1))
+    order = np.zeros((max(cap, 1), N), dtype=np.int32) if want_order else None
+    L = lib()
+    L.orc_skat_permute_trace.restype = C.c_int
+    L.orc_skat_permute_trace.argtypes = L.orc_skat_permute.argtypes + [C.c_int, c_double_p, C.POINTER(C.c_int32)]
+    rc = L.orc_skat_permute_trace(_dp(G), _dp(af), C.c_int64(N), M, _dp(res), float(b1), float(b2), float(obs), int(n_perm),
+                                  float(alpha), 0, C.byref(out), int(cap), _dp(stats),
+                                  order.ctypes.data_as(C.POINTER(C.c_int32)) if want_order else None)
+    n = min(out.actual_perm, cap) if rc == 0 else 0
+    return rc, out, stats[:n], (order[:n] if want_order else None)
+
+
+def perm_stop_run(n_perm, alpha, obs, stats):
+    """Permutation's stop rule fed with stats in order: (actual_perm, num_x, num_equal, pvalue)."""
+    stats = np.ascontiguousarray(stats, dtype=np.float64)
+    out3 = np.zeros(3, dtype=np.int32)
+    L = lib()
+    L.orc_perm_stop_run.restype = C.c_double
+    L.orc_perm_stop_run.argtypes = [C.c_int, C.c_double, C.c_double, c_double_p, C.c_int, c_int_p]
+    p = L.orc_perm_stop_run(int(n_perm), float(alpha), float(obs), _dp(stats), int(stats.size), _ip(out3))
+    return int(out3[0]), int(out3[1]), int(out3[2]), p
+
+
 def metacov_fam(G, chrom, pos, X, U, S, nul, window, use_float=False):
     G = F(G)
     X = F(X)

@@ -1,11 +1,17 @@
 """SKAT permutation p-values through the C ABI.  Exact mode (rvt_set_perm_exact): the same emulated glibc rand() stream as
 the oracle, so the permutations — and with them ActualPerm / NumGreater / NumEqual — are identical, gene after gene.
 Counter-based mode (the default): other random numbers, the same estimator — compared with the exact mode within binomial
-error."""
+error.
+
+The second half holds both modes against tests/permref.py shuffle by shuffle (Engine.debug_perm_trace hands out the statistics
+the stop rule consumed), on the cases of tests/perm_cases.py: the routes a large cohort takes — the integer-plane product beyond
+2048 samples, several 2048-shuffle chunks on one stream, the counter-based kernel at sizes around its groups, slices and
+passes.  tests/test_perm_ref_cpu.py proves the premises (the tie condition) from the reference alone."""
 import numpy as np
 import pytest
 
 import orc
+import perm_cases as pc
 import synth
 
 pytestmark = pytest.mark.gpu
@@ -139,3 +145,158 @@ def test_a_context_whose_null_model_grows_keeps_no_buffer_of_the_old_size(eng, e
         if fresh:
             e.close()
     assert outs[0] == outs[1] and all(t[2] > 0 for t in outs[0])
+
+
+# ---- shuffle by shuffle against tests/permref.py ------------------------------------------------------------------------------
+LD = np.longdouble
+
+
+def _within_bound(Qdev, ref, what):
+    """Every traced statistic lies inside the reference's a-priori bound; returns (and prints) the largest |dQ| / bound."""
+    n = Qdev.size
+    assert n <= ref.st.Q.size, what
+    ratio = np.abs(Qdev.astype(LD) - ref.st.Q[:n]) / ref.dQ[:n]
+    worst = float(ratio.max()) if n else 0.0
+    print("%s: %d shuffles, largest |Q_dev - Q_ref| / bound = %.3g (at shuffle %d)" % (what, n, worst, int(ratio.argmax()) if n else -1))
+    assert worst <= 1.0, (what, worst, int(ratio.argmax()))
+    return worst
+
+
+def _fields(r):
+    vals = [(f[0], getattr(r, f[0])) for f in r._fields_]
+    return [(k, v if v == v else "nan") for k, v in vals]      # (a NaN field equals itself here)
+
+
+def _upload(eng, genes):
+    return [eng.upload_block(G) for G, af in genes], [G.shape[1] for G, af in genes], [af for G, af in genes]
+
+
+def _check_exact_gene(r, ref, n_perm):
+    p = ref.perm
+    assert abs(r.skat_Q - ref.obs) <= pc.OBS_TOL * ref.obs
+    assert r.perm_ok == 1 and r.perm_num_perm == n_perm
+    assert (r.perm_actual_perm, r.perm_num_greater, r.perm_num_equal) == (p.actual_perm, p.num_x, p.num_equal)
+    assert r.perm_pvalue == p.pvalue
+
+
+@pytest.mark.parametrize("N", pc.SWITCH_N)
+def test_exact_mode_matches_the_oracle_on_both_sides_of_the_2048_sample_switch(eng, N):
+    """Five genes on one stream at N = 2048 (sample-order sums), 2049 (the integer planes, the last K chunk 127 rows of
+    padding) and 4100: counters and p-value equal the oracle's gene after gene, and every statistic of the M = 21 gene (six
+    digit planes) lies inside the bound of its route."""
+    import rvtests_amd
+    genes, (X, y, res, v, s2), refs = pc.switch_case(N)
+    eng.set_null(0, X, res, v, s2)
+    eng.set_perm_exact(True)
+    eng.rand_seed(pc.SWITCH_SEED)
+    prm = rvtests_amd.Params(1.0, 25.0, 1.0, 25.0, pc.SWITCH_NPERM, pc.SWITCH_ALPHA)
+    ptrs, Ms, afs = _upload(eng, genes)
+    t = pc.SWITCH_TRACED
+    out = eng.run_blocks(ptrs[:t], Ms[:t], afs[:t], tests=rvtests_amd.TEST_SKAT, params=prm)
+    trace = eng.debug_perm_trace(pc.SWITCH_NPERM)          # (one arming = one gene: the stream goes on over the two calls)
+    out += eng.run_blocks(ptrs[t:], Ms[t:], afs[t:], tests=rvtests_amd.TEST_SKAT, params=prm)
+    for r, ref in zip(out, refs):
+        if ref.obs is None:
+            assert r.skat_ok == 0 and r.perm_ok == 0
+        else:
+            _check_exact_gene(r, ref, pc.SWITCH_NPERM)
+    Qdev = trace()
+    assert Qdev.size == refs[t].perm.actual_perm
+    _within_bound(Qdev, refs[t], "switch N=%d, route %s" % (N, refs[t].route))
+
+
+@pytest.mark.parametrize("N", pc.CHUNKS_N)
+def test_exact_mode_carries_vector_and_stream_across_chunks(eng, N):
+    """Three genes on one stream: 5000 shuffles that never stop (chunks of 2048 + 2048 + 904, all traced), 5000 that stop inside
+    the second chunk, and 200 more that only match the oracle if the stream stood behind the shuffles PERFORMED."""
+    import rvtests_amd
+    genes, (X, y, res, v, s2), refs = pc.chunks_case(N)
+    assert 2048 < refs[1].perm.actual_perm < 4096
+    eng.set_null(0, X, res, v, s2)
+    eng.set_perm_exact(True)
+    eng.rand_seed(pc.CHUNKS_SEED)
+    ptrs, Ms, afs = _upload(eng, genes)
+    trace = eng.debug_perm_trace(pc.CHUNKS_RUNS[0][0])
+    for k, (n_perm, alpha) in enumerate(pc.CHUNKS_RUNS):
+        prm = rvtests_amd.Params(1.0, 25.0, 1.0, 25.0, n_perm, alpha)
+        r = eng.run_blocks(ptrs[k:k + 1], Ms[k:k + 1], afs[k:k + 1], tests=rvtests_amd.TEST_SKAT, params=prm, ids=[k])[0]
+        _check_exact_gene(r, refs[k], n_perm)
+    Qdev = trace()
+    assert Qdev.size == 5000
+    _within_bound(Qdev, refs[0], "chunks N=%d, route %s" % (N, refs[0].route))
+    for s in (2047, 2048, 4095, 4096):                      # (named: both sides of either chunk boundary)
+        assert abs(LD(Qdev[s]) - refs[0].st.Q[s]) <= refs[0].dQ[s]
+
+
+def _run_counter(eng, ptr, M, af, ref):
+    import rvtests_amd
+    prm = rvtests_amd.Params(1.0, 25.0, 1.0, 25.0, ref.n_perm, ref.alpha)
+    trace = eng.debug_perm_trace(ref.n_perm)
+    r = eng.run_blocks([ptr], [M], [af], tests=rvtests_amd.TEST_SKAT, params=prm, ids=[ref.gene_id])[0]
+    assert abs(r.skat_Q - ref.obs) <= pc.OBS_TOL * ref.obs
+    assert r.perm_ok == 1 and r.perm_num_perm == ref.n_perm and r.gene_id == ref.gene_id
+    return r, trace()
+
+
+@pytest.mark.parametrize("N,m", pc.COUNTER_SIZES)
+def test_counter_based_mode_shuffle_by_shuffle(eng, N, m):
+    """perm_counter_partial_kernel / perm_counter_q_kernel against the long-double product of the same keyed shuffles: a run of
+    100 shuffles (36 live rows in the last 64-shuffle block) and one of 2300 (the second chunk starts at shuffle 2048), every
+    statistic inside gamma_N, the counters those of the stop rule on the reference's statistics."""
+    (G, af), (X, y, res, v, s2), refs = pc.counter_case(N, m)
+    eng.set_null(0, X, res, v, s2)
+    eng.set_perm_exact(False)
+    eng.rand_seed(pc.COUNTER_SEED)
+    ptr = eng.upload_block(G)
+    for ref in refs:
+        r, Qdev = _run_counter(eng, ptr, G.shape[1], af, ref)
+        assert Qdev.size == ref.n_perm
+        _within_bound(Qdev, ref, "counter N=%d m=%d nPerm=%d" % (N, m, ref.n_perm))
+        assert (r.perm_actual_perm, r.perm_num_greater, r.perm_num_equal, r.perm_pvalue) == ref.counters
+
+
+def test_counter_based_mode_short_first_chunk_and_early_stop(eng):
+    """alpha = 0.05 of 1000: the first chunk is 250 shuffles, the gene stops in the second one (which starts at shuffle 250)."""
+    (G, af), (X, y, res, v, s2), ref = pc.counter_stop_case()
+    assert 250 < ref.counters[0] < ref.n_perm
+    eng.set_null(0, X, res, v, s2)
+    eng.set_perm_exact(False)
+    eng.rand_seed(pc.COUNTER_SEED)
+    r, Qdev = _run_counter(eng, eng.upload_block(G), G.shape[1], af, ref)
+    assert Qdev.size == ref.counters[0]                     # what the chunk generated past the stop is not recorded
+    _within_bound(Qdev, ref, "counter stop")
+    assert (r.perm_actual_perm, r.perm_num_greater, r.perm_num_equal, r.perm_pvalue) == ref.counters
+
+
+@pytest.mark.parametrize("exact", [True, False])
+def test_the_armed_trace_changes_no_record(eng, exact):
+    """The same genes unarmed, armed, and armed-then-disarmed: records equal field for field, a short buffer is not overrun,
+    a disarmed one is not written."""
+    import rvtests_amd
+    if exact:
+        genes, (X, y, res, v, s2), refs = pc.switch_case(2049)
+        genes, n_perm, alpha, seed = genes[:3], pc.SWITCH_NPERM, pc.SWITCH_ALPHA, pc.SWITCH_SEED
+    else:
+        (G, af), (X, y, res, v, s2), ref = pc.counter_stop_case()
+        genes, n_perm, alpha, seed = [(G, af)], ref.n_perm, ref.alpha, pc.COUNTER_SEED
+    eng.set_null(0, X, res, v, s2)
+    eng.set_perm_exact(exact)
+    prm = rvtests_amd.Params(1.0, 25.0, 1.0, 25.0, n_perm, alpha)
+    ptrs, Ms, afs = _upload(eng, genes)
+    ids = [77 + 5 * k for k in range(len(genes))]
+    runs = []
+    for mode in ("unarmed", "armed", "short", "disarmed"):
+        eng.rand_seed(seed)
+        trace = eng.debug_perm_trace({"armed": n_perm, "short": 7, "disarmed": n_perm}[mode]) if mode != "unarmed" else None
+        if mode == "disarmed":
+            assert eng.debug_perm_trace(None) is None
+        out = eng.run_blocks(ptrs, Ms, afs, tests=rvtests_amd.TEST_SKAT, params=prm, ids=ids)
+        runs.append([_fields(r) for r in out])
+        if mode == "armed":                                 # the first gene of the call was traced, and only that one
+            full = trace()
+            assert full.size == out[0].perm_actual_perm > 7
+        elif mode == "short":
+            assert np.array_equal(trace(), full[:7])
+        elif mode == "disarmed":
+            assert trace().size == 0
+    assert runs[0] == runs[1] == runs[2] == runs[3]
