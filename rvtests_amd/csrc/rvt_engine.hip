@@ -566,7 +566,7 @@ int rvt_block_classify(rvt_ctx* c, const double* dG, int M, int* is_hard_call) {
   if (!c->have_null && !c->have_fam) return fail(c, RVT_E_STATE, "set the null model first (defines N)");
   hipSetDevice(c->device);
   const int64_t N = block_dims(c).N, ld = block_dims(c).ld;
-  HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int)));
+  HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int), c->io_stream, true));
   int rc = enqueue_classify(c, dG, M, N, ld, c->io_stream, c->d_kind);
   if (rc) return rc;
   int flag = 0;
@@ -1708,6 +1708,9 @@ static int cov_tail(rvt_ctx* c, Batch& b) {
   const bool bur = cov->fam && cov->ustat;
   hipLaunchKernelGGL(cov_prepare_kernel, dim3(1), dim3(256), 0, st, b.d_desc, cc, d_xz, d_cs, d_poly,
                      bur ? d_bur : (double*)nullptr, bur ? d_bur + 2 * (size_t)V : (double*)nullptr);
+  // (the rows kernel writes cov[h, j] for j >= h only; the caller gets the whole square: zeros below the diagonal, not what an
+  //  earlier batch left in the arena)
+  if (cov->cov) HIP_TRY(c, hipMemsetAsync(d_cov, 0, sizeof(double) * (size_t)V * V, st));
   hipLaunchKernelGGL(cov_rows_kernel, dim3(V), dim3(256), 0, st, b.d_desc, cc, d_xz, d_cs, d_cov);
   if (bur)
     hipLaunchKernelGGL(fam_burden_finish_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, st, d_cov, V, d_bur,

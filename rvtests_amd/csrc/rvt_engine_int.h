@@ -107,8 +107,12 @@ struct DevBuf {
   // Grow-only: when fewer than `need` bytes are held, the old block is freed (after `sync` has drained, when given: its last
   // reader may still be queued there) and `want` bytes are allocated — uninitialised, or filled with the RVT_POISON byte
   // when `poison` is set (tests: no result may depend on what a fresh allocation happens to hold).
-  hipError_t grow(size_t need, size_t want, hipStream_t sync = nullptr, bool poison = false, unsigned flags = 0) {
-    if (cap >= need) return hipSuccess;
+  // A block that is already large enough is handed over as the last call left it — unless RVT_SCRIBBLE=<byte> is set (tests:
+  // no result may depend on what an earlier call left in a work space): a `poison` request then refills it (scribble).
+  // `what` names the buffer in the trace of the refills.
+  hipError_t grow(size_t need, size_t want, hipStream_t sync = nullptr, bool poison = false, unsigned flags = 0,
+                  const char* what = nullptr) {
+    if (cap >= need) return poison ? scribble(sync, what) : hipSuccess;
     hipError_t e = (p && sync) ? sync_stream(sync) : hipSuccess;
     if (e == hipSuccess) e = reset();
     if (e != hipSuccess) return e;
@@ -121,6 +125,23 @@ struct DevBuf {
     // overwrote the first results written into the block.  Without a stream the blocking fill stays as it was.
     if (const char* v = poison ? getenv("RVT_POISON") : nullptr)
       e = sync ? hipMemsetAsync(q, atoi(v) & 0xff, want, sync) : hipMemset(q, atoi(v) & 0xff, want);
+    return e;
+  }
+  // RVT_SCRIBBLE=<byte> (tests; a no-op otherwise): fill the WHOLE held block with the byte, on `st` — the stream the block's
+  // users run on: behind the last reader of the previous call, in front of the first kernel of this one —, or, without a
+  // stream, blocking between two drains of the device.  RVT_SCRIBBLE_TRACE=1 prints one line per refill to stderr.
+  hipError_t scribble(hipStream_t st, const char* what = nullptr) {
+    const char* v = p ? getenv("RVT_SCRIBBLE") : nullptr;
+    if (!v) return hipSuccess;
+    hipError_t e;
+    if (st) {
+      e = hipMemsetAsync((void*)p, atoi(v) & 0xff, cap, st);
+    } else {
+      e = hipDeviceSynchronize();
+      if (e == hipSuccess) e = hipMemset((void*)p, atoi(v) & 0xff, cap);
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    if (getenv("RVT_SCRIBBLE_TRACE")) fprintf(stderr, "rvt: scribble %s %zu bytes\n", what ? what : "-", cap);
     return e;
   }
   hipError_t alloc(size_t bytes, unsigned flags = 0) {  // a fresh block of `bytes`
@@ -617,7 +638,7 @@ int fail(rvt_ctx* c, int code, const char* fmt, ...) {
 
 // a slot's work space and pinned staging: grow-only, the old block freed once the slot's last batch has finished with it
 int ensure_arena(rvt_ctx* c, Slot& sl, size_t bytes) {
-  HIP_TRY(c, sl.arena.grow(bytes, bytes + bytes / 4, sl.stream, true));
+  HIP_TRY(c, sl.arena.grow(bytes, bytes + bytes / 4, sl.stream, true, 0, "arena"));
   return RVT_OK;
 }
 int ensure_stage(rvt_ctx* c, Slot& sl, size_t bytes) {

@@ -40,13 +40,20 @@ int ensure_fam_cols(rvt_ctx* c, size_t T, int64_t ld) {
   // (the capacity is columns OF THIS LEADING DIMENSION: a context whose null model was replaced by one with more samples
   //  otherwise kept buffers of the old column length — a memory fault in the permutation stage, found in round 6)
   const size_t cols = c->fam_cols_ld ? c->d_Gp.cap / (sizeof(double) * (size_t)c->fam_cols_ld) : 0;  // columns held
-  if (T <= cols && ld <= c->fam_cols_ld) return RVT_OK;
+  // Both are work spaces of the call that asks — every caller asks before it writes them, and runs on the context's stream —, so
+  // they take DevBuf::grow's test fills (RVT_POISON on allocation, RVT_SCRIBBLE on a block that is large enough) on that stream.
+  if (T <= cols && ld <= c->fam_cols_ld) {
+    HIP_TRY(c, c->d_Gp.scribble(c->stream, "d_Gp"));
+    HIP_TRY(c, c->d_Gt.scribble(c->stream, "d_Gt"));
+    return RVT_OK;
+  }
   c->d_Gp.reset();
   c->d_Gt.reset();
   const size_t want = std::max(T + T / 4, cols);
   c->fam_cols_ld = 0;
-  HIP_TRY(c, c->d_Gp.alloc(sizeof(double) * (size_t)ld * want));
-  HIP_TRY(c, c->d_Gt.alloc(sizeof(double) * (size_t)ld * want));
+  const size_t bytes = sizeof(double) * (size_t)ld * want;
+  HIP_TRY(c, c->d_Gp.grow(bytes, bytes, c->stream, true));
+  HIP_TRY(c, c->d_Gt.grow(bytes, bytes, c->stream, true));
   c->fam_cols_ld = ld;
   return RVT_OK;
 }
@@ -349,11 +356,11 @@ struct QuantCols {       // digit planes of a set of columns, in a context-owned
   std::vector<int> sexp;  // per column: entries were scaled by 2^sexp
 };
 
-int ensure_rot_scratch(rvt_ctx* c) {
-  if (!c->d_rot_scale) {
-    HIP_TRY(c, c->d_rot_scale.alloc(sizeof(double) * 4 * kRotMaxCols));  // col | max | row | spare
-    HIP_TRY(c, c->d_rot_sexp.alloc(sizeof(int) * kRotMaxCols));
-  }
+// (work spaces of the call that asks, on its stream: both callers write what they read — scales, maxima, exponents — behind this
+//  and keep nothing here between calls, so the blocks take grow's test fills)
+int ensure_rot_scratch(rvt_ctx* c, hipStream_t st) {
+  HIP_TRY(c, c->d_rot_scale.grow(sizeof(double) * 4 * kRotMaxCols, sizeof(double) * 4 * kRotMaxCols, st, true, 0, "d_rot_scale"));  // col | max | row | spare
+  HIP_TRY(c, c->d_rot_sexp.grow(sizeof(int) * kRotMaxCols, sizeof(int) * kRotMaxCols, st, true, 0, "d_rot_sexp"));
   return RVT_OK;
 }
 
@@ -361,7 +368,7 @@ int ensure_rot_scratch(rvt_ctx* c) {
 // [plane][column (padded to `pad`)][ldk].  One plane when every column holds integers in [-127, 127], else kRotPlanesG.
 int quantize_columns(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld_src, int ncols, int pad, int64_t ldk,
                      DevBuf<signed char>& buf, hipStream_t st, QuantCols* out, bool known_hard_calls = false) {
-  int rc = ensure_rot_scratch(c);
+  int rc = ensure_rot_scratch(c, st);
   if (rc) return rc;
   double* d_max = c->d_rot_scale + kRotMaxCols;
   std::vector<double> cmax(ncols, 2.0);  // (hard calls: 0 / 1 / 2, no scan needed)
@@ -384,7 +391,7 @@ int quantize_columns(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld
   const int64_t cols_pad = ((int64_t)ncols + pad - 1) / pad * pad;
   out->plane_stride = (size_t)cols_pad * (size_t)ldk;
   const size_t need = out->plane_stride * PG;
-  HIP_TRY(c, buf.grow(need, need + need / 4));
+  HIP_TRY(c, buf.grow(need, need + need / 4, st, true));
   out->d = buf;
   HIP_TRY(c, hipMemsetAsync(out->d, 0, need, st));
   HIP_TRY(c, hipMemcpyAsync(c->d_rot_sexp, out->sexp.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
@@ -399,7 +406,7 @@ int quantize_columns(rvt_ctx* c, const double* d_src, int64_t n_rows, int64_t ld
 int planes_gemm(rvt_ctx* c, const signed char* A, size_t a_stride, int PA, int nA, const int* row_exp, int a_exp,
                 const signed char* B, size_t b_stride, int PB, int nB, const int* col_exp, int64_t n_rows, int64_t ldk,
                 double* C, int64_t ldc, hipStream_t st, const int2* a_krange = nullptr) {
-  int rc = ensure_rot_scratch(c);
+  int rc = ensure_rot_scratch(c, st);
   if (rc) return rc;
   std::vector<double> cs(nB), rs;
   for (int j = 0; j < nB; ++j) cs[j] = std::ldexp(1.0, -((row_exp ? 0 : a_exp) + (col_exp ? col_exp[j] : 0)));
@@ -436,7 +443,7 @@ int planes_gemm(rvt_ctx* c, const signed char* A, size_t a_stride, int PA, int n
   if (slices > 1) {
     c_slice = (long long)ldc * nB;
     const size_t need = sizeof(double) * (size_t)c_slice * (size_t)slices;
-    HIP_TRY(c, c->d_rot_part.grow(need, need));
+    HIP_TRY(c, c->d_rot_part.grow(need, need, st, true));
     d_part = c->d_rot_part;
   }
   if (a_krange && !row_exp) {
@@ -718,7 +725,8 @@ int rvt_fit_fam_null(rvt_ctx* c, int64_t N, int d, const double* X, const double
   HIP_TRY(c, d_abs.alloc(sizeof(double) * N));
   HIP_TRY(c, hipMemcpy(d_abs, absS.data(), sizeof(double) * N, hipMemcpyHostToDevice));
   const int rec = lmm_rec_len(d);
-  HIP_TRY(c, c->d_lmm_part.alloc(sizeof(double) * (size_t)kLmmBlocks * rec));
+  // (reset above: a fresh block per fit, with grow's poison fill)
+  HIP_TRY(c, c->d_lmm_part.grow(sizeof(double) * (size_t)kLmmBlocks * rec, sizeof(double) * (size_t)kLmmBlocks * rec, st, true));
   std::vector<double> part((size_t)kLmmBlocks * rec), sums(rec);
   std::vector<double> beta(d, 0.0);
   double sigma2 = 0.0;
@@ -1207,7 +1215,7 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
   // column pointer / flag lists of the batch: one grow-only allocation of the context (no hipMalloc / hipFree per batch)
   {
     const size_t need = (sizeof(double*) + sizeof(int)) * tot * 2 + 64;
-    HIP_TRY(c, c->d_fam_list.grow(need, need + need / 2));
+    HIP_TRY(c, c->d_fam_list.grow(need, need + need / 2, st, true));
   }
   const double** d_cols = reinterpret_cast<const double**>(c->d_fam_list.get());
   int* d_flags = reinterpret_cast<int*>(c->d_fam_list + sizeof(double*) * tot * 2);
@@ -1293,7 +1301,7 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
       const int ncp = (int)std::min<size_t>(kRotMaxCols, T - c0);
       const int64_t cols_pad = ((int64_t)ncp + kRotBN - 1) / kRotBN * kRotBN;
       const size_t need = (size_t)cols_pad * (size_t)ldk;
-      HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
+      HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
       HIP_TRY(c, hipMemsetAsync(c->d_rotB, 0, need, st));
       hipLaunchKernelGGL(fam_flip_quant_kernel, dim3(64, (unsigned)ncp), dim3(256), 0, st, d_cols + tot + c0,
                          d_flags + tot + c0, (long long)N, (long long)ldk, c->d_rotB);
@@ -1513,8 +1521,9 @@ int lrt_prepare(rvt_ctx* c, hipStream_t st, LrtWs* w) {
                o_cs = L.take(sizeof(double) * MV), o_poly = L.take(sizeof(int) * MV), o_ok = L.take(sizeof(int) * MV),
                o_af = L.take(sizeof(double) * MV), o_nll = L.take(sizeof(double) * MV), o_all = L.take(sizeof(double) * MV),
                o_pv = L.take(sizeof(double) * MV);
-  if (c->d_lrt_ws.cap < L.total) c->lrt_gen = 0;  // the constants live in the work space
-  HIP_TRY(c, c->d_lrt_ws.grow(L.total, L.total, nullptr, true));  // (grow-only, outside every loop; RVT_POISON fills it)
+  // the constants live in the work space: a new block has lost them, and so has one that RVT_SCRIBBLE refills
+  if (c->d_lrt_ws.cap < L.total || getenv("RVT_SCRIBBLE")) c->lrt_gen = 0;
+  HIP_TRY(c, c->d_lrt_ws.grow(L.total, L.total, st, true));  // (grow-only, outside every loop; RVT_POISON fills it)
   char* ws = c->d_lrt_ws;
   double* d_vec = reinterpret_cast<double*>(ws + o_vec);
   double* d_abs = reinterpret_cast<double*>(ws + o_abs);
@@ -1639,12 +1648,12 @@ int fam_bed_check(rvt_ctx* c, const char* who) {
   return RVT_OK;
 }
 
-int fam_bed_ws(rvt_ctx* c, FamBedPiece* p) {
+int fam_bed_ws(rvt_ctx* c, hipStream_t st, FamBedPiece* p) {
   const int MV = RVT_MAX_VARIANTS;
   Layout L;
   const size_t o_cnt = L.take(sizeof(unsigned long long) * 4 * MV), o_mu = L.take(sizeof(double) * MV),
                o_muq = L.take(sizeof(double) * MV), o_cs = L.take(sizeof(double) * MV), o_poly = L.take(sizeof(int) * MV);
-  HIP_TRY(c, c->d_fam_bed_ws.grow(L.total, L.total, nullptr, true));
+  HIP_TRY(c, c->d_fam_bed_ws.grow(L.total, L.total, st, true));
   char* ws = c->d_fam_bed_ws;
   p->cnt = reinterpret_cast<unsigned long long*>(ws + o_cnt);
   p->mu = reinterpret_cast<double*>(ws + o_mu);
@@ -1696,7 +1705,7 @@ int fam_bed_front(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int n
   const int64_t ldk = c->uq_ldk;
   const int nB = any_missing ? 2 * n : n;
   const size_t need = (size_t)(((int64_t)nB + kRotBN - 1) / kRotBN * kRotBN) * (size_t)ldk;
-  HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
+  HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
   HIP_TRY(c, hipMemsetAsync(c->d_rotB, 0, need, st));
   hipLaunchKernelGGL(fam_bed_unpack_kernel, dim3((unsigned)((cb + 255) / 256), (unsigned)n), dim3(256), 0, st, d_rows,
                      (long long)cb, (long long)N, n, any_missing ? 1 : 0, c->d_rotB.get(), (long long)ldk);
@@ -1727,7 +1736,7 @@ int rvt_score_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, in
   hipStream_t st = c->stream;
   const size_t cb = (size_t)((c->fam_nc.N + 3) / 4);
   FamBedPiece p;
-  rc = fam_bed_ws(c, &p);
+  rc = fam_bed_ws(c, st, &p);
   if (rc) return rc;
   for (int64_t v0 = 0; v0 < V; v0 += RVT_MAX_VARIANTS) {
     const int n = (int)std::min<int64_t>(RVT_MAX_VARIANTS, V - v0);
@@ -1768,7 +1777,7 @@ int rvt_lrt_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int*
   const size_t cb = (size_t)((c->fam_nc.N + 3) / 4);
   FamBedPiece p;
   LrtWs w;
-  rc = fam_bed_ws(c, &p);
+  rc = fam_bed_ws(c, st, &p);
   if (!rc) rc = lrt_prepare(c, st, &w);
   if (rc) return rc;
   for (int64_t v0 = 0; v0 < V; v0 += RVT_MAX_VARIANTS) {
@@ -1786,7 +1795,7 @@ int fam_bed_rotate_all(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, 
   const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
   const size_t cb = (size_t)((N + 3) / 4);
   FamBedPiece p;
-  int rc = fam_bed_ws(c, &p);
+  int rc = fam_bed_ws(c, st, &p);
   for (int v0 = 0; v0 < ncols && !rc; v0 += RVT_MAX_VARIANTS) {
     const int n = std::min(RVT_MAX_VARIANTS, ncols - v0);
     rc = fam_bed_front(c, st, d_rows + cb * (size_t)v0, n, p, nullptr);
@@ -1875,7 +1884,7 @@ int rvt_fit_grammar_null(rvt_ctx* c, int64_t N, int d, const double* X, const do
   c->have_grammar = false;
   const int64_t ld = rvt_padded_ld(N);
   const GgLayout L = gg_layout(ld, N, d);
-  HIP_TRY(c, c->d_gg_ws.grow(L.total, L.total, nullptr, true));
+  HIP_TRY(c, c->d_gg_ws.grow(L.total, L.total, st, true));
   char* ws = c->d_gg_ws;
   double* d_ty = reinterpret_cast<double*>(ws + L.o_ty);
   double* d_wu1 = reinterpret_cast<double*>(ws + L.o_wu1);

@@ -208,7 +208,7 @@ int gemm_tn_f64(rvt_ctx* c, const double* A, int64_t lda, int M, const double* B
   if (slices > 1) {
     c_slice = ldc * Ntot;
     const size_t need = sizeof(double) * (size_t)c_slice * (size_t)slices;
-    HIP_TRY(c, c->d_rot_part.grow(need, need));
+    HIP_TRY(c, c->d_rot_part.grow(need, need, st, true));
     d_out = c->d_rot_part;
   }
   const int64_t groups = (slices + 7) / 8;
@@ -409,7 +409,7 @@ static int wald_block_impl(rvt_ctx* c, const double* dG, int V, int* ok, double*
   const size_t o_iter = L.take(sizeof(int) * (size_t)Vb), o_l0 = L.take(sizeof(int) * (size_t)Vb),
                o_l1 = L.take(sizeof(int) * (size_t)Vb), o_ok = L.take(sizeof(int) * (size_t)Vb),
                o_rounds = L.take(sizeof(int) * (size_t)Vb), o_cnt = L.take(sizeof(int) * 2);
-  HIP_TRY(c, c->d_wald_ws.grow(L.total, L.total, nullptr, true));
+  HIP_TRY(c, c->d_wald_ws.grow(L.total, L.total, st, true));
   char* ws = c->d_wald_ws;
   double* d_beta = reinterpret_cast<double*>(ws + o_beta);
   double* d_last = reinterpret_cast<double*>(ws + o_last);
@@ -738,7 +738,7 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
                  bT = up(sizeof(double) * (size_t)W * d), bV = up(sizeof(double) * (size_t)W), bP = up(sizeof(int) * (size_t)W);
     const size_t bM = up(sizeof(double) * (size_t)64 * W * (RVT_MAX_COV + 3));   // slice partials of the column pass (<= 64 slices)
     const size_t need = bS + bC + 2 * bT + bV + bP + bM;
-    HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4));
+    HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4, st, true));
     char* q = c->d_cov_work;
     d_S = reinterpret_cast<double*>(q);      // H x (W + d): T sits behind S when heads = window
     q += bS;
@@ -804,7 +804,7 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
     const int64_t ldk = (N + 127) / 128 * 128;
     const int64_t cols_pad = ((int64_t)W + kRotBM - 1) / kRotBM * kRotBM;
     const size_t need = (size_t)cols_pad * (size_t)ldk;
-    HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
+    HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
     // the product reads cols_pad columns of ldk bytes: the column pass writes the W columns' rows up to N rounded to 4 — only
     // the pad rows behind them and the pad columns have to be zeroed (the whole 0.5 GB copy cost 0.1 ms of a 2.3 ms block)
     {
@@ -813,7 +813,7 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
         HIP_TRY(c, hipMemset2DAsync(c->d_rotB + n4, (size_t)ldk, 0, (size_t)(ldk - n4), (size_t)W, st));
       if (cols_pad > W) HIP_TRY(c, hipMemsetAsync(c->d_rotB + (size_t)W * ldk, 0, (size_t)(cols_pad - W) * (size_t)ldk, st));
     }
-    HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int)));
+    HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int), st, true));
     d_bad = c->d_kind;
     HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(int), st));
     {
@@ -842,6 +842,9 @@ static int cov_rect_impl(rvt_ctx* c, const double* dG, int col0, int H, int W, d
     if (rc) return rc;
   }
   hipLaunchKernelGGL(cov_rect_xz_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, cc, T_used, d_cs, W, d_xz);
+  // (the rows kernel writes cov[h, j] for j >= h only, and the whole rectangle goes to the caller: zeros below the diagonal,
+  //  not what an earlier call left in the work space)
+  HIP_TRY(c, hipMemsetAsync(d_cov, 0, sizeof(double) * (size_t)H * W, st));
   hipLaunchKernelGGL(cov_rect_rows_kernel, dim3((unsigned)H), dim3(256), 0, st, cc, d_S, d_cs, d_xz, H, W, d_cov);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(cov, d_cov, sizeof(double) * (size_t)H * W, hipMemcpyDeviceToHost, st));
@@ -950,7 +953,7 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
     const size_t bB = 2 * up(sizeof(float) * (size_t)Hp * ((size_t)halo + 1));
     const size_t bS = fast ? 0 : up(sizeof(double) * (size_t)Hp * Wp);
     const size_t need = 2 * bT + 2 * bV + bP + bM + bB + bS;
-    HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4));
+    HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4, st, true));
     char* q = c->d_cov_work;
     d_T = reinterpret_cast<double*>(q);
     q += bT;
@@ -990,10 +993,10 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
   } else if (fast) {
     // no cache: ONE pass over the window's columns gives the statistics, T = G'X and a linear copy of the window's hard calls
     const size_t need = ((size_t)W + kBandBT) * (size_t)ldk;
-    HIP_TRY(c, c->d_rotB.grow(need, need + need / 4));
+    HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
     const int64_t n4 = (N + 3) / 4 * 4, nw = fp4 ? n4 / 2 : n4;   // bytes of a column the pass writes; the pad behind them: zero
     if (ldk > nw) HIP_TRY(c, hipMemset2DAsync(c->d_rotB + nw, (size_t)ldk, 0, (size_t)(ldk - nw), (size_t)W, st));
-    HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int)));
+    HIP_TRY(c, c->d_kind.grow(sizeof(int), sizeof(int), st, true));
     d_bad = c->d_kind;
     HIP_TRY(c, hipMemsetAsync(d_bad, 0, sizeof(int), st));
     launch_cov_prep(st, d, true, dim3((unsigned)wgs, (unsigned)slices), Gbase, N, ld, W, c->d_X, fp4 ? nullptr : c->d_rotB, ldk8, d_tmp,
@@ -1035,7 +1038,7 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
       nsl = (kbytes + kslice - 1) / kslice;
       const long long set_stride = (long long)n_tiles * (long long)nsl * kBandBT * kBandBT;
       const size_t need = sizeof(int) * (size_t)set_stride * (size_t)n_sets;
-      HIP_TRY(c, c->d_rot_part.grow(need, need));
+      HIP_TRY(c, c->d_rot_part.grow(need, need, st, true));
       int* d_part = reinterpret_cast<int*>(c->d_rot_part.get());
       int pc = r8_col0 + h0;
       if (r8_ring > 0 && pc >= r8_ring) pc -= r8_ring;
@@ -1167,6 +1170,7 @@ static int cov_rect_fam_impl(rvt_ctx* c, const double* dG, int ring, int col0, i
                      d_t1);
   const double b2 = c->famcov_b2;  // MetaCovFamBinary: covXX, covXZ, covZZ each carry b^2 (Model.cpp:651-668)
   if (halo < 0) {
+    HIP_TRY(c, hipMemsetAsync(d_cov, 0, sizeof(double) * (size_t)H * W, st));  // (zeros below the diagonal, as cov_rect_impl)
     hipLaunchKernelGGL(cov_rect_fam_rows_kernel, dim3((unsigned)H), dim3(256), 0, st, cc, d_S, d_cs, d_xz, d_t1, H, W,
                        d_cov);
     HIP_TRY(c, hipGetLastError());
@@ -1269,12 +1273,12 @@ static int packed_columns_pass(rvt_ctx* c, double* dG, int col0, int n, const do
   const int d = c->nc.d, dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
   const int64_t ldk = ck->ldk, ldk4 = ck->ldk4;
   const size_t part_doubles = (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
-  HIP_TRY(c, c->d_cc_part.grow(sizeof(double) * part_doubles, sizeof(double) * part_doubles));
+  HIP_TRY(c, c->d_cc_part.grow(sizeof(double) * part_doubles, sizeof(double) * part_doubles, st, true, 0, "d_cc_part"));
   const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, (int64_t)N / 4096 + 1));
   // (the columns' other values, NaN where a column has none: the pass splits g = h + mu m by them)
   double mu_nan[rvt_ctx::kColQueue];
   for (int k = 0; k < n; ++k) mu_nan[k] = hard[k] ? (double)NAN : mu[k];
-  HIP_TRY(c, c->d_mu_nan.grow(sizeof(double) * (size_t)rvt_ctx::kColQueue, sizeof(double) * (size_t)rvt_ctx::kColQueue));
+  HIP_TRY(c, c->d_mu_nan.grow(sizeof(double) * (size_t)rvt_ctx::kColQueue, sizeof(double) * (size_t)rvt_ctx::kColQueue, st, true));
   double* d_mu_nan = c->d_mu_nan;
   rc = small_h2d(c, d_mu_nan, mu_nan, sizeof(double) * (size_t)n);
   if (!rc) rc = small_h2d(c, ck->d_mu + col0, mu, sizeof(double) * (size_t)n);
@@ -1322,7 +1326,7 @@ int flush_col_queue(rvt_ctx* c) {
   q.n = 0;
   hipSetDevice(c->device);
   const size_t need = q.pitch * (size_t)rvt_ctx::kColQueue + 2 * sizeof(double) * (size_t)rvt_ctx::kColQueue;
-  HIP_TRY(c, c->d_colpack.grow(need, need + need / 2, c->io_stream));
+  HIP_TRY(c, c->d_colpack.grow(need, need + need / 2, c->io_stream, true, 0, "d_colpack"));
   HIP_TRY(c, hipMemcpyAsync(c->d_colpack, q.h[q.cur], q.pitch * (size_t)n, hipMemcpyHostToDevice, c->io_stream));
   if (!q.ev[q.cur]) HIP_TRY(c, hipEventCreateWithFlags(&q.ev[q.cur], hipEventDisableTiming));
   HIP_TRY(c, hipEventRecord(q.ev[q.cur], c->io_stream));
@@ -1393,7 +1397,8 @@ static int upload_packed_columns(rvt_ctx* c, double* dG, int col0, int ncols, co
   if (rc) return rc;
   const size_t N = (size_t)block_dims(c).N, pitch = hcp_row_pitch(N);
   const size_t need = pitch * (size_t)ncols + sizeof(double) * (size_t)ncols;
-  HIP_TRY(c, c->d_colpack.grow(need, need + need / 2));
+  // (io_stream: the stream of the expansion that last read the rows, and — outside a gene submission — of the staged DMA)
+  HIP_TRY(c, c->d_colpack.grow(need, need + need / 2, c->io_stream, true, 0, "d_colpack"));
   if (pitch > c->stage.chunk_bytes) return RVT_OK;
   std::vector<PackedColumn> pc((size_t)ncols);
   const int prc = c->stage.pack_f64(c->d_colpack, pitch, G, N, N, (size_t)ncols, CopyPool::pack_instance(), pc.data());
@@ -1428,7 +1433,7 @@ static int upload_fp64_columns(rvt_ctx* c, double* dG, int col0, int ncols, cons
   const int d = c->nc.d, dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
   const int64_t ldk = ck->ldk, ldk4 = ck->ldk4;
   const size_t part_bytes = sizeof(double) * (size_t)kCovSlices * rvt_ctx::kColQueue * (RVT_MAX_COV + 3);
-  if (cache) HIP_TRY(c, c->d_cc_part.grow(part_bytes, part_bytes));
+  if (cache) HIP_TRY(c, c->d_cc_part.grow(part_bytes, part_bytes, c->io_stream, true));
   for (int col = col0; col < col0 + ncols; ++col) {
     if (!cache) {
       rc = enqueue_classify(c, dG + (size_t)col * ld, 1, (int64_t)N, (int64_t)ld, c->io_stream, ck->d_flags + col);
@@ -1513,8 +1518,8 @@ static int recode_columns(rvt_ctx* c, double* dst, int dst_col, int ncols, int p
   Layout L;
   const size_t n_cnt = (size_t)per * (size_t)ncols;
   const size_t o_cnt = L.take(sizeof(unsigned long long) * n_cnt), o_avg = L.take(sizeof(double) * (size_t)ncols);
-  // (no poison fill: it would run on the null stream, unordered against the clearing of the counts on this one)
-  HIP_TRY(c, c->d_recode_ws.grow(L.total, L.total + L.total / 2, st));
+  // (the poison fill runs on `st`, in front of the clearing of the counts)
+  HIP_TRY(c, c->d_recode_ws.grow(L.total, L.total + L.total / 2, st, true));
   unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(c->d_recode_ws + o_cnt);
   double* d_avg = reinterpret_cast<double*>(c->d_recode_ws + o_avg);
   HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * n_cnt, st));

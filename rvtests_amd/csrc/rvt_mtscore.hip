@@ -329,7 +329,7 @@ int rvt_mt_score_block(rvt_ctx* c, const double* dG, int V, double* ustat, doubl
                o_u = L.take(sizeof(double) * (size_t)Vp * (size_t)T), o_v = L.take(sizeof(double) * (size_t)Vp * (size_t)T),
                o_p = L.take(sizeof(double) * (size_t)Vp * (size_t)T);
   HIP_TRY(c, c->d_mt_ws.grow(L.total, L.total, st, true));
-  HIP_TRY(c, c->d_mt_B.grow((size_t)vpad * (size_t)ldk, (size_t)vpad * (size_t)ldk, st));
+  HIP_TRY(c, c->d_mt_B.grow((size_t)vpad * (size_t)ldk, (size_t)vpad * (size_t)ldk, st, true));
   char* ws = c->d_mt_ws;
   unsigned long long* d_isum = reinterpret_cast<unsigned long long*>(ws + o_isum);
   int* d_bad = reinterpret_cast<int*>(ws + o_bad);

@@ -109,6 +109,12 @@ int exact_permutations(rvt_ctx* c, const double* d_start, int nPerm, double alph
     jump_matrix((uint64_t)(N - 1), c->jump.data());  // one shuffle draws N-1 numbers (LinearAlgebra.h:12-14)
     c->jump_N = N;
   }
+  // the chunk buffers are work spaces of this call (perm_apply_kernel, the caller's statistic and the copy below write what is
+  // read); the index arrays and generator states are rewritten per chunk too, but count as state of the generation
+  HIP_TRY(c, c->d_perm_R.scribble(st, "d_perm_R"));
+  HIP_TRY(c, c->d_perm_C.scribble(st, "d_perm_C"));
+  HIP_TRY(c, c->d_perm_Q.scribble(st, "d_perm_Q"));
+  HIP_TRY(c, c->d_perm_cur.scribble(st, "d_perm_cur"));
   double* cur = c->d_perm_cur;
   double* nxt = c->d_perm_cur + N;
   HIP_TRY(c, hipMemcpyAsync(cur, d_start, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, st));
@@ -217,7 +223,7 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
     constexpr int kChunk = 2048;
     const int Mp = (m + 15) / 16 * 16;
     const long long ngroups = (N + 15) / 16;
-    HIP_TRY(c, c->d_pc_Q.grow(sizeof(double) * kChunk, sizeof(double) * kChunk));
+    HIP_TRY(c, c->d_pc_Q.grow(sizeof(double) * kChunk, sizeof(double) * kChunk, st, true));
     const double obs = r->skat_Q;
     // Permutation::init — `threshold` is an INT member of the reference's class (src/Permutation.h:153): the product is truncated
     // (nPerm = 100, alpha = 0.001 -> 0: the test stops before its first shuffle and reports p = 1; found by running the
@@ -237,7 +243,7 @@ int perm_stage(rvt_ctx* c, const double* dG, int M, const GeneDesc& g0, const rv
       const int gps = (int)((ngroups + slices - 1) / slices);
       slices = (int)((ngroups + gps - 1) / gps);
       const size_t need = (size_t)slices * nb * Mp;
-      HIP_TRY(c, c->d_pc_part.grow(sizeof(double) * need, sizeof(double) * (need + need / 4)));
+      HIP_TRY(c, c->d_pc_part.grow(sizeof(double) * need, sizeof(double) * (need + need / 4), st, true));
       hipLaunchKernelGGL(perm_counter_partial_kernel, dim3((unsigned)slices, (unsigned)n_bt), dim3(64), 0, st, c->d_Gp,
                          (long long)ld, (long long)N, m, c->d_res, (unsigned long long)c->perm_seed,
                          (unsigned long long)r->gene_id, (unsigned)actual, nb, gps, Mp, c->d_pc_part);

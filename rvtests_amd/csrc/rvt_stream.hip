@@ -159,8 +159,10 @@ static int text_acquire(rvt_ctx* c, size_t total) {
     HIP_TRY(c, hipEventCreateWithFlags(&c->ev_text_free[k], hipEventDisableTiming));
     HIP_TRY(c, hipEventCreateWithFlags(&c->ev_text_copied[k], hipEventDisableTiming));
   }
-  HIP_TRY(c, c->text_buf[k].grow(total, total + total / 4));
+  // (the wait first: a test fill of the buffer is queued on the copy stream, behind the kernels that read it last.  What lies
+  //  behind a record's end inside its last 16-byte load is masked by the decoders (vcf_tabs16; BGEN's tail is zeroed by the upload))
   HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_text_free[k], 0));
+  HIP_TRY(c, c->text_buf[k].grow(total, total + total / 4, c->copy_stream, true, 0, "text_buf"));
   c->d_vcf_text = c->text_buf[k];
   c->text_cur = k;
   return RVT_OK;
@@ -225,9 +227,9 @@ int vcf_decode_gene(rvt_ctx* c, const VcfGene* vg, int M, int64_t N, hipStream_t
     max_len = std::max<int64_t>(max_len, vg->len[j]);
   }
   if (int rca = text_acquire(c, total)) return rca;
-  HIP_TRY(c, c->d_vcf_rec.grow(sizeof(VcfRecord) * RVT_MAX_VARIANTS, sizeof(VcfRecord) * RVT_MAX_VARIANTS));
+  HIP_TRY(c, c->d_vcf_rec.grow(sizeof(VcfRecord) * RVT_MAX_VARIANTS, sizeof(VcfRecord) * RVT_MAX_VARIANTS, st, true, 0, "d_vcf_rec"));
   const int max_seg = (int)std::max<int64_t>(1, (max_len + kVcfSegBytes - 1) / kVcfSegBytes);
-  HIP_TRY(c, c->d_vcf_seg.grow(sizeof(int) * max_seg * M, sizeof(int) * max_seg * std::max(M, 64)));
+  HIP_TRY(c, c->d_vcf_seg.grow(sizeof(int) * max_seg * M, sizeof(int) * max_seg * std::max(M, 64), st, true, 0, "d_vcf_seg"));
   {
     int rce = io_err_ready(c);
     if (rce) return rce;
@@ -372,9 +374,9 @@ int bgen_decode_gene(rvt_ctx* c, const BgenGene* bg, int M, int64_t N, hipStream
   total += 16;
   if (int rca = text_acquire(c, total)) return rca;
   c->vcf_alt.clear();  // (one call only)
-  HIP_TRY(c, c->d_bgen_rec.grow(sizeof(BgenRecord) * RVT_MAX_VARIANTS, sizeof(BgenRecord) * RVT_MAX_VARIANTS));
+  HIP_TRY(c, c->d_bgen_rec.grow(sizeof(BgenRecord) * RVT_MAX_VARIANTS, sizeof(BgenRecord) * RVT_MAX_VARIANTS, st, true, 0, "d_bgen_rec"));
   const int max_seg = (int)((n_file + kBgenSeg - 1) / kBgenSeg);
-  HIP_TRY(c, c->d_bgen_seg.grow(sizeof(long long) * max_seg * M, sizeof(long long) * max_seg * std::max(M, 64)));
+  HIP_TRY(c, c->d_bgen_seg.grow(sizeof(long long) * max_seg * M, sizeof(long long) * max_seg * std::max(M, 64), st, true, 0, "d_bgen_seg"));
   {
     int rce = io_err_ready(c);
     if (rce) return rce;
@@ -538,7 +540,7 @@ BlockLease lease_expanded(rvt_ctx* c, int M, int* rc) {
 int consol_nparts(int64_t N) { return (int)((N + kConsolChunk - 1) / kConsolChunk); }
 hipError_t consol_parts_ready(rvt_ctx* c, int M) {
   const int nparts = consol_nparts(c->nc.N);
-  return c->d_consol_parts.grow(sizeof(ConsolPart) * M * nparts, sizeof(ConsolPart) * std::max(M, 128) * nparts);
+  return c->d_consol_parts.grow(sizeof(ConsolPart) * M * nparts, sizeof(ConsolPart) * std::max(M, 128) * nparts, c->io_stream, true);
 }
 struct ConsolOut {
   double* d_af;       // the allele frequencies; NULL: the imputation values are GIVEN (c->d_consol_af's second half), no fill pass
@@ -669,7 +671,7 @@ int fill_packed_f64(const Submit& s, const BlockLease& blk) {
   rvt_ctx* c = s.c;
   const size_t N = (size_t)c->nc.N, pk_pitch = hcp_row_pitch(c->nc.N);
   const int M = s.M;
-  if (c->d_consol_af.grow(sizeof(double) * 2 * M, sizeof(double) * 2 * RVT_MAX_VARIANTS) != hipSuccess ||
+  if (c->d_consol_af.grow(sizeof(double) * 2 * M, sizeof(double) * 2 * RVT_MAX_VARIANTS, c->io_stream, true) != hipSuccess ||
       consol_parts_ready(c, M) != hipSuccess) {
     (void)hipGetLastError();
     return kRetryExpanded;
@@ -728,15 +730,16 @@ int fill_expanded_hardcalls(const Submit& s, const BlockLease& blk, const AfRetu
   int pk = -1;
   hipError_t e;
   if (s.in == GeneInput::kVcfGt) {
-    e = c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4);
+    e = c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4, st, true);
     if (e == hipSuccess && vcf_decode_gene(c, (const VcfGene*)s.G, s.M, N, st, ar.err_slot) != RVT_OK) e = hipErrorUnknown;
     d_packed = c->d_consol_i8;
   } else {
     // host copy on the copy stream into the next landing buffer of the ring (free once the consolidation kernels of the gene
     // that used it last have run); the kernels of THIS gene wait for the copy by event
     pk = next_pack_slot(c);
-    e = c->d_pack[pk].grow(bytes8, bytes8 + bytes8 / 4);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_pack_free[pk], 0);
+    // (the wait first: a test fill of the buffer is queued on the copy stream, behind the kernels that read it last)
+    e = hipStreamWaitEvent(c->copy_stream, c->ev_pack_free[pk], 0);
+    if (e == hipSuccess) e = c->d_pack[pk].grow(bytes8, bytes8 + bytes8 / 4, c->copy_stream, true);
     if (e == hipSuccess && s.in == GeneInput::kBedDev) {  // (device-resident rows: into the same landing buffer, whatever their alignment)
       e = hipMemcpyAsync(c->d_pack[pk], s.G, bytes8, hipMemcpyDeviceToDevice, c->copy_stream);
     } else if (e == hipSuccess) {
@@ -819,7 +822,7 @@ int submit_routed(const Submit& s, bool may_pack) {
   }
   // the consolidation runs on a stream of its own: the set-up stream is also slot 0's batch stream, and waiting on it would
   // wait for a whole batch
-  if (c->d_consol_af.grow(sizeof(double) * 2 * s.M, sizeof(double) * 2 * RVT_MAX_VARIANTS) != hipSuccess)
+  if (c->d_consol_af.grow(sizeof(double) * 2 * s.M, sizeof(double) * 2 * RVT_MAX_VARIANTS, c->io_stream, true) != hipSuccess)
     return fail(c, RVT_E_HIP, "hipMalloc failed");
   AfReturn ar;
   hipError_t e = consol_parts_ready(c, s.M);
@@ -996,7 +999,7 @@ int bed_rows_consolidate(rvt_ctx* c, hipStream_t st, const char* what, const std
   const size_t b_parts = pad(sizeof(ConsolPart) * (size_t)max_rows * nparts);
   const size_t b_af = d_counts ? sizeof(double) * (size_t)max_rows : 0, b_cnt = d_counts ? sizeof(long long) * 4 * (size_t)max_rows : 0;
   const size_t need = b_rows + b_genes + b_parts + b_af + b_cnt;
-  HIP_TRY(c, c->d_bedbatch.grow(need, need + need / 2, st));
+  HIP_TRY(c, c->d_bedbatch.grow(need, need + need / 2, st, true));
   char* w = c->d_bedbatch;
   BedRowRef* d_rows = reinterpret_cast<BedRowRef*>(w);
   BedGeneRef* d_genes = reinterpret_cast<BedGeneRef*>(w + b_rows);
@@ -1470,7 +1473,7 @@ int rvt_vcf_decode(rvt_ctx* c, int M, const char* const* sample_text, const int6
   const size_t bytes8 = (size_t)N * M;
   hipStream_t st = c->io_stream;
   HIP_TRY(c, sync_stream(st));
-  HIP_TRY(c, c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4));
+  HIP_TRY(c, c->d_consol_i8.grow(bytes8, bytes8 + bytes8 / 4, st, true));
   VcfGene vg{sample_text, text_len, gt_index, gd_index, gq_index};
   int rc = io_err_ready(c);
   if (rc) return rc;

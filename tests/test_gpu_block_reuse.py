@@ -28,11 +28,9 @@ def _raw_gene(N, M, seed):
 
 
 def _same_bits(a, b):
-    """Every field of the record but the AnalyticVT block: the engine writes vt_* only when that test is requested (it is not —
-    such a gene is never kept packed), and leaves whatever its work space held otherwise."""
+    """Every field of the record, NaN equal to NaN.  The AnalyticVT block too: the test is not requested here (such a gene is
+    never kept packed), and the p-value kernel then writes zeros there (pvalue_clear_vt)."""
     for name, _ in type(a)._fields_:
-        if name.startswith("vt_"):
-            continue
         x, y = getattr(a, name), getattr(b, name)
         assert x == y or (x != x and y != y), (name, x, y)
 
