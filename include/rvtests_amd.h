@@ -950,12 +950,32 @@ int rvt_bed_recode_block(rvt_ctx* ctx, const unsigned char* d_rows, int V, int c
  * 4 V entries): per row the numbers of 0 / 1 / 2 / missing calls, as rvt_score_bed_dev reports them.  RVT_E_INVALID: a null
  * argument (counts excepted) or V < 1.  RVT_E_STATE: no family null model, or an ordinary null model is installed whose N differs
  * from the family null model's (the rows would have another pitch).  A refused call writes nothing.  Synchronous.
- * Not covered from resident rows: famGrammarGamma, FamSKAT and the family burden tests, the family MetaCov calls, the rvt_group_*
- * layer and the host adapter classes — they take fp64 blocks. */
+ * Not covered from resident rows: famGrammarGamma, the family MetaCov calls, FamAnalyticVT, the rvt_group_* layer and the host
+ * adapter classes — they take fp64 blocks.  (FamSKAT and the family burden tests: rvt_run_fam_tests_bed_dev below.) */
 int rvt_score_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int binary, int* ok, double* ustat, double* vstat,
                           double* af, double* pvalue, long long* counts);
 int rvt_lrt_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int* ok, double* af, double* null_loglik,
                         double* alt_loglik, double* pvalue, long long* counts);
+/* The gene-based tests for related samples from rows of a resident .bed matrix: rvt_run_fam_tests (FamSkatTest,
+ * src/Model.h:3048-3145; FamCMC, src/Model.h:2261-2376; FamZeggini, src/Model.h:2378-2492; the burden tests' collapse and
+ * FastLMM::TestCovariate's SCORE branch, regression/FastLMM.cpp:215-247, and FastLMM::GetAF, :356-398) with gene g given as M[g]
+ * consecutive rows starting at the device address d_rows[g] — the convention of rvt_submit_gene_bed_dev.  The pitch is
+ * ceil(N / 4) bytes, N the family null model's sample count; a row may start at any byte, the padding pairs of a row's last
+ * byte are ignored.  Genes may come in any order, overlap and share rows.  tests is a mask out of RVT_TEST_FAMSKAT |
+ * RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI, and the records (n_variants, n_poly, famskat_*, famcmc_*, famzeg_*, skat_nlambda,
+ * davies_terms, status) equal those of rvt_run_fam_tests on the columns a caller would have uploaded for these rows: the calls
+ * 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing with missing imputed to the mean of the called ones (src/DataConsolidator.cpp:217-245).
+ * The flip to the minor allele and the drop of monomorphic rows (src/DataConsolidator.cpp:46-69,94-142) are decided from the
+ * four counts of a row in integers (flip when n1 + 2 n2 > n0 + n1 + n2; keep when two of n0, n1, n2 are non-zero), the kept rows
+ * are rotated from their codes by the installed form of U as under rvt_score_bed_dev_fam — family form: the fp64 route's records
+ * bit for bit; dense U: the flipped column as c' + mu' m on two single-plane operands, one without a missing call in the batch;
+ * column-compressed U: expanded on the device — and the CMC / Zeggini columns are collapsed from the codes.  No variant exists as
+ * doubles before U'G.  Everything behind the rotation is rvt_run_fam_tests' own tail.
+ * RVT_E_INVALID: a null argument (gene_ids excepted), a null d_rows entry, a mask that is empty or has another bit.
+ * RVT_E_TOO_LARGE: M[g] < 1 or M[g] > RVT_MAX_VARIANTS.  RVT_E_STATE: no family null model, or an ordinary null model of another
+ * N is installed (the rows would have another pitch).  A refused call writes nothing; n_genes == 0 returns RVT_OK.  Synchronous. */
+int rvt_run_fam_tests_bed_dev(rvt_ctx* ctx, int n_genes, const unsigned char* const* d_rows, const int* M, const int64_t* gene_ids,
+                              uint32_t tests, rvt_gene_result* out);
 
 /* ---- VCF text at the boundary (SURVEY §8f "next" #1: the genotype front end) -------------------------------------------
  * Replaces the per-sample loop of VCFGenotypeExtractor::extractMultipleGenotype (src/VCFGenotypeExtractor.cpp:29-140) for
@@ -1143,6 +1163,12 @@ int rvt_debug_rotate_bed(rvt_ctx* ctx, const unsigned char* d_rows, int ncols, d
 /* Measurement (tools/bench_fam_bed.py): the same front stage without the copy to the host; *ms = the device milliseconds
  * between HIP events recorded directly around it. */
 int rvt_debug_rotate_bed_timed(rvt_ctx* ctx, const unsigned char* d_rows, int ncols, double* ms);
+/* Measurement (tools/bench_fam_genes_bed.py): the front stage of rvt_run_fam_tests_bed_dev alone — site pass, kept-row lists,
+ * rotation, burden collapse and its rotation — with that call's arguments and refusals; the records are initialised, no test
+ * runs.  *ms = the device milliseconds between HIP events recorded directly around it (they also enclose the copy of the row
+ * flags to the host and the host's pass over them). */
+int rvt_debug_fam_genes_bed_front_timed(rvt_ctx* ctx, int n_genes, const unsigned char* const* d_rows, const int* M, uint32_t tests,
+                                        rvt_gene_result* out, double* ms);
 int rvt_set_profiling(rvt_ctx* ctx, int on);
 int rvt_get_timing(rvt_ctx* ctx, rvt_timing* t, int reset);
 /* the HIP stream (hipStream_t) the engine launches on, for callers that record their own events */

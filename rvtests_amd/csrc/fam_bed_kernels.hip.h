@@ -15,6 +15,9 @@
 // Bytes per column: N / 4 of codes instead of 8 N of doubles in, 8 N out (family form; the dense form adds 2 N of planes).
 // Rows start at any byte address (N = 515: pitch 129), so every kernel here loads single bytes; the padding pairs of a row's
 // last byte are never looked at (family form: no member index reaches them) or masked out.
+// The second half of the file is the gene side (rvt_run_fam_tests_bed_dev: FamSKAT, FamCMC, FamZeggini): the flip to the minor
+// allele and the drop of monomorphic rows from the counts, the same three rotations over a LIST of kept rows (they are scattered
+// after the drop, and genes lie anywhere) with the flip applied, and the burden collapse from the codes.
 // Included by rvt_fam.hip alone.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -125,6 +128,164 @@ static __global__ __launch_bounds__(256) void fam_bed_combine_kernel(const doubl
   if (i >= N) return;
   const int h = blockIdx.y;
   out[i + (long long)h * ld_dst] = fma(mu[h], C[i + (long long)(n + h) * ldc], C[i + (long long)h * ldc]);
+}
+
+// ---- the gene-based family tests over resident rows (rvt_run_fam_tests_bed_dev) -----------------------------------------------------
+// Step 1 of rvt_run_fam_tests (DataConsolidator.cpp:46-69,94-142) decided from the four counts of a row, in integers, with
+// called = n0 + n1 + n2 and a = n1 + 2 n2: flags[v] bit 0 = flip to the minor allele, bit 1 = keep (polymorphic, the rule of
+// fam_bed_site_kernel), bit 2 = no missing call (a kept row then holds hard calls only: fam_colstat_kernel's bit 2).
+// flip = a > called.  That is the reference's s > rows and fam_colstat_kernel's !(sum <= N) on the imputed column in every case:
+// the imputed column sums to a N / called, which differs from N by at least N / called >= 1 unless a == called — far beyond the
+// rounding of any summation order of N values in [0, 2] — and when a == called the fill value is exactly 1.0, every entry is an
+// integer and the sum is exactly N in any order.  No rounding of either route can decide differently.
+static __global__ __launch_bounds__(256) void fam_bed_gene_site_kernel(const unsigned long long* __restrict__ counts, long long n,
+                                                                       int* __restrict__ flags) {
+  const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (v >= n) return;
+  const long long n0 = (long long)counts[4 * v], n1 = (long long)counts[4 * v + 1], n2 = (long long)counts[4 * v + 2],
+                  nm = (long long)counts[4 * v + 3];
+  const long long called = n0 + n1 + n2, ac = n1 + 2 * n2;
+  flags[v] = (ac > called ? 1 : 0) | (((n0 > 0) + (n1 > 0) + (n2 > 0)) >= 2 ? 2 : 0) | (nm == 0 ? 4 : 0);
+}
+
+// The kept rows of a batch, column k of the compact matrix = row src[k] of the site pass: flip[k]; mu[k] = a / called, the fill
+// value of a missing call BEFORE the flip (the family form and the expansion flip the decoded value, 2.0 - v: the one fp64
+// subtraction of fam_flip_compact_kernel); fillq[k] = the fill value AFTER the flip, mu' = 2.0 - mu where flipped, in the fixed
+// point the digit planes give the column (fam_bed_site_kernel's muq; the largest entry of a flipped kept column is 2 when
+// n0 > 0, else 1).
+static __global__ __launch_bounds__(256) void fam_bed_kept_kernel(const unsigned long long* __restrict__ counts,
+                                                                  const int* __restrict__ src, long long T,
+                                                                  int* __restrict__ flip, double* __restrict__ mu,
+                                                                  double* __restrict__ fillq) {
+  const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= T) return;
+  const long long v = src[k];
+  const long long n0 = (long long)counts[4 * v], n1 = (long long)counts[4 * v + 1], n2 = (long long)counts[4 * v + 2];
+  const long long called = n0 + n1 + n2, ac = n1 + 2 * n2;  // (kept: called >= 2)
+  const bool fl = ac > called;
+  const double m = (double)ac / (double)called, f = fl ? 2.0 - m : m;
+  const int s = 7 * kRotPlanesG - 3 - ((fl ? n0 : n2) > 0 ? 1 : 0);
+  flip[k] = fl ? 1 : 0;
+  mu[k] = m;
+  fillq[k] = ldexp(rint(ldexp(f, s)), -s);
+}
+
+// rot_fam_bed_kernel over a list of rows (rows[k] = the address of kept row k, any byte address) with the flip applied to the
+// tile: the value is flip ? 2.0 - v : v with v = fam_bed_value(code, mu), the very double the fp64 route reads after
+// fam_flip_compact_kernel, so the rotated columns agree with that route bit for bit.  Same grid, chain and stores.
+static __global__ __launch_bounds__(kRotFamRows) void rot_fam_bed_list_kernel(
+    const int* __restrict__ run_ptr, const int* __restrict__ pair_fam, const long long* __restrict__ fam_ptr,
+    const int* __restrict__ members, const long long* __restrict__ colptr, const double* __restrict__ vals,
+    const unsigned char* const* __restrict__ rows, const int* __restrict__ flip, const double* __restrict__ mu, int ncols,
+    double* __restrict__ out, long long ld_dst) {
+  __shared__ double g[kRotFamCols][kRotFamRows];
+  const int e0 = run_ptr[blockIdx.x], nrows = run_ptr[blockIdx.x + 1] - e0;  // nrows <= kRotFamRows
+  const int t = threadIdx.x, col0 = blockIdx.y * kRotFamCols;
+  const int nc = min(kRotFamCols, ncols - col0);
+  const bool active = t < nrows;
+  int k = 0, row0 = 0;
+  const double* u = vals;
+  if (active) {
+    const int e = e0 + t, f = pair_fam[e];
+    const long long fs = fam_ptr[f];
+    k = (int)(fam_ptr[f + 1] - fs);
+    row0 = (int)(fs - e0);
+    u = vals + colptr[e];
+    const int s = members[e], sh = 2 * (s & 3);
+#pragma unroll
+    for (int c = 0; c < kRotFamCols; ++c)
+      if (c < nc) {
+        const double v = fam_bed_value(((unsigned)rows[col0 + c][s >> 2] >> sh) & 3u, mu[col0 + c]);
+        g[c][t] = flip[col0 + c] ? 2.0 - v : v;
+      }
+  }
+  __syncthreads();
+  if (!active) return;
+  double acc[kRotFamCols];
+  rot_fam_chain(u, k, row0, g, acc);
+  double* dst = out + (e0 + t) + (long long)col0 * ld_dst;
+#pragma unroll
+  for (int c = 0; c < kRotFamCols; ++c)
+    if (c < nc) dst[(long long)c * ld_dst] = acc[c];
+}
+
+// fam_bed_unpack_kernel over a list of rows, flipped where flagged: column j = c' (the call, or 2 - call where flipped, on called
+// samples; 0 on missing ones), column n + j = the missing indicator.  The flipped imputed column is c' + mu' m.  grid
+// (ceil(pitch / 256), n).
+static __global__ __launch_bounds__(256) void fam_bed_unpack_list_kernel(const unsigned char* const* __restrict__ rows,
+                                                                         const int* __restrict__ flip, long long pitch,
+                                                                         long long N, int n, int with_m,
+                                                                         signed char* __restrict__ B, long long ldk) {
+  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (b >= pitch) return;
+  const int j = blockIdx.y;
+  const unsigned code = rows[j][b];
+  const bool fl = flip[j] != 0;
+  const long long left = N - 4 * b;  // > 0
+  uint32_t cw = 0u, mw = 0u;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned q = (code >> (2 * e)) & 3u;
+    if (e < left) {
+      const unsigned call = q == 2u ? 1u : (q == 3u ? 2u : 0u);
+      cw |= (q == 1u ? 0u : (fl ? 2u - call : call)) << (8 * e);
+      mw |= (q == 1u ? 1u : 0u) << (8 * e);
+    }
+  }
+  *reinterpret_cast<uint32_t*>(B + (long long)j * ldk + 4 * b) = cw;
+  if (with_m) *reinterpret_cast<uint32_t*>(B + (long long)(n + j) * ldk + 4 * b) = mw;
+}
+
+// bed_expand_columns_kernel over a list of rows, flipped where flagged: column j of G (leading dimension ld) = the doubles
+// fam_flip_compact_kernel writes for the imputed column of row j.  grid (ceil(pitch / 256), n); four samples per thread.
+static __global__ __launch_bounds__(256) void fam_bed_expand_list_kernel(const unsigned char* const* __restrict__ rows,
+                                                                         const int* __restrict__ flip,
+                                                                         const double* __restrict__ mu, long long pitch,
+                                                                         long long N, long long ld, double* __restrict__ G) {
+  const long long b = (long long)blockIdx.x * 256 + threadIdx.x, i = 4 * b;
+  if (b >= pitch) return;
+  const int j = blockIdx.y;
+  const unsigned code = rows[j][b];
+  const double m = mu[j];
+  const bool fl = flip[j] != 0;
+  double* g = G + (long long)j * ld + i;
+  for (int e = 0; e < 4 && i + e < N; ++e) {
+    const double v = fam_bed_value((code >> (2 * e)) & 3u, m);
+    g[e] = fl ? 2.0 - v : v;
+  }
+}
+
+// cmcCollapse / zegginiCollapse (src/Model.cpp:73-89,115-130) from the codes: gene k owns kept rows [off[k], off[k] + m[k]) of
+// the list and writes its two collapsed columns to out + (2k) * ld and out + (2k+1) * ld, as fam_collapse_kernel does from the
+// flipped fp64 block.  A thread takes one byte position (four samples) and walks the gene's kept rows; a sample counts where
+// (int)value > 0 on the flipped, imputed value: a called one when flip ? call < 2 : call > 0, a missing one when its fill value
+// (flip ? 2.0 - mu : mu) is >= 1 — only an unflipped row with a == called, mu = 1.0, gets there.  Reads m N / 4 bytes per gene
+// where the fp64 route reads 8 m N.  grid (ceil(pitch / 256), genes).
+static __global__ __launch_bounds__(256) void fam_bed_collapse_kernel(const unsigned char* const* __restrict__ rows,
+                                                                      const int* __restrict__ flip,
+                                                                      const double* __restrict__ mu, const int* __restrict__ off,
+                                                                      const int* __restrict__ m, long long pitch, long long N,
+                                                                      long long ld, double* __restrict__ out) {
+  const long long b = (long long)blockIdx.x * 256 + threadIdx.x, i = 4 * b;
+  if (b >= pitch) return;
+  const int k = blockIdx.y, j0 = off[k], mk = m[k];
+  int n[4] = {0, 0, 0, 0};
+  for (int j = j0; j < j0 + mk; ++j) {
+    const unsigned code = rows[j][b];
+    const bool fl = flip[j] != 0;
+    const int miss = (int)(fl ? 2.0 - mu[j] : mu[j]) > 0 ? 1 : 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const unsigned q = (code >> (2 * e)) & 3u;  // 0 -> 0, 2 -> 1, 3 -> 2, 1 -> missing
+      n[e] += q == 1u ? miss : (fl ? (q != 3u ? 1 : 0) : (q != 0u ? 1 : 0));
+    }
+  }
+  double* cmc = out + (long long)(2 * k) * ld + i;
+  double* zeg = out + (long long)(2 * k + 1) * ld + i;
+  for (int e = 0; e < 4 && i + e < N; ++e) {
+    cmc[e] = n[e] > 0 ? 1.0 : 0.0;
+    zeg[e] = (double)n[e];
+  }
 }
 
 }  // namespace rvt

@@ -1182,6 +1182,10 @@ int rvt_fam_binary_scale(rvt_ctx* c, int64_t n_case, int64_t n_ctrl, double* alp
   return RVT_OK;
 }
 
+static int fam_tests_tail(rvt_ctx* c, int n, uint32_t tests, const std::vector<int>& Mk, const std::vector<int>& off,
+                          const std::vector<int>& kgene, size_t T, const double* d_bcs, const int* d_bpoly,
+                          rvt_gene_result* out);
+
 int rvt_run_fam_blocks(rvt_ctx* c, int n, const double* const* dG, const int* Ms, const int64_t* ids,
                        rvt_gene_result* out) {
   return rvt_run_fam_tests(c, n, dG, Ms, ids, RVT_TEST_FAMSKAT, out);
@@ -1315,6 +1319,20 @@ int rvt_run_fam_tests(rvt_ctx* c, int n, const double* const* dG, const int* Ms,
     if (rcr) return rcr;
   }
   HIP_TRY(c, sync_stream(st));
+  return fam_tests_tail(c, n, tests, Mk, off, kgene, T, d_bcs, d_bpoly, out);
+}
+
+// The tail of rvt_run_fam_tests and rvt_run_fam_tests_bed_dev, behind either front stage.  The front has initialised the n
+// records (gene_id, n_variants, n_poly) and left in c->d_Gt, leading dimension fam_nc.ld, the T rotated kept columns — gene g
+// owns Mk[g] of them from column off[g] on — and, for the burden tests, behind them the rotated CMC / Zeggini columns of the genes
+// with a kept column (kgene, two each) with their raw sums d_bcs and polymorphic flags d_bpoly on the device.
+static int fam_tests_tail(rvt_ctx* c, int n, uint32_t tests, const std::vector<int>& Mk, const std::vector<int>& off,
+                          const std::vector<int>& kgene, size_t T, const double* d_bcs, const int* d_bpoly,
+                          rvt_gene_result* out) {
+  int rc;
+  const int64_t ld = c->fam_nc.ld;
+  const bool burden = (tests & (RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI)) != 0;
+  const size_t nk = kgene.size(), TB = burden ? 2 * nk : 0;
   if (burden) {
     // FamCMC / FamZeggini: the 2 nk rotated collapsed columns as blocks of the family covariance machinery
     // (V = cov(h,h), U from the uResid column, AF from the allele-frequency column)
@@ -1786,6 +1804,223 @@ int rvt_lrt_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int*
     if (!rc) rc = lrt_piece(c, st, w, n, p.poly, ok + v0, af + v0, null_loglik + v0, alt_loglik + v0, pvalue + v0);
     if (rc) return rc;
   }
+  return RVT_OK;
+}
+
+// FamSKAT / FamCMC / FamZeggini from resident rows: steps 1-2 of rvt_run_fam_tests formed from the 2-bit codes (the gene-side
+// kernels of fam_bed_kernels.hip.h), then its tail.  Work spaces: counts and flags of every row, flip / fill values of the kept
+// ones and the burden columns' sums and flags in d_fam_bed_ws; the kept rows' addresses, their site indices and the genes' ranges
+// in d_fam_list; each is sized once per call, in front of its first write.
+namespace {
+struct FamGenesFront {        // what steps 1-2 leave for fam_tests_tail
+  std::vector<int> Mk, off, kgene;
+  size_t T = 0;
+  const double* d_bcs = nullptr;
+  const int* d_bpoly = nullptr;
+};
+}  // namespace
+
+// steps 1-2: the checks, the records' initialisation and the front stage proper; *run = whether a tail is left to run (n > 0 and
+// a kept row somewhere)
+static int fam_genes_bed_front(rvt_ctx* c, int n, const unsigned char* const* d_rows, const int* Ms, const int64_t* ids,
+                               uint32_t tests, rvt_gene_result* out, FamGenesFront* F, bool* run) {
+  *run = false;
+  if (!c || n < 0 || (n > 0 && (!d_rows || !Ms || !out))) return fail(c, RVT_E_INVALID, "bad batch arguments");
+  if (!(tests & (RVT_TEST_FAMSKAT | RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI)) ||
+      (tests & ~(RVT_TEST_FAMSKAT | RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI)))
+    return fail(c, RVT_E_INVALID, "rvt_run_fam_tests_bed_dev takes the FAMSKAT / FAMCMC / FAMZEGGINI bits");
+  for (int g = 0; g < n; ++g)
+    if (!d_rows[g]) return fail(c, RVT_E_INVALID, "gene %d: null row address", g);
+  int rc = fam_bed_check(c, "rvt_run_fam_tests_bed_dev");
+  if (rc) return rc;
+  if (n == 0) return RVT_OK;
+  size_t tot = 0;
+  std::vector<size_t> row0(n);
+  for (int g = 0; g < n; ++g) {
+    if (Ms[g] < 1 || Ms[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_TOO_LARGE, "gene %d: M=%d", g, Ms[g]);
+    row0[g] = tot;
+    tot += (size_t)Ms[g];
+  }
+  if (tot > (size_t)INT32_MAX) return fail(c, RVT_E_TOO_LARGE, "%zu rows in one call", tot);
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld, cb = (N + 3) / 4;
+  const bool burden = (tests & (RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI)) != 0;
+  // ---- 1. the site pass over the codes: counts, then flip / keep / no-missing flags of every row ---------------------------------
+  Layout W, Lst;  // (sized by the rows of the batch: T <= tot kept rows, at most n genes with one)
+  const size_t o_cnt = W.take(sizeof(unsigned long long) * 4 * tot), o_flags = W.take(sizeof(int) * tot),
+               o_flip = W.take(sizeof(int) * tot), o_mu = W.take(sizeof(double) * tot), o_fq = W.take(sizeof(double) * tot),
+               o_bcs = W.take(sizeof(double) * 2 * (size_t)n), o_bpoly = W.take(sizeof(int) * 2 * (size_t)n);
+  const size_t o_rows = Lst.take(sizeof(unsigned char*) * tot), o_src = Lst.take(sizeof(int) * tot),
+               o_koff = Lst.take(sizeof(int) * 2 * (size_t)n);
+  HIP_TRY(c, c->d_fam_bed_ws.grow(W.total, W.total + W.total / 2, st, true));
+  HIP_TRY(c, c->d_fam_list.grow(Lst.total, Lst.total + Lst.total / 2, st, true));
+  char *ws = c->d_fam_bed_ws, *lst = c->d_fam_list;
+  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(ws + o_cnt);
+  int *d_flags = reinterpret_cast<int*>(ws + o_flags), *d_flip = reinterpret_cast<int*>(ws + o_flip);
+  double *d_mu = reinterpret_cast<double*>(ws + o_mu), *d_fq = reinterpret_cast<double*>(ws + o_fq);
+  double* d_bcs = reinterpret_cast<double*>(ws + o_bcs);
+  int* d_bpoly = reinterpret_cast<int*>(ws + o_bpoly);
+  const unsigned char** d_krow = reinterpret_cast<const unsigned char**>(lst + o_rows);
+  int *d_ksrc = reinterpret_cast<int*>(lst + o_src), *d_koff = reinterpret_cast<int*>(lst + o_koff);
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * tot, st));
+  for (int g = 0; g < n; ++g)  // (the rows of one gene are consecutive, the genes are not)
+    bed_row_counts(st, d_rows[g], cb, N, Ms[g], d_cnt + 4 * row0[g]);
+  hipLaunchKernelGGL(fam_bed_gene_site_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_cnt, (long long)tot,
+                     d_flags);
+  HIP_TRY(c, hipGetLastError());
+  std::vector<int> flags(tot);
+  HIP_TRY(c, hipMemcpyAsync(flags.data(), d_flags, sizeof(int) * tot, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  // ---- 2. the kept rows, flipped where flagged, rotated by U' -----------------------------------------------------------------
+  std::vector<const unsigned char*> krow;
+  std::vector<int> ksrc;
+  std::vector<int>&Mk = F->Mk, &off = F->off, &kgene = F->kgene;
+  Mk.assign(n, 0), off.assign(n, 0);
+  bool any_missing = false;  // a kept row with a missing call (the block route's "not every kept column is a hard call")
+  for (int g = 0; g < n; ++g) {
+    off[g] = (int)krow.size();
+    for (int j = 0; j < Ms[g]; ++j) {
+      const size_t k = row0[g] + (size_t)j;
+      if (!(flags[k] & 2)) continue;
+      krow.push_back(d_rows[g] + (size_t)cb * (size_t)j);
+      ksrc.push_back((int)k);
+      any_missing = any_missing || !(flags[k] & 4);
+    }
+    Mk[g] = (int)krow.size() - off[g];
+  }
+  const size_t T = krow.size();
+  for (int g = 0; g < n; ++g) {
+    rvt_gene_result& r = out[g];
+    std::memset(&r, 0, sizeof(r));
+    r.gene_id = ids ? ids[g] : g;
+    r.n_variants = Ms[g];
+    r.n_poly = Mk[g];
+  }
+  if (T == 0) return RVT_OK;  // genotype.cols == 0 everywhere: all NA (src/Model.h:3066-3069)
+  std::vector<int> kom;  // (kgene: the genes with a kept row) their first kept row, then their numbers of kept rows
+  for (int g = 0; g < n; ++g)
+    if (Mk[g] > 0) kgene.push_back(g);
+  const size_t nk = kgene.size(), TB = burden ? 2 * nk : 0;
+  kom.resize(2 * nk);
+  for (size_t k = 0; k < nk; ++k) kom[k] = off[kgene[k]], kom[nk + k] = Mk[kgene[k]];
+  HIP_TRY(c, hipMemcpyAsync(d_krow, krow.data(), sizeof(unsigned char*) * T, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_ksrc, ksrc.data(), sizeof(int) * T, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_koff, kom.data(), sizeof(int) * 2 * nk, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(fam_bed_kept_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, d_cnt, d_ksrc, (long long)T, d_flip,
+                     d_mu, d_fq);
+  HIP_TRY(c, hipGetLastError());
+  const bool dense = !c->d_fam_run && !(c->d_csc_ptr && !c->d_uq_range);
+  // a dense piece with a missing call is the product [U'c' | U'm] (in d_Gp) of at most kRotMaxCols columns
+  const size_t piece = dense && any_missing ? kRotMaxCols / 2 : kRotMaxCols;
+  rc = ensure_fam_cols(c, std::max(T + TB, dense && any_missing ? 2 * std::min(T, piece) : (size_t)0), ld);
+  if (rc) return rc;
+  if (ld != N)  // pad rows must be zero (the rotation writes rows 0 .. N-1 of every column)
+    HIP_TRY(c, hipMemset2DAsync(c->d_Gt + N, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)(ld - N), T + TB, st));
+  if (c->d_fam_run) {  // the family form: the tile filled from the codes
+    const size_t per = (size_t)65535 * kRotFamCols;  // (gridDim.y holds at most 65535 column tiles)
+    for (size_t t0 = 0; t0 < T; t0 += per) {
+      const int nc = (int)std::min(per, T - t0);
+      hipLaunchKernelGGL(rot_fam_bed_list_kernel, dim3((unsigned)c->fam_runs, (unsigned)((nc + kRotFamCols - 1) / kRotFamCols)),
+                         dim3(kRotFamRows), 0, st, c->d_fam_run, c->d_fam_of, c->d_fam_ptr, c->d_fam_members, c->d_csc_ptr,
+                         c->d_csc_vals, d_krow + t0, d_flip + t0, d_mu + t0, nc, c->d_Gt + t0 * (size_t)ld, (long long)ld);
+      HIP_TRY(c, hipGetLastError());
+    }
+  } else if (!dense) {  // column-compressed U, scattered supports: the flipped fp64 columns on the device, then the gather
+    for (size_t t0 = 0; t0 < T; t0 += 65535) {  // (gridDim.y holds at most 65535 columns)
+      const unsigned nt = (unsigned)std::min<size_t>(65535, T - t0);
+      hipLaunchKernelGGL(fam_bed_expand_list_kernel, dim3((unsigned)((cb + 255) / 256), nt), dim3(256), 0, st, d_krow + t0,
+                         d_flip + t0, d_mu + t0, (long long)cb, (long long)N, (long long)ld, c->d_Gp + t0 * (size_t)ld);
+      HIP_TRY(c, hipGetLastError());
+    }
+    rc = rotate_columns(c, c->d_Gp, ld, (int)T, c->d_Gt, ld, st);
+    if (rc) return rc;
+  } else {  // dense U on digit planes: B = [c' | m], one plane each; without a missing call c' alone, straight into d_Gt
+    const int64_t ldk = c->uq_ldk;
+    for (size_t c0 = 0; c0 < T; c0 += piece) {
+      const int ncp = (int)std::min(piece, T - c0), nB = any_missing ? 2 * ncp : ncp;
+      const size_t need = (size_t)(((int64_t)nB + kRotBN - 1) / kRotBN * kRotBN) * (size_t)ldk;
+      HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
+      HIP_TRY(c, hipMemsetAsync(c->d_rotB, 0, need, st));
+      hipLaunchKernelGGL(fam_bed_unpack_list_kernel, dim3((unsigned)((cb + 255) / 256), (unsigned)ncp), dim3(256), 0, st,
+                         d_krow + c0, d_flip + c0, (long long)cb, (long long)N, ncp, any_missing ? 1 : 0, c->d_rotB.get(),
+                         (long long)ldk);
+      HIP_TRY(c, hipGetLastError());
+      const std::vector<int> zero_exp((size_t)nB, 0);
+      double* dst = c->d_Gt + c0 * (size_t)ld;
+      double* C = any_missing ? c->d_Gp.get() : dst;
+      rc = planes_gemm(c, c->d_Uq, c->uq_plane, kRotPlanesU, (int)N, nullptr, c->uq_sexp, c->d_rotB, need, 1, nB, zero_exp.data(),
+                       N, ldk, C, ld, st, c->d_uq_range);
+      if (rc) return rc;
+      if (any_missing) {
+        hipLaunchKernelGGL(fam_bed_combine_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)ncp), dim3(256), 0, st, C,
+                           (long long)ld, (long long)N, ncp, d_fq + c0, dst, (long long)ld);
+        HIP_TRY(c, hipGetLastError());
+      }
+    }
+  }
+  if (burden) {
+    // cmcCollapse / zegginiCollapse from the codes into columns 0 .. 2 nk - 1 of d_Gp (the rotation above is done with it), their
+    // raw sums and flags (the score test centres the collapsed genotype, FastLMM.cpp:218-220), rotated behind the T columns
+    if (ld != N)
+      HIP_TRY(c, hipMemset2DAsync(c->d_Gp + N, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)(ld - N), TB, st));
+    for (size_t k0 = 0; k0 < nk; k0 += 65535) {  // (gridDim.y)
+      const unsigned nkp = (unsigned)std::min<size_t>(65535, nk - k0);
+      hipLaunchKernelGGL(fam_bed_collapse_kernel, dim3((unsigned)((cb + 255) / 256), nkp), dim3(256), 0, st, d_krow, d_flip, d_mu,
+                         d_koff + k0, d_koff + nk + k0, (long long)cb, (long long)N, (long long)ld,
+                         c->d_Gp + 2 * k0 * (size_t)ld);
+    }
+    hipLaunchKernelGGL(raw_colstat_kernel, dim3((unsigned)TB), dim3(256), 0, st, c->d_Gp.get(), (long long)N, (long long)ld,
+                       d_bcs, d_bpoly);
+    HIP_TRY(c, hipGetLastError());
+    rc = rotate_columns(c, c->d_Gp, ld, (int)TB, c->d_Gt + T * (size_t)ld, ld, st);
+    if (rc) return rc;
+  }
+  HIP_TRY(c, sync_stream(st));
+  F->T = T, F->d_bcs = d_bcs, F->d_bpoly = d_bpoly;
+  *run = true;
+  return RVT_OK;
+}
+
+int rvt_run_fam_tests_bed_dev(rvt_ctx* c, int n, const unsigned char* const* d_rows, const int* Ms, const int64_t* ids,
+                              uint32_t tests, rvt_gene_result* out) {
+  FamGenesFront F;
+  bool run = false;
+  int rc = fam_genes_bed_front(c, n, d_rows, Ms, ids, tests, out, &F, &run);
+  if (rc || !run) return rc;
+  return fam_tests_tail(c, n, tests, F.Mk, F.off, F.kgene, F.T, F.d_bcs, F.d_bpoly, out);
+}
+
+// Measurement hook: the front stage of rvt_run_fam_tests_bed_dev alone (site pass, lists, rotation, burden collapse and its
+// rotation; the records are initialised, no test runs) between two HIP events — the events also enclose the copy of the flags to
+// the host and the host's pass over them (cf. rvt_debug_rotate_bed_timed)
+int rvt_debug_fam_genes_bed_front_timed(rvt_ctx* c, int n, const unsigned char* const* d_rows, const int* Ms, uint32_t tests,
+                                        rvt_gene_result* out, double* ms) {
+  if (!c || !ms) return fail(c, RVT_E_INVALID, "bad arguments");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  HIP_TRY(c, hipEventCreate(&ev[0]));
+  hipError_t e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+  if (e == hipSuccess) {
+    FamGenesFront F;
+    bool run = false;
+    rc = fam_genes_bed_front(c, n, d_rows, Ms, nullptr, tests, out, &F, &run);
+    if (!rc) e = hipEventRecord(ev[1], st);
+    if (!rc && e == hipSuccess) e = sync_stream(st);
+    float t = 0.0f;
+    if (!rc && e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+    *ms = t;
+  }
+  hipEventDestroy(ev[0]);
+  if (ev[1]) hipEventDestroy(ev[1]);
+  if (rc) return rc;
+  HIP_TRY(c, e);
   return RVT_OK;
 }
 

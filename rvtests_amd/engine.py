@@ -1179,6 +1179,36 @@ class Engine:
                                              arr_id.ctypes.data_as(C.POINTER(C.c_int64)), int(tests), out))
         return list(out)
 
+    def run_fam_tests_bed_dev(self, d_rows, Ms, ids=None, tests=16):
+        """run_fam_blocks' records for genes given as Ms[g] consecutive rows of a resident .bed matrix from the device address
+        d_rows[g] on (rvt_run_fam_tests_bed_dev: the columns a caller would have uploaded are the calls with missing imputed to
+        the mean).  tests: TEST_FAMSKAT (16) | TEST_FAMCMC (32) | TEST_FAMZEGGINI (64)"""
+        n = len(d_rows)
+        arr_p = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in d_rows])
+        arr_m = np.ascontiguousarray(Ms, dtype=np.int32)
+        arr_id = np.ascontiguousarray(ids if ids is not None else np.arange(n), dtype=np.int64)
+        out = (GeneResult * n)()
+        self.L.rvt_run_fam_tests_bed_dev.restype = C.c_int
+        self.L.rvt_run_fam_tests_bed_dev.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_int_p, C.POINTER(C.c_int64),
+                                                     C.c_uint32, C.POINTER(GeneResult)]
+        self._check(self.L.rvt_run_fam_tests_bed_dev(self.ctx, n, arr_p, arr_m.ctypes.data_as(c_int_p),
+                                                     arr_id.ctypes.data_as(C.POINTER(C.c_int64)), int(tests), out))
+        return list(out)
+
+    def debug_fam_genes_bed_front_timed(self, d_rows, Ms, tests=16):
+        """Device milliseconds of run_fam_tests_bed_dev's front stage alone (rvt_debug_fam_genes_bed_front_timed)."""
+        n = len(d_rows)
+        arr_p = (C.c_void_p * n)(*[C.c_void_p(int(p)) for p in d_rows])
+        arr_m = np.ascontiguousarray(Ms, dtype=np.int32)
+        out = (GeneResult * n)()
+        ms = C.c_double(0.0)
+        self.L.rvt_debug_fam_genes_bed_front_timed.restype = C.c_int
+        self.L.rvt_debug_fam_genes_bed_front_timed.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_int_p, C.c_uint32,
+                                                               C.POINTER(GeneResult), c_double_p]
+        self._check(self.L.rvt_debug_fam_genes_bed_front_timed(self.ctx, n, arr_p, arr_m.ctypes.data_as(c_int_p), int(tests), out,
+                                                               C.cast(C.byref(ms), c_double_p)))
+        return ms.value
+
     # ---- MetaCov --------------------------------------------------------------------------------------------
     def cov_block(self, ptr, V):
         """Covariance band of one device block of V variants: (cov V x V with cov[h, j] valid for j >= h, xz V x d,
