@@ -371,8 +371,34 @@ int rvt_cov_band(rvt_ctx* ctx, const double* dG, int ring_cols, int col0, int H,
  * trait, columns the engine knows nothing about that turned out not to be hard calls); 1 the MXFP4 band on the column cache
  * (hard calls only); 4 the MXFP4 band of MEAN-IMPUTED hard calls — every column 0 / 1 / 2 plus at most one other value known
  * from its packed upload: four exact integer products combined with the other values in fp64; 2 the MXFP4 band on a copy
- * made inside the call (no cache); 11 / 12 the same on the int8 instruction (RVT_BAND_INT8=1); -1 no call yet. */
+ * made inside the call (no cache); 11 / 12 the same on the int8 instruction (RVT_BAND_INT8=1); -1 no call yet.
+ * After rvt_cov_band_bed_dev: 21 resident rows, one product (no row of the window has a missing call); 24 resident rows, four
+ * products; 20 resident rows through the fp64 band (a binary trait, RVT_METACOV_FP64=1). */
 int rvt_cov_band_last_path(rvt_ctx* ctx);
+/* rvt_cov_band for a window that is W consecutive rows of a RESIDENT .bed matrix (rvt_bed_alloc): no ring, no fp64 column, no
+ * PCIe crossing.  d_rows is the device address of the window's first row; a row is ceil(N / 4) bytes (N the null model's sample
+ * count), rows follow each other without padding and may start at any byte; codes 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing
+ * (libVcf/PlinkInputFile.cpp:24-47); the padding bits of a row's last byte are never counted and never enter a product.
+ * Heads = rows [0, H), markers = rows [0, W), W >= H (W is clipped to H + halo).  The columns are the rows with missing calls
+ * imputed to the mean of the called ones, mu = (n1 + 2 n2) / (n0 + n1 + n2) (src/DataConsolidator.cpp:217-245), as
+ * rvt_score_bed_dev defines them; a row without a called sample is the zero column (mu = 0), monomorphic.
+ * band, xz, zz (may be NULL), polymorphic: the meaning and layout of rvt_cov_band's; `band` leaves by DMA when it lies inside
+ * a range registered with rvt_host_register, the heads in passes of 1 024 with two band buffers.  counts (optional, 4 W
+ * entries): per row the numbers of 0 / 1 / 2 / missing calls, as rvt_score_bed_dev reports them.
+ * Quantitative (unweighted) null model: a front stage (rvtests_amd/csrc/bed_band_kernels.hip.h) reads every row once and writes
+ * the E2M1 nibble rows of the calls h and of the missing mask m, the column g being h + mu m, with the row's counts and its
+ * sums against X; the band is then the exact MXFP4 product h'h — or, when some row of the window has a missing call, the four
+ * products h'h, h'm, m'h, m'm combined with the mu's in fp64, as path 4 of rvt_cov_band.  Binary null model, or
+ * RVT_METACOV_FP64=1: every pass of heads expands its rows into an fp64 work block of at most 1 024 + halo columns and runs
+ * the fp64 band on it.  Successive calls of a sliding window prepare their halo again: (H + halo) / H rows per head.
+ * RVT_E_INVALID: a null argument (zz and counts excepted), H < 1, W < H, halo < 0.  RVT_E_STATE: no null model; RVT_PACKED=0 or
+ * the hard-call kernels switched off (RVT_HARDCALL=0) — the message says which.  A refused call writes nothing.  Synchronous. */
+int rvt_cov_band_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int H, int W, int halo, float scale, float* band,
+                         double* xz, double* zz, int* polymorphic, long long* counts);
+/* With rvt_set_profiling on: the device milliseconds of the last rvt_cov_band_bed_dev between HIP events — ms3[0] the front
+ * stage with its finish (fp64 band: the count pass), ms3[1] the passes (products and band finish; fp64 band: with the
+ * expansions), ms3[2] the whole call up to the last row's copy. */
+int rvt_cov_band_bed_last_timing(rvt_ctx* ctx, double* ms3);
 /* ---- MetaScore: single-variant score statistics (unrelated samples) ----------------------------------------------
  * Replaces the per-variant body of MetaScoreTest::fit for MetaUnrelatedQtl / MetaUnrelatedBinary
  * (src/Model.h:3246-3258 -> 3516-3549 / 3706-3769), i.e. LinearRegressionScoreTest::TestCovariate

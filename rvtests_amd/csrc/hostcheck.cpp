@@ -12,6 +12,7 @@
 #include <chrono>
 #include "host_stage.h"
 #include "band_tiles.h"
+#include "rvt_bed_nibbles.h"
 #include "block_pool.h"
 #include "perm_counter.h"
 #include "rvt_pvalue.h"
@@ -407,6 +408,13 @@ int hc_band_tiles(int H, int W, int halo, int* out) {
       }
   }
   return n;
+}
+// one .bed byte with `live` (1 .. 4) samples -> out[0] = the calls' nibbles, out[1] = the mask's, out[2 .. 5] = calls of 0 / 1 / 2 / missing
+void hc_bed_byte_nibbles(unsigned byte, int live, unsigned* out) {
+  const rvt::BedNibbles nb = rvt::bed_byte_nibbles(byte, rvt::bed_live_mask(live));
+  out[0] = nb.h, out[1] = nb.m;
+  out[2] = (unsigned)rvt::bed_popc16(nb.zero), out[3] = (unsigned)rvt::bed_popc16(nb.one);
+  out[4] = (unsigned)rvt::bed_popc16(nb.two), out[5] = (unsigned)rvt::bed_popc16(nb.miss);
 }
 int hc_band_tile_of(int h, int j, int W, int halo) { return rvt::band_tile_of(h, j, W, halo); }
 long long hc_band_slices(int n_tiles, long long chunks, long long max_part_bytes) {

@@ -278,6 +278,8 @@ void rvt_destroy(rvt_ctx* c) {
   }
   for (auto& e : c->ev_recode)
     if (e) hipEventDestroy(e);
+  for (auto& e : c->ev_band_bed)
+    if (e) hipEventDestroy(e);
   // device memory: the blocks of the streaming interface (raw: the caller's blocks share their pools), then every buffer
   // the context owns (its members' destructors)
   for (auto& p : c->queue)

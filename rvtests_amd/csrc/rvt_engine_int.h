@@ -335,6 +335,9 @@ struct rvt_ctx {
   DevBuf<char> d_recode_ws;   // rvt_block_recode / rvt_bed_recode_block: the columns' integer counts and their avg (grow-only)
   hipEvent_t ev_recode[4] = {};  // with profiling on: around the count pass (0, 1) and the write pass (2, 3) of the last recoding
   double recode_ms[2] = {0.0, 0.0};
+  // rvt_cov_band_bed_dev with profiling on: the call's start (0), behind the front stage (1), around the passes (2, 3), the end (4)
+  hipEvent_t ev_band_bed[5] = {};
+  double band_bed_ms[3] = {0.0, 0.0, 0.0};  // front stage, products + band finish, whole call (rvt_cov_band_bed_last_timing)
   // single columns uploaded one call at a time (MetaCovTest / MetaScoreTest: one site per fit()) are packed into pinned memory
   // and QUEUED: the DMA, the expansion and the column pass run once per kColQueue consecutive columns (flush_col_queue) — the
   // per-call device work (eight HIP calls, ~70 us) was what held the adapter at 9 k sites/s.  ONE RULE: whatever reads a block,

@@ -9,6 +9,8 @@
 #include "wald_logistic.hip.h"
 #include "burdencol_kernels.hip.h"
 #include "recode_kernels.hip.h"
+#include "bed_band_kernels.hip.h"
+#include <functional>
 
 // row slices of MetaCov's column pass (cov_hc_prep_kernel): a function of N alone, so that a column's sums are the same numbers
 // whether it is treated inside a block or alone behind its upload (rvt_block_upload_columns)
@@ -903,6 +905,141 @@ static int ring_hard_calls(rvt_ctx* c, const double* dG, int ring, int col0, int
   return 1;
 }
 
+// The work space of a band call (c->d_cov_work), shared by rvt_cov_band and rvt_cov_band_bed_dev: T and covXZ of the W markers,
+// their sums, imputation values and flags, the column pass's partial results, two band buffers of Hp heads and — for the fp64
+// product — the rectangle of one pass; `extra` bytes behind them for the caller's own use.
+struct BandWork {
+  double *d_T = nullptr, *d_xz = nullptr, *d_cs = nullptr, *d_mu_l = nullptr, *d_tmp = nullptr, *d_S = nullptr;
+  float* d_band = nullptr;
+  int* d_poly = nullptr;
+  char* extra = nullptr;
+};
+static int band_work(rvt_ctx* c, hipStream_t st, int W, int d, int Hp, int Wp, int halo, bool fast, size_t extra, BandWork* w) {
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t bT = up(sizeof(double) * (size_t)W * d), bV = up(sizeof(double) * (size_t)W), bP = up(sizeof(int) * (size_t)W);
+  const size_t bM = up(sizeof(double) * (size_t)kCovSlices * W * (RVT_MAX_COV + 3));
+  const size_t bB = 2 * up(sizeof(float) * (size_t)Hp * ((size_t)halo + 1));
+  const size_t bS = fast ? 0 : up(sizeof(double) * (size_t)Hp * Wp);
+  const size_t need = 2 * bT + 2 * bV + bP + bM + bB + bS + extra;
+  HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4, st, true));
+  char* q = c->d_cov_work;
+  w->d_T = reinterpret_cast<double*>(q);
+  q += bT;
+  w->d_xz = reinterpret_cast<double*>(q);
+  q += bT;
+  w->d_cs = reinterpret_cast<double*>(q);
+  q += bV;
+  w->d_mu_l = reinterpret_cast<double*>(q);
+  q += bV;
+  w->d_poly = reinterpret_cast<int*>(q);
+  q += bP;
+  w->d_tmp = reinterpret_cast<double*>(q);
+  q += bM;
+  w->d_band = reinterpret_cast<float*>(q);
+  q += bB;
+  w->d_S = reinterpret_cast<double*>(q);
+  q += bS;
+  w->extra = q;
+  return RVT_OK;
+}
+
+// What the passes of a band call multiply, behind the column statistics: the nibble / int8 stores of the exact products (fast)
+// or the fp64 columns.
+struct BandRun {
+  int H = 0, W = 0, halo = 0;
+  float scale = 1.0f;
+  int Hc = 1024, Hp = 0;  // heads per pass, heads of the largest pass
+  bool fast = false, masked = false, fp4 = true;
+  const int8_t* R8 = nullptr;                     // the store of the one product (not masked)
+  const int8_t *Hs = nullptr, *Ms = nullptr;      // masked: the stores of h and m of the four products
+  int r8_ring = 0, r8_col0 = 0;                   // the stores' ring and first column
+  int64_t ldk = 0;
+  const double* dG = nullptr;                     // not fast: the block of the fp64 columns, its ring and first column
+  int ring = 0, col0 = 0;
+  // not fast, optional: called at the head of a pass (heads [h0, h0 + nh), markers [h0, h0 + wsub)) to MAKE that pass's
+  // columns and their statistics; *base then is their first column (a linear range)
+  std::function<int(int h0, int nh, int wsub, const double** base)> stage;
+};
+
+// The heads in passes of up to Hc: pass (h0, nh) covers the logical columns [h0, h0 + wsub); its rows are copied to `band` on
+// copy_stream while the next pass multiplies (two band buffers).  The last pass's event is recorded; the caller synchronises.
+static int band_passes(rvt_ctx* c, hipStream_t st, const CovConsts& cc, const BandRun& r, const BandWork& w, float* band) {
+  const NullConsts& nc = c->nc;
+  const int64_t N = nc.N, ld = nc.ld;
+  const int d = nc.d, H = r.H, W = r.W, halo = r.halo, Hc = r.Hc;
+  for (int i = 0; i < 2; ++i) {
+    if (!c->ev_band_fin[i]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_band_fin[i], hipEventDisableTiming));
+    if (!c->ev_band_copied[i]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_band_copied[i], hipEventDisableTiming));
+  }
+  float* const d_band2[2] = {w.d_band, w.d_band + (size_t)r.Hp * ((size_t)halo + 1)};
+  int pass = 0;
+  for (int h0 = 0; h0 < H; h0 += Hc, ++pass) {
+    float* const d_band = d_band2[pass & 1];
+    if (pass >= 2) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_band_copied[pass & 1], 0));  // (the buffer's previous rows have left)
+    const int nh = std::min(Hc, H - h0);
+    const int wsub = (int)std::min<long long>((long long)W - h0, (long long)nh + halo);
+    if (r.fast) {
+      const int n_tiles = band_tiles(nh, wsub, halo);
+      const int64_t kbytes = r.ldk, chunks = kbytes / kRotKC;
+      const int n_sets = r.masked ? 4 : 1;  // (mean-imputed columns: h'h, h'm, m'h, m'm)
+      int64_t nsl = band_slices(n_tiles, chunks, ((size_t)3 << 30) / (size_t)n_sets);
+      if (const char* e = getenv("RVT_BAND_SLICES"))
+        if (atoll(e) > 0) nsl = atoll(e);
+      int64_t kslice = ((chunks + nsl - 1) / nsl) * kRotKC;
+      // a slice's sums are exact in the accumulator: int32 holds 4 N for any N the engine takes; fp32 holds integers below 2^24,
+      // i.e. at most 2^22 samples = 2^21 bytes of E2M1 codes per slice
+      if (r.fp4) kslice = std::min<int64_t>(kslice, (int64_t)1 << 21);
+      nsl = (kbytes + kslice - 1) / kslice;
+      const long long set_stride = (long long)n_tiles * (long long)nsl * kBandBT * kBandBT;
+      const size_t need = sizeof(int) * (size_t)set_stride * (size_t)n_sets;
+      HIP_TRY(c, c->d_rot_part.grow(need, need, st, true));
+      int* d_part = reinterpret_cast<int*>(c->d_rot_part.get());
+      int pc = r.r8_col0 + h0;
+      if (r.r8_ring > 0 && pc >= r.r8_ring) pc -= r.r8_ring;
+      const int pr = (r.r8_ring > 0 && pc + wsub > r.r8_ring) ? r.r8_ring : 0;
+      const unsigned grid = (unsigned)(8 * (int64_t)n_tiles * ((nsl + 7) / 8));
+      if (r.masked) {
+        const int8_t* sideA[4] = {r.Hs, r.Hs, r.Ms, r.Ms};
+        const int8_t* sideB[4] = {r.Hs, r.Ms, r.Hs, r.Ms};
+        for (int k = 0; k < 4; ++k)
+          hipLaunchKernelGGL(band_gemm_fp4, dim3(grid), dim3(kBandThreads), 0, st, sideA[k], sideB[k], (long long)r.ldk, pr, pc, nh, wsub,
+                             halo, (long long)kbytes, (long long)kslice, (int)nsl, n_tiles, d_part + (size_t)k * (size_t)set_stride);
+      } else if (r.fp4) {
+        hipLaunchKernelGGL(band_gemm_fp4, dim3(grid), dim3(kBandThreads), 0, st, r.R8, r.R8, (long long)r.ldk, pr, pc, nh, wsub, halo,
+                           (long long)kbytes, (long long)kslice, (int)nsl, n_tiles, d_part);
+      } else {
+        hipLaunchKernelGGL(band_gemm_i8, dim3(grid), dim3(kBandThreads), 0, st, r.R8, r.R8, (long long)r.ldk, pr, pc, nh, wsub, halo,
+                           (long long)kbytes, (long long)kslice, (int)nsl, n_tiles, d_part);
+      }
+      hipLaunchKernelGGL(band_finish_i32_kernel, dim3((unsigned)nh), dim3(256), 0, st, cc, d_part, (int)nsl, n_tiles, w.d_cs + h0,
+                         w.d_xz + (size_t)h0 * d, nh, wsub, halo, r.scale, d_band, (double*)nullptr,
+                         r.masked ? w.d_mu_l + h0 : (const double*)nullptr, set_stride);
+    } else {
+      // dosages, a binary trait's weights: the band tiles of S = G_H' D G_W on the fp64 matrix cores (gemm_f64.hip.h)
+      const double* wts = nc.binary ? c->d_v : nullptr;
+      int pc = r.col0 + h0;
+      if (r.ring > 0 && pc >= r.ring) pc -= r.ring;
+      int pr = (r.ring > 0 && pc + wsub > r.ring) ? r.ring : 0;
+      const double* base = pr ? r.dG : r.dG + (size_t)pc * ld;
+      if (r.stage) {
+        pr = 0;
+        if (int rc = r.stage(h0, nh, wsub, &base)) return rc;
+      }
+      int rc = gemm_tn_f64(c, base, ld, nh, base, ld, wsub, nullptr, 0, 0, wts, N, w.d_S, nh, true, st, false, halo, pr, pr ? pc : 0);
+      if (rc) return rc;
+      hipLaunchKernelGGL(band_rows_f64_kernel, dim3((unsigned)nh), dim3(256), 0, st, cc, w.d_S, (long long)nh, w.d_cs + h0,
+                         w.d_xz + (size_t)h0 * d, (const double*)nullptr, nh, wsub, halo, 1.0, r.scale, d_band, (double*)nullptr);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_band_fin[pass & 1], st));
+    HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_band_fin[pass & 1], 0));
+    HIP_TRY(c, hipMemcpyAsync(band + (size_t)h0 * ((size_t)halo + 1), d_band, sizeof(float) * (size_t)nh * ((size_t)halo + 1),
+                              hipMemcpyDeviceToHost, c->copy_stream));
+    HIP_TRY(c, hipEventRecord(c->ev_band_copied[pass & 1], c->copy_stream));
+  }
+  return RVT_OK;
+}
+
 static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H, int W, int halo, float scale, float* band,
                          double* xz, double* zz, int* polymorphic, bool allow_fast) {
   if (!c || !dG || ring < 0 || col0 < 0 || H < 1 || W < H || halo < 0 || !band || !xz || !polymorphic)
@@ -943,34 +1080,11 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
   int Hc = 1024;
   if (const char* e = getenv("RVT_BAND_PASS")) Hc = std::max(256, atoi(e) / 256 * 256);
   const int Hp = std::min(H, Hc), Wp = (int)std::min<long long>(W, (long long)Hp + halo);
-  double *d_T = nullptr, *d_cs = nullptr, *d_xz = nullptr, *d_tmp = nullptr, *d_S = nullptr, *d_mu_l = nullptr;
-  float* d_band = nullptr;
-  int* d_poly = nullptr;
-  {
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t bT = up(sizeof(double) * (size_t)W * d), bV = up(sizeof(double) * (size_t)W), bP = up(sizeof(int) * (size_t)W);
-    const size_t bM = up(sizeof(double) * (size_t)kCovSlices * W * (RVT_MAX_COV + 3));
-    const size_t bB = 2 * up(sizeof(float) * (size_t)Hp * ((size_t)halo + 1));
-    const size_t bS = fast ? 0 : up(sizeof(double) * (size_t)Hp * Wp);
-    const size_t need = 2 * bT + 2 * bV + bP + bM + bB + bS;
-    HIP_TRY(c, c->d_cov_work.grow(need, need + need / 4, st, true));
-    char* q = c->d_cov_work;
-    d_T = reinterpret_cast<double*>(q);
-    q += bT;
-    d_xz = reinterpret_cast<double*>(q);
-    q += bT;
-    d_cs = reinterpret_cast<double*>(q);
-    q += bV;
-    d_mu_l = reinterpret_cast<double*>(q);
-    q += bV;
-    d_poly = reinterpret_cast<int*>(q);
-    q += bP;
-    d_tmp = reinterpret_cast<double*>(q);
-    q += bM;
-    d_band = reinterpret_cast<float*>(q);
-    q += bB;
-    d_S = reinterpret_cast<double*>(q);
-  }
+  BandWork bw;
+  rc = band_work(c, st, W, d, Hp, Wp, halo, fast, 0, &bw);
+  if (rc) return rc;
+  double *const d_T = bw.d_T, *const d_cs = bw.d_cs, *const d_xz = bw.d_xz, *const d_tmp = bw.d_tmp, *const d_mu_l = bw.d_mu_l;
+  int* const d_poly = bw.d_poly;
   const int dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
   const int wgs = (W + kCovHcCols - 1) / kCovHcCols;
   const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, N / 4096 + 1));
@@ -1012,75 +1126,18 @@ static int cov_band_impl(rvt_ctx* c, const double* dG, int ring, int col0, int H
   }
   hipLaunchKernelGGL(cov_rect_xz_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, cc, d_T, d_cs, W, d_xz);
   HIP_TRY(c, hipGetLastError());
-  // the heads in passes of up to Hc: pass (h0, nh) covers the logical columns [h0, h0 + wsub)
-  for (int i = 0; i < 2; ++i) {
-    if (!c->ev_band_fin[i]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_band_fin[i], hipEventDisableTiming));
-    if (!c->ev_band_copied[i]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_band_copied[i], hipEventDisableTiming));
+  // the heads in passes of up to Hc (band_passes)
+  BandRun br;
+  br.H = H, br.W = W, br.halo = halo, br.scale = scale, br.Hc = Hc, br.Hp = Hp;
+  br.fast = fast, br.masked = masked, br.fp4 = fp4;
+  br.R8 = R8, br.r8_ring = r8_ring, br.r8_col0 = r8_col0, br.ldk = ldk;
+  if (masked) {
+    br.Hs = reinterpret_cast<const int8_t*>(ckc->d_i4.get());
+    br.Ms = reinterpret_cast<const int8_t*>(ckc->d_m4.get());
   }
-  float* const d_band2[2] = {d_band, d_band + (size_t)Hp * ((size_t)halo + 1)};
-  int pass = 0;
-  for (int h0 = 0; h0 < H; h0 += Hc, ++pass) {
-    float* const d_band = d_band2[pass & 1];
-    if (pass >= 2) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_band_copied[pass & 1], 0));  // (the buffer's previous rows have left)
-    const int nh = std::min(Hc, H - h0);
-    const int wsub = (int)std::min<long long>((long long)W - h0, (long long)nh + halo);
-    if (fast) {
-      const int n_tiles = band_tiles(nh, wsub, halo);
-      const int64_t kbytes = ldk, chunks = kbytes / kRotKC;
-      const int n_sets = masked ? 4 : 1;  // (mean-imputed columns: h'h, h'm, m'h, m'm)
-      int64_t nsl = band_slices(n_tiles, chunks, ((size_t)3 << 30) / (size_t)n_sets);
-      if (const char* e = getenv("RVT_BAND_SLICES"))
-        if (atoll(e) > 0) nsl = atoll(e);
-      int64_t kslice = ((chunks + nsl - 1) / nsl) * kRotKC;
-      // a slice's sums are exact in the accumulator: int32 holds 4 N for any N the engine takes; fp32 holds integers below 2^24,
-      // i.e. at most 2^22 samples = 2^21 bytes of E2M1 codes per slice
-      if (fp4) kslice = std::min<int64_t>(kslice, (int64_t)1 << 21);
-      nsl = (kbytes + kslice - 1) / kslice;
-      const long long set_stride = (long long)n_tiles * (long long)nsl * kBandBT * kBandBT;
-      const size_t need = sizeof(int) * (size_t)set_stride * (size_t)n_sets;
-      HIP_TRY(c, c->d_rot_part.grow(need, need, st, true));
-      int* d_part = reinterpret_cast<int*>(c->d_rot_part.get());
-      int pc = r8_col0 + h0;
-      if (r8_ring > 0 && pc >= r8_ring) pc -= r8_ring;
-      const int pr = (r8_ring > 0 && pc + wsub > r8_ring) ? r8_ring : 0;
-      const unsigned grid = (unsigned)(8 * (int64_t)n_tiles * ((nsl + 7) / 8));
-      if (masked) {
-        const int8_t* Hs = reinterpret_cast<const int8_t*>(ckc->d_i4.get());
-        const int8_t* Ms = reinterpret_cast<const int8_t*>(ckc->d_m4.get());
-        const int8_t* sideA[4] = {Hs, Hs, Ms, Ms};
-        const int8_t* sideB[4] = {Hs, Ms, Hs, Ms};
-        for (int k = 0; k < 4; ++k)
-          hipLaunchKernelGGL(band_gemm_fp4, dim3(grid), dim3(kBandThreads), 0, st, sideA[k], sideB[k], (long long)ldk, pr, pc, nh, wsub,
-                             halo, (long long)kbytes, (long long)kslice, (int)nsl, n_tiles, d_part + (size_t)k * (size_t)set_stride);
-      } else if (fp4) {
-        hipLaunchKernelGGL(band_gemm_fp4, dim3(grid), dim3(kBandThreads), 0, st, R8, R8, (long long)ldk, pr, pc, nh, wsub, halo,
-                           (long long)kbytes, (long long)kslice, (int)nsl, n_tiles, d_part);
-      } else {
-        hipLaunchKernelGGL(band_gemm_i8, dim3(grid), dim3(kBandThreads), 0, st, R8, R8, (long long)ldk, pr, pc, nh, wsub, halo,
-                           (long long)kbytes, (long long)kslice, (int)nsl, n_tiles, d_part);
-      }
-      hipLaunchKernelGGL(band_finish_i32_kernel, dim3((unsigned)nh), dim3(256), 0, st, cc, d_part, (int)nsl, n_tiles, d_cs + h0,
-                         d_xz + (size_t)h0 * d, nh, wsub, halo, scale, d_band, (double*)nullptr,
-                         masked ? d_mu_l + h0 : (const double*)nullptr, set_stride);
-    } else {
-      // dosages, a binary trait's weights: the band tiles of S = G_H' D G_W on the fp64 matrix cores (gemm_f64.hip.h)
-      const double* wts = nc.binary ? c->d_v : nullptr;
-      int pc = col0 + h0;
-      if (ring > 0 && pc >= ring) pc -= ring;
-      const int pr = (ring > 0 && pc + wsub > ring) ? ring : 0;
-      const double* base = pr ? dG : dG + (size_t)pc * ld;
-      rc = gemm_tn_f64(c, base, ld, nh, base, ld, wsub, nullptr, 0, 0, wts, N, d_S, nh, true, st, false, halo, pr, pr ? pc : 0);
-      if (rc) return rc;
-      hipLaunchKernelGGL(band_rows_f64_kernel, dim3((unsigned)nh), dim3(256), 0, st, cc, d_S, (long long)nh, d_cs + h0,
-                         d_xz + (size_t)h0 * d, (const double*)nullptr, nh, wsub, halo, 1.0, scale, d_band, (double*)nullptr);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_band_fin[pass & 1], st));
-    HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_band_fin[pass & 1], 0));
-    HIP_TRY(c, hipMemcpyAsync(band + (size_t)h0 * ((size_t)halo + 1), d_band, sizeof(float) * (size_t)nh * ((size_t)halo + 1),
-                              hipMemcpyDeviceToHost, c->copy_stream));
-    HIP_TRY(c, hipEventRecord(c->ev_band_copied[pass & 1], c->copy_stream));
-  }
+  br.dG = dG, br.ring = ring, br.col0 = col0;
+  rc = band_passes(c, st, cc, br, bw, band);
+  if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(xz, d_xz, sizeof(double) * (size_t)W * d, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(polymorphic, d_poly, sizeof(int) * (size_t)W, hipMemcpyDeviceToHost, st));
   if (d_bad) HIP_TRY(c, hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1094,6 +1151,175 @@ int rvt_cov_band_last_path(rvt_ctx* c) { return c ? c->band_last_path : -1; }
 int rvt_cov_band(rvt_ctx* c, const double* dG, int ring_cols, int col0, int H, int W, int halo, float scale, float* band,
                  double* xz, double* zz, int* polymorphic) {
   return cov_band_impl(c, dG, ring_cols, col0, H, W, halo, scale, band, xz, zz, polymorphic, true);
+}
+
+// ---- MetaCov's band from rows of a resident .bed matrix (bed_band_kernels.hip.h) -------------------------------------------------
+// measurement (rvt_set_profiling): HIP events at the call's start (0), behind the front stage (1), directly in front of and
+// behind the passes (2, 3) and at the end (4)
+static int band_bed_mark(rvt_ctx* c, int k, hipStream_t st) {
+  if (!c->profiling) return RVT_OK;
+  if (!c->ev_band_bed[k]) HIP_TRY(c, hipEventCreate(&c->ev_band_bed[k]));
+  HIP_TRY(c, hipEventRecord(c->ev_band_bed[k], st));
+  return RVT_OK;
+}
+static int band_bed_times(rvt_ctx* c) {  // (behind the call's last synchronisation)
+  if (!c->profiling) return RVT_OK;
+  float a = 0.0f, b = 0.0f, t = 0.0f;
+  HIP_TRY(c, hipEventElapsedTime(&a, c->ev_band_bed[0], c->ev_band_bed[1]));
+  HIP_TRY(c, hipEventElapsedTime(&b, c->ev_band_bed[2], c->ev_band_bed[3]));
+  HIP_TRY(c, hipEventElapsedTime(&t, c->ev_band_bed[0], c->ev_band_bed[4]));
+  c->band_bed_ms[0] = a, c->band_bed_ms[1] = b, c->band_bed_ms[2] = t;
+  return RVT_OK;
+}
+int rvt_cov_band_bed_last_timing(rvt_ctx* c, double* ms3) {
+  if (!c || !ms3) return RVT_E_INVALID;
+  for (int k = 0; k < 3; ++k) ms3[k] = c->band_bed_ms[k];
+  return RVT_OK;
+}
+
+// Heads = rows [0, H), markers = rows [0, W) of the W consecutive rows at d_rows; the columns are the rows with missing calls
+// imputed to the row's mean, g = h + mu m.  Quantitative model: the front stage writes the nibble rows of h (d_rotA) and m
+// (d_rotB) and the rows' statistics; a read-back of one flag chooses one product (no missing call in the window, path 21) or
+// four (path 24).  Binary model or RVT_METACOV_FP64=1 (path 20): counts -> mu, then every pass expands its rows into an fp64
+// block of at most 1 024 + halo columns (d_rotA), takes their statistics from it and multiplies on the fp64 matrix cores.
+int rvt_cov_band_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int H, int W, int halo, float scale, float* band, double* xz,
+                         double* zz, int* polymorphic, long long* counts) {
+  if (!c || !d_rows || H < 1 || W < H || halo < 0 || !band || !xz || !polymorphic) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  // (as rvt_score_bed_dev: the resident-row calls are one family behind the same two switches)
+  if (getenv("RVT_PACKED") && atoi(getenv("RVT_PACKED")) == 0)
+    return fail(c, RVT_E_STATE, "rvt_cov_band_bed_dev: the packed-row kernels are switched off (RVT_PACKED=0)");
+  if (!c->hc_enabled)
+    return fail(c, RVT_E_STATE, "rvt_cov_band_bed_dev: the packed rows need the hard-call kernels, which are switched off (RVT_HARDCALL=0)");
+  if ((long long)W > (long long)H + halo) W = H + halo;  // (markers behind the last head's window are never read)
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const NullConsts& nc = c->nc;
+  const int64_t N = nc.N, ld = nc.ld, cb = (N + 3) / 4;
+  const int d = nc.d;
+  CovConsts cc;
+  std::vector<double> zzv;
+  rc = cov_constants(c, false, &cc, &zzv);
+  if (rc) return rc;
+  const bool fast = !nc.binary && !getenv("RVT_METACOV_FP64");
+  int Hc = 1024;
+  if (const char* e = getenv("RVT_BAND_PASS")) Hc = std::max(256, atoi(e) / 256 * 256);
+  const int Hp = std::min(H, Hc), Wp = (int)std::min<long long>(W, (long long)Hp + halo);
+  const int dmax = d <= 4 ? 4 : (d <= 8 ? 8 : RVT_MAX_COV);
+  const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kCovSlices, N / 4096 + 1));
+  Layout X;  // (behind the shared work space: the front stage's partial results, the counts, the flag)
+  const size_t o_pt = X.take(fast ? sizeof(double) * (size_t)slices * W * 2 * dmax : 0);
+  const size_t o_pc = X.take(fast ? sizeof(int) * (size_t)slices * W * 4 : 0);
+  const size_t o_cnt = X.take(sizeof(long long) * 4 * (size_t)W);
+  const size_t o_flag = X.take(sizeof(int));
+  BandWork bw;
+  rc = band_work(c, st, W, d, Hp, Wp, halo, fast, X.total, &bw);
+  if (rc) return rc;
+  if ((rc = band_bed_mark(c, 0, st))) return rc;
+  long long* d_cnt = reinterpret_cast<long long*>(bw.extra + o_cnt);
+  std::vector<long long> cnt(4 * (size_t)W);
+  BandRun br;
+  br.H = H, br.W = W, br.halo = halo, br.scale = scale, br.Hc = Hc, br.Hp = Hp, br.fast = fast;
+  if (fast) {
+    const int64_t ldk4 = ((N + 1) / 2 + 127) / 128 * 128;
+    const size_t need = ((size_t)W + kBandBT) * (size_t)ldk4;
+    HIP_TRY(c, c->d_rotA.grow(need, need + need / 4, st, true));
+    HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
+    unsigned char* outH = reinterpret_cast<unsigned char*>(c->d_rotA.get());
+    unsigned char* outM = reinterpret_cast<unsigned char*>(c->d_rotB.get());
+    const int64_t nw = (N + 15) / 16 * 8;  // bytes of a nibble row the front stage writes; the pad behind them: zero
+    if (ldk4 > nw) {
+      HIP_TRY(c, hipMemset2DAsync(outH + nw, (size_t)ldk4, 0, (size_t)(ldk4 - nw), (size_t)W, st));
+      HIP_TRY(c, hipMemset2DAsync(outM + nw, (size_t)ldk4, 0, (size_t)(ldk4 - nw), (size_t)W, st));
+    }
+    double* d_pt = reinterpret_cast<double*>(bw.extra + o_pt);
+    int* d_pc = reinterpret_cast<int*>(bw.extra + o_pc);
+    int* d_flag = reinterpret_cast<int*>(bw.extra + o_flag);
+    HIP_TRY(c, hipMemsetAsync(d_flag, 0, sizeof(int), st));
+#define RVT_BED_PREP(DM)                                                                                                      \
+  hipLaunchKernelGGL((bed_band_prep_kernel<DM>), dim3((unsigned)((W + BedBandRows<DM>::value - 1) / BedBandRows<DM>::value),  \
+                                                      (unsigned)slices),                                                     \
+                     dim3(256), 0, st, d_rows, (long long)cb, (long long)N, W, c->d_X, (long long)ld, d, outH, outM,          \
+                     (long long)ldk4, d_pt, d_pc)
+    if (dmax == 4) RVT_BED_PREP(4);
+    else if (dmax == 8) RVT_BED_PREP(8);
+    else RVT_BED_PREP(RVT_MAX_COV);
+#undef RVT_BED_PREP
+    hipLaunchKernelGGL(bed_band_finish_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, d_pt, d_pc, slices, W, d, dmax,
+                       bw.d_cs, bw.d_poly, bw.d_T, bw.d_mu_l, d_cnt, d_flag);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = band_bed_mark(c, 1, st))) return rc;
+    hipLaunchKernelGGL(cov_rect_xz_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, cc, bw.d_T, bw.d_cs, W, bw.d_xz);
+    HIP_TRY(c, hipGetLastError());
+    int h_any = 0;
+    HIP_TRY(c, hipMemcpyAsync(&h_any, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(long long) * cnt.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    br.masked = h_any != 0;  // (no missing call in the window: m = 0, the one product h'h is the whole of S)
+    br.fp4 = true;
+    br.R8 = br.Hs = reinterpret_cast<const int8_t*>(outH);
+    br.Ms = reinterpret_cast<const int8_t*>(outM);
+    br.ldk = ldk4;
+    c->band_last_path = br.masked ? 24 : 21;
+  } else {
+    unsigned long long* d_cnt_u = reinterpret_cast<unsigned long long*>(d_cnt);
+    HIP_TRY(c, hipMemsetAsync(d_cnt_u, 0, sizeof(long long) * cnt.size(), st));
+    constexpr int kRows = 32768;  // rows per launch (gridDim.y)
+    for (int k0 = 0; k0 < W; k0 += kRows)
+      bed_row_counts(st, d_rows + (size_t)k0 * (size_t)cb, cb, N, std::min(kRows, W - k0), d_cnt_u + 4 * (size_t)k0);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(long long) * cnt.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    std::vector<double> mu((size_t)W);
+    for (int j = 0; j < W; ++j) {
+      const long long* q = &cnt[4 * (size_t)j];
+      const long long called = q[0] + q[1] + q[2];
+      mu[(size_t)j] = (q[3] > 0 && called > 0) ? (double)(q[1] + 2 * q[2]) / (double)called : 0.0;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bw.d_mu_l, mu.data(), sizeof(double) * (size_t)W, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, sync_stream(st));  // (mu goes out of use on the host)
+    if ((rc = band_bed_mark(c, 1, st))) return rc;
+    const size_t need = sizeof(double) * (size_t)Wp * (size_t)ld;
+    HIP_TRY(c, c->d_rotA.grow(need, need, st, true));
+    double* E = reinterpret_cast<double*>(c->d_rotA.get());
+    if (ld > N)  // (the expansion writes rows [0, N) of a column; the pad rows behind them: zero)
+      HIP_TRY(c, hipMemset2DAsync(E + N, sizeof(double) * (size_t)ld, 0, sizeof(double) * (size_t)(ld - N), (size_t)Wp, st));
+    const double* wts = nc.binary ? c->d_v : nullptr;
+    br.stage = [=](int h0, int nh, int wsub, const double** base) -> int {
+      (void)nh;
+      for (int k0 = 0; k0 < wsub; k0 += kRows)
+        bed_rows_expand(st, d_rows + (size_t)(h0 + k0) * (size_t)cb, cb, bw.d_mu_l + h0 + k0, N, ld, std::min(kRows, wsub - k0),
+                        E + (size_t)k0 * (size_t)ld);
+      launch_cov_prep(st, d, false, dim3((unsigned)((wsub + kCovHcCols - 1) / kCovHcCols), (unsigned)slices), E, N, ld, wsub, c->d_X,
+                      nullptr, 0, bw.d_tmp, nullptr, wts, nullptr, 0, 0, nullptr, 0);
+      hipLaunchKernelGGL(cov_hc_finish_kernel, dim3((unsigned)((wsub * (dmax + 3) + 255) / 256)), dim3(256), 0, st, bw.d_tmp, slices,
+                         wsub, d, dmax, bw.d_cs + h0, bw.d_poly + h0, bw.d_T);
+      hipLaunchKernelGGL(cov_rect_xz_kernel, dim3((unsigned)((wsub + 255) / 256)), dim3(256), 0, st, cc, bw.d_T, bw.d_cs + h0, wsub,
+                         bw.d_xz + (size_t)h0 * d);
+      HIP_TRY(c, hipGetLastError());
+      *base = E;
+      return RVT_OK;
+    };
+    c->band_last_path = 20;
+  }
+  if ((rc = band_bed_mark(c, 2, st))) return rc;
+  rc = band_passes(c, st, cc, br, bw, band);
+  if (rc) return rc;
+  if ((rc = band_bed_mark(c, 3, st))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(xz, bw.d_xz, sizeof(double) * (size_t)W * d, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(polymorphic, bw.d_poly, sizeof(int) * (size_t)W, hipMemcpyDeviceToHost, st));
+  if (c->profiling) {  // (the whole call ends when the last pass's rows have left)
+    const int last = ((H + Hc - 1) / Hc - 1) & 1;
+    HIP_TRY(c, hipStreamWaitEvent(st, c->ev_band_copied[last], 0));
+    if ((rc = band_bed_mark(c, 4, st))) return rc;
+  }
+  HIP_TRY(c, sync_stream(st));
+  HIP_TRY(c, sync_stream(c->copy_stream));
+  if (zz) std::memcpy(zz, zzv.data(), sizeof(double) * (size_t)d * d);
+  if (counts) std::memcpy(counts, cnt.data(), sizeof(long long) * cnt.size());
+  return band_bed_times(c);
 }
 
 // MetaCov with kinship for windows wider than one block (MetaCovFamQtl / MetaCovFamBinary, src/Model.cpp:437-504,595-692):

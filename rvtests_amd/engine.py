@@ -1414,10 +1414,43 @@ class Engine:
 
     def cov_band_last_path(self):
         """0 fp64 product, 1 MXFP4 band on the column cache, 4 the same for mean-imputed columns (four products), 2 MXFP4 band on a
-        copy made in the call, 11 / 12 the int8 instruction (rvt_cov_band_last_path)."""
+        copy made in the call, 11 / 12 the int8 instruction; after cov_band_bed: 21 resident rows, one product, 24 resident
+        rows, four products, 20 resident rows through the fp64 band (rvt_cov_band_last_path)."""
         self.L.rvt_cov_band_last_path.restype = C.c_int
         self.L.rvt_cov_band_last_path.argtypes = [C.c_void_p]
         return int(self.L.rvt_cov_band_last_path(self.ctx))
+
+    def cov_band_bed(self, d_rows, H, W, halo, scale=1.0, band=None, want_counts=True):
+        """cov_band for a window that is W consecutive rows of a resident .bed matrix, d_rows = device address of the first
+        (rvt_cov_band_bed_dev): heads = rows [0, H), markers = rows [0, W), missing calls imputed to the row's mean.  Returns
+        (band H x (halo + 1) float32, xz W x d, zz, polymorphic, counts (W, 4): n0 n1 n2 missing — None without want_counts),
+        W clipped to H + halo.  `band`: an optional float32 array to write into (e.g. one registered with host_register)."""
+        H, W, halo = int(H), int(W), int(halo)
+        Wc = max(min(W, H + halo), 0)
+        Hb = max(H, 0)
+        if band is None:
+            band = np.empty((Hb, max(halo, 0) + 1), dtype=np.float32)
+        assert band.dtype == np.float32 and band.flags.c_contiguous and band.size >= Hb * (max(halo, 0) + 1)
+        xz = np.zeros((Wc, self.d))
+        zz = np.zeros((self.d, self.d))
+        poly = np.zeros(Wc, dtype=np.int32)
+        cnt = np.zeros((Wc, 4), dtype=np.int64) if want_counts else None
+        self.L.rvt_cov_band_bed_dev.restype = C.c_int
+        self.L.rvt_cov_band_bed_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                C.POINTER(C.c_float), c_double_p, c_double_p, c_int_p, C.c_void_p]
+        self._check(self.L.rvt_cov_band_bed_dev(self.ctx, C.c_void_p(int(d_rows)), H, W, halo, float(scale),
+                                                band.ctypes.data_as(C.POINTER(C.c_float)), _dp(xz), _dp(zz),
+                                                poly.ctypes.data_as(c_int_p), cnt.ctypes.data_as(C.c_void_p) if want_counts else None))
+        return band.reshape(-1)[:H * (halo + 1)].reshape(H, halo + 1), xz, zz, poly, cnt
+
+    def cov_band_bed_last_timing(self):
+        """(front stage ms, products + band finish ms, whole call ms) of the last cov_band_bed, measured with
+        set_profiling(True)."""
+        ms = np.zeros(3)
+        self.L.rvt_cov_band_bed_last_timing.restype = C.c_int
+        self.L.rvt_cov_band_bed_last_timing.argtypes = [C.c_void_p, c_double_p]
+        self._check(self.L.rvt_cov_band_bed_last_timing(self.ctx, _dp(ms)))
+        return tuple(float(v) for v in ms)
 
     def cov_rect_fam(self, ptr, col0, H, W, d):
         """Family-mode heads x window rectangle (after set_kinship + fit_fam_null); d = columns of X."""
