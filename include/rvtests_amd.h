@@ -1156,6 +1156,15 @@ int rvt_debug_collapse(rvt_ctx* ctx, const double* dG, int M, double* cmc_out, d
  * colsum/min/max (M each); host outputs, row-major */
 int rvt_debug_suffstat(rvt_ctx* ctx, const double* dG, int M, double* S, double* T, double* u, double* colsum,
                        double* cmin, double* cmax);
+/* the same of ONE gene of a resident .bed matrix (rvt_bed_alloc / rvt_bed_upload): d_rows = the device address of its first
+ * row, M consecutive rows.  The rows are counted and copied into a packed block as rvt_submit_gene[s]_bed_dev do and run as a
+ * batch of their own on the packed-row kernel; S (M x M), T (M x d), u (M), colsum (M) are host outputs, row-major, over the
+ * mean-imputed calls (any of them may be NULL).  *planes_used (may be NULL): 1 when G'[X | rr] was formed on the int8 matrix
+ * cores from the null tile's eight digit planes, 0 when the fp64 product was (a model whose columns the planes cannot carry,
+ * RVT_HCP_PLANES=0).  RVT_E_STATE for a gene the resident route expands to an fp64 block instead: a binary trait, more than
+ * 13 covariates, M > 96, RVT_PACKED=0 / RVT_HARDCALL=0 — inspect such a gene as a block, rvt_debug_suffstat. */
+int rvt_debug_suffstat_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int M, double* S, double* T, double* u,
+                               double* colsum, int* planes_used);
 /* the spectrum stage of ONE block as the per-gene tail kernels left it, run as a batch of its own under RVT_TEST_ALL with
  * the caller's allele frequencies af (M entries; the two calls above use a constant 0.01).  rec: the gene's record.
  * lambda (2 M doubles, may be NULL): the gene's eigenvalue side buffer — the kept SKAT eigenvalues, descending, from

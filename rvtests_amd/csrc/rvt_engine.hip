@@ -397,8 +397,9 @@ int rvt_set_null(rvt_ctx* c, int trait, int64_t N, int d, const double* X, const
       HIP_TRY(c, hipMemcpy(c->d_vq, vq.data(), vq.size(), hipMemcpyHostToDevice));
       // The workgroup-cooperative kernel (suffstat_hcx.hip.h) multiplies the null tile on the int8 matrix cores too: every
       // column [vX_k | res | v] as six balanced base-128 digits of its fixed-point value, 42 bits below a power of two above
-      // twice the column's largest entry.  A column whose largest entry exceeds 256 x its root mean square would leave
-      // its typical entries fewer than 34 bits: such a model stays on the one-wave kernel (fp64 products of the tile).
+      // twice the column's largest entry.  A column whose largest entry exceeds 4096 x the median of its non-zero magnitudes
+      // (column_scale_ok) would leave its typical entries fewer than 30 bits: such a model stays on the one-wave kernel (fp64
+      // products of the tile).
       const char* ex = getenv("RVT_HCX");
       bool okx = !(ex && atoi(ex) == 0) && d + 2 <= kHcxStageCols;  // (wider models: the LDS stage of the kernel holds 8 columns)
       double scale[kHcxNullCols];
@@ -1596,6 +1597,7 @@ static int launch_integer_genes(rvt_ctx* c, const Batch& b) {
         if (rcp) return rcp;
         planes = c->hcp_planes_state == 1;
       }
+      if (b.dbg && b.dbg->planes_used) *b.dbg->planes_used = planes ? 1 : 0;  // (rvt_debug_suffstat_bed_dev: one gene)
       const HcpPlanes pl{c->d_hcp_xq, c->d_hcp_scale, d + 1};
       k2_launch_hcp(MT, grid, hst, d_desc + k, tile, N, ld, d, planes ? &pl : nullptr,
                     planes && b.cov && b.cov->score && MT <= 2 && !getenv("RVT_SCORE_BED_FULL"));
@@ -2051,6 +2053,14 @@ int rvt_debug_suffstat(rvt_ctx* c, const double* dG, int M, double* S, double* T
   if (rc) return rc;
   rc = rvt_sync(c);
   if (rc) return rc;
+  return debug_suffstat_collect(c, g0, M, S, T, u, colsum, cmin, cmax);
+}
+
+// The wave-part images of ONE gene (its descriptor as the debug batch left it, synchronised) summed on the host the way
+// gene_assemble combines them: rvt_debug_suffstat's second half, shared with rvt_debug_suffstat_bed_dev (rvt_stream.hip) — the
+// packed-row kernel writes the hard-call kernel's layout.
+int debug_suffstat_collect(rvt_ctx* c, GeneDesc g0, int M, double* S, double* T, double* u, double* colsum, double* cmin,
+                           double* cmax) {
   const int d = c->nc.d;
   const size_t psz = (size_t)g0.Mp * g0.Cp;
   if (g0.hc) {  // handed back by the hard-call kernel: the general kernel's statistics are what the buffers hold

@@ -909,6 +909,8 @@ RVT_INTERNAL int rvt_kbac_stage(rvt_ctx* c, const double* dG, int M, const doubl
 RVT_INTERNAL int enqueue_classify(rvt_ctx* c, const double* dG, int M, int64_t N, int64_t ld, hipStream_t st, int* d_flag);
 RVT_INTERNAL int cov_constants(rvt_ctx* c, bool fam, CovConsts* ccp, std::vector<double>* zzp);
 RVT_INTERNAL int ensure_hcp_planes(rvt_ctx* c);
+RVT_INTERNAL int debug_suffstat_collect(rvt_ctx* c, GeneDesc g0, int M, double* S, double* T, double* u, double* colsum,
+                                        double* cmin, double* cmax);
 RVT_INTERNAL int run_blocks_with_perm(rvt_ctx* c, int n, const double* const* dG, const int* M, const double* af,
                                       const int64_t* ids, uint32_t tests, const rvt_params* prm, rvt_gene_result* out);
 }
@@ -942,6 +944,7 @@ struct DebugOut {
   double* cmc = nullptr;
   double* zeg = nullptr;
   GeneDesc* desc0 = nullptr;
+  int* planes_used = nullptr;  // packed rows: 1 = gene_tnull_hcp formed the T columns from the digit planes, 0 = the fp64 product
 };
 
 struct CovOut {  // rvt_cov_block: host destinations

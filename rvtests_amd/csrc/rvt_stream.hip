@@ -1289,6 +1289,55 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
   return rc;
 }
 
+// ---- test hook: the sufficient statistics of ONE resident gene (cf. rvt_debug_suffstat) ------------------------------------------
+// The gene's M rows into a packed block the way rvt_score_bed_dev fills its slices (one lease, the two launches of
+// bed_rows_consolidate), then a batch of its own of kind "packed rows, planes wanted" — what rvt_submit_gene[s]_bed_dev
+// queue — with a DebugOut, and the wave-part images summed on the host (debug_suffstat_collect).  *planes_used: what
+// launch_integer_genes decided for that batch.  A gene the resident route would expand (packed_eligible) is refused: there is no
+// packed block to look at.  Synchronous.
+int rvt_debug_suffstat_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int M, double* S, double* T, double* u, double* colsum,
+                               int* planes_used) {
+  if (!c || !d_rows || M < 1 || M > RVT_MAX_VARIANTS) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  if (!packed_eligible(c, M, RVT_TEST_SKAT, nullptr))
+    return fail(c, RVT_E_STATE, "rvt_debug_suffstat_bed_dev: this gene is not kept as 2-bit rows (a binary trait, more than 13 "
+                "covariates, more than 96 variants, or the packed-row kernel switched off): it is expanded to an fp64 block");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->io_stream;
+  const int64_t N = c->nc.N;
+  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
+  BlockLease blk = lease_packed(c, M);  // (back in the pool on every return: the batch below is finished by then)
+  if (!blk) return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed gene", packed_block_bytes(N, M));
+  if (blk.fresh() && hipMemsetAsync(blk.get(), 0, blk.bytes(), st) != hipSuccess)
+    return fail(c, RVT_E_HIP, "clearing a packed gene's block failed");
+  std::vector<BedRowRef> rows;
+  std::vector<BedGeneRef> genes;
+  for (int j = 0; j < M; ++j) rows.push_back(BedRowRef{d_rows + cb * (size_t)j, packed_rows(blk) + pk_pitch * (size_t)j});
+  genes.push_back(BedGeneRef{0, M, packed_header(blk), nullptr, nullptr});  // (sinks: the work space's)
+  long long* d_cnt = nullptr;
+  rc = bed_rows_consolidate(c, st, "resident .bed gene (debug)", rows, genes, RVT_MAX_VARIANTS, 1, &d_cnt);
+  if (rc) return rc;
+  HIP_TRY(c, sync_stream(st));  // (run_batch launches on its own streams)
+  std::vector<double> af((size_t)M, 0.01);
+  rvt_gene_result r;
+  GeneDesc g0;
+  int planes = 0;
+  DebugOut dbg;
+  dbg.desc0 = &g0;
+  dbg.planes_used = &planes;
+  const double* p = blk.get();
+  const signed char kind = encode_kind(kKindPacked, true);
+  rc = run_batch(c, 1, &p, &M, af.data(), nullptr, RVT_TEST_SKAT, nullptr, &r, &dbg, nullptr, &kind);
+  if (rc) return rc;
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  if (g0.hc != kPathPacked) return fail(c, RVT_E_STATE, "rvt_debug_suffstat_bed_dev: the batch did not take the packed-row kernel");
+  if (planes_used) *planes_used = planes;
+  return debug_suffstat_collect(c, g0, M, S, T, u, colsum, nullptr, nullptr);
+}
+
 int rvt_submit_gene(rvt_ctx* c, int64_t gene_id, int M, const double* G, const double* af, uint32_t tests,
                     const rvt_params* prm) {
   return submit_common(c, gene_id, M, G, GeneInput::kF64, af, nullptr, tests, prm);

@@ -20,7 +20,7 @@
 //   * G'V[X | res] and the burden sums c'V[X | res | v] go to the int8 matrix cores as well: the null-model tile
 //     [vX_0 .. vX_{d-1} | res | v] is quantised ONCE per null model to six balanced base-128 digit planes per column with a
 //     power-of-two scale per column (42 bits below twice the column's largest entry; rvt_set_null checks that no column's
-//     largest entry exceeds 256 x its root mean square, else the model stays on gene_suffstat_hcw) and stored in operand
+//     largest entry exceeds 4096 x the median of its non-zero magnitudes, else the model stays on gene_suffstat_hcw) and stored in operand
 //     order.  One v_mfma_i32_16x16x64_i8 per plane, row tile and 64 samples replaces SIXTEEN fp64 instructions of 64 cycles
 //     — the fp64 matrix pipe leaves the kernel — and every statistic is an exact integer of the quantised inputs:
 //     bit-reproducible whatever the order of the sums;
@@ -259,8 +259,12 @@ __device__ __forceinline__ void hcx_masked_slice(const hcx_lchar* pkb, const hcx
 #pragma unroll
       for (int c = MT - 1; c >= 0; --c) c0 = word[c] ? c : c0;
       const unsigned long long have = __builtin_amdgcn_ballot_w64(c0 >= 0);
-      if (have == 0ull || E + __builtin_popcountll(have) > kHcxListCap) break;
-      if (c0 >= 0) {
+      // (a turn that does not fit takes the first `room` of its lanes: a turn of more than kHcxListCap lanes — a fifth of the
+      //  calls missing, or 2 % of them in a gene of five tiles — once fitted NO list, and the round ended empty with the slice's
+      //  entries untreated)
+      const int nh = __builtin_popcountll(have), room = kHcxListCap - E, rk = rank_of(have);
+      if (have == 0ull || room == 0) break;
+      if (c0 >= 0 && rk < room) {
         unsigned wsel = 0u;
 #pragma unroll
         for (int c = 0; c < MT; ++c) wsel = (c == c0) ? word[c] : wsel;
@@ -276,12 +280,12 @@ __device__ __forceinline__ void hcx_masked_slice(const hcx_lchar* pkb, const hcx
           const int de = (int)(signed char)((w[0] >> (8 * l0)) & 0xffu), dod = (int)(signed char)((w[1] >> (8 * l0)) & 0xffu);
           V = V * 16384 + (long long)(de * 128 + dod);
         }
-        const int idx = E + rank_of(have);
+        const int idx = E + rk;  // (< kHcxListCap: rk < room)
         list[idx * 3 + 0] = (unsigned)(c0 * 16 + v) | ((unsigned)q << 8) | ((unsigned)b << 12);
         list[idx * 3 + 1] = (unsigned)(unsigned long long)V;
         list[idx * 3 + 2] = (unsigned)((unsigned long long)V >> 32);
       }
-      E += __builtin_popcountll(have);
+      E += nh < room ? nh : room;
     }
     if (E == 0) break;  // (nothing left)
     asm volatile("" ::: "memory");

@@ -1069,6 +1069,24 @@ class Engine:
                                               _dp(mn), _dp(mx)))
         return S, T, u, cs, mn, mx
 
+    def debug_suffstat_bed_dev(self, d_rows, M):
+        """The sufficient statistics of one gene of a resident .bed matrix as the packed-row kernels produced them
+        (rvt_debug_suffstat_bed_dev): (S, T, u, colsum, planes_used) — planes_used = 1 when G'[X | rr] came from the null
+        tile's digit planes (gene_tnull_hcp), 0 when the fp64 product formed it.  Raises RvtError for a gene the resident
+        route expands (a binary trait, more than 13 covariates, M > 96)."""
+        d = self.d
+        M = int(M)
+        S = np.zeros((M, M))
+        T = np.zeros((M, d))
+        u = np.zeros(M)
+        cs = np.zeros(M)
+        used = C.c_int(-1)
+        self.L.rvt_debug_suffstat_bed_dev.restype = C.c_int
+        self.L.rvt_debug_suffstat_bed_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [c_double_p] * 4 + [c_int_p]
+        self._check(self.L.rvt_debug_suffstat_bed_dev(self.ctx, C.c_void_p(int(d_rows)), M, _dp(S), _dp(T), _dp(u), _dp(cs),
+                                                      C.byref(used)))
+        return S, T, u, cs, int(used.value)
+
     def debug_spectrum(self, ptr, M, af, beside=None):
         """The spectrum stage of one block as the per-gene tail kernels left it (rvt_debug_spectrum), under the caller's
         allele frequencies: a dict of the record `rec`, the kept SKAT eigenvalues `lam` (descending) and those of SKAT-O's
