@@ -460,13 +460,38 @@ int rvt_null_summary(rvt_ctx* ctx, double* beta, double* covb_diag, double* sigm
  * pvalue: V x T row-major (GetU / GetV / GetPvalue); pvalue is NaN where vstat == 0 (:461-463).  RVT_E_STATE without a
  * multiple-trait null, or when the context also holds a null model of another sample count.  Synchronous.
  *
- * rvt_mt_clear frees the resident planes (rvt_mt_score_block then answers RVT_E_STATE).
- * rvt_mt_last_timing: host milliseconds the last rvt_mt_score_block spent in {genotype pass, products, finishing} (measurement). */
+ * rvt_mt_clear frees the resident planes (rvt_mt_score_block and rvt_mt_score_bed_dev then answer RVT_E_STATE).
+ * rvt_mt_last_timing: host milliseconds the last rvt_mt_score_block or rvt_mt_score_bed_dev spent in {genotype pass (front
+ * stage), products, finishing} (measurement). */
 int rvt_mt_fit_null(rvt_ctx* ctx, int64_t N, int P, const double* Y, int Q, const double* Z, int T, const int* test_pheno,
                     const int* test_cov_ptr, const int* test_cov, int* ok, double* obs, double* sigma2);
 int rvt_mt_score_block(rvt_ctx* ctx, const double* dG, int V, double* ustat, double* vstat, double* pvalue);
 int rvt_mt_clear(rvt_ctx* ctx);
 int rvt_mt_last_timing(rvt_ctx* ctx, double* ms3);
+/* rvt_mt_score_block for V consecutive rows of a RESIDENT .bed matrix (rvt_bed_alloc / rvt_bed_upload), after rvt_mt_fit_null:
+ * TestCovariateBlock (regression/FastMultipleTraitLinearRegressionScoreTest.cpp:391-470) on the columns a caller would have
+ * uploaded — the calls of the 2-bit codes (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing) with missing imputed to the mean of the
+ * called ones (src/DataConsolidator.cpp:217-245; a row with no called sample: mu = 0) — formed from the codes where they lie;
+ * no variant exists as doubles.  The pitch is ceil(N / 4) bytes, N the multiple-trait null's sample count; a row may start at
+ * any byte, the padding pairs of a row's last byte are ignored whatever they hold, and rows are taken as stored (not flipped),
+ * as rvt_mt_score_block takes its columns.  A context whose only model is the multiple-trait null can allocate and fill the
+ * matrix (rvt_bed_alloc, rvt_bed_upload).  Any V: the rows are walked in pieces of 1024.
+ * The imputed column is exactly g = c + mu m, c = the calls with missing -> 0, m = the missing indicator, mu = (n1 + 2 n2) /
+ * (n0 + n1 + n2) from the row's counts.  Exact: the counts; G'[Yc | Zc] and G'indModel of c and of m, integer products of one
+ * int8 plane each with the resident digit planes (6 x 1 plane pairs for c and, only for the rows of a piece that have a missing
+ * call, 6 x 1 more for m — a mean-imputed fp64 column costs 6 x 6 and makes its whole piece cost that).  Rounded once each, in
+ * fp64: mu; sum (g - mu)^2 = (n1 + 4 n2) - (n1 + 2 n2)^2 / (n0 + n1 + n2); the two fma(mu, .'m, .'c); then the cell arithmetic of
+ * rvt_mt_score_block.  mu enters as the double it is (no fixed point).  A piece without a missing call launches the products
+ * of rvt_mt_score_block's hard-call piece of the same width and returns its bits; the c half of a row never depends on the m half.
+ * ustat, vstat, pvalue: V x T row-major, NaN exactly where rvt_mt_score_block gives NaN for the imputed columns.  counts
+ * (optional, 4 V entries): per row the numbers of 0 / 1 / 2 / missing calls, as rvt_score_bed_dev reports them.
+ * RVT_E_INVALID: a null argument (counts excepted) or V < 1.  RVT_E_STATE: no multiple-trait null, or the context also holds a
+ * null model of another sample count (the rule of rvt_mt_score_block).  A refused call writes nothing.  Synchronous;
+ * rvt_mt_last_timing reports its three phases.
+ * Not covered from resident rows: the rvt_group_* layer (no group form of this call) and the host adapter class
+ * FastMultipleTraitScoreTest, which receives one column per fit() and uploads its blocks as before. */
+int rvt_mt_score_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, double* ustat, double* vstat, double* pvalue,
+                         long long* counts);
 /* MetaScore with kinship (MetaFamQtl, src/Model.h:3398-3499; MetaFamBinary, :3556-3668): FastLMM::TestCovariate in its
  * SCORE branch (regression/FastLMM.cpp:215-247) and FastLMM::FastGetAF (:400-424) of every raw column of a device
  * block, after rvt_set_kinship + rvt_fit_fam_null.
@@ -977,7 +1002,8 @@ int rvt_bed_recode_block(rvt_ctx* ctx, const unsigned char* d_rows, int V, int c
  * argument (counts excepted) or V < 1.  RVT_E_STATE: no family null model, or an ordinary null model is installed whose N differs
  * from the family null model's (the rows would have another pitch).  A refused call writes nothing.  Synchronous.
  * Not covered from resident rows: famGrammarGamma, the family MetaCov calls, FamAnalyticVT, the rvt_group_* layer and the host
- * adapter classes — they take fp64 blocks.  (FamSKAT and the family burden tests: rvt_run_fam_tests_bed_dev below.) */
+ * adapter classes — they take fp64 blocks.  (FamSKAT and the family burden tests: rvt_run_fam_tests_bed_dev below; the
+ * multiple-trait score test: rvt_mt_score_bed_dev above.) */
 int rvt_score_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int binary, int* ok, double* ustat, double* vstat,
                           double* af, double* pvalue, long long* counts);
 int rvt_lrt_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int* ok, double* af, double* null_loglik,

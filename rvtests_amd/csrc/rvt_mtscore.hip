@@ -392,7 +392,7 @@ int rvt_mt_score_block(rvt_ctx* c, const double* dG, int V, double* ustat, doubl
     double t2 = now_s();
     c->mt_ms[1] += 1e3 * (t2 - t1);
     // ---- u, v, p of every cell -------------------------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(mt_finish_kernel, dim3((unsigned)((T + kMtFinTests - 1) / kMtFinTests), (unsigned)((nv + kMtFinVars - 1) / kMtFinVars)),
+    hipLaunchKernelGGL((mt_finish_kernel<false>), dim3((unsigned)((T + kMtFinTests - 1) / kMtFinTests), (unsigned)((nv + kMtFinVars - 1) / kMtFinVars)),
                        dim3(256), 0, st, d_c1, (long long)R, d_c2, (long long)K, c->d_mt_rowsum.get(), d_gsum, d_gg,
                        reinterpret_cast<const MtTest*>(c->d_mt_tests.get()), T, nv, (double)N, d_u, d_v, d_p);
     HIP_TRY(c, hipGetLastError());
@@ -406,8 +406,123 @@ int rvt_mt_score_block(rvt_ctx* c, const double* dG, int V, double* ustat, doubl
   return RVT_OK;
 }
 
-// Measurement (tools/bench_mtscore.py): host milliseconds the last rvt_mt_score_block spent in its three phases — the genotype
-// pass, the two products, the finishing kernel with its copies (every phase ends with a wait for the stream).
+// TestCovariateBlock (:391-470) of V consecutive rows of a resident .bed matrix: rvt_mt_score_block's loop with the front stage
+// over the 2-bit codes in place of the pass over fp64 columns (mtscore_kernels.hip.h, second half).  The imputed column is
+// g = c + mu m, so a piece costs the block route's hard-call products of c — launched in that route's shape: one plane, the
+// piece's own width — and, for the rows that have a missing call, the same two products of the compact m.
+int rvt_mt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, double* ustat, double* vstat, double* pvalue,
+                         long long* counts) {
+  if (!c || !d_rows || V < 1 || !ustat || !vstat || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
+  if (!c->have_mt) return fail(c, RVT_E_STATE, "no multiple-trait null model (rvt_mt_fit_null)");
+  const int64_t N = c->mt_N, pitch = (N + 3) / 4;
+  if ((c->have_null && c->nc.N != N) || (!c->have_null && c->have_fam && c->fam_nc.N != N))
+    return fail(c, RVT_E_STATE, "the multiple-trait null and the context's null model differ in N");
+  hipSetDevice(c->device);
+  int rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const int64_t ldk = c->mt_ldk;
+  const int R = c->mt_R, K = c->mt_K, T = c->mt_T;
+  const int Vp = kMtPiece;
+  Layout L;
+  const size_t o_cnt = L.take(sizeof(unsigned long long) * 4 * (size_t)Vp), o_mu = L.take(sizeof(double) * (size_t)Vp),
+               o_gg = L.take(sizeof(double) * (size_t)Vp), o_slot = L.take(sizeof(int) * (size_t)Vp),
+               o_idx = L.take(sizeof(int) * (size_t)Vp), o_c1 = L.take(sizeof(double) * (size_t)R * (size_t)Vp),
+               o_c2 = L.take(sizeof(double) * (size_t)K * (size_t)Vp), o_c1m = L.take(sizeof(double) * (size_t)R * (size_t)Vp),
+               o_c2m = L.take(sizeof(double) * (size_t)K * (size_t)Vp), o_u = L.take(sizeof(double) * (size_t)Vp * (size_t)T),
+               o_v = L.take(sizeof(double) * (size_t)Vp * (size_t)T), o_p = L.take(sizeof(double) * (size_t)Vp * (size_t)T);
+  // B = [c | m]: a piece of c columns, behind them as many m columns as a piece can have
+  const size_t b_half = (size_t)kMtPiece * (size_t)ldk;
+  HIP_TRY(c, c->d_mt_ws.grow(L.total, L.total, st, true));
+  HIP_TRY(c, c->d_mt_B.grow(2 * b_half, 2 * b_half, st, true));
+  char* ws = c->d_mt_ws;
+  unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(ws + o_cnt);
+  double* d_mu = reinterpret_cast<double*>(ws + o_mu);
+  double* d_gg = reinterpret_cast<double*>(ws + o_gg);
+  int* d_slot = reinterpret_cast<int*>(ws + o_slot);
+  int* d_idx = reinterpret_cast<int*>(ws + o_idx);
+  double* d_c1 = reinterpret_cast<double*>(ws + o_c1);
+  double* d_c2 = reinterpret_cast<double*>(ws + o_c2);
+  double* d_c1m = reinterpret_cast<double*>(ws + o_c1m);
+  double* d_c2m = reinterpret_cast<double*>(ws + o_c2m);
+  double* d_u = reinterpret_cast<double*>(ws + o_u);
+  double* d_v = reinterpret_cast<double*>(ws + o_v);
+  double* d_p = reinterpret_cast<double*>(ws + o_p);
+  signed char* Bc = c->d_mt_B;
+  signed char* Bm = c->d_mt_B + b_half;
+  const std::vector<int> zero_exp((size_t)std::max(K, Vp), 0);
+  std::vector<unsigned long long> cnt(4 * (size_t)Vp);
+  std::vector<int> slot((size_t)Vp), idx((size_t)Vp);
+  c->mt_ms[0] = c->mt_ms[1] = c->mt_ms[2] = 0.0;
+  for (int64_t v0 = 0; v0 < V; v0 += kMtPiece) {
+    const int nv = (int)std::min<int64_t>(kMtPiece, V - v0);
+    const int64_t nvpad = ((int64_t)nv + kRotBN - 1) / kRotBN * kRotBN;
+    const unsigned char* rows = d_rows + (size_t)v0 * (size_t)pitch;
+    // ---- front stage: the counts of every row, its moments, the list of the rows with a missing call, c and the compact m --------
+    double t0 = now_s();
+    HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * (size_t)nv, st));
+    bed_row_counts(st, rows, pitch, N, nv, d_cnt);
+    hipLaunchKernelGGL(mt_bed_site_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, d_cnt, nv, d_mu, d_gg);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * 4 * (size_t)nv, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    int nm = 0;  // rows of the piece with a missing call
+    for (int h = 0; h < nv; ++h) {
+      const bool miss = cnt[4 * (size_t)h + 3] != 0;
+      slot[(size_t)h] = miss ? nm : -1;
+      if (miss) idx[(size_t)nm++] = h;
+    }
+    if (counts)
+      for (size_t i = 0; i < 4 * (size_t)nv; ++i) counts[4 * (size_t)v0 + i] = (long long)cnt[i];
+    const int64_t nmpad = ((int64_t)nm + kRotBN - 1) / kRotBN * kRotBN;
+    HIP_TRY(c, hipMemcpyAsync(d_slot, slot.data(), sizeof(int) * (size_t)nv, hipMemcpyHostToDevice, st));
+    if (nm > 0) HIP_TRY(c, hipMemcpyAsync(d_idx, idx.data(), sizeof(int) * (size_t)nm, hipMemcpyHostToDevice, st));
+    if (nvpad > nv)  // the products read whole column tiles: the kernel writes nv (nm) columns of ldk bytes
+      HIP_TRY(c, hipMemsetAsync(Bc + (size_t)nv * (size_t)ldk, 0, (size_t)(nvpad - nv) * (size_t)ldk, st));
+    if (nmpad > nm) HIP_TRY(c, hipMemsetAsync(Bm + (size_t)nm * (size_t)ldk, 0, (size_t)(nmpad - nm) * (size_t)ldk, st));
+    hipLaunchKernelGGL(mt_bed_unpack_kernel, dim3((unsigned)nv, (unsigned)((ldk + kMtPassRows - 1) / kMtPassRows)), dim3(256), 0, st,
+                       rows, (long long)pitch, (long long)N, (long long)nv * (long long)pitch, d_slot, Bc, Bm, (long long)ldk);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, sync_stream(st));  // (slot and idx are refilled for the next piece)
+    double t1 = now_s();
+    c->mt_ms[0] += 1e3 * (t1 - t0);
+    // ---- [Yc | Zc]'c and indModel'c as a hard-call piece of rvt_mt_score_block, then the same of m and C = Cc + mu Cm ---------------
+    rc = rvt_planes_gemm(c, c->d_mt_planes, c->mt_plane, kMtPlanes, R, c->mt_row_exp.data(), 0, Bc, 0, 1, nv, zero_exp.data(), N, ldk,
+                         d_c1, R, st);
+    if (rc) return rc;
+    rc = rvt_planes_gemm(c, c->d_mt_pat, 0, 1, K, zero_exp.data(), 0, Bc, 0, 1, nv, zero_exp.data(), N, ldk, d_c2, K, st);
+    if (rc) return rc;
+    if (nm > 0) {
+      rc = rvt_planes_gemm(c, c->d_mt_planes, c->mt_plane, kMtPlanes, R, c->mt_row_exp.data(), 0, Bm, 0, 1, nm, zero_exp.data(), N, ldk,
+                           d_c1m, R, st);
+      if (rc) return rc;
+      rc = rvt_planes_gemm(c, c->d_mt_pat, 0, 1, K, zero_exp.data(), 0, Bm, 0, 1, nm, zero_exp.data(), N, ldk, d_c2m, K, st);
+      if (rc) return rc;
+      hipLaunchKernelGGL(mt_bed_combine_kernel, dim3((unsigned)((R + K + 255) / 256), (unsigned)nm), dim3(256), 0, st, d_c1, d_c1m,
+                         (long long)R, R, d_c2, d_c2m, (long long)K, K, d_idx, d_mu);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, sync_stream(st));
+    }
+    double t2 = now_s();
+    c->mt_ms[1] += 1e3 * (t2 - t1);
+    // ---- u, v, p of every cell (gbar = mu) --------------------------------------------------------------------------------------------
+    hipLaunchKernelGGL((mt_finish_kernel<true>), dim3((unsigned)((T + kMtFinTests - 1) / kMtFinTests), (unsigned)((nv + kMtFinVars - 1) / kMtFinVars)),
+                       dim3(256), 0, st, d_c1, (long long)R, d_c2, (long long)K, c->d_mt_rowsum.get(), d_mu, d_gg,
+                       reinterpret_cast<const MtTest*>(c->d_mt_tests.get()), T, nv, (double)N, d_u, d_v, d_p);
+    HIP_TRY(c, hipGetLastError());
+    const size_t cells = (size_t)nv * (size_t)T, off = (size_t)v0 * (size_t)T;
+    HIP_TRY(c, hipMemcpyAsync(ustat + off, d_u, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(vstat + off, d_v, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(pvalue + off, d_p, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    c->mt_ms[2] += 1e3 * (now_s() - t2);
+  }
+  return RVT_OK;
+}
+
+// Measurement (tools/bench_mtscore.py, tools/bench_mtscore_bed.py): host milliseconds the last rvt_mt_score_block or
+// rvt_mt_score_bed_dev spent in its three phases — the genotype pass (front stage), the products (with the combine), the
+// finishing kernel with its copies (every phase ends with a wait for the stream).
 int rvt_mt_last_timing(rvt_ctx* c, double* ms3) {
   if (!c || !ms3) return RVT_E_INVALID;
   for (int k = 0; k < 3; ++k) ms3[k] = c->mt_ms[k];

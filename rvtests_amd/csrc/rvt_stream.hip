@@ -1352,9 +1352,10 @@ int rvt_submit_gene_bed(rvt_ctx* c, int64_t gene_id, int M, const unsigned char*
 // rvt_submit_gene_bed_dev then names a gene by the device address of its first row.
 int rvt_bed_alloc(rvt_ctx* c, int64_t n_variants, unsigned char** d_bed) {
   if (!c || !d_bed || n_variants < 1) return fail(c, RVT_E_INVALID, "bad .bed allocation");
-  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  // (a context whose only model is the multiple-trait one, rvt_mt_fit_null: its N gives the pitch, for rvt_mt_score_bed_dev)
+  if (!c->have_null && !c->have_mt) return fail(c, RVT_E_STATE, "no null model set");
   hipSetDevice(c->device);
-  const size_t cb = (size_t)((c->nc.N + 3) / 4);
+  const size_t cb = (size_t)(((c->have_null ? c->nc.N : c->mt_N) + 3) / 4);
   *d_bed = nullptr;
   if (hipMalloc((void**)d_bed, cb * (size_t)n_variants + 16) != hipSuccess) {
     (void)hipGetLastError();
@@ -1364,10 +1365,10 @@ int rvt_bed_alloc(rvt_ctx* c, int64_t n_variants, unsigned char** d_bed) {
 }
 int rvt_bed_upload(rvt_ctx* c, unsigned char* d_bed, int64_t first_variant, int64_t n_variants, const unsigned char* rows) {
   if (!c || !d_bed || !rows || first_variant < 0 || n_variants < 0) return fail(c, RVT_E_INVALID, "bad .bed upload");
-  if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+  if (!c->have_null && !c->have_mt) return fail(c, RVT_E_STATE, "no null model set");
   if (n_variants == 0) return RVT_OK;
   hipSetDevice(c->device);
-  const size_t cb = (size_t)((c->nc.N + 3) / 4);
+  const size_t cb = (size_t)(((c->have_null ? c->nc.N : c->mt_N) + 3) / 4);
   int rc = staged_h2d(c, d_bed + cb * (size_t)first_variant, rows, cb * (size_t)n_variants);
   if (rc) return rc;
   HIP_TRY(c, sync_stream(c->h2d_stream));  // (the caller may reuse `rows`; genes submitted next read the device copy)

@@ -265,6 +265,8 @@ def load_library():
                                   c_double_p, c_double_p]
     L.rvt_mt_score_block.restype = C.c_int
     L.rvt_mt_score_block.argtypes = [vp, vp, C.c_int] + [c_double_p] * 3
+    L.rvt_mt_score_bed_dev.restype = C.c_int
+    L.rvt_mt_score_bed_dev.argtypes = [vp, vp, C.c_int64] + [c_double_p] * 3 + [vp]
     L.rvt_mt_clear.restype = C.c_int
     L.rvt_mt_clear.argtypes = [vp]
     L.rvt_mt_last_timing.restype = C.c_int
@@ -1289,11 +1291,22 @@ class Engine:
         self._check(self.L.rvt_mt_score_block(self.ctx, C.c_void_p(int(ptr)), V, *[_dp(a) for a in arr]))
         return dict(U=arr[0], V=arr[1], p=arr[2])
 
+    def mt_score_bed_dev(self, d_rows, V, want_counts=True):
+        """mt_score_block's dict for V consecutive rows of a resident .bed matrix (rvt_mt_score_bed_dev: missing calls imputed
+        to the row's mean, formed from the 2-bit codes), plus counts (V, 4): n0 n1 n2 missing (None without want_counts).
+        After mt_fit_null; bed_alloc / bed_upload work on a context whose only model is the multiple-trait null."""
+        V, T = int(V), int(getattr(self, "_mt_T", 0) or 1)
+        arr = [np.zeros((max(V, 0), T)) for _ in range(3)]
+        cnt = np.zeros((max(V, 0), 4), dtype=np.int64) if want_counts else None
+        self._check(self.L.rvt_mt_score_bed_dev(self.ctx, C.c_void_p(int(d_rows)), V, *[_dp(a) for a in arr],
+                                                cnt.ctypes.data_as(C.c_void_p) if want_counts else None))
+        return dict(U=arr[0], V=arr[1], p=arr[2], counts=cnt)
+
     def mt_clear(self):
         self._check(self.L.rvt_mt_clear(self.ctx))
 
     def mt_last_timing(self):
-        """Host milliseconds of the last mt_score_block: genotype pass, products, finishing."""
+        """Host milliseconds of the last mt_score_block / mt_score_bed_dev: genotype pass (front stage), products, finishing."""
         ms = np.zeros(3)
         self._check(self.L.rvt_mt_last_timing(self.ctx, _dp(ms)))
         return ms
