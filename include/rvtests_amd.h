@@ -1001,13 +1001,36 @@ int rvt_bed_recode_block(rvt_ctx* ctx, const unsigned char* d_rows, int V, int c
  * 4 V entries): per row the numbers of 0 / 1 / 2 / missing calls, as rvt_score_bed_dev reports them.  RVT_E_INVALID: a null
  * argument (counts excepted) or V < 1.  RVT_E_STATE: no family null model, or an ordinary null model is installed whose N differs
  * from the family null model's (the rows would have another pitch).  A refused call writes nothing.  Synchronous.
- * Not covered from resident rows: famGrammarGamma, the family MetaCov calls, FamAnalyticVT, the rvt_group_* layer and the host
- * adapter classes — they take fp64 blocks.  (FamSKAT and the family burden tests: rvt_run_fam_tests_bed_dev below; the
- * multiple-trait score test: rvt_mt_score_bed_dev above.) */
+ * Not covered from resident rows: the family MetaCov calls, FamAnalyticVT, the rvt_group_* layer and the host
+ * adapter classes — they take fp64 blocks.  (FamSKAT and the family burden tests: rvt_run_fam_tests_bed_dev below;
+ * famGrammarGamma: rvt_grammar_bed_dev below; the multiple-trait score test: rvt_mt_score_bed_dev above.) */
 int rvt_score_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int binary, int* ok, double* ustat, double* vstat,
                           double* af, double* pvalue, long long* counts);
 int rvt_lrt_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int* ok, double* af, double* null_loglik,
                         double* alt_loglik, double* pvalue, long long* counts);
+/* famGrammarGamma from rows of a resident .bed matrix: rvt_grammar_block's five columns (SingleVariantFamilyGrammarGamma,
+ * src/Model.h:714-805; GrammarGamma::TestCovariate, regression/GrammarGamma.cpp:122-152) for V consecutive rows starting at the
+ * device address d_rows, after rvt_fit_grammar_null.  The pitch is ceil(N / 4) bytes, N the GrammarGamma null model's sample
+ * count; a row may start at any byte, the rows are taken as stored (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing), the padding pairs
+ * of a row's last byte are ignored and missing calls are imputed to the mean of the row's called samples
+ * (src/DataConsolidator.cpp:217-245): the results are those of rvt_grammar_block on the column a caller would have uploaded.
+ * No byte at or behind d_rows + V ceil(N / 4) is read.  With g = c + mu m (c the calls, m the missing indicator, mu = ac / called)
+ * the centred g'ty and g'g need only the four counts of a row and the sums of ty over three bit planes of its codes; ty is held
+ * as eight int8 digit planes (56 bits below its largest entry) and the sums are exact integer products on the int8 matrix
+ * cores, N / 4 bytes read per row.  Exact: the counts and the integer sums — a row's results do not depend on V, on where the
+ * row stands in the call or on how the work is split.  Rounded: the digits of ty (2^-56 of its largest entry per sample) and
+ * four roundings in the finish (rvt_grammar_bed.h states the bound).
+ * ok[h] = 0 with NaN beta / beta_var / pvalue when fewer than two of n0, n1, n2 are non-zero (the imputed column is constant).
+ * af_kinship = 0: af[h] = ac / (2 called), 0 without a called sample; this form needs NO rvt_fit_fam_null.  af_kinship != 0:
+ * GetAF's AF_KINSHIP form (:199-213) over U'g of the front stage of rvt_score_bed_dev_fam — it needs a family null model on the
+ * same samples and runs at the rotation's rate; every other output is the same.  counts (optional, 4 V entries): per row the
+ * numbers of 0 / 1 / 2 / missing calls.  RVT_E_INVALID: a null argument (counts excepted) or V < 1.  RVT_E_STATE: no
+ * rvt_fit_grammar_null, an ordinary null model is installed whose N differs from the GrammarGamma null model's (the rows would
+ * have another pitch), af_kinship != 0 without a family null model on the same samples, or ty is not finite.  A refused call
+ * writes nothing.  Synchronous.  RVT_GG_BED_SLICE / RVT_GG_BED_TILES (samples per slice, row tiles per workgroup; experiments
+ * and tests) replace the launch plan's choices, read at every call. */
+int rvt_grammar_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, int af_kinship, int* ok, double* af,
+                        double* beta, double* beta_var, double* pvalue, long long* counts);
 /* The gene-based tests for related samples from rows of a resident .bed matrix: rvt_run_fam_tests (FamSkatTest,
  * src/Model.h:3048-3145; FamCMC, src/Model.h:2261-2376; FamZeggini, src/Model.h:2378-2492; the burden tests' collapse and
  * FastLMM::TestCovariate's SCORE branch, regression/FastLMM.cpp:215-247, and FastLMM::GetAF, :356-398) with gene g given as M[g]
@@ -1230,6 +1253,16 @@ int rvt_debug_rotate_bed_timed(rvt_ctx* ctx, const unsigned char* d_rows, int nc
  * flags to the host and the host's pass over them). */
 int rvt_debug_fam_genes_bed_front_timed(rvt_ctx* ctx, int n_genes, const unsigned char* const* d_rows, const int* M, uint32_t tests,
                                         rvt_gene_result* out, double* ms);
+/* What rvt_grammar_bed_dev multiplies with and what its product returns (test hook), after rvt_fit_grammar_null: planes (8 N
+ * int8, plane p at planes + p N, may be null) are the base-128 digits of q_i = rint(ty_i 2^(55 - *exp2)), the top digit signed
+ * and the others 0 .. 127, totals (8) their sums over the samples; sums (V x 3 x 9 int64, may be null, then d_rows and V are
+ * not used): per row the exact sums of the bit planes H (hi bits), L (lo bits) and HL (hi & lo) of its codes against the eight
+ * planes and against a column of ones.  The refusals of rvt_grammar_bed_dev with af_kinship = 0. */
+int rvt_debug_grammar_bed(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, signed char* planes, int* exp2, long long* totals,
+                          long long* sums);
+/* Measurement (tools/bench_grammar_bed.py): the product kernel of rvt_grammar_bed_dev over the V rows alone; *ms = the device
+ * milliseconds between HIP events recorded directly around it. */
+int rvt_debug_grammar_bed_timed(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, double* ms);
 int rvt_set_profiling(rvt_ctx* ctx, int on);
 int rvt_get_timing(rvt_ctx* ctx, rvt_timing* t, int reset);
 /* the HIP stream (hipStream_t) the engine launches on, for callers that record their own events */

@@ -18,6 +18,7 @@
 #include "rvt_pvalue.h"
 #include "rvt_mvn.h"
 #include "rvt_mtscore.h"
+#include "rvt_grammar_bed.h"
 
 using namespace rvt;
 
@@ -491,6 +492,27 @@ long long hc_pool_lease(void* p, size_t need, int bounded, long long fresh_id, i
   size_t b = 0;
   if (keep) (void)l.release(&b);
   return id;
+}
+
+// ---- rvt_grammar_bed.h: famGrammarGamma from resident .bed rows ---------------------------------------------------------------
+// the digit planes of ty (planes[p * N + i]), their exponent and totals; 0 when ty is not finite
+int hc_grammar_ty_planes(const double* ty, long long N, signed char* planes, int* exp2, long long* totals) {
+  return grammar_ty_planes(ty, N, planes, N, exp2, totals);
+}
+// one row's finish from its counts and the 3 x 8 plane sums (H, L, HL); out4 = af, beta, beta_var, p; returns ok
+int hc_grammar_bed_finish(long long n0, long long n1, long long n2, long long nm, const long long* S, const long long* T, int e,
+                          double gamma, double ysy, double* out4) {
+  int64_t s[3 * kGgPlanes];
+  for (int k = 0; k < 3 * kGgPlanes; ++k) s[k] = S[k];
+  int ok = -1;
+  grammar_bed_finish(n0, n1, n2, nm, s, T, e, gamma, ysy, &ok, out4, out4 + 1, out4 + 2, out4 + 3);
+  return ok;
+}
+// the launch plan; out6 = padded N, slice, slices, row tiles, tiles per workgroup, workgroups along the rows; returns the K-step
+int hc_grammar_bed_plan(long long N, long long V, int cus, long long slice_req, int tiles_req, long long* out6) {
+  const GgBedPlan P = grammar_bed_plan(N, V, cus, slice_req, tiles_req);
+  out6[0] = P.npad, out6[1] = P.slice, out6[2] = P.slices, out6[3] = P.row_tiles, out6[4] = P.tiles, out6[5] = P.groups;
+  return kGgKstep;
 }
 
 int hc_cpu_has(int isa) {

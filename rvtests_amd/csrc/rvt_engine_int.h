@@ -552,6 +552,14 @@ struct rvt_ctx {
   int64_t gg_N = 0;
   int gg_d = 0;
   double gg_delta = 0.0, gg_gamma = 0.0, gg_ysy = 0.0, gg_sumty = 0.0, gg_afden = 0.0;
+  // famGrammarGamma from resident .bed rows (rvt_grammar_bed_dev): the int8 digit planes of ty with their exponent and totals,
+  // formed at the first call after a fit (gg_gen counts rvt_fit_grammar_null, as fam_gen / lrt_gen), and the call's work space
+  uint64_t gg_gen = 0;
+  DevBuf<char> d_gg_planes;
+  uint64_t gg_planes_gen = 0;  // gg_gen the planes were formed for (0: none)
+  int gg_exp = 0;
+  long long gg_totals[8] = {};
+  DevBuf<char> d_gg_bed_ws;
   // the multiple-trait score test (rvt_mtscore.hip): the centred [Yc | Zc] as kMtPlanes digit planes [plane][row][mt_ldk] (the A
   // operand of rot_gemm.hip.h, mt_plane bytes apart, per-row exponents mt_row_exp), the distinct indModel patterns as one 0 / 1
   // plane, the row sums of the stored values, the MtTest constants of the mt_T tests — resident from rvt_mt_fit_null to

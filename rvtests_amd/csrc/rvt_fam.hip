@@ -8,6 +8,7 @@
 #include "rvt_engine_int.h"
 #include "fam_single.hip.h"
 #include "fam_bed_kernels.hip.h"
+#include "grammar_bed_kernels.hip.h"
 
 static void free_csc(rvt_ctx* c) {  // the column-compressed form of U
   c->d_csc_ptr.reset();
@@ -2251,6 +2252,7 @@ int rvt_fit_grammar_null(rvt_ctx* c, int64_t N, int d, const double* X, const do
   c->gg_sumty = sumty;
   c->gg_afden = afden;
   c->have_grammar = true;
+  ++c->gg_gen;  // (rvt_grammar_bed_dev forms the digit planes of ty once per fit)
   out->delta = delta;
   out->sigma2_g = sigma2_g;
   out->gamma = gamma;
@@ -2314,6 +2316,241 @@ int rvt_grammar_block(rvt_ctx* c, const double* dG, int V, int af_kinship, int* 
     HIP_TRY(c, sync_stream(st));
   }
   return RVT_OK;
+}
+
+// ---- famGrammarGamma over rows of a resident .bed matrix (grammar_bed_kernels.hip.h, rvt_grammar_bed.h) ---------------------------
+namespace {
+constexpr int kGgBedPiece = 8192;  // rows of one launch of the product; af=kinship walks the front stage's RVT_MAX_VARIANTS
+
+// what a call may be refused for, before anything is written
+int gg_bed_check(rvt_ctx* c, int af_kinship, const char* who) {
+  if (!c->have_grammar) return fail(c, RVT_E_STATE, "%s: rvt_set_kinship + rvt_fit_grammar_null first", who);
+  if (c->have_null && c->nc.N != c->gg_N)
+    return fail(c, RVT_E_STATE, "%s: the null model has N = %lld, the GrammarGamma null model N = %lld (the resident rows have the former's pitch)",
+                who, (long long)c->nc.N, (long long)c->gg_N);
+  if (af_kinship && (!c->have_fam || c->fam_nc.N != c->gg_N))
+    return fail(c, RVT_E_STATE, "%s: af=kinship needs rvt_fit_fam_null on the same samples (the rotation takes its layout)", who);
+  if (c->gg_N > kGgMaxN) return fail(c, RVT_E_TOO_LARGE, "%s: N = %lld (at most %lld)", who, (long long)c->gg_N, (long long)kGgMaxN);
+  return RVT_OK;
+}
+
+// The digit planes of ty, formed once per rvt_fit_grammar_null (gg_planes_gen) in a buffer of their own; a new block has lost
+// them, and so has one that RVT_SCRIBBLE refills.  ty not finite: RVT_E_STATE.
+int gg_bed_planes(rvt_ctx* c, hipStream_t st, const signed char** planes, int64_t* ldp_out) {
+  const int64_t N = c->gg_N, ldp = (N + kGgKstep - 1) / kGgKstep * kGgKstep;
+  Layout L;
+  const size_t o_pl = L.take((size_t)kGgPlanes * (size_t)ldp), o_e = L.take(sizeof(int) * 2),
+               o_t = L.take(sizeof(long long) * kGgPlanes);
+  if (c->d_gg_planes.cap < L.total || getenv("RVT_SCRIBBLE")) c->gg_planes_gen = 0;
+  HIP_TRY(c, c->d_gg_planes.grow(L.total, L.total, st, true));
+  char* ws = c->d_gg_planes;
+  if (c->gg_planes_gen != c->gg_gen) {
+    const GgLayout G = gg_layout(rvt_padded_ld(N), N, c->gg_d);
+    const double* d_ty = reinterpret_cast<const double*>(c->d_gg_ws.get() + G.o_ty);
+    hipLaunchKernelGGL(grammar_ty_planes_kernel, dim3(1), dim3(1024), 0, st, d_ty, (long long)N,
+                       reinterpret_cast<signed char*>(ws + o_pl), (long long)ldp, reinterpret_cast<int*>(ws + o_e),
+                       reinterpret_cast<long long*>(ws + o_t));
+    HIP_TRY(c, hipGetLastError());
+    int eo[2] = {0, 0};
+    long long tot[kGgPlanes] = {};
+    HIP_TRY(c, hipMemcpyAsync(eo, ws + o_e, sizeof(eo), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    if (!eo[1]) return fail(c, RVT_E_STATE, "the GrammarGamma null model's ty is not finite");
+    HIP_TRY(c, hipMemcpyAsync(tot, ws + o_t, sizeof(tot), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+    c->gg_exp = eo[0];
+    for (int p = 0; p < kGgPlanes; ++p) c->gg_totals[p] = tot[p];
+    c->gg_planes_gen = c->gg_gen;
+  }
+  *planes = reinterpret_cast<const signed char*>(ws + o_pl);
+  *ldp_out = ldp;
+  return RVT_OK;
+}
+
+GgBedPlan gg_bed_plan_of(rvt_ctx* c, int n) {  // (the overrides are read at every call: the tests change them)
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) cus = 0;
+  const char* es = getenv("RVT_GG_BED_SLICE");
+  const char* et = getenv("RVT_GG_BED_TILES");
+  return grammar_bed_plan(c->gg_N, n, cus, es ? atoll(es) : 0, et ? atoi(et) : 0);
+}
+
+struct GgBedOut {  // host arrays of a call (any may be null), V entries each (counts 4 V, sums 27 V)
+  int* ok = nullptr;
+  double *af = nullptr, *beta = nullptr, *beta_var = nullptr, *pvalue = nullptr;
+  long long *counts = nullptr, *sums = nullptr;
+  double* product_ms = nullptr;  // the product kernels alone between two events; nothing else runs
+};
+
+// The call proper, the state checked: pieces of rows through the product, the finish and, with af=kinship, the front stage.
+int gg_bed_run(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int64_t V, int af_kinship, const GgBedOut& out) {
+  const int64_t N = c->gg_N;
+  const size_t cb = (size_t)((N + 3) / 4);
+  const signed char* planes = nullptr;
+  int64_t ldp = 0;
+  int rc = gg_bed_planes(c, st, &planes, &ldp);
+  if (rc) return rc;
+  const int piece = af_kinship ? RVT_MAX_VARIANTS : kGgBedPiece;
+  const int nmax = (int)std::min<int64_t>(piece, V), nlast = (int)(V % piece);
+  size_t part_ints = 0;
+  for (int n : {nmax, nlast}) {
+    if (n < 1) continue;
+    const GgBedPlan P = gg_bed_plan_of(c, n);
+    if (P.slices > 65535) return fail(c, RVT_E_INVALID, "RVT_GG_BED_SLICE: %d slices (at most 65535)", P.slices);
+    part_ints = std::max(part_ints, (size_t)P.slices * (size_t)n * kGgPart);
+  }
+  // the work space, sized once per call in front of its first write
+  Layout L;
+  const size_t o_part = L.take(sizeof(int) * part_ints), o_ok = L.take(sizeof(int) * nmax), o_af = L.take(sizeof(double) * nmax),
+               o_b = L.take(sizeof(double) * nmax), o_bv = L.take(sizeof(double) * nmax), o_pv = L.take(sizeof(double) * nmax),
+               o_cnt = L.take(sizeof(long long) * 4 * nmax), o_sums = L.take(out.sums ? sizeof(long long) * kGgPart * nmax : 0);
+  HIP_TRY(c, c->d_gg_bed_ws.grow(L.total, L.total, st, true));
+  char* ws = c->d_gg_bed_ws;
+  int* d_part = reinterpret_cast<int*>(ws + o_part);
+  int* d_ok = reinterpret_cast<int*>(ws + o_ok);
+  double* d_af = reinterpret_cast<double*>(ws + o_af);
+  double* d_b = reinterpret_cast<double*>(ws + o_b);
+  double* d_bv = reinterpret_cast<double*>(ws + o_bv);
+  double* d_pv = reinterpret_cast<double*>(ws + o_pv);
+  long long* d_cnt = reinterpret_cast<long long*>(ws + o_cnt);
+  long long* d_sums = out.sums ? reinterpret_cast<long long*>(ws + o_sums) : nullptr;
+  FamBedPiece fp;
+  const double* d_wu1 = nullptr;
+  if (af_kinship) {
+    rc = fam_bed_ws(c, st, &fp);
+    if (rc) return rc;
+    const GgLayout G = gg_layout(rvt_padded_ld(N), N, c->gg_d);
+    d_wu1 = reinterpret_cast<const double*>(c->d_gg_ws.get() + G.o_wu1);
+  }
+  GgBedConsts k;
+  k.gamma = c->gg_gamma;
+  k.ysy = c->gg_ysy;
+  k.e = c->gg_exp;
+  for (int p = 0; p < kGgPlanes; ++p) k.T[p] = c->gg_totals[p];
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (out.product_ms) {
+    HIP_TRY(c, hipEventCreate(&ev[0]));
+    hipError_t e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    if (e != hipSuccess) {
+      hipEventDestroy(ev[0]);
+      if (ev[1]) hipEventDestroy(ev[1]);
+      HIP_TRY(c, e);
+    }
+  }
+  hipError_t herr = hipSuccess;
+  std::vector<char> stage;
+  for (int64_t v0 = 0; v0 < V && !rc && herr == hipSuccess; v0 += piece) {
+    const int n = (int)std::min<int64_t>(piece, V - v0);
+    const unsigned char* rows = d_rows + cb * (size_t)v0;
+    const GgBedPlan P = gg_bed_plan_of(c, n);
+    hipLaunchKernelGGL(grammar_bed_kernel, dim3((unsigned)P.groups, (unsigned)P.slices), dim3(kGgThreads),
+                       (size_t)kGgCols * (size_t)P.slice, st, rows, (long long)cb, (long long)N, n, (long long)(cb * (size_t)n),
+                       planes, (long long)ldp, P.npad, P.slice, P.tiles, d_part);
+    herr = hipGetLastError();
+    if (out.product_ms || herr != hipSuccess) continue;
+    hipLaunchKernelGGL(grammar_bed_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_part, P.slices, n,
+                       (long long)N, k, d_ok, d_af, d_b, d_bv, d_pv, d_cnt, d_sums);
+    herr = hipGetLastError();
+    if (herr != hipSuccess) break;
+    if (af_kinship) {  // U'g of the piece by the installed form of U, then GetAF's AF_KINSHIP form over it
+      rc = fam_bed_front(c, st, rows, n, fp, nullptr);
+      if (rc) break;
+      hipLaunchKernelGGL(grammar_af_kin_kernel, dim3((unsigned)n), dim3(256), 0, st, c->d_Gt.get(), (long long)c->fam_nc.ld,
+                         (long long)N, d_wu1, c->gg_afden, d_af);
+      herr = hipGetLastError();
+      if (herr != hipSuccess) break;
+    }
+    // one copy of the piece's outputs (they lie behind one another in the work space), handed out on the host
+    const size_t o_end = out.sums ? o_sums + sizeof(long long) * kGgPart * n : out.counts ? o_cnt + sizeof(long long) * 4 * n
+                                                                                          : o_pv + sizeof(double) * n;
+    stage.resize(o_end - o_ok);
+    herr = hipMemcpyAsync(stage.data(), ws + o_ok, stage.size(), hipMemcpyDeviceToHost, st);
+    if (herr == hipSuccess) herr = sync_stream(st);  // (the next piece writes the same work space)
+    if (herr != hipSuccess) break;
+    auto back = [&](void* dst, size_t off, size_t bytes) {
+      if (dst) std::memcpy(dst, stage.data() + (off - o_ok), bytes);
+    };
+    back(out.ok ? out.ok + v0 : nullptr, o_ok, sizeof(int) * n);
+    back(out.af ? out.af + v0 : nullptr, o_af, sizeof(double) * n);
+    back(out.beta ? out.beta + v0 : nullptr, o_b, sizeof(double) * n);
+    back(out.beta_var ? out.beta_var + v0 : nullptr, o_bv, sizeof(double) * n);
+    back(out.pvalue ? out.pvalue + v0 : nullptr, o_pv, sizeof(double) * n);
+    back(out.counts ? out.counts + 4 * v0 : nullptr, o_cnt, sizeof(long long) * 4 * n);
+    back(out.sums ? out.sums + (int64_t)kGgPart * v0 : nullptr, o_sums, sizeof(long long) * kGgPart * n);
+  }
+  if (out.product_ms) {
+    float t = 0.0f;
+    if (!rc && herr == hipSuccess) herr = hipEventRecord(ev[1], st);
+    if (!rc && herr == hipSuccess) herr = sync_stream(st);
+    if (!rc && herr == hipSuccess) herr = hipEventElapsedTime(&t, ev[0], ev[1]);
+    *out.product_ms = t;
+    hipEventDestroy(ev[0]);
+    hipEventDestroy(ev[1]);
+  }
+  if (rc) return rc;
+  HIP_TRY(c, herr);
+  return RVT_OK;
+}
+}  // namespace
+
+int rvt_grammar_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int af_kinship, int* ok, double* af, double* beta,
+                        double* beta_var, double* pvalue, long long* counts) {
+  if (!c || !d_rows || V < 1 || !ok || !af || !beta || !beta_var || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
+  int rc = gg_bed_check(c, af_kinship, "rvt_grammar_bed_dev");
+  if (rc) return rc;
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  GgBedOut out;
+  out.ok = ok, out.af = af, out.beta = beta, out.beta_var = beta_var, out.pvalue = pvalue, out.counts = counts;
+  return gg_bed_run(c, c->stream, d_rows, V, af_kinship, out);
+}
+
+// Test hook: what rvt_grammar_bed_dev multiplies with and what the product returns.  planes (8 N, plane p at planes + p N, may be
+// null), *exp2 and totals (8) describe ty; sums (V x 3 x 9, may be null): per row the int64 sums of H, L and HL against the eight
+// planes and the ones column.
+int rvt_debug_grammar_bed(rvt_ctx* c, const unsigned char* d_rows, int64_t V, signed char* planes, int* exp2, long long* totals,
+                          long long* sums) {
+  if (!c || !exp2 || !totals || (sums && (!d_rows || V < 1))) return fail(c, RVT_E_INVALID, "bad arguments");
+  int rc = gg_bed_check(c, 0, "rvt_debug_grammar_bed");
+  if (rc) return rc;
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  const signed char* d_planes = nullptr;
+  int64_t ldp = 0;
+  rc = gg_bed_planes(c, st, &d_planes, &ldp);
+  if (rc) return rc;
+  if (sums) {
+    std::vector<int> ok((size_t)V);
+    std::vector<double> v((size_t)V);
+    GgBedOut out;
+    out.ok = ok.data(), out.beta = out.beta_var = out.pvalue = v.data(), out.sums = sums;
+    rc = gg_bed_run(c, st, d_rows, V, 0, out);
+    if (rc) return rc;
+  }
+  if (planes) {
+    HIP_TRY(c, hipMemcpy2DAsync(planes, (size_t)c->gg_N, d_planes, (size_t)ldp, (size_t)c->gg_N, kGgPlanes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, sync_stream(st));
+  }
+  *exp2 = c->gg_exp;
+  for (int p = 0; p < kGgPlanes; ++p) totals[p] = c->gg_totals[p];
+  return RVT_OK;
+}
+
+// Measurement hook: the product kernels of rvt_grammar_bed_dev over the V rows alone, between two HIP events
+int rvt_debug_grammar_bed_timed(rvt_ctx* c, const unsigned char* d_rows, int64_t V, double* ms) {
+  if (!c || !d_rows || V < 1 || !ms) return fail(c, RVT_E_INVALID, "bad arguments");
+  int rc = gg_bed_check(c, 0, "rvt_debug_grammar_bed_timed");
+  if (rc) return rc;
+  hipSetDevice(c->device);
+  rc = rvt_sync(c);
+  if (rc) return rc;
+  GgBedOut out;
+  out.product_ms = ms;
+  return gg_bed_run(c, c->stream, d_rows, V, 0, out);
 }
 
 }  // extern "C"

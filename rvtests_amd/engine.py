@@ -1383,6 +1383,7 @@ class Engine:
         N, d = X.shape
         out = GrammarNull()
         self._check(self.L.rvt_fit_grammar_null(self.ctx, N, d, _dp(X), _dp(y), C.byref(out)))
+        self._gg_N = N
         return out
 
     def grammar_block(self, ptr, V, af_kinship=0):
@@ -1394,6 +1395,46 @@ class Engine:
         self._check(self.L.rvt_grammar_block(self.ctx, C.c_void_p(int(ptr)), V, int(af_kinship),
                                              ok.ctypes.data_as(c_int_p), *[_dp(a) for a in arr]))
         return dict(ok=ok, af=arr[0], beta=arr[1], beta_var=arr[2], p=arr[3])
+
+    def grammar_bed_dev(self, d_rows, V, af_kinship=0, want_counts=True):
+        """grammar_block's dict for V consecutive rows of a resident .bed matrix (rvt_grammar_bed_dev: missing calls imputed to
+        the row's mean, N / 4 bytes read per row), plus counts (V, 4): n0 n1 n2 missing (None without want_counts).  After
+        fit_grammar_null; af_kinship also needs fit_fam_null on the same samples."""
+        V = int(V)
+        ok = np.zeros(V, dtype=np.int32)
+        arr = [np.zeros(V) for _ in range(4)]
+        cnt = np.zeros((V, 4), dtype=np.int64) if want_counts else None
+        self.L.rvt_grammar_bed_dev.restype = C.c_int
+        self.L.rvt_grammar_bed_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, c_int_p] + [c_double_p] * 4 + [C.c_void_p]
+        self._check(self.L.rvt_grammar_bed_dev(self.ctx, C.c_void_p(int(d_rows)), V, int(af_kinship), ok.ctypes.data_as(c_int_p),
+                                               *[_dp(a) for a in arr], cnt.ctypes.data_as(C.c_void_p) if want_counts else None))
+        return dict(ok=ok, af=arr[0], beta=arr[1], beta_var=arr[2], p=arr[3], counts=cnt)
+
+    def debug_grammar_bed(self, d_rows, V):
+        """What grammar_bed_dev multiplies with and what its product returns (rvt_debug_grammar_bed) for V rows (N = the samples
+        of the last fit_grammar_null):
+        dict of planes (8, N) int8 — the base-128 digits of rint(ty 2^(55 - exp2)) —, exp2, totals (8) and sums (V, 3, 9) int64:
+        the sums of the bit planes H, L, HL of every row against the eight planes and a column of ones."""
+        V, N = int(V), int(getattr(self, "_gg_N", 0))
+        if N < 1:
+            raise RvtError("debug_grammar_bed: fit_grammar_null first")
+        planes = np.zeros((8, N), dtype=np.int8)
+        totals = np.zeros(8, dtype=np.int64)
+        sums = np.zeros((V, 3, 9), dtype=np.int64)
+        e = C.c_int(0)
+        self.L.rvt_debug_grammar_bed.restype = C.c_int
+        self.L.rvt_debug_grammar_bed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, c_int_p, C.c_void_p, C.c_void_p]
+        self._check(self.L.rvt_debug_grammar_bed(self.ctx, C.c_void_p(int(d_rows)), V, planes.ctypes.data_as(C.c_void_p),
+                                                 C.byref(e), totals.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
+        return dict(planes=planes, exp2=e.value, totals=totals, sums=sums)
+
+    def debug_grammar_bed_timed(self, d_rows, V):
+        """Device milliseconds of grammar_bed_dev's product kernel over the V rows (rvt_debug_grammar_bed_timed)."""
+        ms = C.c_double(0.0)
+        self.L.rvt_debug_grammar_bed_timed.restype = C.c_int
+        self.L.rvt_debug_grammar_bed_timed.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, c_double_p]
+        self._check(self.L.rvt_debug_grammar_bed_timed(self.ctx, C.c_void_p(int(d_rows)), int(V), C.cast(C.byref(ms), c_double_p)))
+        return ms.value
 
     def fam_null_summary(self, d):
         covb = np.zeros(d)
