@@ -4,8 +4,8 @@
 // T = G'X (band_rows.hip.h, cov_rect_xz_kernel).  No fp64 column exists: a row costs N/4 bytes read and N bytes written
 // (two nibble rows of N/2), against 8 N + N + N/2 + N/2 for a column of the ring with its cache.
 //
-// bed_band_prep_kernel   grid (ceil(W / ROWS), slices), 256 threads.  A lane takes 16 samples (four .bed bytes: one dword where
-//                        the row's address allows it, else byte by byte) of ROWS rows per step and writes 8 bytes of each
+// bed_band_prep_kernel   grid (ceil(W / ROWS), slices), 256 threads.  A lane takes 16 samples (four .bed bytes: bed_load4 of
+//                        rvt_bed_codes.h, where the format is stated) of ROWS rows per step and writes 8 bytes of each
 //                        nibble row; the ROWS rows share the loads of X.  The sums over X are fp64 FMAs with h in {0, 1, 2} and
 //                        m in {0, 1}: per slice and row 2 DMAX partial sums and four integer counts, written — not added — to
 //                        part_t / part_c.  The slice partition is a function of N alone (bed_band_slices), so a row's numbers
@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rvt_bed_codes.h"
 #include "rvt_bed_nibbles.h"
 
 namespace rvt {
@@ -46,6 +47,7 @@ __global__ __launch_bounds__(256) void bed_band_prep_kernel(const unsigned char*
   const int nr = min(ROWS, W - row0);
   const long long per = bed_band_slice_len(N, (int)gridDim.y);
   const long long i0 = (long long)blockIdx.y * per, i1 = (i0 + per < N) ? i0 + per : N;
+  const unsigned char* rows_end = rows + (long long)W * cb;
   double th[ROWS][DMAX], tm[ROWS][DMAX];
   int cnt[ROWS][4];
 #pragma unroll
@@ -57,21 +59,11 @@ __global__ __launch_bounds__(256) void bed_band_prep_kernel(const unsigned char*
   }
   for (long long i = i0 + 16 * (long long)threadIdx.x; i < i1; i += kBedBandStep) {
     const long long b0 = i >> 2;  // (a multiple of 4: i0 and the step are multiples of 16)
+    // (a dword may cover bytes of the next row: samples at or beyond i1 <= N, which `live` below discards)
     unsigned code[ROWS];
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      code[r] = 0;
-      if (r < nr) {
-        const unsigned char* rp = rows + (long long)(row0 + r) * cb + b0;
-        if ((reinterpret_cast<uintptr_t>(rp) & 3u) == 0 && b0 + 4 <= cb) {
-          code[r] = *reinterpret_cast<const unsigned*>(rp);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (b0 + e < cb) code[r] |= (unsigned)rp[e] << (8 * e);
-        }
-      }
-    }
+    for (int r = 0; r < ROWS; ++r)
+      code[r] = r < nr ? bed_load4(rows + (long long)(row0 + r) * cb + b0, rows, rows_end) : 0u;
     unsigned long long hq[ROWS], mq[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) hq[r] = mq[r] = 0ull;
@@ -161,9 +153,8 @@ __global__ __launch_bounds__(256) void bed_band_prep_kernel(const unsigned char*
   }
 }
 
-// One thread per row: the slices added in order; from the integer counts mu = (n1 + 2 n2) / (n0 + n1 + n2) (0 for a row with
-// no called sample or no missing call: the column is its calls), the column sum (n1 + 2 n2) + mu n_missing and the flag — a
-// column has two distinct values iff two of n0, n1, n2 are non-zero (one called value v makes mu = v exactly); T_k = sum h X_k +
+// One thread per row: the slices added in order; from the integer counts (bed_site) mu = the mean of the called samples, 0 for a
+// row with no missing call (the column is its calls), the column sum (n1 + 2 n2) + mu n_missing and the flag; T_k = sum h X_k +
 // mu sum m X_k.  T is W x d column-major; counts (optional): 4 per row; *any_missing is set when some row has a missing call.
 __global__ void bed_band_finish_kernel(const double* __restrict__ part_t, const int* __restrict__ part_c, int slices, int W,
                                        int d, int dmax, double* __restrict__ colsum, int* __restrict__ poly,
@@ -174,10 +165,10 @@ __global__ void bed_band_finish_kernel(const double* __restrict__ part_t, const 
   long long n[4] = {0, 0, 0, 0};
   for (int s = 0; s < slices; ++s)
     for (int q = 0; q < 4; ++q) n[q] += part_c[((long long)s * W + j) * 4 + q];
-  const long long called = n[0] + n[1] + n[2], ac = n[1] + 2 * n[2];
-  const double mu = (n[3] > 0 && called > 0) ? (double)ac / (double)called : 0.0;
-  colsum[j] = (double)ac + mu * (double)n[3];
-  poly[j] = ((n[0] > 0) + (n[1] > 0) + (n[2] > 0)) >= 2 ? 1 : 0;
+  const BedSite s = bed_site(n[0], n[1], n[2], n[3]);
+  const double mu = n[3] > 0 ? s.mean : 0.0;
+  colsum[j] = (double)s.ac + mu * (double)n[3];
+  poly[j] = s.poly ? 1 : 0;
   mu_out[j] = mu;
   for (int k = 0; k < d; ++k) {
     double a = 0.0, b = 0.0;

@@ -6,7 +6,8 @@
 //   grammar_bed_kernel         grid (row-tile groups, sample slices), 512 threads = 8 waves.  The workgroup stages its slice of
 //                              the B operand [8 planes | ones] in LDS once (9 bytes per sample: the seven padding columns of the
 //                              16 are constant zero and come from registers) and every wave walks row tiles of 16 rows over it:
-//                              per step of 256 samples a lane loads the 16 bytes of codes of ITS row and quarter, builds the
+//                              per step of 256 samples a lane loads the 16 bytes of codes of ITS row and quarter (bed_load16
+//                              of rvt_bed_codes.h, where the format is stated: no byte outside the V rows is touched), builds the
 //                              three 0 / 1 int8 operands H = hi bits, L = lo bits, HL = hi & lo in registers and issues
 //                              3 x 4 v_mfma_i32_16x16x64_i8.  The rows of B for samples >= N are zero, ones column included:
 //                              that makes the padding pairs of a row's last byte, and whatever lies behind it, harmless.  The
@@ -85,38 +86,6 @@ static __global__ __launch_bounds__(1024) void grammar_ty_planes_kernel(const do
   }
 }
 
-// 16 bytes of codes at p (any alignment), no byte outside [base, end) touched; bytes at or behind `end` read as zero.  Inside the
-// buffer: five aligned dwords shifted together (four when p is aligned); at its first and last few bytes: byte by byte.
-__device__ __forceinline__ void gg_load_codes(const unsigned char* p, const unsigned char* base, const unsigned char* end,
-                                              uint32_t (&w)[4]) {
-  const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(p) & 3u);
-  const unsigned char* q = p - sh;
-  if (q >= base && q + (sh ? 20 : 16) <= end) {
-    const uint32_t* a = reinterpret_cast<const uint32_t*>(q);
-    const uint32_t a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
-    const uint32_t a4 = sh ? a[4] : 0u;
-    w[0] = __builtin_amdgcn_alignbyte(a1, a0, sh);
-    w[1] = __builtin_amdgcn_alignbyte(a2, a1, sh);
-    w[2] = __builtin_amdgcn_alignbyte(a3, a2, sh);
-    w[3] = __builtin_amdgcn_alignbyte(a4, a3, sh);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      uint32_t v = 0u;
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if (p + 4 * k + b < end) v |= (uint32_t)p[4 * k + b] << (8 * b);
-      w[k] = v;
-    }
-  }
-}
-
-// the four bits at 0, 2, 4, 6 of byte k of x -> bit 0 of the four bytes of a dword: the copies of the byte at shifts 0, 6, 12, 18
-// (one 24-bit multiplication) overlap in a bit that can carry only into an odd bit, which the mask drops
-__device__ __forceinline__ uint32_t gg_spread(uint32_t x, int k) {
-  return __umul24((x >> (8 * k)) & 0x55u, 0x41041u) & 0x01010101u;
-}
-
 // part: [slices][V][kGgPart] int32, row-major.  bytes = V * pitch, the extent of the rows.  Dynamic LDS: 9 * slice bytes.
 static __global__ __launch_bounds__(kGgThreads) void grammar_bed_kernel(const unsigned char* __restrict__ rows, long long pitch,
                                                                         long long N, int V, long long bytes,
@@ -134,13 +103,8 @@ static __global__ __launch_bounds__(kGgThreads) void grammar_bed_kernel(const un
     if (col < kGgPlanes) {
       v = *reinterpret_cast<const uint4*>(planes + col * ldp + s);  // (ldp >= npad, a multiple of 64; zero from sample N on)
     } else {
-      uint32_t o[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const long long left = N - (s + 4 * k);
-        o[k] = left >= 4 ? 0x01010101u : (left <= 0 ? 0u : (0x01010101u & ((1u << (8 * (int)left)) - 1u)));
-      }
-      v = make_uint4(o[0], o[1], o[2], o[3]);
+      v = make_uint4(bed_live_lanes(N - s), bed_live_lanes(N - (s + 4)), bed_live_lanes(N - (s + 8)),
+                     bed_live_lanes(N - (s + 12)));  // the ones column: 1 for the samples that exist
     }
     gg_lds[grp * kGgCols + col] = v;
   }
@@ -155,10 +119,10 @@ static __global__ __launch_bounds__(kGgThreads) void grammar_bed_kernel(const un
     const unsigned char* rp = rows + (row0 + r) * pitch + (s0 >> 2) + 16 * g;
     gg_i4_t accH = {0, 0, 0, 0}, accL = {0, 0, 0, 0}, accHL = {0, 0, 0, 0};
     uint32_t cur[4] = {0u, 0u, 0u, 0u}, nxt[4];
-    if (live && 64 * g < len) gg_load_codes(rp, rows, end, cur);
+    if (live && 64 * g < len) bed_load16(rp, rows, end, cur);
     for (int c0 = 0; c0 < len; c0 += kGgStep) {
       nxt[0] = nxt[1] = nxt[2] = nxt[3] = 0u;
-      if (live && c0 + kGgStep + 64 * g < len) gg_load_codes(rp + ((c0 + kGgStep) >> 2), rows, end, nxt);
+      if (live && c0 + kGgStep + 64 * g < len) bed_load16(rp + ((c0 + kGgStep) >> 2), rows, end, nxt);
       const bool inb = (r < kGgCols) && (c0 + 64 * g < len);
       const uint4* bp = gg_lds + ((c0 >> 4) + 4 * g) * kGgCols + r;
 #pragma unroll
@@ -167,8 +131,8 @@ static __global__ __launch_bounds__(kGgThreads) void grammar_bed_kernel(const un
         gg_i4_t H, L, HL, B = {0, 0, 0, 0};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          H[k] = (int)gg_spread(hi, k);
-          L[k] = (int)gg_spread(lo, k);
+          H[k] = (int)bed_spread(hi, k);
+          L[k] = (int)bed_spread(lo, k);
           HL[k] = H[k] & L[k];
         }
         if (inb) {

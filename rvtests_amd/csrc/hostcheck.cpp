@@ -12,6 +12,7 @@
 #include <chrono>
 #include "host_stage.h"
 #include "band_tiles.h"
+#include "rvt_bed_codes.h"
 #include "rvt_bed_nibbles.h"
 #include "block_pool.h"
 #include "perm_counter.h"
@@ -416,6 +417,32 @@ void hc_bed_byte_nibbles(unsigned byte, int live, unsigned* out) {
   out[0] = nb.h, out[1] = nb.m;
   out[2] = (unsigned)rvt::bed_popc16(nb.zero), out[3] = (unsigned)rvt::bed_popc16(nb.one);
   out[4] = (unsigned)rvt::bed_popc16(nb.two), out[5] = (unsigned)rvt::bed_popc16(nb.miss);
+}
+// ---- rvt_bed_codes.h: what every reader of resident .bed rows shares ---------------------------------------------------------------
+// out5 = called, ac, poly, flip, missing; returns the mean
+double hc_bed_site(long long n0, long long n1, long long n2, long long nm, long long* out5) {
+  const rvt::BedSite s = rvt::bed_site(n0, n1, n2, nm);
+  out5[0] = s.called, out5[1] = s.ac, out5[2] = s.poly ? 1 : 0, out5[3] = s.flip ? 1 : 0, out5[4] = s.missing;
+  return s.mean;
+}
+double hc_bed_value(unsigned q, double fill) { return rvt::bed_value(q, fill); }
+unsigned hc_bed_live_pairs(long long left) { return rvt::bed_live_pairs(left); }
+unsigned hc_bed_live_lanes(long long left) { return rvt::bed_live_lanes(left); }
+// n4 (the caller's, added to): calls of 0 / 1 / 2 / missing among the first `left` of the 16 samples of code
+void hc_bed_counts16(unsigned code, long long left, int* n4) {
+  int n[4] = {n4[0], n4[1], n4[2], n4[3]};
+  rvt::bed_counts16(code, rvt::bed_live_pairs(left), n);
+  for (int k = 0; k < 4; ++k) n4[k] = n[k];
+}
+unsigned hc_bed_spread(unsigned x, int k) { return rvt::bed_spread(x, k); }
+// the loaders at buf + off inside [buf + base, buf + end)
+unsigned hc_bed_load4(const unsigned char* buf, long long off, long long base, long long end) {
+  return rvt::bed_load4(buf + off, buf + base, buf + end);
+}
+void hc_bed_load16(const unsigned char* buf, long long off, long long base, long long end, unsigned* w4) {
+  uint32_t w[4];
+  rvt::bed_load16(buf + off, buf + base, buf + end, w);
+  for (int k = 0; k < 4; ++k) w4[k] = w[k];
 }
 int hc_band_tile_of(int h, int j, int W, int halo) { return rvt::band_tile_of(h, j, W, halo); }
 long long hc_band_slices(int n_tiles, long long chunks, long long max_part_bytes) {

@@ -1,7 +1,6 @@
 // rvtests_amd — the empirical kinship of `vcf2kinship --ibs` / `--bn` (IBSKinship and BaldingNicolsKinship,
 // vcfUtils/vcf2kinship.cpp:138-266, behind the site filters of :943-960) from rows of a resident .bed matrix
-// (rvt_bed_alloc: row r at rows + r * cb, cb = ceil(N / 4) bytes, no alignment; PLINK codes 00 -> 0, 10 -> 1, 11 -> 2,
-// 01 -> missing, sample i in bits 2 (i & 3) of byte i >> 2).  Both methods are Gram products over the sites, N x N x V:
+// (rows cb = ceil(N / 4) bytes apart; the format: rvt_bed_codes.h).  Both methods are Gram products over the sites, N x N x V:
 //
 //   IBS   2 - |g_i - g_j| = n_i n_j + u_i u_j + h_i h_j   with n = [called], u = g - 1, h = [g == 1], all three 0 for a
 //         missing call (0/0: 1+1+0, 0/1: 1+0+0, 0/2: 1-1+0, 1/1: 1+0+1, 1/2: 1+0+0, 2/2: 1+1+0).  The pair count is
@@ -21,6 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rvt_bed_codes.h"
 
 namespace rvt {
 
@@ -49,11 +49,11 @@ static __global__ __launch_bounds__(256) void kin_site_kernel(const unsigned lon
                                                               KinTotals* __restrict__ totals) {
   const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
   if (v >= V) return;
-  const long long n0 = (long long)counts[4 * v], n1 = (long long)counts[4 * v + 1], n2 = (long long)counts[4 * v + 2],
-                  nm = (long long)counts[4 * v + 3];
-  const long long called = n0 + n1 + n2, ac = n1 + 2 * n2;
+  const BedSite site = bed_site((long long)counts[4 * v], (long long)counts[4 * v + 1], (long long)counts[4 * v + 2],
+                                (long long)counts[4 * v + 3]);
+  const long long called = site.called, ac = site.ac;
   int cat = 0;
-  if ((double)nm > max_missing * (double)N) {
+  if ((double)site.missing > max_missing * (double)N) {
     cat = 1;
   } else {
     const double af = called > 0 ? (double)ac / (double)(2 * called) : 0.0;
@@ -66,7 +66,7 @@ static __global__ __launch_bounds__(256) void kin_site_kernel(const unsigned lon
   if (bn) {
     double z0 = 0.0, z1 = 0.0, z2 = 0.0;
     if (cat == 0) {
-      const double mean = (double)ac / (double)called;
+      const double mean = site.mean;  // (ac > 0 here: a sample is called)
       const double scale = sqrt(1.0 / (1.0 - mean / 2.0) / mean);
       z0 = (0.0 - mean) * scale, z1 = (1.0 - mean) * scale, z2 = (2.0 - mean) * scale;
     }

@@ -13,6 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rvt_bed_codes.h"
 #include "rvt_mtscore.h"
 #include "rot_gemm.hip.h"
 
@@ -221,39 +222,32 @@ static __global__ __launch_bounds__(256) void mt_finish_kernel(const double* __r
 }
 
 // ---- rows of a resident .bed matrix (rvt_mt_score_bed_dev) ---------------------------------------------------------------------------
-// Row r at rows + r * pitch, pitch = ceil(n / 4) bytes, no alignment; PLINK codes 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing,
-// sample i in bits 2 (i & 3) of byte i >> 2 (recode_kernels.hip.h, fam_bed_kernels.hip.h).  The column a caller of
+// Rows pitch = ceil(n / 4) bytes apart (the format: rvt_bed_codes.h).  The column a caller of
 // rvt_mt_score_block uploads is exactly g = c + mu m: c = the calls with missing -> 0, m = the missing indicator, mu = the mean of
 // the called ones.  c and m are one int8 plane each, so G'[Yc | Zc] and G'indModel are exact integer products of c, plus mu
 // times those of m for the rows that have a missing call at all.
 
 // The moments of the imputed column from the counts[4 v ..] = n0 n1 n2 missing of row v: mu[v] = a / called with a = n1 + 2 n2
-// and called = n0 + n1 + n2, gg[v] = sum (g - mu)^2 = (n1 + 4 n2) - a a / called (the missing entries sit on the mean) — exact
-// integers and one rounding each; with called = n, mt_int_moments_kernel's expressions.  No called sample: mu = 0, gg = 0.
+// and called = n0 + n1 + n2 (bed_site), gg[v] = sum (g - mu)^2 = (n1 + 4 n2) - a a / called (the missing entries sit on the
+// mean) — exact integers and one rounding each; with called = n, mt_int_moments_kernel's expressions.  No called sample: mu = 0,
+// gg = 0.
 static __global__ void mt_bed_site_kernel(const unsigned long long* __restrict__ counts, int V, double* __restrict__ mu,
                                           double* __restrict__ gg) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= V) return;
-  const long long n0 = (long long)counts[4 * v], n1 = (long long)counts[4 * v + 1], n2 = (long long)counts[4 * v + 2];
-  const long long called = n0 + n1 + n2;
-  const double s1 = (double)(n1 + 2 * n2), s2 = (double)(n1 + 4 * n2), nc = (double)called;
-  mu[v] = called > 0 ? s1 / nc : 0.0;
-  gg[v] = called > 0 ? s2 - s1 * s1 / nc : 0.0;
-}
-
-// the four 2-bit codes of one byte, one per byte of a dword (code e in bits 8 e, 8 e + 1)
-__device__ __forceinline__ uint32_t mt_bed_spread(uint32_t b) {
-  return (b & 0x03u) | ((b & 0x0cu) << 6) | ((b & 0x30u) << 12) | ((b & 0xc0u) << 18);
+  const long long n1 = (long long)counts[4 * v + 1], n2 = (long long)counts[4 * v + 2];
+  const BedSite s = bed_site((long long)counts[4 * v], n1, n2, 0);
+  const double s1 = (double)s.ac, s2 = (double)(n1 + 4 * n2), nc = (double)s.called;
+  mu[v] = s.mean;
+  gg[v] = s.called > 0 ? s2 - s1 * s1 / nc : 0.0;
 }
 
 // Row blockIdx.x of the piece -> column blockIdx.x of Bc (the calls, missing -> 0) and, when slot[row] >= 0, column slot[row] of
 // Bm (the missing indicator): the one-plane B operands of rvt_planes_gemm, column j at B + j * ldk, sample i at byte i, zero
 // from sample n to ldk whatever the padding pairs of the row's last byte hold.  A thread takes 16 samples per step: four bytes
-// of codes in, one 16-byte store per operand out (ldk is a multiple of 128, the operands are 256-byte aligned).  The codes
-// come as one dword where the row's address allows, as two aligned dwords shifted together where the row starts at an odd
-// address, and byte by byte where a dword would reach outside the piece [rows, rows + bytes) — its first and last few bytes
-// only.  Bytes of a dword that belong to the next row are samples >= n and are masked with the padding pairs.
-// grid = (rows of the piece, ceil(ldk / kMtPassRows)), 256 threads.
+// of codes in (bed_load4 inside the piece [rows, rows + bytes)), one 16-byte store per operand out (ldk is a multiple of 128, the
+// operands are 256-byte aligned).  Bytes of a dword that belong to the next row are samples >= n and are masked with the padding
+// pairs.  grid = (rows of the piece, ceil(ldk / kMtPassRows)), 256 threads.
 static __global__ __launch_bounds__(256) void mt_bed_unpack_kernel(const unsigned char* __restrict__ rows, long long pitch,
                                                                    long long n, long long bytes, const int* __restrict__ slot,
                                                                    signed char* __restrict__ Bc, signed char* __restrict__ Bm,
@@ -264,36 +258,19 @@ static __global__ __launch_bounds__(256) void mt_bed_unpack_kernel(const unsigne
   const int sl = slot[col];
   uint4* oc = reinterpret_cast<uint4*>(Bc + (long long)col * ldk);
   uint4* om = sl >= 0 ? reinterpret_cast<uint4*>(Bm + (long long)sl * ldk) : nullptr;
-  const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(r) & 3u);  // (the same for the whole row: b0 is a multiple of 4)
   const long long i_lo = (long long)blockIdx.y * kMtPassRows;
   const long long i_hi = (i_lo + kMtPassRows < ldk) ? i_lo + kMtPassRows : ldk;
   for (long long i = i_lo + 16 * (long long)threadIdx.x; i < i_hi; i += 16 * 256) {
     const long long b0 = i >> 2;
-    uint32_t code = 0u;
-    if (b0 < pitch) {
-      const unsigned char* p = r + b0;
-      const unsigned char* a = p - sh;
-      if (sh == 0u && p + 4 <= end) {
-        code = *reinterpret_cast<const uint32_t*>(p);
-      } else if (sh != 0u && a >= rows && a + 8 <= end) {
-        const uint32_t lo = *reinterpret_cast<const uint32_t*>(a), hi = *reinterpret_cast<const uint32_t*>(a + 4);
-        code = (lo >> (8u * sh)) | (hi << (32u - 8u * sh));
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (b0 + e < pitch) code |= (uint32_t)p[e] << (8 * e);
-      }
-    }
+    const uint32_t code = b0 < pitch ? bed_load4(r + b0, rows, end) : 0u;
     const long long left = n - i;  // samples of this group that exist (may be <= 0: zeros up to ldk)
     uint32_t cw[4], mw[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const uint32_t w = mt_bed_spread((code >> (8 * k)) & 0xffu);
-      const uint32_t lo = w & 0x01010101u, hi = (w >> 1) & 0x01010101u;
-      const long long lk = left - 4 * k;
-      const uint32_t live = lk >= 4 ? 0xffffffffu : (lk <= 0 ? 0u : (1u << (8 * (int)lk)) - 1u);
-      cw[k] = (hi + (hi & lo)) & live;
-      mw[k] = (lo & ~hi) & live;
+      const uint32_t live = bed_live_lanes(left - 4 * k);
+      const uint32_t lo = bed_spread(code, k) & live, hi = bed_spread(code >> 1, k) & live;
+      cw[k] = hi + (hi & lo);
+      mw[k] = lo & ~hi;
     }
     oc[i >> 4] = make_uint4(cw[0], cw[1], cw[2], cw[3]);
     if (om) om[i >> 4] = make_uint4(mw[0], mw[1], mw[2], mw[3]);

@@ -11,6 +11,7 @@
 // Included by rvt_meta.hip (the unit of rvt_block_upload_columns).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "rvt_bed_codes.h"
 
 namespace rvt {
 
@@ -93,9 +94,7 @@ __global__ __launch_bounds__(kRecodeThreads) void recode_write_kernel(const doub
   }
 }
 
-// ---- rows of a resident .bed matrix (rvt_bed_alloc: row r at rows + r * cb, cb = ceil(N / 4) bytes, no alignment) ---------------
-// PLINK 2-bit codes as bed_expand_columns_kernel reads them: sample i in bits 2 (i & 3) of byte i >> 2; 00 -> 0, 10 -> 1,
-// 11 -> 2, 01 -> missing.
+// ---- rows of a resident .bed matrix, cb = ceil(N / 4) bytes apart (the format: rvt_bed_codes.h) -----------------------------------
 // counts[row][0..3] += calls of 0 / 1 / 2 / missing of row blockIdx.y, from the codes by population counts: a lane takes four
 // bytes (16 samples) per step; the bits of the last byte beyond sample N - 1 are masked out.  counts must be zero before.
 __global__ __launch_bounds__(kRecodeThreads) void recode_bed_count_kernel(const unsigned char* __restrict__ rows, long long cb,
@@ -109,14 +108,7 @@ __global__ __launch_bounds__(kRecodeThreads) void recode_bed_count_kernel(const 
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (b0 + e < cb) code |= (unsigned)r[b0 + e] << (8 * e);
-    // the low bit of every sample of this word that exists: 16 samples from sample 4 b0 on
-    const long long left = N - 4 * b0;  // > 0: b0 < cb
-    const unsigned live = left >= 16 ? 0x55555555u : (0x55555555u & ((1u << (2 * (int)left)) - 1u));
-    const unsigned lo = code & 0x55555555u, hi = (code >> 1) & 0x55555555u;
-    v[0] += __popc(live & ~lo & ~hi);
-    v[1] += __popc(live & hi & ~lo);
-    v[2] += __popc(live & hi & lo);
-    v[3] += __popc(live & lo & ~hi);
+    bed_counts16(code, bed_live_pairs(N - 4 * b0), v);  // (the samples of this word that exist: 16 from sample 4 b0 on)
   }
   int s[4];
   recode_block_sum<4>(v, s);

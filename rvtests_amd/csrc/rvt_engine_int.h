@@ -907,6 +907,17 @@ RVT_INTERNAL int gemm_tn_f64(rvt_ctx* c, const double* A, int64_t lda, int M, co
 // the calls of 0 / 1 / 2 / missing of n_rows rows of a resident .bed matrix, added to d_cnt[4 r + k] (recode_bed_count_kernel)
 RVT_INTERNAL void bed_row_counts(hipStream_t st, const unsigned char* d_rows, long long cb, long long N, int n_rows,
                                  unsigned long long* d_cnt);
+// the same of any number of consecutive rows into d_cnt, zeroed first, in launches of at most 32 768 rows; with host or counts,
+// bed_counts_host behind it
+RVT_INTERNAL int bed_piece_counts(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, long long cb, long long N,
+                                  long long n_rows, unsigned long long* d_cnt, std::vector<unsigned long long>* host,
+                                  long long* counts);
+// the counts of n_rows rows copied to the host and st waited for: into host (optional) and, as long long, into counts (optional)
+RVT_INTERNAL int bed_counts_host(rvt_ctx* c, hipStream_t st, const unsigned long long* d_cnt, long long n_rows,
+                                 std::vector<unsigned long long>* host, long long* counts);
+// "the rows handed to `who` have the pitch ceil(N / 4) of this null model's N": the context's ordinary null model, if one is set
+// and rvt_bed_alloc saw it, has the same N (its name for the other one: `other`)
+RVT_INTERNAL int bed_rows_check(rvt_ctx* c, const char* who, long long N, const char* other);
 // n_rows rows of a resident .bed matrix as fp64 columns (leading dimension ld), missing -> d_mu[row] (bed_expand_columns_kernel)
 RVT_INTERNAL void bed_rows_expand(hipStream_t st, const unsigned char* d_rows, long long cb, const double* d_mu, long long N,
                                   long long ld, int n_rows, double* G);

@@ -1657,14 +1657,10 @@ struct FamBedPiece {
   int* poly;
 };
 
-// The state both calls need.  The rows' pitch is ceil(N / 4) bytes with the N of the null model rvt_bed_alloc saw: an ordinary
-// null model of another N beside the family null means rows of another pitch.
+// the state both calls need
 int fam_bed_check(rvt_ctx* c, const char* who) {
   if (!c->have_fam) return fail(c, RVT_E_STATE, "%s: rvt_set_kinship + rvt_fit_fam_null first", who);
-  if (c->have_null && c->nc.N != c->fam_nc.N)
-    return fail(c, RVT_E_STATE, "%s: the null model has N = %lld, the family null model N = %lld (the resident rows have the former's pitch)",
-                who, (long long)c->nc.N, (long long)c->fam_nc.N);
-  return RVT_OK;
+  return bed_rows_check(c, who, (long long)c->fam_nc.N, "family");
 }
 
 int fam_bed_ws(rvt_ctx* c, hipStream_t st, FamBedPiece* p) {
@@ -1690,27 +1686,25 @@ int fam_bed_ws(rvt_ctx* c, hipStream_t st, FamBedPiece* p) {
 int fam_bed_front(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int n, const FamBedPiece& p, long long* counts) {
   const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld, cb = (N + 3) / 4;
   // 1. the site pass over the codes
-  HIP_TRY(c, hipMemsetAsync(p.cnt, 0, sizeof(unsigned long long) * 4 * (size_t)n, st));
-  bed_row_counts(st, d_rows, cb, N, n, p.cnt);
+  int rc = bed_piece_counts(c, st, d_rows, cb, N, n, p.cnt, nullptr, nullptr);
+  if (rc) return rc;
   hipLaunchKernelGGL(fam_bed_site_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p.cnt, n, p.mu, p.muq,
                      p.cs, p.poly);
   HIP_TRY(c, hipGetLastError());
-  std::vector<unsigned long long> cnt(4 * (size_t)n);
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), p.cnt, sizeof(unsigned long long) * cnt.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(c, sync_stream(st));
+  std::vector<unsigned long long> cnt;
+  rc = bed_counts_host(c, st, p.cnt, n, &cnt, counts);
+  if (rc) return rc;
   bool any_missing = false;
   for (int h = 0; h < n; ++h) any_missing = any_missing || cnt[4 * (size_t)h + 3] != 0;
-  if (counts)
-    for (size_t i = 0; i < cnt.size(); ++i) counts[i] = (long long)cnt[i];
   // 2. the rotation, by the installed form
   const bool dense = !c->d_fam_run && !(c->d_csc_ptr && !c->d_uq_range);
-  int rc = ensure_fam_cols(c, (size_t)(dense && any_missing ? 2 * n : n), ld);  // (d_Gp holds [U'c | U'm] of a dense piece)
+  rc = ensure_fam_cols(c, (size_t)(dense && any_missing ? 2 * n : n), ld);  // (d_Gp holds [U'c | U'm] of a dense piece)
   if (rc) return rc;
   HIP_TRY(c, hipMemsetAsync(c->d_Gt, 0, sizeof(double) * (size_t)ld * n, st));
   if (c->d_fam_run) {  // the family form
-    hipLaunchKernelGGL(rot_fam_bed_kernel, dim3((unsigned)c->fam_runs, (unsigned)((n + kRotFamCols - 1) / kRotFamCols)),
+    hipLaunchKernelGGL(rot_fam_bed_kernel<BedRowsAt>, dim3((unsigned)c->fam_runs, (unsigned)((n + kRotFamCols - 1) / kRotFamCols)),
                        dim3(kRotFamRows), 0, st, c->d_fam_run, c->d_fam_of, c->d_fam_ptr, c->d_fam_members, c->d_csc_ptr,
-                       c->d_csc_vals, d_rows, (long long)cb, p.mu, n, c->d_Gt, (long long)ld);
+                       c->d_csc_vals, BedRowsAt{d_rows, (long long)cb}, p.mu, n, c->d_Gt, (long long)ld);
     HIP_TRY(c, hipGetLastError());
     return RVT_OK;
   }
@@ -1726,8 +1720,9 @@ int fam_bed_front(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int n
   const size_t need = (size_t)(((int64_t)nB + kRotBN - 1) / kRotBN * kRotBN) * (size_t)ldk;
   HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
   HIP_TRY(c, hipMemsetAsync(c->d_rotB, 0, need, st));
-  hipLaunchKernelGGL(fam_bed_unpack_kernel, dim3((unsigned)((cb + 255) / 256), (unsigned)n), dim3(256), 0, st, d_rows,
-                     (long long)cb, (long long)N, n, any_missing ? 1 : 0, c->d_rotB.get(), (long long)ldk);
+  hipLaunchKernelGGL(fam_bed_unpack_kernel<BedRowsAt>, dim3((unsigned)((cb + 255) / 256), (unsigned)n), dim3(256), 0, st,
+                     BedRowsAt{d_rows, (long long)cb}, (long long)cb, (long long)N, n, any_missing ? 1 : 0, c->d_rotB.get(),
+                     (long long)ldk);
   HIP_TRY(c, hipGetLastError());
   const std::vector<int> zero_exp((size_t)nB, 0);
   double* C = any_missing ? c->d_Gp.get() : c->d_Gt.get();
@@ -1924,16 +1919,17 @@ static int fam_genes_bed_front(rvt_ctx* c, int n, const unsigned char* const* d_
     const size_t per = (size_t)65535 * kRotFamCols;  // (gridDim.y holds at most 65535 column tiles)
     for (size_t t0 = 0; t0 < T; t0 += per) {
       const int nc = (int)std::min(per, T - t0);
-      hipLaunchKernelGGL(rot_fam_bed_list_kernel, dim3((unsigned)c->fam_runs, (unsigned)((nc + kRotFamCols - 1) / kRotFamCols)),
+      hipLaunchKernelGGL(rot_fam_bed_kernel<BedRowList>, dim3((unsigned)c->fam_runs, (unsigned)((nc + kRotFamCols - 1) / kRotFamCols)),
                          dim3(kRotFamRows), 0, st, c->d_fam_run, c->d_fam_of, c->d_fam_ptr, c->d_fam_members, c->d_csc_ptr,
-                         c->d_csc_vals, d_krow + t0, d_flip + t0, d_mu + t0, nc, c->d_Gt + t0 * (size_t)ld, (long long)ld);
+                         c->d_csc_vals, BedRowList{d_krow + t0, d_flip + t0}, d_mu + t0, nc, c->d_Gt + t0 * (size_t)ld,
+                         (long long)ld);
       HIP_TRY(c, hipGetLastError());
     }
   } else if (!dense) {  // column-compressed U, scattered supports: the flipped fp64 columns on the device, then the gather
     for (size_t t0 = 0; t0 < T; t0 += 65535) {  // (gridDim.y holds at most 65535 columns)
       const unsigned nt = (unsigned)std::min<size_t>(65535, T - t0);
-      hipLaunchKernelGGL(fam_bed_expand_list_kernel, dim3((unsigned)((cb + 255) / 256), nt), dim3(256), 0, st, d_krow + t0,
-                         d_flip + t0, d_mu + t0, (long long)cb, (long long)N, (long long)ld, c->d_Gp + t0 * (size_t)ld);
+      hipLaunchKernelGGL(bed_expand_columns_kernel<BedRowList>, dim3((unsigned)((cb + 255) / 256), nt), dim3(256), 0, st,
+                         BedRowList{d_krow + t0, d_flip + t0}, d_mu + t0, (long long)N, (long long)ld, c->d_Gp + t0 * (size_t)ld);
       HIP_TRY(c, hipGetLastError());
     }
     rc = rotate_columns(c, c->d_Gp, ld, (int)T, c->d_Gt, ld, st);
@@ -1945,9 +1941,9 @@ static int fam_genes_bed_front(rvt_ctx* c, int n, const unsigned char* const* d_
       const size_t need = (size_t)(((int64_t)nB + kRotBN - 1) / kRotBN * kRotBN) * (size_t)ldk;
       HIP_TRY(c, c->d_rotB.grow(need, need + need / 4, st, true));
       HIP_TRY(c, hipMemsetAsync(c->d_rotB, 0, need, st));
-      hipLaunchKernelGGL(fam_bed_unpack_list_kernel, dim3((unsigned)((cb + 255) / 256), (unsigned)ncp), dim3(256), 0, st,
-                         d_krow + c0, d_flip + c0, (long long)cb, (long long)N, ncp, any_missing ? 1 : 0, c->d_rotB.get(),
-                         (long long)ldk);
+      hipLaunchKernelGGL(fam_bed_unpack_kernel<BedRowList>, dim3((unsigned)((cb + 255) / 256), (unsigned)ncp), dim3(256), 0, st,
+                         BedRowList{d_krow + c0, d_flip + c0}, (long long)cb, (long long)N, ncp, any_missing ? 1 : 0,
+                         c->d_rotB.get(), (long long)ldk);
       HIP_TRY(c, hipGetLastError());
       const std::vector<int> zero_exp((size_t)nB, 0);
       double* dst = c->d_Gt + c0 * (size_t)ld;
@@ -2325,9 +2321,7 @@ constexpr int kGgBedPiece = 8192;  // rows of one launch of the product; af=kins
 // what a call may be refused for, before anything is written
 int gg_bed_check(rvt_ctx* c, int af_kinship, const char* who) {
   if (!c->have_grammar) return fail(c, RVT_E_STATE, "%s: rvt_set_kinship + rvt_fit_grammar_null first", who);
-  if (c->have_null && c->nc.N != c->gg_N)
-    return fail(c, RVT_E_STATE, "%s: the null model has N = %lld, the GrammarGamma null model N = %lld (the resident rows have the former's pitch)",
-                who, (long long)c->nc.N, (long long)c->gg_N);
+  if (int rc = bed_rows_check(c, who, (long long)c->gg_N, "GrammarGamma")) return rc;
   if (af_kinship && (!c->have_fam || c->fam_nc.N != c->gg_N))
     return fail(c, RVT_E_STATE, "%s: af=kinship needs rvt_fit_fam_null on the same samples (the rotation takes its layout)", who);
   if (c->gg_N > kGgMaxN) return fail(c, RVT_E_TOO_LARGE, "%s: N = %lld (at most %lld)", who, (long long)c->gg_N, (long long)kGgMaxN);

@@ -4,8 +4,8 @@
 // (hostcheck.cpp: hc_grammar_ty_planes, hc_grammar_bed_finish, hc_grammar_bed_plan), where the CPU tests hold it to numpy.
 //
 // GrammarGamma::TestCovariate (regression/GrammarGamma.cpp:122-152) needs of a column g only (g - gbar)'ty and
-// (g - gbar)'(g - gbar).  A mean-imputed column of PLINK codes (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing; hi = bit 1, lo = bit 0
-// of a pair) is g = c + mu m with c the calls (missing -> 0), m the missing indicator and mu = ac / called, and gbar = mu.  With
+// (g - gbar)'(g - gbar).  A mean-imputed column of PLINK codes (rvt_bed_codes.h; hi = bit 1, lo = bit 0 of a pair) is
+// g = c + mu m with c the calls (missing -> 0), m the missing indicator and mu = ac / called, and gbar = mu.  With
 // the 0 / 1 bit planes H = hi, L = lo, HL = hi & lo of a row:  c = H + HL,  m = L - HL,  so
 //     sum c ty = S_H + S_HL,    sum m ty = S_L - S_HL,    (g - gbar)'ty = (S_H + S_HL) + mu (S_L - S_HL - T),   T = sum ty,
 //     (g - gbar)'(g - gbar) = (called (n1 + 4 n2) - ac^2) / called,
@@ -13,6 +13,7 @@
 // eight base-128 digits (int8 each), and the S_X are exact integer sums per digit plane (the int8 matrix cores form them).
 #pragma once
 #include <stdint.h>
+#include "rvt_bed_codes.h"
 #include "rvt_special.h"
 
 namespace rvt {
@@ -97,16 +98,15 @@ RVT_HD double grammar_planes_value(const int64_t* x) {
 // (fam_single.hip.h).
 RVT_HD void grammar_bed_finish(long long n0, long long n1, long long n2, long long nm, const int64_t* S, const long long* T, int e,
                                double gamma, double ysy, int* ok, double* af, double* beta, double* beta_var, double* p) {
-  (void)nm;
-  const long long called = n0 + n1 + n2, ac = n1 + 2 * n2;
+  const BedSite site = bed_site(n0, n1, n2, nm);
+  const long long called = site.called, ac = site.ac;
   *af = called > 0 ? (double)ac / (2.0 * (double)called) : 0.0;
-  const int kinds = (n0 > 0 ? 1 : 0) + (n1 > 0 ? 1 : 0) + (n2 > 0 ? 1 : 0);
-  if (kinds < 2) {
+  if (!site.poly) {
     *ok = 0;
     *beta = *beta_var = *p = NAN;
     return;
   }
-  const double mu = (double)ac / (double)called;
+  const double mu = site.mean;
   int64_t xc[kGgPlanes], xm[kGgPlanes];
   for (int q = 0; q < kGgPlanes; ++q) {
     xc[q] = S[q] + S[2 * kGgPlanes + q];                               // sum c ty

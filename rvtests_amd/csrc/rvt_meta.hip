@@ -6,6 +6,7 @@
 #include "rvt_engine_int.h"
 #include "gemm_f64.hip.h"
 #include "band_rows.hip.h"
+#include "bed_expand.hip.h"
 #include "wald_logistic.hip.h"
 #include "burdencol_kernels.hip.h"
 #include "recode_kernels.hip.h"
@@ -1264,19 +1265,13 @@ int rvt_cov_band_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int H, int W, 
     br.ldk = ldk4;
     c->band_last_path = br.masked ? 24 : 21;
   } else {
-    unsigned long long* d_cnt_u = reinterpret_cast<unsigned long long*>(d_cnt);
-    HIP_TRY(c, hipMemsetAsync(d_cnt_u, 0, sizeof(long long) * cnt.size(), st));
+    rc = bed_piece_counts(c, st, d_rows, cb, N, W, reinterpret_cast<unsigned long long*>(d_cnt), nullptr, cnt.data());
+    if (rc) return rc;
     constexpr int kRows = 32768;  // rows per launch (gridDim.y)
-    for (int k0 = 0; k0 < W; k0 += kRows)
-      bed_row_counts(st, d_rows + (size_t)k0 * (size_t)cb, cb, N, std::min(kRows, W - k0), d_cnt_u + 4 * (size_t)k0);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(long long) * cnt.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, sync_stream(st));
     std::vector<double> mu((size_t)W);
-    for (int j = 0; j < W; ++j) {
+    for (int j = 0; j < W; ++j) {  // (a row without a missing call is its calls: mu = 0)
       const long long* q = &cnt[4 * (size_t)j];
-      const long long called = q[0] + q[1] + q[2];
-      mu[(size_t)j] = (q[3] > 0 && called > 0) ? (double)(q[1] + 2 * q[2]) / (double)called : 0.0;
+      mu[(size_t)j] = q[3] > 0 ? bed_site(q[0], q[1], q[2], q[3]).mean : 0.0;
     }
     HIP_TRY(c, hipMemcpyAsync(bw.d_mu_l, mu.data(), sizeof(double) * (size_t)W, hipMemcpyHostToDevice, st));
     HIP_TRY(c, sync_stream(st));  // (mu goes out of use on the host)
@@ -1534,9 +1529,9 @@ static int expand_packed_rows(rvt_ctx* c, size_t pitch, size_t rows_cap, const d
   double* d_mu = reinterpret_cast<double*>(c->d_colpack + pitch * rows_cap);
   int rc = small_h2d(c, d_mu, mu, sizeof(double) * (size_t)n);
   if (rc) return rc;
-  hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)n), dim3(256), 0, c->io_stream,
-                     reinterpret_cast<const unsigned char*>(c->d_colpack.get()), (long long)pitch, d_mu, (long long)N, (long long)ld,
-                     dG + (size_t)col0 * ld);
+  hipLaunchKernelGGL(bed_expand_columns_kernel<BedRowsAt>, dim3((unsigned)((N + 1023) / 1024), (unsigned)n), dim3(256), 0,
+                     c->io_stream, BedRowsAt{reinterpret_cast<const unsigned char*>(c->d_colpack.get()), (long long)pitch}, d_mu,
+                     (long long)N, (long long)ld, dG + (size_t)col0 * ld);
   HIP_TRY(c, hipGetLastError());
   return RVT_OK;
 }
@@ -1821,8 +1816,43 @@ void bed_row_counts(hipStream_t st, const unsigned char* d_rows, long long cb, l
 // (bed_expand_columns_kernel).  rvt_fam.hip's front stage over resident rows expands with it when U is column-compressed.
 void bed_rows_expand(hipStream_t st, const unsigned char* d_rows, long long cb, const double* d_mu, long long N, long long ld,
                      int n_rows, double* G) {
-  hipLaunchKernelGGL(bed_expand_columns_kernel, dim3((unsigned)((N + 1023) / 1024), (unsigned)n_rows), dim3(256), 0, st, d_rows,
-                     cb, d_mu, N, ld, G);
+  hipLaunchKernelGGL(bed_expand_columns_kernel<BedRowsAt>, dim3((unsigned)((N + 1023) / 1024), (unsigned)n_rows), dim3(256), 0, st,
+                     BedRowsAt{d_rows, cb}, d_mu, N, ld, G);
+}
+
+// The site pass's counts of n_rows consecutive rows (n0 n1 n2 missing per row) into d_cnt, which is zeroed here, in launches of
+// at most kBedCountRows rows (gridDim.y); with host or counts, bed_counts_host behind it.
+int bed_piece_counts(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, long long cb, long long N, long long n_rows,
+                     unsigned long long* d_cnt, std::vector<unsigned long long>* host, long long* counts) {
+  constexpr long long kBedCountRows = 32768;
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * (size_t)n_rows, st));
+  for (long long k0 = 0; k0 < n_rows; k0 += kBedCountRows)
+    bed_row_counts(st, d_rows + (size_t)k0 * (size_t)cb, cb, N, (int)std::min(kBedCountRows, n_rows - k0), d_cnt + 4 * (size_t)k0);
+  HIP_TRY(c, hipGetLastError());
+  return host || counts ? bed_counts_host(c, st, d_cnt, n_rows, host, counts) : RVT_OK;
+}
+
+// The counts of n_rows rows copied to the host, st waited for: into host (optional) and, as long long, into the caller's counts
+// (optional).  On its own where a caller queues its site kernel between the count and the copy.
+int bed_counts_host(rvt_ctx* c, hipStream_t st, const unsigned long long* d_cnt, long long n_rows,
+                    std::vector<unsigned long long>* host, long long* counts) {
+  std::vector<unsigned long long> own;
+  if (!host) host = &own;
+  host->resize(4 * (size_t)n_rows);
+  HIP_TRY(c, hipMemcpyAsync(host->data(), d_cnt, sizeof(unsigned long long) * host->size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, sync_stream(st));
+  if (counts)
+    for (size_t i = 0; i < host->size(); ++i) counts[i] = (long long)(*host)[i];
+  return RVT_OK;
+}
+
+// Resident rows have the pitch ceil(N / 4) of the N rvt_bed_alloc saw, which is the ordinary null model's when one is set: a
+// null model of another kind (`other`) with another N beside it means rows of another pitch.
+int bed_rows_check(rvt_ctx* c, const char* who, long long N, const char* other) {
+  if (c->have_null && c->nc.N != N)
+    return fail(c, RVT_E_STATE, "%s: the null model has N = %lld, the %s null model N = %lld (the resident rows have the former's pitch)",
+                who, (long long)c->nc.N, other, N);
+  return RVT_OK;
 }
 
 int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int coding, double* dG, int col0, long long* counts) {

@@ -415,7 +415,8 @@ int rvt_mt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, dou
   if (!c || !d_rows || V < 1 || !ustat || !vstat || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
   if (!c->have_mt) return fail(c, RVT_E_STATE, "no multiple-trait null model (rvt_mt_fit_null)");
   const int64_t N = c->mt_N, pitch = (N + 3) / 4;
-  if ((c->have_null && c->nc.N != N) || (!c->have_null && c->have_fam && c->fam_nc.N != N))
+  if (int rc = bed_rows_check(c, "rvt_mt_score_bed_dev", (long long)N, "multiple-trait")) return rc;
+  if (!c->have_null && c->have_fam && c->fam_nc.N != N)  // (rvt_bed_alloc then saw the family null model's N)
     return fail(c, RVT_E_STATE, "the multiple-trait null and the context's null model differ in N");
   hipSetDevice(c->device);
   int rc = rvt_sync(c);
@@ -451,7 +452,7 @@ int rvt_mt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, dou
   signed char* Bc = c->d_mt_B;
   signed char* Bm = c->d_mt_B + b_half;
   const std::vector<int> zero_exp((size_t)std::max(K, Vp), 0);
-  std::vector<unsigned long long> cnt(4 * (size_t)Vp);
+  std::vector<unsigned long long> cnt;
   std::vector<int> slot((size_t)Vp), idx((size_t)Vp);
   c->mt_ms[0] = c->mt_ms[1] = c->mt_ms[2] = 0.0;
   for (int64_t v0 = 0; v0 < V; v0 += kMtPiece) {
@@ -460,20 +461,18 @@ int rvt_mt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, dou
     const unsigned char* rows = d_rows + (size_t)v0 * (size_t)pitch;
     // ---- front stage: the counts of every row, its moments, the list of the rows with a missing call, c and the compact m --------
     double t0 = now_s();
-    HIP_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * 4 * (size_t)nv, st));
-    bed_row_counts(st, rows, pitch, N, nv, d_cnt);
+    rc = bed_piece_counts(c, st, rows, pitch, N, nv, d_cnt, nullptr, nullptr);
+    if (rc) return rc;
     hipLaunchKernelGGL(mt_bed_site_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, d_cnt, nv, d_mu, d_gg);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(cnt.data(), d_cnt, sizeof(unsigned long long) * 4 * (size_t)nv, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, sync_stream(st));
+    rc = bed_counts_host(c, st, d_cnt, nv, &cnt, counts ? counts + 4 * (size_t)v0 : nullptr);
+    if (rc) return rc;
     int nm = 0;  // rows of the piece with a missing call
     for (int h = 0; h < nv; ++h) {
       const bool miss = cnt[4 * (size_t)h + 3] != 0;
       slot[(size_t)h] = miss ? nm : -1;
       if (miss) idx[(size_t)nm++] = h;
     }
-    if (counts)
-      for (size_t i = 0; i < 4 * (size_t)nv; ++i) counts[4 * (size_t)v0 + i] = (long long)cnt[i];
     const int64_t nmpad = ((int64_t)nm + kRotBN - 1) / kRotBN * kRotBN;
     HIP_TRY(c, hipMemcpyAsync(d_slot, slot.data(), sizeof(int) * (size_t)nv, hipMemcpyHostToDevice, st));
     if (nm > 0) HIP_TRY(c, hipMemcpyAsync(d_idx, idx.data(), sizeof(int) * (size_t)nm, hipMemcpyHostToDevice, st));

@@ -6,6 +6,7 @@
 #define RVT_K_SPLIT
 #define RVT_K_STREAM
 #include "rvt_engine_int.h"
+#include "rvt_bed_codes.h"
 
 extern "C" {
 
@@ -885,7 +886,7 @@ __global__ __launch_bounds__(256) void bed_count_copy_rows_kernel(const BedRowRe
   const BedRowRef rr = rows[blockIdx.y];
   const long long i0 = (long long)blockIdx.x * kConsolChunk;
   const long long i1 = (i0 + kConsolChunk < N) ? i0 + kConsolChunk : N;
-  unsigned n1 = 0, n2 = 0, nm = 0;
+  int n[4] = {0, 0, 0, 0};  // calls of 0 / 1 / 2 / missing (the first is not used)
   if ((((N + 3) / 4) & 3) == 0 && (((unsigned long long)rr.src | (unsigned long long)rr.dst) & 3ull) == 0ull) {
     // rows of whole dwords that start on a 4-byte boundary (ceil(N/4) a multiple of 4, e.g. N = 500 000): a dword = 16 samples per
     // thread and trip instead of a byte — the pass moved 1.5 TB/s byte by byte.  Nothing outside the row is read; the samples of
@@ -895,28 +896,22 @@ __global__ __launch_bounds__(256) void bed_count_copy_rows_kernel(const BedRowRe
     for (long long w = (i0 >> 4) + threadIdx.x; 16 * w < i1; w += 256) {
       unsigned v = s4[w];
       const long long left = i1 - 16 * w;
-      if (left < 16) v &= (1u << (2 * left)) - 1u;
+      if (left < 16) v &= 3u * bed_live_pairs(left);  // (the copy holds 00 behind the piece's last sample; 00 counts nowhere)
       d4[w] = v;
-      const unsigned lo = v & 0x55555555u, hi = (v >> 1) & 0x55555555u;
-      n1 += __popc(hi & ~lo);
-      n2 += __popc(hi & lo);
-      nm += __popc(lo & ~hi);
+      bed_counts16(v, 0x55555555u, n);
     }
   } else {
     for (long long b = (i0 >> 2) + threadIdx.x; 4 * b < i1; b += 256) {
       unsigned v = rr.src[b];
       const long long left = i1 - 4 * b;
-      if (left < 4) v &= (1u << (2 * left)) - 1u;
+      if (left < 4) v &= 3u * bed_live_pairs(left);
       rr.dst[b] = (unsigned char)v;
-      const unsigned lo = v & 0x55u, hi = (v >> 1) & 0x55u;
-      n1 += __popc(hi & ~lo);
-      n2 += __popc(hi & lo);
-      nm += __popc(lo & ~hi);
+      bed_counts16(v, 0x55u, n);
     }
   }
-  s_n1[threadIdx.x] = n1;
-  s_n2[threadIdx.x] = n2;
-  s_nm[threadIdx.x] = nm;
+  s_n1[threadIdx.x] = (unsigned)n[1];
+  s_n2[threadIdx.x] = (unsigned)n[2];
+  s_nm[threadIdx.x] = (unsigned)n[3];
   __syncthreads();
   for (int off = 128; off > 0; off >>= 1) {
     if ((int)threadIdx.x < off) {

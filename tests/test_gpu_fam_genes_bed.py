@@ -14,7 +14,7 @@ from test_fam_cpu import make_family_case
 from test_gpu_fam import device_null_for_oracle
 from test_gpu_fam_bed import install_family, resident
 from test_gpu_kinship_bed import calls as kinship_calls, with_null
-from test_gpu_kinship_families import null_for_layout, p_close, rel
+from test_gpu_kinship_families import null_for_layout, p_close, rel, spd_cohort
 from test_gpu_single_fam import grm_case
 
 pytestmark = pytest.mark.gpu
@@ -153,6 +153,65 @@ def test_dense_form_against_the_block_route_and_the_oracle(eng, N, d):
         if b.famskat_ok:
             assert rel(a.famskat_Q, b.famskat_Q, 1e-7)
     check_oracle(alone, order, raw, X, y, U, S, device_null_for_oracle(nul, d), tests=16)
+
+
+# ---- 2b. one gene whose kept rows are not consecutive, rows at every byte alignment ------------------------------------------------
+def scattered_families(N, seed):
+    """Nuclear families of 4 (make_family_case's block) whose members are scattered over the sample order, singletons for the
+    rest: (U, S, X, y) with four non-zeros per eigenvector at rows far apart — the column-compressed form of rvt_set_kinship."""
+    rng = np.random.default_rng(seed)
+    perm = rng.permutation(N)
+    s4, u4 = np.linalg.eigh(np.array([[1, 0, .5, .5], [0, 1, .5, .5], [.5, .5, 1, .5], [.5, .5, .5, 1]]))
+    U, S = np.zeros((N, N)), np.ones(N)
+    for f in range(N // 4):
+        U[np.ix_(perm[4 * f:4 * f + 4], np.arange(4 * f, 4 * f + 4))] = u4
+        S[4 * f:4 * f + 4] = s4
+    for k in range(4 * (N // 4), N):
+        U[perm[k], k] = 1.0
+    U = U.astype(np.float32).astype(np.float64)
+    S = S.astype(np.float32).astype(np.float64)
+    X = np.column_stack([np.ones(N), rng.standard_normal(N)])
+    y = 0.3 * X[:, 1] + (U * np.sqrt(0.4 * S)) @ rng.standard_normal(N) + np.sqrt(0.6) * rng.standard_normal(N)
+    return U, S, X, y
+
+
+@pytest.mark.parametrize("form", ["family", "dense", "gather"])
+def test_kept_rows_around_a_dropped_row_at_every_row_alignment(eng, form):
+    """N = 515 (pitch 129) and the gene of the four hand-made rows alone: rows 0, 1 and 3 are kept around the monomorphic row 2,
+    rows 1 and 3 are flipped, and every kept row has missing calls (row 3 in its last byte only).  The list of kept rows is
+    what the rotation, the expansion (gather form: N mod 4 = 3, so its last thread stores sample by sample) and the collapse
+    read; the block route on the uploaded imputed columns is the reference."""
+    N = 515
+    raw = np.asfortranarray(cases.hand_rows(N, 5150))
+    gene = ("hand", 0, raw.shape[1])
+    flip, keep, mu = cases.decisions(raw)
+    assert keep.tolist() == [True, True, False, True] and flip[keep].tolist() == [False, True, True]
+    assert ((raw < 0).sum(0) > 0).all() and (raw[:4 * (N // 4), 3] >= 0).all()
+    if form == "family":
+        c = spd_cohort([64, 1, 33, 5, 64, 3, 64, 1, 64, 64, 64, 33, 55], 61)
+        assert c.N == N
+        rng = np.random.default_rng(62)
+        X = np.column_stack([np.ones(N), rng.standard_normal(N)])
+        y = 0.3 * X[:, 1] + rng.standard_normal(N)
+        null_for_layout(eng, N)
+        eng.kinship_decompose_families(c.fam_ptr, c.members, c.flat(c.K), install=True)
+    elif form == "dense":
+        N, K, U, S, X, y = grm_case(N, 3, 41 + N)
+        null_for_layout(eng, N)
+        eng.set_kinship(U, S)
+        assert eng.kinship_structure() == 1.0
+    else:
+        U, S, X, y = scattered_families(N, 63)
+        null_for_layout(eng, N)
+        eng.set_kinship(U, S)
+        assert eng.kinship_structure() != 1.0                 # column-compressed U: the kept rows are expanded on the device
+    eng.fit_fam_null(X, y)
+    bed, blk, order = both_routes(eng, raw, [gene])
+    assert bed[0].n_variants == 4 and bed[0].n_poly == 3
+    assert blk[0].famskat_ok == 1 and blk[0].famcmc_ok + blk[0].famzeg_ok >= 1   # (the comparison below is not empty)
+    if form == "family":
+        assert bits(bed[0]) == bits(blk[0])                   # the tile holds the doubles the block route reads
+    check_close(bed, blk)
 
 
 # ---- 3. column-compressed U with scattered supports ------------------------------------------------------------------------------

@@ -165,6 +165,30 @@ def test_rows_without_a_missing_call_take_one_product(base):
     _compare_with_ring(out, ring_out, scale)
 
 
+def test_a_window_that_is_the_whole_matrix_at_every_row_alignment():
+    """N = 515 (pitch 129: consecutive rows start at all four byte alignments), the window is the whole matrix — its first row is
+    the allocation's first bytes, its last row ends at the matrix's last byte and holds a missing call in sample N - 1: the
+    front stage's loads of four bytes at the edges of what it may touch."""
+    N, d, V, halo = 515, 2, 37, 8
+    raw = cases.calls(N, V, seed=515, missing=0.02)
+    raw[N - 1, V - 1] = -9.0
+    X, y, res, v, s2 = cases.null_model(N, d, 0, seed=516)
+    eng = _engine()
+    try:
+        eng.set_null(0, X, res, v, s2)
+        d_bed = eng.bed_alloc(V)
+        eng.bed_upload(d_bed, 0, cases.pack(raw))
+        band, xz, zz, poly, cnt = eng.cov_band_bed(d_bed, V, V, halo)
+        assert eng.cov_band_last_path() == 24
+        eng.bed_free(d_bed)
+    finally:
+        eng.close()
+    G = cases.imputed(raw)
+    assert np.array_equal(cnt, cases.counts(raw)) and cnt[V - 1, 3] == 1
+    assert np.array_equal(poly, cases.polymorphic(G))
+    _check_against_oracle(band, xz, zz, poly, _oracle(G, X, y, 0, halo), halo)
+
+
 @pytest.mark.parametrize("var, value", [("RVT_BAND_PASS", "256"), ("RVT_BAND_SLICES", "3")])
 def test_pass_and_slice_splits_give_the_same_bits(base, monkeypatch, var, value):
     monkeypatch.setenv(var, value)
