@@ -376,8 +376,8 @@ int rvt_cov_band(rvt_ctx* ctx, const double* dG, int ring_cols, int col0, int H,
  * products; 20 resident rows through the fp64 band (a binary trait, RVT_METACOV_FP64=1). */
 int rvt_cov_band_last_path(rvt_ctx* ctx);
 /* rvt_cov_band for a window that is W consecutive rows of a RESIDENT .bed matrix (rvt_bed_alloc): no ring, no fp64 column, no
- * PCIe crossing.  d_rows is the device address of the window's first row; a row is ceil(N / 4) bytes (N the null model's sample
- * count), rows follow each other without padding and may start at any byte; codes 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing
+ * PCIe crossing.  d_rows is the device address of the window's first row (the convention of resident rows: rvt_bed_alloc; the
+ * ordinary null model's N); codes 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing
  * (libVcf/PlinkInputFile.cpp:24-47); the padding bits of a row's last byte are never counted and never enter a product.
  * Heads = rows [0, H), markers = rows [0, W), W >= H (W is clipped to H + halo).  The columns are the rows with missing calls
  * imputed to the mean of the called ones, mu = (n1 + 2 n2) / (n0 + n1 + n2) (src/DataConsolidator.cpp:217-245), as
@@ -472,8 +472,8 @@ int rvt_mt_last_timing(rvt_ctx* ctx, double* ms3);
  * TestCovariateBlock (regression/FastMultipleTraitLinearRegressionScoreTest.cpp:391-470) on the columns a caller would have
  * uploaded — the calls of the 2-bit codes (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing) with missing imputed to the mean of the
  * called ones (src/DataConsolidator.cpp:217-245; a row with no called sample: mu = 0) — formed from the codes where they lie;
- * no variant exists as doubles.  The pitch is ceil(N / 4) bytes, N the multiple-trait null's sample count; a row may start at
- * any byte, the padding pairs of a row's last byte are ignored whatever they hold, and rows are taken as stored (not flipped),
+ * no variant exists as doubles.  The rows follow the convention of resident rows (rvt_bed_alloc) with the multiple-trait
+ * null's N; the padding pairs of a row's last byte are ignored whatever they hold, and rows are taken as stored (not flipped),
  * as rvt_mt_score_block takes its columns.  A context whose only model is the multiple-trait null can allocate and fill the
  * matrix (rvt_bed_alloc, rvt_bed_upload).  Any V: the rows are walked in pieces of 1024.
  * The imputed column is exactly g = c + mu m, c = the calls with missing -> 0, m = the missing indicator, mu = (n1 + 2 n2) /
@@ -726,7 +726,7 @@ int rvt_kinship_decompose_families(rvt_ctx* ctx, int64_t N, int64_t n_fam, const
                                    const float* K_blocks, float* U_blocks_out, float* S_out, int install,
                                    rvt_decompose_info* info);
 /* The empirical kinship of `vcf2kinship --ibs` / `--bn` from V consecutive rows of a resident .bed matrix (rvt_bed_alloc /
- * rvt_bed_upload; d_rows = d_bed + first_row * ceil(N/4), N = the installed null model's sample count): the step in front of
+ * rvt_bed_upload; the convention of resident rows there, with the ordinary null model's N): the step in front of
  * rvt_kinship_decompose.  Synchronous.  K_out: N x N doubles in host memory (need not be registered), symmetric, every entry
  * written.
  * Sites are filtered as the tool's site loop does (vcfUtils/vcf2kinship.cpp:943-960), in its order, and a site is counted in
@@ -937,16 +937,34 @@ int rvt_submit_gene_bed(rvt_ctx* ctx, int64_t gene_id, int M, const unsigned cha
  * libVcf/PlinkInputFile.cpp:24-47, and the PCIe crossing of rvt_submit_gene_bed): 500 000 samples x 2 000 000 variants of 2-bit
  * codes are 250 GB — an exome-scale cohort fits the 288 GB of one MI355X, and a gene is then named by the device address of its
  * first row.
- *   rvt_bed_alloc            n_variants rows of ceil(N/4) bytes, the FILE's layout (no padding between rows; the three magic
- *                            bytes of the file are not part of it); N is the null model's sample count
- *   rvt_bed_upload           rows [first_variant, first_variant + n_variants) from host memory (returns when they are there)
- *   rvt_submit_gene_bed_dev  like rvt_submit_gene_bed with d_rows = d_bed + first_row * ceil(N/4): M consecutive rows.  The
+ * THE CONVENTION OF RESIDENT ROWS, for every call that takes a d_rows.  Row r of a matrix lies at d_bed + r * pitch, pitch =
+ * ceil(N / 4) bytes: the FILE's layout, no padding between rows (the three magic bytes of the file are not part of it), so a row
+ * may start at any byte.  N is the sample count the matrix was SIZED for: the ordinary null model's at rvt_bed_alloc, or the
+ * multiple-trait null's in a context that has no ordinary one.  A call reads its rows at the pitch of the null model it consumes
+ * (each call says which), and the context keeps a record of every matrix it allocated — base, n_variants, N, pitch — against
+ * which the rows of a call are checked on the host, before any device work and before an output is written:
+ *   d_rows inside a matrix of this context   the matrix was sized for another N than the consuming model's: RVT_E_STATE (so a
+ *                            matrix is never re-read at another pitch after rvt_set_null / rvt_fit_null with another N: fit the
+ *                            old N again, or allocate and upload anew); d_rows not on a row boundary, or the call's rows (V, a
+ *                            gene's M, W of a window) running past the last row: RVT_E_INVALID.  A call that names several
+ *                            genes checks all of them first: a refused call queues and computes nothing.
+ *   any other d_rows         (another context's matrix, a caller's own allocation) taken on trust at the pitch of the
+ *                            consuming model's N, as a block that is not of rvt_block_alloc is.
+ * Whatever d_rows is, an ordinary null model of another N beside the consuming model is RVT_E_STATE.  Behind the last row an
+ * allocation has 16 bytes of slack, which some kernels' aligned loads may read and no call interprets; a caller's own matrix
+ * needs the same.
+ *   rvt_bed_alloc            n_variants rows; RVT_E_STATE without an ordinary or a multiple-trait null model
+ *   rvt_bed_upload           rows [first_variant, first_variant + n_variants) from host memory (returns when they are there);
+ *                            d_bed a matrix of this context: first_variant + n_variants beyond its rows is RVT_E_INVALID
+ *   rvt_submit_gene_bed_dev  like rvt_submit_gene_bed with d_rows = d_bed + first_row * pitch: M consecutive rows.  The
  *                            rows are read when the gene is computed: they must stay unchanged until its record has been
  *                            collected.  Same records as rvt_submit_gene_bed of the same rows to 1e-11 relative (SKAT-O's p to
  *                            1e-6): resident genes form G'[X | rr] on the int8 matrix cores from digit planes of the null
  *                            tile; allele frequencies, and genes that have to be expanded, bit for bit.
  *   rvt_submit_genes         kind 7 = the same, several genes per call (data[g] = device address of gene g's first row)
- *   rvt_bed_free             waits for queued genes, then frees */
+ *   rvt_bed_free             waits for queued genes, then frees; d_bed must be NULL (nothing happens) or the address
+ *                            rvt_bed_alloc of THIS context returned and not yet freed: anything else is RVT_E_INVALID and
+ *                            nothing is freed.  rvt_destroy frees no matrix. */
 int rvt_bed_alloc(rvt_ctx* ctx, int64_t n_variants, unsigned char** d_bed);
 int rvt_bed_upload(rvt_ctx* ctx, unsigned char* d_bed, int64_t first_variant, int64_t n_variants, const unsigned char* rows);
 int rvt_bed_free(rvt_ctx* ctx, unsigned char* d_bed);
@@ -983,8 +1001,8 @@ int rvt_bed_recode_block(rvt_ctx* ctx, const unsigned char* d_rows, int V, int c
  * regression/FastLMM.cpp:215-247, and FastLMM::FastGetAF, :400-424) and of rvt_lrt_block_fam (SingleVariantFamilyLRT,
  * src/Model.h:620-712; FastLMM.cpp:150-212 and :362-400) on the columns a caller would have uploaded — the calls of
  * libVcf/PlinkInputFile.cpp:24-47 (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing) with missing imputed to the mean of the called ones
- * (src/DataConsolidator.cpp:217-245) — computed from the 2-bit rows where they lie.  The rows have the pitch ceil(N / 4) bytes,
- * N the family null model's sample count; they start at any byte, and the padding bits of a row's last byte are ignored whatever
+ * (src/DataConsolidator.cpp:217-245) — computed from the 2-bit rows where they lie.  The rows follow the convention of
+ * resident rows (rvt_bed_alloc) with the family null model's N; the padding bits of a row's last byte are ignored whatever
  * they hold.  One front stage serves both calls, at most RVT_MAX_VARIANTS rows at a time: the counts per row give the fill value
  * mu = (n1 + 2 n2) / (N - missing), the column sum n1 + 2 n2 + missing mu and the polymorphic flag (at least two of n0, n1, n2
  * non-zero; a row with no called sample is monomorphic, ok = 0, and is rotated with mu = 0), and the rotation U'g goes by the
@@ -1010,11 +1028,11 @@ int rvt_lrt_bed_dev_fam(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, in
                         double* alt_loglik, double* pvalue, long long* counts);
 /* famGrammarGamma from rows of a resident .bed matrix: rvt_grammar_block's five columns (SingleVariantFamilyGrammarGamma,
  * src/Model.h:714-805; GrammarGamma::TestCovariate, regression/GrammarGamma.cpp:122-152) for V consecutive rows starting at the
- * device address d_rows, after rvt_fit_grammar_null.  The pitch is ceil(N / 4) bytes, N the GrammarGamma null model's sample
- * count; a row may start at any byte, the rows are taken as stored (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing), the padding pairs
+ * device address d_rows, after rvt_fit_grammar_null.  The convention of resident rows (rvt_bed_alloc) with the GrammarGamma null
+ * model's N; the rows are taken as stored (00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing), the padding pairs
  * of a row's last byte are ignored and missing calls are imputed to the mean of the row's called samples
  * (src/DataConsolidator.cpp:217-245): the results are those of rvt_grammar_block on the column a caller would have uploaded.
- * No byte at or behind d_rows + V ceil(N / 4) is read.  With g = c + mu m (c the calls, m the missing indicator, mu = ac / called)
+ * No byte at or behind the end of the V rows is read.  With g = c + mu m (c the calls, m the missing indicator, mu = ac / called)
  * the centred g'ty and g'g need only the four counts of a row and the sums of ty over three bit planes of its codes; ty is held
  * as eight int8 digit planes (56 bits below its largest entry) and the sums are exact integer products on the int8 matrix
  * cores, N / 4 bytes read per row.  Exact: the counts and the integer sums — a row's results do not depend on V, on where the
@@ -1034,10 +1052,9 @@ int rvt_grammar_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, in
 /* The gene-based tests for related samples from rows of a resident .bed matrix: rvt_run_fam_tests (FamSkatTest,
  * src/Model.h:3048-3145; FamCMC, src/Model.h:2261-2376; FamZeggini, src/Model.h:2378-2492; the burden tests' collapse and
  * FastLMM::TestCovariate's SCORE branch, regression/FastLMM.cpp:215-247, and FastLMM::GetAF, :356-398) with gene g given as M[g]
- * consecutive rows starting at the device address d_rows[g] — the convention of rvt_submit_gene_bed_dev.  The pitch is
- * ceil(N / 4) bytes, N the family null model's sample count; a row may start at any byte, the padding pairs of a row's last
- * byte are ignored.  Genes may come in any order, overlap and share rows.  tests is a mask out of RVT_TEST_FAMSKAT |
- * RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI, and the records (n_variants, n_poly, famskat_*, famcmc_*, famzeg_*, skat_nlambda,
+ * consecutive rows starting at the device address d_rows[g], as rvt_submit_gene_bed_dev names a gene — the convention of
+ * resident rows (rvt_bed_alloc) with the family null model's N; the padding pairs of a row's last byte are ignored.  Genes may
+ * come in any order, overlap and share rows.  tests is a mask out of RVT_TEST_FAMSKAT | RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI, and the records (n_variants, n_poly, famskat_*, famcmc_*, famzeg_*, skat_nlambda,
  * davies_terms, status) equal those of rvt_run_fam_tests on the columns a caller would have uploaded for these rows: the calls
  * 00 -> 0, 10 -> 1, 11 -> 2, 01 -> missing with missing imputed to the mean of the called ones (src/DataConsolidator.cpp:217-245).
  * The flip to the minor allele and the drop of monomorphic rows (src/DataConsolidator.cpp:46-69,94-142) are decided from the
@@ -1047,8 +1064,8 @@ int rvt_grammar_bed_dev(rvt_ctx* ctx, const unsigned char* d_rows, int64_t V, in
  * column-compressed U: expanded on the device — and the CMC / Zeggini columns are collapsed from the codes.  No variant exists as
  * doubles before U'G.  Everything behind the rotation is rvt_run_fam_tests' own tail.
  * RVT_E_INVALID: a null argument (gene_ids excepted), a null d_rows entry, a mask that is empty or has another bit.
- * RVT_E_TOO_LARGE: M[g] < 1 or M[g] > RVT_MAX_VARIANTS.  RVT_E_STATE: no family null model, or an ordinary null model of another
- * N is installed (the rows would have another pitch).  A refused call writes nothing; n_genes == 0 returns RVT_OK.  Synchronous. */
+ * RVT_E_TOO_LARGE: M[g] < 1 or M[g] > RVT_MAX_VARIANTS.  RVT_E_STATE: no family null model; and, with RVT_E_INVALID, what the
+ * convention refuses, for any gene of the call.  A refused call writes nothing; n_genes == 0 returns RVT_OK.  Synchronous. */
 int rvt_run_fam_tests_bed_dev(rvt_ctx* ctx, int n_genes, const unsigned char* const* d_rows, const int* M, const int64_t* gene_ids,
                               uint32_t tests, rvt_gene_result* out);
 

@@ -24,6 +24,7 @@
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
 #include <immintrin.h>
 #endif
+#include "rvt_bed_codes.h"
 
 namespace rvt {
 
@@ -409,7 +410,7 @@ inline bool pack_column_i8(const signed char* g, size_t n, unsigned char* out, s
       if (!pack32_i8_avx2(g + i, out + i / 4)) return false;
 #endif
   if (i < n && !pack_i8_scalar(g + i, n - i, out + i / 4)) return false;
-  const size_t o = (n + 3) / 4;
+  const size_t o = (size_t)bed_pitch((long long)n);
   if (o < pitch) std::memset(out + o, 0, pitch - o);
   return true;
 }

@@ -444,6 +444,12 @@ void hc_bed_load16(const unsigned char* buf, long long off, long long base, long
   rvt::bed_load16(buf + off, buf + base, buf + end, w);
   for (int k = 0; k < 4; ++k) w4[k] = w[k];
 }
+// V rows at address `at` in the matrix at `base`: the first row's index, or -1 outside, -2 off a row boundary, -3 rows leave it
+long long hc_bed_span(unsigned long long base, long long n_variants, long long pitch, unsigned long long at, long long V) {
+  return rvt::bed_span(base, n_variants, pitch, at, V);
+}
+long long hc_bed_pitch(long long N) { return rvt::bed_pitch(N); }
+int hc_bed_slack(void) { return rvt::kBedSlackBytes; }
 int hc_band_tile_of(int h, int j, int W, int halo) { return rvt::band_tile_of(h, j, W, halo); }
 long long hc_band_slices(int n_tiles, long long chunks, long long max_part_bytes) {
   return rvt::band_slices(n_tiles, chunks, (size_t)max_part_bytes);

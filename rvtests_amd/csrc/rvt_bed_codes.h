@@ -9,8 +9,10 @@
 //
 // Here: the value of a code, the site pass on the four counts of a row (BedSite), the live masks, the population counts, the
 // spread of a code byte into byte lanes and the loaders of 4 and 16 bytes of codes from any byte address.  (The nibble form of
-// MetaCov's MXFP4 band, with its own per-nibble mask bed_live_mask, is rvt_bed_nibbles.h; the kinship tiles read nine aligned
-// words into the slack rvt_bed_alloc leaves behind the matrix, a contract of their own: kin_stage, kinship_kernels.hip.h.)
+// MetaCov's MXFP4 band, with its own per-nibble mask bed_live_mask, is rvt_bed_nibbles.h.)  The kinship tiles read nine aligned
+// words per row, which may reach past the last row's end (kin_stage, kinship_kernels.hip.h): rvt_bed_alloc leaves kBedSlackBytes
+// behind the matrix for them.  Also here, for the host: the pitch (bed_pitch) and where V rows at an address lie in a matrix of
+// known extent (bed_span) — what the engine's record of a matrix (rvt_ctx::BedMatrix) and bed_rows_span are made of.
 // No HIP types in any signature: compiled by hipcc for the kernels and by g++ for the harness (hostcheck.cpp) and for
 // tools/bed_codes_check.cpp.
 #pragma once
@@ -25,6 +27,23 @@
 #endif
 
 namespace rvt {
+
+// bytes of a row of N samples: the one place that writes it
+constexpr long long bed_pitch(long long N) { return (N + 3) / 4; }
+// bytes rvt_bed_alloc leaves behind the last row (kin_stage's aligned words)
+constexpr int kBedSlackBytes = 16;
+
+// Where V rows at address `at` lie in the matrix of n_variants rows of `pitch` bytes at `base` (addresses as integers): the index
+// of the first row, or one of the three refusals.  In row indices throughout — V is never multiplied by the pitch, so any V of
+// an int64_t caller is answered without overflow.  The slack is not part of the rows: an address in it is outside.
+constexpr long long kBedSpanOutside = -1, kBedSpanOffRow = -2, kBedSpanLeaves = -3;
+inline long long bed_span(uint64_t base, long long n_variants, long long pitch, uint64_t at, long long V) {
+  if (at < base || pitch < 1) return kBedSpanOutside;
+  const uint64_t off = at - base, first = off / (uint64_t)pitch;
+  if (first >= (uint64_t)n_variants) return kBedSpanOutside;
+  if (off % (uint64_t)pitch != 0) return kBedSpanOffRow;
+  return V > n_variants - (long long)first ? kBedSpanLeaves : (long long)first;
+}
 
 // the value of the 2-bit code q with `fill` for a missing call
 RVT_BC_HD double bed_value(unsigned q, double fill) { return q == 0u ? 0.0 : (q == 2u ? 1.0 : (q == 3u ? 2.0 : fill)); }

@@ -384,6 +384,12 @@ struct rvt_ctx {
   uint64_t null_gen = 0;          // counts rvt_set_null / rvt_fit_null: a column cache made under another model is not used
   DevBuf<double> d_cc_part;    // slice partials of the one-column pass (64 slices x (RVT_MAX_COV + 3))
   std::unordered_map<const double*, ColKind> col_kind;
+  // What the engine knows about a resident .bed matrix of rvt_bed_alloc, by base address (ordered: the rows of a call lie
+  // anywhere inside a matrix, bed_rows_span looks up by containment).  rvt_bed_free drops the record; rvt_destroy frees no matrix.
+  struct BedMatrix {
+    int64_t n_variants, N, pitch;  // rows; the N they were sized for; bed_pitch(N)
+  };
+  std::map<const unsigned char*, BedMatrix> bed_mats;
   // VCF text front end (vcf_kernels.hip.h)
   char* d_vcf_text = nullptr;   // the text / block buffer of the gene being submitted: aliases text_buf[text_cur]
   static constexpr int kTextBufs = 3;  // ring: the copies of gene g + 1 run while the decode kernels of gene g read theirs
@@ -915,9 +921,13 @@ RVT_INTERNAL int bed_piece_counts(rvt_ctx* c, hipStream_t st, const unsigned cha
 // the counts of n_rows rows copied to the host and st waited for: into host (optional) and, as long long, into counts (optional)
 RVT_INTERNAL int bed_counts_host(rvt_ctx* c, hipStream_t st, const unsigned long long* d_cnt, long long n_rows,
                                  std::vector<unsigned long long>* host, long long* counts);
-// "the rows handed to `who` have the pitch ceil(N / 4) of this null model's N": the context's ordinary null model, if one is set
-// and rvt_bed_alloc saw it, has the same N (its name for the other one: `other`)
-RVT_INTERNAL int bed_rows_check(rvt_ctx* c, const char* who, long long N, const char* other);
+// The one question every call over resident rows asks before any device work (check_columns' counterpart for rows): may
+// `who`, which consumes null model `model`, read V rows at d_rows, and at what pitch?  Rows inside a matrix the
+// engine knows (rvt_ctx::bed_mats): sized for the model's N, on a row boundary, inside the matrix; the pitch is the record's.
+// A pointer it does not know (another context's matrix, a caller's allocation) is taken on trust at bed_pitch of the model's N,
+// as check_columns takes a block.  d_rows == NULL, V = 0: the state alone.
+enum class BedModel { kNull, kFam, kMt, kGrammar };  // the ordinary, family, multiple-trait, GrammarGamma null model
+RVT_INTERNAL int bed_rows_span(rvt_ctx* c, const char* who, const unsigned char* d_rows, int64_t V, BedModel model, int64_t* pitch);
 // n_rows rows of a resident .bed matrix as fp64 columns (leading dimension ld), missing -> d_mu[row] (bed_expand_columns_kernel)
 RVT_INTERNAL void bed_rows_expand(hipStream_t st, const unsigned char* d_rows, long long cb, const double* d_mu, long long N,
                                   long long ld, int n_rows, double* G);

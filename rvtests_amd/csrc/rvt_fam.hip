@@ -1657,10 +1657,10 @@ struct FamBedPiece {
   int* poly;
 };
 
-// the state both calls need
-int fam_bed_check(rvt_ctx* c, const char* who) {
+// the state every call here needs, and its V rows at d_rows (bed_rows_span): *cb = their pitch
+int fam_bed_check(rvt_ctx* c, const char* who, const unsigned char* d_rows, int64_t V, int64_t* cb) {
   if (!c->have_fam) return fail(c, RVT_E_STATE, "%s: rvt_set_kinship + rvt_fit_fam_null first", who);
-  return bed_rows_check(c, who, (long long)c->fam_nc.N, "family");
+  return bed_rows_span(c, who, d_rows, V, BedModel::kFam, cb);
 }
 
 int fam_bed_ws(rvt_ctx* c, hipStream_t st, FamBedPiece* p) {
@@ -1678,13 +1678,14 @@ int fam_bed_ws(rvt_ctx* c, hipStream_t st, FamBedPiece* p) {
   return RVT_OK;
 }
 
-// The front stage of both calls: n <= RVT_MAX_VARIANTS consecutive rows -> what raw_colstat_kernel + rotate_columns give for
+// The front stage of both calls: n <= RVT_MAX_VARIANTS consecutive rows, cb bytes apart -> what raw_colstat_kernel + rotate_columns give for
 // the imputed fp64 columns of the same calls: the rotated columns in c->d_Gt (leading dimension fam_nc.ld, rows N .. ld - 1
 // zero), their raw sums in p.cs and polymorphic flags in p.poly.  counts (host, 4 n entries, optional): n0 n1 n2 missing per row.
 // The rotation goes by the installed form of U (fam_bed_kernels.hip.h); enqueued on st, which is synchronised on the way (the
 // counts decide on the host whether the piece has a missing call at all).
-int fam_bed_front(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int n, const FamBedPiece& p, long long* counts) {
-  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld, cb = (N + 3) / 4;
+int fam_bed_front(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int64_t cb, int n, const FamBedPiece& p,
+                  long long* counts) {
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
   // 1. the site pass over the codes
   int rc = bed_piece_counts(c, st, d_rows, cb, N, n, p.cnt, nullptr, nullptr);
   if (rc) return rc;
@@ -1742,19 +1743,19 @@ int fam_bed_front(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int n
 int rvt_score_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int binary, int* ok, double* ustat, double* vstat,
                           double* af, double* pvalue, long long* counts) {
   if (!c || !d_rows || V < 1 || !ok || !ustat || !vstat || !af || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
-  int rc = fam_bed_check(c, "rvt_score_bed_dev_fam");
+  int64_t cb = 0;
+  int rc = fam_bed_check(c, "rvt_score_bed_dev_fam", d_rows, V, &cb);
   if (rc) return rc;
   hipSetDevice(c->device);
   rc = rvt_sync(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
-  const size_t cb = (size_t)((c->fam_nc.N + 3) / 4);
   FamBedPiece p;
   rc = fam_bed_ws(c, st, &p);
   if (rc) return rc;
   for (int64_t v0 = 0; v0 < V; v0 += RVT_MAX_VARIANTS) {
     const int n = (int)std::min<int64_t>(RVT_MAX_VARIANTS, V - v0);
-    rc = fam_bed_front(c, st, d_rows + cb * (size_t)v0, n, p, counts ? counts + 4 * v0 : nullptr);
+    rc = fam_bed_front(c, st, d_rows + (size_t)cb * (size_t)v0, cb, n, p, counts ? counts + 4 * v0 : nullptr);
     if (rc) return rc;
     HIP_TRY(c, sync_stream(st));
     CovOut co;
@@ -1782,13 +1783,13 @@ int rvt_lrt_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int*
                         double* alt_loglik, double* pvalue, long long* counts) {
   if (!c || !d_rows || V < 1 || !ok || !af || !null_loglik || !alt_loglik || !pvalue)
     return fail(c, RVT_E_INVALID, "bad arguments");
-  int rc = fam_bed_check(c, "rvt_lrt_bed_dev_fam");
+  int64_t cb = 0;
+  int rc = fam_bed_check(c, "rvt_lrt_bed_dev_fam", d_rows, V, &cb);
   if (rc) return rc;
   hipSetDevice(c->device);
   rc = rvt_sync(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
-  const size_t cb = (size_t)((c->fam_nc.N + 3) / 4);
   FamBedPiece p;
   LrtWs w;
   rc = fam_bed_ws(c, st, &p);
@@ -1796,7 +1797,7 @@ int rvt_lrt_bed_dev_fam(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int*
   if (rc) return rc;
   for (int64_t v0 = 0; v0 < V; v0 += RVT_MAX_VARIANTS) {
     const int n = (int)std::min<int64_t>(RVT_MAX_VARIANTS, V - v0);
-    rc = fam_bed_front(c, st, d_rows + cb * (size_t)v0, n, p, counts ? counts + 4 * v0 : nullptr);
+    rc = fam_bed_front(c, st, d_rows + (size_t)cb * (size_t)v0, cb, n, p, counts ? counts + 4 * v0 : nullptr);
     if (!rc) rc = lrt_piece(c, st, w, n, p.poly, ok + v0, af + v0, null_loglik + v0, alt_loglik + v0, pvalue + v0);
     if (rc) return rc;
   }
@@ -1816,33 +1817,45 @@ struct FamGenesFront {        // what steps 1-2 leave for fam_tests_tail
 };
 }  // namespace
 
-// steps 1-2: the checks, the records' initialisation and the front stage proper; *run = whether a tail is left to run (n > 0 and
-// a kept row somewhere)
-static int fam_genes_bed_front(rvt_ctx* c, int n, const unsigned char* const* d_rows, const int* Ms, const int64_t* ids,
-                               uint32_t tests, rvt_gene_result* out, FamGenesFront* F, bool* run) {
-  *run = false;
+// The checks of a list call, all of them before any device work: the arguments, the state, the rows of EVERY gene (a refused
+// call starts nothing); *cb = the rows' pitch.
+static int fam_genes_bed_check(rvt_ctx* c, int n, const unsigned char* const* d_rows, const int* Ms, uint32_t tests,
+                               rvt_gene_result* out, int64_t* cb) {
   if (!c || n < 0 || (n > 0 && (!d_rows || !Ms || !out))) return fail(c, RVT_E_INVALID, "bad batch arguments");
   if (!(tests & (RVT_TEST_FAMSKAT | RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI)) ||
       (tests & ~(RVT_TEST_FAMSKAT | RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI)))
     return fail(c, RVT_E_INVALID, "rvt_run_fam_tests_bed_dev takes the FAMSKAT / FAMCMC / FAMZEGGINI bits");
   for (int g = 0; g < n; ++g)
     if (!d_rows[g]) return fail(c, RVT_E_INVALID, "gene %d: null row address", g);
-  int rc = fam_bed_check(c, "rvt_run_fam_tests_bed_dev");
-  if (rc) return rc;
+  if (int rc = fam_bed_check(c, "rvt_run_fam_tests_bed_dev", nullptr, 0, cb)) return rc;
+  size_t tot = 0;
+  for (int g = 0; g < n; ++g) {
+    if (Ms[g] < 1 || Ms[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_TOO_LARGE, "gene %d: M=%d", g, Ms[g]);
+    tot += (size_t)Ms[g];
+  }
+  if (tot > (size_t)INT32_MAX) return fail(c, RVT_E_TOO_LARGE, "%zu rows in one call", tot);
+  for (int g = 0; g < n; ++g)
+    if (int rc = fam_bed_check(c, "rvt_run_fam_tests_bed_dev", d_rows[g], Ms[g], cb)) return rc;
+  return RVT_OK;
+}
+
+// steps 1-2 of a checked call: the records' initialisation and the front stage proper; *run = whether a tail is left to run
+// (n > 0 and a kept row somewhere)
+static int fam_genes_bed_front(rvt_ctx* c, int n, const unsigned char* const* d_rows, int64_t cb, const int* Ms, const int64_t* ids,
+                               uint32_t tests, rvt_gene_result* out, FamGenesFront* F, bool* run) {
+  *run = false;
   if (n == 0) return RVT_OK;
   size_t tot = 0;
   std::vector<size_t> row0(n);
   for (int g = 0; g < n; ++g) {
-    if (Ms[g] < 1 || Ms[g] > RVT_MAX_VARIANTS) return fail(c, RVT_E_TOO_LARGE, "gene %d: M=%d", g, Ms[g]);
     row0[g] = tot;
     tot += (size_t)Ms[g];
   }
-  if (tot > (size_t)INT32_MAX) return fail(c, RVT_E_TOO_LARGE, "%zu rows in one call", tot);
   hipSetDevice(c->device);
-  rc = rvt_sync(c);
+  int rc = rvt_sync(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
-  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld, cb = (N + 3) / 4;
+  const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
   const bool burden = (tests & (RVT_TEST_FAMCMC | RVT_TEST_FAMZEGGINI)) != 0;
   // ---- 1. the site pass over the codes: counts, then flip / keep / no-missing flags of every row ---------------------------------
   Layout W, Lst;  // (sized by the rows of the batch: T <= tot kept rows, at most n genes with one)
@@ -1985,7 +1998,9 @@ int rvt_run_fam_tests_bed_dev(rvt_ctx* c, int n, const unsigned char* const* d_r
                               uint32_t tests, rvt_gene_result* out) {
   FamGenesFront F;
   bool run = false;
-  int rc = fam_genes_bed_front(c, n, d_rows, Ms, ids, tests, out, &F, &run);
+  int64_t cb = 0;
+  int rc = fam_genes_bed_check(c, n, d_rows, Ms, tests, out, &cb);
+  if (!rc) rc = fam_genes_bed_front(c, n, d_rows, cb, Ms, ids, tests, out, &F, &run);
   if (rc || !run) return rc;
   return fam_tests_tail(c, n, tests, F.Mk, F.off, F.kgene, F.T, F.d_bcs, F.d_bpoly, out);
 }
@@ -1996,8 +2011,11 @@ int rvt_run_fam_tests_bed_dev(rvt_ctx* c, int n, const unsigned char* const* d_r
 int rvt_debug_fam_genes_bed_front_timed(rvt_ctx* c, int n, const unsigned char* const* d_rows, const int* Ms, uint32_t tests,
                                         rvt_gene_result* out, double* ms) {
   if (!c || !ms) return fail(c, RVT_E_INVALID, "bad arguments");
+  int64_t cb = 0;
+  int rc = fam_genes_bed_check(c, n, d_rows, Ms, tests, out, &cb);
+  if (rc) return rc;
   hipSetDevice(c->device);
-  int rc = rvt_sync(c);
+  rc = rvt_sync(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
   hipEvent_t ev[2] = {nullptr, nullptr};
@@ -2007,7 +2025,7 @@ int rvt_debug_fam_genes_bed_front_timed(rvt_ctx* c, int n, const unsigned char* 
   if (e == hipSuccess) {
     FamGenesFront F;
     bool run = false;
-    rc = fam_genes_bed_front(c, n, d_rows, Ms, nullptr, tests, out, &F, &run);
+    rc = fam_genes_bed_front(c, n, d_rows, cb, Ms, nullptr, tests, out, &F, &run);
     if (!rc) e = hipEventRecord(ev[1], st);
     if (!rc && e == hipSuccess) e = sync_stream(st);
     float t = 0.0f;
@@ -2023,14 +2041,13 @@ int rvt_debug_fam_genes_bed_front_timed(rvt_ctx* c, int n, const unsigned char* 
 
 namespace {
 // the front stage of the first ncols rows, piece by piece; out (host, N x ncols, optional) takes the rotated columns
-int fam_bed_rotate_all(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int ncols, double* out) {
+int fam_bed_rotate_all(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int64_t cb, int ncols, double* out) {
   const int64_t N = c->fam_nc.N, ld = c->fam_nc.ld;
-  const size_t cb = (size_t)((N + 3) / 4);
   FamBedPiece p;
   int rc = fam_bed_ws(c, st, &p);
   for (int v0 = 0; v0 < ncols && !rc; v0 += RVT_MAX_VARIANTS) {
     const int n = std::min(RVT_MAX_VARIANTS, ncols - v0);
-    rc = fam_bed_front(c, st, d_rows + cb * (size_t)v0, n, p, nullptr);
+    rc = fam_bed_front(c, st, d_rows + (size_t)cb * (size_t)v0, cb, n, p, nullptr);
     if (rc || !out) continue;
     HIP_TRY(c, hipMemcpy2DAsync(out + (size_t)N * v0, sizeof(double) * (size_t)N, c->d_Gt, sizeof(double) * (size_t)ld,
                                 sizeof(double) * (size_t)N, (size_t)n, hipMemcpyDeviceToHost, st));
@@ -2043,18 +2060,20 @@ int fam_bed_rotate_all(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, 
 // Test hook: the first ncols rows through the front stage, the rotated columns N x ncols to the host (cf. rvt_debug_rotate)
 int rvt_debug_rotate_bed(rvt_ctx* c, const unsigned char* d_rows, int ncols, double* out) {
   if (!c || !d_rows || !out || ncols < 1) return fail(c, RVT_E_INVALID, "bad arguments");
-  int rc = fam_bed_check(c, "rvt_debug_rotate_bed");
+  int64_t cb = 0;
+  int rc = fam_bed_check(c, "rvt_debug_rotate_bed", d_rows, ncols, &cb);
   if (rc) return rc;
   hipSetDevice(c->device);
   rc = rvt_sync(c);
   if (rc) return rc;
-  return fam_bed_rotate_all(c, c->stream, d_rows, ncols, out);
+  return fam_bed_rotate_all(c, c->stream, d_rows, cb, ncols, out);
 }
 
 // Measurement hook: the same front stage without the copy to the host, between two HIP events (cf. rvt_debug_rotate_timed)
 int rvt_debug_rotate_bed_timed(rvt_ctx* c, const unsigned char* d_rows, int ncols, double* ms) {
   if (!c || !d_rows || !ms || ncols < 1) return fail(c, RVT_E_INVALID, "bad arguments");
-  int rc = fam_bed_check(c, "rvt_debug_rotate_bed_timed");
+  int64_t cb = 0;
+  int rc = fam_bed_check(c, "rvt_debug_rotate_bed_timed", d_rows, ncols, &cb);
   if (rc) return rc;
   hipSetDevice(c->device);
   rc = rvt_sync(c);
@@ -2065,7 +2084,7 @@ int rvt_debug_rotate_bed_timed(rvt_ctx* c, const unsigned char* d_rows, int ncol
   hipError_t e = hipEventCreate(&ev[1]);
   if (e == hipSuccess) e = hipEventRecord(ev[0], st);
   if (e == hipSuccess) {
-    rc = fam_bed_rotate_all(c, st, d_rows, ncols, nullptr);
+    rc = fam_bed_rotate_all(c, st, d_rows, cb, ncols, nullptr);
     if (!rc) e = hipEventRecord(ev[1], st);
     if (!rc && e == hipSuccess) e = sync_stream(st);
     float t = 0.0f;
@@ -2318,10 +2337,10 @@ int rvt_grammar_block(rvt_ctx* c, const double* dG, int V, int af_kinship, int* 
 namespace {
 constexpr int kGgBedPiece = 8192;  // rows of one launch of the product; af=kinship walks the front stage's RVT_MAX_VARIANTS
 
-// what a call may be refused for, before anything is written
-int gg_bed_check(rvt_ctx* c, int af_kinship, const char* who) {
+// what a call may be refused for, before anything is written; *cb = the pitch of its V rows at d_rows
+int gg_bed_check(rvt_ctx* c, int af_kinship, const char* who, const unsigned char* d_rows, int64_t V, int64_t* cb) {
   if (!c->have_grammar) return fail(c, RVT_E_STATE, "%s: rvt_set_kinship + rvt_fit_grammar_null first", who);
-  if (int rc = bed_rows_check(c, who, (long long)c->gg_N, "GrammarGamma")) return rc;
+  if (int rc = bed_rows_span(c, who, d_rows, V, BedModel::kGrammar, cb)) return rc;
   if (af_kinship && (!c->have_fam || c->fam_nc.N != c->gg_N))
     return fail(c, RVT_E_STATE, "%s: af=kinship needs rvt_fit_fam_null on the same samples (the rotation takes its layout)", who);
   if (c->gg_N > kGgMaxN) return fail(c, RVT_E_TOO_LARGE, "%s: N = %lld (at most %lld)", who, (long long)c->gg_N, (long long)kGgMaxN);
@@ -2377,9 +2396,8 @@ struct GgBedOut {  // host arrays of a call (any may be null), V entries each (c
 };
 
 // The call proper, the state checked: pieces of rows through the product, the finish and, with af=kinship, the front stage.
-int gg_bed_run(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int64_t V, int af_kinship, const GgBedOut& out) {
+int gg_bed_run(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, size_t cb, int64_t V, int af_kinship, const GgBedOut& out) {
   const int64_t N = c->gg_N;
-  const size_t cb = (size_t)((N + 3) / 4);
   const signed char* planes = nullptr;
   int64_t ldp = 0;
   int rc = gg_bed_planes(c, st, &planes, &ldp);
@@ -2448,7 +2466,7 @@ int gg_bed_run(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int64_t 
     herr = hipGetLastError();
     if (herr != hipSuccess) break;
     if (af_kinship) {  // U'g of the piece by the installed form of U, then GetAF's AF_KINSHIP form over it
-      rc = fam_bed_front(c, st, rows, n, fp, nullptr);
+      rc = fam_bed_front(c, st, rows, (int64_t)cb, n, fp, nullptr);
       if (rc) break;
       hipLaunchKernelGGL(grammar_af_kin_kernel, dim3((unsigned)n), dim3(256), 0, st, c->d_Gt.get(), (long long)c->fam_nc.ld,
                          (long long)N, d_wu1, c->gg_afden, d_af);
@@ -2491,14 +2509,15 @@ int gg_bed_run(rvt_ctx* c, hipStream_t st, const unsigned char* d_rows, int64_t 
 int rvt_grammar_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int af_kinship, int* ok, double* af, double* beta,
                         double* beta_var, double* pvalue, long long* counts) {
   if (!c || !d_rows || V < 1 || !ok || !af || !beta || !beta_var || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
-  int rc = gg_bed_check(c, af_kinship, "rvt_grammar_bed_dev");
+  int64_t cb = 0;
+  int rc = gg_bed_check(c, af_kinship, "rvt_grammar_bed_dev", d_rows, V, &cb);
   if (rc) return rc;
   hipSetDevice(c->device);
   rc = rvt_sync(c);
   if (rc) return rc;
   GgBedOut out;
   out.ok = ok, out.af = af, out.beta = beta, out.beta_var = beta_var, out.pvalue = pvalue, out.counts = counts;
-  return gg_bed_run(c, c->stream, d_rows, V, af_kinship, out);
+  return gg_bed_run(c, c->stream, d_rows, (size_t)cb, V, af_kinship, out);
 }
 
 // Test hook: what rvt_grammar_bed_dev multiplies with and what the product returns.  planes (8 N, plane p at planes + p N, may be
@@ -2507,7 +2526,8 @@ int rvt_grammar_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int 
 int rvt_debug_grammar_bed(rvt_ctx* c, const unsigned char* d_rows, int64_t V, signed char* planes, int* exp2, long long* totals,
                           long long* sums) {
   if (!c || !exp2 || !totals || (sums && (!d_rows || V < 1))) return fail(c, RVT_E_INVALID, "bad arguments");
-  int rc = gg_bed_check(c, 0, "rvt_debug_grammar_bed");
+  int64_t cb = 0;  // (without sums no row is read: the state alone)
+  int rc = gg_bed_check(c, 0, "rvt_debug_grammar_bed", sums ? d_rows : nullptr, sums ? V : 0, &cb);
   if (rc) return rc;
   hipSetDevice(c->device);
   rc = rvt_sync(c);
@@ -2522,7 +2542,7 @@ int rvt_debug_grammar_bed(rvt_ctx* c, const unsigned char* d_rows, int64_t V, si
     std::vector<double> v((size_t)V);
     GgBedOut out;
     out.ok = ok.data(), out.beta = out.beta_var = out.pvalue = v.data(), out.sums = sums;
-    rc = gg_bed_run(c, st, d_rows, V, 0, out);
+    rc = gg_bed_run(c, st, d_rows, (size_t)cb, V, 0, out);
     if (rc) return rc;
   }
   if (planes) {
@@ -2537,14 +2557,15 @@ int rvt_debug_grammar_bed(rvt_ctx* c, const unsigned char* d_rows, int64_t V, si
 // Measurement hook: the product kernels of rvt_grammar_bed_dev over the V rows alone, between two HIP events
 int rvt_debug_grammar_bed_timed(rvt_ctx* c, const unsigned char* d_rows, int64_t V, double* ms) {
   if (!c || !d_rows || V < 1 || !ms) return fail(c, RVT_E_INVALID, "bad arguments");
-  int rc = gg_bed_check(c, 0, "rvt_debug_grammar_bed_timed");
+  int64_t cb = 0;
+  int rc = gg_bed_check(c, 0, "rvt_debug_grammar_bed_timed", d_rows, V, &cb);
   if (rc) return rc;
   hipSetDevice(c->device);
   rc = rvt_sync(c);
   if (rc) return rc;
   GgBedOut out;
   out.product_ms = ms;
-  return gg_bed_run(c, c->stream, d_rows, V, 0, out);
+  return gg_bed_run(c, c->stream, d_rows, (size_t)cb, V, 0, out);
 }
 
 }  // extern "C"

@@ -355,7 +355,7 @@ static size_t gene_bytes(rvt_group* g, int kind, int M) {
   int64_t N = 0;
   int d = 0;
   if (M < 1 || M > RVT_MAX_VARIANTS || rvt_null_dims(g->member[0], &N, &d) != RVT_OK) return 0;
-  return kind <= 1 ? sizeof(double) * (size_t)N * M : (kind == 2 ? (size_t)N * M : (size_t)((N + 3) / 4) * M);
+  return kind <= 1 ? sizeof(double) * (size_t)N * M : (kind == 2 ? (size_t)N * M : (size_t)rvt::bed_pitch(N) * M);
 }
 
 int rvt_group_submit_gene(rvt_group* g, int64_t gene_id, int M, const double* G, const double* af, uint32_t tests,

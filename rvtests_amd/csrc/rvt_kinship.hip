@@ -43,9 +43,11 @@ int rvt_kinship_from_bed(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int
     return fail(c, RVT_E_INVALID, "rvt_kinship_from_bed: max_missing %g outside [0, 1]", max_missing);
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   if (V > (int64_t)1 << 30) return fail(c, RVT_E_TOO_LARGE, "rvt_kinship_from_bed: %lld sites (the integer sums hold 2^30)", (long long)V);
+  int64_t pitch = 0;
+  if (int rc = bed_rows_span(c, "rvt_kinship_from_bed", d_rows, V, BedModel::kNull, &pitch)) return rc;
   hipSetDevice(c->device);
   const bool bn = method == RVT_KINSHIP_BN;
-  const long long N = c->nc.N, cb = (N + 3) / 4, ld = N;
+  const long long N = c->nc.N, cb = pitch, ld = N;
   const long long nblk = (N + kKinTile - 1) / kKinTile, tiles = nblk * (nblk + 1) / 2;
   // (RVT_KINSHIP_CHUNK, 1 .. 32 768 sites: tests lower it so that small matrices take the path of several chunks)
   const char* env_chunk = getenv("RVT_KINSHIP_CHUNK");

@@ -1193,12 +1193,15 @@ int rvt_cov_band_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int H, int W, 
   if (!c->hc_enabled)
     return fail(c, RVT_E_STATE, "rvt_cov_band_bed_dev: the packed rows need the hard-call kernels, which are switched off (RVT_HARDCALL=0)");
   if ((long long)W > (long long)H + halo) W = H + halo;  // (markers behind the last head's window are never read)
+  int64_t cb = 0;
+  int rc = bed_rows_span(c, "rvt_cov_band_bed_dev", d_rows, W, BedModel::kNull, &cb);
+  if (rc) return rc;
   hipSetDevice(c->device);
-  int rc = rvt_sync(c);
+  rc = rvt_sync(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
   const NullConsts& nc = c->nc;
-  const int64_t N = nc.N, ld = nc.ld, cb = (N + 3) / 4;
+  const int64_t N = nc.N, ld = nc.ld;
   const int d = nc.d;
   CovConsts cc;
   std::vector<double> zzv;
@@ -1846,12 +1849,34 @@ int bed_counts_host(rvt_ctx* c, hipStream_t st, const unsigned long long* d_cnt,
   return RVT_OK;
 }
 
-// Resident rows have the pitch ceil(N / 4) of the N rvt_bed_alloc saw, which is the ordinary null model's when one is set: a
-// null model of another kind (`other`) with another N beside it means rows of another pitch.
-int bed_rows_check(rvt_ctx* c, const char* who, long long N, const char* other) {
+// (rvt_engine_int.h has the contract.)  First the refusals by the models present, which hold for rows the engine does not know
+// as well: rvt_bed_alloc sizes a matrix for the ordinary null model's N when one is set, so an ordinary null model of another N
+// beside the consuming one means rows of another pitch; and the multiple-trait call refuses a family null model of another N in
+// a context without an ordinary one.  Then the record of the matrix the rows lie in.
+int bed_rows_span(rvt_ctx* c, const char* who, const unsigned char* d_rows, int64_t V, BedModel model, int64_t* pitch) {
+  static const char* const kName[] = {"ordinary", "family", "multiple-trait", "GrammarGamma"};
+  const char* name = kName[(int)model];
+  const long long N = model == BedModel::kNull ? c->nc.N : model == BedModel::kFam ? c->fam_nc.N : model == BedModel::kMt ? c->mt_N : c->gg_N;
   if (c->have_null && c->nc.N != N)
     return fail(c, RVT_E_STATE, "%s: the null model has N = %lld, the %s null model N = %lld (the resident rows have the former's pitch)",
-                who, (long long)c->nc.N, other, N);
+                who, (long long)c->nc.N, name, N);
+  if (model == BedModel::kMt && !c->have_null && c->have_fam && c->fam_nc.N != N)
+    return fail(c, RVT_E_STATE, "%s: the multiple-trait null and the context's null model differ in N", who);
+  *pitch = bed_pitch(N);
+  auto it = c->bed_mats.upper_bound(d_rows);  // the matrix with the last base at or below d_rows, if the rows lie inside it
+  if (it == c->bed_mats.begin()) return RVT_OK;
+  const rvt_ctx::BedMatrix& m = (--it)->second;
+  const long long first = bed_span((uint64_t)(uintptr_t)it->first, m.n_variants, m.pitch, (uint64_t)(uintptr_t)d_rows, V);
+  if (first == kBedSpanOutside) return RVT_OK;
+  if (m.N != N)
+    return fail(c, RVT_E_STATE, "%s: the resident matrix was sized for N = %lld, the %s null model has N = %lld", who, (long long)m.N,
+                name, N);
+  if (first == kBedSpanOffRow)
+    return fail(c, RVT_E_INVALID, "%s: the address is not on a row boundary of its resident matrix (rows of %lld bytes)", who,
+                (long long)m.pitch);
+  if (first == kBedSpanLeaves)
+    return fail(c, RVT_E_INVALID, "%s: %lld rows leave the resident matrix (%lld rows)", who, (long long)V, (long long)m.n_variants);
+  *pitch = m.pitch;
   return RVT_OK;
 }
 
@@ -1861,7 +1886,9 @@ int rvt_bed_recode_block(rvt_ctx* c, const unsigned char* d_rows, int V, int cod
     return fail(c, RVT_E_INVALID, "coding %d: 1 = dominant, 2 = recessive", coding);
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   if (int rc = check_columns(c, dG, col0, V)) return rc;
-  const long long N = c->nc.N, ld = c->null_ld, cb = (N + 3) / 4;
+  int64_t cb = 0;
+  if (int rc = bed_rows_span(c, "rvt_bed_recode_block", d_rows, V, BedModel::kNull, &cb)) return rc;
+  const long long N = c->nc.N, ld = c->null_ld;
   return recode_columns(
       c, dG, col0, V, 4, counts,
       [&](int k0, int nk, unsigned long long* d_cnt, hipStream_t st) {

@@ -414,12 +414,12 @@ int rvt_mt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, dou
                          long long* counts) {
   if (!c || !d_rows || V < 1 || !ustat || !vstat || !pvalue) return fail(c, RVT_E_INVALID, "bad arguments");
   if (!c->have_mt) return fail(c, RVT_E_STATE, "no multiple-trait null model (rvt_mt_fit_null)");
-  const int64_t N = c->mt_N, pitch = (N + 3) / 4;
-  if (int rc = bed_rows_check(c, "rvt_mt_score_bed_dev", (long long)N, "multiple-trait")) return rc;
-  if (!c->have_null && c->have_fam && c->fam_nc.N != N)  // (rvt_bed_alloc then saw the family null model's N)
-    return fail(c, RVT_E_STATE, "the multiple-trait null and the context's null model differ in N");
+  const int64_t N = c->mt_N;
+  int64_t pitch = 0;
+  int rc = bed_rows_span(c, "rvt_mt_score_bed_dev", d_rows, V, BedModel::kMt, &pitch);
+  if (rc) return rc;
   hipSetDevice(c->device);
-  int rc = rvt_sync(c);
+  rc = rvt_sync(c);
   if (rc) return rc;
   hipStream_t st = c->stream;
   const int64_t ldk = c->mt_ldk;

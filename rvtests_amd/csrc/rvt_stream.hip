@@ -477,6 +477,7 @@ struct Submit {  // the arguments of one submission
   double* af_out;    // the others: where the caller waits for the device's (may be NULL)
   uint32_t tests;
   const rvt_params* prm;
+  size_t cb;  // kBed, kBedDev: bytes from one row of G to the next
 };
 // expanded to an fp64 block, or kept as 2-bit rows: as they come, made of int8 / of fp64 by the staging threads on the way, or
 // copied from a matrix resident on the device
@@ -619,7 +620,7 @@ HcpHeader* packed_header(const BlockLease& blk) { return reinterpret_cast<HcpHea
 // the io stream.  Nothing is expanded.
 int fill_packed_host(const Submit& s, Route route, const BlockLease& blk, const AfReturn& ar) {
   rvt_ctx* c = s.c;
-  const size_t N = (size_t)c->nc.N, cb = (N + 3) / 4, pk_pitch = hcp_row_pitch(c->nc.N);
+  const size_t N = (size_t)c->nc.N, cb = s.cb, pk_pitch = hcp_row_pitch(c->nc.N);
   unsigned char* rows = packed_rows(blk);
   const int ek = next_pack_slot(c);
   if (blk.fresh()) {
@@ -652,7 +653,7 @@ int fill_packed_host(const Submit& s, Route route, const BlockLease& blk, const 
 int fill_packed_resident(const Submit& s, const BlockLease& blk, const AfReturn& ar) {
   rvt_ctx* c = s.c;
   hipStream_t st = c->io_stream;
-  const long long N = c->nc.N, cb = (N + 3) / 4, pk_pitch = (long long)hcp_row_pitch(c->nc.N);
+  const long long N = c->nc.N, cb = (long long)s.cb, pk_pitch = (long long)hcp_row_pitch(c->nc.N);
   if (blk.fresh()) {
     const hipError_t e = hipMemsetAsync(blk.get(), 0, blk.bytes(), st);
     if (e != hipSuccess) return consol_failed(c, e);
@@ -726,7 +727,7 @@ int fill_expanded_hardcalls(const Submit& s, const BlockLease& blk, const AfRetu
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
   const bool two_bit = s.in == GeneInput::kBed || s.in == GeneInput::kBedDev;
-  const size_t col_bytes = two_bit ? (size_t)((N + 3) / 4) : (size_t)N, bytes8 = col_bytes * s.M;
+  const size_t col_bytes = two_bit ? s.cb : (size_t)N, bytes8 = col_bytes * s.M;
   const void* d_packed = nullptr;  // where the packed genotypes of this gene are on the device
   int pk = -1;
   hipError_t e;
@@ -853,9 +854,12 @@ int submit_common(rvt_ctx* c, int64_t gene_id, int M, const void* G, GeneInput i
   if (!c->have_null) return fail(c, RVT_E_STATE, "no null model set");
   if (tests & RVT_TEST_FAMSKAT) return fail(c, RVT_E_INVALID, "FamSKAT runs through rvt_run_fam_blocks");
   if (M > RVT_MAX_VARIANTS) return fail(c, RVT_E_TOO_LARGE, "gene of %d variants exceeds RVT_MAX_VARIANTS", M);
+  int64_t cb = bed_pitch(c->nc.N);
+  if (in == GeneInput::kBedDev)
+    if (int rc = bed_rows_span(c, "rvt_submit_gene_bed_dev", static_cast<const unsigned char*>(G), M, BedModel::kNull, &cb)) return rc;
   hipSetDevice(c->device);
   TraceScope ts_all(c, &c->tr_block);  // (the whole call; "block" in the trace line = total per gene)
-  const Submit s{c, gene_id, M, G, in, af, af_out, tests, prm};
+  const Submit s{c, gene_id, M, G, in, af, af_out, tests, prm, (size_t)cb};
   int rc = submit_routed(s, true);
   if (rc == kRetryExpanded) rc = submit_routed(s, false);  // (the packed block is back in its pool)
   return rc;
@@ -887,7 +891,7 @@ __global__ __launch_bounds__(256) void bed_count_copy_rows_kernel(const BedRowRe
   const long long i0 = (long long)blockIdx.x * kConsolChunk;
   const long long i1 = (i0 + kConsolChunk < N) ? i0 + kConsolChunk : N;
   int n[4] = {0, 0, 0, 0};  // calls of 0 / 1 / 2 / missing (the first is not used)
-  if ((((N + 3) / 4) & 3) == 0 && (((unsigned long long)rr.src | (unsigned long long)rr.dst) & 3ull) == 0ull) {
+  if ((bed_pitch(N) & 3) == 0 && (((unsigned long long)rr.src | (unsigned long long)rr.dst) & 3ull) == 0ull) {
     // rows of whole dwords that start on a 4-byte boundary (ceil(N/4) a multiple of 4, e.g. N = 500 000): a dword = 16 samples per
     // thread and trip instead of a byte — the pass moved 1.5 TB/s byte by byte.  Nothing outside the row is read; the samples of
     // the last dword beyond N are masked.
@@ -1016,7 +1020,7 @@ int bed_rows_consolidate(rvt_ctx* c, hipStream_t st, const char* what, const std
 }
 
 // returns -1 when the call does not apply (a gene that has to be expanded): the caller submits gene by gene
-int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, const void* const* data, uint32_t tests,
+int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, const void* const* data, size_t cb, uint32_t tests,
                          const rvt_params* prm) {
   if (n < 1 || n > rvt_ctx::kAfSlots / 2) return -1;
   if (!c->have_null || (tests & RVT_TEST_FAMSKAT)) return -1;
@@ -1029,7 +1033,7 @@ int submit_bed_dev_batch(rvt_ctx* c, int n, const int64_t* ids, const int* Ms, c
   TraceScope ts_all(c, &c->tr_block);
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
-  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
+  const size_t pk_pitch = hcp_row_pitch(N);
   HIP_TRY(c, c->h_af_ring.grow(kAfRingBytes, kAfRingBytes, nullptr, false, hipHostMallocMapped));
   if (c->af_unresolved + n > rvt_ctx::kAfSlots) {
     int rc = resolve_af(c);
@@ -1198,9 +1202,12 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
   constexpr int kSlice = 32;
   static const int kChunk = getenv("RVT_SCORE_BED_CHUNK") ? std::max(16, std::min(2048, atoi(getenv("RVT_SCORE_BED_CHUNK")))) : 256;
   if (const char* why = score_bed_refusal(c)) return fail(c, RVT_E_STATE, "rvt_score_bed_dev: %s", why);
+  int64_t cb = 0;
+  int rc = bed_rows_span(c, "rvt_score_bed_dev", d_rows, V, BedModel::kNull, &cb);
+  if (rc) return rc;
   const bool binary = c->nc.binary != 0;
   hipSetDevice(c->device);
-  int rc = rvt_sync(c);
+  rc = rvt_sync(c);
   if (rc) return rc;
   if (binary) {
     // the planes of [v X | res | v], built at the first call under this null model.  There is no fp64 product of packed rows
@@ -1213,7 +1220,7 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
   }
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
-  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
+  const size_t pk_pitch = hcp_row_pitch(N);
   // the slices' blocks: kChunk of them, reused chunk after chunk (the batch is synchronous); back in the pool on every return
   std::vector<BlockLease> leases;
   std::vector<double*> blk;
@@ -1250,9 +1257,9 @@ int rvt_score_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int64_t V, int* o
     for (int g = 0; g < n; ++g) {
       const int M = std::min(kSlice, cols - g * kSlice);
       unsigned char* dst = reinterpret_cast<unsigned char*>(blk[(size_t)g]) + kHcpHeaderBytes;
-      const unsigned char* src = d_rows + cb * (size_t)(v0 + (int64_t)g * kSlice);
+      const unsigned char* src = d_rows + (size_t)cb * (size_t)(v0 + (int64_t)g * kSlice);
       const int r0 = (int)rows.size();
-      for (int j = 0; j < M; ++j) rows.push_back(BedRowRef{src + cb * (size_t)j, dst + pk_pitch * (size_t)j});
+      for (int j = 0; j < M; ++j) rows.push_back(BedRowRef{src + (size_t)cb * (size_t)j, dst + pk_pitch * (size_t)j});
       // (a shorter last slice: the rows behind it in the block keep an earlier slice's codes — beyond M, never read)
       genes.push_back(BedGeneRef{r0, M, reinterpret_cast<HcpHeader*>(blk[(size_t)g]), nullptr, nullptr});  // (sinks: the work space's)
       ptr.push_back(blk[(size_t)g]);
@@ -1297,19 +1304,22 @@ int rvt_debug_suffstat_bed_dev(rvt_ctx* c, const unsigned char* d_rows, int M, d
   if (!packed_eligible(c, M, RVT_TEST_SKAT, nullptr))
     return fail(c, RVT_E_STATE, "rvt_debug_suffstat_bed_dev: this gene is not kept as 2-bit rows (a binary trait, more than 13 "
                 "covariates, more than 96 variants, or the packed-row kernel switched off): it is expanded to an fp64 block");
+  int64_t cb = 0;
+  int rc = bed_rows_span(c, "rvt_debug_suffstat_bed_dev", d_rows, M, BedModel::kNull, &cb);
+  if (rc) return rc;
   hipSetDevice(c->device);
-  int rc = rvt_sync(c);
+  rc = rvt_sync(c);
   if (rc) return rc;
   hipStream_t st = c->io_stream;
   const int64_t N = c->nc.N;
-  const size_t cb = (size_t)((N + 3) / 4), pk_pitch = hcp_row_pitch(N);
+  const size_t pk_pitch = hcp_row_pitch(N);
   BlockLease blk = lease_packed(c, M);  // (back in the pool on every return: the batch below is finished by then)
   if (!blk) return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a packed gene", packed_block_bytes(N, M));
   if (blk.fresh() && hipMemsetAsync(blk.get(), 0, blk.bytes(), st) != hipSuccess)
     return fail(c, RVT_E_HIP, "clearing a packed gene's block failed");
   std::vector<BedRowRef> rows;
   std::vector<BedGeneRef> genes;
-  for (int j = 0; j < M; ++j) rows.push_back(BedRowRef{d_rows + cb * (size_t)j, packed_rows(blk) + pk_pitch * (size_t)j});
+  for (int j = 0; j < M; ++j) rows.push_back(BedRowRef{d_rows + (size_t)cb * (size_t)j, packed_rows(blk) + pk_pitch * (size_t)j});
   genes.push_back(BedGeneRef{0, M, packed_header(blk), nullptr, nullptr});  // (sinks: the work space's)
   long long* d_cnt = nullptr;
   rc = bed_rows_consolidate(c, st, "resident .bed gene (debug)", rows, genes, RVT_MAX_VARIANTS, 1, &d_cnt);
@@ -1344,26 +1354,36 @@ int rvt_submit_gene_bed(rvt_ctx* c, int64_t gene_id, int M, const unsigned char*
 // ---- a .bed matrix resident in HBM ---------------------------------------------------------------------------------------
 // 500 000 samples x 2 000 000 variants of PLINK 2-bit rows are 250 GB: a whole exome-scale cohort fits the 288 GB of one
 // MI355X.  rvt_bed_alloc / rvt_bed_upload put rows there once (file layout: ceil(N/4) bytes per variant, no padding);
-// rvt_submit_gene_bed_dev then names a gene by the device address of its first row.
+// rvt_submit_gene_bed_dev then names a gene by the device address of its first row.  The engine keeps a record of every matrix
+// (rvt_ctx::bed_mats): what bed_rows_span checks the rows of a call against.
 int rvt_bed_alloc(rvt_ctx* c, int64_t n_variants, unsigned char** d_bed) {
   if (!c || !d_bed || n_variants < 1) return fail(c, RVT_E_INVALID, "bad .bed allocation");
   // (a context whose only model is the multiple-trait one, rvt_mt_fit_null: its N gives the pitch, for rvt_mt_score_bed_dev)
   if (!c->have_null && !c->have_mt) return fail(c, RVT_E_STATE, "no null model set");
   hipSetDevice(c->device);
-  const size_t cb = (size_t)(((c->have_null ? c->nc.N : c->mt_N) + 3) / 4);
+  const int64_t N = c->have_null ? c->nc.N : c->mt_N, cb = bed_pitch(N);
   *d_bed = nullptr;
-  if (hipMalloc((void**)d_bed, cb * (size_t)n_variants + 16) != hipSuccess) {
+  if (hipMalloc((void**)d_bed, (size_t)cb * (size_t)n_variants + kBedSlackBytes) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a resident .bed matrix", cb * (size_t)n_variants);
+    return fail(c, RVT_E_HIP, "hipMalloc(%zu bytes) failed for a resident .bed matrix", (size_t)cb * (size_t)n_variants);
   }
+  c->bed_mats[*d_bed] = rvt_ctx::BedMatrix{n_variants, N, cb};
   return RVT_OK;
 }
 int rvt_bed_upload(rvt_ctx* c, unsigned char* d_bed, int64_t first_variant, int64_t n_variants, const unsigned char* rows) {
   if (!c || !d_bed || !rows || first_variant < 0 || n_variants < 0) return fail(c, RVT_E_INVALID, "bad .bed upload");
   if (!c->have_null && !c->have_mt) return fail(c, RVT_E_STATE, "no null model set");
+  size_t cb = (size_t)bed_pitch(c->have_null ? c->nc.N : c->mt_N);  // (a matrix the engine does not know: as ever)
+  const auto it = c->bed_mats.find(d_bed);
+  if (it != c->bed_mats.end()) {
+    const rvt_ctx::BedMatrix& m = it->second;
+    if (first_variant > m.n_variants || n_variants > m.n_variants - first_variant)
+      return fail(c, RVT_E_INVALID, "rows [%lld, +%lld) leave the resident matrix (%lld rows)", (long long)first_variant,
+                  (long long)n_variants, (long long)m.n_variants);
+    cb = (size_t)m.pitch;
+  }
   if (n_variants == 0) return RVT_OK;
   hipSetDevice(c->device);
-  const size_t cb = (size_t)(((c->have_null ? c->nc.N : c->mt_N) + 3) / 4);
   int rc = staged_h2d(c, d_bed + cb * (size_t)first_variant, rows, cb * (size_t)n_variants);
   if (rc) return rc;
   HIP_TRY(c, sync_stream(c->h2d_stream));  // (the caller may reuse `rows`; genes submitted next read the device copy)
@@ -1372,8 +1392,11 @@ int rvt_bed_upload(rvt_ctx* c, unsigned char* d_bed, int64_t first_variant, int6
 int rvt_bed_free(rvt_ctx* c, unsigned char* d_bed) {
   if (!c) return RVT_E_INVALID;
   if (!d_bed) return RVT_OK;
+  const auto it = c->bed_mats.find(d_bed);
+  if (it == c->bed_mats.end()) return fail(c, RVT_E_INVALID, "rvt_bed_free: not the address of a matrix of this context's rvt_bed_alloc");
   hipSetDevice(c->device);
   int rc = rvt_sync(c);  // (queued genes may still read it)
+  c->bed_mats.erase(it);
   hipFree(d_bed);
   return rc;
 }
@@ -1404,12 +1427,16 @@ int rvt_submit_genes(rvt_ctx* c, int kind, int n, const int64_t* gene_ids, const
   if (in == GeneInput::kBedDev) {
     // resident rows: whole calls at once where every gene may stay packed, groups of up to 256 genes per batch of the pipeline
     // (nothing waits for a link here: the larger the batch, the fuller the chip)
+    if (n > 0 && !c->have_null) return fail(c, RVT_E_STATE, "no null model set");
+    int64_t cb = 0;
+    for (int g = 0; g < n; ++g)  // every gene's rows before the first is queued: a refused call queues nothing
+      if (int rc = bed_rows_span(c, "rvt_submit_genes", static_cast<const unsigned char*>(data[g]), M[g], BedModel::kNull, &cb)) return rc;
     const int group0 = c->submit_group;
     c->submit_group = std::max(group0, 256);
     int rc = RVT_OK;
     for (int g0 = 0; g0 < n && !rc; g0 += rvt_ctx::kAfSlots / 2) {
       const int ng = std::min(n - g0, rvt_ctx::kAfSlots / 2);
-      rc = submit_bed_dev_batch(c, ng, gene_ids + g0, M + g0, data + g0, tests, prm);
+      rc = submit_bed_dev_batch(c, ng, gene_ids + g0, M + g0, data + g0, (size_t)cb, tests, prm);
       if (rc == -1) {
         rc = RVT_OK;
         for (int g = g0; g < g0 + ng && !rc; ++g)

@@ -20,12 +20,13 @@
 // Bound by the vector and matrix pipes, not by memory (≈6 MB per gene).
 #pragma once
 #include "suffstat_hc.hip.h"
+#include "rvt_bed_codes.h"
 
 namespace rvt {
 
 constexpr int kHcpHeaderBytes = 1024;  // in front of the packed rows
 // bytes from one packed row of N samples to the next: four samples a byte, rounded up to 16 bytes
-constexpr size_t hcp_row_pitch(long long N) { return ((size_t)((N + 3) / 4) + 15) / 16 * 16; }
+constexpr size_t hcp_row_pitch(long long N) { return ((size_t)bed_pitch(N) + 15) / 16 * 16; }
 struct HcpHeader {                     // written by hcp_header_kernel (fam_kernels.hip.h) after the count pass
   double mu[96];                       // imputed value of column j (0 when the column has no missing call)
   unsigned short flip[8], poly[8], cm[8];  // per 16-column block: sum > N; min != max; the imputed value counts

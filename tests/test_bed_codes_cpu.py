@@ -1,8 +1,9 @@
 """What every reader of resident .bed rows shares (rvtests_amd/csrc/rvt_bed_codes.h through hc_bed_*) against a few lines of numpy:
 the value of a code, the site pass on a row's four counts, the live masks, the population counts, the spread of a code byte into
-byte lanes and the loaders of 4 and 16 bytes from any byte address; and the loaders once more as a stand-alone program under
-the address and undefined-behaviour sanitizers (tools/bed_codes_check.cpp), the proof that they touch no byte outside
-[base, end)."""
+byte lanes and the loaders of 4 and 16 bytes from any byte address; where V rows at an address lie in a matrix of known extent
+(bed_span, the arithmetic under every range check of resident rows) against Python integers; and the loaders and bed_span once
+more as a stand-alone program under the address and undefined-behaviour sanitizers (tools/bed_codes_check.cpp), the proof that
+the loaders touch no byte outside [base, end) and that the row arithmetic overflows nowhere."""
 import ctypes as C
 import os
 import shutil
@@ -137,10 +138,60 @@ def test_loaders_at_every_alignment_and_distance_from_both_ends():
                 assert list(w4) == want, (align, db, de)
 
 
+OUTSIDE, OFF_ROW, LEAVES = -1, -2, -3
+
+
+def span(base, nv, pitch, at, V):
+    """bed_span in Python integers"""
+    off = at - base
+    if off < 0 or off >= nv * pitch:
+        return OUTSIDE
+    if off % pitch:
+        return OFF_ROW
+    return LEAVES if off // pitch + V > nv else off // pitch
+
+
+@pytest.mark.parametrize("pitch", [1, 129, 125000])
+@pytest.mark.parametrize("nv", [1, 2, 4099])
+def test_span_of_rows_in_a_matrix(pitch, nv):
+    """Where V rows at an address lie in a matrix of nv rows: every first row, V from 1 to one past the end, addresses around
+    both ends, off the row boundaries and in the slack, bases near 2^47, and V = 2^30, 2^62 (no overflow: "leave the matrix")."""
+    L = lib()
+    L.hc_bed_span.restype = C.c_longlong
+    L.hc_bed_span.argtypes = [C.c_ulonglong, C.c_longlong, C.c_longlong, C.c_ulonglong, C.c_longlong]
+    L.hc_bed_pitch.restype = C.c_longlong
+    L.hc_bed_pitch.argtypes = [C.c_longlong]
+    assert [L.hc_bed_pitch(n) for n in (1, 4, 5, 515, 516, 517, 500000)] == [1, 1, 2, 129, 129, 130, 125000]
+    slack = L.hc_bed_slack()
+    assert slack == 16
+
+    def same(base, at, V):
+        got, want = L.hc_bed_span(base, nv, pitch, at, V), span(base, nv, pitch, at, V)
+        assert got == want, (base, at - base, V, got, want)
+        return got
+
+    for base in (1 << 12, (1 << 47) - 4096, (1 << 47) - 1, (1 << 47) + 3):
+        end = base + nv * pitch
+        for first in range(nv):                                    # every first row
+            at = base + first * pitch
+            left = nv - first
+            assert same(base, at, left) == first and same(base, at, left + 1) == LEAVES
+            assert same(base, at, 1 << 30) == (first if left >= 1 << 30 else LEAVES)
+            assert same(base, at, 1 << 62) == LEAVES and same(base, at, (1 << 63) - 1) == LEAVES
+            if pitch > 1:
+                assert same(base, at + 1, 1) == OFF_ROW and same(base, at + pitch - 1, 1) == OFF_ROW
+        for first in sorted({0, nv // 2, nv - 1}):                 # V from 1 to one past the end
+            for V in (range(1, nv - first + 2) if nv < 100 or first else range(1, nv + 2)):
+                assert same(base, base + first * pitch, V) == (first if first + V <= nv else LEAVES)
+        for at in (base - 1, base - pitch, end, end + 1, end + slack - 1, end + slack, end + pitch):
+            for V in (1, nv, 1 << 62):
+                assert same(base, at, V) == OUTSIDE
+
+
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="sanitizer runs belong on machines without a GPU")
 def test_the_loaders_touch_no_byte_outside_the_buffer(tmp_path):
     """tools/bed_codes_check.cpp under -fsanitize=address,undefined: heap buffers of exactly end - base bytes, every length
-    1 .. 40, every offset."""
+    1 .. 40, every offset; and bed_span over a few hundred cases against 128-bit arithmetic."""
     gxx = shutil.which("g++")
     assert gxx
     exe = str(tmp_path / "bed_codes_check")
